@@ -21,6 +21,14 @@ The JSON line also carries
   cpu_baseline -- the oracle (CPU restatement of the reference, reference-
                   faithful op sequence, reference gradient semantics) timed on
                   this box's host cores on a bounded sample, rank 0, N = 1 only.
+
+--dump-outputs DIR: after all timed legs, rank 0 builds the timed workload afresh (data, initial parameters and
+optimizer state are seeded: the same arguments give the same inputs, bit for bit), runs one step of the timed path on
+it, untimed, and writes what that step computed as DIR/<name>.npy (float32, or float64 for the losses and counters):
+see last_step_outputs and dump_outputs.  Not the last timed step itself: the kernels' atomic sums round in an order that
+varies from run to run, and training amplifies that from step to step (Adam scales every gradient to about lr), so the
+state the timed steps end in differs between two runs by far more than rounding; one step from the seeded state does
+not.
 """
 import argparse
 import json
@@ -62,7 +70,13 @@ def parse():
     ap.add_argument("--storage", default="fp32", choices=["fp32", "bf16", "bf16+grads"],
                     help="activation storage of the timed step (the headline line is fp32; the default run adds a "
                          "bf16-storage line item beside it; --storage bf16 --profile-only is for the rocprofv3 passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed legs, run one untimed step of the timed path from the seeded inputs and write "
+                         "what it computed (loss, logits, fingerprints, gradients, updated parameters) as "
+                         "DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.profile_only:
         args.small_batch, args.fit_pipeline, args.no_cpu_baseline = 0, 0, True
     return args
@@ -171,6 +185,7 @@ def make_workload(args, rank, device, batch, storage="fp32", widths=(64, 64), de
     labels = torch.as_tensor(to_one_hot(y.flatten(), 2).reshape(-1, args.tasks, 2).astype(np.float32),
                              device=device)
     weights = torch.as_tensor(w.astype(np.float32), device=device)
+    torch.manual_seed(1000 + rank)  # the initial parameters, like the data: the same from run to run
     model = dc.models.torch_models.GraphConvModel(args.tasks, number_input_features=[75] + list(widths[:-1]),
                                                   graph_conv_layers=list(widths), dense_layer_size=dense,
                                                   batch_size=batch, mode="classification",
@@ -184,6 +199,52 @@ def run_steps(model, dbatch, labels, weights, n):
         for _ in range(n):
             yield (dbatch, [labels], [weights])
     return model.fit_generator(gen(), checkpoint_interval=0)
+
+
+DUMP_BUDGET_BYTES = 63 * 10**6  # --dump-outputs: every file of the dump together (64 MB less room for file system blocks)
+
+
+def last_step_outputs(model, mean_loss):
+    """What the last step of ``run_steps`` computed, as host arrays: its batch loss, the logits and graph fingerprints
+    of its forward (one row per molecule of the batch), the gradient of every trained parameter, and every parameter
+    and BatchNorm statistic after its Adam update; beside them ``mean_loss``, the value fit_generator returned."""
+    native = model.model.__dict__.get("_native")  # the fused driver the step ran on (GraphConvModel._train_step)
+    if native is None or getattr(native, "_last", None) is None:
+        raise RuntimeError("--dump-outputs: the timed steps did not run on the native whole-model step")
+    _io, logits, _probs, fp, loss, _x, _graph = native._last
+    out = {"loss": loss, "logits": logits, "fingerprint": fp}
+    for name, p in model.model.named_parameters():
+        if p.grad is not None:
+            out["grad." + name] = p.grad
+    for name, t in model.model.state_dict().items():
+        out["param." + name] = t
+    out = {k: v.detach().to("cpu", torch.float32 if v.dtype == torch.float32 else torch.float64).numpy()
+           for k, v in out.items()}
+    out["mean_loss"] = np.array(mean_loss, dtype=np.float64)
+    return out
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BUDGET_BYTES):
+    """Write ``arrays`` as out_dir/<name>.npy, all files together within ``budget`` bytes.  The smallest arrays are
+    written whole; an array larger than its even share of what is left keeps a fixed seeded sample of its rows
+    (sorted), whose indices go beside it as <name>.rows.npy.  Same shapes, same sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+    left = budget
+    for i, name in enumerate(names):
+        a = arrays[name]
+        share = left // (len(names) - i) - 256  # (two .npy headers of at most 128 bytes)
+        if a.nbytes > share:
+            row_bytes = a.nbytes // a.shape[0] + 8  # (+ its float64 index)
+            k = max(1, share // row_bytes)
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], k, replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + ".rows.npy"), rows.astype(np.float64))
+            left -= os.path.getsize(os.path.join(out_dir, name + ".rows.npy"))
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= os.path.getsize(os.path.join(out_dir, name + ".npy"))
+    if left < 0:
+        raise RuntimeError("--dump-outputs: %d bytes over the budget of %d" % (-left, budget))
 
 
 def usable_cores() -> int:
@@ -799,6 +860,12 @@ def main():
                                                        grad_mode=args.grad_mode)
     elif rank == 0:
         out["cpu_baseline"] = None
+    if rank == 0 and args.dump_outputs:
+        # one step of the timed path from the seeded inputs (module docstring: why not the last timed step)
+        deepchem_amd.set_gemm_mode(args.gemm_mode)
+        dm, db, dl, dw = make_workload(args, rank, device, args.batch, args.storage)
+        dump_outputs(last_step_outputs(dm, run_steps(dm, db, dl, dw, 1)), args.dump_outputs)
+        del dm, db, dl, dw
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
