@@ -1,6 +1,6 @@
 """bench.py -- molecules/s of the GraphConvModel training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 N > 1: either launched by ``python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N``
 (RANK / LOCAL_RANK / WORLD_SIZE from the environment), or -- when WORLD_SIZE is not set -- this process
@@ -13,14 +13,18 @@ synthetic molecules that is already resident in HBM when the timed region
 starts.  ``value`` = molecules processed by all ranks / wall time of K steps
 (max over ranks, barrier + synchronize on both sides).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, dumps (--dump-outputs) and prints the JSON line, which also carries
   roofline     -- the GraphConv gather-sum kernel: algorithmic bytes
                   (E*(4F+4) + N*4F per forward launch) / its
                   average duration measured with HIP events on the launch
-                  stream during the timed steps, against HBM peak 8 TB/s;
+                  stream during the timed steps, against HBM peak 8 TB/s.
+--full runs everything else after the timed steps and adds it to the line: the per-kernel breakdown pass
+(kernel_ms_per_step, roofline_by_kernel), the task head alone (head_gemm), the bf16-storage items, the small-batch,
+fit(), PCBA-shape, MolNet-width, exact-GEMM and real-Tox21 legs (config), and
   cpu_baseline -- the oracle (CPU restatement of the reference, reference-
                   faithful op sequence, reference gradient semantics) timed on
-                  this box's host cores on a bounded sample, rank 0, N = 1 only.
+                  this box's host cores on a bounded sample, rank 0, N = 1 only
+                  (null in a plain run).
 
 --dump-outputs DIR: after all timed legs, rank 0 builds the timed workload afresh (data, initial parameters and
 optimizer state are seeded: the same arguments give the same inputs, bit for bit), runs one step of the timed path on
@@ -59,17 +63,22 @@ def parse():
                     help="arithmetic of the matrix products (deepchem_amd.set_gemm_mode)")
     ap.add_argument("--tasks", type=int, default=12)
     ap.add_argument("--grad-mode", default="full", choices=["full", "reference"])
-    ap.add_argument("--cpu-seconds", type=float, default=15.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beside the headline: the per-kernel breakdown pass, "
+                         "the head GEMM, the bf16-storage items, the small-batch, fit(), PCBA-shape, MolNet-width, "
+                         "exact-GEMM and real-Tox21 legs and the CPU baselines")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="(--full) seconds the CPU baseline runs for")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baselines")
     ap.add_argument("--fit-pipeline", type=int, default=1,
-                    help="also time end-to-end fit() (collation + H2D + step) on a PackedDataset")
+                    help="(--full) also time end-to-end fit() (collation + H2D + step) on a PackedDataset")
     ap.add_argument("--profile-only", action="store_true",
-                    help="only the large-batch steps (for rocprofv3 passes): no small-batch, fit or CPU legs")
+                    help="(--full) only the large-batch steps and their per-kernel breakdown (for rocprofv3 passes): "
+                         "no other legs")
     ap.add_argument("--small-batch", type=int, default=100,
-                    help="also report mol/s at the reference's default batch size (0 = skip)")
+                    help="(--full) also report mol/s at the reference's default batch size (0 = skip)")
     ap.add_argument("--storage", default="fp32", choices=["fp32", "bf16", "bf16+grads"],
-                    help="activation storage of the timed step (the headline line is fp32; the default run adds a "
-                         "bf16-storage line item beside it; --storage bf16 --profile-only is for the rocprofv3 passes)")
+                    help="activation storage of the timed step (the headline line is fp32; --full adds the "
+                         "bf16-storage line items beside it; --storage bf16 is for the rocprofv3 passes)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed legs, run one untimed step of the timed path from the seeded inputs and write "
                          "what it computed (loss, logits, fingerprints, gradients, updated parameters) as "
@@ -77,7 +86,10 @@ def parse():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.profile_only:
+    # a plain run times the large-batch step alone; --full adds its per-kernel breakdown pass and the other legs,
+    # --full --profile-only the breakdown pass alone
+    args.other_legs = args.full and not args.profile_only
+    if not args.other_legs:
         args.small_batch, args.fit_pipeline, args.no_cpu_baseline = 0, 0, True
     return args
 
@@ -549,7 +561,7 @@ def main():
                   "fused_bwd": K_FUSED_BWD}
     # Inside the timed region only the roofline kernel is event-timed: every timed launch is
     # bracketed by two event records on the launch stream, which costs ~10 us of queue time each.
-    # The other kernel families are measured in a second, untimed pass.
+    # The other kernel families are measured in a second, untimed pass (--full).
     ops.timing_enable(K_GATHER_SUM, True)
     ops.timing_read(K_GATHER_SUM, reset=True)
 
@@ -565,15 +577,17 @@ def main():
     barrier()
     wall = time.perf_counter() - t0
     gather_time = ops.timing_read(K_GATHER_SUM, reset=True)
+    ops.timing_enable(K_GATHER_SUM, False)
     breakdown_steps = min(args.steps, 5)
-    for kid in kernel_ids.values():
-        ops.timing_enable(kid, True)
-        ops.timing_read(kid, reset=True)
-    run_steps(model, dbatch, labels, weights, breakdown_steps)
-    torch.cuda.synchronize()
-    ktimes = {name: ops.timing_read(kid, reset=True) for name, kid in kernel_ids.items()}
-    for kid in kernel_ids.values():
-        ops.timing_enable(kid, False)
+    if args.full:
+        for kid in kernel_ids.values():
+            ops.timing_enable(kid, True)
+            ops.timing_read(kid, reset=True)
+        run_steps(model, dbatch, labels, weights, breakdown_steps)
+        torch.cuda.synchronize()
+        ktimes = {name: ops.timing_read(kid, reset=True) for name, kid in kernel_ids.items()}
+        for kid in kernel_ids.values():
+            ops.timing_enable(kid, False)
     if world > 1:
         t = torch.tensor([wall], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -643,57 +657,59 @@ def main():
             "launches_per_step": launches_per_step,
             "avg_launch_us": round(ms * 1e3 / max(n_launch, 1), 2),
         },
-        "kernel_ms_per_step": {k: round(v[1] / breakdown_steps, 4) for k, v in ktimes.items()},
     }
+    if args.full:
+        out["kernel_ms_per_step"] = {k: round(v[1] / breakdown_steps, 4) for k, v in ktimes.items()}
     if measured_traffic.step_bytes:
         # all kernels of the step together: measured bytes (same counter passes) over the measured step time
         sb = measured_traffic.step_bytes
         out["step_traffic"] = {"hbm_bytes_per_step": sb, "source": traffic_file,
                                "achieved": round(sb / (wall / args.steps) / 1e9, 1), "unit": "GB/s",
                                "frac_of_hbm_peak": round(sb / (wall / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
-    # Every event-timed kernel family against the same HBM peak (second, untimed pass): algorithmic bytes per
-    # step = operands read once + results written once (DESIGN.md section 7 lists the terms).
-    N, E, B = g.n_atoms, g.n_edges, args.batch
-    fam_bytes = {
-        "gather_sum": per_step,
-        "gather_max": 2 * (E * (4 * 64 + 4) + 2 * N * 4 * 64 + N * 64),
-        # GraphPool backward of the last block; in "full" mode also the two-stage pass (gather of dS onto the self
-        # part + the GraphPool backward of block 0; its dX never leaves LDS: minus one write and one read of N x 64)
-        "gather_max_bwd": (E * (5 * 64 + 5) + 2 * N * 4 * 64 + N * 64) +
-        ((E * (5 * 64 + 5) + 2 * N * 4 * 64 + N * 64) + gather_sum_bytes(N, E, n0, 64, True) - 2 * N * 4 * 64
-         if args.grad_mode == "full" else 0),
-        "readout": N * (4 * 128 + 4) + B * 8 * 128,
-        # forward: GraphConv 0/1, dense, head; backward: head (the blocks' backward products: fused_bwd)
-        "seg_gemm": 4 * (N * (75 + 75 + 64) + N * (64 + 64 + 64) + N * (64 + 128) + B * (256 + 24) + B * (24 + 256)),
-        # dW = A^T dY of the head (the blocks' weight gradients: fused_bwd)
-        "wgrad": 4 * B * (256 + 24),
-        # forward statistics ride in the epilogue of the producing product, the backward sums come from per-molecule
-        # data (dense layer) or from the block above (GraphConv layers): what is left reads B x 640 floats
-        "batchnorm": 4 * B * (256 + 128 + 256),
-        # one pass per block: dense (reads dense 128 + pool 64, writes dpool 64; + ~77 floats per atom of per-molecule
-        # gradient rows fetched once per degree run), GraphConv 1 (dy, gc, S, x -> dS, dXs), GraphConv 0 (dy, gc, S, x)
-        "fused_bwd": 4 * (N * (128 + 64 + 64) + (N * (6 * 64) + N * (64 + 64 + 76 + 76) if args.grad_mode == "full" else 0)),
-    }
-    fam_real, fam_file = family_traffic(args.storage)
-    out["roofline_by_kernel"] = {}
-    for k in ktimes:
-        ms_k = ktimes[k][1] / breakdown_steps
-        rec = {"ms": round(ms_k, 4)}
-        if not h:  # SURVEY 8d's count (fp32 rows; the LDS windows beat it, hence fractions above 1 for the gathers)
-            rec["algorithmic_bytes"] = int(fam_bytes[k])
-            rec["frac_algorithmic"] = round(fam_bytes[k] / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) if ms_k > 0 else 0.0
-        # what the family really moved: PMC bytes of the committed passes over the time measured in THIS run
-        if fam_real is not None and ms_k > 0:
-            rec["hbm_bytes"] = fam_real[k]
-            rec["GBps_real"] = round(fam_real[k] / (ms_k * 1e-3) / 1e9, 1)
-            rec["frac_real"] = round(fam_real[k] / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)
-        out["roofline_by_kernel"][k] = rec
-    out["roofline_by_kernel_source"] = fam_file
+    if args.full:
+        # Every event-timed kernel family against the same HBM peak (second, untimed pass): algorithmic bytes per
+        # step = operands read once + results written once (DESIGN.md section 7 lists the terms).
+        N, E, B = g.n_atoms, g.n_edges, args.batch
+        fam_bytes = {
+            "gather_sum": per_step,
+            "gather_max": 2 * (E * (4 * 64 + 4) + 2 * N * 4 * 64 + N * 64),
+            # GraphPool backward of the last block; in "full" mode also the two-stage pass (gather of dS onto the self
+            # part + the GraphPool backward of block 0; its dX never leaves LDS: minus one write and one read of N x 64)
+            "gather_max_bwd": (E * (5 * 64 + 5) + 2 * N * 4 * 64 + N * 64) +
+            ((E * (5 * 64 + 5) + 2 * N * 4 * 64 + N * 64) + gather_sum_bytes(N, E, n0, 64, True) - 2 * N * 4 * 64
+             if args.grad_mode == "full" else 0),
+            "readout": N * (4 * 128 + 4) + B * 8 * 128,
+            # forward: GraphConv 0/1, dense, head; backward: head (the blocks' backward products: fused_bwd)
+            "seg_gemm": 4 * (N * (75 + 75 + 64) + N * (64 + 64 + 64) + N * (64 + 128) + B * (256 + 24) + B * (24 + 256)),
+            # dW = A^T dY of the head (the blocks' weight gradients: fused_bwd)
+            "wgrad": 4 * B * (256 + 24),
+            # forward statistics ride in the epilogue of the producing product, the backward sums come from per-molecule
+            # data (dense layer) or from the block above (GraphConv layers): what is left reads B x 640 floats
+            "batchnorm": 4 * B * (256 + 128 + 256),
+            # one pass per block: dense (reads dense 128 + pool 64, writes dpool 64; + ~77 floats per atom of per-molecule
+            # gradient rows fetched once per degree run), GraphConv 1 (dy, gc, S, x -> dS, dXs), GraphConv 0 (dy, gc, S, x)
+            "fused_bwd": 4 * (N * (128 + 64 + 64) + (N * (6 * 64) + N * (64 + 64 + 76 + 76) if args.grad_mode == "full" else 0)),
+        }
+        fam_real, fam_file = family_traffic(args.storage)
+        out["roofline_by_kernel"] = {}
+        for k in ktimes:
+            ms_k = ktimes[k][1] / breakdown_steps
+            rec = {"ms": round(ms_k, 4)}
+            if not h:  # SURVEY 8d's count (fp32 rows; the LDS windows beat it, hence fractions above 1 for the gathers)
+                rec["algorithmic_bytes"] = int(fam_bytes[k])
+                rec["frac_algorithmic"] = round(fam_bytes[k] / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 3) if ms_k > 0 else 0.0
+            # what the family really moved: PMC bytes of the committed passes over the time measured in THIS run
+            if fam_real is not None and ms_k > 0:
+                rec["hbm_bytes"] = fam_real[k]
+                rec["GBps_real"] = round(fam_real[k] / (ms_k * 1e-3) / 1e9, 1)
+                rec["frac_real"] = round(fam_real[k] / (ms_k * 1e-3) / 1e9 / HBM_PEAK_GBS, 3)
+            out["roofline_by_kernel"][k] = rec
+        out["roofline_by_kernel_source"] = fam_file
 
-    if rank == 0 and world == 1 and not args.profile_only:
+    if rank == 0 and world == 1 and args.other_legs:
         out["head_gemm"] = head_gemm_utilisation(device, args)
 
-    if rank == 0 and world == 1 and not args.profile_only and args.storage == "fp32" and args.gemm_mode == "fast":
+    if rank == 0 and world == 1 and args.other_legs and args.storage == "fp32" and args.gemm_mode == "fast":
         # BASELINE config 2 "bf16/fp32": the SAME step with every activation the step writes and reads back stored as
         # bf16 (gcmi_model_* storage = 1; fp32 arithmetic, parameters, gradients, Adam) -- beside the f32 headline,
         # never instead of it
@@ -791,7 +807,7 @@ def main():
         out["config"]["fit_molecules_per_s_batch_%d_atom_codes" % args.batch] = round(
             fit_epochs * big.n_mols / (time.perf_counter() - t1), 1)
 
-    if not args.profile_only and args.scaling == "weak" and not (args.batch == 8192 and args.tasks == 128):
+    if args.other_legs and args.scaling == "weak" and not (args.batch == 8192 and args.tasks == 128):
         # BASELINE config 3's per-GPU shape beside the Tox21 headline: 8 192 molecules x 128 two-class tasks per rank,
         # same step (fwd + bwd + Adam, one flat all-reduce per step for N > 1), same timing rules (collective leg)
         import copy
@@ -818,7 +834,7 @@ def main():
                 "molecules_per_s": round(8192 * world * p_steps / p_wall, 1), "ms_per_step": round(p_wall / p_steps * 1e3, 4),
                 "steps": p_steps, "n_gpus": world, "grad_mode": args.grad_mode}
         del pm, pb, pl, pw
-    if rank == 0 and world == 1 and not args.profile_only and args.storage == "fp32":
+    if rank == 0 and world == 1 and args.other_legs and args.storage == "fp32":
         # MolNet's preset widths ([128, 128] GraphConv layers, dense 256: molnet/preset_hyper_parameters.py:128-135) at the
         # headline batch: these shapes run on the general product / gradient kernels, not the one-pass block kernels
         wm, wb, wl, ww = make_workload(args, rank, device, args.batch, "fp32", widths=(128, 128), dense=256)
@@ -832,7 +848,7 @@ def main():
                                                      "ms_per_step": round(w_wall / 5 * 1e3, 4), "steps": 5,
                                                      "molecules_per_step": args.batch}
         del wm, wb, wl, ww
-    if rank == 0 and world == 1 and not args.profile_only and args.gemm_mode == "fast":
+    if rank == 0 and world == 1 and args.other_legs and args.gemm_mode == "fast":
         # the same step on the exact-fp32 matrix-core chain (the arithmetic whose trajectories track the reference)
         deepchem_amd.set_gemm_mode("exact")
         try:

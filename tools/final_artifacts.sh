@@ -1,19 +1,20 @@
 # Round-end evidence: full GPU suite (twice, second time in reverse file order), smoke, bench, kernel statistics and a
-# one-step timeline of the same bench command.  Outputs under gpurun_out/.
+# one-step timeline of the same bench command.  Outputs under $OUT_DIR (default out/).
 set -e
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-mkdir -p gpurun_out
-timeout -k 10 600 python -m pytest tests -q -m gpu > gpurun_out/final_tests.log 2>&1 || { tail -30 gpurun_out/final_tests.log; exit 1; }
-tail -1 gpurun_out/final_tests.log
-timeout -k 10 600 python -m pytest $(ls tests/test_*.py | sort -r) -q -m gpu -p no:cacheprovider > gpurun_out/final_tests_rev.log 2>&1 || { tail -30 gpurun_out/final_tests_rev.log; exit 1; }
-tail -1 gpurun_out/final_tests_rev.log
+out=${OUT_DIR:-out}
+mkdir -p $out
+timeout -k 10 600 python -m pytest tests -q -m gpu > $out/final_tests.log 2>&1 || { tail -30 $out/final_tests.log; exit 1; }
+tail -1 $out/final_tests.log
+timeout -k 10 600 python -m pytest $(ls tests/test_*.py | sort -r) -q -m gpu -p no:cacheprovider > $out/final_tests_rev.log 2>&1 || { tail -30 $out/final_tests_rev.log; exit 1; }
+tail -1 $out/final_tests_rev.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py 2>/dev/null | tail -1 > gpurun_out/final_bench.json
-rm -rf gpurun_out/prof_final
-rocprofv3 --kernel-trace --stats -d gpurun_out/prof_final -- python3 bench.py --profile-only --steps 5 --warmup 2 > gpurun_out/prof_final.log 2>&1
-python tools/step_timeline.py gpurun_out/prof_final > gpurun_out/final_timeline.txt 2>&1 || true
-python tools/kernel_stats.py gpurun_out/prof_final > gpurun_out/final_kernel_stats.csv
-ls gpurun_out/prof_final/* | head -5
-rm -rf gpurun_out/prof_final
-head -c 400 gpurun_out/final_bench.json; echo
-tail -25 gpurun_out/final_timeline.txt
+python bench.py --full 2>/dev/null | tail -1 > $out/final_bench.json
+rm -rf $out/prof_final
+rocprofv3 --kernel-trace --stats -d $out/prof_final -- python3 bench.py --profile-only --steps 5 --warmup 2 > $out/prof_final.log 2>&1
+python tools/step_timeline.py $out/prof_final > $out/final_timeline.txt 2>&1 || true
+python tools/kernel_stats.py $out/prof_final > $out/final_kernel_stats.csv
+ls $out/prof_final/* | head -5
+rm -rf $out/prof_final
+head -c 400 $out/final_bench.json; echo
+tail -25 $out/final_timeline.txt
