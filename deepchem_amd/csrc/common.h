@@ -189,13 +189,14 @@ int fwd_fused_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
 
 // head_bwd.hip: loss + d logits + task-head gradients + tanh' of the readout + the dense BatchNorm's backward sums in
 // one kernel over the molecules (<= 32 outputs), or two on the matrix cores (33..256 outputs, d_dl_scratch = n_mols x
-// outputs floats); GCMI_ERR_UNSUPPORTED = shape not covered (256-column fingerprint)
+// outputs floats, d_img = kHeadImgFloats floats that it fills with head_prep's images of d_w first);
+// GCMI_ERR_UNSUPPORTED = shape not covered (256-column fingerprint)
 int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights, int64_t n_rows,
                    int32_t n_tasks, int32_t n_classes, int64_t n_mols, const float* d_fp, int64_t ldfp,
                    const float* d_w, float* d_dw, float* d_db, float* d_g2, int64_t ldg2, double* d_loss_acc,
                    const int32_t* d_runs, int32_t n_deg, const int32_t* d_arg, const float* d_rawsum,
                    const float* d_mean, const float* d_invstd, double* d_sums, int32_t dense_width, hipStream_t st,
-                   float* d_dl_scratch = nullptr, const float* d_img = nullptr);
+                   float* d_dl_scratch = nullptr, float* d_img = nullptr);
 // ... and the forward head with 33..256 outputs (one segment, 256-column rows, nn.Linear weight, no activation); d_img:
 // the fragment images head_prep made of d_w (kHeadImgFloats floats: forward order, then backward order), or nullptr
 constexpr int kHeadImgFloats = 2 * 8 * 16 * 3 * 64 * 4;

@@ -867,9 +867,13 @@ static bool head_wide_enabled() {
   return on && !gemm_exact_mode();
 }
 
-// the two fragment images of the head matrix (kHeadImgFloats floats at d_img); GCMI_ERR_UNSUPPORTED: outside 33..256 outputs
+// whether n_out outputs take the matrix-core head kernels: the one predicate of head_prep, head_fwd_wide and
+// head_bwd_fused (the product mode is read on every call, so forward and backward may see different answers)
+static bool head_wide(int n_out) { return head_wide_enabled() && n_out >= head_wide_min() && n_out <= kWTC; }
+
+// the two fragment images of the head matrix (kHeadImgFloats floats at d_img); GCMI_ERR_UNSUPPORTED: not head_wide(n_out)
 int head_prep(const float* d_w, int32_t n_out, float* d_img, hipStream_t st) {
-  if (!head_wide_enabled() || n_out < head_wide_min() || n_out > kWTC || d_img == nullptr || !aligned16(d_w) || !aligned16(d_img))
+  if (!head_wide(n_out) || d_img == nullptr || !aligned16(d_w) || !aligned16(d_img))
     return GCMI_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(head_prep_kernel, dim3(2 * kImgTiles * kImgKs * 64 / 256), dim3(256), 0, st, d_w, n_out,
                      reinterpret_cast<u32x4*>(d_img));
@@ -881,8 +885,7 @@ int head_prep(const float* d_w, int32_t n_out, float* d_img, hipStream_t st) {
 // d_img: the images head_prep made of THIS d_w (the forward one is read), or nullptr: the weights are split per workgroup
 int head_fwd_wide(const float* d_in, int64_t ldin, int64_t n_rows, int32_t k, const float* d_w, const float* d_bias,
                   int32_t n_out, int32_t act, float* d_out, int64_t ldo, hipStream_t st, const float* d_img) {
-  if (!head_wide_enabled() || k != kHB || n_out < head_wide_min() || n_out > kWTC || act != 0 || ldin % 4 != 0 || !aligned16(d_in) ||
-      !aligned16(d_w) || n_rows <= 0)
+  if (!head_wide(n_out) || k != kHB || act != 0 || ldin % 4 != 0 || !aligned16(d_in) || !aligned16(d_w) || n_rows <= 0)
     return GCMI_ERR_UNSUPPORTED;
   if (d_img != nullptr) {
     hipLaunchKernelGGL(head_fwd_img_kernel, dim3((unsigned)((n_rows + kHM - 1) / kHM)), dim3(kWT), 0, st, d_in, ldin, n_rows,
@@ -908,21 +911,21 @@ int head_fwd_wide(const float* d_in, int64_t ldin, int64_t n_rows, int32_t k, co
   return GCMI_OK;
 }
 
-// GCMI_ERR_UNSUPPORTED: other widths than a 256-column fingerprint; more than 32 task outputs without d_dl_scratch
-// (n_mols x outputs floats) and d_img (head_prep's images of d_w), or more than 256
+// GCMI_ERR_UNSUPPORTED: other widths than a 256-column fingerprint; more than 32 task outputs unless head_wide() and
+// there are d_dl_scratch (n_mols x outputs floats) and d_img (room for the images, which are made here of d_w: what a
+// forward left there may be of other weights, or nothing)
 int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights, int64_t n_rows,
                    int32_t n_tasks, int32_t n_classes, int64_t n_mols, const float* d_fp, int64_t ldfp,
                    const float* d_w, float* d_dw, float* d_db, float* d_g2, int64_t ldg2, double* d_loss_acc,
                    const int32_t* d_runs, int32_t n_deg, const int32_t* d_arg, const float* d_rawsum,
                    const float* d_mean, const float* d_invstd, double* d_sums, int32_t dense_width, hipStream_t st,
-                   float* d_dl_scratch, const float* d_img) {
+                   float* d_dl_scratch, float* d_img) {
   static const bool on = !(getenv("GCMI_FUSED_HEAD") && atoi(getenv("GCMI_FUSED_HEAD")) == 0);
   const int tc = n_tasks * (kind == 0 ? n_classes : 1);
   if (!on || !fused_bwd_enabled() || 2 * dense_width != kHB || tc < 1 || n_mols <= 0) return GCMI_ERR_UNSUPPORTED;
-  const bool wide = tc > kHT || (tc >= head_wide_min() && d_dl_scratch != nullptr && d_img != nullptr && head_wide_enabled());
-  if (wide && (tc > kWTC || d_dl_scratch == nullptr || d_img == nullptr || !head_wide_enabled() || ldfp % 4 != 0 ||
-               !aligned16(d_fp)))
-    return GCMI_ERR_UNSUPPORTED;
+  const bool wide = head_wide(tc) && d_dl_scratch != nullptr && d_img != nullptr && ldfp % 4 == 0 && aligned16(d_fp) &&
+                    aligned16(d_w) && aligned16(d_img);
+  if (!wide && tc > kHT) return GCMI_ERR_UNSUPPORTED;  // (the caller runs the separate launches)
   if (d_sums != nullptr && (!d_runs || !d_arg || !d_rawsum || !d_mean || !d_invstd)) return GCMI_ERR_UNSUPPORTED;
   HeadArgs a;
   memset(&a, 0, sizeof(a));
@@ -943,6 +946,8 @@ int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, c
       }
       attr_done = true;
     }
+    const int rc = head_prep(d_w, tc, d_img, st);
+    if (rc != GCMI_OK) return rc;
     hipLaunchKernelGGL(head_bwd_wide_kernel, dim3((unsigned)((n_mols + kHM - 1) / kHM)), dim3(kWT), shmem, st, a, d_dl_scratch,
                        reinterpret_cast<const u32x4*>(d_img) + kImgEntries);
     GCMI_CHECK_LAUNCH("head_bwd_wide");

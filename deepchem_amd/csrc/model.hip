@@ -64,7 +64,8 @@ struct Ws {
   int64_t dense, arg_r, rsum, dfp, tA, tB, tC, tD, tE, total;
   int64_t xb;    // storage == 1: bf16 copy of the atom features (ld = ldS[0])
   int64_t wimg;  // scratch of the forward products (split weight fragments in lane order, rebuilt by every launch)
-  int64_t himg;  // more than 32 task outputs: the head matrix's two fragment images (head_bwd.hip: head_prep), forward -> backward
+  int64_t himg;  // more than 32 task outputs: the head matrix's two fragment images (head_bwd.hip: head_prep; the
+                 // forward and the backward each make them of the weights they are given)
   // one region the backward zeroes with a single memset: [dlogits | dbsum per layer | lacc | acc]
   int64_t dlogits, dbsum[kMaxL], lacc, acc, acc2, z_end;
 };
@@ -152,8 +153,8 @@ static int unpack_bias_grads(const gcmi_model_desc* m, const BiasLayers& bl, int
   return GCMI_OK;
 }
 
-// The task head's forward product: with more than 32 outputs on the prepared images (head_bwd.hip), which stay in the
-// workspace for the backward; otherwise (and in the exact product mode) the segmented product.
+// The task head's forward product: with more than 32 outputs on the prepared images (head_bwd.hip; the backward makes
+// its own of the weights it is given); otherwise (and in the exact product mode) the segmented product.
 static int head_forward(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, const gcmi_model_io* io,
                         int64_t B, void* stream) {
   const int D = m->dense_width;
@@ -182,13 +183,13 @@ static int check_desc(const gcmi_model_desc* m) {
   for (int l = 0; l < m->n_layers; ++l) GCMI_CHECK_ARG(m->conv_width[l] > 0, "bad conv width");
   if (m->storage != 0) {
     // bf16 activation storage in the streaming kernels (fwd_bf16.hip, bwd_fused.hip HB, gather_lds.hip *OpH): the
-    // default shapes -- GraphConv widths 64 over 65..80 input columns, dense width 128, BatchNorm on
+    // default shapes -- GraphConv widths 64 over 73..76 input columns (the fp32 -> bf16 window gather of the atom
+    // features has the 76-column instantiation only), dense width 128, BatchNorm on
     // (2 = the gradient streams between the kernels are bf16 as well)
-    bool ok = (m->storage == 1 || m->storage == 2) && m->batch_norm && m->dense_width == 128 && m->n_feat_in > 64 &&
-              m->n_feat_in <= 80;
+    bool ok = (m->storage == 1 || m->storage == 2) && m->batch_norm && m->dense_width == 128 && up4(m->n_feat_in) == 76;
     for (int l = 0; l < m->n_layers; ++l) ok = ok && m->conv_width[l] == 64;
     if (!ok) {
-      set_error("gcmi_model_*: bf16 activation storage covers graph_conv_layers of width 64 over 65..80 atom features, "
+      set_error("gcmi_model_*: bf16 activation storage covers graph_conv_layers of width 64 over 73..76 atom features, "
                 "dense_layer_size 128 and batch_normalize=True (other shapes: gcmi_small_* or storage 0)");
       return GCMI_ERR_UNSUPPORTED;
     }
@@ -239,7 +240,8 @@ static int require_h(const gcmi_model_desc* m, const gcmi_graph* g, const gcmi_m
     set_error("bf16 activation storage: not available in the exact-fp32 product mode (set_gemm_mode('fast'))");
     return GCMI_ERR_UNSUPPORTED;
   }
-  if (g->n_atoms > 0 && (!win_usable_h(g, 64) || !win_usable_h(g, 80) || !win_usable(g, (int)up4(m->n_feat_in), false))) {
+  if (g->n_atoms > 0 && (!win_usable_h(g, 64) || !win_usable_h(g, 80) || !win_usable(g, (int)up4(m->n_feat_in), false) ||
+                         !win_has_width((int)up4(m->n_feat_in)))) {
     set_error("bf16 activation storage: the graph carries no usable molecule-window plan (collate with gcmi_collate_plans)");
     return GCMI_ERR_UNSUPPORTED;
   }

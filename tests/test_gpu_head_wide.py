@@ -29,8 +29,8 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("mode,tasks,classes,n,seed", CASES)
-def test_wide_head_meets_the_oracle(mode, tasks, classes, n, seed):
+def _head_case(mode, tasks, classes, n, seed):
+    """Molecules, labels, weights and the initial state of one case."""
     from oracle import graphconv_oracle as O
     from deepchem_amd.utils.synthetic import synthetic_labels, synthetic_molecules
     packed = synthetic_molecules(n, seed=seed, max_atoms=40)
@@ -41,15 +41,94 @@ def test_wide_head_meets_the_oracle(mode, tasks, classes, n, seed):
     else:
         y, w = synthetic_labels(n, tasks, "regression", tasks)
     cfg = O.ModelConfig(tasks, mode=mode, n_classes=classes, batch_size=n)
-    state = O.init_state(cfg, 9)
+    return packed, y, w, O.init_state(cfg, 9)
+
+
+def _check_against_oracle(native, packed, y, w, tasks, state, mode, classes):
     kw = dict(mode=mode, n_classes=classes)
-    native = _native_step(packed, y, w, tasks, "full", state, **kw)
 
     def outs(o):  # _check reads outs[1] (outputs) and outs[2] (fingerprint)
         return o if mode == "classification" else (o[0], [None, o[1][0], o[1][1]], o[2], o[3])
     checked, report = _check(native, outs(_oracle_step(packed, y, w, tasks, "full", state, **kw)),
                              outs(_oracle_step(packed, y, w, tasks, "full", state, double=True, **kw)))
     assert checked > 40
+
+
+def wide_head_meets_the_oracle(mode, tasks, classes, n, seed):
+    packed, y, w, state = _head_case(mode, tasks, classes, n, seed)
+    native = _native_step(packed, y, w, tasks, "full", state, mode=mode, n_classes=classes)
+    _check_against_oracle(native, packed, y, w, tasks, state, mode, classes)
+
+
+@pytest.mark.parametrize("mode,tasks,classes,n,seed", CASES)
+def test_wide_head_meets_the_oracle(mode, tasks, classes, n, seed):
+    wide_head_meets_the_oracle(mode, tasks, classes, n, seed)
+
+
+@pytest.mark.parametrize("switch,cases", [
+    # the forward declines the wide kernels below the minimum: the backward must not read the images it did not build
+    ("GCMI_HEAD_WIDE_MIN=64", [CASES[0], CASES[4]]),
+    # the wide kernels below 33 outputs
+    ("GCMI_HEAD_WIDE_MIN=16", [("classification", 12, 2, 75, 98)]),
+    # the wide kernels off: the separate launches above 32 outputs
+    ("GCMI_HEAD_WIDE=0", [CASES[0]]),
+])
+def test_wide_head_switches_meet_the_oracle(switch, cases):
+    """The switches are read once per process: each runs in a child of its own (one GPU process at a time)."""
+    import os
+    import subprocess
+    import sys
+    code = ("from tests.test_gpu_head_wide import wide_head_meets_the_oracle\n"
+            "for c in %r:\n    wide_head_meets_the_oracle(*c)\nprint('ok')\n" % (cases,))
+    name, value = switch.split("=")
+    env = dict(os.environ)
+    env.pop("GCMI_HEAD_WIDE_MIN", None)
+    env.pop("GCMI_HEAD_WIDE", None)
+    env[name] = value
+    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300,
+                         cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert out.returncode == 0 and "ok" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+
+
+def test_wide_head_backward_after_a_product_mode_switch():
+    """The head matrix's fragment images are made by a fast-mode forward; the weights then change in place, an
+    exact-mode forward (which makes no images) runs on them, and the backward runs in fast mode.  It must use the
+    weights it is given, not the images of the earlier ones."""
+    import deepchem_amd as dc
+    from deepchem_amd.data.collate import collate_to_device
+    from deepchem_amd.metrics import to_one_hot
+    mode, tasks, classes, n, seed = CASES[0]
+    packed, y, w, state = _head_case(mode, tasks, classes, n, seed)
+    w2 = state["reshape_dense.weight"].flip(0) * 1.5  # W2: other values, the same scale
+    state2 = dict(state, **{"reshape_dense.weight": w2.clone()})
+    dev = torch.device("cuda:0")
+    dbatch = collate_to_device(packed, None, dev)
+    labels = torch.as_tensor(to_one_hot(y.flatten(), classes).reshape(-1, tasks, classes).astype(np.float32), device=dev)
+    weights = torch.as_tensor(w.astype(np.float32), device=dev)
+    model = dc.models.torch_models.GraphConvModel(tasks, number_input_features=[75, 64], mode=mode, n_classes=classes,
+                                                  batch_size=n, grad_mode="full", device=dev)
+    model.model.load_state_dict({k: v.clone() for k, v in state.items()})
+    native = model.model._native_net()
+    g = dbatch.graph
+    g.set_mols(n)
+    off = native.offsets["reshape_dense.weight"]
+    try:
+        dc.set_gemm_mode("fast")
+        model.model.eval()
+        native.forward(dbatch.atom_features, g, False, want_probs=False)  # makes the images of W1
+        native.flat[off:off + w2.numel()].copy_(w2.reshape(-1).to(dev))
+        model.model.train()
+        dc.set_gemm_mode("exact")
+        logits, _, fp = native.forward(dbatch.atom_features, g, True, want_probs=False)
+        dc.set_gemm_mode("fast")
+        loss = native.loss_backward(labels, weights, n)
+        torch.cuda.synchronize()
+    finally:
+        dc.set_gemm_mode("fast")
+    names = [k for k, _ in model.model.named_parameters()]
+    native_out = (float(loss), logits.cpu(), fp.cpu(), native.grad_flat.clone().cpu(), list(zip(names, native._slices)),
+                  native.grad_range, None, g)
+    _check_against_oracle(native_out, packed, y, w, tasks, state2, mode, classes)
 
 
 @pytest.mark.parametrize("rows,n_out,with_scratch", [(100, 24, True), (75, 40, True), (8192, 256, True), (333, 256, False),
