@@ -724,16 +724,9 @@ static int launch_fused(const FusedTable& st, int n_tiles, const FusedArgs& a, h
   if (DGRAD)
     shmem += sizeof(unsigned short) * (size_t)NOPS * 3 * KP * (NG + 8) + sizeof(float) * kFRows * (NOPS * KT * 32 + 8);
   auto kern = fused_bwd_kernel<NG, KT, NOPS, TRANS, RD, DGRAD, HB, GB>;
-  static bool attr_done = false;  // per instantiation
-  if (!attr_done) {
-    // exactly what is asked for: the kernel also has a few hundred bytes of static LDS (the segment table)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) {
-      (void)hipGetLastError();
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    attr_done = true;
-  }
+  // exactly what is asked for: the kernel also has a few hundred bytes of static LDS (the segment table)
+  static LdsLimit lim;  // per instantiation
+  if (!raise_lds_limit(lim, reinterpret_cast<const void*>(kern), shmem)) return GCMI_ERR_UNSUPPORTED;
   const int per_cu = DGRAD ? 1 : 2;
   const int grid = std::min(n_tiles, 256 * per_cu);
   static const bool diag_on = getenv("GCMI_FUSED_DIAG") && atoi(getenv("GCMI_FUSED_DIAG")) != 0;

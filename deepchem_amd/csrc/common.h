@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <atomic>
 #include <stdlib.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -14,7 +15,16 @@ namespace gcmi {
 void set_error(const char* fmt, ...);
 // 0 / 1 alternately: whether the next row-streaming launch walks its rows backwards (core.cpp)
 int next_sweep_direction();
-int next_sweep_direction_windows();  // the same for the window gathers (GCMI_SWEEP=1 leaves them forwards)
+
+// Dynamic-LDS limit of one kernel, raised once per device: hipFuncSetAttribute acts on the current device only, so the
+// cache is keyed by hipGetDevice (one static LdsLimit per kernel instantiation).  raise_lds_limit returns 0 when HIP
+// refuses the limit (its error cleared, nothing cached); otherwise, with threads > 0, how many workgroups of `threads`
+// threads with `shmem` bytes of dynamic LDS one CU of this device holds (2 where HIP cannot say), else 1.
+constexpr int kMaxDev = 64;
+struct LdsLimit {
+  std::atomic<int> per_cu[kMaxDev];
+};
+int raise_lds_limit(LdsLimit& a, const void* kern, size_t lds_bytes, int threads = 0, size_t shmem = 0);
 
 #define GCMI_CHECK_ARG(cond, ...)          \
   do {                                     \
@@ -77,11 +87,6 @@ int win_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, i
 bool win_two_stage_usable(const gcmi_graph* g, int n_feat);
 int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int n_feat, float* d_dxs,
                               int64_t lddxs, const uint8_t* d_arg, float* d_dy, int64_t lddy, hipStream_t st);
-// the same, also adding the column sums of the BatchNorm backward (sum dx, sum dx*xhat; bn.hip scratch layout)
-bool win_stats_usable(const gcmi_graph* g, int n_feat);
-int win_gather_max_bwd_stats(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
-                             float* d_dx, int64_t lddx, const float* d_x, int64_t ldx, const float* d_mean,
-                             const float* d_invstd, double* d_sums, hipStream_t st);
 // BatchNorm backward from the sums sum dP, sum dP * P over the rows of the block ABOVE (bwd_fused.hip: psums), with
 // P = max over neighbours of the BatchNorm output y = gamma * xhat + beta: sum dy = sum dP and
 // sum dy * xhat = (sum dP * P - beta * sum dP) / gamma, no pass over dy.  Where that division is ill-conditioned
@@ -116,10 +121,6 @@ bool win_two_stage_usable_h(const gcmi_graph* g, int n_feat);
 int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const unsigned short* d_ds, int64_t ldds, int n_feat,
                                 unsigned short* d_dxs, int64_t lddxs, const uint8_t* d_arg, unsigned short* d_dy,
                                 int64_t lddy, hipStream_t st);
-bool win_max_sum_usable_h(const gcmi_graph* g, int n_feat);
-int win_gather_max_sum_h(const gcmi_graph* g, const unsigned short* d_x, int64_t ldx, int n_feat, const float* d_scale,
-                         const float* d_shift, unsigned short* d_out, int64_t ldo, uint8_t* d_arg, unsigned short* d_s,
-                         int64_t lds, hipStream_t st);
 // fwd_bf16.hip: forward product over bf16 operands, bf16 output, BatchNorm sums of the rounded output
 int fwd_h_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const unsigned short* d_a1, int64_t lda1,
                int32_t k1, const float* d_w1, const int64_t* w1_off, const unsigned short* d_a2, int64_t lda2, int32_t k2,
@@ -149,12 +150,6 @@ int launch_wgrad3(const SlabTable& st, int slabs, const float* d_a, int64_t lda,
 
 // gemm_split.hip: the segmented GEMM on the bf16 matrix cores with exactly split fp32 operands;
 // GCMI_ERR_UNSUPPORTED = shape not covered (fall back to gemm.hip)
-int launch_seg_gemm3(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1,
-                     int64_t lda1, int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2,
-                     int64_t lda2, int32_t k2, const float* d_w2, const int64_t* w2_off, const float* d_bias,
-                     const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act, float* d_out,
-                     int64_t ldo, hipStream_t sm);
-
 int launch_seg_gemm4(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1,
                      int64_t lda1, int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2,
                      int64_t lda2, int32_t k2, const float* d_w2, const int64_t* w2_off, const float* d_bias,
@@ -218,9 +213,6 @@ int seg_gemm_stats(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
                    int32_t n_out, int32_t trans_w, int32_t act, float* d_out, int64_t ldo, double* d_stats,
                    bool* fused, void* stream, float* d_wimg_scratch = nullptr);
 // gcmi_readout_fwd that also leaves the per-molecule sums of the rows before the folded BatchNorm in d_rawsum
-// GraphGather forward over the LDS molecule windows (gather_lds.hip: ReadoutOp); GCMI_ERR_UNSUPPORTED: not applicable
-int win_readout(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_feat, const float* d_scale, const float* d_shift,
-                int act, float* d_out, int64_t ldo, int32_t* d_arg, float* d_rawsum, int x_bf16, hipStream_t st);
 int readout_fwd_impl(const gcmi_graph* g, const float* d_x, int64_t ldx, int32_t n_feat, const float* d_scale,
                      const float* d_shift, int32_t act, float* d_out, int64_t ldo, int32_t* d_arg, float* d_rawsum,
                      void* stream, int32_t x_bf16 = 0);

@@ -16,20 +16,32 @@ static thread_local char g_err[512] = "";
 // launched right after its producer then starts on the rows the producer wrote LAST, which are the ones still in the
 // 256 MB Infinity Cache (an N x 64 float array of the benchmark batch is 0.31 GB), instead of evicting them while it
 // re-reads the oldest rows from HBM.
-// GCMI_SWEEP: 0 = always forwards, 1 = the row-linear kernels alternate, 2 (default) = the window gathers take part
-// too.  Same box, back to back: 4.73 / 4.67 / 4.66 ms per step.
-static int sweep_mode() {
-  static const int mode = getenv("GCMI_SWEEP") ? atoi(getenv("GCMI_SWEEP")) : 2;
-  return mode;
-}
+// Same box, back to back: 4.73 ms per step with every launch forwards, 4.67 with only the row-linear kernels taking
+// turns, 4.66 with the window gathers taking part too.
 static std::atomic<unsigned> g_sweep_counter{0};
-int next_sweep_direction() {
-  if (sweep_mode() == 0) return 0;
-  return (int)(g_sweep_counter.fetch_add(1, std::memory_order_relaxed) & 1u);
-}
-int next_sweep_direction_windows() {
-  if (sweep_mode() != 2) return 0;
-  return (int)(g_sweep_counter.fetch_add(1, std::memory_order_relaxed) & 1u);
+int next_sweep_direction() { return (int)(g_sweep_counter.fetch_add(1, std::memory_order_relaxed) & 1u); }
+
+int raise_lds_limit(LdsLimit& a, const void* kern, size_t lds_bytes, int threads, size_t shmem) {
+  int dev = -1;
+  const bool keyed = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDev;
+  if (keyed) {
+    const int done = a.per_cu[dev].load(std::memory_order_relaxed);
+    if (done > 0) return done;
+  } else {
+    (void)hipGetLastError();
+  }
+  if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  int per_cu = 1;
+  if (threads > 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, shmem) != hipSuccess ||
+                      per_cu < 1)) {
+    (void)hipGetLastError();
+    per_cu = 2;
+  }
+  if (keyed) a.per_cu[dev].store(per_cu, std::memory_order_relaxed);
+  return per_cu;
 }
 
 void set_error(const char* fmt, ...) {

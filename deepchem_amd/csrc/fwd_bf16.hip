@@ -57,7 +57,7 @@ struct FwdHArgs {
 // strided dword loads per fragment and lane, which the compiler (short of registers) issues one at a time, each behind
 // a full wait: 64 dependent L2 round trips per segment change, 20-40 us that EVERY workgroup pays at its start.  This
 // kernel splits every fragment of every segment once -- [segment][32-column tile][k-step][piece][lane] 16-byte entries
-// -- so that a reload is NKS * NPW coalesced 1 KiB wave loads with one wait behind them.
+// -- so that a reload is NKS * 3 coalesced 1 KiB wave loads with one wait behind them.
 template <bool TRANS>
 __global__ void __launch_bounds__(256)
 wprep_kernel(FwdHTable st, const float* __restrict__ w0, const float* __restrict__ w1, int k_in, int KO, int NOPS,
@@ -91,248 +91,11 @@ wprep_kernel(FwdHTable st, const float* __restrict__ w0, const float* __restrict
   }
 }
 
-// NOPS operands of KO (padded) columns each, NOUT output columns, NPW bf16 pieces kept of every weight (3: exact to
-// 2^-24; 2: to 2^-16, far below the 2^-9 of the stored result); TRANS: weights stored NOUT x k_in (nn.Linear)
-template <int NOPS, int KO, int NOUT, bool TRANS, int NPW>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NPW == 2 ? 3 : 2)))
-fwd_h_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
-  constexpr int NT = 256, ROWS = 64;
-  constexpr int NC = NOPS * KO;               // contraction length
-  constexpr int AP = NC + 8;                  // pitch of an operand row in LDS (bf16 elements): conflict-free b128 reads
-  constexpr int NKS = NC / 16;
-  constexpr int TW = NOUT / 32;               // 32-column tiles of the output
-  constexpr int TPW = TW / 2;                 // ... per wave: waves = 2 row blocks x 2 column groups
-  static_assert(TW % 2 == 0 && KO % 8 == 0 && NC % 16 == 0, "tile shapes");
-  constexpr int IQ = KO / 8;                  // 16-byte pieces of an operand row
-  constexpr int RQ = NOPS * IQ;               // ... of a tile row over all operands
-  constexpr int IPASS = ROWS * RQ / NT;
-  static_assert(ROWS * RQ % NT == 0, "tile loads divide evenly");
-  constexpr int OPB = NOUT * 2 + 16;          // pitch of an output row in LDS (bytes)
-  constexpr int OQ = NOUT / 8;                // 16-byte pieces of an output row
-  constexpr int OPASS = ROWS * OQ / NT;
-  static_assert(ROWS * OQ % NT == 0 && NT % OQ == 0, "a thread keeps its column piece over the passes");
-  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  bf16_t* As = reinterpret_cast<bf16_t*>(lds_raw);                       // [ROWS][AP]
-  unsigned char* Outs = lds_raw + (size_t)ROWS * AP * 2;                  // [ROWS][OPB]
-  __shared__ int t_begin_s[kHMaxSeg], t_end_s[kHMaxSeg], t_tile_s[kHMaxSeg + 1];
-  __shared__ long long t_w_s[2][kHMaxSeg], t_b_s[kHMaxSeg];
-  __shared__ __attribute__((aligned(16))) float bias_s[NOUT];
-  __shared__ double stat_s[2][NOUT];
-
-  const int tid = threadIdx.x;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63;
-  const int half = lane >> 5;
-  const int l31 = lane & 31;
-  const int rb = wave & 1, twb = wave >> 1;   // rows rb*32.., column tiles twb, twb + 2, ...
-
-  if (tid <= kHMaxSeg) {
-    t_tile_s[tid] = pick_n(st.tile_start, tid);
-    if (tid < kHMaxSeg) {
-      t_begin_s[tid] = pick_n(st.seg_begin, tid);
-      t_end_s[tid] = pick_n(st.seg_end, tid);
-      t_w_s[0][tid] = pick_n(st.w_off[0], tid);
-      t_w_s[1][tid] = pick_n(st.w_off[1], tid);
-      t_b_s[tid] = pick_n(st.b_off, tid);
-    }
-  }
-  for (int c = tid; c < 2 * NOUT; c += NT) stat_s[c / NOUT][c % NOUT] = 0.0;
-  const int n_seg = st.n_seg;
-  __syncthreads();
-
-  const int b = rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
-  // (64-bit division runs on the vector unit: say that the results are uniform)
-  const int t_begin = __builtin_amdgcn_readfirstlane((int)((int64_t)b * n_tiles / gridDim.x));
-  const int t_end = __builtin_amdgcn_readfirstlane((int)((int64_t)(b + 1) * n_tiles / gridDim.x));
-  const int my_tiles = t_end - t_begin;  // >= 1: the grid is never larger than the tile count
-  auto tile_at = [&](int i) { return rev ? t_end - 1 - i : t_begin + i; };
-  auto tile_info = [&](int tile, int& seg, int& row0, int& valid) {
-    int s = 0;
-    for (int k = 1; k < n_seg; ++k) s += tile >= t_tile_s[k] ? 1 : 0;
-    seg = __builtin_amdgcn_readfirstlane(s);  // LDS reads land in vector registers; these are uniform
-    row0 = __builtin_amdgcn_readfirstlane(t_begin_s[seg] + (tile - t_tile_s[seg]) * ROWS);
-    const int left = __builtin_amdgcn_readfirstlane(t_end_s[seg]) - row0;
-    valid = left < ROWS ? left : ROWS;
-  };
-
-  // ---- prefetch registers: the next tile's operand rows, 16 bytes (8 elements) per lane, unconditional from clamped
-  // addresses; a tile row is the RQ pieces of its operands side by side, as it will lie in LDS
-  // (ext_vector_type, not HIP's uint4 struct: an array of those captured by the lambdas below goes to scratch memory)
-  u32x4 pin[IPASS];
-  auto slot_rj = [&](int p, int& r, int& j) {
-    int slot = tid + p * NT;
-    asm volatile("" : "+v"(slot));  // formed at each use: hoisted out of the tile loop these would be spilled
-    r = slot / RQ;
-    j = slot - r * RQ;
-  };
-  auto load_src = [&](int row0, int valid) {
-#pragma unroll
-    for (int p = 0; p < IPASS; ++p) {
-      int r, j;
-      slot_rj(p, r, j);
-      const int o = NOPS == 2 ? (j >= IQ ? 1 : 0) : 0;
-      const int q = j - o * IQ;
-      const int ld = o == 1 ? a.ldin[1] : a.ldin[0];
-      const int qc = 8 * q + 8 <= ld ? 8 * q : 0;  // a piece beyond the stored row (ld < KO): any finite bytes, its weights are zero
-      const int rc = r < valid ? r : valid - 1;
-      unsigned off = ((unsigned)(row0 + rc) * (unsigned)ld + (unsigned)qc) * 2u;
-      asm volatile("" : "+v"(off));
-      const char* base = reinterpret_cast<const char*>(o == 1 ? a.in[1] : a.in[0]);
-      pin[p] = *reinterpret_cast<const u32x4*>(base + off);
-    }
-  };
-  // the prefetched rows -> LDS as they are.  Rows beyond a ragged tile's end hold copies of its last row (their
-  // results are never stored); columns [k_in, KO) meet zero weights and hold zeros or finite padding.
-  auto write_as = [&]() {
-#pragma unroll
-    for (int p = 0; p < IPASS; ++p) {
-      int r, j;
-      slot_rj(p, r, j);
-      *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(As) + (r * AP + j * 8) * 2) = pin[p];
-    }
-  };
-
-  // ---- this wave's weight fragments of the segment (the matrix core's A operand: lane = output column, eight
-  // consecutive contraction indices), split into NPW bf16 pieces, and the segment's bias row in LDS
-  u32x4 wf[TPW][NKS][NPW];
-  auto load_w = [&](int seg_) {
-    // (wprep_kernel's images: [segment][32-column tile][k-step][piece][lane])
-    const u32x4* base = a.wimg + (size_t)seg_ * TW * NKS * 3 * 64 + lane;
-#pragma unroll
-    for (int j = 0; j < TPW; ++j)
-#pragma unroll
-      for (int ks = 0; ks < NKS; ++ks)
-#pragma unroll
-        for (int pc = 0; pc < NPW; ++pc)
-          wf[j][ks][pc] = base[(size_t)(((twb + 2 * j) * NKS + ks) * 3 + pc) * 64];
-  };
-
-  // ---- the previous tile's output: LDS -> HBM as whole rows, and the BatchNorm sums of the ROUNDED values on the way
-  // (fp32 partials per thread over eight tiles -- a thread keeps its column piece --, then fp64 in LDS)
-  float ps1[8], ps2[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) ps1[i] = ps2[i] = 0.f;
-  auto flush_stats = [&]() {
-    const int q = tid % OQ;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      atomicAdd(&stat_s[0][8 * q + i], (double)ps1[i]);
-      atomicAdd(&stat_s[1][8 * q + i], (double)ps2[i]);
-      ps1[i] = ps2[i] = 0.f;
-    }
-  };
-  auto store_out = [&](int prow0, int pvalid) {
-#pragma unroll
-    for (int p = 0; p < OPASS; ++p) {
-      const int slot = tid + p * NT;
-      const int r = slot / OQ, q = slot - r * OQ;
-      if (r < pvalid) {
-        const uint4 v = *reinterpret_cast<const uint4*>(Outs + r * OPB + q * 16);
-        unsigned off = ((unsigned)(prow0 + r) * (unsigned)a.ldo + 8u * q) * 2u;
-        *reinterpret_cast<uint4*>(reinterpret_cast<char*>(a.out) + off) = v;
-        if (a.stats != nullptr) {
-          float f[8];
-          widen8(v, f);
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            ps1[i] += f[i];
-            ps2[i] = fmaf(f[i], f[i], ps2[i]);
-          }
-        }
-      }
-    }
-  };
-
-  // ---- this wave's output tile(s): products, bias, ReLU, rounding -> the LDS output tile
-  auto products = [&]() {
-    f32x16 acc[TPW];
-#pragma unroll
-    for (int j = 0; j < TPW; ++j)
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc[j][k] = 0.f;
-    const unsigned char* arow = reinterpret_cast<const unsigned char*>(As) + ((rb * 32 + l31) * AP + 8 * half) * 2;
-    u32x4 xa = *reinterpret_cast<const u32x4*>(arow);
-#pragma unroll
-    for (int ks = 0; ks < NKS; ++ks) {
-      const u32x4 x = xa;
-      if (ks + 1 < NKS) xa = *reinterpret_cast<const u32x4*>(arow + (ks + 1) * 32);  // issued before this k-step's MFMAs
-#pragma unroll
-      for (int j = 0; j < TPW; ++j) {
-        // output columns x rows: lane = row of the tile, registers = output columns; small terms first
-#pragma unroll
-        for (int pc = NPW - 1; pc >= 0; --pc)
-          acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(wf[j][ks][pc]), as_bf16x8(x), acc[j], 0, 0, 0);
-      }
-    }
-    unsigned char* orow = Outs + (rb * 32 + l31) * OPB;
-#pragma unroll
-    for (int j = 0; j < TPW; ++j) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int c0 = (twb + 2 * j) * 32 + 8 * g + 4 * half;
-        const float4 bv = *reinterpret_cast<const float4*>(bias_s + c0);
-        float v0 = acc[j][4 * g + 0] + bv.x, v1 = acc[j][4 * g + 1] + bv.y;
-        float v2 = acc[j][4 * g + 2] + bv.z, v3 = acc[j][4 * g + 3] + bv.w;
-        if (a.relu) {
-          v0 = v0 > 0.f ? v0 : 0.f; v1 = v1 > 0.f ? v1 : 0.f;
-          v2 = v2 > 0.f ? v2 : 0.f; v3 = v3 > 0.f ? v3 : 0.f;
-        }
-        *reinterpret_cast<uint2*>(orow + c0 * 2) = narrow4(v0, v1, v2, v3);
-      }
-    }
-  };
-
-  int seg, row0, valid;
-  tile_info(tile_at(0), seg, row0, valid);
-  int nseg = seg, nrow0 = row0, nvalid = valid;
-  if (my_tiles > 1) tile_info(tile_at(1), nseg, nrow0, nvalid);
-  load_src(row0, valid);
-  int cur_seg = -1;
-  int prow0 = row0, pvalid = 0;
-
-  for (int i = 0; i < my_tiles; ++i) {
-    // the prefetched rows first (their loads are the oldest entries of the memory queue), then the previous tile's
-    // stores: no store sits between a load and the wait for it
-    write_as();
-    if (i > 0) {
-      store_out(prow0, pvalid);
-      if (a.stats != nullptr && (i & 7) == 0) flush_stats();
-    }
-    if (seg != cur_seg) {  // uniform; everyone passed the barrier that ended the previous tile
-      const int64_t boff = t_b_s[seg];
-      for (int n = tid; n < NOUT; n += NT) bias_s[n] = (a.bias != nullptr && boff >= 0) ? a.bias[boff + n] : 0.f;
-    }
-    __syncthreads();
-    int n2seg = nseg, n2row0 = nrow0, n2valid = nvalid;
-    if (i + 2 < my_tiles) tile_info(tile_at(i + 2), n2seg, n2row0, n2valid);
-    load_src(nrow0, nvalid);
-    if (seg != cur_seg) {
-      cur_seg = seg;
-      load_w(seg);
-    }
-    products();
-    __syncthreads();
-    prow0 = row0; pvalid = valid;
-    seg = nseg; row0 = nrow0; valid = nvalid;
-    nseg = n2seg; nrow0 = n2row0; nvalid = n2valid;
-  }
-  store_out(prow0, pvalid);
-  if (a.stats != nullptr) {
-    flush_stats();
-    __syncthreads();
-    for (int c = tid; c < 2 * NOUT; c += NT) {
-      const int which = c / NOUT, col = c - which * NOUT;
-      atomicAdd(a.stats + (size_t)2 * NOUT * (1 + (blockIdx.x % kBnReplicas)) + (size_t)which * NOUT + col,
-                stat_s[which][col]);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------------
-// The same product with the operand rows brought in by LDS-DMA, two tiles ahead.
-// fwd_h_kernel keeps ONE tile of prefetch per workgroup in registers: with two four-wave workgroups per CU an
-// iteration is load issue -> ~0.5 us of products -> wait for loads that were issued half a microsecond ago, i.e. it runs
-// at memory latency (~4 us per tile and workgroup, measured 150-190 us per launch = 3 TB/s).  Here the rows go
+// The product, with the operand rows brought in by LDS-DMA, two tiles ahead.
+// One tile of prefetch per workgroup in registers (the retired fwd_h_kernel) ran at memory latency: with two four-wave
+// workgroups per CU an iteration was load issue -> ~0.5 us of products -> wait for loads that were issued half a
+// microsecond ago (~4 us per tile and workgroup, measured 150-190 us per launch = 3 TB/s).  Here the rows go
 // HBM -> LDS directly (global_load_lds_dwordx4: no registers, per-lane source address, lane-linear LDS image) into a
 // ring of D + 1 tile buffers, D tiles ahead, and a tile is waited for with a COUNTED s_waitcnt: the memory queue is in
 // order, so "all but the youngest D * (stores of one tile) + (D - 1) * (loads of one tile)" is exactly "tile i has
@@ -354,10 +117,12 @@ __device__ __forceinline__ void glds16_h(const void* gsrc, unsigned lds_dst) {
 
 __device__ u32x4 g_fwdh_dump[512 * 256];  // where the rows beyond a ragged tile's end are stored: one slot per thread
 
-template <int NOPS, int KO, int NOUT, bool TRANS, int NPW>
+// NOPS operands of KO (padded) columns each, NOUT output columns, NPW = 3 bf16 pieces kept of every weight (exact to
+// 2^-24); TRANS: weights stored NOUT x k_in (nn.Linear)
+template <int NOPS, int KO, int NOUT, bool TRANS>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
-  constexpr int NT = 256, ROWS = 64, D = 2, NBUF = D + 1;
+  constexpr int NT = 256, ROWS = 64, D = 2, NBUF = D + 1, NPW = 3;
   constexpr int NC = NOPS * KO;
   constexpr int NKS = NC / 16;
   constexpr int TW = NOUT / 32, TPW = TW / 2;
@@ -620,29 +385,15 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
   }
 }
 
-template <int NOPS, int KO, int NOUT, bool TRANS, int NPW>
+template <int NOPS, int KO, int NOUT, bool TRANS>
 static int launch_fwd_hd(const FwdHTable& st, int n_tiles, const FwdHArgs& a, hipStream_t sm) {
   constexpr int RQ = NOPS * KO / 8;
   const size_t shmem = (size_t)3 * 64 * RQ * 16 + (size_t)64 * (NOUT * 2 + 16);
-  auto kern = fwd_hd_kernel<NOPS, KO, NOUT, TRANS, NPW>;
-  static bool attr_done = false;  // per instantiation
-  static int per_cu = 1;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) {
-      (void)hipGetLastError();
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), 256, shmem) != hipSuccess ||
-        occ < 1) {
-      (void)hipGetLastError();
-      occ = 2;
-    }
-    per_cu = std::min(occ, 2);  // (g_fwdh_dump is sized for 512 workgroups)
-    if (const char* e = getenv("GCMI_FWD_H_PER_CU")) per_cu = std::max(1, std::min(atoi(e), 2));
-    attr_done = true;
-  }
+  auto kern = fwd_hd_kernel<NOPS, KO, NOUT, TRANS>;
+  static LdsLimit lim;  // per instantiation
+  const int occ = raise_lds_limit(lim, reinterpret_cast<const void*>(kern), shmem, 256, shmem);
+  if (!occ) return GCMI_ERR_UNSUPPORTED;
+  const int per_cu = std::min(occ, 2);  // (g_fwdh_dump is sized for 512 workgroups)
   const int grid = std::min(n_tiles, 256 * per_cu);
 #ifdef GCMI_FWD_H_DIAG_BUILD
   static unsigned long long* d_diag = nullptr;
@@ -693,35 +444,6 @@ int fwd_weight_images(int32_t n_seg, const int64_t* w1_off, const int64_t* w2_of
   else
     hipLaunchKernelGGL(wprep_kernel<false>, dim3(blocks), dim3(256), 0, sm, st, d_w1, d_w2, k_in, ko, n_ops, n_out, wimg);
   GCMI_CHECK_LAUNCH("fwd weight images");
-  return GCMI_OK;
-}
-
-template <int NOPS, int KO, int NOUT, bool TRANS, int NPW>
-static int launch_fwd_h(const FwdHTable& st, int n_tiles, const FwdHArgs& a, hipStream_t sm) {
-  constexpr int NC = NOPS * KO;
-  const size_t shmem = (size_t)64 * (NC + 8) * 2 + (size_t)64 * (NOUT * 2 + 16);
-  auto kern = fwd_h_kernel<NOPS, KO, NOUT, TRANS, NPW>;
-  static bool attr_done = false;  // per instantiation
-  static int per_cu = 1;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) {
-      (void)hipGetLastError();
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(kern), 256, shmem) != hipSuccess ||
-        occ < 1) {
-      (void)hipGetLastError();
-      occ = 2;
-    }
-    per_cu = std::min(occ, 4);
-    if (const char* e = getenv("GCMI_FWD_H_PER_CU")) per_cu = std::max(1, std::min(atoi(e), 8));
-    attr_done = true;
-  }
-  const int grid = std::min(n_tiles, 256 * per_cu);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, sm, st, n_tiles, a, next_sweep_direction());
-  GCMI_CHECK_LAUNCH("fwd_h");
   return GCMI_OK;
 }
 
@@ -779,27 +501,9 @@ int fwd_h_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, 
     GCMI_CHECK_LAUNCH("fwd_h wprep");
     a.wimg = wimg;
   }
-  static const int npw = getenv("GCMI_FWD_H_PIECES") ? atoi(getenv("GCMI_FWD_H_PIECES")) : 3;
-  // operand rows by LDS-DMA two tiles ahead (default) or one tile ahead in registers (GCMI_FWD_H_DMA=0)
-  static const int dma = getenv("GCMI_FWD_H_DMA") ? atoi(getenv("GCMI_FWD_H_DMA")) : 1;
-  if (dma && npw != 2) {
-    if (conv80) return launch_fwd_hd<2, 80, 64, false, 3>(st, (int)tiles, a, sm);
-    if (conv) return launch_fwd_hd<2, 64, 64, false, 3>(st, (int)tiles, a, sm);
-    return launch_fwd_hd<1, 64, 128, true, 3>(st, (int)tiles, a, sm);
-  }
-  if (dma) {
-    if (conv80) return launch_fwd_hd<2, 80, 64, false, 2>(st, (int)tiles, a, sm);
-    if (conv) return launch_fwd_hd<2, 64, 64, false, 2>(st, (int)tiles, a, sm);
-    return launch_fwd_hd<1, 64, 128, true, 2>(st, (int)tiles, a, sm);
-  }
-  if (npw == 2) {
-    if (conv80) return launch_fwd_h<2, 80, 64, false, 2>(st, (int)tiles, a, sm);
-    if (conv) return launch_fwd_h<2, 64, 64, false, 2>(st, (int)tiles, a, sm);
-    return launch_fwd_h<1, 64, 128, true, 2>(st, (int)tiles, a, sm);
-  }
-  if (conv80) return launch_fwd_h<2, 80, 64, false, 3>(st, (int)tiles, a, sm);
-  if (conv) return launch_fwd_h<2, 64, 64, false, 3>(st, (int)tiles, a, sm);
-  return launch_fwd_h<1, 64, 128, true, 3>(st, (int)tiles, a, sm);
+  if (conv80) return launch_fwd_hd<2, 80, 64, false>(st, (int)tiles, a, sm);
+  if (conv) return launch_fwd_hd<2, 64, 64, false>(st, (int)tiles, a, sm);
+  return launch_fwd_hd<1, 64, 128, true>(st, (int)tiles, a, sm);
 }
 
 }  // namespace gcmi

@@ -590,24 +590,12 @@ static int launch_fwd(const FwdTable& st, int n_tiles, const FwdArgs& a, hipStre
   const size_t shmem = sizeof(float) * ROWS * (NC + 4) + sizeof(unsigned short) * (size_t)3 * NOUT * (NC + 8) +
                        sizeof(float) * ROWS * (NOUT + 8);
   auto kern = fwd_fused_kernel<ROWS, NOPS, KO, NOUT, TRANS>;
-  static bool attr_done = false;  // per instantiation
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) {
-      (void)hipGetLastError();
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    attr_done = true;
-  }
+  static LdsLimit lim;  // per instantiation
+  if (!raise_lds_limit(lim, reinterpret_cast<const void*>(kern), shmem)) return GCMI_ERR_UNSUPPORTED;
   const int grid = std::min(n_tiles, 256);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(512), shmem, sm, st, n_tiles, a, next_sweep_direction());
   GCMI_CHECK_LAUNCH("fwd_fused");
   return GCMI_OK;
-}
-
-static bool fwd_reg_on() {
-  static const int env = getenv("GCMI_FWD_REG") ? atoi(getenv("GCMI_FWD_REG")) : 1;
-  return env != 0;
 }
 
 template <int NOPS, int KO, int NOUT, bool TRANS>
@@ -615,15 +603,8 @@ static int launch_fwd_reg(const FwdTable& st, int n_tiles, const FwdArgs& a, hip
   constexpr int NC = NOPS * KO;
   const size_t shmem = sizeof(float) * 64 * (NC + 4);
   auto kern = fwd_reg_kernel<NOPS, KO, NOUT, TRANS>;
-  static bool attr_done = false;  // per instantiation
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) {
-      (void)hipGetLastError();
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    attr_done = true;
-  }
+  static LdsLimit lim;  // per instantiation
+  if (!raise_lds_limit(lim, reinterpret_cast<const void*>(kern), shmem)) return GCMI_ERR_UNSUPPORTED;
   const int grid = std::min(n_tiles, 512);  // two workgroups per CU (g_fwd_dump is sized for this)
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, sm, st, n_tiles, a, next_sweep_direction());
   GCMI_CHECK_LAUNCH("fwd_reg");
@@ -642,7 +623,7 @@ int fwd_fused_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
   if (!fwd_fused_on() || !fused_bwd_enabled() || n_seg > kWMaxSeg || (act != 0 && act != 1)) return GCMI_ERR_UNSUPPORTED;
   const bool two = d_a1 != nullptr && d_a2 != nullptr;
   const bool conv = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 32 && k1 <= 64;
-  const bool conv80 = fwd_reg_on() && two && !trans_w && n_out == 64 && k1 == k2 && k1 > 64 && k1 <= 80;
+  const bool conv80 = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 64 && k1 <= 80;
   const bool dense = !two && d_a1 != nullptr && trans_w && n_out == 128 && k1 > 32 && k1 <= 64;
   if (!conv && !dense && !conv80) return GCMI_ERR_UNSUPPORTED;
   if (!aligned16(d_a1) || lda1 % 4 || (two && (!aligned16(d_a2) || lda2 % 4)) || !aligned16(d_out) || ldo % 4 ||

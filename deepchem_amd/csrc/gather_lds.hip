@@ -178,10 +178,10 @@ __device__ __forceinline__ void stage_extra(char* dst, const Layout& L, const Wi
 }
 
 // ---------------------------------------------------------------- per-window compute phases
-// Rows this thread also needs from HBM in the compute phase (the old value of an accumulated output, the BatchNorm
-// input of the statistics) are requested for up to kPre elements up front, unconditionally from clamped addresses,
-// and used after the LDS work of all of them: the wait for them is also a wait for the LDS-DMA of the next window
-// (one counter, in order), which the loop would wait for at its top anyway.
+// Rows this thread also needs from HBM in the compute phase (the old value of an accumulated output) are requested for
+// up to kPre elements up front, unconditionally from clamped addresses, and used after the LDS work of all of them:
+// the wait for them is also a wait for the LDS-DMA of the next window (one counter, in order), which the loop would
+// wait for at its top anyway.
 constexpr int kPre = 4;
 
 struct NoState {};
@@ -307,60 +307,29 @@ struct MaxOp {
 
 // dx[k] = dout[k]*[arg[k]==0] + sum_j dout[i_j]*[arg[i_j] == rev_pos(k,j)+1]: tile = dout rows,
 // aux = arg rows of the window.
-// STATS: dx is the gradient w.r.t. a BatchNorm output; the column sums its backward needs (sum dx, sum dx*xhat with
-// xhat = (x - mean)*invstd of the BatchNorm input x, col_sums_kernel MODE 1 of bn.hip: same fp32 xhat, same fp64
-// products and sums) are taken here from the values about to be stored, so dx is not read again for them.  A
-// thread's column piece is the same for all its elements (WT % LPR == 0): eight fp64 accumulators per thread,
-// combined per workgroup at the end and added to the replicated accumulators with one atomic per column.
-template <bool STATS>
 struct MaxBwdOp {
   float* __restrict__ dx;
   int64_t lddx;
-  const float* __restrict__ x;      // STATS: BatchNorm input rows
-  int64_t ldx;
-  const float* __restrict__ mean;
-  const float* __restrict__ invstd;
-  double* __restrict__ sums;        // bn.hip scratch layout: [coef 2F][replica][sum F | sum of products F]
   // optional (bn_bwd_pool_impl): dx is needed only where the pooled BatchNorm sums are ill-conditioned
   const float* __restrict__ only_if_gamma;
   const float* __restrict__ only_if_beta;
+  using State = NoState;
   static constexpr bool kExtraTile = false;
   static constexpr int kEPP = 4;
   __device__ __forceinline__ bool skip(int n_feat) const {
     return only_if_gamma != nullptr && !bn_pool_ill_conditioned(only_if_gamma, only_if_beta, n_feat);
   }
-  struct State {
-    double s1[STATS ? 4 : 1], s2[STATS ? 4 : 1];
-  };
   template <int WT>
-  __device__ __forceinline__ void init(float* sh_lds, int n_feat, State& acc_) const {
-    if constexpr (STATS) {
-      for (int i = threadIdx.x; i < n_feat; i += WT) {
-        sh_lds[i] = mean[i];
-        sh_lds[256 + i] = invstd[i];
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc_.s1[q] = acc_.s2[q] = 0.0;
-    }
-  }
+  __device__ __forceinline__ void init(float*, int, State&) const {}
+  template <int WT>
+  __device__ __forceinline__ void finish(char*, int, State&) const {}
   template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float* sh_lds,
-                                      State& acc_) const {
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State&) const {
     const float4* tile = reinterpret_cast<const float4*>(buf);
     const uchar4* atile = reinterpret_cast<const uchar4*>(buf + L.tile_bytes);
     const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
     const int n16 = m.sb[kND] * LPR;
     for (int e0 = threadIdx.x; e0 < n16; e0 += kPre * WT) {
-      float4 xr[kPre];
-      if constexpr (STATS) {
-#pragma unroll
-        for (int k = 0; k < kPre; ++k) {
-          const int e = e0 + k * WT < n16 ? e0 + k * WT : n16 - 1;
-          const int slot = e / LPR;
-          const int c = e - slot * LPR;
-          xr[k] = *reinterpret_cast<const float4*>(x + (int64_t)row_of_slot(m, L.maxd, slot) * ldx + c * 4);
-        }
-      }
 #pragma unroll
       for (int k = 0; k < kPre; ++k) {
         const int e = e0 + k * WT;
@@ -388,39 +357,6 @@ struct MaxBwdOp {
           acc.w += a.w == want ? g.w : 0.f;
         }
         win_store4(dx + (int64_t)row * lddx + c * 4, acc);
-        if constexpr (STATS) {
-          const float4 mu = *reinterpret_cast<const float4*>(sh_lds + c * 4);
-          const float4 is = *reinterpret_cast<const float4*>(sh_lds + 256 + c * 4);
-          acc_.s1[0] += (double)acc.x; acc_.s2[0] += (double)acc.x * (double)((xr[k].x - mu.x) * is.x);
-          acc_.s1[1] += (double)acc.y; acc_.s2[1] += (double)acc.y * (double)((xr[k].y - mu.y) * is.y);
-          acc_.s1[2] += (double)acc.z; acc_.s2[2] += (double)acc.z * (double)((xr[k].z - mu.z) * is.z);
-          acc_.s1[3] += (double)acc.w; acc_.s2[3] += (double)acc.w * (double)((xr[k].w - mu.w) * is.w);
-        }
-      }
-    }
-  }
-  // after the last window (every thread of the workgroup arrives here): wave partials by shuffles over the lanes
-  // that share a column piece, the waves' partials meet in the (now idle) window buffers, one fp64 atomic per column
-  template <int WT>
-  __device__ __forceinline__ void finish(char* smem, int lpr, State& acc_) const {
-    if constexpr (STATS) {
-      const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-      double v[8] = {acc_.s1[0], acc_.s1[1], acc_.s1[2], acc_.s1[3], acc_.s2[0], acc_.s2[1], acc_.s2[2], acc_.s2[3]};
-      for (int o = lpr; o < 64; o <<= 1)  // lpr is 16 or 32: lanes l, l + lpr, ... hold the same piece
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] += __shfl_xor(v[i], o, 64);
-      __syncthreads();  // the window buffers are no longer read
-      double* red = reinterpret_cast<double*>(smem);  // [wave][piece][8]
-      if (lane < lpr)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) red[(wave * lpr + lane) * 8 + i] = v[i];
-      __syncthreads();
-      const int n_feat = lpr * 4;
-      for (int t = tid; t < 2 * n_feat; t += WT) {
-        const int which = t / n_feat, col = t - which * n_feat;
-        double tot = 0.0;
-        for (int w = 0; w < WT / 64; ++w) tot += red[(w * lpr + (col >> 2)) * 8 + which * 4 + (col & 3)];
-        atomicAdd(sums + (size_t)2 * n_feat * (1 + (blockIdx.x % kBnReplicas)) + (size_t)which * n_feat + col, tot);
       }
     }
   }
@@ -677,116 +613,6 @@ struct MaxOpH {
   }
 };
 
-// GraphPool of block l and GraphConv.sum_neigh of block l + 1 in ONE window pass (bf16 rows): the pooled rows of the
-// window are formed in a third LDS tile (and stored, with their arg-max bytes, as MaxOpH stores them), then every atom
-// sums its neighbours' pooled rows from that tile.  The pooled matrix is written once and NOT read back by a second
-// launch (-128 bytes per atom and one launch); the third tile is half the size it would be in fp32, so two workgroups
-// still share a CU.  Same values as MaxOpH followed by SumOpH (same candidates in the same order, the same rounded
-// pooled values summed in the same neighbour order).  Oversized windows take the two separate ops over their own rows.
-template <bool BN>
-struct MaxSumOpH {
-  const float* __restrict__ scale;
-  const float* __restrict__ shift;
-  bf16_t* __restrict__ out;   // pooled rows
-  int64_t ldo;
-  uint8_t* __restrict__ arg;
-  bf16_t* __restrict__ s;     // neighbour sums of the pooled rows
-  int64_t lds;
-  struct State {
-    char* extra;  // the third tile: [slot][LPR] 16-byte pieces of pooled rows
-  };
-  static constexpr bool kExtraTile = true;
-  static constexpr int kEPP = 8;
-  __device__ __forceinline__ bool skip(int) const { return false; }
-  template <int WT>
-  __device__ __forceinline__ void init(float* sh_lds, int n_feat, State&) const {
-    if (BN)
-      for (int i = threadIdx.x; i < n_feat; i += WT) {
-        sh_lds[i] = scale[i];
-        sh_lds[256 + i] = shift[i];
-      }
-  }
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float* sh_lds,
-                                      State& st) const {
-    const uint4* tile = reinterpret_cast<const uint4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    uint4* t2 = reinterpret_cast<uint4*>(st.extra);
-    const int n16 = m.sb[kND] * LPR;
-    // ---- stage 1: the pooled rows of the window -> HBM and the third tile
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float sc[8], sh[8];
-      if (BN) {
-        const float4 a0 = *reinterpret_cast<const float4*>(sh_lds + c * 8);
-        const float4 a1 = *reinterpret_cast<const float4*>(sh_lds + c * 8 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(sh_lds + 256 + c * 8);
-        const float4 b1 = *reinterpret_cast<const float4*>(sh_lds + 256 + c * 8 + 4);
-        sc[0] = a0.x; sc[1] = a0.y; sc[2] = a0.z; sc[3] = a0.w; sc[4] = a1.x; sc[5] = a1.y; sc[6] = a1.z; sc[7] = a1.w;
-        sh[0] = b0.x; sh[1] = b0.y; sh[2] = b0.z; sh[3] = b0.w; sh[4] = b1.x; sh[5] = b1.y; sh[6] = b1.z; sh[7] = b1.w;
-      }
-      float best[8];
-      widen8(tile[e], best);  // self first
-      unsigned char ba[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        if (BN) best[q] = fmaf(best[q], sc[q], sh[q]);
-        ba[q] = 0;
-      }
-      for (int j = 0; j < d; ++j) {
-        const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-        float v[8];
-        widen8(tile[sl * LPR + c], v);
-        const unsigned char a = (unsigned char)(j + 1);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (BN) v[q] = fmaf(v[q], sc[q], sh[q]);
-          if (v[q] > best[q]) { best[q] = v[q]; ba[q] = a; }  // strict >: the first maximum wins
-        }
-      }
-      uint4 o;
-      o.x = pack_bf16x2(best[0], best[1]); o.y = pack_bf16x2(best[2], best[3]);
-      o.z = pack_bf16x2(best[4], best[5]); o.w = pack_bf16x2(best[6], best[7]);
-      *reinterpret_cast<uint4*>(out + (int64_t)row * ldo + c * 8) = o;
-      t2[e] = o;
-      if (arg) {
-        uint2 av;
-        av.x = (unsigned)ba[0] | ((unsigned)ba[1] << 8) | ((unsigned)ba[2] << 16) | ((unsigned)ba[3] << 24);
-        av.y = (unsigned)ba[4] | ((unsigned)ba[5] << 8) | ((unsigned)ba[6] << 16) | ((unsigned)ba[7] << 24);
-        *reinterpret_cast<uint2*>(arg + (int64_t)row * (LPR * 8) + c * 8) = av;
-      }
-    }
-    __syncthreads();
-    // ---- stage 2: every atom sums its neighbours' pooled rows
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float acc[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = 0.f;
-      for (int j = 0; j < d; ++j) {
-        const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-        float v[8];
-        widen8(t2[sl * LPR + c], v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] += v[q];
-      }
-      uint4 o;
-      o.x = pack_bf16x2(acc[0], acc[1]); o.y = pack_bf16x2(acc[2], acc[3]);
-      o.z = pack_bf16x2(acc[4], acc[5]); o.w = pack_bf16x2(acc[6], acc[7]);
-      *reinterpret_cast<uint4*>(s + (int64_t)row * lds + c * 8) = o;
-    }
-    // (the walker's barrier at the top of the next window comes before the third tile is written again)
-  }
-};
-
 // ---------------------------------------------------------------- gradient streams in bf16 (storage == 2)
 // The gradients that travel between kernels (dpool, dy, dS, dXs) as bf16 rows: the same ops as MaxBwdOp, SumOp<true> and
 // SumAccMaxBwdOp over pieces of eight elements, sums in fp32, one rounding at the store.  The arg-max bytes of a piece
@@ -971,119 +797,6 @@ struct SumAccMaxBwdOpH {
 // ---------------------------------------------------------------- the persistent window walker
 // Workgroups [0, g_norm) walk the ordinary windows double-buffered; workgroups [g_norm, gridDim)
 // walk the oversized windows (one big molecule each) using both buffers as one.
-// GraphGather over the windows: out[b] = act([sum over the atoms of molecule b | max over them]) of the (folded-BatchNorm)
-// rows (layers.py:6450-6479), with the arg-max rows and the raw sums the BatchNorm backward wants -- what
-// readout_fwd_kernel (readout.hip) computes walking a molecule's <= 11 row runs in HBM, at 3.3 TB/s.  A window holds
-// WHOLE molecules, so once its rows are in LDS every molecule of it is reduced from LDS: a thread = (molecule, 16-byte
-// column piece), the molecule's rows in ascending row order (degree block by degree block: the order of
-// readout_fwd_kernel, so sums are bit-identical and the first maximum wins as there).  The molecules of a window are
-// the membership of its first and last rows; their row runs come from d_mol_runs.  (Those few global loads sit in the
-// compute phase and wait behind the next window's DMA like the kPre loads of the accumulating ops.)
-// F = the row width the outputs are laid out for; the tile holds the columns [col0, col0 + LPR * kEPP) of the rows (fp32
-// rows of 128 columns do not fit two window buffers: two passes of 64).
-template <bool BN, bool HB>
-struct ReadoutOp {
-  const float* __restrict__ scale;
-  const float* __restrict__ shift;
-  const int32_t* __restrict__ runs;
-  const int32_t* __restrict__ membership;
-  int n_deg, act, F, col0;
-  float* __restrict__ out;
-  int64_t ldo;
-  int32_t* __restrict__ arg;
-  float* __restrict__ rawsum;
-  static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = HB ? 8 : 4;
-  using State = NoState;
-  __device__ __forceinline__ bool skip(int) const { return false; }
-  template <int WT>
-  __device__ __forceinline__ void init(float* sh_lds, int n_cols, State&) const {
-    if (BN)
-      for (int i = threadIdx.x; i < n_cols; i += WT) {
-        sh_lds[i] = scale[col0 + i];
-        sh_lds[256 + i] = shift[col0 + i];
-      }
-  }
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float* sh_lds, State&) const {
-    constexpr int V = kEPP;
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    // the window's molecules
-    int m0 = INT_MAX, m1 = -1;
-#pragma unroll
-    for (int d = 0; d < kND; ++d) {
-      if (d <= L.maxd && m.sb[d + 1] > m.sb[d]) {
-        const int a = membership[m.rb[d] + m.sb[d]], b = membership[m.rb[d] + m.sb[d + 1] - 1];
-        m0 = a < m0 ? a : m0;
-        m1 = b > m1 ? b : m1;
-      }
-    }
-    const int n_items = (m1 - m0 + 1) * LPR;
-    for (int e = threadIdx.x; e < n_items; e += WT) {
-      const int mi = e / LPR;
-      const int c = e - mi * LPR;
-      const int b = m0 + mi;
-      const int2* rb = reinterpret_cast<const int2*>(runs + (int64_t)b * n_deg * 2);
-      int2 run[kND];
-#pragma unroll
-      for (int d = 0; d < kND; ++d) run[d] = d < n_deg ? rb[d] : make_int2(0, 0);
-      float sc[V], sh[V], sum[V], mx[V], raw[V], rawmx[V];
-      int am[V];
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        sc[q] = BN ? sh_lds[c * V + q] : 1.f;
-        sh[q] = BN ? sh_lds[256 + c * V + q] : 0.f;
-        raw[q] = 0.f; rawmx[q] = 0.f; sum[q] = 0.f;
-        mx[q] = -INFINITY;
-        am[q] = -1;
-      }
-#pragma unroll
-      for (int d = 0; d < kND; ++d) {
-        for (int r = run[d].x; r < run[d].y; ++r) {
-          const int slot = r - m.rb[d];
-          float v[V];
-          if constexpr (HB) {
-            widen8(reinterpret_cast<const uint4*>(buf)[slot * LPR + c], v);
-          } else {
-            const float4 t = reinterpret_cast<const float4*>(buf)[slot * LPR + c];
-            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-          }
-#pragma unroll
-          for (int q = 0; q < V; ++q) {
-            const float a = BN ? fmaf(v[q], sc[q], sh[q]) : v[q];
-            raw[q] += v[q];
-            sum[q] += a;
-            if (a > mx[q]) { mx[q] = a; am[q] = r; rawmx[q] = v[q]; }
-          }
-        }
-      }
-      float* o = out + (int64_t)b * ldo + col0 + c * V;
-#pragma unroll
-      for (int h = 0; h < V / 4; ++h) {
-        f32x4 so, mo;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          so[q] = act == 1 ? tanhf(sum[4 * h + q]) : sum[4 * h + q];
-          mo[q] = act == 1 ? tanhf(mx[4 * h + q]) : mx[4 * h + q];
-        }
-        *reinterpret_cast<f32x4*>(o + 4 * h) = so;
-        *reinterpret_cast<f32x4*>(o + F + 4 * h) = mo;
-        if (arg)
-          *reinterpret_cast<i32x4*>(arg + (int64_t)b * F + col0 + c * V + 4 * h) =
-              i32x4{am[4 * h], am[4 * h + 1], am[4 * h + 2], am[4 * h + 3]};
-        if (rawsum) {  // [sum of the rows | value of the arg-max row], both BEFORE the folded BatchNorm
-          float* rs = rawsum + (int64_t)b * 2 * F + col0 + c * V + 4 * h;
-          *reinterpret_cast<f32x4*>(rs) = f32x4{raw[4 * h], raw[4 * h + 1], raw[4 * h + 2], raw[4 * h + 3]};
-          *reinterpret_cast<f32x4*>(rs + F) = f32x4{rawmx[4 * h], rawmx[4 * h + 1], rawmx[4 * h + 2], rawmx[4 * h + 3]};
-        }
-      }
-    }
-  }
-};
-
 // ops whose third tile is filled by the DMA, one per window buffer (kExtraDma)
 template <class Op>
 static constexpr auto extra_dma(int) -> decltype(Op::kExtraDma) { return Op::kExtraDma; }
@@ -1168,11 +881,6 @@ static bool windows_disabled() {
   return v == 1;
 }
 
-static int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v && *v ? atoi(v) : dflt;
-}
-
 // (n_feat counts FLOATS per tile row: a bf16 row of n elements is a tile row of n / 2 "floats")
 // aux: 0 none, 4 / 8 = aux bytes per 16-byte piece (fp32 / bf16 rows; stage())
 static Layout make_layout(int alloc, int ecap, int maxd, int n_feat, int aux) {
@@ -1217,26 +925,29 @@ bool win_usable(const gcmi_graph* g, int n_feat, bool aux) {
   return make_plan(g, n_feat, aux ? 4 : 0).ok;
 }
 
-// bytes of an op's third LDS tile in units of the window tile (1 unless the op says otherwise: kExtraScale)
+// threads per workgroup: what an op asks for (kThreads), 512 when it has no preference.  The two-stage ops
+// (kExtraTile): fp32 tiles hold one workgroup per CU by LDS, so make it a full one (1 024 threads: 292 us against 346
+// at 512); bf16 tiles are half the size and two 512-thread workgroups share a CU (288 us against 367 at 1 024).
 template <class Op>
-static constexpr auto extra_scale(int) -> decltype(Op::kExtraScale) { return Op::kExtraScale; }
+static constexpr auto op_threads(int) -> decltype(Op::kThreads) { return Op::kThreads; }
 template <class Op>
-static constexpr int extra_scale(long) { return 1; }
+static constexpr int op_threads(long) { return 512; }
+template <class Op>
+static constexpr int win_threads() {
+  if constexpr (Op::kExtraTile) return Op::kEPP == 8 ? 512 : 1024;
+  else return op_threads<Op>(0);
+}
 
-template <int WT, int LPR, bool AUX, class Op>
-static int launch_wt(const gcmi_graph* g, const WinPlan& p, const char* x, int64_t ldx, const uint8_t* aux,
-                     const Op& op, hipStream_t st, const char* what, int which = 0) {  // which: 0 all windows,
-                                                                                        // 1 ordinary, 2 oversized only
+// which: 0 all windows, 1 ordinary, 2 oversized only
+template <int LPR, bool AUX, class Op>
+static int launch_lpr(const gcmi_graph* g, const WinPlan& p, const char* x, int64_t ldx, const uint8_t* aux,
+                      const Op& op, hipStream_t st, const char* what, int which) {
+  constexpr int WT = win_threads<Op>();
   auto kern = win_kernel<WT, LPR, AUX, Op>;
-  static bool attr_done = false;  // per instantiation
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            kLdsPerCU) != hipSuccess) {
-      (void)hipGetLastError();
-      set_error("%s: cannot raise the dynamic LDS limit", what);
-      return GCMI_ERR_LAUNCH;
-    }
-    attr_done = true;
+  static LdsLimit lim;  // per instantiation
+  if (!raise_lds_limit(lim, reinterpret_cast<const void*>(kern), kLdsPerCU)) {
+    set_error("%s: cannot raise the dynamic LDS limit", what);
+    return GCMI_ERR_LAUNCH;
   }
   const int n_norm = g->n_win - g->n_win_big;
   size_t shmem = p.shmem;
@@ -1245,44 +956,19 @@ static int launch_wt(const gcmi_graph* g, const WinPlan& p, const char* x, int64
       set_error("%s: oversized windows are not handled by the two-stage form", what);
       return GCMI_ERR_UNSUPPORTED;
     }
-    shmem += (size_t)p.L.tile_bytes * extra_scale<Op>(0);
+    shmem += (size_t)p.L.tile_bytes * Op::kExtraScale;  // the third tile, in units of the window tile
     if (shmem > (size_t)kLdsPerCU) return GCMI_ERR_UNSUPPORTED;
   }
   const int by_lds = (int)((size_t)kLdsPerCU / shmem);
   const int by_threads = 2048 / WT;
-  const int per_cu = std::max(1, std::min(env_int("GCMI_WIN_PER_CU", 8), std::min(by_lds, by_threads)));
+  const int per_cu = std::max(1, std::min(8, std::min(by_lds, by_threads)));
   const int g_norm = which == 2 ? 0 : std::min(n_norm, 256 * per_cu);
   const int g_big = which == 1 ? 0 : std::min(g->n_win_big, 64);
   if (g_norm + g_big == 0) return GCMI_OK;
   hipLaunchKernelGGL(kern, dim3(g_norm + g_big), dim3(WT), shmem, st, g->d_win_meta, g->d_win_edges, n_norm,
-                     g->n_win, g_norm, p.L, p.Lbig, x, ldx, aux, op, next_sweep_direction_windows());
+                     g->n_win, g_norm, p.L, p.Lbig, x, ldx, aux, op, next_sweep_direction());
   GCMI_CHECK_LAUNCH(what);
   return GCMI_OK;
-}
-
-// threads per workgroup an op asks for (kThreads) unless GCMI_WIN_THREADS says otherwise; 512 when it has no preference
-template <class Op>
-static constexpr auto op_threads(int) -> decltype(Op::kThreads) { return Op::kThreads; }
-template <class Op>
-static constexpr int op_threads(long) { return 512; }
-
-template <int LPR, bool AUX, class Op>
-static int launch_lpr(const gcmi_graph* g, const WinPlan& p, const char* x, int64_t ldx, const uint8_t* aux,
-                      const Op& op, hipStream_t st, const char* what, int which) {
-  static const int wt_env = env_int("GCMI_WIN_THREADS", 0);
-  const int wt = wt_env ? wt_env : op_threads<Op>(0);
-  if constexpr (Op::kExtraTile) {
-    // fp32 tiles: one workgroup per CU by LDS, so make it a full one (1 024 threads: 292 us against 346 at 512).  bf16
-    // tiles are half the size and two 512-thread workgroups share a CU: 288 us against 367 at 1 024 (SumAccMaxBwdOpH)
-    static const int wt2 = env_int("GCMI_WIN_THREADS_TWO_STAGE", 0);
-    const int want = wt2 ? wt2 : (Op::kEPP == 8 ? 512 : 1024);
-    if (want == 1024) return launch_wt<1024, LPR, AUX, Op>(g, p, x, ldx, aux, op, st, what, which);
-    if (want == 768) return launch_wt<768, LPR, AUX, Op>(g, p, x, ldx, aux, op, st, what, which);
-    if (want == 512) return launch_wt<512, LPR, AUX, Op>(g, p, x, ldx, aux, op, st, what, which);
-  }
-  if (wt == 1024) return launch_wt<1024, LPR, AUX, Op>(g, p, x, ldx, aux, op, st, what, which);
-  if (wt == 256) return launch_wt<256, LPR, AUX, Op>(g, p, x, ldx, aux, op, st, what, which);
-  return launch_wt<512, LPR, AUX, Op>(g, p, x, ldx, aux, op, st, what, which);
 }
 
 template <bool AUX, class Op>
@@ -1316,47 +1002,6 @@ static int launch_h(const gcmi_graph* g, int n_feat, const bf16_t* x, int64_t ld
   return GCMI_ERR_UNSUPPORTED;
 }
 
-// GraphGather forward over the windows (ReadoutOp): GCMI_ERR_UNSUPPORTED where the window form does not apply -- no
-// window plan, molecules without atoms (the plan says how many molecules its windows cover: gcmi_graph.win_reserved[0]),
-// other widths than 128 columns -- and the caller walks the row runs instead (readout.hip).
-int win_readout(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_feat, const float* d_scale, const float* d_shift,
-                int act, float* d_out, int64_t ldo, int32_t* d_arg, float* d_rawsum, int x_bf16, hipStream_t st) {
-  // Kept, OFF (GCMI_READOUT_WINDOWS=1 turns it on; results identical, tests pass with it): measured 311 + 297 us for the
-  // two fp32 passes against readout_fwd_kernel's 187, and 737 us against 130 on bf16 rows.  A window is ~25 molecules, so
-  // the compute phase has 25 x 16 serial chains of ~18 rows for 512 threads at ONE workgroup per CU (LDS), and its
-  // run-bound loads wait behind the next window's DMA; the row-run walk keeps thousands of molecules in flight per CU.
-  static const bool on = getenv("GCMI_READOUT_WINDOWS") && atoi(getenv("GCMI_READOUT_WINDOWS")) == 1;
-  if (!on || n_feat != 128 || g->win_reserved[0] != g->n_mols || g->n_mols <= 0 || g->d_membership == nullptr ||
-      g->d_mol_runs == nullptr || (reinterpret_cast<uintptr_t>(g->d_mol_runs) & 7u) || ldo % 4 || !aligned16(d_out) ||
-      (d_arg && !aligned16(d_arg)) || (d_rawsum && !aligned16(d_rawsum)))
-    return GCMI_ERR_UNSUPPORTED;
-  const bool bn = d_scale != nullptr;
-  if (x_bf16) {
-    if (!win_usable_h(g, 128) || (reinterpret_cast<uintptr_t>(d_x) & 15u) || ldx % 8) return GCMI_ERR_UNSUPPORTED;
-    const bf16_t* xh = reinterpret_cast<const bf16_t*>(d_x);
-    if (bn) {
-      ReadoutOp<true, true> op{d_scale, d_shift, g->d_mol_runs, g->d_membership, g->max_deg + 1, act, 128, 0, d_out, ldo, d_arg, d_rawsum};
-      return launch_h<ReadoutOp<true, true>>(g, 128, xh, ldx, op, st, "win_readout");
-    }
-    ReadoutOp<false, true> op{nullptr, nullptr, g->d_mol_runs, g->d_membership, g->max_deg + 1, act, 128, 0, d_out, ldo, d_arg, d_rawsum};
-    return launch_h<ReadoutOp<false, true>>(g, 128, xh, ldx, op, st, "win_readout");
-  }
-  // fp32 rows: two passes of 64 columns (512-byte rows do not fit two window buffers)
-  if (!win_usable(g, 64, false) || !aligned16(d_x) || ldx % 4) return GCMI_ERR_UNSUPPORTED;
-  for (int col0 = 0; col0 < 128; col0 += 64) {
-    int rc;
-    if (bn) {
-      ReadoutOp<true, false> op{d_scale, d_shift, g->d_mol_runs, g->d_membership, g->max_deg + 1, act, 128, col0, d_out, ldo, d_arg, d_rawsum};
-      rc = launch<false, ReadoutOp<true, false>>(g, 64, d_x + col0, ldx, nullptr, op, st, "win_readout");
-    } else {
-      ReadoutOp<false, false> op{nullptr, nullptr, g->d_mol_runs, g->d_membership, g->max_deg + 1, act, 128, col0, d_out, ldo, d_arg, d_rawsum};
-      rc = launch<false, ReadoutOp<false, false>>(g, 64, d_x + col0, ldx, nullptr, op, st, "win_readout");
-    }
-    if (rc) return rc;
-  }
-  return GCMI_OK;
-}
-
 bool win_has_width(int n_feat) { return n_feat == 64 || n_feat == 76 || n_feat == 128; }
 
 int win_gather_sum(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_feat, float* d_s,
@@ -1381,13 +1026,13 @@ int win_gather_max(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_fea
 
 int win_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat,
                        const uint8_t* d_arg, float* d_dx, int64_t lddx, hipStream_t st) {
-  MaxBwdOp<false> op{d_dx, lddx, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+  MaxBwdOp op{d_dx, lddx, nullptr, nullptr};
   return launch<true>(g, n_feat, d_dout, lddo, d_arg, op, st, "win_gather_max_bwd");
 }
 
 int win_gather_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
                               float* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, hipStream_t st) {
-  MaxBwdOp<false> op{d_dx, lddx, nullptr, 0, nullptr, nullptr, nullptr, d_gamma, d_beta};
+  MaxBwdOp op{d_dx, lddx, d_gamma, d_beta};
   return launch<true>(g, n_feat, d_dout, lddo, d_arg, op, st, "win_gather_max_bwd (conditional)");
 }
 
@@ -1458,42 +1103,6 @@ int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const bf16_t* d_ds, int64_t
   return launch_h<MaxBwdOpH, true>(g, n_feat, d_dxs, lddxs, mb, st, "win_gather_max_bwd (bf16, oversized windows)", 2, d_arg);
 }
 
-// GraphPool of this block + sum_neigh of the next in one window pass (MaxSumOpH); the oversized windows (a molecule
-// above the window cap each) take the two separate ops over their own rows
-bool win_max_sum_usable_h(const gcmi_graph* g, int n_feat) {
-  // measured on the 65 536-molecule step: 288 us for the fused pass against 196 + 72 for the two it replaces (the second
-  // stage waits behind a barrier for the whole window's pooled rows) -- 153 MB less traffic, 20 us more time: off by
-  // default, GCMI_FUSED_POOL_SUM=1 switches it on
-  static const bool on = getenv("GCMI_FUSED_POOL_SUM") && atoi(getenv("GCMI_FUSED_POOL_SUM")) != 0;
-  if (!on || !win_usable_h(g, n_feat)) return false;
-  const WinPlan p = make_plan(g, n_feat / 2, 0);
-  return p.shmem + (size_t)p.L.tile_bytes <= (size_t)kLdsPerCU;
-}
-
-int win_gather_max_sum_h(const gcmi_graph* g, const bf16_t* d_x, int64_t ldx, int n_feat, const float* d_scale,
-                         const float* d_shift, bf16_t* d_out, int64_t ldo, uint8_t* d_arg, bf16_t* d_s, int64_t lds,
-                         hipStream_t st) {
-  int rc;
-  if (d_scale) {
-    MaxSumOpH<true> op{d_scale, d_shift, d_out, ldo, d_arg, d_s, lds};
-    rc = launch_h(g, n_feat, d_x, ldx, op, st, "win_gather_max_sum (bf16)", 1);
-  } else {
-    MaxSumOpH<false> op{nullptr, nullptr, d_out, ldo, d_arg, d_s, lds};
-    rc = launch_h(g, n_feat, d_x, ldx, op, st, "win_gather_max_sum (bf16)", 1);
-  }
-  if (rc || g->n_win_big == 0) return rc;
-  if (d_scale) {
-    MaxOpH<true> mx{d_scale, d_shift, d_out, ldo, d_arg};
-    rc = launch_h(g, n_feat, d_x, ldx, mx, st, "win_gather_max (bf16, oversized windows)", 2);
-  } else {
-    MaxOpH<false> mx{nullptr, nullptr, d_out, ldo, d_arg};
-    rc = launch_h(g, n_feat, d_x, ldx, mx, st, "win_gather_max (bf16, oversized windows)", 2);
-  }
-  if (rc) return rc;
-  SumOpH sm{d_s, lds};
-  return launch_h(g, n_feat, d_out, ldo, sm, st, "win_gather_sum (bf16, oversized windows)", 2);
-}
-
 // dy = GraphPool backward of (dXs + gather of dS), dX kept in LDS only.  GCMI_ERR_UNSUPPORTED: oversized windows in
 // the batch, or no LDS for the third tile.
 bool win_two_stage_usable(const gcmi_graph* g, int n_feat) {
@@ -1513,20 +1122,8 @@ int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ld
   SumOp<true> acc{d_dxs, lddxs};
   rc = launch<false>(g, n_feat, d_ds, ldds, nullptr, acc, st, "win_gather_sum (accumulate, oversized windows)", 2);
   if (rc) return rc;
-  MaxBwdOp<false> mb{d_dy, lddy, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+  MaxBwdOp mb{d_dy, lddy, nullptr, nullptr};
   return launch<true>(g, n_feat, d_dxs, lddxs, d_arg, mb, st, "win_gather_max_bwd (oversized windows)", 2);
-}
-
-// threads per workgroup of the window kernels must be a multiple of the row's 16-byte pieces for the statistics form
-bool win_stats_usable(const gcmi_graph* g, int n_feat) {
-  return (n_feat == 64 || n_feat == 128) && win_usable(g, n_feat, true);
-}
-
-int win_gather_max_bwd_stats(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
-                             float* d_dx, int64_t lddx, const float* d_x, int64_t ldx, const float* d_mean,
-                             const float* d_invstd, double* d_sums, hipStream_t st) {
-  MaxBwdOp<true> op{d_dx, lddx, d_x, ldx, d_mean, d_invstd, d_sums, nullptr, nullptr};
-  return launch<true>(g, n_feat, d_dout, lddo, d_arg, op, st, "win_gather_max_bwd (statistics)");
 }
 
 }  // namespace gcmi

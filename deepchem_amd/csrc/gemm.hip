@@ -186,44 +186,41 @@ seg_gemm_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1,
 // while the MFMAs of the current chunk run, so HBM/L2 latency overlaps the matrix work of the
 // same workgroup instead of relying on other workgroups to cover it.
 
-template <bool TRANS, int NT, int BMT, bool FRAG, int KCT>
+template <bool TRANS, int NT>
 __global__ void __launch_bounds__(kGBlock)
 seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1,
                  const float* __restrict__ w1, const float* __restrict__ a2, int64_t lda2, int k2,
                  const float* __restrict__ w2, const float* __restrict__ bias, int n_out, int act,
-                 float* __restrict__ out, int64_t ldo, int diag) {
+                 float* __restrict__ out, int64_t ldo) {
   constexpr int BN2 = NT * 32;
-  constexpr int BPASS = (KCT * BN2) / kGBlock;  // B elements per thread per chunk
-  constexpr int LPRW = KCT / 4;          // lanes per A row (16 bytes each)
+  constexpr int BPASS = (KC * BN2) / kGBlock;  // B elements per thread per chunk
+  constexpr int LPRW = KC / 4;          // lanes per A row (16 bytes each)
   constexpr int RPP = kGBlock / LPRW;    // A rows per pass
-  constexpr int APASS = BMT / RPP;   // A float4 per thread per chunk
-  constexpr int WR = BMT / 32;      // wave rows: BMT=128 -> 4 waves x 32 rows; BMT=64 -> 2 x 2 waves
-  constexpr int WC = 4 / WR;        // waves side by side along the columns
-  constexpr int NTW = NT / WC > 0 ? NT / WC : 1;  // 32-column tiles per wave
-  __shared__ float As[BMT][KCT + 1];
-  __shared__ float Bs[KCT][BN2 + 1];
+  constexpr int APASS = BM2 / RPP;   // A float4 per thread per chunk
+  __shared__ float As[BM2][KC + 1];
+  __shared__ float Bs[KC][BN2 + 1];
   const int b = blockIdx.x;
   const int s = seg_of_tile(st, b);
-  const int row0 = pick_seg(st.seg_begin, s) + (b - pick_seg(st.tile_start, s)) * BMT;
+  const int row0 = pick_seg(st.seg_begin, s) + (b - pick_seg(st.tile_start, s)) * BM2;
   const int seg_end = pick_seg(st.seg_end, s);
-  const int rows_valid = (seg_end - row0 < BMT) ? seg_end - row0 : BMT;
+  const int rows_valid = (seg_end - row0 < BM2) ? seg_end - row0 : BM2;
   const int col0 = blockIdx.y * BN2;
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int lane = tid & 63;
   const int half = lane >> 5;
-  const int wrow = wave % WR, wcol = wave / WR;
-  f32x16 acc[NTW];
+  const int wrow = wave;  // 4 waves x 32 rows, each over all NT 32-column tiles
+  f32x16 acc[NT];
 #pragma unroll
-  for (int t = 0; t < NTW; ++t)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
 
   const int64_t woff1 = pick_seg(st.w1_off, s), woff2 = pick_seg(st.w2_off, s);
   const bool on1 = a1 != nullptr && w1 != nullptr && woff1 >= 0;
   const bool on2 = a2 != nullptr && w2 != nullptr && woff2 >= 0;
-  const int n1 = on1 ? (k1 + KCT - 1) / KCT : 0;
-  const int n2 = on2 ? (k2 + KCT - 1) / KCT : 0;
+  const int n1 = on1 ? (k1 + KC - 1) / KC : 0;
+  const int n2 = on2 ? (k2 + KC - 1) / KC : 0;
   const int nchunks = n1 + n2;
 
   // Prefetch registers.  Loads are UNCONDITIONAL from clamped (always valid) addresses and
@@ -239,7 +236,7 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
     const int64_t lda = first ? lda1 : lda2;
     const int K = first ? k1 : k2;
     const float* w = first ? w1 + woff1 : w2 + woff2;
-    const int k0 = (first ? c : c - n1) * KCT;
+    const int k0 = (first ? c : c - n1) * KC;
     pend_k0 = k0;
     pend_K = K;
     const int kcol = k0 + (tid % LPRW) * 4;
@@ -260,11 +257,11 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
         rb[pass] = w[(int64_t)kkc * n_out + jc];
       }
     } else {  // w is n_out x K
-      const int kk = k0 + (tid % KCT);
+      const int kk = k0 + (tid % KC);
       const int kkc = kk < K ? kk : K - 1;
 #pragma unroll
       for (int pass = 0; pass < BPASS; ++pass) {
-        const int j = col0 + tid / KCT + pass * (kGBlock / KCT);
+        const int j = col0 + tid / KC + pass * (kGBlock / KC);
         const int jc = j < n_out ? j : n_out - 1;
         rb[pass] = w[(int64_t)jc * K + kkc];
       }
@@ -291,11 +288,11 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
         Bs[kk][j] = (jok && pend_k0 + kk < pend_K) ? rb[pass] : 0.f;
       }
     } else {
-      const int kk = tid % KCT;
+      const int kk = tid % KC;
       const bool kok = pend_k0 + kk < pend_K;
 #pragma unroll
       for (int pass = 0; pass < BPASS; ++pass) {
-        const int j = tid / KCT + pass * (kGBlock / KCT);
+        const int j = tid / KC + pass * (kGBlock / KC);
         Bs[kk][j] = (kok && col0 + j < n_out) ? rb[pass] : 0.f;
       }
     }
@@ -306,44 +303,30 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
     sstore();
     __syncthreads();
     for (int c = 0; c < nchunks; ++c) {
-      if (c + 1 < nchunks && !(diag & 2)) gload(c + 1);  // in flight while the matrix pipe works on chunk c
-      if (!(diag & 1)) {
-        if constexpr (FRAG) {
-          // fragments of half a chunk first, then the MFMAs back to back: the LDS latency is
-          // paid once per 8 k-steps instead of once per k-step
+      if (c + 1 < nchunks) gload(c + 1);  // in flight while the matrix pipe works on chunk c
+      // fragments of half a chunk first, then the MFMAs back to back: the LDS latency is
+      // paid once per 8 k-steps instead of once per k-step
 #pragma unroll
-          for (int h = 0; h < KCT / 16; ++h) {
-            float af[8], bf[NTW][8];
+      for (int h = 0; h < KC / 16; ++h) {
+        float af[8], bf[NT][8];
 #pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              const int kk = h * 16 + q * 2;
-              af[q] = As[wrow * 32 + (lane & 31)][kk + half];
+        for (int q = 0; q < 8; ++q) {
+          const int kk = h * 16 + q * 2;
+          af[q] = As[wrow * 32 + (lane & 31)][kk + half];
 #pragma unroll
-              for (int t = 0; t < NTW; ++t) bf[t][q] = Bs[kk + half][(wcol * NTW + t) * 32 + (lane & 31)];
-            }
-            __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead of the MFMAs
-#pragma unroll
-            for (int q = 0; q < 8; ++q)
-#pragma unroll
-              for (int t = 0; t < NTW; ++t)
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[t][q], af[q], acc[t], 0, 0, 0);
-          }
-        } else {
-#pragma unroll
-          for (int kk = 0; kk < KCT; kk += 2) {
-            const float av = As[wrow * 32 + (lane & 31)][kk + half];
-#pragma unroll
-            for (int t = 0; t < NTW; ++t) {
-              const float bv = Bs[kk + half][(wcol * NTW + t) * 32 + (lane & 31)];
-              // operands swapped on purpose: the accumulator holds out^T -- lane = atom row, 4
-              // consecutive registers = 4 consecutive output columns -> 16-byte stores per lane
-              acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(bv, av, acc[t], 0, 0, 0);
-            }
-          }
+          for (int t = 0; t < NT; ++t) bf[t][q] = Bs[kk + half][t * 32 + (lane & 31)];
         }
+        __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead of the MFMAs
+        // operands swapped on purpose: the accumulator holds out^T -- lane = atom row, 4
+        // consecutive registers = 4 consecutive output columns -> 16-byte stores per lane
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+#pragma unroll
+          for (int t = 0; t < NT; ++t)
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[t][q], af[q], acc[t], 0, 0, 0);
       }
       __syncthreads();
-      if (c + 1 < nchunks && !(diag & 2)) {
+      if (c + 1 < nchunks) {
         sstore();
         __syncthreads();
       }
@@ -352,24 +335,24 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
   const int64_t boff = pick_seg(st.bias_off, s);
   const bool has_bias = bias != nullptr && boff >= 0;
   const int r = wrow * 32 + (lane & 31);
-  float bv[NTW][4][4];
+  float bv[NT][4][4];
 #pragma unroll
-  for (int t = 0; t < NTW; ++t)
+  for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const int c = col0 + (wcol * NTW + t) * 32 + 8 * rg + 4 * half + q;
+        const int c = col0 + t * 32 + 8 * rg + 4 * half + q;
         bv[t][rg][q] = has_bias ? bias[boff + (c < n_out ? c : n_out - 1)] : 0.f;
       }
   if (r < rows_valid) {
     float* orow = out + (int64_t)(row0 + r) * ldo;
     const bool vec_out = (ldo % 4 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15u) == 0);
 #pragma unroll
-    for (int t = 0; t < NTW; ++t) {
+    for (int t = 0; t < NT; ++t) {
 #pragma unroll
       for (int rg = 0; rg < 4; ++rg) {
-        const int c = col0 + (wcol * NTW + t) * 32 + 8 * rg + 4 * half;  // columns c .. c+3 = registers 4rg .. 4rg+3
+        const int c = col0 + t * 32 + 8 * rg + 4 * half;  // columns c .. c+3 = registers 4rg .. 4rg+3
         float v[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -608,13 +591,8 @@ int gcmi_seg_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_en
   hipStream_t sm = (hipStream_t)stream;
   const bool vec4 = (d_a1 == nullptr || (aligned16(d_a1) && lda1 % 4 == 0)) &&
                     (d_a2 == nullptr || (aligned16(d_a2) && lda2 % 4 == 0));
-  static const bool use_v1 = getenv("GCMI_GEMM_V1") != nullptr;  // A/B switches for tools/kbench.py
-  static const int bm_env = getenv("GCMI_GEMM_BM") ? atoi(getenv("GCMI_GEMM_BM")) : 128;
-  static const int frag_env = getenv("GCMI_GEMM_FRAG") ? atoi(getenv("GCMI_GEMM_FRAG")) : 1;
-  static const int diag = getenv("GCMI_GEMM_DIAG") ? atoi(getenv("GCMI_GEMM_DIAG")) : 0;
-  const bool v2 = vec4 && !use_v1;
   const int nt = n_out <= 32 ? 1 : (n_out <= 64 ? 2 : 4);
-  const int bm = v2 ? ((bm_env == 64 && nt >= 2) ? 64 : BM2) : BM;
+  const int bm = vec4 ? BM2 : BM;
   SegTable st;
   memset(&st, 0, sizeof(st));
   st.n_seg = n_seg;
@@ -636,14 +614,7 @@ int gcmi_seg_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_en
   st.tile_start[kMaxSeg] = (int32_t)tiles;
   if (tiles == 0) return GCMI_OK;
   TimedScope ts(GCMI_K_SEG_GEMM, sm);
-  // GCMI_GEMM_V3=1: fp32-accurate product on the bf16 matrix cores (gemm_split.hip).  Measured on
-  // MI355X it is 20-28 % faster than the exact-fp32 MFMA kernels below on cache-warm operands
-  // (tools/kbench.py) and equal to them inside the model, where both are bound by their operand
-  // streams from HBM; the exact-fp32 chain stays the default.
-  static const bool v3 = getenv("GCMI_GEMM_V3") && atoi(getenv("GCMI_GEMM_V3")) == 1;
   const bool exact = gemm_exact_mode();
-  // GCMI_GEMM_V4=0 disables the LDS-staged split-bf16 kernel (default path)
-  static const bool v4 = !(getenv("GCMI_GEMM_V4") && atoi(getenv("GCMI_GEMM_V4")) == 0);
   if (!exact && n_seg == 1 && d_a2 == nullptr && trans_w && seg_begin[0] == 0 && w1_off[0] >= 0) {
     // the task head with more than 32 outputs (head_bwd.hip)
     const int rc = head_fwd_wide(d_a1, lda1, seg_end[0], k1, d_w1 + w1_off[0],
@@ -651,35 +622,21 @@ int gcmi_seg_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_en
                                  ldo, sm);
     if (rc != GCMI_ERR_UNSUPPORTED) return rc;
   }
-  if (v4 && !v3 && !exact) {
+  if (!exact) {  // the LDS-staged split-bf16 kernel (gemm_split.hip)
     const int rc = launch_seg_gemm4(n_seg, seg_begin, seg_end, d_a1, lda1, k1, d_w1, w1_off, d_a2, lda2, k2,
                                     d_w2, w2_off, d_bias, bias_off, n_out, trans_w, act, d_out, ldo, sm);
     if (rc != GCMI_ERR_UNSUPPORTED) return rc;
   }
-  if (v3 && vec4 && !exact) {
-    const int rc = launch_seg_gemm3(n_seg, seg_begin, seg_end, d_a1, lda1, k1, d_w1, w1_off, d_a2, lda2, k2,
-                                    d_w2, w2_off, d_bias, bias_off, n_out, trans_w, act, d_out, ldo, sm);
-    if (rc != GCMI_ERR_UNSUPPORTED) return rc;
-  }
-  if (v2) {
+  if (vec4) {
     dim3 grid((unsigned)tiles, (unsigned)((n_out + nt * 32 - 1) / (nt * 32)));
-    static const int kc_env = getenv("GCMI_GEMM_KC") ? atoi(getenv("GCMI_GEMM_KC")) : 32;
-#define LAUNCH_SG2(TT, NN, BB, FF)                                                                \
-  do {                                                                                            \
-    if (kc_env == 64)                                                                             \
-      hipLaunchKernelGGL((seg_gemm2_kernel<TT, NN, BB, FF, 64>), grid, dim3(kGBlock), 0, sm, st, d_a1, \
-                         lda1, k1, d_w1, d_a2, lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo, diag); \
-    else                                                                                          \
-      hipLaunchKernelGGL((seg_gemm2_kernel<TT, NN, BB, FF, 32>), grid, dim3(kGBlock), 0, sm, st, d_a1, \
-                         lda1, k1, d_w1, d_a2, lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo, diag); \
-  } while (0)
-#define LAUNCH_SG2_T(TT)                                                                     \
-  do {                                                                                       \
-    if (nt == 1) { if (frag_env) LAUNCH_SG2(TT, 1, 128, true); else LAUNCH_SG2(TT, 1, 128, false); }         \
-    else if (nt == 2 && bm == 128) { if (frag_env) LAUNCH_SG2(TT, 2, 128, true); else LAUNCH_SG2(TT, 2, 128, false); } \
-    else if (nt == 2) { if (frag_env) LAUNCH_SG2(TT, 2, 64, true); else LAUNCH_SG2(TT, 2, 64, false); }    \
-    else if (bm == 128) { if (frag_env) LAUNCH_SG2(TT, 4, 128, true); else LAUNCH_SG2(TT, 4, 128, false); } \
-    else { if (frag_env) LAUNCH_SG2(TT, 4, 64, true); else LAUNCH_SG2(TT, 4, 64, false); }               \
+#define LAUNCH_SG2(TT, NN)                                                                             \
+  hipLaunchKernelGGL((seg_gemm2_kernel<TT, NN>), grid, dim3(kGBlock), 0, sm, st, d_a1, lda1, k1, d_w1, d_a2, \
+                     lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo)
+#define LAUNCH_SG2_T(TT)                                   \
+  do {                                                     \
+    if (nt == 1) LAUNCH_SG2(TT, 1);                        \
+    else if (nt == 2) LAUNCH_SG2(TT, 2);                   \
+    else LAUNCH_SG2(TT, 4);                                \
   } while (0)
     if (trans_w) LAUNCH_SG2_T(true); else LAUNCH_SG2_T(false);
 #undef LAUNCH_SG2_T
@@ -689,11 +646,7 @@ int gcmi_seg_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_en
 #define LAUNCH_SG(TT, VV)                                                                       \
   hipLaunchKernelGGL((seg_gemm_kernel<TT, VV>), grid, dim3(kGBlock), 0, sm, st, d_a1, lda1, k1,  \
                      d_w1, d_a2, lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo)
-    if (trans_w) {
-      if (vec4) LAUNCH_SG(true, true); else LAUNCH_SG(true, false);
-    } else {
-      if (vec4) LAUNCH_SG(false, true); else LAUNCH_SG(false, false);
-    }
+    if (trans_w) LAUNCH_SG(true, false); else LAUNCH_SG(false, false);
 #undef LAUNCH_SG
   }
   GCMI_CHECK_LAUNCH("seg_gemm");
@@ -726,8 +679,7 @@ int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* 
   const int kt = (k + 31) / 32;
   const int64_t resident = 256 * (kt <= 2 ? 4 : (kt == 3 ? 3 : 2)) - n_seg;  // every segment may add a partial slab
   // (more than four k-tiles: the split kernel runs ceil(kt / 4) chunks per slab, so slabs are that much longer)
-  static const bool wg3_on = !(getenv("GCMI_WGRAD_V3") && atoi(getenv("GCMI_WGRAD_V3")) == 0);
-  const int64_t chunks = (kt > 4 && wg3_on && !gemm_exact_mode()) ? (kt + 3) / 4 : 1;
+  const int64_t chunks = (kt > 4 && !gemm_exact_mode()) ? (kt + 3) / 4 : 1;
   int64_t slab = (total_rows * chunks + resident - 1) / resident;
   slab = ((slab + 63) / 64) * 64;
   if (slab < 256) slab = 256;
@@ -736,8 +688,7 @@ int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* 
     // Few rows (the task head's weight gradient at a per-GPU batch of a few thousand molecules): 256-row slabs leave
     // most CUs idle.  Smaller slabs, down to a floor, until the launch has a workgroup per CU; below the floor the
     // k x n atomic adds every workgroup ends with outweigh its row loop.
-    static const int floor_env = getenv("GCMI_WGRAD_MIN_SLAB") ? atoi(getenv("GCMI_WGRAD_MIN_SLAB")) : 128;
-    const int64_t floor_rows = floor_env >= 64 && floor_env % 64 == 0 ? floor_env : 256;
+    const int64_t floor_rows = 128;
     const int nt_all = (n + 31) / 32;
     const int64_t col_groups = nt_all >= 3 ? (nt_all + 3) / 4 : 1;
     while (slab > floor_rows && ((total_rows + slab - 1) / slab + n_seg - 1) * col_groups * chunks < 256) slab -= 64;
@@ -763,10 +714,9 @@ int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* 
   const int KT_total = (k + 31) / 32;
   dim3 grid((unsigned)slabs, (unsigned)((NT + ntw - 1) / ntw));
   TimedScope ts(GCMI_K_WGRAD, sm);
-  // GCMI_WGRAD_V3=0 keeps the exact-fp32 MFMA kernel below; default: the split-bf16 form
-  // (gemm_split.hip: fp32-accurate, 6 bf16 MFMAs per 16 rows instead of 8 fp32 ones)
-  static const bool wg3 = !(getenv("GCMI_WGRAD_V3") && atoi(getenv("GCMI_WGRAD_V3")) == 0);
-  if (wg3 && !gemm_exact_mode()) {
+  // fast mode: the split-bf16 form (gemm_split.hip: fp32-accurate, 6 bf16 MFMAs per 16 rows instead of 8 fp32 ones);
+  // exact mode and the shapes it does not cover: the exact-fp32 MFMA kernel below
+  if (!gemm_exact_mode()) {
     const int rc = launch_wgrad3(st, (int)slabs, d_a, lda, k, d_g, ldg, n, d_dw, d_dbias, trans_w, sm);
     if (rc != GCMI_ERR_UNSUPPORTED) return rc;
   }
@@ -848,13 +798,11 @@ int seg_gemm_stats(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
                    bool* fused, void* stream, float* d_wimg_scratch) {
   *fused = false;
   const bool allow = g_fused_bn_stats.load(std::memory_order_relaxed) != 0;  // GCMI_OPT_FUSED_BN_STATS
-  static const bool v3 = getenv("GCMI_GEMM_V3") && atoi(getenv("GCMI_GEMM_V3")) == 1;
-  static const bool v4 = !(getenv("GCMI_GEMM_V4") && atoi(getenv("GCMI_GEMM_V4")) == 0);
   const bool shapes_ok = n_seg >= 1 && n_seg <= kMaxSeg && seg_begin && seg_end && n_out > 0 && ldo >= n_out && d_out &&
                          (d_a1 || d_a2) && (d_a1 == nullptr || (d_w1 && w1_off && k1 > 0 && lda1 >= k1)) &&
                          (d_a2 == nullptr || (d_w2 && w2_off && k2 > 0 && lda2 >= k2)) &&
                          (d_bias == nullptr || bias_off != nullptr) && (act == 0 || act == 1);
-  if (shapes_ok && v4 && !v3 && !gemm_exact_mode()) {
+  if (shapes_ok && !gemm_exact_mode()) {
     // the persistent form (fwd_fused.hip) for the shapes it covers
     hipStream_t sm = (hipStream_t)stream;
     TimedScope ts(GCMI_K_SEG_GEMM, sm);
@@ -866,7 +814,7 @@ int seg_gemm_stats(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
       return rc;
     }
   }
-  if (allow && d_stats && shapes_ok && v4 && !v3 && !gemm_exact_mode()) {
+  if (allow && d_stats && shapes_ok && !gemm_exact_mode()) {
     hipStream_t sm = (hipStream_t)stream;
     TimedScope ts(GCMI_K_SEG_GEMM, sm);
     const int rc = launch_seg_gemm4(n_seg, seg_begin, seg_end, d_a1, lda1, k1, d_w1, w1_off, d_a2, lda2, k2, d_w2,

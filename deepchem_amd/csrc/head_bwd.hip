@@ -895,15 +895,8 @@ int head_fwd_wide(const float* d_in, int64_t ldin, int64_t n_rows, int32_t k, co
     return GCMI_OK;
   }
   constexpr size_t shmem = sizeof(unsigned short) * 3 * (kHM * kWP + 2 * kWTC * kFWP);
-  static bool attr_done = false;
-  if (!attr_done) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(head_fwd_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)shmem) != hipSuccess) {
-      (void)hipGetLastError();
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    attr_done = true;
-  }
+  static LdsLimit lim;
+  if (!raise_lds_limit(lim, reinterpret_cast<const void*>(head_fwd_wide_kernel), shmem)) return GCMI_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(head_fwd_wide_kernel, dim3((unsigned)((n_rows + kHM - 1) / kHM)), dim3(kWT), shmem, st, d_in, ldin,
                      n_rows, d_w, d_bias, n_out, d_out, ldo);
   GCMI_CHECK_LAUNCH("head_fwd_wide");
@@ -937,15 +930,8 @@ int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, c
   a.sums = d_sums;
   if (wide) {
     constexpr size_t shmem = sizeof(unsigned short) * 3 * kHM * kWP + sizeof(float) * (2 * kHM * kHB + kHM * (kHB / 2));
-    static bool attr_done = false;
-    if (!attr_done) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(head_bwd_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)shmem) != hipSuccess) {
-        (void)hipGetLastError();
-        return GCMI_ERR_UNSUPPORTED;
-      }
-      attr_done = true;
-    }
+    static LdsLimit lim;
+    if (!raise_lds_limit(lim, reinterpret_cast<const void*>(head_bwd_wide_kernel), shmem)) return GCMI_ERR_UNSUPPORTED;
     const int rc = head_prep(d_w, tc, d_img, st);
     if (rc != GCMI_OK) return rc;
     hipLaunchKernelGGL(head_bwd_wide_kernel, dim3((unsigned)((n_mols + kHM - 1) / kHM)), dim3(kWT), shmem, st, a, d_dl_scratch,
@@ -953,9 +939,8 @@ int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, c
     GCMI_CHECK_LAUNCH("head_bwd_wide");
     HD_PRINT("bwd_wide", 0, st);
     // slabs: two workgroups per CU over all blocks of dW (measured at 8 192 x 256: 1 024 workgroups 24.1 us, 512: 18.8, 256: 19.8 -- the atomics of more, shorter slabs against the latency of fewer, longer ones), never below 64 molecules
-    static const int wg_env = getenv("GCMI_HEAD_WGRAD_WGS") ? atoi(getenv("GCMI_HEAD_WGRAD_WGS")) : 512;
     const int blocks = ((tc + 63) / 64) * 4;
-    int64_t slabs = std::max<int64_t>(1, wg_env / blocks);
+    int64_t slabs = std::max<int64_t>(1, 512 / blocks);
     slabs = std::min<int64_t>(slabs, (n_mols + 63) / 64);
     const int rps = (int)(((n_mols + slabs - 1) / slabs + 31) / 32 * 32);
     slabs = (n_mols + rps - 1) / rps;

@@ -282,7 +282,6 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
   }
   const bf16_t* xin = nullptr;
   int64_t ldin = 0;
-  bool sum_done = false;  // S[l] was written by the fused pass of block l - 1
   RUN(pack_biases(m, w, ws, d_params, st));
   for (int l = 0; l < L; ++l) {
     const int K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
@@ -298,7 +297,7 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
           RUN(win_gather_sum_fh(g, io->d_atom_features, io->ld_features, (int)w.ngather[0], H(w.S[0]), H(w.xb), w.ldS[0], st));
           xin = H(w.xb);
           ldin = w.ldS[0];
-        } else if (!sum_done) {
+        } else {
           RUN(win_gather_sum_h(g, xin, ldin, K, H(w.S[l]), w.ldS[l], st));
         }
       }
@@ -321,15 +320,8 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
       }
       {
         TimedScope ts(GCMI_K_GATHER_MAX, st);
-        // GraphPool of this block, and where another GraphConv follows its neighbour sums in the same window pass
-        sum_done = l + 1 < L && m->conv_width[l + 1] == W && win_max_sum_usable_h(g, W);
-        if (sum_done)
-          RUN(win_gather_max_sum_h(g, H(w.gc[l]), W, W, scale, shift, H(w.pool[l]), W,
-                                   training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, H(w.S[l + 1]),
-                                   w.ldS[l + 1], st));
-        else
-          RUN(win_gather_max_h(g, H(w.gc[l]), W, W, scale, shift, H(w.pool[l]), W,
-                               training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, st));
+        RUN(win_gather_max_h(g, H(w.gc[l]), W, W, scale, shift, H(w.pool[l]), W,
+                             training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, st));
       }
     }
     xin = H(w.pool[l]);
@@ -759,8 +751,6 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
   const float* coef = ws + w.acc;  // [A | B | C] of the BatchNorm backward just computed (bn.hip: head of its scratch)
   bool dense_done = false;
   bool have_psums = false;  // acc2 holds sum dP, sum dP * P for the BatchNorm below the block just processed
-  static const bool psums_env = !(getenv("GCMI_FUSED_PSUMS") && atoi(getenv("GCMI_FUSED_PSUMS")) == 0);
-  static const bool two_stage_env = !(getenv("GCMI_TWO_STAGE_GATHER") && atoi(getenv("GCMI_TWO_STAGE_GATHER")) == 0);
   bool dy_ready = false;  // the gather of the block above already left this block's dy (two-stage window pass)
   if (m->batch_norm) {
     // GraphGather backward is recomputed inside the BatchNorm backward from the per-molecule
@@ -791,10 +781,10 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
                                      reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.dense, D, coef, D,
                                      ws + w.pool[L - 1], Wl, Wl, d_params + m->off_dense_w, d_grads + m->off_dense_w,
                                      d_grads + m->off_dense_b, dpool, Wl,
-                                     psums_env ? reinterpret_cast<double*>(ws + w.acc2) : nullptr, st);
+                                     reinterpret_cast<double*>(ws + w.acc2), st);
       if (rc == GCMI_OK) {
         dense_done = true;
-        have_psums = psums_env;
+        have_psums = true;
       }
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
       else  // not covered after all (misaligned buffers): the separate pass, with its sums once more
@@ -834,11 +824,7 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
     // the fused pass covers the default widths in split-bf16 mode; it wants 16-byte rows of every operand
     const bool try_fused = full && fused_bwd_enabled() && W == 64 && ldx % 4 == 0 && aligned16(xin) &&
                            ((l == 0 && K > 32 && K <= 96) || (l > 0 && K > 32 && K <= 64));
-    // GraphPool backward; when nothing needs the elementwise BatchNorm pass afterwards, the window kernel also
-    // takes the column sums of the BatchNorm backward from the rows it stores (dy is then not read again for them)
-    static const bool stats_env = getenv("GCMI_STATS_IN_GATHER") && atoi(getenv("GCMI_STATS_IN_GATHER")) != 0;
-    const bool stats_in_gather = stats_env && m->batch_norm && sym && fused_bwd_enabled() && (try_fused || !full) &&
-                                 win_stats_usable(g, W) && aligned16(dpool) && aligned16(dy) && aligned16(ws + w.gc[l]);
+    // GraphPool backward
     if (!sym) RUN(zero(dy, sizeof(float) * (size_t)(N * W)));
     const bool pool_sums = have_psums && m->batch_norm && sym && (try_fused || !full) && win_usable(g, W, true) &&
                            win_has_width(W);
@@ -860,15 +846,6 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       RUN(bn_bwd_pool_impl(dy, W, ws + w.gc[l], W, N, W, d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], bnv,
                            bnv + W, d_grads + m->off_bn_gamma[l], d_grads + m->off_bn_beta[l],
                            reinterpret_cast<double*>(ws + w.acc2), reinterpret_cast<double*>(ws + w.acc), stream));
-    } else if (stats_in_gather && !dy_ready) {
-      const float* bnv = ws + w.bnv[l];
-      {
-        TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-        RUN(win_gather_max_bwd_stats(g, dpool, W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), dy, W,
-                                     ws + w.gc[l], W, bnv, bnv + W, reinterpret_cast<double*>(ws + w.acc), st));
-      }
-      RUN(bn_bwd_params_impl(N, W, d_params + m->off_bn_gamma[l], bnv, bnv + W, d_grads + m->off_bn_gamma[l],
-                             d_grads + m->off_bn_beta[l], reinterpret_cast<double*>(ws + w.acc), stream));
     } else {
       if (!dy_ready)
         RUN(gcmi_gather_max_bwd(g, dpool, W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), dy, W, stream));
@@ -893,11 +870,11 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
                                     m->batch_norm ? coef : nullptr, W, ws + w.S[l], w.ldS[l], xin, ldx, K,
                                     d_params + m->off_conv_w[l], d_grads + m->off_conv_w[l], ws + w.dbsum[l],
                                     l > 0 ? dS : nullptr, K, l > 0 ? dX : nullptr, K,
-                                    (psums_env && l > 0 && sym && m->batch_norm) ? reinterpret_cast<double*>(ws + w.acc2)
-                                                                                 : nullptr, st);
+                                    (l > 0 && sym && m->batch_norm) ? reinterpret_cast<double*>(ws + w.acc2) : nullptr,
+                                    st);
       if (rc == GCMI_OK) {
         fused_done = true;
-        have_psums = psums_env && l > 0 && sym && m->batch_norm;
+        have_psums = l > 0 && sym && m->batch_norm;
       }
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
       else if (m->batch_norm) {  // not covered after all (misaligned buffers): the separate pass, sums once more
@@ -926,7 +903,7 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       // of dS is a gather)
       // ... and when the window kernels can hold a third tile, the GraphPool backward of the block below in the
       // same pass: dX = dXs + gather(dS) is consumed in LDS and never exists in HBM
-      const bool two_stage = sym && two_stage_env && fused_bwd_enabled() && win_two_stage_usable(g, K) &&
+      const bool two_stage = sym && fused_bwd_enabled() && win_two_stage_usable(g, K) &&
                              aligned16(dS) && aligned16(dX) && aligned16(ws + w.tD);
       if (two_stage) {
         TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);

@@ -1904,7 +1904,6 @@ struct SideStream {
   std::mutex busy;
 };
 static SideStream* side_stream() {
-  constexpr int kMaxDev = 64;
   static std::mutex mu;
   static SideStream* per_dev[kMaxDev] = {nullptr};
   static bool failed[kMaxDev] = {false};
@@ -1983,9 +1982,8 @@ int gcmi_small_fit_dp(const gcmi_model_desc* m, float* d_params, float* d_grads,
   }
   // Reference gradient mode trains nothing the GraphConv stack reads (frozen weights, frozen BatchNorm 0..L-2), so
   // the stack of step i+1 runs on a second stream while step i's dense layer, readout, backward and Adam run on the
-  // caller's; the two parities of the conv outputs / statistics keep them apart.  (GCMI_SMALL_OVERLAP=0: one stream.)
-  static const bool overlap_env = !(getenv("GCMI_SMALL_OVERLAP") && atoi(getenv("GCMI_SMALL_OVERLAP")) == 0);
-  SideStream* side = (!full && overlap_env && n_batches > 1) ? side_stream() : nullptr;
+  // caller's; the two parities of the conv outputs / statistics keep them apart.
+  SideStream* side = (!full && n_batches > 1) ? side_stream() : nullptr;
   std::unique_lock<std::mutex> side_lock;
   if (side) side_lock = std::unique_lock<std::mutex>(side->busy);  // held while this call enqueues
   std::vector<SmallGraph> graphs((size_t)n_batches);

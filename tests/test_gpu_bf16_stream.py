@@ -24,16 +24,16 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
-def _native_step(packed, y, w, tasks, grad_mode, state, storage, train=True, n_feat=75):
+def _native_step(packed, y, w, tasks, grad_mode, state, storage, train=True, n_feat=75, dev=DEV):
     import deepchem_amd as dc
     from deepchem_amd.data.collate import collate_to_device
     from deepchem_amd.metrics import to_one_hot
     n = packed.n_mols
-    dbatch = collate_to_device(packed, None, DEV)
-    labels = torch.as_tensor(to_one_hot(y.flatten(), 2).reshape(-1, tasks, 2).astype(np.float32), device=DEV)
-    weights = torch.as_tensor(w.astype(np.float32), device=DEV)
+    dbatch = collate_to_device(packed, None, dev)
+    labels = torch.as_tensor(to_one_hot(y.flatten(), 2).reshape(-1, tasks, 2).astype(np.float32), device=dev)
+    weights = torch.as_tensor(w.astype(np.float32), device=dev)
     model = dc.models.torch_models.GraphConvModel(tasks, number_input_features=[n_feat, 64], batch_size=n,
-                                                  grad_mode=grad_mode, device=DEV, activation_storage=storage)
+                                                  grad_mode=grad_mode, device=dev, activation_storage=storage)
     model.model.load_state_dict({k: v.clone() for k, v in state.items()})
     native = model.model._native_net()
     assert native is not None and native.desc.storage == {"fp32": 0, "bf16": 1, "bf16+grads": 2}[storage]
@@ -43,10 +43,10 @@ def _native_step(packed, y, w, tasks, grad_mode, state, storage, train=True, n_f
     model.model.train(train)
     logits, _, fp = native.forward(dbatch.atom_features, g, train, want_probs=False)
     if not train:
-        torch.cuda.synchronize()
+        torch.cuda.synchronize(dev)
         return logits.cpu(), fp.cpu()
     loss = native.loss_backward(labels, weights, n)
-    torch.cuda.synchronize()
+    torch.cuda.synchronize(dev)
     names = [k for k, _ in model.model.named_parameters()]
     stats = [(bn.running_mean.clone().cpu(), bn.running_var.clone().cpu()) for bn in model.model.batch_norms]
     return (float(loss), logits.cpu(), fp.cpu(), native.grad_flat.clone().cpu(), list(zip(names, native._slices)),
@@ -134,12 +134,12 @@ def test_streaming_step_in_bf16_storage_against_the_oracle(batch_4096, grad_mode
     _bf16_step_meets_the_oracle(*batch_4096, grad_mode, storage)
 
 
-def _bf16_step_meets_the_oracle(packed, y, w, tasks, state, grad_mode, storage, n_feat=75):
-    native = _native_step(packed, y, w, tasks, grad_mode, state, storage, n_feat=n_feat)
+def _bf16_step_meets_the_oracle(packed, y, w, tasks, state, grad_mode, storage, n_feat=75, dev=DEV):
+    native = _native_step(packed, y, w, tasks, grad_mode, state, storage, n_feat=n_feat, dev=dev)
     same = _deviations(native, _oracle_step(packed, y, w, tasks, grad_mode, state, bf16=True, n_feat=n_feat))
     oracle32 = _oracle_step(packed, y, w, tasks, grad_mode, state, bf16=False, n_feat=n_feat)
     plain = _deviations(native, oracle32)
-    native32 = _native_step(packed, y, w, tasks, grad_mode, state, "fp32", n_feat=n_feat)
+    native32 = _native_step(packed, y, w, tasks, grad_mode, state, "fp32", n_feat=n_feat, dev=dev)
     fp32 = _deviations(native32, oracle32)
     exact = _deviations(native32, _oracle_step_exact(packed, y, w, tasks, grad_mode, state, double=True, n_feat=n_feat))
     print(grad_mode, storage, "| vs the oracle with the same rounding:", _fmt(same))
@@ -165,6 +165,18 @@ def _bf16_step_meets_the_oracle(packed, y, w, tasks, state, grad_mode, storage, 
     # arithmetic -- the float32 oracle's own rounding moves single logits of this batch by up to ~4e-4 of scale with the
     # host's CPU and thread count (the order its matrix products sum in), the float64 oracle by ~1e-11
     assert exact["logits_max"] <= 1e-4 and exact["fp_mean"] <= 1e-5 and exact["grad_l2"] <= 2e-3, exact
+
+
+def test_streaming_step_in_bf16_storage_on_two_devices(batch_4096):
+    """The launch setup the library keeps per device (a kernel's dynamic-LDS limit, its occupancy): the same seeded
+    bf16-storage step -- its products are fwd_hd_kernel launches with ~70 KB of dynamic LDS -- on device 0 and then on
+    device 1 of one process, each held to the bounds of test_streaming_step_in_bf16_storage_against_the_oracle."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible devices")
+    for i in range(2):
+        dev = torch.device("cuda", i)
+        with torch.cuda.device(dev):
+            _bf16_step_meets_the_oracle(*batch_4096, "full", "bf16", dev=dev)
 
 
 @pytest.mark.parametrize("n_feat", [73, 74, 76])

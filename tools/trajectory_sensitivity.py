@@ -2,6 +2,7 @@
 (tests/golden/model_cls_bn.npz, 2 epochs of Adam) and prints the distance of its predictions to the
 reference's, for the current GEMM kernels and for inputs perturbed in the last bit (development
 tool; needs a GPU)."""
+import ctypes
 import os
 import sys
 
@@ -9,6 +10,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from deepchem_amd import _lib  # noqa: E402
 from tests.test_gpu_model import build_model, dataset_from  # noqa: E402
 from tests.util import load_golden  # noqa: E402
 
@@ -29,7 +31,9 @@ def run(perturb):
 
 
 base_l, base_p, g = run(0.0)
-print("kernels: GEMM_V4=%s" % os.environ.get("GCMI_GEMM_V4", "1"))
+exact = ctypes.c_int32(0)
+_lib.call("gcmi_get_option", _lib.GCMI_OPT_GEMM_EXACT, ctypes.byref(exact))
+print("gemm mode:", "exact" if exact.value else "fast")
 print("vs reference: max |pred diff| %.4g, losses rel %.3g" % (np.abs(base_p - g["full_predict"]).max(),
       np.abs(base_l / g["full_fit_losses"] - 1).max()))
 for eps in (1e-7, 1e-6):
