@@ -24,6 +24,7 @@ GCMI_OPT_FUSED_BN_STATS = 2
 GCMI_OPT_FUSED_BWD = 3
 GCMI_OPT_FUSED_BWD_LAUNCHES = 4
 GCMI_OPT_READOUT_PIPELINED = 5
+GCMI_OPT_ONE_PIECE_LAUNCHES = 6
 GCMI_WIN_META_INTS = 24
 GCMI_COLLATE_WIN_DESC_INTS = 36
 GCMI_WIN_MAX_SLOTS = 4095
@@ -99,6 +100,8 @@ class GcmiModelIO(Structure):
         ("d_probs", c_void_p),
         ("d_fingerprint", c_void_p),
         ("d_loss", c_void_p),
+        ("features_small_int", c_int32),
+        ("reserved_", c_int32),
     ]
 
 
@@ -131,6 +134,9 @@ _SIGNATURES = {
                      c_int64, _P, _G],
     "gcmi_collate_plans": [_P, c_int64, _P, _P, _P, _P, c_int64, c_int32, _P, c_int64, c_int64, _P, _P,
                            c_int64, _P, _P, _I32P, c_int32, _P, _P, _G],
+    "gcmi_collate_plans_p": [_P, c_int64, _P, _P, _P, _P, c_int64, c_int32, _P, c_int64, c_int64, _P, _P,
+                             c_int64, _P, _P, _I32P, c_int32, _P, _P, _G, c_int32, _I32P],
+    "gcmi_count_not_small_int": [_P, c_int64, c_int64, c_int32, c_int32, _P, _P],
     "gcmi_molset_tables": [_P, _P, _P, c_int64, c_int32, _P, _P, _P, _I32P, c_int32],
     "gcmi_collate_plan": [_P, _P, _P, c_int64, c_int32, c_int32, _P, c_int64, _P, _G],
     "gcmi_collate_rows": [_P, c_int64, _P, _P, _P, _P, _P, _P, _G, _P, c_int64, _P, _P, _P, _P, _P, _P, _P],

@@ -83,10 +83,16 @@ struct FusedArgs {
 // GB (with HB; storage == 2): the gradient STREAMS are bf16 as well -- dy arrives as 8-byte pieces, the input gradients
 // leave rounded once (the column sums for the BatchNorm below are taken from the rounded values: they describe what the
 // next kernel reads).
-template <int NG, int KT, int NOPS, bool TRANS, bool RD, bool DGRAD, bool HB = false, bool GB = false>
+// IB without HB (the first GraphConv over small-integer atom features, fp32 storage: model.hip): In alone arrives as
+// bf16 rows, which hold its values EXACTLY; x and dy are fp32.  The weight-gradient fragment of In is its one piece as
+// above, but G keeps all THREE pieces (3 MFMAs per fragment instead of 6): the forward was not rounded, so nothing
+// justifies dropping a term here.
+template <int NG, int KT, int NOPS, bool TRANS, bool RD, bool DGRAD, bool HB = false, bool GB = false, bool IB = HB>
 __global__ void __launch_bounds__(DGRAD ? 512 : 256) __attribute__((amdgpu_waves_per_eu(2)))
 fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
   static_assert(!GB || HB, "bf16 gradient streams come with bf16 activations");
+  static_assert(IB || !HB, "bf16 activations include the block's inputs");
+  static_assert(IB == HB || !DGRAD, "In alone as bf16: the weight-gradient-only form");
   constexpr int NT = DGRAD ? 512 : 256;
   constexpr int NJ = NG / 32;                 // 32-column groups of G
   constexpr int KP = KT * 32;                 // padded width of In
@@ -199,10 +205,20 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
     if constexpr (HB) return widen4(v);
     else return v;
   };
+  using InV = typename std::conditional<IB, uint2, float4>::type;   // four elements of an In row
+  auto load_in = [](const float* base, unsigned elem) -> InV {
+    if constexpr (IB) return *reinterpret_cast<const uint2*>(reinterpret_cast<const bf16_t*>(base) + elem);
+    else return *reinterpret_cast<const float4*>(base + elem);
+  };
+  auto in4 = [](const InV& v) -> float4 {
+    if constexpr (IB) return widen4(v);
+    else return v;
+  };
   using DyV = typename std::conditional<GB && !RD, uint2, float4>::type;  // four incoming gradients
   DyV pdy[GPASS];
   float4 pgm[RD ? GPASS : 1];
-  ActV px[GPASS], pin[NOPS][IPASS];
+  ActV px[GPASS];
+  InV pin[NOPS][IPASS];
   int4 parg[RD ? GPASS : 1];
   int mem1[RD ? GPASS : 1];
   auto clampr = [](int r, int valid) { return r < valid ? r : valid - 1; };
@@ -235,7 +251,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
         const int r = slot / IQ, q = slot - r * IQ;
         const int ld = a.ldin[o];
         const int qc = 4 * q + 4 <= ld ? 4 * q : 0;
-        pin[o][p] = load_act(a.in[o], (unsigned)(row0 + clampr(r, valid)) * (unsigned)ld + qc);
+        pin[o][p] = load_in(a.in[o], (unsigned)(row0 + clampr(r, valid)) * (unsigned)ld + qc);
       }
     }
   };
@@ -433,7 +449,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
         const int slot = tid + p * NT;
         const int r = slot / IQ, q = slot - r * IQ;
         const int tail = a.k_in - 4 * q;
-        float4 v = act4(pin[o][p]);
+        float4 v = in4(pin[o][p]);
         const bool ok = r < valid;
         v.x = (ok && tail > 0) ? v.x : 0.f;
         v.y = (ok && tail > 1) ? v.y : 0.f;
@@ -564,19 +580,24 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
         const bool next_is_g = (f + 1) % FPS == 0;  // (compile-time under the unrolling)
         auto pair_split = [&](int i) {
           if (!more) return;
-          if (HB && !next_is_g) {  // a fragment of stored bf16 values: exact in one piece
+          if (IB && !next_is_g) {  // a fragment of stored bf16 values: exact in one piece
             q[0][i] = pack_exact_bf16x2(raw[2 * i], raw[2 * i + 1]);
             q[1][i] = q[2][i] = 0u;
           } else {
             split3_pair(raw[2 * i], raw[2 * i + 1], q[0][i], q[1][i], q[2][i]);
           }
         };
-        if (HB && w_ != 0 && on) {  // uniform: In in one piece x G in three
+        if (IB && w_ != 0 && on) {  // uniform: In in one piece
           const int t = w_ - 1;
           const Frag3& L = TRANS ? fg : cur;
           const Frag3& R = TRANS ? cur : fg;
-          // (In is `cur`: TRANS -> the right operand R.p[0], else the left operand L.p[0]; G in its two leading pieces,
-          // the smaller first)
+          // (In is `cur`: TRANS -> the right operand R.p[0], else the left operand L.p[0]; G in its two leading pieces
+          // -- all three when the forward was not rounded --, the smaller first)
+          if constexpr (!HB) {
+            accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(TRANS ? L.p[2] : L.p[0]),
+                                                              as_bf16x8(TRANS ? R.p[0] : R.p[2]), accs[t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
           pair_split(0);
           pair_split(1);
           __builtin_amdgcn_sched_barrier(0);
@@ -717,13 +738,13 @@ void set_fused_bwd(int on) { g_fused_bwd.store(on ? 1 : 0, std::memory_order_rel
 int get_fused_bwd() { return g_fused_bwd.load(std::memory_order_relaxed); }
 bool fused_bwd_enabled() { return fused_bwd_on() && get_fused_bwd() != 0 && !gemm_exact_mode(); }
 
-template <int NG, int KT, int NOPS, bool TRANS, bool RD, bool DGRAD, bool HB = false, bool GB = false>
+template <int NG, int KT, int NOPS, bool TRANS, bool RD, bool DGRAD, bool HB = false, bool GB = false, bool IB = HB>
 static int launch_fused(const FusedTable& st, int n_tiles, const FusedArgs& a, hipStream_t sm) {
   constexpr int KP = KT * 32;
   size_t shmem = sizeof(float) * kFRows * (NG + 4) + sizeof(float) * (size_t)NOPS * kFRows * (KP + 4);
   if (DGRAD)
     shmem += sizeof(unsigned short) * (size_t)NOPS * 3 * KP * (NG + 8) + sizeof(float) * kFRows * (NOPS * KT * 32 + 8);
-  auto kern = fused_bwd_kernel<NG, KT, NOPS, TRANS, RD, DGRAD, HB, GB>;
+  auto kern = fused_bwd_kernel<NG, KT, NOPS, TRANS, RD, DGRAD, HB, GB, IB>;
   // exactly what is asked for: the kernel also has a few hundred bytes of static LDS (the segment table)
   static LdsLimit lim;  // per instantiation
   if (!raise_lds_limit(lim, reinterpret_cast<const void*>(kern), shmem)) return GCMI_ERR_UNSUPPORTED;
@@ -778,8 +799,12 @@ int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
                    const int64_t* w_self, const int64_t* b_off, const float* d_dy, int64_t lddy, const float* d_gc,
                    int64_t ldgc, const float* d_coef, int32_t width, const float* d_s, int64_t lds, const float* d_x,
                    int64_t ldx, int32_t k_in, const float* d_w, float* d_dw, float* d_dbsum, float* d_ds_out,
-                   int64_t ldds, float* d_dxs_out, int64_t lddxs, double* d_psums, hipStream_t sm, int32_t act_bf16) {
+                   int64_t ldds, float* d_dxs_out, int64_t lddxs, double* d_psums, hipStream_t sm, int32_t act_bf16,
+                   int32_t in_bf16) {
   if (!fused_bwd_enabled() || n_seg > kFMaxSeg || width != 64) return GCMI_ERR_UNSUPPORTED;
+  // (in_bf16 without act_bf16: d_s and d_x alone point to bf16 rows that hold their values exactly -- the first
+  // GraphConv, which needs no input gradient)
+  if (in_bf16 && (act_bf16 || d_ds_out != nullptr || k_in <= 64 || k_in > 96)) return GCMI_ERR_UNSUPPORTED;
   {  // 32-bit element offsets inside the kernel: every array below 2^30 elements
     int64_t rows = 0;
     for (int sgi = 0; sgi < n_seg; ++sgi) rows = std::max<int64_t>(rows, seg_end[sgi]);
@@ -789,7 +814,7 @@ int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
   if (!aligned16(d_dy) || lddy % 4 || !aligned16(d_gc) || ldgc % 4) return GCMI_ERR_UNSUPPORTED;
   if (d_coef && !aligned16(d_coef)) return GCMI_ERR_UNSUPPORTED;
   // (act_bf16: d_gc, d_s and d_x point to bf16 rows, their leading dimensions count elements; 8-byte pieces)
-  if (act_bf16 && (!aligned16(d_s) || lds % 4 || !aligned16(d_x) || ldx % 4)) return GCMI_ERR_UNSUPPORTED;
+  if ((act_bf16 || in_bf16) && (!aligned16(d_s) || lds % 4 || !aligned16(d_x) || ldx % 4)) return GCMI_ERR_UNSUPPORTED;
   const bool dgrad = d_ds_out != nullptr;
   FusedTable st;
   const int tiles = make_table(n_seg, seg_begin, seg_end, w_rel, w_self, b_off, &st);
@@ -814,6 +839,7 @@ int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
     return act_bf16 == 2 ? launch_fused<64, 2, 2, false, false, false, true, true>(st, tiles, a, sm)
            : act_bf16    ? launch_fused<64, 2, 2, false, false, false, true>(st, tiles, a, sm)
                          : launch_fused<64, 2, 2, false, false, false>(st, tiles, a, sm);
+  if (in_bf16) return launch_fused<64, 3, 2, false, false, false, false, false, true>(st, tiles, a, sm);
   if (k_in > 64 && k_in <= 96)
     return act_bf16 == 2 ? launch_fused<64, 3, 2, false, false, false, true, true>(st, tiles, a, sm)
            : act_bf16    ? launch_fused<64, 3, 2, false, false, false, true>(st, tiles, a, sm)

@@ -11,6 +11,7 @@
 // every degree block, a serial prefix over molecules turns that into per-molecule
 // row bases (and closes the LDS windows), and a second parallel pass writes rows.
 // The result is identical for any thread count.
+#include <cmath>
 #include <algorithm>
 #include <cstdlib>
 #include <string>
@@ -220,6 +221,19 @@ int gcmi_collate_plans(const float* atom_features, int64_t n_feat, const int64_t
                        int64_t cap_edges, int32_t* out_mol_runs, uint8_t* out_rev_pos,
                        int32_t* out_symmetric, int32_t win_cap, int32_t* out_win_meta,
                        uint16_t* out_win_edges, gcmi_graph* graph) {
+  return gcmi_collate_plans_p(atom_features, n_feat, atom_ptr, adj_ptr, adj_idx, sel, n_sel, max_deg, out_features, out_ld,
+                              cap_atoms, out_membership, out_col_idx, cap_edges, out_mol_runs, out_rev_pos, out_symmetric,
+                              win_cap, out_win_meta, out_win_edges, graph, 0, nullptr);
+}
+
+int gcmi_collate_plans_p(const float* atom_features, int64_t n_feat, const int64_t* atom_ptr,
+                         const int64_t* adj_ptr, const int32_t* adj_idx, const int64_t* sel,
+                         int64_t n_sel, int32_t max_deg, float* out_features, int64_t out_ld,
+                         int64_t cap_atoms, int32_t* out_membership, int32_t* out_col_idx,
+                         int64_t cap_edges, int32_t* out_mol_runs, uint8_t* out_rev_pos,
+                         int32_t* out_symmetric, int32_t win_cap, int32_t* out_win_meta,
+                         uint16_t* out_win_edges, gcmi_graph* graph, int32_t atom_codes, int32_t* out_small_int) {
+  GCMI_CHECK_ARG(!atom_codes || n_feat == 2, "collate: atom codes are rows of 8 bytes (n_feat = 2)");
   GCMI_CHECK_ARG(atom_features && atom_ptr && adj_ptr && (sel || n_sel == 0) && graph,
                  "collate: NULL input");
   GCMI_CHECK_ARG(n_feat > 0 && out_ld >= n_feat, "collate: out_ld %lld < n_feat %lld",
@@ -276,6 +290,11 @@ int gcmi_collate_plans(const float* atom_features, int64_t n_feat, const int64_t
   // pass 2 (parallel): rows, features, membership, neighbour tables, runs, reverse slots, LDS slots
   std::vector<int> bad2(std::max(1, n_threads), 0);
   std::vector<int> asym(std::max(1, n_threads), 0);
+  // "every feature element is an integer of magnitude <= 256 / max_deg" (gcmi_model_io.features_small_int): each
+  // worker notes a violation among its own rows; the batch's answer is the OR, whatever the number of workers
+  std::vector<int> not_small(std::max(1, n_threads), 0);
+  const bool want_small = out_small_int != nullptr;
+  const float small_lim = (float)(256 / std::max(1, (int)max_deg));
   parallel_for(n_sel, n_threads, [&](int64_t p0, int64_t p1, int t) {
     std::vector<int32_t> new_row;
     std::vector<int32_t> deg_of;
@@ -308,6 +327,21 @@ int gcmi_collate_plans(const float* atom_features, int64_t n_feat, const int64_t
         float* dst = out_features + row * out_ld;
         memcpy(dst, atom_features + a * n_feat, sizeof(float) * (size_t)n_feat);
         for (int64_t f = n_feat; f < out_ld; ++f) dst[f] = 0.f;
+        if (want_small) {  // (the row is in cache: it was just copied)
+          int viol = 0;
+          if (atom_codes) {
+            // an expanded code row is one-hot blocks (0 / 1) plus three values: charge (int8), radical electrons, aromatic
+            const uint8_t* code = reinterpret_cast<const uint8_t*>(dst);
+            const int charge = (int8_t)code[3];
+            viol = (float)std::abs(charge) > small_lim || (float)code[4] > small_lim || (float)code[6] > small_lim;
+          } else {
+            for (int64_t f = 0; f < n_feat; ++f) {
+              const float v = fabsf(dst[f]) <= small_lim ? dst[f] : 0.5f;  // NaN, infinities, large values: violations
+              viol |= v != (float)(int)v;
+            }
+          }
+          not_small[t] |= viol;
+        }
         out_membership[row] = (int32_t)p;
         const int64_t eb = edge_start[d] + (row - deg_start[d]) * d;
         for (int j = 0; j < d; ++j) {
@@ -358,6 +392,11 @@ int gcmi_collate_plans(const float* atom_features, int64_t n_feat, const int64_t
     *out_symmetric = 1;
     for (int b : asym)
       if (b) *out_symmetric = 0;
+  }
+  if (out_small_int) {
+    *out_small_int = 1;
+    for (int b : not_small)
+      if (b) *out_small_int = 0;
   }
   graph->n_atoms = (int32_t)n_atoms;
   graph->n_edges = (int32_t)n_edges;

@@ -122,11 +122,12 @@ int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const unsigned short* d_ds,
                                 unsigned short* d_dxs, int64_t lddxs, const uint8_t* d_arg, unsigned short* d_dy,
                                 int64_t lddy, hipStream_t st);
 // fwd_bf16.hip: forward product over bf16 operands, bf16 output, BatchNorm sums of the rounded output
+// (d_out_f32: fp32 output rows and sums of the unrounded values instead -- the two-operand 65..80-column shape only)
 int fwd_h_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const unsigned short* d_a1, int64_t lda1,
                int32_t k1, const float* d_w1, const int64_t* w1_off, const unsigned short* d_a2, int64_t lda2, int32_t k2,
                const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off, int32_t n_out,
                int32_t trans_w, int32_t act, unsigned short* d_out, int64_t ldo, double* d_stats, float* d_wimg_scratch,
-               hipStream_t sm);
+               hipStream_t sm, float* d_out_f32 = nullptr);
 int fwd_weight_images(int32_t n_seg, const int64_t* w1_off, const int64_t* w2_off, const float* d_w1, const float* d_w2,
                       int32_t k_in, int32_t ko, int32_t n_ops, int32_t n_out, int32_t trans_w, float* d_scratch,
                       hipStream_t sm);
@@ -164,11 +165,13 @@ void set_fused_bwd(int on);
 int get_fused_bwd();
 bool fused_bwd_enabled();
 int fused_bwd_launches();  // launches of the one-pass kernel so far (tests)
+int one_piece_launches();  // model.hip: launches of the first block's one-piece forward product and backward so far
 int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_rel,
                    const int64_t* w_self, const int64_t* b_off, const float* d_dy, int64_t lddy, const float* d_gc,
                    int64_t ldgc, const float* d_coef, int32_t width, const float* d_s, int64_t lds, const float* d_x,
                    int64_t ldx, int32_t k_in, const float* d_w, float* d_dw, float* d_dbsum, float* d_ds_out,
-                   int64_t ldds, float* d_dxs_out, int64_t lddxs, double* d_psums, hipStream_t sm, int32_t act_bf16 = 0);
+                   int64_t ldds, float* d_dxs_out, int64_t lddxs, double* d_psums, hipStream_t sm, int32_t act_bf16 = 0,
+                   int32_t in_bf16 = 0);
 int fused_dense_bwd(int64_t n_rows, const int32_t* d_membership, const float* d_g2, int64_t ldg2,
                     const int32_t* d_arg, const float* d_dense, int64_t ldd, const float* d_coef, int32_t width,
                     const float* d_p, int64_t ldp, int32_t k_in, const float* d_w, float* d_dw, float* d_db,

@@ -41,7 +41,7 @@ struct FwdHArgs {
   int32_t k_in;          // columns of every operand (<= KO)
   const float* w[2];
   const float* bias;
-  bf16_t* out;
+  void* out;             // bf16 rows, or fp32 rows (the kernel's F32OUT form)
   int32_t ldo;           // elements, multiple of 8
   int32_t relu;
   double* stats;         // bn.hip scratch layout, or nullptr
@@ -119,7 +119,10 @@ __device__ u32x4 g_fwdh_dump[512 * 256];  // where the rows beyond a ragged tile
 
 // NOPS operands of KO (padded) columns each, NOUT output columns, NPW = 3 bf16 pieces kept of every weight (exact to
 // 2^-24); TRANS: weights stored NOUT x k_in (nn.Linear)
-template <int NOPS, int KO, int NOUT, bool TRANS>
+// F32OUT: the operands are bf16 rows that hold their values EXACTLY (the first GraphConv over small-integer atom
+// features, fp32 storage: model.hip), so nothing of the product is lost against the split-fp32 kernels and the output
+// stays fp32 -- rows of 16-byte pieces of FOUR columns, the BatchNorm sums taken from the unrounded values.
+template <int NOPS, int KO, int NOUT, bool TRANS, bool F32OUT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
 fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
   constexpr int NT = 256, ROWS = 64, D = 2, NBUF = D + 1, NPW = 3;
@@ -133,7 +136,9 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
   constexpr int TILE_BYTES = TILE_CHUNKS * 16;
   constexpr int LPW = TILE_CHUNKS / NT;                  // DMA instructions per wave and tile
   static_assert(TILE_CHUNKS % NT == 0, "tile loads divide evenly");
-  constexpr int OPB = NOUT * 2 + 16, OQ = NOUT / 8, OPASS = ROWS * OQ / NT;
+  constexpr int OES = F32OUT ? 4 : 2;                    // bytes of an output element
+  constexpr int OPC = 16 / OES;                          // columns of a 16-byte output piece
+  constexpr int OPB = NOUT * OES + 16, OQ = NOUT / OPC, OPASS = ROWS * OQ / NT;
   static_assert(ROWS * OQ % NT == 0 && NT % OQ == 0, "a thread keeps its column piece over the passes");
   constexpr int kWaitSteady = D * OPASS + (D - 1) * LPW;  // younger than tile i's loads when iteration i starts
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -245,15 +250,15 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
           wf[j][ks][pc] = base[(size_t)(((twb + 2 * j) * NKS + ks) * 3 + pc) * 64];
   };
 
-  float ps1[8], ps2[8];
+  float ps1[OPC], ps2[OPC];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) ps1[i] = ps2[i] = 0.f;
+  for (int i = 0; i < OPC; ++i) ps1[i] = ps2[i] = 0.f;
   auto flush_stats = [&]() {
     const int q = tid % OQ;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      atomicAdd(&stat_s[0][8 * q + i], (double)ps1[i]);
-      atomicAdd(&stat_s[1][8 * q + i], (double)ps2[i]);
+    for (int i = 0; i < OPC; ++i) {
+      atomicAdd(&stat_s[0][OPC * q + i], (double)ps1[i]);
+      atomicAdd(&stat_s[1][OPC * q + i], (double)ps2[i]);
       ps1[i] = ps2[i] = 0.f;
     }
   };
@@ -266,14 +271,19 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
       const int r = slot / OQ, q = slot - r * OQ;
       const bool live = r < valid_;
       const u32x4 v = *reinterpret_cast<const u32x4*>(Outs + r * OPB + q * 16);
-      const unsigned off = ((unsigned)(row0_ + r) * (unsigned)a.ldo + 8u * q) * 2u;
+      const unsigned off = ((unsigned)(row0_ + r) * (unsigned)a.ldo + (unsigned)OPC * q) * (unsigned)OES;
       u32x4* dst = live ? reinterpret_cast<u32x4*>(reinterpret_cast<char*>(a.out) + off) : my_dump;
       *dst = v;
       if (a.stats != nullptr && live) {
-        float f[8];
-        widen8(uint4{v.x, v.y, v.z, v.w}, f);
+        float f[OPC];
+        if constexpr (F32OUT) {
+          f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y);
+          f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
+        } else {
+          widen8(uint4{v.x, v.y, v.z, v.w}, f);
+        }
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < OPC; ++i) {
           ps1[i] += f[i];
           ps2[i] = fmaf(f[i], f[i], ps2[i]);
         }
@@ -316,7 +326,8 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
           v0 = v0 > 0.f ? v0 : 0.f; v1 = v1 > 0.f ? v1 : 0.f;
           v2 = v2 > 0.f ? v2 : 0.f; v3 = v3 > 0.f ? v3 : 0.f;
         }
-        *reinterpret_cast<uint2*>(orow + c0 * 2) = narrow4(v0, v1, v2, v3);
+        if constexpr (F32OUT) *reinterpret_cast<float4*>(orow + c0 * 4) = make_float4(v0, v1, v2, v3);
+        else *reinterpret_cast<uint2*>(orow + c0 * 2) = narrow4(v0, v1, v2, v3);
       }
     }
   };
@@ -385,11 +396,11 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
   }
 }
 
-template <int NOPS, int KO, int NOUT, bool TRANS>
+template <int NOPS, int KO, int NOUT, bool TRANS, bool F32OUT = false>
 static int launch_fwd_hd(const FwdHTable& st, int n_tiles, const FwdHArgs& a, hipStream_t sm) {
   constexpr int RQ = NOPS * KO / 8;
-  const size_t shmem = (size_t)3 * 64 * RQ * 16 + (size_t)64 * (NOUT * 2 + 16);
-  auto kern = fwd_hd_kernel<NOPS, KO, NOUT, TRANS>;
+  const size_t shmem = (size_t)3 * 64 * RQ * 16 + (size_t)64 * (NOUT * (F32OUT ? 4 : 2) + 16);
+  auto kern = fwd_hd_kernel<NOPS, KO, NOUT, TRANS, F32OUT>;
   static LdsLimit lim;  // per instantiation
   const int occ = raise_lds_limit(lim, reinterpret_cast<const void*>(kern), shmem, 256, shmem);
   if (!occ) return GCMI_ERR_UNSUPPORTED;
@@ -454,13 +465,16 @@ int fwd_h_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, 
                int32_t k1, const float* d_w1, const int64_t* w1_off, const bf16_t* d_a2, int64_t lda2, int32_t k2,
                const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off, int32_t n_out,
                int32_t trans_w, int32_t act, bf16_t* d_out, int64_t ldo, double* d_stats, float* d_wimg_scratch,
-               hipStream_t sm) {
+               hipStream_t sm, float* d_out_f32) {
+  // (d_out_f32: the output rows are fp32 -- the exact-operand form of the first GraphConv; d_out is not used then)
+  if (d_out_f32 != nullptr) d_out = reinterpret_cast<bf16_t*>(d_out_f32);
   if (n_seg > kHMaxSeg || d_wimg_scratch == nullptr || !aligned16(d_wimg_scratch) || (act != 0 && act != 1) || gemm_exact_mode()) return GCMI_ERR_UNSUPPORTED;
   const bool two = d_a1 != nullptr && d_a2 != nullptr;
   const bool conv = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 32 && k1 <= 64;
   const bool conv80 = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 64 && k1 <= 80;
   const bool dense = !two && d_a1 != nullptr && trans_w && n_out == 128 && k1 > 32 && k1 <= 64;
   if (!conv && !dense && !conv80) return GCMI_ERR_UNSUPPORTED;
+  if (d_out_f32 != nullptr && !conv80) return GCMI_ERR_UNSUPPORTED;
   if (!aligned16(d_a1) || lda1 % 8 || (two && (!aligned16(d_a2) || lda2 % 8)) || !aligned16(d_out) || ldo % 8 ||
       ldo < n_out || (d_bias && !aligned16(d_bias)))
     return GCMI_ERR_UNSUPPORTED;
@@ -501,6 +515,7 @@ int fwd_h_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, 
     GCMI_CHECK_LAUNCH("fwd_h wprep");
     a.wimg = wimg;
   }
+  if (conv80 && d_out_f32 != nullptr) return launch_fwd_hd<2, 80, 64, false, true>(st, (int)tiles, a, sm);
   if (conv80) return launch_fwd_hd<2, 80, 64, false>(st, (int)tiles, a, sm);
   if (conv) return launch_fwd_hd<2, 64, 64, false>(st, (int)tiles, a, sm);
   return launch_fwd_hd<1, 64, 128, true>(st, (int)tiles, a, sm);

@@ -3,6 +3,9 @@
 // fit_generator step (models/torch_models/torch_model.py:436-442) as one C call each.
 // Host code only enqueues the kernels of this library on the caller's stream; the few
 // device functions here are parameter-layout helpers (bias packing, counters).
+#include <map>
+#include <mutex>
+
 #include "common.h"
 #include "split_bf16.h"
 
@@ -45,6 +48,20 @@ __global__ void bias_unpack_kernel(BiasLayers bl, int max_deg) {
   }
 }
 
+// elements of an n_rows x n_cols matrix that are NOT integers of magnitude <= limit (NaN and infinities count)
+__global__ void small_int_count_kernel(const float* __restrict__ x, int64_t ld, int64_t n_rows, int n_cols, float limit,
+                                       unsigned long long* __restrict__ count) {
+  const int64_t total = n_rows * n_cols;
+  unsigned bad = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = i / n_cols;
+    const float v = x[r * ld + (i - r * n_cols)];
+    bad += (fabsf(v) <= limit && v == truncf(v)) ? 0u : 1u;
+  }
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  if ((threadIdx.x & 63) == 0 && bad) atomicAdd(count, (unsigned long long)bad);
+}
+
 struct CounterPtrs {
   int64_t* p[kMaxL + 1];
   int n;
@@ -62,7 +79,8 @@ struct Ws {
   int64_t S[kMaxL], gc[kMaxL], pool[kMaxL], arg[kMaxL], bsum[kMaxL], bnv[kMaxL + 1];
   int64_t ldS[kMaxL], ngather[kMaxL];
   int64_t dense, arg_r, rsum, dfp, tA, tB, tC, tD, tE, total;
-  int64_t xb;    // storage == 1: bf16 copy of the atom features (ld = ldS[0])
+  int64_t xb;    // bf16 copy of the atom features: storage == 1 (ld = ldS[0]); storage == 0 over 73..76 features
+                 // (ld = kOnePieceLd), used by the first block's one-piece form
   int64_t wimg;  // scratch of the forward products (split weight fragments in lane order, rebuilt by every launch)
   int64_t himg;  // more than 32 task outputs: the head matrix's two fragment images (head_bwd.hip: head_prep; the
                  // forward and the backward each make them of the weights they are given)
@@ -71,6 +89,8 @@ struct Ws {
 };
 
 static inline int64_t up8(int64_t n) { return (n + 7) / 8 * 8; }
+
+constexpr int64_t kOnePieceLd = 80;  // elements of a bf16 row of S0 / Xb in the first block's one-piece form
 
 static Ws carve(const gcmi_model_desc* m, int64_t N, int64_t B, int64_t ld_features) {
   Ws w;
@@ -97,6 +117,8 @@ static Ws carve(const gcmi_model_desc* m, int64_t N, int64_t B, int64_t ld_featu
     const int64_t wd = m->conv_width[l];
     w.S[l] = take_act(N, w.ldS[l]);
     if (h && l == 0) w.xb = take_act(N, w.ldS[0]);
+    // (fp32 storage: S[0]'s own block, N x 76 floats, is large enough for the bf16 sums of the one-piece form)
+    if (!h && l == 0 && up4(m->n_feat_in) == 76) w.xb = take((N * kOnePieceLd + 1) / 2);
     if (l == 0) w.wimg = take(kFwdHWimgFloats);
     w.gc[l] = take_act(N, wd);
     w.pool[l] = take_act(N, wd);
@@ -222,6 +244,40 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
 static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, float* d_grads,
                                  const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
                                  int64_t* grad_lo, int64_t* grad_hi, void* stream);
+
+// ------------------------------------------------------------------------------------------------------------------
+// storage == 0, the first GraphConv block over SMALL-INTEGER atom features (gcmi_model_io.features_small_int: every
+// element an integer with |x| <= 256 / max_deg).  Such an element is exactly one bf16 value, and so is every neighbour
+// sum (at most max_deg terms: an integer below 256).  The window pass then writes S0 and a copy Xb of the rows as bf16
+// (gather_lds.hip SumOpFH), the forward product reads them as they are (fwd_bf16.hip, fp32 output rows: 3 MFMAs per
+// k-step instead of 6 and no operand split) and the backward takes In = [S0 | Xb] in one piece against G in three
+// (bwd_fused.hip IB).  Every term the split-fp32 kernels compute is still computed: the two operand pieces that are
+// dropped are zero.  Conditions = what the bf16 kernels need (require_h below): fast product mode, BatchNorm on, the
+// default widths, window plans, reverse slots, the one-pass backward enabled.  Anything else runs the fp32 sequence.
+static bool one_piece_block0(const gcmi_model_desc* m, const gcmi_graph* g, const gcmi_model_io* io) {
+  if (!io->features_small_int || m->storage != 0 || !m->batch_norm || g->n_atoms <= 0) return false;
+  if (gemm_exact_mode() || !fused_bwd_enabled()) return false;
+  if (m->conv_width[0] != 64 || up4(m->n_feat_in) != 76 || m->max_deg < 1 || m->max_deg > 10) return false;
+  if (io->ld_features % 4 != 0 || io->ld_features < 76 || !aligned16(io->d_atom_features) || !aligned16(io->d_workspace))
+    return false;
+  if (!win_usable(g, 76, false) || !win_has_width(76)) return false;
+  return g->d_rev_pos != nullptr || g->n_edges == 0;
+}
+// What the last training forward on a workspace decided: the backward reads S0 / Xb in the form they were written,
+// whatever the options say by then.
+static std::mutex g_one_piece_mu;
+static std::map<const void*, bool> g_one_piece_ws;
+static void note_one_piece(const void* ws, bool on) {
+  std::lock_guard<std::mutex> lk(g_one_piece_mu);
+  if (on) g_one_piece_ws[ws] = true;
+  else g_one_piece_ws.erase(ws);
+}
+static bool noted_one_piece(const void* ws) {
+  std::lock_guard<std::mutex> lk(g_one_piece_mu);
+  return g_one_piece_ws.count(ws) != 0;
+}
+static std::atomic<int> g_one_piece_launches{0};
+int one_piece_launches() { return g_one_piece_launches.load(std::memory_order_relaxed); }
 
 #define RUN(call)            \
   do {                       \
@@ -537,6 +593,23 @@ using namespace gcmi;
 
 extern "C" {
 
+int gcmi_count_not_small_int(const float* d_x, int64_t ld, int64_t n_rows, int32_t n_cols, int32_t max_deg,
+                             int64_t* d_count, void* stream) {
+  GCMI_CHECK_ARG(d_count != nullptr && n_rows >= 0 && n_cols >= 0 && ld >= n_cols, "count_not_small_int: bad shape");
+  GCMI_CHECK_ARG(n_rows * (int64_t)n_cols == 0 || d_x != nullptr, "count_not_small_int: NULL matrix");
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(d_count, 0, sizeof(int64_t), st) != hipSuccess) {
+    set_error("count_not_small_int: memset failed");
+    return GCMI_ERR_LAUNCH;
+  }
+  if (n_rows * (int64_t)n_cols == 0) return GCMI_OK;
+  const float limit = (float)(256 / std::max(1, max_deg));
+  hipLaunchKernelGGL(small_int_count_kernel, dim3(grid_for(n_rows * (int64_t)n_cols, 256)), dim3(256), 0, st, d_x, ld, n_rows,
+                     n_cols, limit, reinterpret_cast<unsigned long long*>(d_count));
+  GCMI_CHECK_LAUNCH("count_not_small_int");
+  return GCMI_OK;
+}
+
 int64_t gcmi_model_workspace_floats(const gcmi_model_desc* m, int64_t n_atoms, int64_t n_mols) {
   if (check_desc(m) != GCMI_OK || n_atoms < 0 || n_mols < 0) return -1;
   // ld of the features is not known here: assume the padded width (worst case)
@@ -567,13 +640,33 @@ int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const floa
     return GCMI_ERR_LAUNCH;
   }
   bool stats_fused = false;
+  const bool one_piece = one_piece_block0(m, g, io);
+  note_one_piece(ws, one_piece);
   RUN(pack_biases(m, w, ws, d_params, st));
   for (int l = 0; l < L; ++l) {
     const int K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
     const int W = m->conv_width[l];
     const Segs sg = make_segs(g, K, W);
     stats_fused = false;
-    if (N > 0) {
+    if (l == 0 && one_piece) {
+      bf16_t* s0 = reinterpret_cast<bf16_t*>(ws + w.S[0]);
+      bf16_t* xb = reinterpret_cast<bf16_t*>(ws + w.xb);
+      double* stats = training ? reinterpret_cast<double*>(ws + w.acc) : nullptr;
+      {
+        TimedScope ts(GCMI_K_GATHER_SUM, st);
+        RUN(win_gather_sum_fh(g, x, ldx, 76, s0, xb, kOnePieceLd, st));
+      }
+      {
+        TimedScope ts(GCMI_K_SEG_GEMM, st);
+        const int rc = fwd_h_gemm(sg.n, sg.begin, sg.end, s0, kOnePieceLd, K, d_params + m->off_conv_w[0], sg.w_rel, xb,
+                                  kOnePieceLd, K, d_params + m->off_conv_w[0], sg.w_self, ws + w.bsum[0], sg.b_off, W, 0, 1,
+                                  nullptr, W, stats, ws + w.wimg, st, ws + w.gc[0]);
+        if (rc == GCMI_ERR_UNSUPPORTED) set_error("model_forward: the one-piece product of GraphConv 0 refused its shape");
+        RUN(rc);
+      }
+      g_one_piece_launches.fetch_add(1, std::memory_order_relaxed);
+      stats_fused = training != 0;
+    } else if (N > 0) {
       RUN(gcmi_gather_sum_fwd(g, x, ldx, (int32_t)w.ngather[l], ws + w.S[l], w.ldS[l], 0, stream));
       // training with BatchNorm: the product's epilogue also adds the column sums of its output into the
       // BatchNorm accumulators (clean: zeroed above, self-cleaning afterwards), so the layer output is not read again
@@ -817,8 +910,11 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
     float* dy = ws + w.tD;  // grad w.r.t. the (normalised) pool input
     float* dgc = ws + w.tA;  // grad w.r.t. the GraphConv pre-activation
     const Segs sg = make_segs(g, K, W);
-    const float* xin = l == 0 ? io->d_atom_features : ws + w.pool[l - 1];
-    const int64_t ldx = l == 0 ? io->ld_features : m->conv_width[l - 1];
+    // (one-piece form of the first block: S0 and the copy Xb of the atom features are bf16 rows, as the forward left them)
+    const bool one_piece = l == 0 && noted_one_piece(ws);
+    const float* xin = one_piece ? ws + w.xb : l == 0 ? io->d_atom_features : ws + w.pool[l - 1];
+    const int64_t ldx = one_piece ? kOnePieceLd : l == 0 ? io->ld_features : m->conv_width[l - 1];
+    const int64_t ldS = one_piece ? kOnePieceLd : w.ldS[l];
     float* dS = ws + w.tE;
     float* dX = ws + w.tC;
     // the fused pass covers the default widths in split-bf16 mode; it wants 16-byte rows of every operand
@@ -867,14 +963,15 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       // and the self part of dX
       TimedScope ts(GCMI_K_FUSED_BWD, st);
       const int rc = fused_conv_bwd(sg.n, sg.begin, sg.end, sg.w_rel, sg.w_self, sg.b_off, dy, W, ws + w.gc[l], W,
-                                    m->batch_norm ? coef : nullptr, W, ws + w.S[l], w.ldS[l], xin, ldx, K,
+                                    m->batch_norm ? coef : nullptr, W, ws + w.S[l], ldS, xin, ldx, K,
                                     d_params + m->off_conv_w[l], d_grads + m->off_conv_w[l], ws + w.dbsum[l],
                                     l > 0 ? dS : nullptr, K, l > 0 ? dX : nullptr, K,
                                     (l > 0 && sym && m->batch_norm) ? reinterpret_cast<double*>(ws + w.acc2) : nullptr,
-                                    st);
+                                    st, 0, one_piece ? 1 : 0);
       if (rc == GCMI_OK) {
         fused_done = true;
         have_psums = l > 0 && sym && m->batch_norm;
+        if (one_piece) g_one_piece_launches.fetch_add(1, std::memory_order_relaxed);
       }
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
       else if (m->batch_norm) {  // not covered after all (misaligned buffers): the separate pass, sums once more
@@ -886,6 +983,11 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
         RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
         dgc = dy;
       }
+    }
+    if (!fused_done && one_piece) {  // (the one-pass backward was switched off between the forward and this call)
+      set_error("model_loss_backward: the forward left the first block's operands as bf16 rows, and the one-pass "
+                "backward that reads them is not available now (GCMI_OPT_FUSED_BWD / GCMI_OPT_GEMM_EXACT changed?)");
+      return GCMI_ERR_UNSUPPORTED;
     }
     if (!fused_done) {
       RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, ws + w.S[l], w.ldS[l], K, dgc, W, W,

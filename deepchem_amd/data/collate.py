@@ -34,11 +34,17 @@ class DeviceBatch:
     n_samples     : real molecules in the batch (rows kept by TrimGraphOutput)
     """
 
-    def __init__(self, atom_features: torch.Tensor, graph: BatchGraph, n_samples: int, n_feat: int):
+    def __init__(self, atom_features: torch.Tensor, graph: BatchGraph, n_samples: int, n_feat: int,
+                 small_int_features: bool = False):
         self.atom_features = atom_features
         self.graph = graph
         self.n_samples = int(n_samples)
         self.n_feat = int(n_feat)
+        # every feature element is an integer with |x| <= 256 / max_deg (include/gcmi.h: features_small_int).  False
+        # unless the code that made the batch established it.
+        self.small_int_features = bool(small_int_features)
+        if self.small_int_features:
+            graph.note_small_int_features(atom_features)
 
     @property
     def n_atoms(self) -> int:
@@ -85,8 +91,9 @@ class HostBatch:
     device copy."""
 
     def __init__(self, arena, offsets, n_atoms, n_edges, n_sel, n_feat, ld, n_deg, deg_counts,
-                 symmetric, plan):
+                 symmetric, plan, small_int: bool = False):
         self.arena, self.off = arena, offsets
+        self.small_int = bool(small_int)      # the feature rows are small integers (for atom codes: what they expand to)
         self.n_atoms, self.n_edges, self.n_sel = n_atoms, n_edges, n_sel
         self.n_feat, self.ld, self.n_deg = n_feat, ld, n_deg
         self.deg_counts, self.symmetric = deg_counts, symmetric
@@ -164,13 +171,15 @@ def collate_host(packed: PackedMols, sel: Optional[np.ndarray], max_deg: int = 1
     adj_idx = np.ascontiguousarray(packed.adj_idx, np.int32)
     g = _lib.GcmiGraph()
     sym = ctypes.c_int32(1)
-    _lib.call("gcmi_collate_plans", feats.ctypes.data, n_feat, atom_ptr.ctypes.data, adj_ptr.ctypes.data,
+    small = ctypes.c_int32(0)
+    _lib.call("gcmi_collate_plans_p", feats.ctypes.data, n_feat, atom_ptr.ctypes.data, adj_ptr.ctypes.data,
               adj_idx.ctypes.data, sel.ctypes.data, n_sel, max_deg, base, ld, n_atoms,
               base + 4 * off["mem"], base + 4 * off["col"], n_edges, base + 4 * off["runs"],
               base + 4 * off["rev"], ctypes.byref(sym), int(win_cap), base + 4 * off["win"],
-              base + 4 * off["loc"], ctypes.byref(g))
+              base + 4 * off["loc"], ctypes.byref(g), 1 if coded else 0, ctypes.byref(small))
     counts = [g.deg_start[d + 1] - g.deg_start[d] for d in range(n_deg)]
-    hb = HostBatch(arena, off, n_atoms, n_edges, n_sel, n_feat, ld, n_deg, counts, bool(sym.value), g)
+    hb = HostBatch(arena, off, n_atoms, n_edges, n_sel, n_feat, ld, n_deg, counts, bool(sym.value), g,
+                   small_int=bool(small.value))
     hb.coded = coded
     return hb
 
@@ -197,7 +206,8 @@ def collate_to_device(packed: PackedMols, sel: Optional[np.ndarray], device: tor
         ld_out = ((75 + pad_features_to - 1) // pad_features_to) * pad_features_to
         feats = ops.expand_atom_codes(feats.view(torch.uint8), max(76, (ld_out + 3) // 4 * 4))
         n_feat = 75
-    return DeviceBatch(feats, graph, hb.n_sel if n_samples is None else n_samples, n_feat)
+    return DeviceBatch(feats, graph, hb.n_sel if n_samples is None else n_samples, n_feat,
+                       small_int_features=hb.small_int)
 
 
 def _is_symmetric(packed: PackedMols) -> bool:

@@ -63,10 +63,10 @@ class BatchPlan:
         off["end"] = max(off["rev"] + up4((self.n_edges + 3) // 4), 4)
         self.off = off
 
-    def host_batch(self, arena) -> HostBatch:
+    def host_batch(self, arena, small_int: bool = False) -> HostBatch:
         counts = [self.g.deg_start[d + 1] - self.g.deg_start[d] for d in range(self.n_deg)]
         return HostBatch(arena, self.off, self.n_atoms, self.n_edges, self.n_sel, self.n_feat, self.ld, self.n_deg,
-                         counts, True, self.g)
+                         counts, True, self.g, small_int=small_int)
 
 
 def plan_batch(mol_hist: np.ndarray, atom_ptr: np.ndarray, sel: np.ndarray, n_feat: int, ld: int, max_deg: int = 10,
@@ -114,6 +114,21 @@ class ResidentMolSet:
         self.d_adj_idx = torch.from_numpy(np.ascontiguousarray(packed.adj_idx, np.int32)).to(dev)
         self.d_rank = torch.from_numpy(np.ascontiguousarray(rank)).to(dev)
         self.d_rev = torch.from_numpy(np.ascontiguousarray(rev)).to(dev)
+        # "every feature element is an integer with |x| <= 256 / max_deg" (include/gcmi.h: features_small_int): decided
+        # ONCE for the set -- every batch is a selection of its rows.  Codes: one-hot columns expand to 0 / 1, so it is
+        # the three value bytes (formal charge, radical electrons, aromatic flag) that have to be within the limit;
+        # float rows: one pass on the device over the rows just uploaded.
+        lim = 256 // max(1, self.max_deg)
+        if self.coded:
+            c = np.ascontiguousarray(packed.atom_codes).reshape(-1, 8)
+            self.small_int = bool(c.shape[0] == 0 or (np.abs(c[:, 3].view(np.int8).astype(np.int32)).max() <= lim and
+                                                      c[:, 4].max() <= lim and c[:, 6].max() <= lim))
+        else:
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            _lib.call("gcmi_count_not_small_int", self.d_feats.data_ptr(), self.n_feat, int(self.d_feats.shape[0]),
+                      self.n_feat, self.max_deg, count.data_ptr(),
+                      ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+            self.small_int = int(count.item()) == 0
         torch.cuda.current_stream(dev).synchronize()  # the collating streams start reading right away
 
     @staticmethod
@@ -137,7 +152,7 @@ class ResidentMolSet:
         if ring is not None:
             ring.mark()
         arena = torch.empty(plan.off["end"], dtype=torch.float32, device=dev)
-        hb = plan.host_batch(None)
+        hb = plan.host_batch(None, self.small_int)
         base = arena.data_ptr()
         off = plan.off
         d_off = plan.offsets
@@ -165,4 +180,5 @@ class ResidentMolSet:
             ld_out = ((75 + self.pad_features_to - 1) // self.pad_features_to) * self.pad_features_to
             feats = ops.expand_atom_codes(feats.view(torch.uint8), max(76, (ld_out + 3) // 4 * 4))
             n_feat = 75
-        return DeviceBatch(feats, graph, n_sel if n_samples is None else n_samples, n_feat)
+        return DeviceBatch(feats, graph, n_sel if n_samples is None else n_samples, n_feat,
+                           small_int_features=self.small_int)

@@ -57,6 +57,9 @@ class BatchGraph:
         self.membership = membership
         self.device = col_idx.device
         self.symmetric = symmetric
+        # "every element of the atom-feature matrix at address ... is an integer with |x| <= 256 / max_deg": a property
+        # of the BATCH, established where it is collated (note_small_int_features); a graph built by hand has none
+        self._small_int_ptr = None
         self.n_mols = None
         self.mol_runs = None
         self.c = GcmiGraph()
@@ -116,6 +119,14 @@ class BatchGraph:
         self.n_mols = int(n_mols)
         self.mol_runs = mol_runs
         self.c.d_mol_runs = mol_runs.data_ptr()
+
+    def note_small_int_features(self, features: Optional[torch.Tensor]):
+        """State that the batch's atom-feature matrix ``features`` holds small integers only (``None``: withdraw).
+        The statement is tied to that tensor's storage: another matrix run over the same graph does not inherit it."""
+        self._small_int_ptr = None if features is None else int(features.data_ptr())
+
+    def small_int_features(self, features: torch.Tensor) -> bool:
+        return self._small_int_ptr is not None and self._small_int_ptr == int(features.data_ptr())
 
     def attach_rev_pos(self, rev: torch.Tensor):
         """Reverse edge slots computed by the host collation (symmetric adjacency)."""

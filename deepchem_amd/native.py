@@ -185,6 +185,8 @@ class NativeNet:
         io = GcmiModelIO()
         io.d_atom_features = x.data_ptr()
         io.ld_features = int(x.stride(0)) if x.shape[0] > 1 else int(x.shape[1])
+        # (the collation's statement about THIS matrix; anything else makes no promise and runs the fp32 kernels)
+        io.features_small_int = 1 if (graph.max_deg == d.max_deg and graph.small_int_features(x)) else 0
         io.d_workspace = self._workspace(graph.n_atoms, B).data_ptr()
         if d.batch_norm:
             for i in range(self.n_layers + 1):

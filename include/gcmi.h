@@ -125,7 +125,10 @@ enum {
    * rounds with two rounds in flight and the run bounds held in registers (readout.hip); 0: run by run, one round
    * at a time.  Same rows in the same order: the results are bit-identical.  Environment: GCMI_READOUT_PRE=0
    * before the library is loaded.                                                                              */
-  GCMI_OPT_READOUT_PIPELINED = 5
+  GCMI_OPT_READOUT_PIPELINED = 5,
+  /* read-only (gcmi_get_option): launches so far of the first GraphConv block's one-piece kernels (forward product and
+   * backward each count one), taken when gcmi_model_io.features_small_int holds                                  */
+  GCMI_OPT_ONE_PIECE_LAUNCHES = 6
 };
 int gcmi_set_option(int32_t option, int32_t value);
 int gcmi_get_option(int32_t option, int32_t* value);
@@ -164,6 +167,18 @@ int gcmi_collate_plans(const float* atom_features, int64_t n_feat, const int64_t
                        int64_t cap_edges, int32_t* out_mol_runs, uint8_t* out_rev_pos,
                        int32_t* out_symmetric, int32_t win_cap, int32_t* out_win_meta,
                        uint16_t* out_win_edges, gcmi_graph* graph);
+/* The same, and *out_small_int = 1 when every feature element of the batch is an integer with
+ * |x| <= 256 / max(1, max_deg) (gcmi_model_io.features_small_int; tested while a row is copied, no second pass), else 0.
+ * atom_codes != 0: the rows are 8-byte atom codes (n_feat = 2 "floats"; gcmi_expand_atom_codes) and the test is made on
+ * what they expand to: one-hot columns are 0 / 1, so it is the three value bytes -- formal charge (int8), radical
+ * electrons, aromatic flag -- that must be within the limit.                                                        */
+int gcmi_collate_plans_p(const float* atom_features, int64_t n_feat, const int64_t* atom_ptr,
+                         const int64_t* adj_ptr, const int32_t* adj_idx, const int64_t* sel,
+                         int64_t n_sel, int32_t max_deg, float* out_features, int64_t out_ld,
+                         int64_t cap_atoms, int32_t* out_membership, int32_t* out_col_idx,
+                         int64_t cap_edges, int32_t* out_mol_runs, uint8_t* out_rev_pos,
+                         int32_t* out_symmetric, int32_t win_cap, int32_t* out_win_meta,
+                         uint16_t* out_win_edges, gcmi_graph* graph, int32_t atom_codes, int32_t* out_small_int);
 
 /* ---------------------------------------------------------------- collation on the device
  * The same batches (ConvMol.agglomerate_mols, feat/mol_graphs.py:256-349; the arena gcmi_collate_plans
@@ -528,7 +543,24 @@ typedef struct gcmi_model_io {
   float* d_probs;                        /* classification softmax; may be NULL              */
   float* d_fingerprint;                  /* n_mols x 2*dense_width                           */
   float* d_loss;                         /* 1 float (loss_backward)                          */
+  int32_t features_small_int;            /* a PROMISE about d_atom_features (0 = none): every element, pad columns
+                                            included, is an integer with |x| <= 256 / max(1, max_deg) -- 25 for
+                                            max_deg 10; what ConvMolFeaturizer rows (one-hot blocks, small counts)
+                                            are.  Such elements and their neighbour sums (< 256) are exact in bf16,
+                                            and gcmi_model_forward / _loss_backward (storage 0, fast product mode,
+                                            BatchNorm, widths 64 over 73..76 features, window plans and reverse slots
+                                            on the graph) then run the first GraphConv block on one-piece bf16
+                                            operands: the same terms, half the matrix work.  Established where the
+                                            batch is made (gcmi_collate_plans_p, gcmi_count_not_small_int); a false
+                                            promise gives rounded features without notice.  gcmi_small_*: ignored. */
+  int32_t reserved_;
 } gcmi_model_io;
+
+/* How many elements of the n_rows x n_cols device matrix d_x (row stride ld) are NOT integers with
+ * |x| <= 256 / max(1, max_deg) (NaN and infinities count) -> *d_count (device, one int64), one pass on `stream`.
+ * 0 = the features_small_int promise may be made.  For tests and for sets that live on the device; no step launches it. */
+int gcmi_count_not_small_int(const float* d_x, int64_t ld, int64_t n_rows, int32_t n_cols, int32_t max_deg,
+                             int64_t* d_count, void* stream);
 
 /* floats of workspace needed for a batch of n_atoms / n_mols (forward + backward). */
 int64_t gcmi_model_workspace_floats(const gcmi_model_desc* m, int64_t n_atoms, int64_t n_mols);
