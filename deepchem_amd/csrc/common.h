@@ -104,6 +104,108 @@ int bn_bwd_params_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, con
                        const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, void* stream,
                        double* d_loss_acc = nullptr, int loss_rep = 0, float loss_inv_count = 0.f, float* d_loss = nullptr);
 
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// ---- One segmented forward product,
+//     out[rows of s] = act(a1[rows of s] . w1[s] + a2[rows of s] . w2[s] + bias[s])      for the row segments s,
+// as its kernels are handed it (gemm.hip, gemm_split.hip, fwd_fused.hip, fwd_bf16.hip).  TA / TO = element type of the
+// operand / output rows: float, or unsigned short for rows stored as raw bf16 patterns (leading dimensions in elements).
+template <typename TA>
+struct SegOperand {
+  const TA* a = nullptr;           // rows; nullptr: term absent
+  int64_t ld = 0;
+  int32_t k = 0;                   // columns contracted
+  const float* w = nullptr;        // weights, k x n_out per segment (trans_w: n_out x k, nn.Linear)
+  const int64_t* w_off = nullptr;  // per segment: where its block starts in w; < 0: term absent in that segment
+};
+template <typename TA, typename TO = TA>
+struct SegProduct {
+  int32_t n_seg = 0;
+  const int32_t* seg_begin = nullptr;  // rows [seg_begin[s], seg_end[s])
+  const int32_t* seg_end = nullptr;
+  SegOperand<TA> op[2];
+  const float* bias = nullptr;
+  const int64_t* bias_off = nullptr;  // per segment, into bias; < 0: none
+  int32_t n_out = 0;
+  int32_t trans_w = 0;
+  int32_t act = 0;  // 0 none, 1 ReLU, 2 out += result
+  TO* out = nullptr;
+  int64_t ldo = 0;
+};
+
+// One segment, rows [0, *n_rows) of one operand against one weight block and bias row (the dense layer, the task head
+// and their input gradients; callers set trans_w and act by name).  The description holds pointers: *n_rows must
+// outlive it.
+inline constexpr int32_t kZero32 = 0;
+inline constexpr int64_t kZero64 = 0;
+template <typename TA, typename TO>
+inline SegProduct<TA, TO> one_segment(const int32_t* n_rows, const TA* a, int64_t lda, int32_t k, const float* w,
+                                      const float* bias, int32_t n_out, TO* out, int64_t ldo) {
+  SegProduct<TA, TO> p;
+  p.n_seg = 1;
+  p.seg_begin = &kZero32;
+  p.seg_end = n_rows;
+  p.op[0] = {a, lda, k, w, &kZero64};
+  p.bias = bias;
+  p.bias_off = bias ? &kZero64 : nullptr;
+  p.n_out = n_out;
+  p.out = out;
+  p.ldo = ldo;
+  return p;
+}
+
+// The shapes of the default model that the persistent forward kernels cover (fwd_fused.hip in split-bf16 mode,
+// fwd_bf16.hip over bf16 rows):
+//   kFwdConv80  two operands of 65..80 columns -> 64 columns (the first GraphConv)
+//   kFwdConv    two operands of 33..64 columns -> 64 columns (GraphConv over pooled rows)
+//   kFwdDense   one operand of 33..64 columns -> 128 columns in nn.Linear layout (the atom-level dense layer)
+// with no activation or ReLU, 16-byte addressable rows (ld a multiple of 4 floats / 8 bf16 elements) and 32-bit
+// element offsets (rows * ld < 2^30).  Anything else: kFwdNone, and the caller answers GCMI_ERR_UNSUPPORTED.
+constexpr int kMaxProductSeg = 16;  // segments of a product (= kMaxSeg, kS3MaxSeg, kWMaxSeg, kHMaxSeg of its kernels' files)
+enum FwdShape { kFwdNone = 0, kFwdConv80, kFwdConv, kFwdDense };
+template <typename TA, typename TO>
+inline FwdShape fwd_shape(const SegProduct<TA, TO>& p) {
+  const SegOperand<TA>&a1 = p.op[0], &a2 = p.op[1];
+  if (p.n_seg > kMaxProductSeg || (p.act != 0 && p.act != 1) || a1.a == nullptr) return kFwdNone;
+  const bool two = a2.a != nullptr;
+  const bool conv_like = two && !p.trans_w && p.n_out == 64 && a1.k == a2.k;
+  const FwdShape shape = (conv_like && a1.k > 64 && a1.k <= 80)                            ? kFwdConv80
+                         : (conv_like && a1.k > 32 && a1.k <= 64)                          ? kFwdConv
+                         : (!two && p.trans_w && p.n_out == 128 && a1.k > 32 && a1.k <= 64) ? kFwdDense
+                                                                                           : kFwdNone;
+  if (shape == kFwdNone) return kFwdNone;
+  constexpr int64_t kPiece = 16 / sizeof(TA);  // elements of a 16-byte piece of an operand row
+  if (!aligned16(a1.a) || a1.ld % kPiece || (two && (!aligned16(a2.a) || a2.ld % kPiece)) || !aligned16(p.out) ||
+      p.ldo % kPiece || p.ldo < p.n_out || (p.bias && !aligned16(p.bias)))
+    return kFwdNone;
+  int64_t rows = 0;
+  for (int s = 0; s < p.n_seg; ++s) rows = std::max<int64_t>(rows, p.seg_end[s]);
+  if (rows * std::max(std::max(a1.ld, two ? a2.ld : 0), p.ldo) >= (int64_t)1 << 30) return kFwdNone;
+  return shape;
+}
+// The per-segment table a product kernel takes by value (SegTable, SegTable3, FwdTable, FwdHTable: one type per file),
+// for tiles of tile_rows rows: its segments and tile starts, and the offsets into its three arrays (one per operand and
+// the bias; -1 = absent).  Returns the number of tiles.
+template <typename Table, typename TA, typename TO>
+inline int64_t fill_seg_table(Table& st, int64_t* w1_off, int64_t* w2_off, int64_t* bias_off, const SegProduct<TA, TO>& p,
+                              int tile_rows) {
+  memset(&st, 0, sizeof(st));
+  st.n_seg = p.n_seg;
+  int64_t tiles = 0;
+  for (int s = 0; s < kMaxProductSeg; ++s) {
+    const bool in = s < p.n_seg;
+    st.tile_start[s] = (int32_t)tiles;
+    st.seg_begin[s] = in ? p.seg_begin[s] : 0;
+    st.seg_end[s] = in ? p.seg_end[s] : 0;
+    w1_off[s] = (in && p.op[0].a && p.op[0].w_off) ? p.op[0].w_off[s] : -1;
+    w2_off[s] = (in && p.op[1].a && p.op[1].w_off) ? p.op[1].w_off[s] : -1;
+    bias_off[s] = (in && p.bias && p.bias_off) ? p.bias_off[s] : -1;
+    if (in) tiles += (p.seg_end[s] - p.seg_begin[s] + tile_rows - 1) / tile_rows;
+  }
+  st.tile_start[kMaxProductSeg] = (int32_t)tiles;
+  return tiles;
+}
+
 // ---- bf16 activation storage (gcmi_model_desc.storage == 1): raw 16-bit patterns, leading dimensions in elements
 bool win_usable_h(const gcmi_graph* g, int n_feat);
 int win_gather_sum_fh(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_feat, unsigned short* d_s,
@@ -121,13 +223,11 @@ bool win_two_stage_usable_h(const gcmi_graph* g, int n_feat);
 int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const unsigned short* d_ds, int64_t ldds, int n_feat,
                                 unsigned short* d_dxs, int64_t lddxs, const uint8_t* d_arg, unsigned short* d_dy,
                                 int64_t lddy, hipStream_t st);
-// fwd_bf16.hip: forward product over bf16 operands, bf16 output, BatchNorm sums of the rounded output
-// (d_out_f32: fp32 output rows and sums of the unrounded values instead -- the two-operand 65..80-column shape only)
-int fwd_h_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const unsigned short* d_a1, int64_t lda1,
-               int32_t k1, const float* d_w1, const int64_t* w1_off, const unsigned short* d_a2, int64_t lda2, int32_t k2,
-               const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off, int32_t n_out,
-               int32_t trans_w, int32_t act, unsigned short* d_out, int64_t ldo, double* d_stats, float* d_wimg_scratch,
-               hipStream_t sm, float* d_out_f32 = nullptr);
+// fwd_bf16.hip: forward product over bf16 operands (shapes: fwd_shape above), BatchNorm sums of the rounded output.
+// TO = unsigned short: bf16 output rows; TO = float: fp32 output rows and sums of the unrounded values -- the
+// two-operand 65..80-column shape only
+template <typename TO>
+int fwd_h_gemm(const SegProduct<unsigned short, TO>& p, double* d_stats, float* d_wimg_scratch, hipStream_t sm);
 int fwd_weight_images(int32_t n_seg, const int64_t* w1_off, const int64_t* w2_off, const float* d_w1, const float* d_w2,
                       int32_t k_in, int32_t ko, int32_t n_ops, int32_t n_out, int32_t trans_w, float* d_scratch,
                       hipStream_t sm);
@@ -151,11 +251,7 @@ int launch_wgrad3(const SlabTable& st, int slabs, const float* d_a, int64_t lda,
 
 // gemm_split.hip: the segmented GEMM on the bf16 matrix cores with exactly split fp32 operands;
 // GCMI_ERR_UNSUPPORTED = shape not covered (fall back to gemm.hip)
-int launch_seg_gemm4(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1,
-                     int64_t lda1, int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2,
-                     int64_t lda2, int32_t k2, const float* d_w2, const int64_t* w2_off, const float* d_bias,
-                     const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act, float* d_out,
-                     int64_t ldo, hipStream_t sm, double* d_stats = nullptr);
+int launch_seg_gemm4(const SegProduct<float>& p, hipStream_t sm, double* d_stats = nullptr);
 
 // bwd_fused.hip: BatchNorm-backward + weight gradients + input gradients of one block in one pass over the rows;
 // GCMI_ERR_UNSUPPORTED = switched off / exact mode / shape not covered (the caller runs the separate kernels)
@@ -177,13 +273,9 @@ int fused_dense_bwd(int64_t n_rows, const int32_t* d_membership, const float* d_
                     const float* d_p, int64_t ldp, int32_t k_in, const float* d_w, float* d_dw, float* d_db,
                     float* d_dp, int64_t lddp, double* d_psums, hipStream_t sm, int32_t act_bf16 = 0);
 
-// fwd_fused.hip: the forward product of a block as persistent workgroups with resident weight images (default widths,
-// split-bf16 mode); GCMI_ERR_UNSUPPORTED = shape not covered
-int fwd_fused_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1, int64_t lda1,
-                   int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2, int64_t lda2, int32_t k2,
-                   const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off,
-                   int32_t n_out, int32_t trans_w, int32_t act, float* d_out, int64_t ldo, double* d_stats,
-                   hipStream_t sm, float* d_wimg_scratch = nullptr);
+// fwd_fused.hip: the forward product of a block as persistent workgroups with resident weight images (split-bf16 mode,
+// shapes: fwd_shape above); GCMI_ERR_UNSUPPORTED = shape not covered
+int fwd_fused_gemm(const SegProduct<float>& p, double* d_stats, hipStream_t sm, float* d_wimg_scratch = nullptr);
 
 // head_bwd.hip: loss + d logits + task-head gradients + tanh' of the readout + the dense BatchNorm's backward sums in
 // one kernel over the molecules (<= 32 outputs), or two on the matrix cores (33..256 outputs, d_dl_scratch = n_mols x
@@ -208,13 +300,12 @@ int loss_finalize_impl(double* d_acc, float inv_count, float* d_loss, void* stre
 // accumulator replicas of the BatchNorm column sums (same-address fp64 atomics serialise); scratch layout in
 // doubles: [0, 2F) backward coefficient vectors, then kBnReplicas blocks of [sum(F) | sum of squares(F)]
 constexpr int kBnReplicas = 32;
-// gcmi_seg_gemm with the column sums of the output (after bias and activation) added into d_stats in that layout
+// gcmi_seg_gemm on a description (gemm.hip): the same argument checks, the same kernels
+int seg_gemm(const SegProduct<float>& p, hipStream_t sm);
+// ... with the column sums of the output (after bias and activation) added into d_stats in that layout
 // by the product's own epilogue; *fused = false (and nothing added) when the kernel in charge cannot do it
-int seg_gemm_stats(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1, int64_t lda1,
-                   int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2, int64_t lda2, int32_t k2,
-                   const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off,
-                   int32_t n_out, int32_t trans_w, int32_t act, float* d_out, int64_t ldo, double* d_stats,
-                   bool* fused, void* stream, float* d_wimg_scratch = nullptr);
+int seg_gemm_stats(const SegProduct<float>& p, double* d_stats, bool* fused, hipStream_t sm,
+                   float* d_wimg_scratch = nullptr);
 // gcmi_readout_fwd that also leaves the per-molecule sums of the rows before the folded BatchNorm in d_rawsum
 int readout_fwd_impl(const gcmi_graph* g, const float* d_x, int64_t ldx, int32_t n_feat, const float* d_scale,
                      const float* d_shift, int32_t act, float* d_out, int64_t ldo, int32_t* d_arg, float* d_rawsum,
@@ -264,8 +355,6 @@ __device__ __forceinline__ bool bn_pool_ill_conditioned(const float* __restrict_
   }
   return __ballot(bad) != 0ull;
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // vector width usable for a row-major matrix access
 inline int vec_width(const void* p, int64_t ld, int n_feat) {

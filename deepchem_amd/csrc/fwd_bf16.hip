@@ -24,7 +24,7 @@
 
 namespace gcmi {
 
-constexpr int kHMaxSeg = 16;
+constexpr int kHMaxSeg = kMaxProductSeg;
 
 struct FwdHTable {
   int32_t n_seg;
@@ -458,67 +458,34 @@ int fwd_weight_images(int32_t n_seg, const int64_t* w1_off, const int64_t* w2_of
   return GCMI_OK;
 }
 
-// The shapes of the default model: two operands of 65..80 columns -> 64 columns (the first GraphConv), two 64-column
-// operands -> 64 columns (GraphConv over pooled rows), one 64-column operand -> 128 columns in nn.Linear layout (the
-// atom-level dense layer).  Anything else: GCMI_ERR_UNSUPPORTED (bf16 storage is for these shapes).
-int fwd_h_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const bf16_t* d_a1, int64_t lda1,
-               int32_t k1, const float* d_w1, const int64_t* w1_off, const bf16_t* d_a2, int64_t lda2, int32_t k2,
-               const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off, int32_t n_out,
-               int32_t trans_w, int32_t act, bf16_t* d_out, int64_t ldo, double* d_stats, float* d_wimg_scratch,
-               hipStream_t sm, float* d_out_f32) {
-  // (d_out_f32: the output rows are fp32 -- the exact-operand form of the first GraphConv; d_out is not used then)
-  if (d_out_f32 != nullptr) d_out = reinterpret_cast<bf16_t*>(d_out_f32);
-  if (n_seg > kHMaxSeg || d_wimg_scratch == nullptr || !aligned16(d_wimg_scratch) || (act != 0 && act != 1) || gemm_exact_mode()) return GCMI_ERR_UNSUPPORTED;
-  const bool two = d_a1 != nullptr && d_a2 != nullptr;
-  const bool conv = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 32 && k1 <= 64;
-  const bool conv80 = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 64 && k1 <= 80;
-  const bool dense = !two && d_a1 != nullptr && trans_w && n_out == 128 && k1 > 32 && k1 <= 64;
-  if (!conv && !dense && !conv80) return GCMI_ERR_UNSUPPORTED;
-  if (d_out_f32 != nullptr && !conv80) return GCMI_ERR_UNSUPPORTED;
-  if (!aligned16(d_a1) || lda1 % 8 || (two && (!aligned16(d_a2) || lda2 % 8)) || !aligned16(d_out) || ldo % 8 ||
-      ldo < n_out || (d_bias && !aligned16(d_bias)))
-    return GCMI_ERR_UNSUPPORTED;
-  int64_t rows = 0;
-  for (int s = 0; s < n_seg; ++s) rows = std::max<int64_t>(rows, seg_end[s]);
-  if (rows * std::max(std::max(lda1, two ? lda2 : 0), ldo) >= (int64_t)1 << 30) return GCMI_ERR_UNSUPPORTED;
+// The shapes of fwd_shape (common.h).  Anything else: GCMI_ERR_UNSUPPORTED (bf16 storage is for these shapes).
+template <typename TO>
+int fwd_h_gemm(const SegProduct<bf16_t, TO>& p, double* d_stats, float* d_wimg_scratch, hipStream_t sm) {
+  // (fp32 output rows: the exact-operand form of the first GraphConv)
+  constexpr bool kF32Out = sizeof(TO) == sizeof(float);
+  if (d_wimg_scratch == nullptr || !aligned16(d_wimg_scratch) || gemm_exact_mode()) return GCMI_ERR_UNSUPPORTED;
+  const FwdShape shape = fwd_shape(p);
+  if (shape == kFwdNone || (kF32Out && shape != kFwdConv80)) return GCMI_ERR_UNSUPPORTED;
   FwdHTable st;
-  memset(&st, 0, sizeof(st));
-  st.n_seg = n_seg;
-  int64_t tiles = 0;
-  for (int s = 0; s < kHMaxSeg; ++s) {
-    st.tile_start[s] = (int32_t)tiles;
-    st.w_off[0][s] = st.w_off[1][s] = st.b_off[s] = -1;
-    if (s < n_seg) {
-      st.seg_begin[s] = seg_begin[s];
-      st.seg_end[s] = seg_end[s];
-      st.w_off[0][s] = w1_off ? w1_off[s] : -1;
-      st.w_off[1][s] = (two && w2_off) ? w2_off[s] : -1;
-      st.b_off[s] = (d_bias && bias_off) ? bias_off[s] : -1;
-      tiles += (seg_end[s] - seg_begin[s] + 63) / 64;
-    }
-  }
-  st.tile_start[kHMaxSeg] = (int32_t)tiles;
+  const int64_t tiles = fill_seg_table(st, st.w_off[0], st.w_off[1], st.b_off, p, 64);
   if (tiles == 0) return GCMI_OK;
   FwdHArgs a;
   memset(&a, 0, sizeof(a));
-  a.in[0] = d_a1; a.ldin[0] = (int32_t)lda1; a.in[1] = d_a2; a.ldin[1] = (int32_t)lda2; a.k_in = k1;
-  a.w[0] = d_w1; a.w[1] = d_w2; a.bias = d_bias; a.out = d_out; a.ldo = (int32_t)ldo; a.relu = act; a.stats = d_stats;
-  {  // the segments' weight fragments, split once (kFwdHWimgFloats of scratch cover every shape above)
-    u32x4* wimg = reinterpret_cast<u32x4*>(d_wimg_scratch);
-    const int KO = conv80 ? 80 : 64, NOPS = two ? 2 : 1;
-    const int entries = n_seg * (n_out / 32) * (NOPS * KO / 16) * 64;
-    const int blocks = std::min((entries + 255) / 256, 1024);
-    if (trans_w)
-      hipLaunchKernelGGL(wprep_kernel<true>, dim3(blocks), dim3(256), 0, sm, st, d_w1, d_w2, k1, KO, NOPS, n_out, wimg);
-    else
-      hipLaunchKernelGGL(wprep_kernel<false>, dim3(blocks), dim3(256), 0, sm, st, d_w1, d_w2, k1, KO, NOPS, n_out, wimg);
-    GCMI_CHECK_LAUNCH("fwd_h wprep");
-    a.wimg = wimg;
-  }
-  if (conv80 && d_out_f32 != nullptr) return launch_fwd_hd<2, 80, 64, false, true>(st, (int)tiles, a, sm);
-  if (conv80) return launch_fwd_hd<2, 80, 64, false>(st, (int)tiles, a, sm);
-  if (conv) return launch_fwd_hd<2, 64, 64, false>(st, (int)tiles, a, sm);
+  a.in[0] = p.op[0].a; a.ldin[0] = (int32_t)p.op[0].ld; a.in[1] = p.op[1].a; a.ldin[1] = (int32_t)p.op[1].ld;
+  a.k_in = p.op[0].k; a.w[0] = p.op[0].w; a.w[1] = p.op[1].w; a.bias = p.bias; a.out = p.out; a.ldo = (int32_t)p.ldo;
+  a.relu = p.act; a.stats = d_stats;
+  // the segments' weight fragments, split once (kFwdHWimgFloats of scratch cover every shape above)
+  const int rc = fwd_weight_images(p.n_seg, p.op[0].w_off, p.op[1].w_off, p.op[0].w, p.op[1].w, p.op[0].k,
+                                   shape == kFwdConv80 ? 80 : 64, shape == kFwdDense ? 1 : 2, p.n_out, p.trans_w,
+                                   d_wimg_scratch, sm);
+  if (rc != GCMI_OK) return rc;
+  a.wimg = reinterpret_cast<const u32x4*>(d_wimg_scratch);
+  if constexpr (kF32Out) return launch_fwd_hd<2, 80, 64, false, true>(st, (int)tiles, a, sm);
+  if (shape == kFwdConv80) return launch_fwd_hd<2, 80, 64, false>(st, (int)tiles, a, sm);
+  if (shape == kFwdConv) return launch_fwd_hd<2, 64, 64, false>(st, (int)tiles, a, sm);
   return launch_fwd_hd<1, 64, 128, true>(st, (int)tiles, a, sm);
 }
+template int fwd_h_gemm(const SegProduct<bf16_t, float>&, double*, float*, hipStream_t);
+template int fwd_h_gemm(const SegProduct<bf16_t, bf16_t>&, double*, float*, hipStream_t);
 
 }  // namespace gcmi

@@ -15,7 +15,7 @@
 
 namespace gcmi {
 
-constexpr int kWMaxSeg = 16;
+constexpr int kWMaxSeg = kMaxProductSeg;
 
 struct FwdTable {
   int32_t n_seg;
@@ -611,59 +611,29 @@ static int launch_fwd_reg(const FwdTable& st, int n_tiles, const FwdArgs& a, hip
   return GCMI_OK;
 }
 
-// The shapes of the default model in split-bf16 mode: two operands of 65..80 columns -> 64 columns (the first
-// GraphConv: fwd_reg_kernel), two 64-column operands -> 64 columns (GraphConv over pooled rows), one 64-column
-// operand -> 128 columns in nn.Linear layout (the atom-level dense layer).  Anything else:
-// GCMI_ERR_UNSUPPORTED, and the caller runs seg_gemm4_kernel.  *fused: the BatchNorm sums were added to d_stats.
-int fwd_fused_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1, int64_t lda1,
-                   int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2, int64_t lda2, int32_t k2,
-                   const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off,
-                   int32_t n_out, int32_t trans_w, int32_t act, float* d_out, int64_t ldo, double* d_stats,
-                   hipStream_t sm, float* d_wimg_scratch) {
-  if (!fwd_fused_on() || !fused_bwd_enabled() || n_seg > kWMaxSeg || (act != 0 && act != 1)) return GCMI_ERR_UNSUPPORTED;
-  const bool two = d_a1 != nullptr && d_a2 != nullptr;
-  const bool conv = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 32 && k1 <= 64;
-  const bool conv80 = two && !trans_w && n_out == 64 && k1 == k2 && k1 > 64 && k1 <= 80;
-  const bool dense = !two && d_a1 != nullptr && trans_w && n_out == 128 && k1 > 32 && k1 <= 64;
-  if (!conv && !dense && !conv80) return GCMI_ERR_UNSUPPORTED;
-  if (!aligned16(d_a1) || lda1 % 4 || (two && (!aligned16(d_a2) || lda2 % 4)) || !aligned16(d_out) || ldo % 4 ||
-      (d_bias && !aligned16(d_bias)))
-    return GCMI_ERR_UNSUPPORTED;
-  int64_t rows = 0;
-  for (int s = 0; s < n_seg; ++s) rows = std::max<int64_t>(rows, seg_end[s]);
-  if (rows * std::max(std::max(lda1, two ? lda2 : 0), ldo) >= (int64_t)1 << 30) return GCMI_ERR_UNSUPPORTED;
-  const int tile_rows = conv ? 128 : 64;
+// The shapes of fwd_shape (common.h); kFwdConv80 on fwd_reg_kernel.  Anything else: GCMI_ERR_UNSUPPORTED, and the caller
+// runs seg_gemm4_kernel.  d_stats: the BatchNorm sums are added there.
+int fwd_fused_gemm(const SegProduct<float>& p, double* d_stats, hipStream_t sm, float* d_wimg_scratch) {
+  if (!fwd_fused_on() || !fused_bwd_enabled()) return GCMI_ERR_UNSUPPORTED;
+  const FwdShape shape = fwd_shape(p);
+  if (shape == kFwdNone) return GCMI_ERR_UNSUPPORTED;
   FwdTable st;
-  memset(&st, 0, sizeof(st));
-  st.n_seg = n_seg;
-  int64_t tiles = 0;
-  for (int s = 0; s < kWMaxSeg; ++s) {
-    st.tile_start[s] = (int32_t)tiles;
-    st.w_off[0][s] = st.w_off[1][s] = st.b_off[s] = -1;
-    if (s < n_seg) {
-      st.seg_begin[s] = seg_begin[s];
-      st.seg_end[s] = seg_end[s];
-      st.w_off[0][s] = w1_off ? w1_off[s] : -1;
-      st.w_off[1][s] = (two && w2_off) ? w2_off[s] : -1;
-      st.b_off[s] = (d_bias && bias_off) ? bias_off[s] : -1;
-      tiles += (seg_end[s] - seg_begin[s] + tile_rows - 1) / tile_rows;
-    }
-  }
-  st.tile_start[kWMaxSeg] = (int32_t)tiles;
+  const int64_t tiles = fill_seg_table(st, st.w_off[0], st.w_off[1], st.b_off, p, shape == kFwdConv ? 128 : 64);
   if (tiles == 0) return GCMI_OK;
   FwdArgs a;
   memset(&a, 0, sizeof(a));
-  a.in[0] = d_a1; a.ldin[0] = (int32_t)lda1; a.in[1] = d_a2; a.ldin[1] = (int32_t)lda2; a.k_in = k1;
-  a.w[0] = d_w1; a.w[1] = d_w2; a.bias = d_bias; a.out = d_out; a.ldo = (int32_t)ldo; a.relu = act; a.stats = d_stats;
-  if (conv80) {
+  a.in[0] = p.op[0].a; a.ldin[0] = (int32_t)p.op[0].ld; a.in[1] = p.op[1].a; a.ldin[1] = (int32_t)p.op[1].ld;
+  a.k_in = p.op[0].k; a.w[0] = p.op[0].w; a.w[1] = p.op[1].w; a.bias = p.bias; a.out = p.out; a.ldo = (int32_t)p.ldo;
+  a.relu = p.act; a.stats = d_stats;
+  if (shape == kFwdConv80) {
     // (needs the caller's scratch for the weight images; without it the shape goes to seg_gemm4_kernel)
-    if (d_wimg_scratch == nullptr ||
-        fwd_weight_images(n_seg, w1_off, w2_off, d_w1, d_w2, k1, 80, 2, 64, 0, d_wimg_scratch, sm) != GCMI_OK)
+    if (d_wimg_scratch == nullptr || fwd_weight_images(p.n_seg, p.op[0].w_off, p.op[1].w_off, p.op[0].w, p.op[1].w,
+                                                       p.op[0].k, 80, 2, 64, 0, d_wimg_scratch, sm) != GCMI_OK)
       return GCMI_ERR_UNSUPPORTED;
     a.wimg = reinterpret_cast<const u32x4*>(d_wimg_scratch);
     return launch_fwd_reg<2, 80, 64, false>(st, (int)tiles, a, sm);
   }
-  if (conv) return launch_fwd<128, 2, 64, 64, false>(st, (int)tiles, a, sm);
+  if (shape == kFwdConv) return launch_fwd<128, 2, 64, 64, false>(st, (int)tiles, a, sm);
   return launch_fwd<64, 1, 64, 128, true>(st, (int)tiles, a, sm);
 }
 

@@ -26,7 +26,7 @@ namespace gcmi {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kMaxSeg = 16;
+constexpr int kMaxSeg = kMaxProductSeg;
 constexpr int kGBlock = 256;
 constexpr int BM = 64;
 constexpr int BNT = 64;
@@ -543,6 +543,99 @@ bool gemm_exact_mode() { return g_gemm_exact.load(std::memory_order_relaxed) != 
 // GCMI_OPT_FUSED_BN_STATS (env GCMI_GEMM_STATS=0 starts it off)
 static std::atomic<int> g_fused_bn_stats{getenv("GCMI_GEMM_STATS") && atoi(getenv("GCMI_GEMM_STATS")) == 0 ? 0 : 1};
 
+// the argument checks of gcmi_seg_gemm
+static int check_seg_product(const SegProduct<float>& p) {
+  const SegOperand<float>&a1 = p.op[0], &a2 = p.op[1];
+  GCMI_CHECK_ARG(p.n_seg >= 1 && p.n_seg <= kMaxSeg, "seg_gemm: n_seg %d outside [1,%d]", p.n_seg, kMaxSeg);
+  GCMI_CHECK_ARG(p.seg_begin && p.seg_end, "seg_gemm: NULL segment table");
+  GCMI_CHECK_ARG(p.n_out > 0 && p.ldo >= p.n_out && p.out, "seg_gemm: bad output");
+  GCMI_CHECK_ARG((a1.a && a1.w && a1.w_off && a1.k > 0 && a1.ld >= a1.k) || (a1.a == nullptr),
+                 "seg_gemm: bad first operand");
+  GCMI_CHECK_ARG((a2.a && a2.w && a2.w_off && a2.k > 0 && a2.ld >= a2.k) || (a2.a == nullptr),
+                 "seg_gemm: bad second operand");
+  GCMI_CHECK_ARG(a1.a || a2.a, "seg_gemm: no operand");
+  GCMI_CHECK_ARG(p.bias == nullptr || p.bias_off != nullptr, "seg_gemm: bias without offsets");
+  GCMI_CHECK_ARG(p.act >= 0 && p.act <= 2, "seg_gemm: act must be 0 (none), 1 (ReLU) or 2 (out += result)");
+  for (int s = 0; s < p.n_seg; ++s)
+    GCMI_CHECK_ARG(p.seg_end[s] >= p.seg_begin[s] && p.seg_begin[s] >= 0, "seg_gemm: bad segment %d", s);
+  return GCMI_OK;
+}
+
+int seg_gemm(const SegProduct<float>& p, hipStream_t sm) {
+  const int rc_args = check_seg_product(p);
+  if (rc_args != GCMI_OK) return rc_args;
+  const SegOperand<float>&a1 = p.op[0], &a2 = p.op[1];
+  const int32_t n_out = p.n_out;
+  const bool vec4 = (a1.a == nullptr || (aligned16(a1.a) && a1.ld % 4 == 0)) &&
+                    (a2.a == nullptr || (aligned16(a2.a) && a2.ld % 4 == 0));
+  const int nt = n_out <= 32 ? 1 : (n_out <= 64 ? 2 : 4);
+  SegTable st;
+  const int64_t tiles = fill_seg_table(st, st.w1_off, st.w2_off, st.bias_off, p, vec4 ? BM2 : BM);
+  if (tiles == 0) return GCMI_OK;
+  TimedScope ts(GCMI_K_SEG_GEMM, sm);
+  const bool exact = gemm_exact_mode();
+  if (!exact && p.n_seg == 1 && a2.a == nullptr && p.trans_w && p.seg_begin[0] == 0 && a1.w_off[0] >= 0) {
+    // the task head with more than 32 outputs (head_bwd.hip)
+    const int rc = head_fwd_wide(a1.a, a1.ld, p.seg_end[0], a1.k, a1.w + a1.w_off[0],
+                                 (p.bias && p.bias_off && p.bias_off[0] >= 0) ? p.bias + p.bias_off[0] : nullptr, n_out,
+                                 p.act, p.out, p.ldo, sm);
+    if (rc != GCMI_ERR_UNSUPPORTED) return rc;
+  }
+  if (!exact) {  // the LDS-staged split-bf16 kernel (gemm_split.hip)
+    const int rc = launch_seg_gemm4(p, sm);
+    if (rc != GCMI_ERR_UNSUPPORTED) return rc;
+  }
+  if (vec4) {
+    dim3 grid((unsigned)tiles, (unsigned)((n_out + nt * 32 - 1) / (nt * 32)));
+#define LAUNCH_SG2(TT, NN)                                                                                       \
+  hipLaunchKernelGGL((seg_gemm2_kernel<TT, NN>), grid, dim3(kGBlock), 0, sm, st, a1.a, a1.ld, a1.k, a1.w, a2.a, \
+                     a2.ld, a2.k, a2.w, p.bias, n_out, p.act, p.out, p.ldo)
+#define LAUNCH_SG2_T(TT)                                   \
+  do {                                                     \
+    if (nt == 1) LAUNCH_SG2(TT, 1);                        \
+    else if (nt == 2) LAUNCH_SG2(TT, 2);                   \
+    else LAUNCH_SG2(TT, 4);                                \
+  } while (0)
+    if (p.trans_w) LAUNCH_SG2_T(true); else LAUNCH_SG2_T(false);
+#undef LAUNCH_SG2_T
+#undef LAUNCH_SG2
+  } else {
+    dim3 grid((unsigned)tiles, (unsigned)((n_out + BNT - 1) / BNT));
+#define LAUNCH_SG(TT, VV)                                                                        \
+  hipLaunchKernelGGL((seg_gemm_kernel<TT, VV>), grid, dim3(kGBlock), 0, sm, st, a1.a, a1.ld, a1.k, \
+                     a1.w, a2.a, a2.ld, a2.k, a2.w, p.bias, n_out, p.act, p.out, p.ldo)
+    if (p.trans_w) LAUNCH_SG(true, false); else LAUNCH_SG(false, false);
+#undef LAUNCH_SG
+  }
+  GCMI_CHECK_LAUNCH("seg_gemm");
+  return GCMI_OK;
+}
+
+int seg_gemm_stats(const SegProduct<float>& p, double* d_stats, bool* fused, hipStream_t sm, float* d_wimg_scratch) {
+  *fused = false;
+  // the sums only under GCMI_OPT_FUSED_BN_STATS
+  double* stats = g_fused_bn_stats.load(std::memory_order_relaxed) != 0 ? d_stats : nullptr;
+  // (an invalid description goes to seg_gemm below, which reports it)
+  const bool fast = check_seg_product(p) == GCMI_OK && (p.act == 0 || p.act == 1) && !gemm_exact_mode();
+  if (fast) {  // the persistent form (fwd_fused.hip) for the shapes it covers
+    TimedScope ts(GCMI_K_SEG_GEMM, sm);
+    const int rc = fwd_fused_gemm(p, stats, sm, d_wimg_scratch);
+    if (rc != GCMI_ERR_UNSUPPORTED) {
+      *fused = rc == GCMI_OK && stats != nullptr;
+      return rc;
+    }
+  }
+  if (fast && stats) {
+    TimedScope ts(GCMI_K_SEG_GEMM, sm);
+    const int rc = launch_seg_gemm4(p, sm, stats);
+    if (rc != GCMI_ERR_UNSUPPORTED) {
+      *fused = rc == GCMI_OK;
+      return rc;
+    }
+  }
+  return seg_gemm(p, sm);
+}
+
 }  // namespace gcmi
 
 using namespace gcmi;
@@ -580,79 +673,9 @@ int gcmi_seg_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_en
                   const float* d_w2, const int64_t* w2_off, const float* d_bias,
                   const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act,
                   float* d_out, int64_t ldo, void* stream) {
-  GCMI_CHECK_ARG(n_seg >= 1 && n_seg <= kMaxSeg, "seg_gemm: n_seg %d outside [1,%d]", n_seg, kMaxSeg);
-  GCMI_CHECK_ARG(seg_begin && seg_end, "seg_gemm: NULL segment table");
-  GCMI_CHECK_ARG(n_out > 0 && ldo >= n_out && d_out, "seg_gemm: bad output");
-  GCMI_CHECK_ARG((d_a1 && d_w1 && w1_off && k1 > 0 && lda1 >= k1) || (d_a1 == nullptr),
-                 "seg_gemm: bad first operand");
-  GCMI_CHECK_ARG((d_a2 && d_w2 && w2_off && k2 > 0 && lda2 >= k2) || (d_a2 == nullptr),
-                 "seg_gemm: bad second operand");
-  GCMI_CHECK_ARG(d_a1 || d_a2, "seg_gemm: no operand");
-  GCMI_CHECK_ARG(d_bias == nullptr || bias_off != nullptr, "seg_gemm: bias without offsets");
-  GCMI_CHECK_ARG(act >= 0 && act <= 2, "seg_gemm: act must be 0 (none), 1 (ReLU) or 2 (out += result)");
-  hipStream_t sm = (hipStream_t)stream;
-  const bool vec4 = (d_a1 == nullptr || (aligned16(d_a1) && lda1 % 4 == 0)) &&
-                    (d_a2 == nullptr || (aligned16(d_a2) && lda2 % 4 == 0));
-  const int nt = n_out <= 32 ? 1 : (n_out <= 64 ? 2 : 4);
-  const int bm = vec4 ? BM2 : BM;
-  SegTable st;
-  memset(&st, 0, sizeof(st));
-  st.n_seg = n_seg;
-  int64_t tiles = 0;
-  for (int s = 0; s < kMaxSeg; ++s) {
-    st.tile_start[s] = (int32_t)tiles;
-    if (s < n_seg) {
-      GCMI_CHECK_ARG(seg_end[s] >= seg_begin[s] && seg_begin[s] >= 0, "seg_gemm: bad segment %d", s);
-      st.seg_begin[s] = seg_begin[s];
-      st.seg_end[s] = seg_end[s];
-      st.w1_off[s] = (d_a1 && w1_off) ? w1_off[s] : -1;
-      st.w2_off[s] = (d_a2 && w2_off) ? w2_off[s] : -1;
-      st.bias_off[s] = (d_bias && bias_off) ? bias_off[s] : -1;
-      tiles += (seg_end[s] - seg_begin[s] + bm - 1) / bm;
-    } else {
-      st.w1_off[s] = st.w2_off[s] = st.bias_off[s] = -1;
-    }
-  }
-  st.tile_start[kMaxSeg] = (int32_t)tiles;
-  if (tiles == 0) return GCMI_OK;
-  TimedScope ts(GCMI_K_SEG_GEMM, sm);
-  const bool exact = gemm_exact_mode();
-  if (!exact && n_seg == 1 && d_a2 == nullptr && trans_w && seg_begin[0] == 0 && w1_off[0] >= 0) {
-    // the task head with more than 32 outputs (head_bwd.hip)
-    const int rc = head_fwd_wide(d_a1, lda1, seg_end[0], k1, d_w1 + w1_off[0],
-                                 (d_bias && bias_off && bias_off[0] >= 0) ? d_bias + bias_off[0] : nullptr, n_out, act, d_out,
-                                 ldo, sm);
-    if (rc != GCMI_ERR_UNSUPPORTED) return rc;
-  }
-  if (!exact) {  // the LDS-staged split-bf16 kernel (gemm_split.hip)
-    const int rc = launch_seg_gemm4(n_seg, seg_begin, seg_end, d_a1, lda1, k1, d_w1, w1_off, d_a2, lda2, k2,
-                                    d_w2, w2_off, d_bias, bias_off, n_out, trans_w, act, d_out, ldo, sm);
-    if (rc != GCMI_ERR_UNSUPPORTED) return rc;
-  }
-  if (vec4) {
-    dim3 grid((unsigned)tiles, (unsigned)((n_out + nt * 32 - 1) / (nt * 32)));
-#define LAUNCH_SG2(TT, NN)                                                                             \
-  hipLaunchKernelGGL((seg_gemm2_kernel<TT, NN>), grid, dim3(kGBlock), 0, sm, st, d_a1, lda1, k1, d_w1, d_a2, \
-                     lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo)
-#define LAUNCH_SG2_T(TT)                                   \
-  do {                                                     \
-    if (nt == 1) LAUNCH_SG2(TT, 1);                        \
-    else if (nt == 2) LAUNCH_SG2(TT, 2);                   \
-    else LAUNCH_SG2(TT, 4);                                \
-  } while (0)
-    if (trans_w) LAUNCH_SG2_T(true); else LAUNCH_SG2_T(false);
-#undef LAUNCH_SG2_T
-#undef LAUNCH_SG2
-  } else {
-    dim3 grid((unsigned)tiles, (unsigned)((n_out + BNT - 1) / BNT));
-#define LAUNCH_SG(TT, VV)                                                                       \
-  hipLaunchKernelGGL((seg_gemm_kernel<TT, VV>), grid, dim3(kGBlock), 0, sm, st, d_a1, lda1, k1,  \
-                     d_w1, d_a2, lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo)
-    if (trans_w) LAUNCH_SG(true, false); else LAUNCH_SG(false, false);
-#undef LAUNCH_SG
-  }
-  GCMI_CHECK_LAUNCH("seg_gemm");
-  return GCMI_OK;
+  const SegProduct<float> p{n_seg, seg_begin, seg_end, {{d_a1, lda1, k1, d_w1, w1_off}, {d_a2, lda2, k2, d_w2, w2_off}},
+                            d_bias, bias_off, n_out, trans_w, act, d_out, ldo};
+  return seg_gemm(p, (hipStream_t)stream);
 }
 
 int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end,
@@ -764,10 +787,10 @@ int gcmi_task_head_forward(const float* d_fingerprint, int64_t ld, int64_t n_row
     if (rc == GCMI_OK) rc = head_fwd_wide(d_fingerprint, ld, n_rows, k, d_w, d_bias, n_out, 0, d_out, ldo, st, d_img_scratch);
     if (rc != GCMI_ERR_UNSUPPORTED) return rc;
   }
-  const int32_t zero32 = 0, nr = (int32_t)n_rows;
-  const int64_t zero64 = 0;
-  return gcmi_seg_gemm(1, &zero32, &nr, d_fingerprint, ld, k, d_w, &zero64, nullptr, 0, 0, nullptr, nullptr, d_bias,
-                       d_bias ? &zero64 : nullptr, n_out, 1, 0, d_out, ldo, stream);
+  const int32_t nr = (int32_t)n_rows;
+  SegProduct<float> p = one_segment(&nr, d_fingerprint, ld, k, d_w, d_bias, n_out, d_out, ldo);
+  p.trans_w = 1;
+  return seg_gemm(p, st);
 }
 
 int gcmi_relu_bwd(float* d_g, int64_t ldg, const float* d_y, int64_t ldy, int64_t n_rows,
@@ -790,48 +813,6 @@ int gcmi_relu_bwd(float* d_g, int64_t ldg, const float* d_y, int64_t ldy, int64_
 }
 
 }  // extern "C"
-
-namespace gcmi {
-
-int seg_gemm_stats(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1, int64_t lda1,
-                   int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2, int64_t lda2, int32_t k2,
-                   const float* d_w2, const int64_t* w2_off, const float* d_bias, const int64_t* bias_off,
-                   int32_t n_out, int32_t trans_w, int32_t act, float* d_out, int64_t ldo, double* d_stats,
-                   bool* fused, void* stream, float* d_wimg_scratch) {
-  *fused = false;
-  const bool allow = g_fused_bn_stats.load(std::memory_order_relaxed) != 0;  // GCMI_OPT_FUSED_BN_STATS
-  const bool shapes_ok = n_seg >= 1 && n_seg <= kMaxSeg && seg_begin && seg_end && n_out > 0 && ldo >= n_out && d_out &&
-                         (d_a1 || d_a2) && (d_a1 == nullptr || (d_w1 && w1_off && k1 > 0 && lda1 >= k1)) &&
-                         (d_a2 == nullptr || (d_w2 && w2_off && k2 > 0 && lda2 >= k2)) &&
-                         (d_bias == nullptr || bias_off != nullptr) && (act == 0 || act == 1);
-  if (shapes_ok && !gemm_exact_mode()) {
-    // the persistent form (fwd_fused.hip) for the shapes it covers
-    hipStream_t sm = (hipStream_t)stream;
-    TimedScope ts(GCMI_K_SEG_GEMM, sm);
-    double* stats = (allow && d_stats) ? d_stats : nullptr;
-    const int rc = fwd_fused_gemm(n_seg, seg_begin, seg_end, d_a1, lda1, k1, d_w1, w1_off, d_a2, lda2, k2, d_w2, w2_off,
-                                  d_bias, bias_off, n_out, trans_w, act, d_out, ldo, stats, sm, d_wimg_scratch);
-    if (rc != GCMI_ERR_UNSUPPORTED) {
-      *fused = rc == GCMI_OK && stats != nullptr;
-      return rc;
-    }
-  }
-  if (allow && d_stats && shapes_ok && !gemm_exact_mode()) {
-    hipStream_t sm = (hipStream_t)stream;
-    TimedScope ts(GCMI_K_SEG_GEMM, sm);
-    const int rc = launch_seg_gemm4(n_seg, seg_begin, seg_end, d_a1, lda1, k1, d_w1, w1_off, d_a2, lda2, k2, d_w2,
-                                    w2_off, d_bias, bias_off, n_out, trans_w, act, d_out, ldo, sm, d_stats);
-    if (rc != GCMI_ERR_UNSUPPORTED) {
-      *fused = rc == GCMI_OK;
-      return rc;
-    }
-  }
-  return gcmi_seg_gemm(n_seg, seg_begin, seg_end, d_a1, lda1, k1, d_w1, w1_off, d_a2, lda2, k2, d_w2, w2_off, d_bias,
-                       bias_off, n_out, trans_w, act, d_out, ldo, stream);
-}
-
-}  // namespace gcmi
-
 
 // ------------------------------------------------------------------ diagnostics
 // Peak rate of v_mfma_f32_32x32x2_f32 from registers (no memory traffic): the ceiling the

@@ -26,7 +26,7 @@ namespace gcmi {
 
 constexpr int kS3Block = 256;
 constexpr int kS3Rows = 128;
-constexpr int kS3MaxSeg = 16;
+constexpr int kS3MaxSeg = kMaxProductSeg;
 
 struct SegTable3 {
   int32_t n_seg;
@@ -309,34 +309,16 @@ seg_gemm4_kernel(SegTable3 st, const float* __restrict__ a1, int64_t lda1, int k
   }
 }
 
-int launch_seg_gemm4(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const float* d_a1,
-                     int64_t lda1, int32_t k1, const float* d_w1, const int64_t* w1_off, const float* d_a2,
-                     int64_t lda2, int32_t k2, const float* d_w2, const int64_t* w2_off, const float* d_bias,
-                     const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act, float* d_out,
-                     int64_t ldo, hipStream_t sm, double* d_stats) {
-  if (n_seg > kS3MaxSeg) return GCMI_ERR_UNSUPPORTED;
-  if (d_stats && act == 2) return GCMI_ERR_UNSUPPORTED;
-  const bool avec = !((d_a1 && (!aligned16(d_a1) || lda1 % 4)) || (d_a2 && (!aligned16(d_a2) || lda2 % 4)));
-  if (n_out % 4 || ldo % 4 || !aligned16(d_out)) return GCMI_ERR_UNSUPPORTED;
+int launch_seg_gemm4(const SegProduct<float>& p, hipStream_t sm, double* d_stats) {
+  const SegOperand<float>&a1 = p.op[0], &a2 = p.op[1];
+  const int32_t n_out = p.n_out;
+  if (p.n_seg > kS3MaxSeg) return GCMI_ERR_UNSUPPORTED;
+  if (d_stats && p.act == 2) return GCMI_ERR_UNSUPPORTED;
+  const bool avec = !((a1.a && (!aligned16(a1.a) || a1.ld % 4)) || (a2.a && (!aligned16(a2.a) || a2.ld % 4)));
+  if (n_out % 4 || p.ldo % 4 || !aligned16(p.out)) return GCMI_ERR_UNSUPPORTED;
   int nt = n_out <= 32 ? 1 : (n_out <= 64 ? 2 : 4);
   SegTable3 st;
-  memset(&st, 0, sizeof(st));
-  st.n_seg = n_seg;
-  int64_t tiles = 0;
-  for (int s = 0; s < kS3MaxSeg; ++s) {
-    st.tile_start[s] = (int32_t)tiles;
-    if (s < n_seg) {
-      st.seg_begin[s] = seg_begin[s];
-      st.seg_end[s] = seg_end[s];
-      st.w1_off[s] = (d_a1 && w1_off) ? w1_off[s] : -1;
-      st.w2_off[s] = (d_a2 && w2_off) ? w2_off[s] : -1;
-      st.bias_off[s] = (d_bias && bias_off) ? bias_off[s] : -1;
-      tiles += (seg_end[s] - seg_begin[s] + kS3Rows - 1) / kS3Rows;
-    } else {
-      st.w1_off[s] = st.w2_off[s] = st.bias_off[s] = -1;
-    }
-  }
-  st.tile_start[kS3MaxSeg] = (int32_t)tiles;
+  const int64_t tiles = fill_seg_table(st, st.w1_off, st.w2_off, st.bias_off, p, kS3Rows);
   if (tiles == 0) return GCMI_OK;
   // Few row tiles (a per-molecule product: the task heads at a per-GPU batch of a few thousand molecules) leave most
   // of the 256 CUs idle at 128 rows x 128 columns per workgroup: narrower column groups then, until the launch has a
@@ -345,16 +327,16 @@ int launch_seg_gemm4(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg
   while (nt > 1 && tiles * ((n_out + nt * 32 - 1) / (nt * 32)) < 256) nt >>= 1;
   dim3 grid((unsigned)tiles, (unsigned)((n_out + nt * 32 - 1) / (nt * 32)));
   const int rev = next_sweep_direction();
-#define LAUNCH_S4(TT, NN)                                                                                      \
-  do {                                                                                                         \
-    if (avec)                                                                                                  \
-      hipLaunchKernelGGL((seg_gemm4_kernel<TT, NN, true>), grid, dim3(kS3Block), 0, sm, st, d_a1, lda1, k1, d_w1,   \
-                         d_a2, lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo, d_stats, rev);                  \
-    else                                                                                                       \
-      hipLaunchKernelGGL((seg_gemm4_kernel<TT, NN, false>), grid, dim3(kS3Block), 0, sm, st, d_a1, lda1, k1, d_w1,  \
-                         d_a2, lda2, k2, d_w2, d_bias, n_out, act, d_out, ldo, d_stats, rev);                  \
+#define LAUNCH_S4(TT, NN)                                                                                         \
+  do {                                                                                                            \
+    if (avec)                                                                                                     \
+      hipLaunchKernelGGL((seg_gemm4_kernel<TT, NN, true>), grid, dim3(kS3Block), 0, sm, st, a1.a, a1.ld, a1.k, a1.w,   \
+                         a2.a, a2.ld, a2.k, a2.w, p.bias, n_out, p.act, p.out, p.ldo, d_stats, rev);              \
+    else                                                                                                          \
+      hipLaunchKernelGGL((seg_gemm4_kernel<TT, NN, false>), grid, dim3(kS3Block), 0, sm, st, a1.a, a1.ld, a1.k, a1.w,  \
+                         a2.a, a2.ld, a2.k, a2.w, p.bias, n_out, p.act, p.out, p.ldo, d_stats, rev);              \
   } while (0)
-  if (trans_w) {
+  if (p.trans_w) {
     if (nt == 1) LAUNCH_S4(true, 1); else if (nt == 2) LAUNCH_S4(true, 2); else LAUNCH_S4(true, 4);
   } else {
     if (nt == 1) LAUNCH_S4(false, 1); else if (nt == 2) LAUNCH_S4(false, 2); else LAUNCH_S4(false, 4);

@@ -181,18 +181,19 @@ static int head_forward(const gcmi_model_desc* m, const Ws& w, float* ws, const 
                         int64_t B, void* stream) {
   const int D = m->dense_width;
   const int TC = m->n_tasks * m->n_classes;
-  const int32_t zero32 = 0, nB = (int32_t)B;
-  const int64_t zero64 = 0;
+  const int32_t nB = (int32_t)B;
+  hipStream_t st = (hipStream_t)stream;
   if (w.himg >= 0 && B > 0) {
-    hipStream_t st = (hipStream_t)stream;
     int rc = head_prep(d_params + m->off_head_w, TC, ws + w.himg, st);
     if (rc == GCMI_OK)
       rc = head_fwd_wide(io->d_fingerprint, 2 * D, B, 2 * D, d_params + m->off_head_w, d_params + m->off_head_b, TC, 0,
                          io->d_logits, TC, st, ws + w.himg);
     if (rc != GCMI_ERR_UNSUPPORTED) return rc;
   }
-  return gcmi_seg_gemm(1, &zero32, &nB, io->d_fingerprint, 2 * D, 2 * D, d_params + m->off_head_w, &zero64, nullptr, 0, 0,
-                       nullptr, nullptr, d_params + m->off_head_b, &zero64, TC, 1, 0, io->d_logits, TC, stream);
+  SegProduct<float> p = one_segment(&nB, io->d_fingerprint, 2 * D, 2 * D, d_params + m->off_head_w,
+                                    d_params + m->off_head_b, TC, io->d_logits, TC);
+  p.trans_w = 1;
+  return seg_gemm(p, st);
 }
 
 static int check_desc(const gcmi_model_desc* m) {
@@ -239,12 +240,6 @@ static Segs make_segs(const gcmi_graph* g, int64_t k, int64_t width) {
   return s;
 }
 
-static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, const gcmi_model_io* io,
-                           int32_t training, void* stream);
-static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, float* d_grads,
-                                 const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
-                                 int64_t* grad_lo, int64_t* grad_hi, void* stream);
-
 // ------------------------------------------------------------------------------------------------------------------
 // storage == 0, the first GraphConv block over SMALL-INTEGER atom features (gcmi_model_io.features_small_int: every
 // element an integer with |x| <= 256 / max_deg).  Such an element is exactly one bf16 value, and so is every neighbour
@@ -285,6 +280,152 @@ int one_piece_launches() { return g_one_piece_launches.load(std::memory_order_re
     if (rc__) return rc__;   \
   } while (0)
 
+// Block l of the step (l < n_layers: GraphConv + BatchNorm + GraphPool; l == n_layers: the atom-level dense layer and
+// its BatchNorm): its widths and where its parameters, their gradients and its BatchNorm vectors live.
+struct Block {
+  int K, W;                       // input / output columns
+  const float *w, *bias;          // bias: the rows the product adds (GraphConv: the per-degree sums pack_biases left)
+  const float *gamma, *beta;      // nullptr without BatchNorm, as everything BatchNorm below
+  float *dw, *dbias;              // gradients; nullptr in the forward.  dbias of a GraphConv: per-degree sums in the
+  float* dbias_rows;              // workspace, unpacked into the reference's bias rows (dbias_rows) after the loop
+  float *dgamma, *dbeta;
+  float *mean, *invstd, *scale, *shift;  // this batch's statistics and the folded affine map (workspace)
+  float *running_mean, *running_var;
+  int64_t* batches_tracked;
+};
+
+static void make_blocks(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, float* d_grads,
+                        const gcmi_model_io* io, Block* blk) {
+  const int L = m->n_layers;
+  auto grad = [&](int64_t off) { return d_grads ? d_grads + off : nullptr; };
+  for (int l = 0; l <= L; ++l) {
+    Block& b = blk[l];
+    b.K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
+    b.W = l == L ? m->dense_width : m->conv_width[l];
+    b.w = d_params + (l == L ? m->off_dense_w : m->off_conv_w[l]);
+    b.bias = l == L ? d_params + m->off_dense_b : ws + w.bsum[l];
+    b.dw = grad(l == L ? m->off_dense_w : m->off_conv_w[l]);
+    b.dbias = l == L ? grad(m->off_dense_b) : ws + w.dbsum[l];
+    b.dbias_rows = l == L ? nullptr : grad(m->off_conv_b[l]);
+    const bool bn = m->batch_norm != 0;
+    b.gamma = bn ? d_params + m->off_bn_gamma[l] : nullptr;
+    b.beta = bn ? d_params + m->off_bn_beta[l] : nullptr;
+    b.dgamma = bn ? grad(m->off_bn_gamma[l]) : nullptr;
+    b.dbeta = bn ? grad(m->off_bn_beta[l]) : nullptr;
+    float* bnv = ws + w.bnv[l];
+    b.mean = bnv;
+    b.invstd = bnv + b.W;
+    b.scale = bnv + 2 * b.W;
+    b.shift = bnv + 3 * b.W;
+    b.running_mean = io->d_bn_running_mean[l];
+    b.running_var = io->d_bn_running_var[l];
+    b.batches_tracked = io->d_bn_batches_tracked[l];
+  }
+}
+
+// A product over the degree segments with the first operand's weight blocks at w_off (sg.w_rel / sg.w_self)
+template <typename TA, typename TO>
+static SegProduct<TA, TO> seg_product(const Segs& sg, const TA* a, int64_t lda, int32_t k, const float* w,
+                                      const int64_t* w_off, int32_t n_out, TO* out) {
+  SegProduct<TA, TO> p;
+  p.n_seg = sg.n;
+  p.seg_begin = sg.begin;
+  p.seg_end = sg.end;
+  p.op[0] = {a, lda, k, w, w_off};
+  p.n_out = n_out;
+  p.out = out;
+  p.ldo = n_out;
+  return p;
+}
+
+// The product of GraphConv block b: relu([S | X] . [W_rel[d]; W_self[d]] + bsum[d])
+template <typename TA, typename TO>
+static SegProduct<TA, TO> conv_product(const Segs& sg, const TA* s, int64_t lds, const TA* x, int64_t ldx, const Block& b,
+                                       TO* out) {
+  SegProduct<TA, TO> p = seg_product(sg, s, lds, b.K, b.w, sg.w_rel, b.W, out);
+  p.op[1] = {x, ldx, b.K, b.w, sg.w_self};
+  p.bias = b.bias;
+  p.bias_off = sg.b_off;
+  p.act = 1;
+  return p;
+}
+
+// BatchNorm of block b in the forward, folded into b.scale / b.shift for the kernel that reads the rows next: training
+// = this batch's statistics, from the sums the product left in acc (stats_fused) or from a pass over the rows; eval =
+// the running statistics
+static int bn_forward(const gcmi_model_desc* m, const Block& b, int64_t N, int32_t training, bool stats_fused,
+                      const float* rows, int64_t ld, double* acc, void* stream) {
+  if (training && stats_fused)
+    return bn_finalize_impl(N, b.W, b.gamma, b.beta, m->bn_eps, m->bn_momentum, b.running_mean, b.running_var, b.mean,
+                            b.invstd, b.scale, b.shift, acc, stream, b.batches_tracked);
+  if (training)
+    return bn_stats_impl(rows, ld, N, b.W, b.gamma, b.beta, m->bn_eps, m->bn_momentum, b.running_mean, b.running_var,
+                         b.mean, b.invstd, b.scale, b.shift, acc, true, stream, b.batches_tracked);
+  return gcmi_bn_fold_eval(b.gamma, b.beta, b.running_mean, b.running_var, m->bn_eps, b.W, b.scale, b.shift, stream);
+}
+
+// A training batch without atoms launches no statistics kernel, and those are what bump the counters otherwise
+static int bump_counters(const gcmi_model_desc* m, const gcmi_model_io* io, hipStream_t st) {
+  CounterPtrs c;
+  c.n = m->n_layers + 1;
+  bool any = false;
+  for (int i = 0; i <= kMaxL; ++i) {
+    c.p[i] = i <= m->n_layers ? io->d_bn_batches_tracked[i] : nullptr;
+    any = any || c.p[i] != nullptr;
+  }
+  if (any) {
+    hipLaunchKernelGGL(bump_counters_kernel, dim3(1), dim3(64), 0, st, c);
+    GCMI_CHECK_LAUNCH("bump_counters");
+  }
+  return GCMI_OK;
+}
+
+// The first block's forward in its one-piece form (one_piece_block0 above): the window pass writes S0 and Xb as bf16
+// rows, the product reads them as they are and leaves fp32 rows (and, training, the BatchNorm sums in acc)
+static int one_piece_forward(const gcmi_graph* g, const Ws& w, float* ws, const Block& b, const Segs& sg,
+                             const gcmi_model_io* io, double* stats, hipStream_t st) {
+  bf16_t* s0 = reinterpret_cast<bf16_t*>(ws + w.S[0]);
+  bf16_t* xb = reinterpret_cast<bf16_t*>(ws + w.xb);
+  {
+    TimedScope ts(GCMI_K_GATHER_SUM, st);
+    RUN(win_gather_sum_fh(g, io->d_atom_features, io->ld_features, 76, s0, xb, kOnePieceLd, st));
+  }
+  {
+    TimedScope ts(GCMI_K_SEG_GEMM, st);
+    const int rc = fwd_h_gemm(conv_product(sg, s0, kOnePieceLd, xb, kOnePieceLd, b, ws + w.gc[0]), stats, ws + w.wimg, st);
+    if (rc == GCMI_ERR_UNSUPPORTED) set_error("model_forward: the one-piece product of GraphConv 0 refused its shape");
+    RUN(rc);
+  }
+  g_one_piece_launches.fetch_add(1, std::memory_order_relaxed);
+  return GCMI_OK;
+}
+
+// The per-molecule part of the backward as separate launches (what head_bwd_fused does in one, for the shapes it does
+// not cover): loss and d logits of the first n_rows molecules, the head's gradients, the gradient w.r.t. the
+// fingerprint in dfp; prep: the tanh derivative applied to it in place, for a BatchNorm backward that recomputes the
+// GraphGather backward from it
+static int head_backward_separate(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, float* d_grads,
+                                  const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
+                                  int64_t B, bool prep, void* stream) {
+  const int D = m->dense_width;
+  const int TC = m->n_tasks * m->n_classes;
+  const int32_t nB = (int32_t)B;
+  RUN(loss_impl(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks, m->n_classes, io->d_loss,
+                ws + w.dlogits, nullptr, reinterpret_cast<double*>(ws + w.lacc), true, stream));
+  RUN(gcmi_seg_gemm_wgrad(1, &kZero32, &nB, io->d_fingerprint, 2 * D, 2 * D, ws + w.dlogits, TC, TC,
+                          d_grads + m->off_head_w, &kZero64, d_grads + m->off_head_b, &kZero64, 1, stream));
+  hipStream_t st = (hipStream_t)stream;
+  RUN(seg_gemm(one_segment(&nB, ws + w.dlogits, TC, TC, d_params + m->off_head_w, nullptr, 2 * D, ws + w.dfp, 2 * D), st));
+  if (prep) RUN(readout_grad_prep(ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, B, D, st));
+  return GCMI_OK;
+}
+
+// the dense block's backward takes the one-pass kernel (bwd_fused.hip: fused_dense_bwd) -- asked once per call: the
+// head kernel in front of it leaves the BatchNorm sums only for that kernel
+static bool dense_block_one_pass(const gcmi_model_desc* m, int64_t N) {
+  const int Wl = m->conv_width[m->n_layers - 1];
+  return m->batch_norm && N > 0 && fused_bwd_enabled() && m->dense_width == 128 && Wl > 32 && Wl <= 64;
+}
 
 // ------------------------------------------------------------------------------------------------------------------
 // storage == 1: the same step with every matrix it writes and reads back kept as bf16 (fp32 arithmetic, fp64
@@ -331,7 +472,10 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
   const int64_t N = g->n_atoms, B = g->n_mols;
   const Ws w = carve(m, N, B, io->ld_features);
   float* ws = io->d_workspace;
+  Block blk[kMaxL + 1];
+  make_blocks(m, w, ws, d_params, nullptr, io, blk);
   auto H = [&](int64_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
+  double* acc = reinterpret_cast<double*>(ws + w.acc);
   if (training && N > 0 && hipMemsetAsync(ws + w.acc, 0, sizeof(float) * (size_t)(w.z_end - w.acc), st) != hipSuccess) {
     set_error("model_forward: memset failed");
     return GCMI_ERR_LAUNCH;
@@ -340,12 +484,8 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
   int64_t ldin = 0;
   RUN(pack_biases(m, w, ws, d_params, st));
   for (int l = 0; l < L; ++l) {
-    const int K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
-    const int W = m->conv_width[l];
-    const Segs sg = make_segs(g, K, W);
-    float* bnv = ws + w.bnv[l];
-    float* scale = bnv + 2 * W;
-    float* shift = bnv + 3 * W;
+    const Block& b = blk[l];
+    const Segs sg = make_segs(g, b.K, b.W);
     if (N > 0) {
       {
         TimedScope ts(GCMI_K_GATHER_SUM, st);
@@ -354,81 +494,47 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
           xin = H(w.xb);
           ldin = w.ldS[0];
         } else {
-          RUN(win_gather_sum_h(g, xin, ldin, K, H(w.S[l]), w.ldS[l], st));
+          RUN(win_gather_sum_h(g, xin, ldin, b.K, H(w.S[l]), w.ldS[l], st));
         }
       }
       {
         TimedScope ts(GCMI_K_SEG_GEMM, st);
-        const int rc = fwd_h_gemm(sg.n, sg.begin, sg.end, H(w.S[l]), w.ldS[l], K, d_params + m->off_conv_w[l], sg.w_rel, xin,
-                                  ldin, K, d_params + m->off_conv_w[l], sg.w_self, ws + w.bsum[l], sg.b_off, W, 0, 1,
-                                  H(w.gc[l]), W, training ? reinterpret_cast<double*>(ws + w.acc) : nullptr, ws + w.wimg,
-                                  st);
+        const int rc = fwd_h_gemm(conv_product(sg, H(w.S[l]), w.ldS[l], xin, ldin, b, H(w.gc[l])),
+                                  training ? acc : nullptr, ws + w.wimg, st);
         if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: GraphConv %d has no bf16 product kernel", l);
         RUN(rc);
       }
-      if (training) {
-        RUN(bn_finalize_impl(N, W, d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], m->bn_eps, m->bn_momentum,
-                             io->d_bn_running_mean[l], io->d_bn_running_var[l], bnv, bnv + W, scale, shift,
-                             reinterpret_cast<double*>(ws + w.acc), stream, io->d_bn_batches_tracked[l]));
-      } else {
-        RUN(gcmi_bn_fold_eval(d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], io->d_bn_running_mean[l],
-                              io->d_bn_running_var[l], m->bn_eps, W, scale, shift, stream));
-      }
+      RUN(bn_forward(m, b, N, training, true, nullptr, 0, acc, stream));
       {
         TimedScope ts(GCMI_K_GATHER_MAX, st);
-        RUN(win_gather_max_h(g, H(w.gc[l]), W, W, scale, shift, H(w.pool[l]), W,
+        RUN(win_gather_max_h(g, H(w.gc[l]), b.W, b.W, b.scale, b.shift, H(w.pool[l]), b.W,
                              training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, st));
       }
     }
     xin = H(w.pool[l]);
-    ldin = W;
+    ldin = b.W;
   }
-  const int Wl = m->conv_width[L - 1];
-  const int D = m->dense_width;
-  const int32_t zero32 = 0;
-  const int64_t zero64 = 0;
-  float* bnvD = ws + w.bnv[L];
-  float* scale = bnvD + 2 * D;
-  float* shift = bnvD + 3 * D;
+  const Block& dn = blk[L];
+  const int D = dn.W;
   if (N > 0) {
     const int32_t nN = (int32_t)N;
     {
       TimedScope ts(GCMI_K_SEG_GEMM, st);
-      const int rc = fwd_h_gemm(1, &zero32, &nN, xin, ldin, Wl, d_params + m->off_dense_w, &zero64, nullptr, 0, 0, nullptr,
-                                nullptr, d_params + m->off_dense_b, &zero64, D, 1, 1, H(w.dense), D,
-                                training ? reinterpret_cast<double*>(ws + w.acc) : nullptr, ws + w.wimg, st);
+      SegProduct<bf16_t> p = one_segment(&nN, xin, ldin, dn.K, dn.w, dn.bias, D, H(w.dense), D);
+      p.trans_w = 1;
+      p.act = 1;
+      const int rc = fwd_h_gemm(p, training ? acc : nullptr, ws + w.wimg, st);
       if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense layer has no bf16 product kernel");
       RUN(rc);
     }
-    if (training) {
-      RUN(bn_finalize_impl(N, D, d_params + m->off_bn_gamma[L], d_params + m->off_bn_beta[L], m->bn_eps, m->bn_momentum,
-                           io->d_bn_running_mean[L], io->d_bn_running_var[L], bnvD, bnvD + D, scale, shift,
-                           reinterpret_cast<double*>(ws + w.acc), stream, io->d_bn_batches_tracked[L]));
-    } else {
-      RUN(gcmi_bn_fold_eval(d_params + m->off_bn_gamma[L], d_params + m->off_bn_beta[L], io->d_bn_running_mean[L],
-                            io->d_bn_running_var[L], m->bn_eps, D, scale, shift, stream));
-    }
+    RUN(bn_forward(m, dn, N, training, true, nullptr, 0, acc, stream));
   }
-  RUN(readout_fwd_impl(g, reinterpret_cast<const float*>(H(w.dense)), D, D, N > 0 ? scale : nullptr,
-                       N > 0 ? shift : nullptr, 1, io->d_fingerprint, 2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
+  RUN(readout_fwd_impl(g, reinterpret_cast<const float*>(H(w.dense)), D, D, N > 0 ? dn.scale : nullptr,
+                       N > 0 ? dn.shift : nullptr, 1, io->d_fingerprint, 2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
                        training ? ws + w.rsum : nullptr, stream, 1));
-  const int TC = m->n_tasks * m->n_classes;
-  const int32_t nB = (int32_t)B;
   RUN(head_forward(m, w, ws, d_params, io, B, stream));
   if (m->mode == 0 && io->d_probs) RUN(gcmi_softmax(io->d_logits, B * m->n_tasks, m->n_classes, io->d_probs, stream));
-  if (training && N == 0) {  // (with atoms, every layer's statistics launch bumps its own counter)
-    CounterPtrs c;
-    c.n = L + 1;
-    bool any = false;
-    for (int i = 0; i <= kMaxL; ++i) {
-      c.p[i] = i <= L ? io->d_bn_batches_tracked[i] : nullptr;
-      any = any || c.p[i] != nullptr;
-    }
-    if (any) {
-      hipLaunchKernelGGL(bump_counters_kernel, dim3(1), dim3(64), 0, st, c);
-      GCMI_CHECK_LAUNCH("bump_counters");
-    }
-  }
+  if (training && N == 0) RUN(bump_counters(m, io, st));
   return GCMI_OK;
 }
 
@@ -441,10 +547,10 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
   const int64_t N = g->n_atoms, B = g->n_mols;
   const Ws w = carve(m, N, B, io->ld_features);
   float* ws = io->d_workspace;
+  Block blk[kMaxL + 1];
+  make_blocks(m, w, ws, d_params, d_grads, io, blk);
   auto H = [&](int64_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
   auto HF = [&](int64_t off) { return reinterpret_cast<const float*>(ws + off); };  // a bf16 matrix behind a float* parameter
-  const int D = m->dense_width;
-  const int TC = m->n_tasks * m->n_classes;
   const bool full = m->grad_mode == 1;
   const int64_t lo = full ? 0 : m->off_bn_gamma[L - 1];
   const int64_t hi = m->n_params;
@@ -455,38 +561,32 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
     set_error("model_loss_backward: memset failed");
     return GCMI_ERR_LAUNCH;
   }
-  const int32_t zero32 = 0;
-  const int64_t zero64 = 0;
-  const int32_t nB = (int32_t)B;
+  double* acc = reinterpret_cast<double*>(ws + w.acc);
+  double* acc2 = reinterpret_cast<double*>(ws + w.acc2);
+  double* lacc = reinterpret_cast<double*>(ws + w.lacc);
+  const float loss_inv_count = 1.f / (float)(n_rows * m->n_tasks);
   // ---- per-molecule part (fp32 throughout: the fingerprint and everything behind it are per-molecule rows)
-  const float* bnvL = ws + w.bnv[L];
+  const Block& dn = blk[L];
+  const int D = dn.W;
   bool head_sums = false;
   {
     const int rc = head_bwd_fused(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks, m->n_classes,
                                   B, io->d_fingerprint, 2 * D, d_params + m->off_head_w, d_grads + m->off_head_w,
-                                  d_grads + m->off_head_b, ws + w.dfp, 2 * D, reinterpret_cast<double*>(ws + w.lacc),
-                                  g->d_mol_runs, g->max_deg + 1, reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.rsum,
-                                  bnvL, bnvL + D, (N > 0 && g->d_mol_runs) ? reinterpret_cast<double*>(ws + w.acc) : nullptr,
-                                  D, st, ws + w.dlogits, w.himg >= 0 ? ws + w.himg : nullptr);
+                                  d_grads + m->off_head_b, ws + w.dfp, 2 * D, lacc, g->d_mol_runs, g->max_deg + 1,
+                                  reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.rsum, dn.mean, dn.invstd,
+                                  (N > 0 && g->d_mol_runs) ? acc : nullptr, D, st, ws + w.dlogits,
+                                  w.himg >= 0 ? ws + w.himg : nullptr);
     if (rc == GCMI_OK) {
       head_sums = N > 0 && g->d_mol_runs != nullptr;
       // (with head_sums the loss is finalised by the BatchNorm parameter launch that follows)
-      if (!head_sums)
-        RUN(loss_finalize_impl(reinterpret_cast<double*>(ws + w.lacc), 1.f / (float)(n_rows * m->n_tasks), io->d_loss, stream, kLossRep));
+      if (!head_sums) RUN(loss_finalize_impl(lacc, loss_inv_count, io->d_loss, stream, kLossRep));
     } else if (rc != GCMI_ERR_UNSUPPORTED) {
       return rc;
     } else {
-      RUN(loss_impl(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks, m->n_classes, io->d_loss,
-                    ws + w.dlogits, nullptr, reinterpret_cast<double*>(ws + w.lacc), true, stream));
-      RUN(gcmi_seg_gemm_wgrad(1, &zero32, &nB, io->d_fingerprint, 2 * D, 2 * D, ws + w.dlogits, TC, TC,
-                              d_grads + m->off_head_w, &zero64, d_grads + m->off_head_b, &zero64, 1, stream));
-      RUN(gcmi_seg_gemm(1, &zero32, &nB, ws + w.dlogits, TC, TC, d_params + m->off_head_w, &zero64, nullptr, 0, 0, nullptr,
-                        nullptr, nullptr, nullptr, 2 * D, 0, 0, ws + w.dfp, 2 * D, stream));
-      RUN(readout_grad_prep(ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, B, D, st));
+      RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, true, stream));
     }
   }
   if (N == 0) return GCMI_OK;
-  const int Wl = m->conv_width[L - 1];
   float* dpool = ws + w.tC;
   const float* coef = ws + w.acc;
   // storage == 2: dpool, dy, dS and dXs are bf16 rows (in the same fp32-sized workspace blocks, ld in elements)
@@ -494,23 +594,19 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
   auto HG = [](float* p) { return reinterpret_cast<bf16_t*>(p); };
   // ---- dense block: BatchNorm sums from per-molecule data, then one pass (dense and pool rows arrive as bf16)
   if (head_sums) {
-    RUN(bn_bwd_params_impl(N, D, d_params + m->off_bn_gamma[L], bnvL, bnvL + D, d_grads + m->off_bn_gamma[L],
-                           d_grads + m->off_bn_beta[L], reinterpret_cast<double*>(ws + w.acc), stream,
-                           reinterpret_cast<double*>(ws + w.lacc), kLossRep, 1.f / (float)(n_rows * m->n_tasks), io->d_loss));
+    RUN(bn_bwd_params_impl(N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, acc, stream, lacc, kLossRep,
+                           loss_inv_count, io->d_loss));
   } else {
     // (the per-molecule sums kernel reads rawsum, never the atom rows: the bf16 matrix is only passed through)
     RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, reinterpret_cast<const int32_t*>(ws + w.arg_r),
-                            HF(w.dense), D, N, D, d_params + m->off_bn_gamma[L], bnvL, bnvL + D,
-                            d_grads + m->off_bn_gamma[L], d_grads + m->off_bn_beta[L], nullptr, D, 1,
-                            reinterpret_cast<double*>(ws + w.acc), true, stream, ws + w.rsum, g->d_mol_runs, g->n_mols,
-                            g->max_deg + 1));
+                            HF(w.dense), D, N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, nullptr, D, 1, acc,
+                            true, stream, ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1));
   }
   {
     TimedScope ts(GCMI_K_FUSED_BWD, st);
     const int rc = fused_dense_bwd(N, g->d_membership, ws + w.dfp, 2 * D, reinterpret_cast<const int32_t*>(ws + w.arg_r),
-                                   HF(w.dense), D, coef, D, HF(w.pool[L - 1]), Wl, Wl, d_params + m->off_dense_w,
-                                   d_grads + m->off_dense_w, d_grads + m->off_dense_b, dpool, Wl,
-                                   reinterpret_cast<double*>(ws + w.acc2), st, gb ? 2 : 1);
+                                   HF(w.dense), D, coef, D, HF(w.pool[L - 1]), dn.K, dn.K, dn.w, dn.dw, dn.dbias, dpool,
+                                   dn.K, acc2, st, gb ? 2 : 1);
     if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense block has no one-pass backward");
     RUN(rc);
   }
@@ -519,64 +615,59 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
   BiasLayers ub;
   memset(&ub, 0, sizeof(ub));
   for (int l = L - 1; l >= 0; --l) {
-    const int W = m->conv_width[l];
-    const int K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
+    const Block& b = blk[l];
+    const int W = b.W, K = b.K;
     float* dy = ws + w.tD;
     const Segs sg = make_segs(g, K, W);
     const bf16_t* xin = l == 0 ? H(w.xb) : H(w.pool[l - 1]);
     const int64_t ldx = l == 0 ? w.ldS[0] : m->conv_width[l - 1];
     float* dS = ws + w.tE;
     float* dX = ws + w.tC;
-    const float* bnv = ws + w.bnv[l];
+    const uint8_t* arg = reinterpret_cast<const uint8_t*>(ws + w.arg[l]);
     // the block above left sum dP and sum dP * P: this BatchNorm's backward needs no pass over dy (bn_bwd_pool_impl);
     // dy itself only when the GraphConv below trains, or where the pooled sums are ill-conditioned
     if (dy_ready) {
       // (left by win_gather_sumacc_max_bwd below, one iteration ago)
     } else if (gb) {
       TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_max_bwd_h(g, HG(dpool), W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), HG(dy), W,
-                               full ? nullptr : d_params + m->off_bn_gamma[l], full ? nullptr : d_params + m->off_bn_beta[l],
-                               st));
+      RUN(win_gather_max_bwd_h(g, HG(dpool), W, W, arg, HG(dy), W, full ? nullptr : b.gamma, full ? nullptr : b.beta, st));
     } else if (full) {
-      RUN(gcmi_gather_max_bwd(g, dpool, W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), dy, W, stream));
+      RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
     } else {
       TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), dy, W,
-                                    d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], st));
+      RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.gamma, b.beta, st));
     }
-    RUN(bn_bwd_pool_impl(dy, W, HF(w.gc[l]), W, N, W, d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], bnv, bnv + W,
-                         d_grads + m->off_bn_gamma[l], d_grads + m->off_bn_beta[l], reinterpret_cast<double*>(ws + w.acc2),
-                         reinterpret_cast<double*>(ws + w.acc), stream, gb ? 2 : 1));
+    RUN(bn_bwd_pool_impl(dy, W, HF(w.gc[l]), W, N, W, b.gamma, b.beta, b.mean, b.invstd, b.dgamma, b.dbeta, acc2, acc,
+                         stream, gb ? 2 : 1));
     dy_ready = false;
     if (!full) break;  // reference semantics: nothing in front of a GraphConv output trains
     {
       TimedScope ts(GCMI_K_FUSED_BWD, st);
       const int rc = fused_conv_bwd(sg.n, sg.begin, sg.end, sg.w_rel, sg.w_self, sg.b_off, dy, W, HF(w.gc[l]), W, coef, W,
-                                    HF(w.S[l]), w.ldS[l], reinterpret_cast<const float*>(xin), ldx, K,
-                                    d_params + m->off_conv_w[l], d_grads + m->off_conv_w[l], ws + w.dbsum[l],
-                                    l > 0 ? dS : nullptr, K, l > 0 ? dX : nullptr, K,
-                                    l > 0 ? reinterpret_cast<double*>(ws + w.acc2) : nullptr, st, gb ? 2 : 1);
+                                    HF(w.S[l]), w.ldS[l], reinterpret_cast<const float*>(xin), ldx, K, b.w, b.dw, b.dbias,
+                                    l > 0 ? dS : nullptr, K, l > 0 ? dX : nullptr, K, l > 0 ? acc2 : nullptr, st,
+                                    gb ? 2 : 1);
       if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: GraphConv %d has no one-pass backward", l);
       RUN(rc);
     }
-    ub.src[l] = ws + w.dbsum[l];  // (unpacked into the reference's bias rows in one launch after the loop)
-    ub.dst[l] = d_grads + m->off_conv_b[l];
+    ub.src[l] = b.dbias;  // (unpacked into the reference's bias rows in one launch after the loop)
+    ub.dst[l] = b.dbias_rows;
     ub.width[l] = W;
     if (l == 0) break;  // the atom features need no gradient
     // dX holds the self part; the neighbour part is added onto it, and where the window kernels can hold a third tile
     // the GraphPool backward of the block below runs in the same pass
+    const uint8_t* arg_below = reinterpret_cast<const uint8_t*>(ws + w.arg[l - 1]);
     if (gb) {
       if (!win_two_stage_usable_h(g, K)) {
         set_error("bf16 gradient streams: no LDS for the two-stage window pass");
         return GCMI_ERR_UNSUPPORTED;
       }
       TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_sumacc_max_bwd_h(g, HG(dS), K, K, HG(dX), K, reinterpret_cast<const uint8_t*>(ws + w.arg[l - 1]),
-                                      HG(ws + w.tD), K, st));
+      RUN(win_gather_sumacc_max_bwd_h(g, HG(dS), K, K, HG(dX), K, arg_below, HG(ws + w.tD), K, st));
       dy_ready = true;
     } else if (win_two_stage_usable(g, K) && aligned16(dS) && aligned16(dX) && aligned16(ws + w.tD)) {
       TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_sumacc_max_bwd(g, dS, K, K, dX, K, reinterpret_cast<const uint8_t*>(ws + w.arg[l - 1]), ws + w.tD, K, st));
+      RUN(win_gather_sumacc_max_bwd(g, dS, K, K, dX, K, arg_below, ws + w.tD, K, st));
       dy_ready = true;
     } else {
       RUN(gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 1, stream));
@@ -632,6 +723,8 @@ int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const floa
   const int64_t N = g->n_atoms, B = g->n_mols;
   const Ws w = carve(m, N, B, io->ld_features);
   float* ws = io->d_workspace;
+  Block blk[kMaxL + 1];
+  make_blocks(m, w, ws, d_params, nullptr, io, blk);
   const float* x = io->d_atom_features;
   int64_t ldx = io->ld_features;
   if (training && m->batch_norm && N > 0 &&
@@ -639,123 +732,53 @@ int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const floa
     set_error("model_forward: memset failed");
     return GCMI_ERR_LAUNCH;
   }
+  // training with BatchNorm: a product's epilogue also adds the column sums of its output into the BatchNorm
+  // accumulators (clean: zeroed above, self-cleaning afterwards), so the layer output is not read again
+  double* acc = reinterpret_cast<double*>(ws + w.acc);
+  double* stats = (m->batch_norm && training) ? acc : nullptr;
   bool stats_fused = false;
   const bool one_piece = one_piece_block0(m, g, io);
   note_one_piece(ws, one_piece);
   RUN(pack_biases(m, w, ws, d_params, st));
   for (int l = 0; l < L; ++l) {
-    const int K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
-    const int W = m->conv_width[l];
-    const Segs sg = make_segs(g, K, W);
+    const Block& b = blk[l];
+    const int W = b.W;
+    const Segs sg = make_segs(g, b.K, W);
     stats_fused = false;
     if (l == 0 && one_piece) {
-      bf16_t* s0 = reinterpret_cast<bf16_t*>(ws + w.S[0]);
-      bf16_t* xb = reinterpret_cast<bf16_t*>(ws + w.xb);
-      double* stats = training ? reinterpret_cast<double*>(ws + w.acc) : nullptr;
-      {
-        TimedScope ts(GCMI_K_GATHER_SUM, st);
-        RUN(win_gather_sum_fh(g, x, ldx, 76, s0, xb, kOnePieceLd, st));
-      }
-      {
-        TimedScope ts(GCMI_K_SEG_GEMM, st);
-        const int rc = fwd_h_gemm(sg.n, sg.begin, sg.end, s0, kOnePieceLd, K, d_params + m->off_conv_w[0], sg.w_rel, xb,
-                                  kOnePieceLd, K, d_params + m->off_conv_w[0], sg.w_self, ws + w.bsum[0], sg.b_off, W, 0, 1,
-                                  nullptr, W, stats, ws + w.wimg, st, ws + w.gc[0]);
-        if (rc == GCMI_ERR_UNSUPPORTED) set_error("model_forward: the one-piece product of GraphConv 0 refused its shape");
-        RUN(rc);
-      }
-      g_one_piece_launches.fetch_add(1, std::memory_order_relaxed);
+      RUN(one_piece_forward(g, w, ws, b, sg, io, stats, st));
       stats_fused = training != 0;
     } else if (N > 0) {
       RUN(gcmi_gather_sum_fwd(g, x, ldx, (int32_t)w.ngather[l], ws + w.S[l], w.ldS[l], 0, stream));
-      // training with BatchNorm: the product's epilogue also adds the column sums of its output into the
-      // BatchNorm accumulators (clean: zeroed above, self-cleaning afterwards), so the layer output is not read again
-      RUN(seg_gemm_stats(sg.n, sg.begin, sg.end, ws + w.S[l], w.ldS[l], K, d_params + m->off_conv_w[l],
-                         sg.w_rel, x, ldx, K, d_params + m->off_conv_w[l], sg.w_self, ws + w.bsum[l],
-                         sg.b_off, W, 0, 1, ws + w.gc[l], W,
-                         (m->batch_norm && training) ? reinterpret_cast<double*>(ws + w.acc) : nullptr,
-                         &stats_fused, stream, ws + w.wimg));
+      RUN(seg_gemm_stats(conv_product(sg, ws + w.S[l], w.ldS[l], x, ldx, b, ws + w.gc[l]), stats, &stats_fused, st,
+                         ws + w.wimg));
     }
-    float* scale = nullptr;
-    float* shift = nullptr;
-    if (m->batch_norm && N > 0) {
-      float* bnv = ws + w.bnv[l];
-      scale = bnv + 2 * W;
-      shift = bnv + 3 * W;
-      if (training && stats_fused) {
-        RUN(bn_finalize_impl(N, W, d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], m->bn_eps,
-                             m->bn_momentum, io->d_bn_running_mean[l], io->d_bn_running_var[l], bnv, bnv + W,
-                             scale, shift, reinterpret_cast<double*>(ws + w.acc), stream, io->d_bn_batches_tracked[l]));
-      } else if (training) {
-        RUN(bn_stats_impl(ws + w.gc[l], W, N, W, d_params + m->off_bn_gamma[l],
-                          d_params + m->off_bn_beta[l], m->bn_eps, m->bn_momentum,
-                          io->d_bn_running_mean[l], io->d_bn_running_var[l], bnv, bnv + W, scale, shift,
-                          reinterpret_cast<double*>(ws + w.acc), true, stream, io->d_bn_batches_tracked[l]));
-      } else {
-        RUN(gcmi_bn_fold_eval(d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l],
-                              io->d_bn_running_mean[l], io->d_bn_running_var[l], m->bn_eps, W, scale,
-                              shift, stream));
-      }
-    }
+    const bool bn = m->batch_norm && N > 0;
+    if (bn) RUN(bn_forward(m, b, N, training, stats_fused, ws + w.gc[l], W, acc, stream));
     if (N > 0)
-      RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, scale, shift, ws + w.pool[l], W,
+      RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, bn ? b.scale : nullptr, bn ? b.shift : nullptr, ws + w.pool[l], W,
                               training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, stream));
     x = ws + w.pool[l];
     ldx = W;
   }
-  const int Wl = m->conv_width[L - 1];
-  const int D = m->dense_width;
-  const int32_t zero32 = 0;
-  const int64_t zero64 = 0;
+  const Block& dn = blk[L];
+  const int D = dn.W;
   if (N > 0) {
     const int32_t nN = (int32_t)N;
-    RUN(seg_gemm_stats(1, &zero32, &nN, x, ldx, Wl, d_params + m->off_dense_w, &zero64, nullptr, 0, 0,
-                       nullptr, nullptr, d_params + m->off_dense_b, &zero64, D, 1, 1, ws + w.dense, D,
-                       (m->batch_norm && training) ? reinterpret_cast<double*>(ws + w.acc) : nullptr,
-                       &stats_fused, stream));
+    SegProduct<float> p = one_segment(&nN, x, ldx, dn.K, dn.w, dn.bias, D, ws + w.dense, D);
+    p.trans_w = 1;
+    p.act = 1;
+    RUN(seg_gemm_stats(p, stats, &stats_fused, st));
   }
-  float* scale = nullptr;
-  float* shift = nullptr;
-  if (m->batch_norm && N > 0) {
-    float* bnv = ws + w.bnv[L];
-    scale = bnv + 2 * D;
-    shift = bnv + 3 * D;
-    if (training && stats_fused) {
-      RUN(bn_finalize_impl(N, D, d_params + m->off_bn_gamma[L], d_params + m->off_bn_beta[L], m->bn_eps,
-                           m->bn_momentum, io->d_bn_running_mean[L], io->d_bn_running_var[L], bnv, bnv + D, scale,
-                           shift, reinterpret_cast<double*>(ws + w.acc), stream, io->d_bn_batches_tracked[L]));
-    } else if (training) {
-      RUN(bn_stats_impl(ws + w.dense, D, N, D, d_params + m->off_bn_gamma[L], d_params + m->off_bn_beta[L],
-                        m->bn_eps, m->bn_momentum, io->d_bn_running_mean[L], io->d_bn_running_var[L], bnv,
-                        bnv + D, scale, shift, reinterpret_cast<double*>(ws + w.acc), true, stream,
-                        io->d_bn_batches_tracked[L]));
-    } else {
-      RUN(gcmi_bn_fold_eval(d_params + m->off_bn_gamma[L], d_params + m->off_bn_beta[L],
-                            io->d_bn_running_mean[L], io->d_bn_running_var[L], m->bn_eps, D, scale, shift,
-                            stream));
-    }
-  }
-  RUN(readout_fwd_impl(g, ws + w.dense, D, D, scale, shift, 1, io->d_fingerprint, 2 * D,
-                       reinterpret_cast<int32_t*>(ws + w.arg_r), (training && m->batch_norm) ? ws + w.rsum : nullptr,
-                       stream));
-  const int TC = m->n_tasks * m->n_classes;
-  const int32_t nB = (int32_t)B;
+  const bool bn = m->batch_norm && N > 0;
+  if (bn) RUN(bn_forward(m, dn, N, training, stats_fused, ws + w.dense, D, acc, stream));
+  RUN(readout_fwd_impl(g, ws + w.dense, D, D, bn ? dn.scale : nullptr, bn ? dn.shift : nullptr, 1, io->d_fingerprint,
+                       2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
+                       (training && m->batch_norm) ? ws + w.rsum : nullptr, stream));
   RUN(head_forward(m, w, ws, d_params, io, B, stream));
   if (m->mode == 0 && io->d_probs)
     RUN(gcmi_softmax(io->d_logits, B * m->n_tasks, m->n_classes, io->d_probs, stream));
-  if (training && m->batch_norm && N == 0) {  // (with atoms, every layer's statistics launch bumps its own counter)
-    CounterPtrs c;
-    c.n = L + 1;
-    bool any = false;
-    for (int i = 0; i <= kMaxL; ++i) {
-      c.p[i] = i <= L ? io->d_bn_batches_tracked[i] : nullptr;
-      any = any || c.p[i] != nullptr;
-    }
-    if (any) {
-      hipLaunchKernelGGL(bump_counters_kernel, dim3(1), dim3(64), 0, st, c);
-      GCMI_CHECK_LAUNCH("bump_counters");
-    }
-  }
+  if (training && m->batch_norm && N == 0) RUN(bump_counters(m, io, st));
   return GCMI_OK;
 }
 
@@ -777,8 +800,8 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
   const int64_t N = g->n_atoms, B = g->n_mols;
   const Ws w = carve(m, N, B, io->ld_features);
   float* ws = io->d_workspace;
-  const int D = m->dense_width;
-  const int TC = m->n_tasks * m->n_classes;
+  Block blk[kMaxL + 1];
+  make_blocks(m, w, ws, d_params, d_grads, io, blk);
   const bool full = m->grad_mode == 1;
   const bool sym = g->d_rev_pos != nullptr || g->n_edges == 0;
   const int64_t lo = full ? 0 : (m->batch_norm ? m->off_bn_gamma[L - 1] : m->off_dense_w);
@@ -795,118 +818,93 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
   RUN(zero(d_grads + lo, sizeof(float) * (size_t)(hi - lo)));
   // dlogits (rows beyond n_rows carry no gradient), the bias-gradient sums and every accumulator
   RUN(zero(ws + w.dlogits, sizeof(float) * (size_t)(w.z_end - w.dlogits)));
-  const int32_t zero32 = 0;
-  const int64_t zero64 = 0;
-  const int32_t nB = (int32_t)B, nN = (int32_t)N;
+  double* acc = reinterpret_cast<double*>(ws + w.acc);
+  double* acc2 = reinterpret_cast<double*>(ws + w.acc2);
+  double* lacc = reinterpret_cast<double*>(ws + w.lacc);
+  const float loss_inv_count = 1.f / (float)(n_rows * m->n_tasks);
+  const Block& dn = blk[L];
+  const int D = dn.W, Wl = dn.K;
+  const int32_t nN = (int32_t)N;
   // ---- per-molecule part in one kernel where the shapes allow (head_bwd.hip): loss, d logits, head gradients, the
   // gradient w.r.t. GraphGather's pre-activation (tanh derivative applied), and -- when the one-pass dense block
   // follows -- the BatchNorm backward sums of the dense layer
-  const bool dense_fused_next = m->batch_norm && N > 0 && fused_bwd_enabled() && D == 128 &&
-                                m->conv_width[L - 1] > 32 && m->conv_width[L - 1] <= 64;
+  const bool dense_one_pass = dense_block_one_pass(m, N);
   bool head_done = false, head_sums = false;
   if (m->batch_norm) {  // (without BatchNorm the readout backward applies the tanh derivative itself)
-    const float* bnvL = ws + w.bnv[L];
     const int rc = head_bwd_fused(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks,
                                   m->n_classes, B, io->d_fingerprint, 2 * D, d_params + m->off_head_w,
-                                  d_grads + m->off_head_w, d_grads + m->off_head_b, ws + w.dfp, 2 * D,
-                                  reinterpret_cast<double*>(ws + w.lacc), g->d_mol_runs, g->max_deg + 1,
-                                  reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.rsum, bnvL, bnvL + D,
-                                  (dense_fused_next && g->d_mol_runs) ? reinterpret_cast<double*>(ws + w.acc) : nullptr, D,
-                                  st, ws + w.dlogits, w.himg >= 0 ? ws + w.himg : nullptr);
+                                  d_grads + m->off_head_w, d_grads + m->off_head_b, ws + w.dfp, 2 * D, lacc, g->d_mol_runs,
+                                  g->max_deg + 1, reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.rsum, dn.mean,
+                                  dn.invstd, (dense_one_pass && g->d_mol_runs) ? acc : nullptr, D, st, ws + w.dlogits,
+                                  w.himg >= 0 ? ws + w.himg : nullptr);
     if (rc == GCMI_OK) {
       head_done = true;
-      head_sums = dense_fused_next && g->d_mol_runs != nullptr;
+      head_sums = dense_one_pass && g->d_mol_runs != nullptr;
       // (with head_sums the loss is finalised by the BatchNorm parameter launch that follows)
-      if (!head_sums)
-        RUN(loss_finalize_impl(reinterpret_cast<double*>(ws + w.lacc), 1.f / (float)(n_rows * m->n_tasks), io->d_loss,
-                               stream, kLossRep));
+      if (!head_sums) RUN(loss_finalize_impl(lacc, loss_inv_count, io->d_loss, stream, kLossRep));
     } else if (rc != GCMI_ERR_UNSUPPORTED) {
       return rc;
     }
   }
-  if (!head_done) {
-    // ---- loss on the first n_rows molecules
-    RUN(loss_impl(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks,
-                  m->n_classes, io->d_loss, ws + w.dlogits, nullptr,
-                  reinterpret_cast<double*>(ws + w.lacc), true, stream));
-    // ---- head
-    RUN(gcmi_seg_gemm_wgrad(1, &zero32, &nB, io->d_fingerprint, 2 * D, 2 * D, ws + w.dlogits, TC, TC,
-                            d_grads + m->off_head_w, &zero64, d_grads + m->off_head_b, &zero64, 1, stream));
-    RUN(gcmi_seg_gemm(1, &zero32, &nB, ws + w.dlogits, TC, TC, d_params + m->off_head_w, &zero64, nullptr, 0,
-                      0, nullptr, nullptr, nullptr, nullptr, 2 * D, 0, 0, ws + w.dfp, 2 * D, stream));
-  }
+  // (the tanh derivative applied in place only for the BatchNorm backward below)
+  if (!head_done)
+    RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, m->batch_norm && N > 0,
+                               stream));
   if (N == 0) return GCMI_OK;
   // ---- readout (+ folded BatchNorm of the dense layer, + its ReLU mask)
   float* dyD = ws + w.tA;   // grad w.r.t. the (normalised) readout input
   float* dxD = ws + w.tB;   // grad w.r.t. the dense pre-activation
-  const int Wl = m->conv_width[L - 1];
   float* dpool = ws + w.tC;  // grad w.r.t. the output of the last GraphPool
   const float* coef = ws + w.acc;  // [A | B | C] of the BatchNorm backward just computed (bn.hip: head of its scratch)
+  const int32_t* arg_r = reinterpret_cast<const int32_t*>(ws + w.arg_r);
   bool dense_done = false;
   bool have_psums = false;  // acc2 holds sum dP, sum dP * P for the BatchNorm below the block just processed
   bool dy_ready = false;  // the gather of the block above already left this block's dy (two-stage window pass)
   if (m->batch_norm) {
     // GraphGather backward is recomputed inside the BatchNorm backward from the per-molecule
     // gradient (tanh derivative applied in place): the N x D gradient is never written or re-read
-    if (!head_done) RUN(readout_grad_prep(ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, B, D, st));
-    const float* bnv = ws + w.bnv[L];
-    const bool try_fused = fused_bwd_enabled() && D == 128 && Wl > 32 && Wl <= 64;
-    if (head_sums && !try_fused)  // (cannot happen: head_sums is computed from the same conditions)
-      RUN(loss_finalize_impl(reinterpret_cast<double*>(ws + w.lacc), 1.f / (float)(n_rows * m->n_tasks), io->d_loss,
-                             stream, kLossRep));
-    if (head_sums && try_fused) {
+    if (head_sums) {
       // the sums are in place (head_bwd.hip): dgamma, dbeta and the coefficient vectors
-      RUN(bn_bwd_params_impl(N, D, d_params + m->off_bn_gamma[L], bnv, bnv + D, d_grads + m->off_bn_gamma[L],
-                             d_grads + m->off_bn_beta[L], reinterpret_cast<double*>(ws + w.acc), stream,
-                             reinterpret_cast<double*>(ws + w.lacc), kLossRep, 1.f / (float)(n_rows * m->n_tasks),
-                             io->d_loss));
+      RUN(bn_bwd_params_impl(N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, acc, stream, lacc, kLossRep,
+                             loss_inv_count, io->d_loss));
     } else {
-      RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, reinterpret_cast<const int32_t*>(ws + w.arg_r),
-                              ws + w.dense, D, N, D, d_params + m->off_bn_gamma[L], bnv, bnv + D,
-                              d_grads + m->off_bn_gamma[L], d_grads + m->off_bn_beta[L], try_fused ? nullptr : dxD, D, 1,
-                              reinterpret_cast<double*>(ws + w.acc), true, stream, ws + w.rsum, g->d_mol_runs,
-                              g->n_mols, g->max_deg + 1));
+      RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, N, D, dn.gamma, dn.mean,
+                              dn.invstd, dn.dgamma, dn.dbeta, dense_one_pass ? nullptr : dxD, D, 1, acc, true, stream,
+                              ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1));
     }
-    if (try_fused) {
+    if (dense_one_pass) {
       // one pass: dxD formed per 64-row tile in LDS, dW_dense += dxD^T pool, db += colsum, dpool = dxD W_dense
       TimedScope ts(GCMI_K_FUSED_BWD, st);
-      const int rc = fused_dense_bwd(N, g->d_membership, ws + w.dfp, 2 * D,
-                                     reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.dense, D, coef, D,
-                                     ws + w.pool[L - 1], Wl, Wl, d_params + m->off_dense_w, d_grads + m->off_dense_w,
-                                     d_grads + m->off_dense_b, dpool, Wl,
-                                     reinterpret_cast<double*>(ws + w.acc2), st);
+      const int rc = fused_dense_bwd(N, g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, coef, D,
+                                     ws + w.pool[L - 1], Wl, Wl, dn.w, dn.dw, dn.dbias, dpool, Wl, acc2, st);
       if (rc == GCMI_OK) {
         dense_done = true;
         have_psums = true;
       }
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
       else  // not covered after all (misaligned buffers): the separate pass, with its sums once more
-        RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, reinterpret_cast<const int32_t*>(ws + w.arg_r),
-                                ws + w.dense, D, N, D, d_params + m->off_bn_gamma[L], bnv, bnv + D,
-                                d_grads + m->off_bn_gamma[L], d_grads + m->off_bn_beta[L], dxD, D, 1,
-                                reinterpret_cast<double*>(ws + w.acc), true, stream, ws + w.rsum, g->d_mol_runs,
+        RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, N, D, dn.gamma, dn.mean,
+                                dn.invstd, dn.dgamma, dn.dbeta, dxD, D, 1, acc, true, stream, ws + w.rsum, g->d_mol_runs,
                                 g->n_mols, g->max_deg + 1));
     }
   } else {
-    RUN(gcmi_readout_bwd(g, ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, D, 1,
-                         reinterpret_cast<const int32_t*>(ws + w.arg_r), dyD, D, stream));
+    RUN(gcmi_readout_bwd(g, ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, D, 1, arg_r, dyD, D, stream));
     RUN(gcmi_relu_bwd(dyD, D, ws + w.dense, D, N, D, stream));
     dxD = dyD;
   }
   // ---- dense layer
   if (!dense_done) {
-    RUN(gcmi_seg_gemm_wgrad(1, &zero32, &nN, ws + w.pool[L - 1], Wl, Wl, dxD, D, D, d_grads + m->off_dense_w,
-                            &zero64, d_grads + m->off_dense_b, &zero64, 1, stream));
-    RUN(gcmi_seg_gemm(1, &zero32, &nN, dxD, D, D, d_params + m->off_dense_w, &zero64, nullptr, 0, 0, nullptr,
-                      nullptr, nullptr, nullptr, Wl, 0, 0, dpool, Wl, stream));
+    RUN(gcmi_seg_gemm_wgrad(1, &kZero32, &nN, ws + w.pool[L - 1], Wl, Wl, dxD, D, D, dn.dw, &kZero64, dn.dbias, &kZero64,
+                            1, stream));
+    RUN(seg_gemm(one_segment(&nN, dxD, D, D, dn.w, nullptr, Wl, dpool, Wl), st));
   }
   // ---- GraphConv / BatchNorm / GraphPool blocks, last to first
   BiasLayers ub;
   memset(&ub, 0, sizeof(ub));
   for (int l = L - 1; l >= 0; --l) {
     if (!full && !m->batch_norm) break;  // nothing trainable in front of the dense layer
-    const int W = m->conv_width[l];
-    const int K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
+    const Block& b = blk[l];
+    const int W = b.W, K = b.K;
     float* dy = ws + w.tD;  // grad w.r.t. the (normalised) pool input
     float* dgc = ws + w.tA;  // grad w.r.t. the GraphConv pre-activation
     const Segs sg = make_segs(g, K, W);
@@ -917,6 +915,7 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
     const int64_t ldS = one_piece ? kOnePieceLd : w.ldS[l];
     float* dS = ws + w.tE;
     float* dX = ws + w.tC;
+    const uint8_t* arg = reinterpret_cast<const uint8_t*>(ws + w.arg[l]);
     // the fused pass covers the default widths in split-bf16 mode; it wants 16-byte rows of every operand
     const bool try_fused = full && fused_bwd_enabled() && W == 64 && ldx % 4 == 0 && aligned16(xin) &&
                            ((l == 0 && K > 32 && K <= 96) || (l > 0 && K > 32 && K <= 64));
@@ -929,27 +928,21 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       // The block above left sum dP and sum dP * P: this BatchNorm's backward needs no pass over dy (bn.hip,
       // bn_bwd_pool_impl).  dy itself is needed when the GraphConv below trains; otherwise only by the
       // ill-conditioned fallback, and the kernel returns at once unless that applies.
-      const float* bnv = ws + w.bnv[l];
       if (dy_ready) {
         // (left by win_gather_sumacc_max_bwd below, one iteration ago)
       } else if (full) {
-        RUN(gcmi_gather_max_bwd(g, dpool, W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), dy, W, stream));
+        RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
       } else {
         TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-        RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), dy, W,
-                                      d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], st));
+        RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.gamma, b.beta, st));
       }
-      RUN(bn_bwd_pool_impl(dy, W, ws + w.gc[l], W, N, W, d_params + m->off_bn_gamma[l], d_params + m->off_bn_beta[l], bnv,
-                           bnv + W, d_grads + m->off_bn_gamma[l], d_grads + m->off_bn_beta[l],
-                           reinterpret_cast<double*>(ws + w.acc2), reinterpret_cast<double*>(ws + w.acc), stream));
+      RUN(bn_bwd_pool_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.beta, b.mean, b.invstd, b.dgamma, b.dbeta, acc2, acc,
+                           stream));
     } else {
-      if (!dy_ready)
-        RUN(gcmi_gather_max_bwd(g, dpool, W, W, reinterpret_cast<const uint8_t*>(ws + w.arg[l]), dy, W, stream));
+      if (!dy_ready) RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
       if (m->batch_norm) {
-        const float* bnv = ws + w.bnv[l];
-        RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, d_params + m->off_bn_gamma[l], bnv, bnv + W,
-                        d_grads + m->off_bn_gamma[l], d_grads + m->off_bn_beta[l], (full && !try_fused) ? dgc : nullptr,
-                        W, 1, reinterpret_cast<double*>(ws + w.acc), true, stream));
+        RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.mean, b.invstd, b.dgamma, b.dbeta,
+                        (full && !try_fused) ? dgc : nullptr, W, 1, acc, true, stream));
       } else if (full && !try_fused) {
         RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
         dgc = dy;
@@ -963,11 +956,9 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       // and the self part of dX
       TimedScope ts(GCMI_K_FUSED_BWD, st);
       const int rc = fused_conv_bwd(sg.n, sg.begin, sg.end, sg.w_rel, sg.w_self, sg.b_off, dy, W, ws + w.gc[l], W,
-                                    m->batch_norm ? coef : nullptr, W, ws + w.S[l], ldS, xin, ldx, K,
-                                    d_params + m->off_conv_w[l], d_grads + m->off_conv_w[l], ws + w.dbsum[l],
+                                    m->batch_norm ? coef : nullptr, W, ws + w.S[l], ldS, xin, ldx, K, b.w, b.dw, b.dbias,
                                     l > 0 ? dS : nullptr, K, l > 0 ? dX : nullptr, K,
-                                    (l > 0 && sym && m->batch_norm) ? reinterpret_cast<double*>(ws + w.acc2) : nullptr,
-                                    st, 0, one_piece ? 1 : 0);
+                                    (l > 0 && sym && m->batch_norm) ? acc2 : nullptr, st, 0, one_piece ? 1 : 0);
       if (rc == GCMI_OK) {
         fused_done = true;
         have_psums = l > 0 && sym && m->batch_norm;
@@ -975,10 +966,8 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       }
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
       else if (m->batch_norm) {  // not covered after all (misaligned buffers): the separate pass, sums once more
-        const float* bnv = ws + w.bnv[l];
-        RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, d_params + m->off_bn_gamma[l], bnv, bnv + W,
-                        d_grads + m->off_bn_gamma[l], d_grads + m->off_bn_beta[l], dgc, W, 1,
-                        reinterpret_cast<double*>(ws + w.acc), true, stream));
+        RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.mean, b.invstd, b.dgamma, b.dbeta, dgc, W, 1, acc, true,
+                        stream));
       } else {
         RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
         dgc = dy;
@@ -990,13 +979,13 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       return GCMI_ERR_UNSUPPORTED;
     }
     if (!fused_done) {
-      RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, ws + w.S[l], w.ldS[l], K, dgc, W, W,
-                              d_grads + m->off_conv_w[l], sg.w_rel, nullptr, nullptr, 0, stream));
-      RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, xin, ldx, K, dgc, W, W, d_grads + m->off_conv_w[l],
-                              sg.w_self, ws + w.dbsum[l], sg.b_off, 0, stream));
+      RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, ws + w.S[l], w.ldS[l], K, dgc, W, W, b.dw, sg.w_rel, nullptr,
+                              nullptr, 0, stream));
+      RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, xin, ldx, K, dgc, W, W, b.dw, sg.w_self, b.dbias, sg.b_off, 0,
+                              stream));
     }
-    ub.src[l] = ws + w.dbsum[l];  // (unpacked into the reference's bias rows in one launch after the loop)
-    ub.dst[l] = d_grads + m->off_conv_b[l];
+    ub.src[l] = b.dbias;  // (unpacked into the reference's bias rows in one launch after the loop)
+    ub.dst[l] = b.dbias_rows;
     ub.width[l] = W;
     if (l == 0) break;  // the atom features need no gradient
     // dS = dgc . W_rel^T ; dX = dgc . W_self^T + (transposed gather of dS)
@@ -1015,13 +1004,17 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
       } else if (sym) RUN(gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 1, stream));
       else RUN(gcmi_scatter_add(g, dS, K, K, dX, K, stream));
     } else {
-      RUN(gcmi_seg_gemm(sg.n, sg.begin, sg.end, dgc, W, W, d_params + m->off_conv_w[l], sg.w_rel, nullptr, 0,
-                        0, nullptr, nullptr, nullptr, nullptr, K, 1, 0, dS, K, stream));
+      // dS = dgc . W_rel[d]^T
+      SegProduct<float> dg = seg_product(sg, dgc, W, W, b.w, sg.w_rel, K, dS);
+      dg.trans_w = 1;
+      RUN(seg_gemm(dg, st));
       // bonds listed from both ends: the scatter of dS is a gather (LDS-window kernel), and the
       // self term accumulates onto it in the GEMM epilogue
       if (sym) RUN(gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 0, stream));
-      RUN(gcmi_seg_gemm(sg.n, sg.begin, sg.end, dgc, W, W, d_params + m->off_conv_w[l], sg.w_self, nullptr, 0,
-                        0, nullptr, nullptr, nullptr, nullptr, K, 1, sym ? 2 : 0, dX, K, stream));
+      dg.op[0].w_off = sg.w_self;  // dX (+)= dgc . W_self[d]^T
+      dg.act = sym ? 2 : 0;
+      dg.out = dX;
+      RUN(seg_gemm(dg, st));
       if (!sym) RUN(gcmi_scatter_add(g, dS, K, K, dX, K, stream));
     }
     dpool = dX;
