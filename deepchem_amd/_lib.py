@@ -185,6 +185,14 @@ _SIGNATURES = {
     "gcmi_lstm_cell": [_P, c_int64, c_int32, c_int64, _P, c_int64, _P, c_int64, _P],
     "gcmi_model_forward": [_MD, _G, _P, _MIO, c_int32, _P],
     "gcmi_model_loss_backward": [_MD, _G, _P, _P, _MIO, _P, _P, c_int64, _I64P, _I64P, _P],
+    # (the two pointers before the stream: gcmi_stat_sync_fn and its context)
+    "gcmi_model_forward_dp": [_MD, _G, _P, _MIO, c_int32, _P, _P, _P],
+    "gcmi_model_loss_backward_dp": [_MD, _G, _P, _P, _MIO, _P, _P, c_int64, _I64P, _I64P, _P, _P, _P],
+    "gcmi_bn_sync_sums": [_P, c_int64, c_int64, c_int32, _P, _P, _P],
+    "gcmi_bn_sync_finalize": [_P, c_int32, _P, _P, c_float, c_float, _P, _P, _P, _P, _P, _P, _P, _P],
+    "gcmi_bn_sync_bwd_sums": [_P, c_int64, _P, c_int64, c_int64, c_int32, _P, _P, _P, _P, _P, _P, _P, _P],
+    "gcmi_bn_sync_bwd_pool": [_P, _P, c_int64, c_int32, _P, _P, _P, _P, _P, _P],
+    "gcmi_bn_sync_bwd_coef": [_P, c_int32, _P, _P, _P, _P, _P],
     "gcmi_collate_batches": [_P, c_int64, _P, _P, _P, _P, _P, c_int64, c_int32, c_int64, c_int64, _P, _P, _P, _P, _P,
                              c_int32],
     "gcmi_small_bind": [_P, _P, _P, _P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P,

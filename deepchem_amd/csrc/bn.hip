@@ -303,6 +303,103 @@ __global__ void bn_bwd_params_kernel(double* __restrict__ sums, int64_t n_rows, 
   }
 }
 
+// ---- synchronised BatchNorm (data parallel: the statistics of the GLOBAL batch).  Between "sums complete" and
+// "finalise" the step exchanges one packed buffer per BatchNorm point: [sum a (F) | sum b (F) | row count] as doubles,
+// summed over the ranks by the host's callback (gcmi_stat_sync_fn).  The collapse kernel makes that buffer of the 32
+// replicas and leaves them zero; the two kernels behind it are bn_finalize_kernel / bn_bwd_params_kernel reading
+// their sums and their row count from the buffer instead.
+//
+// Collapse, one launch, 32 lanes per column (a wave takes two), no atomics.  Backward (dgamma / dbeta given): the
+// parameter gradients are THIS rank's sums (torch SyncBatchNorm: the gradient average over the ranks that follows
+// would count global sums twice), written here, before the exchange.  psums: the pooled sums of bwd_fused.hip
+// (bn_bwd_params_pool_kernel's choice between them and the direct sums, both accumulators left clean).  loss_acc:
+// the loss finalisation of bn_bwd_params_kernel, which is this rank's own as well.
+__global__ void bn_collapse_kernel(double* __restrict__ sums, double* __restrict__ psums, int64_t n_rows, int n_feat,
+                                   const float* __restrict__ gamma, const float* __restrict__ beta,
+                                   float* __restrict__ dgamma, float* __restrict__ dbeta, double* __restrict__ xbuf,
+                                   double* __restrict__ loss_acc, int loss_rep, float loss_inv_count,
+                                   float* __restrict__ loss) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    xbuf[2 * n_feat] = (double)n_rows;
+    if (loss_acc != nullptr) {
+      double t = 0.0;
+      for (int i = 0; i < loss_rep; ++i) {
+        t += loss_acc[i];
+        loss_acc[i] = 0.0;
+      }
+      *loss = (float)(t * (double)loss_inv_count);
+    }
+  }
+  const bool direct = psums == nullptr || bn_pool_ill_conditioned(gamma, beta, n_feat);
+  const int cpb = blockDim.x / kReplicas;
+  const int rl = threadIdx.x % kReplicas;
+  for (int c0 = blockIdx.x * cpb; c0 < n_feat; c0 += gridDim.x * cpb) {
+    const int c = c0 + threadIdx.x / kReplicas;
+    double t1, t2, p1 = 0.0, p2 = 0.0;
+    take_sums_lanes(sums, n_feat, c, rl, c < n_feat, t1, t2);
+    if (psums != nullptr) take_sums_lanes(psums, n_feat, c, rl, c < n_feat, p1, p2);
+    if (c >= n_feat || rl != 0) continue;
+    if (!direct) {
+      const double gm = (double)(gamma ? gamma[c] : 1.f), bt = (double)(beta ? beta[c] : 0.f);
+      t1 = p1;
+      t2 = (p2 - bt * p1) / gm;
+    }
+    if (dbeta) dbeta[c] = (float)t1;
+    if (dgamma) dgamma[c] = (float)t2;
+    xbuf[c] = t1;
+    xbuf[n_feat + c] = t2;
+  }
+}
+
+// bn_finalize_kernel on the exchanged buffer: a thread per column.  N_g == 0 (no rank has an atom): as a batch without
+// atoms, only the counter moves; N_g == 1: the variance goes into running_var as it is (bn_finalize_kernel's guard).
+__global__ void bn_finalize_sync_kernel(const double* __restrict__ xbuf, int n_feat, const float* __restrict__ gamma,
+                                        const float* __restrict__ beta, float eps, float momentum,
+                                        float* __restrict__ running_mean, float* __restrict__ running_var,
+                                        float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale,
+                                        float* __restrict__ shift, int64_t* __restrict__ batches_tracked) {
+  if (batches_tracked != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *batches_tracked += 1;
+  const double n = xbuf[2 * n_feat];
+  if (!(n > 0.0)) return;
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n_feat; c += gridDim.x * blockDim.x) {
+    const double m = xbuf[c] / n;
+    double var = xbuf[n_feat + c] / n - m * m;  // biased
+    if (var < 0.0) var = 0.0;
+    const float mf = (float)m;
+    const float is = (float)(1.0 / sqrt(var + (double)eps));
+    const float g = gamma ? gamma[c] : 1.f;
+    const float b = beta ? beta[c] : 0.f;
+    const float sc = g * is;
+    if (mean) mean[c] = mf;
+    if (invstd) invstd[c] = is;
+    scale[c] = sc;
+    shift[c] = b - mf * sc;
+    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mf;
+    if (running_var) {
+      const double unbiased = n > 1.0 ? var * n / (n - 1.0) : var;
+      running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
+    }
+  }
+}
+
+// the coefficient vectors [A | B | C] of bn_bwd_params_kernel from the GLOBAL sums and the global row count
+__global__ void bn_bwd_coef_sync_kernel(const double* __restrict__ xbuf, int n_feat, const float* __restrict__ gamma,
+                                        const float* __restrict__ mean, const float* __restrict__ invstd,
+                                        float* __restrict__ coef) {
+  const double n = xbuf[2 * n_feat];
+  const double inv_n = n > 0.0 ? 1.0 / n : 0.0;
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < n_feat; c += gridDim.x * blockDim.x) {
+    const double db = xbuf[c], dg = xbuf[n_feat + c];
+    const double is = (double)invstd[c];
+    const double A = (double)(gamma ? gamma[c] : 1.f) * is;
+    const double B = -A * is * dg * inv_n;
+    const double C = -A * db * inv_n - B * (double)mean[c];
+    coef[c] = (float)A;
+    coef[n_feat + c] = (float)B;
+    coef[2 * n_feat + c] = (float)C;
+  }
+}
+
 constexpr int kDxRows = 256;  // smallest share of rows a workgroup takes
 
 template <int V, bool RELU, bool RD>
@@ -454,10 +551,87 @@ int bn_finalize_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, const
   return GCMI_OK;
 }
 
+// ---- synchronised BatchNorm, host side
+static int bn_sync_collapse(double* d_acc, double* d_psums, int64_t n_rows, int32_t n_feat, const float* d_gamma,
+                            const float* d_beta, float* d_dgamma, float* d_dbeta, double* d_xbuf, hipStream_t st,
+                            double* d_loss_acc = nullptr, int loss_rep = 0, float loss_inv_count = 0.f,
+                            float* d_loss = nullptr) {
+  static_assert(kReplicas == 32, "bn_collapse_kernel: one lane per replica");
+  hipLaunchKernelGGL(bn_collapse_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, d_psums, n_rows, n_feat, d_gamma,
+                     d_beta, d_dgamma, d_dbeta, d_xbuf, d_loss_acc, loss_rep, loss_inv_count, d_loss);
+  GCMI_CHECK_LAUNCH("bn_collapse");
+  return GCMI_OK;
+}
+
+// The exchange of one BatchNorm point: this rank's buffer (n_rows == 0: zero sums and count 0, no kernel filled it)
+// summed over the ranks by the caller's collective, in order on the stream
+static int bn_sync_exchange(const BnSync& sy, int64_t n_rows, int32_t n_feat, hipStream_t st) {
+  const int64_t n = 2 * (int64_t)n_feat + 1;
+  if (n_rows == 0 && hipMemsetAsync(sy.buf, 0, sizeof(double) * (size_t)n, st) != hipSuccess) {
+    set_error("bn sync: memset failed");
+    return GCMI_ERR_LAUNCH;
+  }
+  if (sy.fn(sy.ctx, sy.buf, n, st) != 0) {
+    set_error("synchronised BatchNorm: the statistics exchange callback failed");
+    return GCMI_ERR_LAUNCH;
+  }
+  return GCMI_OK;
+}
+
+static int bn_sync_finalize(const BnSync& sy, int32_t n_feat, const float* d_gamma, const float* d_beta, float eps,
+                            float momentum, float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
+                            float* d_scale, float* d_shift, hipStream_t st, int64_t* d_batches_tracked) {
+  hipLaunchKernelGGL(bn_finalize_sync_kernel, dim3((n_feat + 255) / 256), dim3(256), 0, st, sy.buf, n_feat, d_gamma, d_beta,
+                     eps, momentum, d_running_mean, d_running_var, d_mean, d_invstd, d_scale, d_shift, d_batches_tracked);
+  GCMI_CHECK_LAUNCH("bn_finalize_sync");
+  return GCMI_OK;
+}
+
+int bn_stats_sync_impl(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
+                       const float* d_beta, float eps, float momentum, float* d_running_mean, float* d_running_var,
+                       float* d_mean, float* d_invstd, float* d_scale, float* d_shift, double* d_acc, bool sums_ready,
+                       const BnSync& sy, void* stream, int64_t* d_batches_tracked) {
+  GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && d_scale && d_shift && d_acc && sy.fn && sy.buf, "bn_stats_sync: bad arguments");
+  GCMI_CHECK_ARG(n_rows == 0 || sums_ready || (d_x && ldx >= n_feat), "bn_stats_sync: bad rows");
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_BATCHNORM, st);
+  int rc = GCMI_OK;
+  if (n_rows > 0) {
+    if (!sums_ready) rc = launch_col_sums(0, d_x, ldx, nullptr, 0, nullptr, nullptr, n_rows, n_feat, d_acc, true, st);
+    if (rc == GCMI_OK)
+      rc = bn_sync_collapse(d_acc, nullptr, n_rows, n_feat, nullptr, nullptr, nullptr, nullptr, sy.buf, st);
+  }
+  if (rc == GCMI_OK) rc = bn_sync_exchange(sy, n_rows, n_feat, st);
+  if (rc == GCMI_OK)
+    rc = bn_sync_finalize(sy, n_feat, d_gamma, d_beta, eps, momentum, d_running_mean, d_running_var, d_mean, d_invstd,
+                          d_scale, d_shift, st, d_batches_tracked);
+  return rc;
+}
+
+// The backward after its sums: dgamma / dbeta of this rank, the exchange, the coefficient vectors of the global batch
+// at the head of d_acc.  n_rows == 0: the exchange alone (zero sums, count 0) -- the other ranks wait for it.
+int bn_bwd_sync_finish(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_beta, const float* d_mean,
+                       const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, double* d_psums,
+                       const BnSync& sy, void* stream, double* d_loss_acc, int loss_rep, float loss_inv_count,
+                       float* d_loss) {
+  GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && sy.fn && sy.buf, "bn_bwd_sync: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (n_rows == 0) return bn_sync_exchange(sy, 0, n_feat, st);
+  GCMI_CHECK_ARG(d_mean && d_invstd && d_acc, "bn_bwd_sync: NULL buffer");
+  int rc = bn_sync_collapse(d_acc, d_psums, n_rows, n_feat, d_gamma, d_beta, d_dgamma, d_dbeta, sy.buf, st, d_loss_acc,
+                            loss_rep, loss_inv_count, d_loss);
+  if (rc == GCMI_OK) rc = bn_sync_exchange(sy, n_rows, n_feat, st);
+  if (rc != GCMI_OK) return rc;
+  hipLaunchKernelGGL(bn_bwd_coef_sync_kernel, dim3((n_feat + 255) / 256), dim3(256), 0, st, sy.buf, n_feat, d_gamma, d_mean,
+                     d_invstd, reinterpret_cast<float*>(d_acc));
+  GCMI_CHECK_LAUNCH("bn_bwd_coef_sync");
+  return GCMI_OK;
+}
+
 int bn_bwd_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows,
                 int32_t n_feat, const float* d_gamma, const float* d_mean,
                 const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
-                int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream);
+                int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy);
 
 }  // namespace gcmi
 
@@ -513,7 +687,55 @@ int gcmi_bn_bwd(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, 
                 const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
                 int64_t lddx, int32_t relu_mask, double* d_acc, void* stream) {
   return bn_bwd_impl(d_dy, lddy, d_x, ldx, n_rows, n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta,
-                     d_dx, lddx, relu_mask, d_acc, false, stream);
+                     d_dx, lddx, relu_mask, d_acc, false, stream, nullptr);
+}
+
+// ---- synchronised BatchNorm in pieces (gcmi.h): what gcmi_model_*_dp runs around its exchange callback
+int gcmi_bn_sync_sums(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, double* d_acc, double* d_xbuf,
+                      void* stream) {
+  GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && d_acc && d_xbuf && (n_rows == 0 || (d_x && ldx >= n_feat)),
+                 "bn_sync_sums: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_col_sums(0, d_x, ldx, nullptr, 0, nullptr, nullptr, n_rows, n_feat, d_acc, false, st);
+  if (rc) return rc;
+  return bn_sync_collapse(d_acc, nullptr, n_rows, n_feat, nullptr, nullptr, nullptr, nullptr, d_xbuf, st);
+}
+
+int gcmi_bn_sync_finalize(const double* d_xbuf, int32_t n_feat, const float* d_gamma, const float* d_beta, float eps,
+                          float momentum, float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
+                          float* d_scale, float* d_shift, int64_t* d_batches_tracked, void* stream) {
+  GCMI_CHECK_ARG(n_feat > 0 && d_xbuf && d_scale && d_shift, "bn_sync_finalize: bad arguments");
+  BnSync sy{nullptr, nullptr, const_cast<double*>(d_xbuf)};
+  return bn_sync_finalize(sy, n_feat, d_gamma, d_beta, eps, momentum, d_running_mean, d_running_var, d_mean, d_invstd,
+                          d_scale, d_shift, (hipStream_t)stream, d_batches_tracked);
+}
+
+int gcmi_bn_sync_bwd_sums(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
+                          const float* d_gamma, const float* d_mean, const float* d_invstd, float* d_dgamma,
+                          float* d_dbeta, double* d_acc, double* d_xbuf, void* stream) {
+  GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && d_acc && d_xbuf && d_mean && d_invstd &&
+                     (n_rows == 0 || (d_dy && d_x && lddy >= n_feat && ldx >= n_feat)),
+                 "bn_sync_bwd_sums: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  int rc = launch_col_sums(1, d_dy, lddy, d_x, ldx, d_mean, d_invstd, n_rows, n_feat, d_acc, false, st);
+  if (rc) return rc;
+  return bn_sync_collapse(d_acc, nullptr, n_rows, n_feat, d_gamma, nullptr, d_dgamma, d_dbeta, d_xbuf, st);
+}
+
+int gcmi_bn_sync_bwd_pool(double* d_psums, double* d_acc, int64_t n_rows, int32_t n_feat, const float* d_gamma,
+                          const float* d_beta, float* d_dgamma, float* d_dbeta, double* d_xbuf, void* stream) {
+  GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && d_psums && d_acc && d_xbuf && d_gamma && d_beta,
+                 "bn_sync_bwd_pool: bad arguments");
+  return bn_sync_collapse(d_acc, d_psums, n_rows, n_feat, d_gamma, d_beta, d_dgamma, d_dbeta, d_xbuf, (hipStream_t)stream);
+}
+
+int gcmi_bn_sync_bwd_coef(const double* d_xbuf, int32_t n_feat, const float* d_gamma, const float* d_mean,
+                          const float* d_invstd, float* d_coef, void* stream) {
+  GCMI_CHECK_ARG(n_feat > 0 && d_xbuf && d_mean && d_invstd && d_coef, "bn_sync_bwd_coef: bad arguments");
+  hipLaunchKernelGGL(bn_bwd_coef_sync_kernel, dim3((n_feat + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_xbuf, n_feat,
+                     d_gamma, d_mean, d_invstd, d_coef);
+  GCMI_CHECK_LAUNCH("bn_bwd_coef_sync");
+  return GCMI_OK;
 }
 
 }  // extern "C"
@@ -523,15 +745,15 @@ namespace gcmi {
 static int bn_bwd_any(const ReadoutGrad* rgp, const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx,
                       int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
                       const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx, int64_t lddx,
-                      int32_t relu_mask, double* d_acc, bool acc_clean, void* stream);
+                      int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy);
 
 int bn_bwd_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows,
                 int32_t n_feat, const float* d_gamma, const float* d_mean,
                 const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
-                int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream) {
+                int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy) {
   GCMI_CHECK_ARG(lddy >= n_feat && d_dy, "bn_bwd: bad dy");
   return bn_bwd_any(nullptr, d_dy, lddy, d_x, ldx, n_rows, n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta,
-                    d_dx, lddx, relu_mask, d_acc, acc_clean, stream);
+                    d_dx, lddx, relu_mask, d_acc, acc_clean, stream, sy);
 }
 
 // BatchNorm backward whose incoming gradient is the GraphGather backward, recomputed on the fly
@@ -591,7 +813,8 @@ int bn_bwd_readout_impl(const int32_t* d_membership, const float* d_g2, int64_t 
                         const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
                         const float* d_mean, const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
                         int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream,
-                        const float* d_rawsum, const int32_t* d_mol_runs, int32_t n_mols, int32_t n_deg) {
+                        const float* d_rawsum, const int32_t* d_mol_runs, int32_t n_mols, int32_t n_deg,
+                        const BnSync* sy) {
   GCMI_CHECK_ARG(d_membership && d_g2 && d_arg && ldg2 >= 2 * (int64_t)n_feat, "bn_bwd_readout: bad readout gradient");
   ReadoutGrad rg{d_membership, d_g2, ldg2, d_arg};
   rg.rawsum = d_rawsum;
@@ -599,7 +822,7 @@ int bn_bwd_readout_impl(const int32_t* d_membership, const float* d_g2, int64_t 
   rg.n_mols = n_mols;
   rg.n_deg = n_deg;
   return bn_bwd_any(&rg, nullptr, 0, d_x, ldx, n_rows, n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta, d_dx,
-                    lddx, relu_mask, d_acc, acc_clean, stream);
+                    lddx, relu_mask, d_acc, acc_clean, stream, sy);
 }
 
 // dbeta = sum dy, dgamma = sum dy * xhat and the coefficient vectors, from the pooled sums (psums) or, where those
@@ -646,7 +869,8 @@ __global__ void bn_bwd_params_pool_kernel(double* __restrict__ psums, double* __
 
 int bn_bwd_pool_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
                      const float* d_gamma, const float* d_beta, const float* d_mean, const float* d_invstd,
-                     float* d_dgamma, float* d_dbeta, double* d_psums, double* d_acc, void* stream, int32_t x_bf16) {
+                     float* d_dgamma, float* d_dbeta, double* d_psums, double* d_acc, void* stream, int32_t x_bf16,
+                     const BnSync* sy) {
   GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && d_mean && d_invstd && d_acc && d_psums && d_x && d_gamma && d_beta,
                  "bn_bwd_pool: bad arguments");
   hipStream_t st = (hipStream_t)stream;
@@ -656,6 +880,9 @@ int bn_bwd_pool_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t 
                                    d_gamma, d_beta, x_bf16);
     if (rc) return rc;
   }
+  if (sy != nullptr)
+    return bn_bwd_sync_finish(n_rows, n_feat, d_gamma, d_beta, d_mean, d_invstd, d_dgamma, d_dbeta, d_acc, d_psums, *sy,
+                              stream, nullptr, 0, 0.f, nullptr);
   static_assert(kReplicas == 32, "bn_bwd_params_pool_kernel: one lane per replica");
   hipLaunchKernelGGL(bn_bwd_params_pool_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_psums, d_acc, n_rows, n_feat, d_gamma,
                      d_beta, d_mean, d_invstd, d_dgamma, d_dbeta, reinterpret_cast<float*>(d_acc));
@@ -665,10 +892,13 @@ int bn_bwd_pool_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t 
 
 int bn_bwd_params_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
                        const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, void* stream,
-                       double* d_loss_acc, int loss_rep, float loss_inv_count, float* d_loss) {
+                       double* d_loss_acc, int loss_rep, float loss_inv_count, float* d_loss, const BnSync* sy) {
   GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && d_mean && d_invstd && d_acc, "bn_bwd_params: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   TimedScope ts(GCMI_K_BATCHNORM, st);
+  if (sy != nullptr)
+    return bn_bwd_sync_finish(n_rows, n_feat, d_gamma, nullptr, d_mean, d_invstd, d_dgamma, d_dbeta, d_acc, nullptr, *sy,
+                              stream, d_loss_acc, loss_rep, loss_inv_count, d_loss);
   hipLaunchKernelGGL(bn_bwd_params_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, n_rows, n_feat,
                      d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta, reinterpret_cast<float*>(d_acc), d_loss_acc, loss_rep,
                      loss_inv_count, d_loss);
@@ -679,7 +909,7 @@ int bn_bwd_params_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, con
 static int bn_bwd_any(const ReadoutGrad* rgp, const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx,
                       int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
                       const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx, int64_t lddx,
-                      int32_t relu_mask, double* d_acc, bool acc_clean, void* stream) {
+                      int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy) {
   GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && ldx >= n_feat, "bn_bwd: bad shape");
   GCMI_CHECK_ARG(d_x && d_mean && d_invstd && d_acc, "bn_bwd: NULL buffer");
   GCMI_CHECK_ARG(d_dx == nullptr || lddx >= n_feat, "bn_bwd: bad lddx");
@@ -707,9 +937,15 @@ static int bn_bwd_any(const ReadoutGrad* rgp, const float* d_dy, int64_t lddy, c
   if (rc) return rc;
   // coefficient vectors (3F floats) live in the first 2F doubles of the scratch
   float* coef = reinterpret_cast<float*>(d_acc);
-  hipLaunchKernelGGL(bn_bwd_params_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, n_rows,
-                     n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta, coef, nullptr, 0, 0.f, nullptr);
-  GCMI_CHECK_LAUNCH("bn_bwd_params");
+  if (sy != nullptr) {
+    rc = bn_bwd_sync_finish(n_rows, n_feat, d_gamma, nullptr, d_mean, d_invstd, d_dgamma, d_dbeta, d_acc, nullptr, *sy, stream,
+                            nullptr, 0, 0.f, nullptr);
+    if (rc) return rc;
+  } else {
+    hipLaunchKernelGGL(bn_bwd_params_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, n_rows,
+                       n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta, coef, nullptr, 0, 0.f, nullptr);
+    GCMI_CHECK_LAUNCH("bn_bwd_params");
+  }
   if (d_dx) {
     ReadoutGrad rg{nullptr, nullptr, 0, nullptr};
     if (rgp) rg = *rgp;

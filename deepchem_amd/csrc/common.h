@@ -95,14 +95,16 @@ int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ld
 // unless the test below says so.  d_dy may be NULL when the caller never produces it (then the direct sums are too).
 int bn_bwd_pool_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
                      const float* d_gamma, const float* d_beta, const float* d_mean, const float* d_invstd,
-                     float* d_dgamma, float* d_dbeta, double* d_psums, double* d_acc, void* stream, int32_t x_bf16 = 0);
+                     float* d_dgamma, float* d_dbeta, double* d_psums, double* d_acc, void* stream, int32_t x_bf16 = 0,
+                     const struct BnSync* sy = nullptr);
 int win_gather_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
                               float* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, hipStream_t st);
 // the part of the BatchNorm backward after its column sums (dgamma, dbeta, coefficient vectors at the head of d_acc)
 // (d_loss_acc: also *d_loss = inv_count * sum of the loss_rep accumulator replicas, cleared -- loss_finalize_impl folded in)
 int bn_bwd_params_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
                        const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, void* stream,
-                       double* d_loss_acc = nullptr, int loss_rep = 0, float loss_inv_count = 0.f, float* d_loss = nullptr);
+                       double* d_loss_acc = nullptr, int loss_rep = 0, float loss_inv_count = 0.f, float* d_loss = nullptr,
+                       const struct BnSync* sy = nullptr);
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
@@ -324,13 +326,30 @@ int bn_stats_impl(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
 int bn_bwd_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows,
                 int32_t n_feat, const float* d_gamma, const float* d_mean, const float* d_invstd,
                 float* d_dgamma, float* d_dbeta, float* d_dx, int64_t lddx, int32_t relu_mask,
-                double* d_acc, bool acc_clean, void* stream);
+                double* d_acc, bool acc_clean, void* stream, const struct BnSync* sy = nullptr);
 int bn_bwd_readout_impl(const int32_t* d_membership, const float* d_g2, int64_t ldg2, const int32_t* d_arg,
                         const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
                         const float* d_mean, const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
                         int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream,
                         const float* d_rawsum = nullptr, const int32_t* d_mol_runs = nullptr, int32_t n_mols = 0,
-                        int32_t n_deg = 0);
+                        int32_t n_deg = 0, const struct BnSync* sy = nullptr);
+// Synchronised BatchNorm (gcmi_model_*_dp): with a BnSync the four backward calls above, after their sums, write THIS
+// rank's dgamma / dbeta, exchange [sum dy | sum dy xhat | rows] through the callback and make the coefficient vectors
+// of the global batch; the forward is bn_stats_sync_impl (sums_ready: a product's epilogue left them in d_acc).  A rank
+// without rows (n_rows == 0) takes part in every exchange with zero sums.  buf: 2F + 1 doubles.
+struct BnSync {
+  gcmi_stat_sync_fn fn;
+  void* ctx;
+  double* buf;
+};
+int bn_stats_sync_impl(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
+                       const float* d_beta, float eps, float momentum, float* d_running_mean, float* d_running_var,
+                       float* d_mean, float* d_invstd, float* d_scale, float* d_shift, double* d_acc, bool sums_ready,
+                       const BnSync& sy, void* stream, int64_t* d_batches_tracked);
+int bn_bwd_sync_finish(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_beta, const float* d_mean,
+                       const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, double* d_psums,
+                       const BnSync& sy, void* stream, double* d_loss_acc, int loss_rep, float loss_inv_count,
+                       float* d_loss);
 int readout_grad_prep(float* d_g, int64_t ldg, const float* d_out, int64_t ldo, int64_t n_mols, int n_feat,
                       hipStream_t st);
 int loss_impl(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights,

@@ -86,6 +86,7 @@ struct Ws {
                  // forward and the backward each make them of the weights they are given)
   // one region the backward zeroes with a single memset: [dlogits | dbsum per layer | lacc | acc]
   int64_t dlogits, dbsum[kMaxL], lacc, acc, acc2, z_end;
+  int64_t xch;   // synchronised BatchNorm: the exchange buffer of one BatchNorm point, 2 wmax + 1 doubles (bn.hip)
 };
 
 static inline int64_t up8(int64_t n) { return (n + 7) / 8 * 8; }
@@ -147,6 +148,7 @@ static Ws carve(const gcmi_model_desc* m, int64_t N, int64_t B, int64_t ld_featu
   w.acc = take(2 * GCMI_BN_ACC_DOUBLES(wmax));
   w.acc2 = take(2 * GCMI_BN_ACC_DOUBLES(wmax));  // pooled BatchNorm-backward sums of the block below (bwd_fused.hip)
   w.z_end = off;
+  w.xch = take(2 * (2 * wmax + 2));
   w.total = off;
   return w;
 }
@@ -353,8 +355,12 @@ static SegProduct<TA, TO> conv_product(const Segs& sg, const TA* s, int64_t lds,
 // BatchNorm of block b in the forward, folded into b.scale / b.shift for the kernel that reads the rows next: training
 // = this batch's statistics, from the sums the product left in acc (stats_fused) or from a pass over the rows; eval =
 // the running statistics
+// (sy: synchronised BatchNorm, training only -- the statistics of the global batch, also for a rank with N == 0)
 static int bn_forward(const gcmi_model_desc* m, const Block& b, int64_t N, int32_t training, bool stats_fused,
-                      const float* rows, int64_t ld, double* acc, void* stream) {
+                      const float* rows, int64_t ld, double* acc, void* stream, const BnSync* sy = nullptr) {
+  if (training && sy)
+    return bn_stats_sync_impl(rows, ld, N, b.W, b.gamma, b.beta, m->bn_eps, m->bn_momentum, b.running_mean, b.running_var,
+                              b.mean, b.invstd, b.scale, b.shift, acc, stats_fused, *sy, stream, b.batches_tracked);
   if (training && stats_fused)
     return bn_finalize_impl(N, b.W, b.gamma, b.beta, m->bn_eps, m->bn_momentum, b.running_mean, b.running_var, b.mean,
                             b.invstd, b.scale, b.shift, acc, stream, b.batches_tracked);
@@ -378,6 +384,50 @@ static int bump_counters(const gcmi_model_desc* m, const gcmi_model_io* io, hipS
     GCMI_CHECK_LAUNCH("bump_counters");
   }
   return GCMI_OK;
+}
+
+// Synchronised BatchNorm: the caller's exchange callback and the exchange buffer in the workspace
+static BnSync make_sync(gcmi_stat_sync_fn sync, void* sync_ctx, const Ws& w, float* ws) {
+  return BnSync{sync, sync_ctx, reinterpret_cast<double*>(ws + w.xch)};
+}
+
+// ... and the backward of a rank whose batch has no atoms: no BatchNorm kernel runs, but the other ranks wait in the
+// exchange of every BatchNorm point their backward computes (the dense block's, then the GraphConv blocks' last to
+// first; reference gradient mode stops behind the last GraphConv block)
+static int empty_backward_syncs(const gcmi_model_desc* m, const Block* blk, const BnSync& sy, void* stream) {
+  for (int l = m->n_layers; l >= 0; --l) {
+    RUN(bn_bwd_sync_finish(0, blk[l].W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, sy, stream,
+                           nullptr, 0, 0.f, nullptr));
+    if (m->grad_mode != 1 && l < m->n_layers) break;
+  }
+  return GCMI_OK;
+}
+
+// Synchronised BatchNorm: what makes a one-pass block kernel refuse its buffers after dispatch is known before the
+// first launch -- a workspace that is not 16-byte aligned (every block of it then is not), or rows x leading dimension
+// beyond the kernels' 32-bit element offsets.  Refused at the entry of both calls, before this rank makes any exchange
+// of the step.
+static int check_sync_buffers(const gcmi_model_desc* m, const gcmi_graph* g, const gcmi_model_io* io) {
+  if (!aligned16(io->d_workspace)) {
+    set_error("synchronised BatchNorm: the workspace must be 16-byte aligned");
+    return GCMI_ERR_UNSUPPORTED;
+  }
+  const int64_t ldmax = std::max<int64_t>(2 * (int64_t)m->dense_width, std::max<int64_t>(io->ld_features, kOnePieceLd));
+  if (fused_bwd_enabled() && (int64_t)g->n_atoms * ldmax >= (int64_t)1 << 30) {
+    set_error("synchronised BatchNorm: %lld atoms per rank are beyond the one-pass block kernels (rows x row length "
+              "below 2^30); use smaller shards", (long long)g->n_atoms);
+    return GCMI_ERR_UNSUPPORTED;
+  }
+  return GCMI_OK;
+}
+
+// The backstop of check_sync_buffers (a kernel that cannot get its LDS).  One more pass of a BatchNorm backward's sums
+// (a one-pass block kernel refused its buffers after all) would be one
+// more exchange than the other ranks make
+static int refuse_second_sync(const char* what) {
+  set_error("synchronised BatchNorm: %s refused its buffers, and the separate pass would exchange this BatchNorm's sums "
+            "twice (16-byte aligned workspace and feature rows needed)", what);
+  return GCMI_ERR_UNSUPPORTED;
 }
 
 // The first block's forward in its one-piece form (one_piece_block0 above): the window pass writes S0 and Xb as bf16
@@ -465,7 +515,7 @@ static int require_h(const gcmi_model_desc* m, const gcmi_graph* g, const gcmi_m
 }
 
 static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, const gcmi_model_io* io,
-                           int32_t training, void* stream) {
+                           int32_t training, gcmi_stat_sync_fn sync, void* sync_ctx, void* stream) {
   RUN(require_h(m, g, io, false));
   hipStream_t st = (hipStream_t)stream;
   const int L = m->n_layers;
@@ -476,6 +526,8 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
   make_blocks(m, w, ws, d_params, nullptr, io, blk);
   auto H = [&](int64_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
   double* acc = reinterpret_cast<double*>(ws + w.acc);
+  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
+  const BnSync* sy = (sync && training) ? &sync_s : nullptr;
   if (training && N > 0 && hipMemsetAsync(ws + w.acc, 0, sizeof(float) * (size_t)(w.z_end - w.acc), st) != hipSuccess) {
     set_error("model_forward: memset failed");
     return GCMI_ERR_LAUNCH;
@@ -504,12 +556,14 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
         if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: GraphConv %d has no bf16 product kernel", l);
         RUN(rc);
       }
-      RUN(bn_forward(m, b, N, training, true, nullptr, 0, acc, stream));
+      RUN(bn_forward(m, b, N, training, true, nullptr, 0, acc, stream, sy));
       {
         TimedScope ts(GCMI_K_GATHER_MAX, st);
         RUN(win_gather_max_h(g, H(w.gc[l]), b.W, b.W, b.scale, b.shift, H(w.pool[l]), b.W,
                              training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, st));
       }
+    } else if (sy) {
+      RUN(bn_forward(m, b, 0, training, true, nullptr, 0, acc, stream, sy));
     }
     xin = H(w.pool[l]);
     ldin = b.W;
@@ -527,20 +581,23 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
       if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense layer has no bf16 product kernel");
       RUN(rc);
     }
-    RUN(bn_forward(m, dn, N, training, true, nullptr, 0, acc, stream));
+    RUN(bn_forward(m, dn, N, training, true, nullptr, 0, acc, stream, sy));
+  } else if (sy) {
+    RUN(bn_forward(m, dn, 0, training, true, nullptr, 0, acc, stream, sy));
   }
   RUN(readout_fwd_impl(g, reinterpret_cast<const float*>(H(w.dense)), D, D, N > 0 ? dn.scale : nullptr,
                        N > 0 ? dn.shift : nullptr, 1, io->d_fingerprint, 2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
                        training ? ws + w.rsum : nullptr, stream, 1));
   RUN(head_forward(m, w, ws, d_params, io, B, stream));
   if (m->mode == 0 && io->d_probs) RUN(gcmi_softmax(io->d_logits, B * m->n_tasks, m->n_classes, io->d_probs, stream));
-  if (training && N == 0) RUN(bump_counters(m, io, st));
+  if (training && N == 0 && !sy) RUN(bump_counters(m, io, st));  // (sy: the finalisation of every exchange did)
   return GCMI_OK;
 }
 
 static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, float* d_grads,
                                  const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
-                                 int64_t* grad_lo, int64_t* grad_hi, void* stream) {
+                                 int64_t* grad_lo, int64_t* grad_hi, gcmi_stat_sync_fn sync, void* sync_ctx,
+                                 void* stream) {
   RUN(require_h(m, g, io, true));
   hipStream_t st = (hipStream_t)stream;
   const int L = m->n_layers;
@@ -565,6 +622,8 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
   double* acc2 = reinterpret_cast<double*>(ws + w.acc2);
   double* lacc = reinterpret_cast<double*>(ws + w.lacc);
   const float loss_inv_count = 1.f / (float)(n_rows * m->n_tasks);
+  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
+  const BnSync* sy = sync ? &sync_s : nullptr;
   // ---- per-molecule part (fp32 throughout: the fingerprint and everything behind it are per-molecule rows)
   const Block& dn = blk[L];
   const int D = dn.W;
@@ -586,7 +645,7 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
       RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, true, stream));
     }
   }
-  if (N == 0) return GCMI_OK;
+  if (N == 0) return sy ? empty_backward_syncs(m, blk, *sy, stream) : GCMI_OK;
   float* dpool = ws + w.tC;
   const float* coef = ws + w.acc;
   // storage == 2: dpool, dy, dS and dXs are bf16 rows (in the same fp32-sized workspace blocks, ld in elements)
@@ -595,12 +654,12 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
   // ---- dense block: BatchNorm sums from per-molecule data, then one pass (dense and pool rows arrive as bf16)
   if (head_sums) {
     RUN(bn_bwd_params_impl(N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, acc, stream, lacc, kLossRep,
-                           loss_inv_count, io->d_loss));
+                           loss_inv_count, io->d_loss, sy));
   } else {
     // (the per-molecule sums kernel reads rawsum, never the atom rows: the bf16 matrix is only passed through)
     RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, reinterpret_cast<const int32_t*>(ws + w.arg_r),
                             HF(w.dense), D, N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, nullptr, D, 1, acc,
-                            true, stream, ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1));
+                            true, stream, ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1, sy));
   }
   {
     TimedScope ts(GCMI_K_FUSED_BWD, st);
@@ -638,7 +697,7 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
       RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.gamma, b.beta, st));
     }
     RUN(bn_bwd_pool_impl(dy, W, HF(w.gc[l]), W, N, W, b.gamma, b.beta, b.mean, b.invstd, b.dgamma, b.dbeta, acc2, acc,
-                         stream, gb ? 2 : 1));
+                         stream, gb ? 2 : 1, sy));
     dy_ready = false;
     if (!full) break;  // reference semantics: nothing in front of a GraphConv output trains
     {
@@ -709,7 +768,14 @@ int64_t gcmi_model_workspace_floats(const gcmi_model_desc* m, int64_t n_atoms, i
 
 int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params,
                        const gcmi_model_io* io, int32_t training, void* stream) {
+  return gcmi_model_forward_dp(m, g, d_params, io, training, nullptr, nullptr, stream);
+}
+
+int gcmi_model_forward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params,
+                          const gcmi_model_io* io, int32_t training, gcmi_stat_sync_fn sync, void* sync_ctx,
+                          void* stream) {
   RUN(check_desc(m));
+  GCMI_CHECK_ARG(sync == nullptr || m->batch_norm, "model_forward_dp: a statistics exchange for a model without BatchNorm");
   RUN(check_graph(g, true));
   GCMI_CHECK_ARG(io && d_params && io->d_workspace && io->d_logits && io->d_fingerprint,
                  "model_forward: NULL buffer");
@@ -717,7 +783,8 @@ int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const floa
   GCMI_CHECK_ARG(g->n_mols > 1, "graph_gather requires batches larger than 1");
   GCMI_CHECK_ARG(g->n_atoms == 0 || io->d_atom_features, "model_forward: NULL atom features");
   GCMI_CHECK_ARG(io->ld_features >= m->n_feat_in, "ld_features < n_feat_in");
-  if (m->storage >= 1) return model_forward_h(m, g, d_params, io, training, stream);
+  if (sync && training) RUN(check_sync_buffers(m, g, io));
+  if (m->storage >= 1) return model_forward_h(m, g, d_params, io, training, sync, sync_ctx, stream);
   hipStream_t st = (hipStream_t)stream;
   const int L = m->n_layers;
   const int64_t N = g->n_atoms, B = g->n_mols;
@@ -736,6 +803,8 @@ int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const floa
   // accumulators (clean: zeroed above, self-cleaning afterwards), so the layer output is not read again
   double* acc = reinterpret_cast<double*>(ws + w.acc);
   double* stats = (m->batch_norm && training) ? acc : nullptr;
+  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
+  const BnSync* sy = (sync && training) ? &sync_s : nullptr;
   bool stats_fused = false;
   const bool one_piece = one_piece_block0(m, g, io);
   note_one_piece(ws, one_piece);
@@ -754,7 +823,7 @@ int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const floa
                          ws + w.wimg));
     }
     const bool bn = m->batch_norm && N > 0;
-    if (bn) RUN(bn_forward(m, b, N, training, stats_fused, ws + w.gc[l], W, acc, stream));
+    if (bn || sy) RUN(bn_forward(m, b, N, training, stats_fused, ws + w.gc[l], W, acc, stream, sy));
     if (N > 0)
       RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, bn ? b.scale : nullptr, bn ? b.shift : nullptr, ws + w.pool[l], W,
                               training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, stream));
@@ -771,14 +840,14 @@ int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const floa
     RUN(seg_gemm_stats(p, stats, &stats_fused, st));
   }
   const bool bn = m->batch_norm && N > 0;
-  if (bn) RUN(bn_forward(m, dn, N, training, stats_fused, ws + w.dense, D, acc, stream));
+  if (bn || sy) RUN(bn_forward(m, dn, N, training, stats_fused, ws + w.dense, D, acc, stream, sy));
   RUN(readout_fwd_impl(g, ws + w.dense, D, D, bn ? dn.scale : nullptr, bn ? dn.shift : nullptr, 1, io->d_fingerprint,
                        2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
                        (training && m->batch_norm) ? ws + w.rsum : nullptr, stream));
   RUN(head_forward(m, w, ws, d_params, io, B, stream));
   if (m->mode == 0 && io->d_probs)
     RUN(gcmi_softmax(io->d_logits, B * m->n_tasks, m->n_classes, io->d_probs, stream));
-  if (training && m->batch_norm && N == 0) RUN(bump_counters(m, io, st));
+  if (training && m->batch_norm && N == 0 && !sy) RUN(bump_counters(m, io, st));  // (sy: every exchange's finalisation did)
   return GCMI_OK;
 }
 
@@ -786,15 +855,27 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
                              float* d_grads, const gcmi_model_io* io, const float* d_labels,
                              const float* d_weights, int64_t n_rows, int64_t* grad_lo,
                              int64_t* grad_hi, void* stream) {
+  return gcmi_model_loss_backward_dp(m, g, d_params, d_grads, io, d_labels, d_weights, n_rows, grad_lo, grad_hi, nullptr,
+                                     nullptr, stream);
+}
+
+int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params,
+                                float* d_grads, const gcmi_model_io* io, const float* d_labels,
+                                const float* d_weights, int64_t n_rows, int64_t* grad_lo, int64_t* grad_hi,
+                                gcmi_stat_sync_fn sync, void* sync_ctx, void* stream) {
   RUN(check_desc(m));
+  GCMI_CHECK_ARG(sync == nullptr || m->batch_norm,
+                 "model_loss_backward_dp: a statistics exchange for a model without BatchNorm");
   RUN(check_graph(g, true));
   GCMI_CHECK_ARG(io && d_params && d_grads && io->d_workspace && io->d_logits && io->d_fingerprint &&
                      io->d_loss && d_labels,
                  "model_loss_backward: NULL buffer");
   GCMI_CHECK_ARG(n_rows > 0 && n_rows <= g->n_mols, "n_rows %lld outside (0, n_mols=%d]", (long long)n_rows,
                  g->n_mols);
+  if (sync) RUN(check_sync_buffers(m, g, io));
   if (m->storage >= 1)
-    return model_loss_backward_h(m, g, d_params, d_grads, io, d_labels, d_weights, n_rows, grad_lo, grad_hi, stream);
+    return model_loss_backward_h(m, g, d_params, d_grads, io, d_labels, d_weights, n_rows, grad_lo, grad_hi, sync,
+                                 sync_ctx, stream);
   hipStream_t st = (hipStream_t)stream;
   const int L = m->n_layers;
   const int64_t N = g->n_atoms, B = g->n_mols;
@@ -822,6 +903,8 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
   double* acc2 = reinterpret_cast<double*>(ws + w.acc2);
   double* lacc = reinterpret_cast<double*>(ws + w.lacc);
   const float loss_inv_count = 1.f / (float)(n_rows * m->n_tasks);
+  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
+  const BnSync* sy = sync ? &sync_s : nullptr;
   const Block& dn = blk[L];
   const int D = dn.W, Wl = dn.K;
   const int32_t nN = (int32_t)N;
@@ -850,7 +933,7 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
   if (!head_done)
     RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, m->batch_norm && N > 0,
                                stream));
-  if (N == 0) return GCMI_OK;
+  if (N == 0) return sy ? empty_backward_syncs(m, blk, *sy, stream) : GCMI_OK;
   // ---- readout (+ folded BatchNorm of the dense layer, + its ReLU mask)
   float* dyD = ws + w.tA;   // grad w.r.t. the (normalised) readout input
   float* dxD = ws + w.tB;   // grad w.r.t. the dense pre-activation
@@ -866,11 +949,11 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
     if (head_sums) {
       // the sums are in place (head_bwd.hip): dgamma, dbeta and the coefficient vectors
       RUN(bn_bwd_params_impl(N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, acc, stream, lacc, kLossRep,
-                             loss_inv_count, io->d_loss));
+                             loss_inv_count, io->d_loss, sy));
     } else {
       RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, N, D, dn.gamma, dn.mean,
                               dn.invstd, dn.dgamma, dn.dbeta, dense_one_pass ? nullptr : dxD, D, 1, acc, true, stream,
-                              ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1));
+                              ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1, sy));
     }
     if (dense_one_pass) {
       // one pass: dxD formed per 64-row tile in LDS, dW_dense += dxD^T pool, db += colsum, dpool = dxD W_dense
@@ -882,6 +965,7 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
         have_psums = true;
       }
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
+      else if (sy) return refuse_second_sync("the one-pass dense block");
       else  // not covered after all (misaligned buffers): the separate pass, with its sums once more
         RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, N, D, dn.gamma, dn.mean,
                                 dn.invstd, dn.dgamma, dn.dbeta, dxD, D, 1, acc, true, stream, ws + w.rsum, g->d_mol_runs,
@@ -937,12 +1021,12 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
         RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.gamma, b.beta, st));
       }
       RUN(bn_bwd_pool_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.beta, b.mean, b.invstd, b.dgamma, b.dbeta, acc2, acc,
-                           stream));
+                           stream, 0, sy));
     } else {
       if (!dy_ready) RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
       if (m->batch_norm) {
         RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.mean, b.invstd, b.dgamma, b.dbeta,
-                        (full && !try_fused) ? dgc : nullptr, W, 1, acc, true, stream));
+                        (full && !try_fused) ? dgc : nullptr, W, 1, acc, true, stream, sy));
       } else if (full && !try_fused) {
         RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
         dgc = dy;
@@ -965,6 +1049,7 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
         if (one_piece) g_one_piece_launches.fetch_add(1, std::memory_order_relaxed);
       }
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
+      else if (sy) return refuse_second_sync("the one-pass GraphConv block");
       else if (m->batch_norm) {  // not covered after all (misaligned buffers): the separate pass, sums once more
         RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.mean, b.invstd, b.dgamma, b.dbeta, dgc, W, 1, acc, true,
                         stream));

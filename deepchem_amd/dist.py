@@ -9,8 +9,21 @@ all 204 k floats in ``"full"``.  At <= 1 MB the ring is latency-bound on the
 7 x 153 GB/s links, so a single fused call beats per-tensor calls; the result
 is scaled by 1/world_size, which equals the single-process mean over the global
 batch when every rank holds the same number of molecules
-(loss = mean over (B, T), torch_model.py:1290-1291).  BatchNorm statistics stay
-per rank, as torch DDP would leave them.
+(loss = mean over (B, T), torch_model.py:1290-1291).
+
+BatchNorm.  By default its statistics stay per rank, as torch DDP would leave them: every
+rank normalises over its own shard, the ranks end with different running statistics, and a
+two-rank run is not the single-process run at the global batch.
+``shard_model(model, sync_batchnorm=True)`` makes the native ``GraphConvModel`` step
+normalise over the GLOBAL batch (what ``torch.nn.SyncBatchNorm`` does for an autograd
+model): at each of its BatchNorm points the library hands ``StatAllReduce`` one packed
+float64 buffer ``[sum a | sum b | rows]`` of 2 F + 1 doubles to sum over the ranks --
+L + 1 small collectives in the forward (a = x, b = x^2) and L + 1 in the backward of
+``grad_mode="full"`` (2 in ``"reference"``; a = dy, b = dy * xhat).  Mean, variance and the
+running statistics come from the global sums and the global row count; in the backward
+dgamma / dbeta stay this rank's sums (the gradient all-reduce averages them like every
+other gradient) and only the dx coefficients use the global sums.  Every rank makes every
+call, one whose shard has no atoms included.  DESIGN.md section 6 has the details.
 """
 from typing import List, Optional, Sequence, Tuple
 
@@ -131,15 +144,60 @@ class FlatGradArena:
         return all(p.grad is not None and p.grad.data_ptr() == v.data_ptr() for p, v in self.views)
 
 
-def shard_model(model, group=None) -> None:
+class StatAllReduce:
+    """The statistics exchange of synchronised BatchNorm: a float64 SUM all-reduce of the buffer the native step
+    names (``native.NativeNet`` wraps it as a view of its workspace), enqueued on the current stream."""
+
+    def __init__(self, world_size: Optional[int] = None, group=None):
+        self.group = group
+        self.world_size = world_size if world_size is not None else dist.get_world_size(group)
+
+    def reduce_stats(self, buf: torch.Tensor) -> None:
+        if buf.dtype != torch.float64 or not buf.is_contiguous():
+            raise ValueError("the statistics buffer must be contiguous float64")
+        if self.world_size == 1 or buf.numel() == 0:
+            return
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group)
+
+
+def _check_sync_batchnorm(model) -> None:
+    """Synchronised BatchNorm exists in the native GraphConvModel step only: refuse everything else here, by name."""
+    module = model.model
+    if not hasattr(module, "_native_net"):
+        raise ValueError("sync_batchnorm=True: %s has no native training step (only GraphConvModel's native step "
+                         "exchanges BatchNorm statistics)" % type(model).__name__)
+    if getattr(module, "uncertainty", False) or getattr(model, "uncertainty", False):
+        raise ValueError("sync_batchnorm=True: the uncertainty head trains through autograd, which has no exchange")
+    bns = list(getattr(module, "batch_norms", []))
+    if not bns or not any(isinstance(bn, torch.nn.BatchNorm1d) for bn in bns):
+        raise ValueError("sync_batchnorm=True: the model has no BatchNorm (batch_normalize=False): nothing to synchronise")
+    for bn in bns:
+        if not isinstance(bn, torch.nn.BatchNorm1d) or not bn.affine or not bn.track_running_stats:
+            raise ValueError("sync_batchnorm=True: non-standard BatchNorm (the native step covers affine BatchNorm1d "
+                             "with running statistics after every layer)")
+    if next(module.parameters()).is_cuda and module._native_net() is None:
+        raise ValueError("sync_batchnorm=True: the native GraphConv step does not cover this configuration")
+
+
+def shard_model(model, group=None, sync_batchnorm: bool = False) -> None:
     """Make ``model.fit*`` data-parallel across the initialised process group:
-    broadcast rank 0's parameters and buffers, then all-reduce gradients each step."""
+    broadcast rank 0's parameters and buffers, then all-reduce gradients each step.
+
+    ``sync_batchnorm=True`` (``GraphConvModel`` with ``batch_normalize=True``): every training BatchNorm normalises
+    over the global batch, through one small float64 all-reduce per BatchNorm point (module docstring); the ranks
+    then hold identical running statistics, and equal shards reproduce the single-process step at the global batch.
+    ``fit`` then takes the per-batch native step and NOT the small-batch engine, whose statistics stay per rank by
+    design.  A model or a step the native path does not cover raises (here, or at the first step) -- it never trains
+    unsynchronised without saying so.  Default ``False``: statistics per rank, as before."""
     if not dist.is_initialized():
         raise RuntimeError("torch.distributed is not initialised")
+    if sync_batchnorm:
+        _check_sync_batchnorm(model)
     with torch.no_grad():
         for t in list(model.model.parameters()) + list(model.model.buffers()):
             dist.broadcast(t, src=0, group=group)
     model._grad_sync = FlatGradAllReduce(group=group)
+    model._stat_sync = StatAllReduce(group=group) if sync_batchnorm else None
     # models whose backward runs through autograd get one flat gradient arena, so that their exchange is the same single
     # zero-copy all-reduce (GraphConvModel's native step brings its own)
     if getattr(model, "_grad_arena", None) is not None and model._grad_arena.covers(model.model):

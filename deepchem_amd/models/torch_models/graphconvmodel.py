@@ -372,6 +372,12 @@ class GraphConvModel(TorchModel):
                 and len(labels) == 1 and len(weights) == 1 and not self.uncertainty):
             native = self.model._native_net(quick=self._native_checked)
             self._native_checked = native is not None
+        stat_sync = getattr(self, "_stat_sync", None)
+        if stat_sync is not None and (native is None or not native.desc.batch_norm):
+            # (never a silent per-rank BatchNorm: the autograd path has no exchange)
+            raise RuntimeError("shard_model(sync_batchnorm=True): this step does not run on the native GraphConv step "
+                               "with BatchNorm (custom loss / optimizer / regularisation, an uncertainty head, or a "
+                               "configuration the native step does not cover), so its BatchNorm cannot be synchronised")
         if native is None:
             return super(GraphConvModel, self)._train_step(inputs, labels, weights, loss, optimizer)
         graph = getattr(inputs, "graph", None)
@@ -383,8 +389,8 @@ class GraphConvModel(TorchModel):
         graph.set_mols(self.model.graph_gather.batch_size)
         if optimizer._flat is None or optimizer._flat["p"].data_ptr() != native.flat.data_ptr():
             optimizer.attach_flat(native.flat, native.grad_flat, native._slices)
-        native.forward(x.to(torch.float32), graph, True, want_probs=False)
-        batch_loss = native.loss_backward(labels[0], weights[0], int(n_samples))
+        native.forward(x.to(torch.float32), graph, True, want_probs=False, stat_sync=stat_sync)
+        batch_loss = native.loss_backward(labels[0], weights[0], int(n_samples), stat_sync=stat_sync)
         lo, hi = native.grad_range
         if self._grad_sync is not None:
             if hasattr(self._grad_sync, "reduce_flat"):
@@ -485,7 +491,9 @@ class GraphConvModel(TorchModel):
         done = None
         # (data parallel: the engine takes a gradient exchange that works on the flat arena, deepchem_amd.dist)
         plain = (variables is None and loss is None and not callbacks and self.regularization_loss is None
-                 and (self._grad_sync is None or hasattr(self._grad_sync, "reduce_flat")))
+                 and (self._grad_sync is None or hasattr(self._grad_sync, "reduce_flat"))
+                 # synchronised BatchNorm (dist.shard_model): the per-batch step; the engine's statistics are per rank
+                 and getattr(self, "_stat_sync", None) is None)
         if plain:
             done = self._fit_small(dataset, nb_epoch, max_checkpoints_to_keep, checkpoint_interval, deterministic,
                                    restore, all_losses)

@@ -4,7 +4,9 @@
 helper re-points every ``nn.Parameter`` at a slice of ONE flat fp32 arena (in
 ``parameters()`` order), keeps a same-shaped gradient arena, and drives
 ``gcmi_model_forward`` / ``gcmi_model_loss_backward`` (include/gcmi.h), which enqueue
-every kernel of the step back to back without returning to Python.  The flat
+every kernel of the step back to back without returning to Python (with a statistics
+exchanger -- synchronised BatchNorm, ``deepchem_amd.dist`` -- their ``_dp`` forms, which
+call back once per BatchNorm point for the collective).  The flat
 arenas also make the optimizer one launch (``GcmiAdam``) and the data-parallel
 gradient exchange one zero-copy all-reduce (``deepchem_amd.dist``).
 
@@ -29,6 +31,8 @@ class NativeUnsupported(Exception):
 
 
 class NativeNet:
+    # gcmi_stat_sync_fn (include/gcmi.h): int (*)(void* ctx, double* d_buf, int64_t n_doubles, void* stream)
+    _STAT_SYNC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
 
     def __init__(self, module: nn.Module):
         self.module = module
@@ -201,8 +205,35 @@ class NativeNet:
         return io, logits, probs, fp, loss
 
     # ------------------------------------------------------------------ calls
-    def forward(self, x: torch.Tensor, graph: BatchGraph, training: bool, want_probs: bool = True):
-        """Returns (logits (B, T*C), probs|None, fingerprint (B, 2*dense)), all untrimmed."""
+    def _call_dp(self, name: str, stat_sync, head, tail):
+        """``name`` with the statistics exchange callback between ``head`` and ``tail``: the buffer the library names
+        is all-reduced as a float64 view of the workspace tensor.  An exception in the callback never unwinds through
+        the C frames: it is kept, the callback returns non-zero, and it is raised once the call is back."""
+        ws = self._ws
+        failure = []
+
+        def _sync(ctx, ptr, count, stream):
+            try:
+                off = (ptr or 0) - ws.data_ptr()
+                if off < 0 or off % 16 or count <= 0 or off + 8 * count > 4 * ws.numel():
+                    raise RuntimeError("statistics buffer outside the workspace")
+                stat_sync.reduce_stats(ws[off // 4:off // 4 + 2 * count].view(torch.float64))
+                return 0
+            except BaseException as e:
+                failure.append(e)
+                return 1
+
+        cb = self._STAT_SYNC_FN(_sync)
+        try:
+            _lib.call(name, *head, ctypes.cast(cb, ctypes.c_void_p), None, *tail)
+        except _lib.GcmiError:
+            if failure:
+                raise failure[0]
+            raise
+
+    def forward(self, x: torch.Tensor, graph: BatchGraph, training: bool, want_probs: bool = True, stat_sync=None):
+        """Returns (logits (B, T*C), probs|None, fingerprint (B, 2*dense)), all untrimmed.  ``stat_sync`` (training
+        only): an exchanger with ``reduce_stats(float64 tensor)``; BatchNorm then normalises over the global batch."""
         d = self.desc
         if not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or x.shape[0] != graph.n_atoms \
                 or (x.shape[1] > 1 and x.stride(1) != 1):
@@ -213,13 +244,19 @@ class NativeNet:
             raise ValueError("the graph has no readout plan (set_mols)")
         io, logits, probs, fp, loss = self._io(x, graph, want_probs)
         self._last = (io, logits, probs, fp, loss, x, graph)
-        _lib.call("gcmi_model_forward", ctypes.byref(d), graph.ref, ctypes.c_void_p(self.flat.data_ptr()),
-                  ctypes.byref(io), 1 if training else 0, _stream())
+        head = (ctypes.byref(d), graph.ref, ctypes.c_void_p(self.flat.data_ptr()), ctypes.byref(io), 1 if training else 0)
+        if stat_sync is not None and training:
+            if not d.batch_norm:
+                raise ValueError("synchronised BatchNorm asked of a model without BatchNorm")
+            self._call_dp("gcmi_model_forward_dp", stat_sync, head, (_stream(),))
+        else:
+            _lib.call("gcmi_model_forward", *head, _stream())
         return logits, probs, fp
 
-    def loss_backward(self, labels: torch.Tensor, weights: Optional[torch.Tensor], n_rows: int):
+    def loss_backward(self, labels: torch.Tensor, weights: Optional[torch.Tensor], n_rows: int, stat_sync=None):
         """After ``forward(training=True)``: loss over the first n_rows molecules and the backward
-        pass into the gradient arena.  Returns the loss (0-dim device tensor)."""
+        pass into the gradient arena.  Returns the loss (0-dim device tensor).  ``stat_sync``: the exchanger the
+        forward was given (the BatchNorm backward then uses the global sums for dx, this rank's for dgamma / dbeta)."""
         io, logits, probs, fp, loss, x, graph = self._last
         d = self.desc
         graph.ensure_rev_pos()
@@ -238,11 +275,14 @@ class NativeNet:
             if weights.numel() != n_rows * d.n_tasks:
                 raise ValueError("weights %s do not match (%d, %d)" % (tuple(weights.shape), n_rows, d.n_tasks))
         lo, hi = ctypes.c_int64(0), ctypes.c_int64(0)
-        _lib.call("gcmi_model_loss_backward", ctypes.byref(d), graph.ref,
-                  ctypes.c_void_p(self.flat.data_ptr()), ctypes.c_void_p(self.grad_flat.data_ptr()),
-                  ctypes.byref(io), ctypes.c_void_p(labels.data_ptr()),
-                  ctypes.c_void_p(weights.data_ptr()) if weights is not None else None, int(n_rows),
-                  ctypes.byref(lo), ctypes.byref(hi), _stream())
+        head = (ctypes.byref(d), graph.ref, ctypes.c_void_p(self.flat.data_ptr()),
+                ctypes.c_void_p(self.grad_flat.data_ptr()), ctypes.byref(io), ctypes.c_void_p(labels.data_ptr()),
+                ctypes.c_void_p(weights.data_ptr()) if weights is not None else None, int(n_rows), ctypes.byref(lo),
+                ctypes.byref(hi))
+        if stat_sync is not None:
+            self._call_dp("gcmi_model_loss_backward_dp", stat_sync, head, (_stream(),))
+        else:
+            _lib.call("gcmi_model_loss_backward", *head, _stream())
         self.grad_range = (int(lo.value), int(hi.value))
         self._expose_grads()
         return loss

@@ -576,6 +576,52 @@ int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, cons
                              float* d_grads, const gcmi_model_io* io, const float* d_labels,
                              const float* d_weights, int64_t n_rows, int64_t* grad_lo,
                              int64_t* grad_hi, void* stream);
+/* Data-parallel form with SYNCHRONISED BatchNorm: exactly the two calls above, with every training
+ * BatchNorm of the step normalising over the GLOBAL batch.  Between "column sums complete" and "finalise" of each
+ * BatchNorm point the library calls, on the calling thread,
+ *     sync(ctx, d_buf, n_doubles, stream)
+ * with d_buf = [sum a (F) | sum b (F) | rows of this rank] as doubles (n_doubles = 2 F + 1, inside io->d_workspace,
+ * 16-byte aligned; F = the width of that BatchNorm).  Contract as gcmi_grad_sync_fn: it must ENQUEUE, in order on
+ * `stream`, a SUM all-reduce of those doubles over the ranks and return 0; a non-zero return aborts the call with
+ * GCMI_ERR_LAUNCH; the library makes no RCCL call itself.  Forward (training): n_layers + 1 calls, a = x, b = x^2;
+ * mean, biased variance, the folded scale / shift and the running statistics (unbiased factor N_g / (N_g - 1)) come
+ * from the global sums and the global row count N_g; num_batches_tracked moves once per rank.  Backward: n_layers + 1
+ * calls in full gradient mode, 2 in reference mode, a = dy, b = dy * xhat; dgamma / dbeta are THIS rank's sums (torch
+ * SyncBatchNorm: the gradient average over the ranks follows), the dx coefficients come from the global sums and N_g.
+ * Every rank makes the same calls in the same order, a rank whose batch has no atoms included (zero sums, count 0).
+ * The model must have BatchNorm (else GCMI_ERR_ARG).  sync == NULL: gcmi_model_forward / _loss_backward; the
+ * eval-mode forward never calls sync.                                                                           */
+typedef int (*gcmi_stat_sync_fn)(void* ctx, double* d_buf, int64_t n_doubles, void* stream);
+int gcmi_model_forward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params,
+                          const gcmi_model_io* io, int32_t training, gcmi_stat_sync_fn sync, void* sync_ctx,
+                          void* stream);
+int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params,
+                                float* d_grads, const gcmi_model_io* io, const float* d_labels,
+                                const float* d_weights, int64_t n_rows, int64_t* grad_lo, int64_t* grad_hi,
+                                gcmi_stat_sync_fn sync, void* sync_ctx, void* stream);
+/* The pieces of a synchronised BatchNorm for callers that sequence their own step.  d_xbuf: 2 F + 1 doubles.
+ * gcmi_bn_sync_sums: column sums of x and x^2 and the row count of THIS rank -> d_xbuf (d_acc: GCMI_BN_ACC_DOUBLES(F)
+ *   doubles of scratch, left zero behind its first 2 F doubles).  Sum d_xbuf over the ranks, then
+ * gcmi_bn_sync_finalize: what gcmi_bn_stats leaves, from the summed buffer.
+ * gcmi_bn_sync_bwd_sums: sums of dy and dy * xhat -> d_xbuf; d_dgamma / d_dbeta (may be NULL) = this rank's sums.
+ * gcmi_bn_sync_bwd_pool: the same buffer and gradients from accumulators the caller's kernels filled (both in the
+ *   GCMI_BN_ACC_DOUBLES layout, both left zero behind their first 2 F doubles): d_psums holds the POOLED sums of a
+ *   one-pass block backward, sum dP and sum dP * P with P = gamma * xhat + beta, so that sum dy * xhat =
+ *   (sum dP * P - beta * sum dP) / gamma; d_acc holds the direct sums, which are used instead when some column has
+ *   |beta| > 64 |gamma| (the pooled form is ill-conditioned there).
+ * gcmi_bn_sync_bwd_coef: from the summed buffer the 3 F floats [A | B | C] with dx = A dy + B x + C (gcmi_bn_bwd).   */
+int gcmi_bn_sync_sums(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, double* d_acc, double* d_xbuf,
+                      void* stream);
+int gcmi_bn_sync_finalize(const double* d_xbuf, int32_t n_feat, const float* d_gamma, const float* d_beta, float eps,
+                          float momentum, float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
+                          float* d_scale, float* d_shift, int64_t* d_batches_tracked, void* stream);
+int gcmi_bn_sync_bwd_sums(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
+                          const float* d_gamma, const float* d_mean, const float* d_invstd, float* d_dgamma,
+                          float* d_dbeta, double* d_acc, double* d_xbuf, void* stream);
+int gcmi_bn_sync_bwd_pool(double* d_psums, double* d_acc, int64_t n_rows, int32_t n_feat, const float* d_gamma,
+                          const float* d_beta, float* d_dgamma, float* d_dbeta, double* d_xbuf, void* stream);
+int gcmi_bn_sync_bwd_coef(const double* d_xbuf, int32_t n_feat, const float* d_gamma, const float* d_mean,
+                          const float* d_invstd, float* d_coef, void* stream);
 
 /* ---------------------------------------------------------------- small-batch engine
  * The same model step for batches whose activations live in L2 (the reference's default batch of 100
