@@ -105,6 +105,22 @@ class GcmiModelIO(Structure):
     ]
 
 
+class GcmiOptDesc(Structure):
+    """struct gcmi_opt_desc (include/gcmi.h)."""
+    _fields_ = [
+        ("rule", c_int32),
+        ("beta1", c_float),
+        ("beta2", c_float),
+        ("eps", c_float),
+        ("weight_decay", c_float),
+        ("alpha", c_float),
+        ("momentum", c_float),
+    ]
+
+
+RULE_SGD, RULE_ADAGRAD, RULE_RMSPROP, RULE_ADAM_L2, RULE_ADAMW, RULE_LAMB = 0, 1, 2, 3, 4, 5
+
+
 class GcmiSmallBatch(Structure):
     """struct gcmi_small_batch (include/gcmi.h)."""
     _fields_ = [
@@ -164,6 +180,8 @@ _SIGNATURES = {
     "gcmi_loss_fwd_bwd": [c_int32, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P],
     "gcmi_softmax": [_P, c_int64, c_int32, _P, _P],
     "gcmi_adam_step": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int64, _P],
+    "gcmi_opt_step": [POINTER(GcmiOptDesc), _P, _P, _P, _P, c_int64, c_float, c_int64, _P],
+    "gcmi_lamb_step": [POINTER(GcmiOptDesc), _P, _P, _P, _P, _P, _P, c_int32, c_int64, _P, c_float, _P],
     "gcmi_fold_affine": [_P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P],
     "gcmi_weave_pair_to_atom": [_P, c_int64, c_int32, _P, c_int64, c_int32, _P, _P, c_int32, _P, c_int64, _P],
     "gcmi_weave_pair_features": [_P, _P, c_int64, c_int32, _P, _P, c_int64, c_int32, _P, _P, c_int32, _P,
@@ -201,6 +219,8 @@ _SIGNATURES = {
                        c_int64, _P, _I64P, _I64P, _P],
     "gcmi_small_fit_dp": [_MD, _P, _P, _P, _P, _MIO, _P, c_int64, c_int64, c_int64, c_float, c_float, c_float, c_float,
                           c_int64, _P, _I64P, _I64P, _P, _P, _P],
+    "gcmi_small_fit_opt": [_MD, _P, _P, _P, _P, _MIO, _P, c_int64, c_int64, c_int64, POINTER(GcmiOptDesc),
+                           POINTER(c_float), c_int64, _P, _I64P, _I64P, _P, _P, _P],
     "gcmi_small_predict": [_MD, _P, _MIO, _P, c_int64, c_int64, c_int64, _P],
     "gcmi_diag_mfma_peak": [c_int32, c_int32, _P, _P],
     "gcmi_set_option": [c_int32, c_int32],
@@ -213,7 +233,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = ["gcmi_version", "gcmi_last_error", "gcmi_model_workspace_floats", "gcmi_small_workspace_floats",
-           "gcmi_task_head_scratch_floats",
+           "gcmi_task_head_scratch_floats", "gcmi_lamb_scratch_floats",
            "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout"] + sorted(_SIGNATURES)
 
 _lib = None
@@ -257,6 +277,7 @@ def load():
         "gcmi_smiles_check": (c_char_p, [c_char_p]),
         "gcmi_collate_plan_words": (c_int64, [c_int64]),
         "gcmi_task_head_scratch_floats": (c_int64, []),
+        "gcmi_lamb_scratch_floats": (c_int64, [c_int64, c_int64]),
     }
     for name, (restype, argtypes) in special.items():
         if host_only and not hasattr(lib, name):

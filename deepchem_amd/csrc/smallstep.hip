@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "optim_rules.h"
 
 namespace gcmi {
 
@@ -1399,10 +1400,10 @@ small_gather_add_kernel(SmallGraph g, const float* __restrict__ dXs, const float
 struct StepEnd {
   float* p;
   float* grad;
-  float* m;
+  float* m;                // the rule's state arenas (optim_rules.h); Adam: exp_avg, exp_avg_sq
   float* v;
   int64_t lo, hi;          // trained range of the flat arenas
-  float one_minus_b1, b2, one_minus_b2, step_size, inv_bc2_sqrt, eps;
+  OptConsts k;
   double* loss_acc;
   float* loss_out;         // this step's loss
   float inv_count;
@@ -1420,26 +1421,26 @@ struct StepEnd {
   int64_t zero2_doubles;
 };
 
+template <int R>
 __global__ void __launch_bounds__(kSBlock)
 small_step_end_kernel(StepEnd s) {
-  // torch.optim.Adam (optimizers.py:231-241): exp_avg.lerp_, exp_avg_sq.mul_.addcmul_, addcdiv_
+  // the optimizer rule over the trained range (optim_rules.h; kRuleAdam: torch.optim.Adam, optimizers.py:231-241)
+  constexpr int kStates = R == kRuleSGD ? 0 : (R == kRuleAdagrad || R == kRuleRMSprop) ? 1 : 2;
   const int64_t n4 = (s.hi - s.lo) / 4;
   for (int64_t i = (int64_t)blockIdx.x * kSBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kSBlock) {
     const int64_t o = s.lo + 4 * i;
-    float4 g = ld4(s.grad + o), m = ld4(s.m + o), v = ld4(s.v + o), p = ld4(s.p + o);
+    float4 g = ld4(s.grad + o), p = ld4(s.p + o);
+    float4 m = make_float4(0.f, 0.f, 0.f, 0.f), v = m;
+    if constexpr (kStates >= 1) m = ld4(s.m + o);
+    if constexpr (kStates >= 2) v = ld4(s.v + o);
     float* gf = reinterpret_cast<float*>(&g);
     float* mf = reinterpret_cast<float*>(&m);
     float* vf = reinterpret_cast<float*>(&v);
     float* pf = reinterpret_cast<float*>(&p);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      mf[c] = mf[c] + (gf[c] - mf[c]) * s.one_minus_b1;
-      vf[c] = vf[c] * s.b2 + gf[c] * gf[c] * s.one_minus_b2;
-      const float denom = sqrtf(vf[c]) * s.inv_bc2_sqrt + s.eps;
-      pf[c] -= s.step_size * (mf[c] / denom);
-    }
-    st4(s.m + o, m);
-    st4(s.v + o, v);
+    for (int c = 0; c < 4; ++c) opt_update<R>(pf[c], gf[c], mf[c], vf[c], s.k);
+    if constexpr (kStates >= 1) st4(s.m + o, m);
+    if constexpr (kStates >= 2) st4(s.v + o, v);
     st4(s.p + o, p);
     st4(s.grad + o, make_float4(0.f, 0.f, 0.f, 0.f));  // the next step accumulates into a clean arena
   }
@@ -1936,12 +1937,30 @@ int64_t gcmi_small_workspace_floats(const gcmi_model_desc* m, int64_t max_atoms,
   return small_carve(m, max_atoms, max_mols).total;
 }
 
+// Adam without weight decay at one rate for the whole call: what gcmi_small_fit / gcmi_small_fit_dp promise
+static int small_fit_adam(const gcmi_model_desc* m, float* d_params, float* d_grads, float* d_adam_m, float* d_adam_v,
+                          const gcmi_model_io* io, const gcmi_small_batch* batches, int64_t n_batches, int64_t ws_atoms,
+                          int64_t ws_mols, float lr, float beta1, float beta2, float eps, int64_t first_step,
+                          float* d_losses, int64_t* grad_lo, int64_t* grad_hi, gcmi_grad_sync_fn sync, void* sync_ctx,
+                          void* stream) {
+  GCMI_CHECK_ARG(d_adam_m && d_adam_v, "small_fit: NULL buffer");
+  gcmi_opt_desc opt;
+  memset(&opt, 0, sizeof(opt));
+  opt.rule = GCMI_RULE_ADAM_L2;
+  opt.beta1 = beta1;
+  opt.beta2 = beta2;
+  opt.eps = eps;
+  const std::vector<float> rates((size_t)std::max<int64_t>(n_batches, 1), lr);
+  return gcmi_small_fit_opt(m, d_params, d_grads, d_adam_m, d_adam_v, io, batches, n_batches, ws_atoms, ws_mols, &opt,
+                            rates.data(), first_step, d_losses, grad_lo, grad_hi, sync, sync_ctx, stream);
+}
+
 int gcmi_small_fit(const gcmi_model_desc* m, float* d_params, float* d_grads, float* d_adam_m, float* d_adam_v,
                    const gcmi_model_io* io, const gcmi_small_batch* batches, int64_t n_batches, int64_t ws_atoms,
                    int64_t ws_mols, float lr, float beta1, float beta2, float eps, int64_t first_step,
                    float* d_losses, int64_t* grad_lo, int64_t* grad_hi, void* stream) {
-  return gcmi_small_fit_dp(m, d_params, d_grads, d_adam_m, d_adam_v, io, batches, n_batches, ws_atoms, ws_mols, lr, beta1,
-                           beta2, eps, first_step, d_losses, grad_lo, grad_hi, nullptr, nullptr, stream);
+  return small_fit_adam(m, d_params, d_grads, d_adam_m, d_adam_v, io, batches, n_batches, ws_atoms, ws_mols, lr, beta1,
+                        beta2, eps, first_step, d_losses, grad_lo, grad_hi, nullptr, nullptr, stream);
 }
 
 int gcmi_small_fit_dp(const gcmi_model_desc* m, float* d_params, float* d_grads, float* d_adam_m, float* d_adam_v,
@@ -1949,10 +1968,24 @@ int gcmi_small_fit_dp(const gcmi_model_desc* m, float* d_params, float* d_grads,
                       int64_t ws_mols, float lr, float beta1, float beta2, float eps, int64_t first_step,
                       float* d_losses, int64_t* grad_lo, int64_t* grad_hi, gcmi_grad_sync_fn sync, void* sync_ctx,
                       void* stream) {
+  return small_fit_adam(m, d_params, d_grads, d_adam_m, d_adam_v, io, batches, n_batches, ws_atoms, ws_mols, lr, beta1,
+                        beta2, eps, first_step, d_losses, grad_lo, grad_hi, sync, sync_ctx, stream);
+}
+
+int gcmi_small_fit_opt(const gcmi_model_desc* m, float* d_params, float* d_grads, float* d_state1, float* d_state2,
+                       const gcmi_model_io* io, const gcmi_small_batch* batches, int64_t n_batches, int64_t ws_atoms,
+                       int64_t ws_mols, const gcmi_opt_desc* opt, const float* lr_per_step, int64_t first_step,
+                       float* d_losses, int64_t* grad_lo, int64_t* grad_hi, gcmi_grad_sync_fn sync, void* sync_ctx,
+                       void* stream) {
   SRUN(small_check(m));
-  GCMI_CHECK_ARG(d_params && d_grads && d_adam_m && d_adam_v && io && io->d_workspace && (batches || n_batches == 0),
-                 "small_fit: NULL buffer");
   GCMI_CHECK_ARG(n_batches >= 0 && first_step >= 1, "small_fit: bad n_batches / first_step");
+  OptConsts k0;
+  int rule = 0;
+  SRUN(opt_consts(opt, 0.f, first_step, &k0, &rule));
+  const int n_states = opt_rule_states(rule);
+  GCMI_CHECK_ARG((n_states < 1 || d_state1) && (n_states < 2 || d_state2) && (lr_per_step || n_batches == 0),
+                 "small_fit: NULL optimizer state / learning rates");
+  GCMI_CHECK_ARG(d_params && d_grads && io && io->d_workspace && (batches || n_batches == 0), "small_fit: NULL buffer");
   const int L = m->n_layers;
   const bool full = m->grad_mode == 1;
   const int64_t lo = full ? 0 : (m->batch_norm ? m->off_bn_gamma[L - 1] : m->off_dense_w);
@@ -2060,24 +2093,16 @@ int gcmi_small_fit_dp(const gcmi_model_desc* m, float* d_params, float* d_grads,
       set_error("small_fit: the gradient all-reduce callback failed at step %lld", (long long)(first_step + i));
       return GCMI_ERR_LAUNCH;
     }
-    // Adam over the trained range, loss, running statistics, counters, zeroing
+    // the optimizer rule over the trained range, loss, running statistics, counters, zeroing
     StepEnd se;
     memset(&se, 0, sizeof(se));
-    const int64_t step = first_step + i;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
+    SRUN(opt_consts(opt, lr_per_step[i], first_step + i, &se.k, &rule));
     se.p = d_params;
     se.grad = d_grads;
-    se.m = d_adam_m;
-    se.v = d_adam_v;
+    se.m = d_state1;
+    se.v = d_state2;
     se.lo = lo;
     se.hi = hi;
-    se.one_minus_b1 = 1.f - beta1;
-    se.b2 = beta2;
-    se.one_minus_b2 = 1.f - beta2;
-    se.step_size = (float)((double)lr / bc1);
-    se.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    se.eps = eps;
     se.loss_acc = c.accs + c.w.loss;
     se.loss_out = d_losses ? d_losses + i : nullptr;
     se.inv_count = ra.inv_count;
@@ -2099,7 +2124,9 @@ int gcmi_small_fit_dp(const gcmi_model_desc* m, float* d_params, float* d_grads,
     int blocks = (int)((n4 + kSBlock - 1) / kSBlock);
     if (blocks < 1) blocks = 1;
     if (blocks > 512) blocks = 512;
-    hipLaunchKernelGGL(small_step_end_kernel, dim3(blocks), dim3(kSBlock), 0, c.st, se);
+    opt_dispatch(rule, [&](auto r) {
+      hipLaunchKernelGGL((small_step_end_kernel<decltype(r)::value>), dim3(blocks), dim3(kSBlock), 0, c.st, se);
+    });
     GCMI_CHECK_LAUNCH("small_step_end");
     if (side && ((i + 1) % kAhead == 0 || i + 1 == n_batches) &&
         hipEventRecord(side->ev_free[(i / kAhead) & 1], c.st) != hipSuccess) {

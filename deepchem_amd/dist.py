@@ -110,7 +110,7 @@ class FlatGradArena:
             self.slices.append((off, p.numel()))
             off += n
         # home_params: the parameters themselves move into one flat buffer of the same layout, so that the optimizer
-        # step is ONE launch over [params | grads | moments] (GcmiAdam.attach_flat / step_flat) instead of one per tensor
+        # step is ONE launch over [params | grads | moments] (FlatOptimizer.attach_flat / step_flat) instead of one per tensor
         self.pflat = None
         if home_params:
             self.pflat = torch.zeros_like(self.flat)

@@ -362,13 +362,13 @@ class GraphConvModel(TorchModel):
 
     def _train_step(self, inputs, labels, weights, loss, optimizer):
         """One optimizer step.  With the model's own loss and optimizer this is three C calls
-        (forward, loss + backward, Adam over the flat gradient range); anything custom goes through
+        (forward, loss + backward, the optimizer rule over the flat gradient range); anything custom goes through
         the autograd path of TorchModel._train_step."""
-        from deepchem_amd.models.optimizers import GcmiAdam
+        from deepchem_amd.models.optimizers import FlatOptimizer
         from deepchem_amd.models.torch_models.torch_model import _StandardLoss
         native = None
         if (loss is self._loss_fn and isinstance(loss, _StandardLoss) and self.regularization_loss is None
-                and isinstance(optimizer, GcmiAdam) and optimizer is self._pytorch_optimizer
+                and isinstance(optimizer, FlatOptimizer) and optimizer is self._pytorch_optimizer
                 and len(labels) == 1 and len(weights) == 1 and not self.uncertainty):
             native = self.model._native_net(quick=self._native_checked)
             self._native_checked = native is not None
@@ -503,13 +503,14 @@ class GraphConvModel(TorchModel):
                                                deterministic, restore, variables, loss, callbacks, all_losses)
 
     def _fit_small(self, dataset, nb_epoch, max_keep, interval, deterministic, restore, all_losses):
-        from deepchem_amd.models.optimizers import GcmiAdam
+        from deepchem_amd.models.optimizers import FlatOptimizer
         from deepchem_amd.models.torch_models.torch_model import _LossWindow, _StandardLoss, logger
         from deepchem_amd.small import SMALL_MAX_ATOMS, ChunkCollator, HeldChunks
         if not isinstance(self._loss_fn, _StandardLoss) or self.device.type != 'cuda':
             return None
         self._ensure_built()
-        if self._lr_schedule is not None or not isinstance(self._pytorch_optimizer, GcmiAdam):
+        # (Lamb needs per-tensor norms: the per-batch native step)
+        if not isinstance(self._pytorch_optimizer, FlatOptimizer) or not self._pytorch_optimizer._small_engine_rule:
             return None
         engine = self._small_engine()
         if engine is None:
@@ -577,7 +578,8 @@ class GraphConvModel(TorchModel):
                 if r < B:
                     w_t[b * B + r:(b + 1) * B] = 0  # padding rows of a ragged last batch carry no weight
             collator.bind(ch, [B] * ch.n_batches, labels=y_t, label_stride=label_stride, weights=w_t, weight_stride=T)
-            losses = engine.fit(ch.descs, self._pytorch_optimizer, ch.max_atoms, B, grad_sync=self._grad_sync)
+            losses = engine.fit(ch.descs, self._pytorch_optimizer, ch.max_atoms, B, grad_sync=self._grad_sync,
+                                schedule=self._lr_schedule)
             held.hold(ch)
             pending.append((self._global_step + 1, losses))
             self._global_step += ch.n_batches

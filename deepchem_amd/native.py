@@ -7,7 +7,7 @@ helper re-points every ``nn.Parameter`` at a slice of ONE flat fp32 arena (in
 every kernel of the step back to back without returning to Python (with a statistics
 exchanger -- synchronised BatchNorm, ``deepchem_amd.dist`` -- their ``_dp`` forms, which
 call back once per BatchNorm point for the collective).  The flat
-arenas also make the optimizer one launch (``GcmiAdam``) and the data-parallel
+arenas also make the optimizer one launch (``FlatOptimizer``) and the data-parallel
 gradient exchange one zero-copy all-reduce (``deepchem_amd.dist``).
 
 Numerically this is the same kernel sequence as the autograd path in

@@ -331,6 +331,63 @@ def adam_step_(p, grad, m, v, lr, beta1, beta2, eps, step: int):
               float(beta2), float(eps), int(step), _stream())
 
 
+OPT_RULES = {"sgd": _lib.RULE_SGD, "adagrad": _lib.RULE_ADAGRAD, "rmsprop": _lib.RULE_RMSPROP,
+             "adam_l2": _lib.RULE_ADAM_L2, "adamw": _lib.RULE_ADAMW, "lamb": _lib.RULE_LAMB}
+
+
+def opt_desc(rule, beta1=0.0, beta2=0.0, eps=0.0, weight_decay=0.0, alpha=0.0, momentum=0.0) -> "_lib.GcmiOptDesc":
+    """struct gcmi_opt_desc; ``rule``: a key of ``OPT_RULES`` or the number itself."""
+    d = _lib.GcmiOptDesc()
+    d.rule = OPT_RULES[rule] if isinstance(rule, str) else int(rule)
+    d.beta1, d.beta2, d.eps = float(beta1), float(beta2), float(eps)
+    d.weight_decay, d.alpha, d.momentum = float(weight_decay), float(alpha), float(momentum)
+    return d
+
+
+def _flat_f32(t, name, n):
+    if t is None:
+        return
+    if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+        raise ValueError("%s must be a contiguous float32 CUDA tensor of %d" % (name, n))
+
+
+def opt_step_(desc, p, grad, state1, state2, lr, step: int):
+    """One elementwise optimizer step (gcmi_opt_step) on flat float32 tensors, in place.  ``state1`` / ``state2``:
+    what the rule keeps (include/gcmi.h); None where it keeps nothing."""
+    n = p.numel()
+    for t, nm in ((p, "param"), (grad, "grad"), (state1, "state1"), (state2, "state2")):
+        _flat_f32(t, "opt: " + nm, n)
+    _lib.call("gcmi_opt_step", ctypes.byref(desc), _ptr(p), _ptr(grad), _ptr(state1), _ptr(state2), n, float(lr),
+              int(step), _stream())
+
+
+def lamb_scratch_floats(n: int, n_segments: int) -> int:
+    need = int(_lib.load().gcmi_lamb_scratch_floats(int(n), int(n_segments)))
+    if need < 0:
+        raise ValueError("lamb: bad sizes (%d floats, %d segments)" % (n, n_segments))
+    return need
+
+
+def lamb_step_(desc, p, grad, m, v, scratch, segments, norms, lr):
+    """One Lamb step (gcmi_lamb_step) over flat float32 arenas, in place.  ``segments``: int64 CUDA tensor
+    (n_segments, 2) of (offset, numel); ``norms``: float32 CUDA tensor (n_segments, 3) or None; ``scratch``:
+    ``lamb_scratch_floats`` floats."""
+    n = p.numel()
+    for t, nm in ((p, "param"), (grad, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
+        _flat_f32(t, "lamb: " + nm, n)
+    if (not segments.is_cuda or segments.dtype != torch.int64 or not segments.is_contiguous() or segments.dim() != 2
+            or segments.shape[1] != 2):
+        raise ValueError("lamb: segments must be a contiguous int64 CUDA tensor (n_segments, 2)")
+    n_seg = int(segments.shape[0])
+    _flat_f32(scratch, "lamb: scratch", scratch.numel())
+    if scratch.numel() < lamb_scratch_floats(n, n_seg):
+        raise ValueError("lamb: the scratch holds %d floats, %d needed" % (scratch.numel(), lamb_scratch_floats(n, n_seg)))
+    if norms is not None:
+        _flat_f32(norms, "lamb: norms", 3 * n_seg)
+    _lib.call("gcmi_lamb_step", ctypes.byref(desc), _ptr(p), _ptr(grad), _ptr(m), _ptr(v), _ptr(scratch), _ptr(segments),
+              n_seg, n, _ptr(norms), float(lr), _stream())
+
+
 # ------------------------------------------------------------------ Weave
 def fold_affine(w: torch.Tensor, b: Optional[torch.Tensor], scale: Optional[torch.Tensor],
                 shift: Optional[torch.Tensor], trans_w: bool = False):

@@ -6,9 +6,9 @@ leave the GPU almost empty and the Python loop of ``fit_generator`` (torch_model
 than the arithmetic.  ``gcmi_small_fit`` / ``gcmi_small_predict`` (include/gcmi.h, csrc/smallstep.hip)
 run the whole step -- forward, loss, backward, Adam, BatchNorm running statistics -- as 8-12 launches
 on 16-row degree tiles, for a whole list of collated batches per call.  This class owns the host side:
-the descriptor array, the workspace, and the hand-over of the optimizer state (the flat moment buffers
-of ``GcmiAdam``, so a checkpoint taken afterwards is indistinguishable from one written by the
-per-batch path).
+the descriptor array, the workspace, the learning rate of every step of a call, and the hand-over of the
+optimizer state (the flat state buffers of a ``FlatOptimizer``, so a checkpoint taken afterwards is
+indistinguishable from one written by the per-batch path).
 """
 import ctypes
 from typing import List, Optional, Sequence, Tuple
@@ -84,18 +84,25 @@ class SmallBatchEngine:
     _SYNC_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p)
 
     def fit(self, descs: Sequence[GcmiSmallBatch], optimizer, max_atoms: int, max_mols: int,
-            grad_sync=None) -> torch.Tensor:
-        """One Adam step per descriptor, in order.  Returns the per-step losses (device, float32).
+            grad_sync=None, schedule=None) -> torch.Tensor:
+        """One optimizer step per descriptor, in order.  Returns the per-step losses (device, float32).
+
+        ``optimizer``: a ``FlatOptimizer`` with an elementwise rule (``deepchem_amd.models.optimizers``; not Lamb).
+        ``schedule``: the torch scheduler of ``optimizer`` or None.  Step i runs under the rate the optimizer holds
+        after i scheduler steps: the rates of the whole call are read here, ``group["lr"]`` then ``schedule.step()``
+        once per descriptor, so they are torch's own values and the scheduler ends where the per-batch loop leaves it.
 
         ``grad_sync`` (data parallel, ``deepchem_amd.dist.FlatGradAllReduce``): its ``reduce_flat`` is called once
-        per step on the trained range of the gradient arena, between the backward launches and the Adam launch of
-        that step (``gcmi_small_fit_dp``); torch.distributed orders the collective on the current stream, which is the
-        stream the library launches on."""
+        per step on the trained range of the gradient arena, between the backward launches and the optimizer launch of
+        that step; torch.distributed orders the collective on the current stream, which is the stream the library
+        launches on."""
         nat = self.native
         n = len(descs)
         losses = torch.empty(n, dtype=torch.float32, device=nat.flat.device)
         if n == 0:
             return losses
+        if not getattr(optimizer, "_small_engine_rule", False):
+            raise SmallUnsupported("the small-batch engine has no %s step" % type(optimizer).__name__)
         if optimizer._flat is None or optimizer._flat["p"].data_ptr() != nat.flat.data_ptr():
             optimizer.attach_flat(nat.flat, nat.grad_flat, nat._slices)
         d = nat.desc
@@ -106,21 +113,23 @@ class SmallBatchEngine:
         if f.get("range") != (lo, hi):
             optimizer._setup_flat_range(lo, hi)
         group = optimizer.param_groups[0]
-        beta1, beta2 = group["betas"]
+        opt = optimizer._desc(group)
+        states = [ctypes.c_void_p(t.data_ptr()) for t in f["bufs"]] + [None, None]
         first_step = int(f["step_t"].item()) + 1
+        rates = (ctypes.c_float * n)()
+        optimizer._opt_called = True  # (torch's schedulers warn when they step before the optimizer ever has)
+        for i in range(n):
+            rates[i] = float(group["lr"])
+            if schedule is not None:
+                schedule.step()
         arr = (GcmiSmallBatch * n)(*descs)
         ws, a, b = self._workspace(max_atoms, max_mols)
         io = self._io(ws)
         glo, ghi = ctypes.c_int64(0), ctypes.c_int64(0)
-        if grad_sync is None:
-            _lib.call("gcmi_small_fit", ctypes.byref(d), ctypes.c_void_p(nat.flat.data_ptr()),
-                      ctypes.c_void_p(nat.grad_flat.data_ptr()), ctypes.c_void_p(f["m"].data_ptr()),
-                      ctypes.c_void_p(f["v"].data_ptr()), ctypes.byref(io), ctypes.cast(arr, ctypes.c_void_p), n, a, b,
-                      float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), first_step,
-                      ctypes.c_void_p(losses.data_ptr()), ctypes.byref(glo), ctypes.byref(ghi), _stream())
-        else:
+        failure = []
+        cb = None
+        if grad_sync is not None:
             bucket = nat.grad_flat[lo:hi]
-            failure = []
 
             def _sync(ctx, ptr, count, stream):
                 try:
@@ -133,17 +142,16 @@ class SmallBatchEngine:
                     return 1
 
             cb = self._SYNC_FN(_sync)
-            try:
-                _lib.call("gcmi_small_fit_dp", ctypes.byref(d), ctypes.c_void_p(nat.flat.data_ptr()),
-                          ctypes.c_void_p(nat.grad_flat.data_ptr()), ctypes.c_void_p(f["m"].data_ptr()),
-                          ctypes.c_void_p(f["v"].data_ptr()), ctypes.byref(io), ctypes.cast(arr, ctypes.c_void_p), n, a, b,
-                          float(group["lr"]), float(beta1), float(beta2), float(group["eps"]), first_step,
-                          ctypes.c_void_p(losses.data_ptr()), ctypes.byref(glo), ctypes.byref(ghi),
-                          ctypes.cast(cb, ctypes.c_void_p), None, _stream())
-            except _lib.GcmiError:
-                if failure:
-                    raise failure[0]
-                raise
+        try:
+            _lib.call("gcmi_small_fit_opt", ctypes.byref(d), ctypes.c_void_p(nat.flat.data_ptr()),
+                      ctypes.c_void_p(nat.grad_flat.data_ptr()), states[0], states[1], ctypes.byref(io),
+                      ctypes.cast(arr, ctypes.c_void_p), n, a, b, ctypes.byref(opt), rates, first_step,
+                      ctypes.c_void_p(losses.data_ptr()), ctypes.byref(glo), ctypes.byref(ghi),
+                      ctypes.cast(cb, ctypes.c_void_p) if cb is not None else None, None, _stream())
+        except _lib.GcmiError:
+            if failure:
+                raise failure[0]
+            raise
         assert (glo.value, ghi.value) == (lo, hi)
         f["step_t"] += n
         nat.grad_range = (lo, hi)

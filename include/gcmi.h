@@ -488,6 +488,47 @@ int gcmi_softmax(const float* d_logits, int64_t n_rows_tasks, int32_t n_classes,
 int gcmi_adam_step(float* d_param, const float* d_grad, float* d_m, float* d_v, int64_t n,
                    float lr, float beta1, float beta2, float eps, int64_t step, void* stream);
 
+/* The other optimizers of models/optimizers.py on flat ranges (csrc/optim.hip).
+ * gcmi_opt_desc: rule + its hyper-parameters (the ones a rule does not use are ignored):
+ *   GCMI_RULE_SGD      p -= lr g                                                   (torch.optim.SGD, :482-488)
+ *   GCMI_RULE_ADAGRAD  sum += g^2; p -= lr g / (sqrt(sum) + eps)                   (torch.optim.Adagrad, :160-170;
+ *                      state1 = sum, which the caller starts at initial_accumulator_value)
+ *   GCMI_RULE_RMSPROP  sq = alpha sq + (1 - alpha) g^2; avg = sqrt(sq) + eps; momentum != 0: buf = momentum buf + g / avg,
+ *                      p -= lr buf; else p -= lr g / avg                           (torch.optim.RMSprop, :427-437;
+ *                      state1 = square_avg, state2 = momentum_buffer, NULL allowed without momentum)
+ *   GCMI_RULE_ADAM_L2  g += weight_decay p, then Adam                              (torch.optim.Adam, :231-241;
+ *                      state1 = exp_avg, state2 = exp_avg_sq; weight_decay == 0 IS the adam step above, bit for bit)
+ *   GCMI_RULE_ADAMW    p *= 1 - lr weight_decay, then Adam (no amsgrad)            (torch.optim.AdamW, :360-367)
+ *   GCMI_RULE_LAMB     the Lamb step below only
+ * each in the operation order of torch's single-tensor implementation.  step = 1-based count after this update.
+ * Any n >= 0; 16-byte accesses when every pointer is 16-byte aligned, scalar otherwise; no atomics.          */
+enum {
+  GCMI_RULE_SGD = 0,
+  GCMI_RULE_ADAGRAD = 1,
+  GCMI_RULE_RMSPROP = 2,
+  GCMI_RULE_ADAM_L2 = 3,
+  GCMI_RULE_ADAMW = 4,
+  GCMI_RULE_LAMB = 5
+};
+typedef struct gcmi_opt_desc {
+  int32_t rule;
+  float beta1, beta2, eps, weight_decay, alpha, momentum;
+} gcmi_opt_desc;
+int gcmi_opt_step(const gcmi_opt_desc* desc, float* d_param, const float* d_grad, float* d_state1, float* d_state2,
+                  int64_t n, float lr, int64_t step, void* stream);
+/* LambOptimizer (utils/optimizer_utils.py:91-163 as models/optimizers.py:872-881 configures it: debias=False,
+ * adam=False, clamp_value=10) over arenas of n floats.  d_segments: n_segments pairs (offset, numel) of int64 in
+ * DEVICE memory, one per parameter tensor; floats between segments belong to none and are left alone, and a pair that
+ * does not lie inside [0, n) is skipped.  Two launches: moments + update u = m / (sqrt(v) + eps) + weight_decay p +
+ * per-chunk fp64 sums of p^2 and u^2, then per segment trust = min(||p||, 10) / ||u|| (1 when either norm is 0) and
+ * p -= lr trust u.  The sums are combined in a fixed order (no floating-point atomics): equal inputs, equal bits.
+ * d_norms (may be NULL): n_segments x 3 floats [weight_norm, adam_norm, trust_ratio] of this step.
+ * d_scratch: gcmi_lamb_scratch_floats(n, n_segments) floats (negative: bad arguments), 16-byte aligned.      */
+int64_t gcmi_lamb_scratch_floats(int64_t n, int64_t n_segments);
+int gcmi_lamb_step(const gcmi_opt_desc* desc, float* d_param, const float* d_grad, float* d_m, float* d_v,
+                   float* d_scratch, const int64_t* d_segments, int32_t n_segments, int64_t n, float* d_norms, float lr,
+                   void* stream);
+
 /* ---------------------------------------------------------------- whole-model sequencing
  * _GraphConvTorchModel.forward (models/torch_models/graphconvmodel.py:188-249) and the
  * loss + backward of one fit_generator step (models/torch_models/torch_model.py:436-442)
@@ -677,6 +718,16 @@ int gcmi_small_fit_dp(const gcmi_model_desc* m, float* d_params, float* d_grads,
                       int64_t ws_mols, float lr, float beta1, float beta2, float eps, int64_t first_step,
                       float* d_losses, int64_t* grad_lo, int64_t* grad_hi, gcmi_grad_sync_fn sync, void* sync_ctx,
                       void* stream);
+/* The same loop under any elementwise rule and a learning rate per step: gcmi_small_fit_dp with the four Adam scalars
+ * replaced by the description, d_state1 / d_state2 by the rule's state arenas (gcmi_opt_step; one the rule does not
+ * use may be NULL) and lr by lr_per_step, a HOST array of n_batches values read while the call enqueues.  Step
+ * i runs under lr_per_step[i] as step number first_step + i.  gcmi_small_fit and gcmi_small_fit_dp are this call
+ * with GCMI_RULE_ADAM_L2, weight_decay 0 and a constant array.  GCMI_RULE_LAMB is not an elementwise rule.   */
+int gcmi_small_fit_opt(const gcmi_model_desc* m, float* d_params, float* d_grads, float* d_state1, float* d_state2,
+                       const gcmi_model_io* io, const gcmi_small_batch* batches, int64_t n_batches, int64_t ws_atoms,
+                       int64_t ws_mols, const gcmi_opt_desc* opt, const float* lr_per_step, int64_t first_step,
+                       float* d_losses, int64_t* grad_lo, int64_t* grad_hi, gcmi_grad_sync_fn sync, void* sync_ctx,
+                       void* stream);
 int gcmi_small_predict(const gcmi_model_desc* m, const float* d_params, const gcmi_model_io* io,
                        const gcmi_small_batch* batches, int64_t n_batches, int64_t ws_atoms, int64_t ws_mols,
                        void* stream);
