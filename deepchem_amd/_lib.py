@@ -25,6 +25,9 @@ GCMI_OPT_FUSED_BWD = 3
 GCMI_OPT_FUSED_BWD_LAUNCHES = 4
 GCMI_OPT_READOUT_PIPELINED = 5
 GCMI_OPT_ONE_PIECE_LAUNCHES = 6
+GCMI_METRIC_ROC_AUC, GCMI_METRIC_PRC_AUC = 0, 1
+GCMI_METRIC_MOMENTS, GCMI_METRIC_ACCURACY = 0, 1
+GCMI_METRIC_MOMENT_DOUBLES = 12
 GCMI_WIN_META_INTS = 24
 GCMI_COLLATE_WIN_DESC_INTS = 36
 GCMI_WIN_MAX_SLOTS = 4095
@@ -179,6 +182,8 @@ _SIGNATURES = {
     "gcmi_relu_bwd": [_P, c_int64, _P, c_int64, c_int64, c_int32, _P],
     "gcmi_loss_fwd_bwd": [c_int32, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P],
     "gcmi_softmax": [_P, c_int64, c_int32, _P, _P],
+    "gcmi_metric_rank": [c_int32, _P, c_int64, c_int64, _P, c_int32, _P, c_int64, c_int32, _P, _P, _P, _P],
+    "gcmi_metric_moments": [c_int32, _P, c_int64, c_int64, c_int32, _P, _P, _P, _P, c_int64, c_int32, _P, _P],
     "gcmi_adam_step": [_P, _P, _P, _P, c_int64, c_float, c_float, c_float, c_float, c_int64, _P],
     "gcmi_opt_step": [POINTER(GcmiOptDesc), _P, _P, _P, _P, c_int64, c_float, c_int64, _P],
     "gcmi_lamb_step": [POINTER(GcmiOptDesc), _P, _P, _P, _P, _P, _P, c_int32, c_int64, _P, c_float, _P],
@@ -233,7 +238,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = ["gcmi_version", "gcmi_last_error", "gcmi_model_workspace_floats", "gcmi_small_workspace_floats",
-           "gcmi_task_head_scratch_floats", "gcmi_lamb_scratch_floats",
+           "gcmi_task_head_scratch_floats", "gcmi_lamb_scratch_floats", "gcmi_metrics_workspace_bytes",
            "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout"] + sorted(_SIGNATURES)
 
 _lib = None
@@ -278,6 +283,7 @@ def load():
         "gcmi_collate_plan_words": (c_int64, [c_int64]),
         "gcmi_task_head_scratch_floats": (c_int64, []),
         "gcmi_lamb_scratch_floats": (c_int64, [c_int64, c_int64]),
+        "gcmi_metrics_workspace_bytes": (c_int64, [c_int64, c_int32]),
     }
     for name, (restype, argtypes) in special.items():
         if host_only and not hasattr(lib, name):

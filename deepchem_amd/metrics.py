@@ -1,5 +1,19 @@
-"""The two metric helpers the GraphConv path touches."""
+"""``dc.metrics``: ``Metric`` and the score functions the MolNet scripts use (deepchem/metrics/metric.py,
+score_function.py), as plain NumPy float64 host functions -- nothing here imports sklearn or scipy except the
+older ``roc_auc_per_task`` helper.  ``Model.evaluate`` scores ``Metric`` objects that wrap one of the nine
+functions below on the GPU (``deepchem_amd/csrc/metrics.hip``) when it can; these host functions are what it is
+checked against and what it falls back to.
+
+A behaviour of the reference to keep in mind: ``Metric.compute_metric`` does NOT drop zero-weight rows.  ``w``
+reaches the score function only with ``use_sample_weights=True`` (as ``sample_weight``); by default every row
+counts, missing labels stored as ``y = 0, w = 0`` included.  (``roc_auc_per_task`` below drops them.)
+"""
+import logging
+from typing import Any, Callable, Optional
+
 import numpy as np
+
+logger = logging.getLogger(__name__)
 
 
 def to_one_hot(y: np.ndarray, n_classes: int = 2) -> np.ndarray:
@@ -17,6 +31,11 @@ def to_one_hot(y: np.ndarray, n_classes: int = 2) -> np.ndarray:
     return y_hot
 
 
+def from_one_hot(y: np.ndarray, axis: int = 1) -> np.ndarray:
+    """(N, n_classes) one-hot -> (N,) class indices (metric.py:404-419)."""
+    return np.argmax(y, axis=axis)
+
+
 def roc_auc_per_task(y_true: np.ndarray, y_prob: np.ndarray, w: np.ndarray = None):
     """Per-task ROC-AUC as deepchem.metrics.Metric(roc_auc_score) computes it
     (metrics/metric.py:568-665: samples with zero weight are dropped; sklearn's
@@ -31,3 +50,400 @@ def roc_auc_per_task(y_true: np.ndarray, y_prob: np.ndarray, w: np.ndarray = Non
         yt, yp = y_true[keep, t], y_prob[keep, t]
         out.append(float("nan") if len(np.unique(yt)) < 2 else roc_auc_score(yt, yp))
     return np.array(out)
+
+
+# ---------------------------------------------------------------------------------------------- score functions
+def _checked_weights(sample_weight, n: int) -> Optional[np.ndarray]:
+    if sample_weight is None:
+        return None
+    w = np.asarray(sample_weight, np.float64).reshape(-1)
+    if w.shape[0] != n:
+        raise ValueError("sample_weight has %d entries for %d samples" % (w.shape[0], n))
+    return w
+
+
+def _tie_groups(positive: np.ndarray, score: np.ndarray, w: Optional[np.ndarray]):
+    """Cumulative (weighted) positives and negatives at the end of every group of equal scores, groups in
+    descending score order.  Rows without weight are left out, as sklearn's curve code leaves them out."""
+    score = np.asarray(score, np.float64).reshape(-1)
+    if np.isnan(score).any():
+        raise ValueError("Input contains NaN.")
+    if np.isinf(score).any():
+        raise ValueError("Input contains infinity or a value too large for dtype('float64').")
+    if w is not None:
+        keep = w != 0
+        positive, score, w = positive[keep], score[keep], w[keep]
+    order = np.argsort(-score, kind="stable")
+    score, positive = score[order], positive[order]
+    weight = np.ones(score.shape[0]) if w is None else w[order]
+    tails = np.r_[np.nonzero(score[1:] != score[:-1])[0], max(score.shape[0] - 1, 0)][:score.shape[0]]
+    tp = np.cumsum(np.where(positive, weight, 0.0))[tails]
+    fp = np.cumsum(np.where(positive, 0.0, weight))[tails]
+    return tp, fp
+
+
+def _binary_roc_auc(positive: np.ndarray, score: np.ndarray, w: Optional[np.ndarray]) -> float:
+    if positive.all() or not positive.any():
+        raise ValueError("Only one class present in y_true. ROC AUC score is not defined in that case.")
+    tp, fp = _tie_groups(positive, score, w)
+    if tp.shape[0] == 0 or tp[-1] <= 0 or fp[-1] <= 0:
+        return float("nan")
+    tp0 = np.r_[0.0, tp[:-1]]
+    fp0 = np.r_[0.0, fp[:-1]]
+    # every negative of a group is ranked below the positives before the group and level with those inside it
+    return float(np.sum((fp - fp0) * (tp0 + tp)) / (2.0 * tp[-1] * fp[-1]))
+
+
+def roc_auc_score(y_true: np.ndarray, y_score: np.ndarray, sample_weight=None) -> float:
+    """Area under the ROC curve: (2 #{pos > neg} + #{pos = neg}) / (2 P N), with weights the same over weight
+    products.  ``y_true``: binary labels (N,), or an indicator matrix (N, C) scored column by column against
+    ``y_score`` (N, C) and averaged (what the reference's ``Metric`` hands over: one-hot labels and class
+    probabilities).  One class only, or (N,) labels of more than two classes: ValueError."""
+    y_true, y_score = np.asarray(y_true), np.asarray(y_score)
+    w = _checked_weights(sample_weight, y_true.shape[0])
+    if y_true.ndim == 2 and y_true.shape[1] == 1 and y_score.ndim == 1:
+        y_true = y_true[:, 0]
+    if y_true.ndim == 1:
+        classes = np.unique(y_true)
+        if len(classes) > 2 or (y_score.ndim == 2 and y_score.shape[1] > 2):
+            raise ValueError("multi_class must be in ('ovo', 'ovr')")
+        if y_score.ndim != 1:
+            raise ValueError("y_score must be of shape (N,) for binary labels")
+        return _binary_roc_auc(y_true == classes[-1], y_score, w)
+    if y_true.ndim != 2 or y_true.shape != y_score.shape:
+        raise ValueError("y_true and y_score must have the same shape")
+    columns = [_binary_roc_auc(y_true[:, c] == 1, y_score[:, c], w) for c in range(y_true.shape[1])]
+    return float(np.mean(columns))
+
+
+def _binary_prc_auc(positive: np.ndarray, score: np.ndarray, w: Optional[np.ndarray] = None) -> float:
+    """Trapezoids under (recall, precision) over the distinct thresholds in descending order, from the point
+    (recall 0, precision 1); thresholds past full recall add nothing."""
+    tp, fp = _tie_groups(positive, score, w)
+    total = tp + fp
+    with np.errstate(divide="ignore", invalid="ignore"):
+        precision = np.where(total > 0, tp / np.where(total > 0, total, 1.0), 0.0)
+        recall = tp / tp[-1] if tp[-1] > 0 else np.ones_like(tp)
+    precision0 = np.r_[1.0, precision[:-1]]
+    recall0 = np.r_[0.0, recall[:-1]]
+    return float(np.sum((recall - recall0) * (precision + precision0) * 0.5))
+
+
+def prc_auc_score(y: np.ndarray, y_pred: np.ndarray) -> float:
+    """Area under the precision-recall curve of class 1; ``y`` one-hot (N, n_classes), ``y_pred`` class
+    probabilities (N, n_classes) (score_function.py:103-119)."""
+    y, y_pred = np.asarray(y), np.asarray(y_pred)
+    return _binary_prc_auc(y[:, 1] == 1, y_pred[:, 1])
+
+
+def accuracy_score(y_true: np.ndarray, y_pred: np.ndarray, normalize: bool = True, sample_weight=None) -> float:
+    """Fraction (or, without ``normalize``, weighted count) of rows predicted exactly; rows of indicator
+    matrices count when every column agrees."""
+    y_true, y_pred = np.asarray(y_true), np.asarray(y_pred)
+    if y_true.shape != y_pred.shape:
+        raise ValueError("y_true and y_pred must have the same shape")
+    hit = (y_true == y_pred) if y_true.ndim == 1 else np.all(y_true == y_pred, axis=tuple(range(1, y_true.ndim)))
+    w = _checked_weights(sample_weight, y_true.shape[0])
+    if not normalize:
+        return float(hit.sum() if w is None else np.dot(hit, w))
+    return float(np.average(hit, weights=w))
+
+
+def _regression_pair(y_true, y_pred, sample_weight):
+    y_true, y_pred = np.asarray(y_true, np.float64), np.asarray(y_pred, np.float64)
+    if y_true.shape != y_pred.shape:
+        raise ValueError("y_true and y_pred must have the same shape")
+    return y_true, y_pred, _checked_weights(sample_weight, y_true.shape[0])
+
+
+def mean_squared_error(y_true, y_pred, sample_weight=None) -> float:
+    y_true, y_pred, w = _regression_pair(y_true, y_pred, sample_weight)
+    return float(np.mean(np.average((y_true - y_pred) ** 2, axis=0, weights=w)))
+
+
+def mean_absolute_error(y_true, y_pred, sample_weight=None) -> float:
+    y_true, y_pred, w = _regression_pair(y_true, y_pred, sample_weight)
+    return float(np.mean(np.average(np.abs(y_true - y_pred), axis=0, weights=w)))
+
+
+def rms_score(y_true, y_pred) -> float:
+    """Root of the mean squared error (score_function.py:122-124)."""
+    return float(np.sqrt(mean_squared_error(y_true, y_pred)))
+
+
+def mae_score(y_true, y_pred) -> float:
+    """Mean absolute error (score_function.py:127-129)."""
+    return mean_absolute_error(y_true, y_pred)
+
+
+def r2_score(y_true, y_pred, sample_weight=None) -> float:
+    """Coefficient of determination 1 - sum w (y - p)^2 / sum w (y - mean_w y)^2.  A constant ``y_true`` gives 1
+    for a perfect prediction and 0 otherwise; fewer than two samples give nan."""
+    y_true, y_pred, w = _regression_pair(y_true, y_pred, sample_weight)
+    if y_true.shape[0] < 2:
+        return float("nan")
+    weight = np.ones(y_true.shape[0]) if w is None else w
+    weight = weight.reshape((-1,) + (1,) * (y_true.ndim - 1))
+    residual = np.sum(weight * (y_true - y_pred) ** 2, axis=0)
+    spread = np.sum(weight * (y_true - np.average(y_true, axis=0, weights=w)) ** 2, axis=0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        score = np.where(spread != 0, 1.0 - residual / np.where(spread != 0, spread, 1.0),
+                         np.where(residual == 0, 1.0, 0.0))
+    return float(np.mean(score))
+
+
+def pearson_r2_score(y: np.ndarray, y_pred: np.ndarray) -> float:
+    """Square of the Pearson correlation coefficient (score_function.py:43-58); nan when either side is constant."""
+    y, y_pred = np.asarray(y, np.float64), np.asarray(y_pred, np.float64)
+    if y.shape != y_pred.shape or y.ndim != 1:
+        raise ValueError("x and y must be vectors of the same length.")
+    if y.shape[0] < 2:
+        raise ValueError("x and y must have length at least 2.")
+    a, b = y - y.mean(), y_pred - y_pred.mean()
+    na, nb = np.linalg.norm(a), np.linalg.norm(b)
+    if na == 0 or nb == 0:
+        return float("nan")
+    r = float(np.clip(np.dot(a / na, b / nb), -1.0, 1.0))
+    return r * r
+
+
+# the functions Model.evaluate can score where the predictions sit (deepchem_amd/csrc/metrics.hip)
+_CLASSIFICATION_DEFAULTS = {
+    "threshold": ("matthews_corrcoef", "cohen_kappa_score", "kappa_score", "balanced_accuracy_score", "recall_score",
+                  "jaccard_score", "jaccard_index", "pixel_error", "f1_score"),
+    "threshold-one-hot": ("accuracy_score", "precision_score", "bedroc_score"),
+    "direct": ("roc_auc_score", "prc_auc_score", "precision_recall_curve"),
+}
+_REGRESSION_NAMES = ("pearson_r2_score", "r2_score", "mean_squared_error", "mean_absolute_error", "rms_score",
+                     "mae_score", "pearsonr", "concordance_index")
+
+
+# ---------------------------------------------------------------------------------------------- shapes
+def threshold_predictions(y: np.ndarray, threshold: Optional[float] = None) -> np.ndarray:
+    """(N, n_classes) probabilities -> (N,) class indices: argmax, or for two classes and a given threshold
+    ``p[:, 1] >= threshold`` (metric.py:10-38)."""
+    if not isinstance(y, np.ndarray) or not len(y.shape) == 2:
+        raise ValueError("y must be a ndarray of shape (N, n_classes)")
+    if y.shape[1] != 2 or threshold is None:
+        return np.argmax(y, axis=1)
+    return np.where(y[:, 1] >= threshold, np.ones(y.shape[0]), np.zeros(y.shape[0]))
+
+
+def normalize_weight_shape(w: Optional[np.ndarray], n_samples: int, n_tasks: int) -> np.ndarray:
+    """None, a scalar, (N,), (N, 1) or (N, n_tasks) -> (N, n_tasks) (metric.py:41-101)."""
+    if w is None:
+        return np.ones((n_samples, n_tasks))
+    if not isinstance(w, np.ndarray) or len(w.shape) == 0:
+        return w * np.ones((n_samples, n_tasks))
+    if len(w.shape) == 1:
+        if len(w) != n_samples:
+            raise ValueError("Length of w isn't n_samples")
+        return np.tile(w, (n_tasks, 1)).T
+    if len(w.shape) == 2:
+        if w.shape == (n_samples, 1):
+            return np.tile(np.squeeze(w, axis=1), (n_tasks, 1)).T
+        if w.shape != (n_samples, n_tasks):
+            raise ValueError("Shape for w doens't match (n_samples, n_tasks)")
+        return w
+    raise ValueError("w must be of dimension 1, 2, or 3")
+
+
+def _with_task_axis(y: np.ndarray, mode, n_tasks, n_classes) -> np.ndarray:
+    # (N, n_classes) for one classification task: the task axis is missing
+    if mode == "classification" and len(y.shape) == 2 and n_classes == y.shape[1]:
+        if n_tasks != 1 and n_classes != n_tasks:
+            raise ValueError("Shape of input doesn't match expected n_tasks=1")
+        if n_tasks == 1:
+            y = np.expand_dims(y, 1)
+    return y
+
+
+def _one_hot_tasks(y: np.ndarray, n_tasks: int, n_classes: int) -> np.ndarray:
+    return np.concatenate([np.expand_dims(to_one_hot(y[:, t], n_classes=n_classes), 1) for t in range(n_tasks)],
+                          axis=1)
+
+
+def normalize_labels_shape(y: np.ndarray, mode: Optional[str] = None, n_tasks: Optional[int] = None,
+                           n_classes: Optional[int] = None) -> np.ndarray:
+    """Labels -> (N, n_tasks) for regression, one-hot (N, n_tasks, n_classes) for classification
+    (metric.py:104-179)."""
+    if n_tasks is None:
+        raise ValueError("n_tasks must be specified")
+    if mode not in ["classification", "regression"]:
+        raise ValueError("mode must be either classification or regression.")
+    if mode == "classification" and n_classes is None:
+        raise ValueError("n_classes must be specified")
+    if not isinstance(y, np.ndarray):
+        raise ValueError("y must be a np.ndarray")
+    y = _with_task_axis(y, mode, n_tasks, n_classes)
+    if len(y.shape) == 1 and n_tasks != 1:
+        raise ValueError("n_tasks must equal 1 for a 1D set of labels.")
+    if len(y.shape) in (2, 3) and n_tasks != y.shape[1]:
+        raise ValueError("Shape of input doesn't match expected n_tasks=%d" % n_tasks)
+    if len(y.shape) >= 4:
+        raise ValueError("Labels y must be a float scalar or a ndarray of shape `(N,)` or `(N, n_tasks)` or "
+                         "`(N, n_tasks, 1)` for regression problems and of shape `(N,)` or `(N, n_tasks)` or "
+                         "`(N, n_tasks, 1)` for classification problems")
+    if len(y.shape) == 1:
+        y = np.expand_dims(y, 1)
+    elif len(y.shape) == 3:
+        if y.shape[-1] != 1:  # already one-hot
+            return y
+        y = np.squeeze(y, axis=-1)
+    return _one_hot_tasks(y, n_tasks, n_classes) if mode == "classification" else y
+
+
+def normalize_prediction_shape(y: np.ndarray, mode: Optional[str] = None, n_tasks: Optional[int] = None,
+                               n_classes: Optional[int] = None) -> np.ndarray:
+    """Predictions -> (N, n_tasks) for regression, (N, n_tasks, n_classes) for classification; a binary task given
+    as the positive-class probability p becomes [1 - p, p] (metric.py:182-295)."""
+    if n_tasks is None:
+        raise ValueError("n_tasks must be specified")
+    if mode == "classification" and n_classes is None:
+        raise ValueError("n_classes must be specified")
+    if not isinstance(y, np.ndarray):
+        raise ValueError("y must be a np.ndarray")
+    y = _with_task_axis(y, mode, n_tasks, n_classes)
+    if len(y.shape) in (2, 3) and n_tasks != y.shape[1]:
+        raise ValueError("Shape of input doesn't match expected n_tasks=%d" % n_tasks)
+    if len(y.shape) >= 4:
+        raise ValueError("Predictions y must be a float scalar or a ndarray of shape `(N,)` or `(N, n_tasks)` or "
+                         "`(N, n_tasks, 1)` for regression problems and of shape `(N,)` or `(N, n_tasks)` or "
+                         "`(N, n_tasks, n_classes)` for classification problems")
+    if mode == "classification":
+        if len(y.shape) == 3:
+            return y
+        if len(y.shape) == 1:
+            y = y[:, np.newaxis]
+        per_task = []
+        for t in range(n_tasks):
+            y_task = y[:, t]
+            if len(np.unique(y_task)) > n_classes:  # continuous: probabilities of the positive class
+                if n_classes > 2:
+                    raise ValueError("Cannot handle continuous probabilities for multiclass problems."
+                                     "Need a per-class probability")
+                per_task.append(np.expand_dims(np.array([1 - y_task, y_task]).T, 1))
+            else:
+                per_task.append(np.expand_dims(to_one_hot(y_task, n_classes=n_classes), 1))
+        return np.concatenate(per_task, axis=1)
+    if mode == "regression":
+        if len(y.shape) == 1:
+            return np.expand_dims(y, 1)
+        if len(y.shape) == 3:
+            if y.shape[-1] != 1:
+                raise ValueError("y must be a float scalar or a ndarray of shape `(N,)` or `(N, n_tasks)` or "
+                                 "`(N, n_tasks, 1)` for regression problems.")
+            return np.squeeze(y, axis=-1)
+        return y
+    raise ValueError("mode must be either classification or regression.")
+
+
+def handle_classification_mode(y: np.ndarray, classification_handling_mode: Optional[str],
+                               threshold_value: Optional[float] = None) -> np.ndarray:
+    """(N, n_tasks, n_classes) as it is ("direct"), as class indices (N, n_tasks) ("threshold"), or as the one-hot
+    form of those ("threshold-one-hot") (metric.py:298-368)."""
+    if len(y.shape) != 3:
+        raise ValueError("y must be of shape (N, n_tasks, n_classes)")
+    n_tasks, n_classes = y.shape[1], y.shape[2]
+    if classification_handling_mode == "direct":
+        return y
+    if classification_handling_mode == "threshold":
+        return np.concatenate([np.expand_dims(threshold_predictions(y[:, t, :], threshold_value), 1)
+                               for t in range(n_tasks)], axis=1)
+    if classification_handling_mode == "threshold-one-hot":
+        return np.concatenate(
+            [np.expand_dims(to_one_hot(threshold_predictions(y[:, t, :], threshold_value), n_classes=n_classes), 1)
+             for t in range(n_tasks)], axis=1)
+    raise ValueError("classification_handling_mode must be one of direct, threshold, threshold-one-hot")
+
+
+# ---------------------------------------------------------------------------------------------- Metric
+class Metric(object):
+    """A score function with its multitask handling (metric.py:422-727): the mode ("classification" /
+    "regression") and how class probabilities reach the function are inferred from the function's name unless
+    given, every task is scored on its own and ``task_averager`` (default ``np.mean``) combines the tasks."""
+
+    def __init__(self, metric: Callable[..., float], task_averager: Optional[Callable[..., Any]] = None,
+                 name: Optional[str] = None, threshold: Optional[float] = None, mode: Optional[str] = None,
+                 n_tasks: Optional[int] = None, classification_handling_mode: Optional[str] = None,
+                 threshold_value: Optional[float] = None):
+        if threshold is not None:
+            logger.warning("threshold is deprecated and will be removed in a future version of DeepChem."
+                           "Set threshold in compute_metric instead.")
+        self.metric = metric
+        self.task_averager = np.mean if task_averager is None else task_averager
+        if name is not None:
+            self.name = name
+        elif not hasattr(metric, '__name__'):
+            self.name = "unknown metric"
+        elif task_averager is None:
+            self.name = metric.__name__
+        else:
+            self.name = task_averager.__name__ + "-" + metric.__name__
+        fn_name = metric.__name__
+        if mode is None:
+            if any(fn_name in names for names in _CLASSIFICATION_DEFAULTS.values()):
+                mode = "classification"
+            elif fn_name in _REGRESSION_NAMES:
+                mode = "regression"
+            else:
+                raise ValueError(
+                    "Please specify the mode of this metric. mode must be 'regression' or 'classification'")
+        if mode == "classification":
+            if classification_handling_mode is None:
+                for handling, names in _CLASSIFICATION_DEFAULTS.items():
+                    if fn_name in names:
+                        classification_handling_mode = handling
+            if classification_handling_mode not in ["direct", "threshold", "threshold-one-hot"]:
+                raise ValueError(
+                    "classification_handling_mode must be one of 'direct', 'threshold', 'threshold_one_hot'")
+        self.mode = mode
+        self.n_tasks = n_tasks
+        self.classification_handling_mode = classification_handling_mode
+        self.threshold_value = threshold_value
+
+    def compute_metric(self, y_true, y_pred, w=None, n_tasks: Optional[int] = None, n_classes: int = 2,
+                       per_task_metrics: bool = False, use_sample_weights: bool = False, **kwargs) -> Any:
+        """The averaged score, or ``(average, per-task scores)`` with ``per_task_metrics``; for one task the
+        per-task part is the bare value.  No row is dropped: ``w`` is used only with ``use_sample_weights``."""
+        y_true_arr, y_pred_arr = np.asarray(y_true), np.asarray(y_pred)
+        if n_tasks is None:
+            if self.n_tasks is None:
+                n_tasks = 1 if len(y_true_arr.shape) == 1 else y_true_arr.shape[1]
+            else:
+                n_tasks = self.n_tasks
+        assert isinstance(n_tasks, int)
+        y_true_arr = normalize_labels_shape(y_true_arr, mode=self.mode, n_tasks=n_tasks, n_classes=n_classes)
+        y_pred_arr = normalize_prediction_shape(y_pred_arr, mode=self.mode, n_tasks=n_tasks, n_classes=n_classes)
+        if self.mode == "classification":
+            y_true_arr = handle_classification_mode(y_true_arr, self.classification_handling_mode,
+                                                    self.threshold_value)
+            y_pred_arr = handle_classification_mode(y_pred_arr, self.classification_handling_mode,
+                                                    self.threshold_value)
+        w = normalize_weight_shape(None if w is None else np.asarray(w), y_true_arr.shape[0], n_tasks)
+        computed = [self.compute_singletask_metric(y_true_arr[:, t], y_pred_arr[:, t], w[:, t],
+                                                   use_sample_weights=use_sample_weights, **kwargs)
+                    for t in range(n_tasks)]
+        return self._combine(computed, n_tasks, per_task_metrics)
+
+    def _combine(self, computed, n_tasks: int, per_task_metrics: bool):
+        logger.info("computed_metrics: %s" % str(computed))
+        if n_tasks == 1:
+            computed = computed[0]
+        if not per_task_metrics:
+            return self.task_averager(computed)
+        return self.task_averager(computed), computed
+
+    def compute_singletask_metric(self, y_true, y_pred, w=None, n_samples: Optional[int] = None,
+                                  use_sample_weights: bool = False, **kwargs) -> float:
+        if n_samples is not None:
+            logger.warning("n_samples is a deprecated argument which is ignored.")
+        y_true_arr, y_pred_arr = np.asarray(y_true), np.asarray(y_pred)
+        if self.mode == "regression":
+            if len(y_true_arr.shape) != 1 or len(y_pred_arr.shape) != 1 or y_true_arr.shape != y_pred_arr.shape:
+                raise ValueError("For regression metrics, y_true and y_pred must both be of shape (N,)")
+        elif self.mode != "classification":
+            raise ValueError("Only classification and regression are supported for metrics calculations.")
+        if use_sample_weights:
+            return self.metric(y_true_arr, y_pred_arr, sample_weight=w, **kwargs)
+        return self.metric(y_true_arr, y_pred_arr, **kwargs)

@@ -489,20 +489,28 @@ class GraphConvModel(TorchModel):
         engine: the whole loop of fit_generator runs inside libgcmi.so, ``small_chunk_batches`` optimizer steps
         per call (same batches, same order, same losses, logging windows and checkpoint steps)."""
         done = None
+        from collections.abc import Sequence as SequenceCollection
+        from deepchem_amd.models.callbacks import ValidationCallback
+        # callbacks that say at which steps they need the model (ValidationCallback.interval) run on the engine too:
+        # its chunks end at those steps.  Any other callback wants every step: the per-batch path.
+        stepped = [] if not callbacks else list(callbacks) if isinstance(callbacks, SequenceCollection) else [callbacks]
+        if not all(type(cb) is ValidationCallback and isinstance(cb.interval, int) and cb.interval > 0
+                   for cb in stepped):
+            stepped = None
         # (data parallel: the engine takes a gradient exchange that works on the flat arena, deepchem_amd.dist)
-        plain = (variables is None and loss is None and not callbacks and self.regularization_loss is None
+        plain = (variables is None and loss is None and stepped is not None and self.regularization_loss is None
                  and (self._grad_sync is None or hasattr(self._grad_sync, "reduce_flat"))
                  # synchronised BatchNorm (dist.shard_model): the per-batch step; the engine's statistics are per rank
                  and getattr(self, "_stat_sync", None) is None)
         if plain:
             done = self._fit_small(dataset, nb_epoch, max_checkpoints_to_keep, checkpoint_interval, deterministic,
-                                   restore, all_losses)
+                                   restore, all_losses, stepped)
         if done is not None:
             return done
         return super(GraphConvModel, self).fit(dataset, nb_epoch, max_checkpoints_to_keep, checkpoint_interval,
                                                deterministic, restore, variables, loss, callbacks, all_losses)
 
-    def _fit_small(self, dataset, nb_epoch, max_keep, interval, deterministic, restore, all_losses):
+    def _fit_small(self, dataset, nb_epoch, max_keep, interval, deterministic, restore, all_losses, callbacks=()):
         from deepchem_amd.models.optimizers import FlatOptimizer
         from deepchem_amd.models.torch_models.torch_model import _LossWindow, _StandardLoss, logger
         from deepchem_amd.small import SMALL_MAX_ATOMS, ChunkCollator, HeldChunks
@@ -560,8 +568,11 @@ class GraphConvModel(TorchModel):
         from deepchem_amd.small import chunks_ahead
         step0 = self._global_step
 
-        def cut_after(k):  # the optimizer step that a checkpoint follows ends its chunk
-            return interval > 0 and (step0 + k) % interval == interval - 1
+        def checkpoint_at(step):
+            return interval > 0 and step % interval == interval - 1
+
+        def cut_after(k):  # the optimizer step that a checkpoint or a callback follows ends its chunk
+            return checkpoint_at(step0 + k) or any((step0 + k) % cb.interval == 0 for cb in callbacks)
 
         def checked(batches):
             for idx, n_real in batches:
@@ -569,8 +580,7 @@ class GraphConvModel(TorchModel):
                     raise ValueError("the small-batch engine needs padded batches")
                 yield idx, n_real
 
-        for host_chunk, at_checkpoint in chunks_ahead(collator, checked(index_batches), self.small_chunk_batches,
-                                                      cut_after):
+        for host_chunk, at_cut in chunks_ahead(collator, checked(index_batches), self.small_chunk_batches, cut_after):
             ch = collator.to_device(host_chunk)
             y_t = y_dev.index_select(0, ch.sel_dev)
             w_t = w_dev.index_select(0, ch.sel_dev)
@@ -584,8 +594,21 @@ class GraphConvModel(TorchModel):
             pending.append((self._global_step + 1, losses))
             self._global_step += ch.n_batches
             fold(False)
-            if at_checkpoint:
+            if at_cut and checkpoint_at(self._global_step):
                 self.save_checkpoint(max_keep)
+            due = [cb for cb in callbacks if at_cut and self._global_step % cb.interval == 0]
+            if due:
+                # the callback predicts with this model: through a collator of its own (the worker thread of
+                # chunks_ahead is collating the next chunks with ours), and training mode is set again after it
+                self.__dict__["_small_collator"] = self.__dict__.get("_small_eval_collator")
+                try:
+                    for cb in due:
+                        cb(self, self._global_step)
+                finally:
+                    self.__dict__["_small_eval_collator"] = self.__dict__.get("_small_collator")
+                    self.__dict__["_small_collator"] = collator
+                    self.model.train()
+                    engine.native.refresh()
         fold(True)
         window.close(self._global_step)
         held.drain()
@@ -658,9 +681,9 @@ class GraphConvModel(TorchModel):
             return None
         return _SmallPredictPlan(self, engine, packed, index_batches)
 
-    def _predict(self, generator, transformers, uncertainty, other_output_types):
+    def _fill_sink(self, generator, transformers, uncertainty, other_output_types):
         if not isinstance(generator, _SmallPredictPlan):
-            return super(GraphConvModel, self)._predict(generator, transformers, uncertainty, other_output_types)
+            return super(GraphConvModel, self)._fill_sink(generator, transformers, uncertainty, other_output_types)
         from deepchem_amd.models.torch_models.torch_model import _OutputSink
         _OutputSink.check(self._roles, uncertainty, other_output_types)
         sink = _OutputSink(self._roles, transformers, uncertainty, other_output_types)
@@ -668,7 +691,7 @@ class GraphConvModel(TorchModel):
         self.model.eval()
         for outputs in generator.run():
             sink.push(outputs)
-        return sink.result()
+        return sink
 
     def _batch_generator(self, dataset, epochs: int = 1, mode: str = 'fit',
                          deterministic: bool = True, pad_batches: bool = True):

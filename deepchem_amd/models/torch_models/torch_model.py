@@ -174,6 +174,17 @@ class _OutputSink:
                 col.to_host()
             self._pending = 0
 
+    def device_column(self) -> Optional[torch.Tensor]:
+        """The single requested output of the whole pass as one device tensor (rows joined, nothing copied to the
+        host), for scoring in place (deepchem_amd.models.device_metrics); None when there is more than one column,
+        transformers are pending, or part of the pass has already moved to the host."""
+        if self.transformers or self.uncertainty or not self.columns or len(self.columns) != 1:
+            return None
+        col = self.columns[0]
+        if col.host_parts or not col.device_parts or not all(p.is_cuda for p in col.device_parts):
+            return None
+        return col.device_parts[0] if len(col.device_parts) == 1 else torch.cat(col.device_parts, dim=0)
+
     def result(self):
         joined = [c.joined() for c in (self.columns or [])]
         if self.transformers:  # row-wise maps: undoing them on the joined array equals batch by batch
@@ -357,6 +368,11 @@ class TorchModel(Model):
     # ------------------------------------------------------------------ prediction
     def _predict(self, generator: Iterable[Tuple[Any, Any, Any]], transformers: List,
                  uncertainty: bool, other_output_types):
+        return self._fill_sink(generator, transformers, uncertainty, other_output_types).result()
+
+    def _fill_sink(self, generator: Iterable[Tuple[Any, Any, Any]], transformers: List, uncertainty: bool,
+                   other_output_types) -> _OutputSink:
+        """One prediction pass into an ``_OutputSink`` (its outputs still where the pass left them)."""
         _OutputSink.check(self._roles, uncertainty, other_output_types)
         sink = _OutputSink(self._roles, transformers, uncertainty, other_output_types)
         self._ensure_built()
@@ -365,7 +381,14 @@ class TorchModel(Model):
             for inputs, _labels, _weights in generator:
                 prepared, _, _ = self._prepare_batch((inputs, None, None))
                 sink.push(self._forward_lists(self._unwrap_single(prepared)))
-        return sink.result()
+        return sink
+
+    # evaluate() calls that scored their metrics on the device (tests assert the path through this)
+    device_metric_passes: int = 0
+
+    def _device_scores(self, dataset, metrics, on_labels, use_sample_weights: bool, n_classes: int):
+        from deepchem_amd.models import device_metrics
+        return device_metrics.score(self, dataset, metrics, on_labels, use_sample_weights, n_classes)
 
     def predict_on_generator(self, generator, transformers: List = [], output_types=None):
         return self._predict(generator, transformers, False, output_types)

@@ -482,6 +482,38 @@ int gcmi_loss_fwd_bwd(int32_t kind, const float* d_logits, const float* d_labels
 int gcmi_softmax(const float* d_logits, int64_t n_rows_tasks, int32_t n_classes, float* d_probs,
                  void* stream);
 
+/* ---------------------------------------------------------------- metrics (metrics.hip)
+ * Per-task scores of n rows x n_tasks predictions where they sit in HBM (deepchem/metrics/metric.py:568-727: no row is
+ * dropped; weights enter only as sample weights, NULL = none).  Element (row, task) of a prediction array is at
+ * d_x[row * row_stride + task * elem_stride] (strides in floats: the class-1 probability of an (n, T, 2) tensor has
+ * row_stride 2T, elem_stride 2).  d_labels (fp64) and d_weights (fp32) are contiguous n x n_tasks.
+ *
+ * gcmi_metric_rank: ROC-AUC or the trapezoid area under the precision-recall curve of every task: a stable LSD radix
+ * sort of (score image, row) per task, then one scan over the tie groups.  A row is positive when its label equals
+ * `positive`.  d_out[t]: the score; d_status[t]: 0 ok, or the sum of 1 one class (or no weight on one class), 2 a NaN score,
+ * 4 an infinite score (sklearn rejects those; they are ranked all the same, NaN is not and d_out[t] is then meaningless).  Unweighted ROC-AUC is computed in integers up to one final division.  d_workspace:
+ * gcmi_metrics_workspace_bytes(n, n_tasks) bytes, 16-byte aligned.
+ *
+ * gcmi_metric_moments: GCMI_METRIC_MOMENT_DOUBLES sums per task in one pass, shifted by the first row's values
+ * (y0, p0) so that variances come out of small numbers.  With p = (double)pred * scale[t] + shift[t] (NULL: 1, 0),
+ * dy = y - y0, dp = p - p0:  [0] sum w, [1] sum w dy, [2] sum w dp, [3] sum w dy^2, [4] sum w dp^2, [5] sum w dy dp,
+ * [6] sum w |y - p|, [7] sum w (y - p)^2, [8] y0, [9] p0, [10] (which = ACCURACY only) sum w [argmax_c pred == y],
+ * first maximum on ties, pred then being n_classes consecutive floats per element, [11] 0.                         */
+enum {
+  GCMI_METRIC_ROC_AUC = 0,
+  GCMI_METRIC_PRC_AUC = 1,
+  GCMI_METRIC_MOMENTS = 0,
+  GCMI_METRIC_ACCURACY = 1
+};
+#define GCMI_METRIC_MOMENT_DOUBLES 12
+int64_t gcmi_metrics_workspace_bytes(int64_t n, int32_t n_tasks);
+int gcmi_metric_rank(int32_t which, const float* d_scores, int64_t row_stride, int64_t elem_stride,
+                     const double* d_labels, int32_t positive, const float* d_weights, int64_t n, int32_t n_tasks,
+                     double* d_out, int32_t* d_status, void* d_workspace, void* stream);
+int gcmi_metric_moments(int32_t which, const float* d_pred, int64_t row_stride, int64_t elem_stride, int32_t n_classes,
+                        const double* d_labels, const float* d_weights, const double* d_scale, const double* d_shift,
+                        int64_t n, int32_t n_tasks, double* d_out, void* stream);
+
 /* ---------------------------------------------------------------- optimizer
  * torch.optim.Adam(lr, betas, eps, weight_decay=0) (models/optimizers.py:231-241)
  * on one flat range.  step = 1-based step count after this update.            */
