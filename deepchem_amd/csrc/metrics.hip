@@ -298,6 +298,14 @@ rank_scan_kernel(int which, const uint32_t* __restrict__ keys, const uint32_t* _
 constexpr int kMomBlock = 256;
 constexpr int kMomSums = 9;  // [0..7] of the header's layout and the accuracy sum
 
+// x * scale + shift in two roundings, as the host's z * std + mean.  (__dmul_rn / __dadd_rn are a plain `*` and `+` in
+// HIP's headers and contract into one fma under hipcc's default -ffp-contract=fast: one rounding, an ulp off the host.)
+__device__ __forceinline__ double affine_two_roundings(double x, double scale, double shift) {
+#pragma clang fp contract(off)
+  const double m = x * scale;
+  return m + shift;
+}
+
 __global__ void __launch_bounds__(kMomBlock)
 moments_kernel(int which, const float* __restrict__ pred, int64_t row_stride, int64_t elem_stride, int n_classes,
                const double* __restrict__ labels, const float* __restrict__ weights, const double* __restrict__ scale,
@@ -313,14 +321,14 @@ moments_kernel(int which, const float* __restrict__ pred, int64_t row_stride, in
   if (live_t) {
     const double sc = scale ? scale[t] : 1.0, sh = shift ? shift[t] : 0.0;
     y0 = labels[t];
-    if (which == GCMI_METRIC_MOMENTS) p0 = __dadd_rn(__dmul_rn((double)pred[t * elem_stride], sc), sh);
+    if (which == GCMI_METRIC_MOMENTS) p0 = affine_two_roundings((double)pred[t * elem_stride], sc, sh);
     for (int64_t r = (int64_t)blockIdx.y * rows_per_pass + ty; r < n; r += (int64_t)gridDim.y * rows_per_pass) {
       const double y = labels[r * n_tasks + t];
       const double w = weights ? (double)weights[r * n_tasks + t] : 1.0;
       const float* x = pred + r * row_stride + t * elem_stride;
       acc[0] += w;
       if (which == GCMI_METRIC_MOMENTS) {
-        const double p = __dadd_rn(__dmul_rn((double)x[0], sc), sh);  // two roundings, as the host's z * std + mean
+        const double p = affine_two_roundings((double)x[0], sc, sh);
         const double dy = y - y0, dp = p - p0, e = y - p;
         acc[1] += w * dy;
         acc[2] += w * dp;

@@ -490,8 +490,8 @@ int gcmi_softmax(const float* d_logits, int64_t n_rows_tasks, int32_t n_classes,
  *
  * gcmi_metric_rank: ROC-AUC or the trapezoid area under the precision-recall curve of every task: a stable LSD radix
  * sort of (score image, row) per task, then one scan over the tie groups.  A row is positive when its label equals
- * `positive`.  d_out[t]: the score; d_status[t]: 0 ok, or the sum of 1 one class (or no weight on one class), 2 a NaN score,
- * 4 an infinite score (sklearn rejects those; they are ranked all the same, NaN is not and d_out[t] is then meaningless).  Unweighted ROC-AUC is computed in integers up to one final division.  d_workspace:
+ * `positive`.  d_out[t]: the score; d_status[t]: 0 ok, or the bitwise OR of 1 one class (or no weight on one class), 2 a NaN
+ * score, 4 an infinite score, each flag once however many rows raise it (sklearn rejects those; they are ranked all the same, NaN is not and d_out[t] is then meaningless).  Unweighted ROC-AUC is computed in integers up to one final division.  d_workspace:
  * gcmi_metrics_workspace_bytes(n, n_tasks) bytes, 16-byte aligned.
  *
  * gcmi_metric_moments: GCMI_METRIC_MOMENT_DOUBLES sums per task in one pass, shifted by the first row's values
