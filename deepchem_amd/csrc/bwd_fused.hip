@@ -27,16 +27,6 @@
 namespace gcmi {
 
 constexpr int kFRows = 64;
-constexpr int kFMaxSeg = 16;
-
-struct FusedTable {
-  int32_t n_seg;
-  int32_t seg_begin[kFMaxSeg];
-  int32_t seg_end[kFMaxSeg];
-  int32_t tile_start[kFMaxSeg + 1];
-  int64_t w_off[2][kFMaxSeg];  // weight block of operand o = the same block of the gradient; < 0: term absent
-  int64_t db_off[kFMaxSeg];    // bias-gradient row; < 0: none
-};
 
 struct FusedArgs {
   // sources of G
@@ -89,7 +79,7 @@ struct FusedArgs {
 // justifies dropping a term here.
 template <int NG, int KT, int NOPS, bool TRANS, bool RD, bool DGRAD, bool HB = false, bool GB = false, bool IB = HB>
 __global__ void __launch_bounds__(DGRAD ? 512 : 256) __attribute__((amdgpu_waves_per_eu(2)))
-fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
+fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
   static_assert(!GB || HB, "bf16 gradient streams come with bf16 activations");
   static_assert(IB || !HB, "bf16 activations include the block's inputs");
   static_assert(IB == HB || !DGRAD, "In alone as bf16: the weight-gradient-only form");
@@ -122,9 +112,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
   float* Ins = Gs + kFRows * GP;                                   // [NOPS][64][IP]
   unsigned short* Wimg = reinterpret_cast<unsigned short*>(Ins + NOPS * kFRows * IP);
   float* Outs = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(Wimg) + kWBytes);  // [64][OP] (DGRAD)
-  // the segment table, in LDS (indexing the by-value struct dynamically would go through scratch)
-  __shared__ int t_begin_s[kFMaxSeg], t_end_s[kFMaxSeg], t_tile_s[kFMaxSeg + 1];
-  __shared__ long long t_w_s[2][kFMaxSeg], t_db_s[kFMaxSeg];
+  __shared__ SegTableLds tl;  // (tl.b: the bias-gradient rows)
   __shared__ __attribute__((aligned(16))) float coef_s[3 * NG];  // [A | B | C] of the BatchNorm backward
   __shared__ double stat_s[2][DGRAD ? KP : 1];                   // sum dP | sum dP * P per input column (psums)
 
@@ -140,23 +128,10 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
   // input-gradient wave: row block rb, output tiles [cg * TPW, cg * TPW + TPW)
   const int rb = wq & 1, cg = wq >> 1;
 
-  if (tid <= kFMaxSeg) {
-    t_tile_s[tid] = pick_n(st.tile_start, tid);
-    if (tid < kFMaxSeg) {
-      t_begin_s[tid] = pick_n(st.seg_begin, tid);
-      t_end_s[tid] = pick_n(st.seg_end, tid);
-      t_w_s[0][tid] = pick_n(st.w_off[0], tid);
-      t_w_s[1][tid] = pick_n(st.w_off[1], tid);
-      t_db_s[tid] = pick_n(st.db_off, tid);
-    }
-  }
-  const int n_seg = st.n_seg;
+  tl.fill(st);
 
-  const int b = rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
-  const int t_begin = (int)((int64_t)b * n_tiles / gridDim.x);
-  const int t_end = (int)((int64_t)(b + 1) * n_tiles / gridDim.x);
-  const int my_tiles = t_end - t_begin;  // >= 1: the grid is never larger than the tile count
-  auto tile_at = [&](int i) { return rev ? t_end - 1 - i : t_begin + i; };
+  const TileRange tiles = tile_range<false>(n_tiles, rev);
+  const int my_tiles = tiles.count();
 
   // ---- per-thread constants of the G phase: this thread's 16-byte column piece
   const int gq = tid % QPR;
@@ -167,32 +142,9 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
 
   __syncthreads();
 
-  // Tile -> (segment, first row, rows) by a cursor that moves with the walk: a workgroup's tiles are consecutive, so the
-  // segment changes now and then and a look-up is otherwise two scalar operations.  (The per-tile search it replaces --
-  // a loop of LDS reads over the segment starts, each landing in a vector register -- measured ~1 200 cycles per
-  // look-up in fwd_hd_kernel's phase clocks, csrc/fwd_bf16.hip.)
-  struct Cursor { int seg, t0, t1, r0, r1; } cur;
-  auto cur_load = [&]() {
-    cur.t0 = __builtin_amdgcn_readfirstlane(t_tile_s[cur.seg]);
-    cur.t1 = __builtin_amdgcn_readfirstlane(t_tile_s[cur.seg + 1]);
-    cur.r0 = __builtin_amdgcn_readfirstlane(t_begin_s[cur.seg]);
-    cur.r1 = __builtin_amdgcn_readfirstlane(t_end_s[cur.seg]);
-  };
-  {
-    const int first = tile_at(0);
-    int sg = 0;
-    for (int k = 1; k < n_seg; ++k) sg += first >= t_tile_s[k] ? 1 : 0;
-    cur.seg = __builtin_amdgcn_readfirstlane(sg);
-    cur_load();
-  }
-  auto tile_info = [&](int tile, int& seg, int& row0, int& valid) {
-    while (tile >= cur.t1) { ++cur.seg; cur_load(); }  // (uniform; empty segments are stepped over)
-    while (tile < cur.t0) { --cur.seg; cur_load(); }
-    seg = cur.seg;
-    row0 = cur.r0 + (tile - cur.t0) * kFRows;
-    const int left = cur.r1 - row0;
-    valid = left < kFRows ? left : kFRows;
-  };
+  SegCursor cur;  // tile -> (segment, first row, rows), moving with the walk
+  cur.init(tl, st.n_seg, tiles.at(0));
+  auto tile_info = [&](int tile, int& seg, int& row0, int& valid) { seg = cur.seek<kFRows>(tl, tile, row0, valid); };
 
   // ---- prefetch registers (one tile ahead; the molecule index two tiles ahead): all loads are 16 bytes per lane,
   // unconditional, from clamped addresses; what lies outside the tile is zeroed when it goes to LDS
@@ -267,7 +219,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
     for (int i = 0; i < 16; ++i) accs[t][i] = 0.f;
   float bsum = 0.f;
   auto flush_w = [&](int seg) {
-    const int64_t woff = t_w_s[NOPS == 2 ? wo : 0][seg];
+    const int64_t woff = tl.w[NOPS == 2 ? wo : 0][seg];
     if (woff >= 0) {
       // this lane's first element; its offset is made opaque so that the 32 addresses behind it are formed here
       // and not hoisted out of the tile loop into 64 registers
@@ -293,7 +245,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) accs[t][i] = 0.f;
     if (wo == 0) {
-      const int64_t boff = t_db_s[seg];
+      const int64_t boff = tl.b[seg];
       const float s = bsum + __shfl_xor(bsum, 32);
       if (half == 0 && a.db != nullptr && boff >= 0) atomicAdd(a.db + boff + wj * 32 + l31, s);
     }
@@ -361,9 +313,9 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
 
   // ---- prologue: sources of the first tile, molecule indices of the first two
   int seg, row0, valid;
-  tile_info(tile_at(0), seg, row0, valid);
+  tile_info(tiles.at(0), seg, row0, valid);
   int nseg = seg, nrow0 = row0, nvalid = valid;  // the tile after this one (itself when there is none)
-  if (my_tiles > 1) tile_info(tile_at(1), nseg, nrow0, nvalid);
+  if (my_tiles > 1) tile_info(tiles.at(1), nseg, nrow0, nvalid);
   load_mem(row0, valid, mem1);
   load_src(row0, valid);
   load_mem(nrow0, nvalid, mem1);  // mem1 now describes tile 1: its sources are requested in phase (b) of tile 0
@@ -393,7 +345,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
             ko = r / NG;
             c = r - ko * NG;
           }
-          const int64_t woff = t_w_s[NOPS == 2 ? (o & 1) : 0][seg];
+          const int64_t woff = tl.w[NOPS == 2 ? (o & 1) : 0][seg];
           float v = 0.f;
           if (woff >= 0 && ko < a.k_in)
             v = TRANS ? a.w[woff + (int64_t)c * a.k_in + ko] : a.w[woff + (int64_t)ko * NG + c];
@@ -464,7 +416,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
 
     // ---- phase (b): next tile's sources in flight, products from LDS
     int n2seg = nseg, n2row0 = nrow0, n2valid = nvalid;
-    if (i + 2 < my_tiles) tile_info(tile_at(i + 2), n2seg, n2row0, n2valid);
+    if (i + 2 < my_tiles) tile_info(tiles.at(i + 2), n2seg, n2row0, n2valid);
     load_src(nrow0, nvalid);             // uses mem1 = molecule indices of the next tile (read when the loads issue)
     load_mem(n2row0, n2valid, mem1);     // ... which the indices of the tile after it then replace
     if (is_dgrad) {
@@ -478,7 +430,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
           const int ot = cg * TPW + t;
-          on[t] = t_w_s[NOPS == 2 ? ((ot / KT) & 1) : 0][seg] >= 0;
+          on[t] = tl.w[NOPS == 2 ? ((ot / KT) & 1) : 0][seg] >= 0;
         }
         // units (k-step, output tile), the LDS reads of unit u + 1 issued before the split and the MFMAs of unit u:
         // with two waves per SIMD nobody else hides a read's latency
@@ -537,7 +489,7 @@ fused_bwd_kernel(FusedTable st, int n_tiles, FusedArgs a, int rev) {
         }
       }
     } else {
-      const bool on = t_w_s[NOPS == 2 ? wo : 0][seg] >= 0;
+      const bool on = tl.w[NOPS == 2 ? wo : 0][seg] >= 0;
       const float* irow = Ins + (NOPS == 2 ? wo : 0) * kFRows * IP;
       // Fragments in order: per 16-row step the G columns, then the KT column groups of In.  The eight LDS reads of
       // fragment f + 1 are issued before fragment f is split and multiplied: with two waves per SIMD nobody else
@@ -739,7 +691,7 @@ int get_fused_bwd() { return g_fused_bwd.load(std::memory_order_relaxed); }
 bool fused_bwd_enabled() { return fused_bwd_on() && get_fused_bwd() != 0 && !gemm_exact_mode(); }
 
 template <int NG, int KT, int NOPS, bool TRANS, bool RD, bool DGRAD, bool HB = false, bool GB = false, bool IB = HB>
-static int launch_fused(const FusedTable& st, int n_tiles, const FusedArgs& a, hipStream_t sm) {
+static int launch_fused(const SegTable& st, int n_tiles, const FusedArgs& a, hipStream_t sm) {
   constexpr int KP = KT * 32;
   size_t shmem = sizeof(float) * kFRows * (NG + 4) + sizeof(float) * (size_t)NOPS * kFRows * (KP + 4);
   if (DGRAD)
@@ -772,27 +724,6 @@ static int launch_fused(const FusedTable& st, int n_tiles, const FusedArgs& a, h
   return GCMI_OK;
 }
 
-static int make_table(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w0_off,
-                      const int64_t* w1_off, const int64_t* db_off, FusedTable* st) {
-  memset(st, 0, sizeof(*st));
-  st->n_seg = n_seg;
-  int64_t tiles = 0;
-  for (int s = 0; s < kFMaxSeg; ++s) {
-    st->tile_start[s] = (int32_t)tiles;
-    st->w_off[0][s] = st->w_off[1][s] = st->db_off[s] = -1;
-    if (s < n_seg) {
-      st->seg_begin[s] = seg_begin[s];
-      st->seg_end[s] = seg_end[s];
-      st->w_off[0][s] = w0_off ? w0_off[s] : -1;
-      st->w_off[1][s] = w1_off ? w1_off[s] : -1;
-      st->db_off[s] = db_off ? db_off[s] : -1;
-      tiles += (seg_end[s] - seg_begin[s] + kFRows - 1) / kFRows;
-    }
-  }
-  st->tile_start[kFMaxSeg] = (int32_t)tiles;
-  return (int)tiles;
-}
-
 // GraphConv block: dW_rel += S^T G, dW_self += X^T G, dbsum += colsum G, and (d_ds != nullptr) dS = G W_rel^T,
 // dXs = G W_self^T.  GCMI_ERR_UNSUPPORTED = shape not covered (the caller runs the separate kernels).
 int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_rel,
@@ -801,7 +732,7 @@ int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
                    int64_t ldx, int32_t k_in, const float* d_w, float* d_dw, float* d_dbsum, float* d_ds_out,
                    int64_t ldds, float* d_dxs_out, int64_t lddxs, double* d_psums, hipStream_t sm, int32_t act_bf16,
                    int32_t in_bf16) {
-  if (!fused_bwd_enabled() || n_seg > kFMaxSeg || width != 64) return GCMI_ERR_UNSUPPORTED;
+  if (!fused_bwd_enabled() || n_seg > kMaxProductSeg || width != 64) return GCMI_ERR_UNSUPPORTED;
   // (in_bf16 without act_bf16: d_s and d_x alone point to bf16 rows that hold their values exactly -- the first
   // GraphConv, which needs no input gradient)
   if (in_bf16 && (act_bf16 || d_ds_out != nullptr || k_in <= 64 || k_in > 96)) return GCMI_ERR_UNSUPPORTED;
@@ -816,8 +747,8 @@ int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
   // (act_bf16: d_gc, d_s and d_x point to bf16 rows, their leading dimensions count elements; 8-byte pieces)
   if ((act_bf16 || in_bf16) && (!aligned16(d_s) || lds % 4 || !aligned16(d_x) || ldx % 4)) return GCMI_ERR_UNSUPPORTED;
   const bool dgrad = d_ds_out != nullptr;
-  FusedTable st;
-  const int tiles = make_table(n_seg, seg_begin, seg_end, w_rel, w_self, b_off, &st);
+  SegTable st;
+  const int tiles = (int)fill_seg_table(st, n_seg, seg_begin, seg_end, w_rel, w_self, b_off, kFRows);
   if (tiles == 0) return GCMI_OK;
   FusedArgs a;
   memset(&a, 0, sizeof(a));
@@ -860,8 +791,8 @@ int fused_dense_bwd(int64_t n_rows, const int32_t* d_membership, const float* d_
   if (n_rows * std::max<int64_t>(std::max(ldd, ldg2), std::max(ldp, lddp)) >= (int64_t)1 << 30) return GCMI_ERR_UNSUPPORTED;
   const int32_t zero = 0, nn = (int32_t)n_rows;
   const int64_t off0 = 0;
-  FusedTable st;
-  const int tiles = make_table(1, &zero, &nn, &off0, nullptr, &off0, &st);
+  SegTable st;
+  const int tiles = (int)fill_seg_table(st, 1, &zero, &nn, &off0, nullptr, &off0, kFRows);
   FusedArgs a;
   memset(&a, 0, sizeof(a));
   a.x = d_dense; a.ldx = (int32_t)ldd; a.coef = d_coef;

@@ -163,7 +163,7 @@ inline SegProduct<TA, TO> one_segment(const int32_t* n_rows, const TA* a, int64_
 //   kFwdDense   one operand of 33..64 columns -> 128 columns in nn.Linear layout (the atom-level dense layer)
 // with no activation or ReLU, 16-byte addressable rows (ld a multiple of 4 floats / 8 bf16 elements) and 32-bit
 // element offsets (rows * ld < 2^30).  Anything else: kFwdNone, and the caller answers GCMI_ERR_UNSUPPORTED.
-constexpr int kMaxProductSeg = 16;  // segments of a product (= kMaxSeg, kS3MaxSeg, kWMaxSeg, kHMaxSeg of its kernels' files)
+constexpr int kMaxProductSeg = 16;  // segments of a product: the size of SegTable below, which every product kernel takes
 enum FwdShape { kFwdNone = 0, kFwdConv80, kFwdConv, kFwdDense };
 template <typename TA, typename TO>
 inline FwdShape fwd_shape(const SegProduct<TA, TO>& p) {
@@ -185,28 +185,162 @@ inline FwdShape fwd_shape(const SegProduct<TA, TO>& p) {
   if (rows * std::max(std::max(a1.ld, two ? a2.ld : 0), p.ldo) >= (int64_t)1 << 30) return kFwdNone;
   return shape;
 }
-// The per-segment table a product kernel takes by value (SegTable, SegTable3, FwdTable, FwdHTable: one type per file),
-// for tiles of tile_rows rows: its segments and tile starts, and the offsets into its three arrays (one per operand and
-// the bias; -1 = absent).  Returns the number of tiles.
-template <typename Table, typename TA, typename TO>
-inline int64_t fill_seg_table(Table& st, int64_t* w1_off, int64_t* w2_off, int64_t* bias_off, const SegProduct<TA, TO>& p,
-                              int tile_rows) {
+// ---- The per-segment table every segmented kernel takes BY VALUE (kernarg segment / SGPRs): the forward products of
+// gemm.hip, gemm_split.hip, fwd_fused.hip and fwd_bf16.hip and the one-pass backward of bwd_fused.hip.  For tiles of
+// tile_rows rows: the segments, the first tile of each (tile_start[kMaxProductSeg] = the total), and per segment the
+// offsets into the weight array of either operand and into the bias (-1 = absent; slots past n_seg are zeroed).
+struct SegTable {
+  int32_t n_seg;
+  int32_t seg_begin[kMaxProductSeg];
+  int32_t seg_end[kMaxProductSeg];
+  int32_t tile_start[kMaxProductSeg + 1];
+  int64_t w_off[2][kMaxProductSeg];  // weight block of operand o (backward: the same block of the gradient); < 0: term absent
+  int64_t b_off[kMaxProductSeg];     // bias row (backward: the bias-GRADIENT row); < 0: none
+};
+// Fills it from raw per-segment arrays (a nullptr offset array = that term absent everywhere; no bounds = no rows, for a
+// kernel that reads the offsets only); returns the number of tiles.
+inline int64_t fill_seg_table(SegTable& st, int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end,
+                              const int64_t* w0_off, const int64_t* w1_off, const int64_t* b_off, int tile_rows) {
   memset(&st, 0, sizeof(st));
-  st.n_seg = p.n_seg;
+  st.n_seg = n_seg;
   int64_t tiles = 0;
   for (int s = 0; s < kMaxProductSeg; ++s) {
-    const bool in = s < p.n_seg;
+    const bool in = s < n_seg;
     st.tile_start[s] = (int32_t)tiles;
-    st.seg_begin[s] = in ? p.seg_begin[s] : 0;
-    st.seg_end[s] = in ? p.seg_end[s] : 0;
-    w1_off[s] = (in && p.op[0].a && p.op[0].w_off) ? p.op[0].w_off[s] : -1;
-    w2_off[s] = (in && p.op[1].a && p.op[1].w_off) ? p.op[1].w_off[s] : -1;
-    bias_off[s] = (in && p.bias && p.bias_off) ? p.bias_off[s] : -1;
-    if (in) tiles += (p.seg_end[s] - p.seg_begin[s] + tile_rows - 1) / tile_rows;
+    const bool rows = in && seg_begin && seg_end;
+    st.seg_begin[s] = rows ? seg_begin[s] : 0;
+    st.seg_end[s] = rows ? seg_end[s] : 0;
+    st.w_off[0][s] = (in && w0_off) ? w0_off[s] : -1;
+    st.w_off[1][s] = (in && w1_off) ? w1_off[s] : -1;
+    st.b_off[s] = (in && b_off) ? b_off[s] : -1;
+    if (rows) tiles += (seg_end[s] - seg_begin[s] + tile_rows - 1) / tile_rows;
   }
   st.tile_start[kMaxProductSeg] = (int32_t)tiles;
   return tiles;
 }
+template <typename TA, typename TO>
+inline int64_t fill_seg_table(SegTable& st, const SegProduct<TA, TO>& p, int tile_rows) {
+  return fill_seg_table(st, p.n_seg, p.seg_begin, p.seg_end, p.op[0].a ? p.op[0].w_off : nullptr,
+                        p.op[1].a ? p.op[1].w_off : nullptr, p.bias ? p.bias_off : nullptr, tile_rows);
+}
+
+// row slabs of the weight-gradient kernels (gemm.hip, gemm_split.hip): slabs instead of tiles, other offsets
+constexpr int kMaxSegW = 16;
+struct SlabTable {
+  int32_t n_seg;
+  int32_t slab_rows;
+  int32_t seg_begin[kMaxSegW];
+  int32_t seg_end[kMaxSegW];
+  int32_t slab_start[kMaxSegW + 1];
+  int64_t dw_off[kMaxSegW];
+  int64_t db_off[kMaxSegW];
+};
+
+// ---- device side of the two tables
+// Entry s of a by-value table array, picked with selects (a dynamic index into a kernarg struct would go through
+// scratch).  The pointer form looks at the first N entries only.
+template <int N, typename T>
+__device__ __forceinline__ T pick_n(const T* a, int s) {
+  T v = a[0];
+#pragma unroll
+  for (int k = 1; k < N; ++k) v = (s == k) ? a[k] : v;
+  return v;
+}
+template <typename T, int N>
+__device__ __forceinline__ T pick_n(const T (&a)[N], int s) {
+  return pick_n<N>(&a[0], s);
+}
+// The first tile / slab of segment s.  Over the first 16 entries on purpose: s < 16, the 17th entry is the total, and the
+// array form of pick_n would add a select per use to every one-tile kernel.
+__device__ __forceinline__ int first_tile(const SegTable& st, int s) { return pick_n<kMaxProductSeg>(st.tile_start, s); }
+__device__ __forceinline__ int first_slab(const SlabTable& st, int s) { return pick_n<kMaxSegW>(st.slab_start, s); }
+// the segment of tile b / of slab b: the number of segment starts (s >= 1) that are <= b
+__device__ __forceinline__ int seg_of_tile(const SegTable& st, int b) {
+  int s = 0;
+#pragma unroll
+  for (int k = 1; k < kMaxProductSeg; ++k) s += (k < st.n_seg && b >= st.tile_start[k]) ? 1 : 0;
+  return s;
+}
+__device__ __forceinline__ int seg_of_slab(const SlabTable& st, int b) {
+  int s = 0;
+#pragma unroll
+  for (int q = 1; q < kMaxSegW; ++q) s += (q < st.n_seg && b >= st.slab_start[q]) ? 1 : 0;
+  return s;
+}
+
+// ---- The tile walk of the persistent kernels (fwd_fused_kernel, fwd_reg_kernel, fwd_hd_kernel, fused_bwd_kernel): a
+// workgroup copies the table to LDS once, takes a contiguous range of the tiles and walks it, forwards or (rev)
+// backwards, with a cursor.
+// The table in LDS, where a dynamic index costs a read: filled by the first kMaxProductSeg + 1 threads, valid after
+// the caller's next barrier.
+struct SegTableLds {
+  int begin[kMaxProductSeg], end[kMaxProductSeg], tile[kMaxProductSeg + 1];
+  long long w[2][kMaxProductSeg], b[kMaxProductSeg];
+  __device__ __forceinline__ void fill(const SegTable& st) {
+    const int tid = threadIdx.x;
+    if (tid <= kMaxProductSeg) {
+      tile[tid] = pick_n(st.tile_start, tid);
+      if (tid < kMaxProductSeg) {
+        begin[tid] = pick_n(st.seg_begin, tid);
+        end[tid] = pick_n(st.seg_end, tid);
+        w[0][tid] = pick_n(st.w_off[0], tid);
+        w[1][tid] = pick_n(st.w_off[1], tid);
+        b[tid] = pick_n(st.b_off, tid);
+      }
+    }
+  }
+};
+// Tiles [t_begin, t_end) of this workgroup, an even share of n_tiles (>= 1 tile: the grids are never larger than the
+// tile count); at(i) = the i-th tile it visits.  rev: last-written rows first on alternate launches, and the
+// workgroups in reverse order too.  UNIFORM says that the bounds are wave-uniform (their 64-bit division runs on the
+// vector unit): fwd_reg_kernel and fwd_hd_kernel do, fwd_fused_kernel and fused_bwd_kernel leave them as computed.
+struct TileRange {
+  int t_begin, t_end, rev;
+  __device__ __forceinline__ int count() const { return t_end - t_begin; }
+  __device__ __forceinline__ int at(int i) const { return rev ? t_end - 1 - i : t_begin + i; }
+};
+template <bool UNIFORM>
+__device__ __forceinline__ TileRange tile_range(int n_tiles, int rev) {
+  const int b = rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
+  int t_begin = (int)((int64_t)b * n_tiles / gridDim.x);
+  int t_end = (int)((int64_t)(b + 1) * n_tiles / gridDim.x);
+  if constexpr (UNIFORM) {
+    t_begin = __builtin_amdgcn_readfirstlane(t_begin);
+    t_end = __builtin_amdgcn_readfirstlane(t_end);
+  }
+  return {t_begin, t_end, rev};
+}
+// Tile -> (segment, first row, rows) by a cursor that moves with the walk: a workgroup's tiles are consecutive, so the
+// segment changes now and then and a look-up is otherwise two scalar operations.  (The per-tile search it replaces --
+// a loop of LDS reads over the segment starts, each landing in a vector register -- measured ~1 200 cycles per
+// look-up in fwd_hd_kernel's phase clocks, two look-ups per tile: a third of its tile loop.)  A kernel may keep several
+// (fwd_hd_kernel: one for the tiles it requests, one for the tile it multiplies).
+struct SegCursor {
+  int seg, t0, t1, r0, r1;  // the segment, its tiles [t0, t1) and rows [r0, r1): all wave-uniform
+  __device__ __forceinline__ void load(const SegTableLds& tl) {
+    t0 = __builtin_amdgcn_readfirstlane(tl.tile[seg]);
+    t1 = __builtin_amdgcn_readfirstlane(tl.tile[seg + 1]);
+    r0 = __builtin_amdgcn_readfirstlane(tl.begin[seg]);
+    r1 = __builtin_amdgcn_readfirstlane(tl.end[seg]);
+  }
+  // the one search, for the first tile of the walk
+  __device__ __forceinline__ void init(const SegTableLds& tl, int n_seg, int tile) {
+    int sg = 0;
+    for (int k = 1; k < n_seg; ++k) sg += tile >= tl.tile[k] ? 1 : 0;
+    seg = __builtin_amdgcn_readfirstlane(sg);
+    load(tl);
+  }
+  // moves to `tile` (either direction); returns its segment, and its first row and row count (<= ROWS) in row0, valid
+  template <int ROWS>
+  __device__ __forceinline__ int seek(const SegTableLds& tl, int tile, int& row0, int& valid) {
+    while (tile >= t1) { ++seg; load(tl); }  // (uniform; empty segments are stepped over)
+    while (tile < t0) { --seg; load(tl); }
+    row0 = r0 + (tile - t0) * ROWS;
+    const int left = r1 - row0;
+    valid = left < ROWS ? left : ROWS;
+    return seg;
+  }
+};
 
 // ---- bf16 activation storage (gcmi_model_desc.storage == 1): raw 16-bit patterns, leading dimensions in elements
 bool win_usable_h(const gcmi_graph* g, int n_feat);
@@ -237,17 +371,6 @@ constexpr int64_t kFwdHWimgFloats = 16 * 20 * 3 * 256;  // scratch of fwd_h_gemm
 
 bool gemm_exact_mode();  // gcmi_set_option(GCMI_OPT_GEMM_EXACT)
 
-// row slabs of the weight-gradient kernels (gemm.hip, gemm_split.hip)
-constexpr int kMaxSegW = 16;
-struct SlabTable {
-  int32_t n_seg;
-  int32_t slab_rows;
-  int32_t seg_begin[kMaxSegW];
-  int32_t seg_end[kMaxSegW];
-  int32_t slab_start[kMaxSegW + 1];
-  int64_t dw_off[kMaxSegW];
-  int64_t db_off[kMaxSegW];
-};
 int launch_wgrad3(const SlabTable& st, int slabs, const float* d_a, int64_t lda, int k, const float* d_g, int64_t ldg,
                   int n, float* d_dw, float* d_dbias, int trans_w, hipStream_t sm);
 

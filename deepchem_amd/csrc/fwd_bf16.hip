@@ -24,17 +24,6 @@
 
 namespace gcmi {
 
-constexpr int kHMaxSeg = kMaxProductSeg;
-
-struct FwdHTable {
-  int32_t n_seg;
-  int32_t seg_begin[kHMaxSeg];
-  int32_t seg_end[kHMaxSeg];
-  int32_t tile_start[kHMaxSeg + 1];
-  int64_t w_off[2][kHMaxSeg];  // weight block of operand o; < 0: term absent
-  int64_t b_off[kHMaxSeg];     // bias row; < 0: none
-};
-
 struct FwdHArgs {
   const bf16_t* in[2];
   int32_t ldin[2];       // elements, multiples of 8; columns [k_in, KO) of the rows are zero (or absent: ld < KO)
@@ -60,7 +49,7 @@ struct FwdHArgs {
 // -- so that a reload is NKS * 3 coalesced 1 KiB wave loads with one wait behind them.
 template <bool TRANS>
 __global__ void __launch_bounds__(256)
-wprep_kernel(FwdHTable st, const float* __restrict__ w0, const float* __restrict__ w1, int k_in, int KO, int NOPS,
+wprep_kernel(SegTable st, const float* __restrict__ w0, const float* __restrict__ w1, int k_in, int KO, int NOPS,
              int NOUT, u32x4* __restrict__ wimg) {
   const int NKS = NOPS * KO / 16, TW = NOUT / 32;
   const int total = st.n_seg * TW * NKS * 64;
@@ -124,7 +113,7 @@ __device__ u32x4 g_fwdh_dump[512 * 256];  // where the rows beyond a ragged tile
 // stays fp32 -- rows of 16-byte pieces of FOUR columns, the BatchNorm sums taken from the unrounded values.
 template <int NOPS, int KO, int NOUT, bool TRANS, bool F32OUT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
-fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
+fwd_hd_kernel(SegTable st, int n_tiles, FwdHArgs a, int rev) {
   constexpr int NT = 256, ROWS = 64, D = 2, NBUF = D + 1, NPW = 3;
   constexpr int NC = NOPS * KO;
   constexpr int NKS = NC / 16;
@@ -144,8 +133,7 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   unsigned char* As = lds_raw;                                         // [NBUF][ROWS][RQ] chunks
   unsigned char* Outs = lds_raw + (size_t)NBUF * TILE_BYTES;           // [ROWS][OPB]
-  __shared__ int t_begin_s[kHMaxSeg], t_end_s[kHMaxSeg], t_tile_s[kHMaxSeg + 1];
-  __shared__ long long t_w_s[2][kHMaxSeg], t_b_s[kHMaxSeg];
+  __shared__ SegTableLds tl;
   __shared__ __attribute__((aligned(16))) float bias_s[NOUT];
   __shared__ double stat_s[2][NOUT];
 
@@ -157,51 +145,14 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
   const int rb = wave & 1, twb = wave >> 1;
   auto swz = [](int r) { return RQ == 16 ? (r & 15) : RQ == 20 ? ((r >> 2) & 3) : ((r >> 1) & 7); };
 
-  if (tid <= kHMaxSeg) {
-    t_tile_s[tid] = pick_n(st.tile_start, tid);
-    if (tid < kHMaxSeg) {
-      t_begin_s[tid] = pick_n(st.seg_begin, tid);
-      t_end_s[tid] = pick_n(st.seg_end, tid);
-      t_w_s[0][tid] = pick_n(st.w_off[0], tid);
-      t_w_s[1][tid] = pick_n(st.w_off[1], tid);
-      t_b_s[tid] = pick_n(st.b_off, tid);
-    }
-  }
+  tl.fill(st);
   for (int c = tid; c < 2 * NOUT; c += NT) stat_s[c / NOUT][c % NOUT] = 0.0;
-  const int n_seg = st.n_seg;
   __syncthreads();
 
-  const int b = rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
-  const int t_begin = __builtin_amdgcn_readfirstlane((int)((int64_t)b * n_tiles / gridDim.x));
-  const int t_end = __builtin_amdgcn_readfirstlane((int)((int64_t)(b + 1) * n_tiles / gridDim.x));
-  const int my_tiles = t_end - t_begin;  // >= 1
-  auto tile_at = [&](int i) { return rev ? t_end - 1 - i : t_begin + i; };
-  // Tile -> (segment, first row, rows), kept INCREMENTALLY: a workgroup walks consecutive tiles, so a cursor moves to the
-  // next segment now and then and is otherwise two scalar operations.  (Looking the segment up per tile -- a loop of
-  // LDS reads over the segment starts, each landing in a vector register -- measured 1 200 cycles per look-up, two
-  // look-ups per tile: a third of the tile loop.)
-  struct Cursor { int seg, t0, t1, r0, r1; };
-  auto cur_load = [&](Cursor& c) {
-    c.t0 = __builtin_amdgcn_readfirstlane(t_tile_s[c.seg]);
-    c.t1 = __builtin_amdgcn_readfirstlane(t_tile_s[c.seg + 1]);
-    c.r0 = __builtin_amdgcn_readfirstlane(t_begin_s[c.seg]);
-    c.r1 = __builtin_amdgcn_readfirstlane(t_end_s[c.seg]);
-  };
-  auto cur_init = [&](Cursor& c, int tile) {
-    int sg = 0;
-    for (int k = 1; k < n_seg; ++k) sg += tile >= t_tile_s[k] ? 1 : 0;
-    c.seg = __builtin_amdgcn_readfirstlane(sg);
-    cur_load(c);
-  };
-  auto cur_seek = [&](Cursor& c, int tile, int& row0, int& valid) {
-    while (tile >= c.t1) { ++c.seg; cur_load(c); }  // (uniform; empty segments are stepped over)
-    while (tile < c.t0) { --c.seg; cur_load(c); }
-    row0 = c.r0 + (tile - c.t0) * ROWS;
-    const int left = c.r1 - row0;
-    valid = left < ROWS ? left : ROWS;
-  };
-  Cursor cur_issue, cur_run;
-  cur_init(cur_issue, tile_at(0));
+  const TileRange tiles = tile_range<true>(n_tiles, rev);
+  const int my_tiles = tiles.count();
+  SegCursor cur_issue, cur_run;  // of the tile being requested, D tiles ahead, and of the tile being multiplied
+  cur_issue.init(tl, st.n_seg, tiles.at(0));
   cur_run = cur_issue;
   const unsigned as_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(lds_ptr_h)As);
 
@@ -227,7 +178,7 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
   }
   auto issue_tile = [&](int it) {
     int row0_, valid_;
-    cur_seek(cur_issue, tile_at(it < my_tiles ? it : my_tiles - 1), row0_, valid_);
+    cur_issue.seek<ROWS>(tl, tiles.at(it < my_tiles ? it : my_tiles - 1), row0_, valid_);
     const unsigned buf = as_base + (unsigned)(it % NBUF) * TILE_BYTES + (unsigned)wave * 1024u;
 #pragma unroll
     for (int p = 0; p < LPW; ++p) {
@@ -350,8 +301,7 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
 #endif
   for (int i = 0; i < my_tiles; ++i) {
     int row0, valid;
-    cur_seek(cur_run, tile_at(i), row0, valid);
-    const int seg = cur_run.seg;
+    const int seg = cur_run.seek<ROWS>(tl, tiles.at(i), row0, valid);
     DIAG_T(0);
     // tile i has landed: in the steady state all but the D * OPASS stores and (D - 1) * LPW loads issued after its loads;
     // the first D iterations (no stores of earlier tiles in the queue yet) simply wait for everything
@@ -359,7 +309,7 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
     else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kWaitSteady) : "memory");
     DIAG_T(1);
     if (seg != cur_seg) {  // uniform; everyone passed the barrier that ended the previous tile's products
-      const int64_t boff = t_b_s[seg];
+      const int64_t boff = tl.b[seg];
       for (int n = tid; n < NOUT; n += NT) bias_s[n] = (a.bias != nullptr && boff >= 0) ? a.bias[boff + n] : 0.f;
     }
     __syncthreads();  // every wave's part of tile i is in LDS; buffer (i + D) % NBUF (tile i - 1) and Outs are free
@@ -397,7 +347,7 @@ fwd_hd_kernel(FwdHTable st, int n_tiles, FwdHArgs a, int rev) {
 }
 
 template <int NOPS, int KO, int NOUT, bool TRANS, bool F32OUT = false>
-static int launch_fwd_hd(const FwdHTable& st, int n_tiles, const FwdHArgs& a, hipStream_t sm) {
+static int launch_fwd_hd(const SegTable& st, int n_tiles, const FwdHArgs& a, hipStream_t sm) {
   constexpr int RQ = NOPS * KO / 8;
   const size_t shmem = (size_t)3 * 64 * RQ * 16 + (size_t)64 * (NOUT * (F32OUT ? 4 : 2) + 16);
   auto kern = fwd_hd_kernel<NOPS, KO, NOUT, TRANS, F32OUT>;
@@ -438,15 +388,10 @@ static int launch_fwd_hd(const FwdHTable& st, int n_tiles, const FwdHArgs& a, hi
 int fwd_weight_images(int32_t n_seg, const int64_t* w1_off, const int64_t* w2_off, const float* d_w1, const float* d_w2,
                       int32_t k_in, int32_t ko, int32_t n_ops, int32_t n_out, int32_t trans_w, float* d_scratch,
                       hipStream_t sm) {
-  if (n_seg > kHMaxSeg || d_scratch == nullptr || !aligned16(d_scratch)) return GCMI_ERR_UNSUPPORTED;
+  if (n_seg > kMaxProductSeg || d_scratch == nullptr || !aligned16(d_scratch)) return GCMI_ERR_UNSUPPORTED;
   if ((int64_t)n_seg * (n_out / 32) * (n_ops * ko / 16) * 3 * 256 > kFwdHWimgFloats) return GCMI_ERR_UNSUPPORTED;
-  FwdHTable st;
-  memset(&st, 0, sizeof(st));
-  st.n_seg = n_seg;
-  for (int s = 0; s < kHMaxSeg; ++s) {
-    st.w_off[0][s] = (s < n_seg && w1_off) ? w1_off[s] : -1;
-    st.w_off[1][s] = (s < n_seg && w2_off && n_ops == 2) ? w2_off[s] : -1;
-  }
+  SegTable st;  // (wprep_kernel reads n_seg and the weight offsets only: no bounds, no bias)
+  fill_seg_table(st, n_seg, nullptr, nullptr, w1_off, n_ops == 2 ? w2_off : nullptr, nullptr, 64);
   const int entries = n_seg * (n_out / 32) * (n_ops * ko / 16) * 64;
   const int blocks = std::min((entries + 255) / 256, 1024);
   u32x4* wimg = reinterpret_cast<u32x4*>(d_scratch);
@@ -466,8 +411,8 @@ int fwd_h_gemm(const SegProduct<bf16_t, TO>& p, double* d_stats, float* d_wimg_s
   if (d_wimg_scratch == nullptr || !aligned16(d_wimg_scratch) || gemm_exact_mode()) return GCMI_ERR_UNSUPPORTED;
   const FwdShape shape = fwd_shape(p);
   if (shape == kFwdNone || (kF32Out && shape != kFwdConv80)) return GCMI_ERR_UNSUPPORTED;
-  FwdHTable st;
-  const int64_t tiles = fill_seg_table(st, st.w_off[0], st.w_off[1], st.b_off, p, 64);
+  SegTable st;
+  const int64_t tiles = fill_seg_table(st, p, 64);
   if (tiles == 0) return GCMI_OK;
   FwdHArgs a;
   memset(&a, 0, sizeof(a));

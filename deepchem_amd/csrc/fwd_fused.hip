@@ -15,17 +15,6 @@
 
 namespace gcmi {
 
-constexpr int kWMaxSeg = kMaxProductSeg;
-
-struct FwdTable {
-  int32_t n_seg;
-  int32_t seg_begin[kWMaxSeg];
-  int32_t seg_end[kWMaxSeg];
-  int32_t tile_start[kWMaxSeg + 1];
-  int64_t w_off[2][kWMaxSeg];  // weight block of operand o; < 0: term absent
-  int64_t b_off[kWMaxSeg];     // bias row; < 0: none
-};
-
 struct FwdArgs {
   const float* in[2];
   int32_t ldin[2];
@@ -44,7 +33,7 @@ struct FwdArgs {
 // NOUT x k_in (nn.Linear) instead of k_in x NOUT
 template <int ROWS, int NOPS, int KO, int NOUT, bool TRANS>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2)))
-fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
+fwd_fused_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
   constexpr int NT = 512;
   constexpr int NC = NOPS * KO;               // contraction length
   constexpr int AP = NC + 4;                  // pitch of an operand row in LDS (floats)
@@ -62,8 +51,7 @@ fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
   float* As = reinterpret_cast<float*>(lds_raw);                                       // [ROWS][AP]
   unsigned short* Wimg = reinterpret_cast<unsigned short*>(As + ROWS * AP);            // [3][NOUT][WP]
   float* Outs = reinterpret_cast<float*>(Wimg + (size_t)3 * NOUT * WP);                // [ROWS][OP]
-  __shared__ int t_begin_s[kWMaxSeg], t_end_s[kWMaxSeg], t_tile_s[kWMaxSeg + 1];
-  __shared__ long long t_w_s[2][kWMaxSeg], t_b_s[kWMaxSeg];
+  __shared__ SegTableLds tl;
   __shared__ __attribute__((aligned(16))) float bias_s[NOUT];
   __shared__ double stat_s[2][NOUT];
 
@@ -74,51 +62,15 @@ fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
   const int l31 = lane & 31;
   const int rb = wave % RB, tw = wave / RB;   // this wave's output tile: rows rb*32.., columns tw*32..
 
-  if (tid <= kWMaxSeg) {
-    t_tile_s[tid] = pick_n(st.tile_start, tid);
-    if (tid < kWMaxSeg) {
-      t_begin_s[tid] = pick_n(st.seg_begin, tid);
-      t_end_s[tid] = pick_n(st.seg_end, tid);
-      t_w_s[0][tid] = pick_n(st.w_off[0], tid);
-      t_w_s[1][tid] = pick_n(st.w_off[1], tid);
-      t_b_s[tid] = pick_n(st.b_off, tid);
-    }
-  }
+  tl.fill(st);
   for (int c = tid; c < 2 * NOUT; c += NT) stat_s[c / NOUT][c % NOUT] = 0.0;
-  const int n_seg = st.n_seg;
   __syncthreads();
 
-  const int b = rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
-  const int t_begin = (int)((int64_t)b * n_tiles / gridDim.x);
-  const int t_end = (int)((int64_t)(b + 1) * n_tiles / gridDim.x);
-  const int my_tiles = t_end - t_begin;  // >= 1: the grid is never larger than the tile count
-  auto tile_at = [&](int i) { return rev ? t_end - 1 - i : t_begin + i; };
-  // Tile -> (segment, first row, rows) by a cursor that moves with the walk: a workgroup's tiles are consecutive, so the
-  // segment changes now and then and a look-up is otherwise two scalar operations.  (The per-tile search it replaces --
-  // a loop of LDS reads over the segment starts, each landing in a vector register -- measured ~1 200 cycles per
-  // look-up in fwd_hd_kernel's phase clocks, csrc/fwd_bf16.hip.)
-  struct Cursor { int seg, t0, t1, r0, r1; } cur;
-  auto cur_load = [&]() {
-    cur.t0 = __builtin_amdgcn_readfirstlane(t_tile_s[cur.seg]);
-    cur.t1 = __builtin_amdgcn_readfirstlane(t_tile_s[cur.seg + 1]);
-    cur.r0 = __builtin_amdgcn_readfirstlane(t_begin_s[cur.seg]);
-    cur.r1 = __builtin_amdgcn_readfirstlane(t_end_s[cur.seg]);
-  };
-  {
-    const int first = tile_at(0);
-    int sg = 0;
-    for (int k = 1; k < n_seg; ++k) sg += first >= t_tile_s[k] ? 1 : 0;
-    cur.seg = __builtin_amdgcn_readfirstlane(sg);
-    cur_load();
-  }
-  auto tile_info = [&](int tile, int& seg, int& row0, int& valid) {
-    while (tile >= cur.t1) { ++cur.seg; cur_load(); }  // (uniform; empty segments are stepped over)
-    while (tile < cur.t0) { --cur.seg; cur_load(); }
-    seg = cur.seg;
-    row0 = cur.r0 + (tile - cur.t0) * ROWS;
-    const int left = cur.r1 - row0;
-    valid = left < ROWS ? left : ROWS;
-  };
+  const TileRange tiles = tile_range<false>(n_tiles, rev);
+  const int my_tiles = tiles.count();
+  SegCursor cur;  // tile -> (segment, first row, rows), moving with the walk
+  cur.init(tl, st.n_seg, tiles.at(0));
+  auto tile_info = [&](int tile, int& seg, int& row0, int& valid) { seg = cur.seek<ROWS>(tl, tile, row0, valid); };
 
   // ---- prefetch registers: the next tile's operand rows, 16 bytes per lane, unconditional from clamped addresses
   float4 pin[NOPS][IPASS];
@@ -168,9 +120,9 @@ fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
   };
 
   int seg, row0, valid;
-  tile_info(tile_at(0), seg, row0, valid);
+  tile_info(tiles.at(0), seg, row0, valid);
   int nseg = seg, nrow0 = row0, nvalid = valid;
-  if (my_tiles > 1) tile_info(tile_at(1), nseg, nrow0, nvalid);
+  if (my_tiles > 1) tile_info(tiles.at(1), nseg, nrow0, nvalid);
   load_src(row0, valid);
   int cur_seg = -1;
   int prow0 = row0, pvalid = 0;
@@ -191,7 +143,7 @@ fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
           n = e - c * NOUT;
         }
         const int o = c / KO, ck = c - o * KO;
-        const int64_t woff = t_w_s[o][seg];
+        const int64_t woff = tl.w[o][seg];
         float v = 0.f;
         if (woff >= 0 && ck < a.k_in) {
           const float* w = o == 1 ? a.w[1] : a.w[0];
@@ -204,7 +156,7 @@ fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
         dst[(size_t)NOUT * WP] = (unsigned short)(p2 >> 16);
         dst[(size_t)2 * NOUT * WP] = (unsigned short)(p3 >> 16);
       }
-      const int64_t boff = t_b_s[seg];
+      const int64_t boff = tl.b[seg];
       for (int n = tid; n < NOUT; n += NT) bias_s[n] = (a.bias != nullptr && boff >= 0) ? a.bias[boff + n] : 0.f;
     }
 
@@ -215,7 +167,7 @@ fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
     }
 #pragma unroll
     for (int o = 0; o < NOPS; ++o) {
-      const bool present = t_w_s[o][seg] >= 0;
+      const bool present = tl.w[o][seg] >= 0;
 #pragma unroll
       for (int p = 0; p < IPASS; ++p) {
         const int slot = tid + p * NT;
@@ -234,7 +186,7 @@ fwd_fused_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
 
     // ---- phase (b): the next tile's rows in flight, this wave's 32 x 32 output tile over the whole contraction
     int n2seg = nseg, n2row0 = nrow0, n2valid = nvalid;
-    if (i + 2 < my_tiles) tile_info(tile_at(i + 2), n2seg, n2row0, n2valid);
+    if (i + 2 < my_tiles) tile_info(tiles.at(i + 2), n2seg, n2row0, n2valid);
     load_src(nrow0, nvalid);
     {
       f32x16 acc;
@@ -318,7 +270,7 @@ __device__ float g_fwd_dump[512 * 256];
 
 template <int NOPS, int KO, int NOUT, bool TRANS>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2)))
-fwd_reg_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
+fwd_reg_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
   constexpr int NT = 256, ROWS = 64;
   constexpr int NC = NOPS * KO;               // contraction length
   constexpr int AP = NC + 4;                  // pitch of an operand row in LDS (floats)
@@ -331,8 +283,7 @@ fwd_reg_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
   static_assert(ROWS * IQ % NT == 0, "tile loads divide evenly");
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   float* As = reinterpret_cast<float*>(lds_raw);  // [ROWS][AP]
-  __shared__ int t_begin_s[kWMaxSeg], t_end_s[kWMaxSeg], t_tile_s[kWMaxSeg + 1];
-  __shared__ long long t_w_s[2][kWMaxSeg], t_b_s[kWMaxSeg];
+  __shared__ SegTableLds tl;
   __shared__ double stat_s[2][NOUT];
 
   const int tid = threadIdx.x;
@@ -343,52 +294,15 @@ fwd_reg_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
   const int rb = wave & 1, twb = wave >> 1;   // rows rb*32.., column tiles twb, twb + 2, ...
   float* const my_dump = &g_fwd_dump[(blockIdx.x % 512) * 256 + tid];
 
-  if (tid <= kWMaxSeg) {
-    t_tile_s[tid] = pick_n(st.tile_start, tid);
-    if (tid < kWMaxSeg) {
-      t_begin_s[tid] = pick_n(st.seg_begin, tid);
-      t_end_s[tid] = pick_n(st.seg_end, tid);
-      t_w_s[0][tid] = pick_n(st.w_off[0], tid);
-      t_w_s[1][tid] = pick_n(st.w_off[1], tid);
-      t_b_s[tid] = pick_n(st.b_off, tid);
-    }
-  }
+  tl.fill(st);
   for (int c = tid; c < 2 * NOUT; c += NT) stat_s[c / NOUT][c % NOUT] = 0.0;
-  const int n_seg = st.n_seg;
   __syncthreads();
 
-  const int b = rev ? (int)gridDim.x - 1 - (int)blockIdx.x : (int)blockIdx.x;
-  // (64-bit division runs on the vector unit: say that the results are uniform)
-  const int t_begin = __builtin_amdgcn_readfirstlane((int)((int64_t)b * n_tiles / gridDim.x));
-  const int t_end = __builtin_amdgcn_readfirstlane((int)((int64_t)(b + 1) * n_tiles / gridDim.x));
-  const int my_tiles = t_end - t_begin;  // >= 1: the grid is never larger than the tile count
-  auto tile_at = [&](int i) { return rev ? t_end - 1 - i : t_begin + i; };
-  // Tile -> (segment, first row, rows) by a cursor that moves with the walk: a workgroup's tiles are consecutive, so the
-  // segment changes now and then and a look-up is otherwise two scalar operations.  (The per-tile search it replaces --
-  // a loop of LDS reads over the segment starts, each landing in a vector register -- measured ~1 200 cycles per
-  // look-up in fwd_hd_kernel's phase clocks, csrc/fwd_bf16.hip.)
-  struct Cursor { int seg, t0, t1, r0, r1; } cur;
-  auto cur_load = [&]() {
-    cur.t0 = __builtin_amdgcn_readfirstlane(t_tile_s[cur.seg]);
-    cur.t1 = __builtin_amdgcn_readfirstlane(t_tile_s[cur.seg + 1]);
-    cur.r0 = __builtin_amdgcn_readfirstlane(t_begin_s[cur.seg]);
-    cur.r1 = __builtin_amdgcn_readfirstlane(t_end_s[cur.seg]);
-  };
-  {
-    const int first = tile_at(0);
-    int sg = 0;
-    for (int k = 1; k < n_seg; ++k) sg += first >= t_tile_s[k] ? 1 : 0;
-    cur.seg = __builtin_amdgcn_readfirstlane(sg);
-    cur_load();
-  }
-  auto tile_info = [&](int tile, int& seg, int& row0, int& valid) {
-    while (tile >= cur.t1) { ++cur.seg; cur_load(); }  // (uniform; empty segments are stepped over)
-    while (tile < cur.t0) { --cur.seg; cur_load(); }
-    seg = cur.seg;
-    row0 = cur.r0 + (tile - cur.t0) * ROWS;
-    const int left = cur.r1 - row0;
-    valid = left < ROWS ? left : ROWS;
-  };
+  const TileRange tiles = tile_range<true>(n_tiles, rev);
+  const int my_tiles = tiles.count();
+  SegCursor cur;  // tile -> (segment, first row, rows), moving with the walk
+  cur.init(tl, st.n_seg, tiles.at(0));
+  auto tile_info = [&](int tile, int& seg, int& row0, int& valid) { seg = cur.seek<ROWS>(tl, tile, row0, valid); };
 
   // ---- prefetch registers: the next tile's operand rows, 16 bytes per lane, unconditional from clamped addresses.
   // Addresses stay (uniform base, 32-bit byte offset) formed at the load: anything the compiler can hoist out of the
@@ -428,10 +342,10 @@ fwd_reg_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
   auto write_as = [&](int seg_, int valid_) {
     bool whole = valid_ == ROWS && a.k_in == KO;
 #pragma unroll
-    for (int o = 0; o < NOPS; ++o) whole = whole && t_w_s[o][seg_] >= 0;
+    for (int o = 0; o < NOPS; ++o) whole = whole && tl.w[o][seg_] >= 0;
 #pragma unroll
     for (int o = 0; o < NOPS; ++o) {
-      const bool present = t_w_s[o][seg_] >= 0;
+      const bool present = tl.w[o][seg_] >= 0;
 #pragma unroll
       for (int p = 0; p < IPASS; ++p) {
         int r, q;
@@ -465,7 +379,7 @@ fwd_reg_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
       for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) wf[j][ks][pc] = base[(size_t)(((twb + 2 * j) * NKS + ks) * 3 + pc) * 64];
-      const int64_t boff = t_b_s[seg_];
+      const int64_t boff = tl.b[seg_];
       bv[j] = (a.bias != nullptr && boff >= 0) ? a.bias[boff + (twb + 2 * j) * 32 + l31] : 0.f;
     }
   };
@@ -545,9 +459,9 @@ fwd_reg_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
   };
 
   int seg, row0, valid;
-  tile_info(tile_at(0), seg, row0, valid);
+  tile_info(tiles.at(0), seg, row0, valid);
   int nseg = seg, nrow0 = row0, nvalid = valid;
-  if (my_tiles > 1) tile_info(tile_at(1), nseg, nrow0, nvalid);
+  if (my_tiles > 1) tile_info(tiles.at(1), nseg, nrow0, nvalid);
   load_src(row0, valid);
   int cur_seg = seg;
   load_w(seg);
@@ -556,7 +470,7 @@ fwd_reg_kernel(FwdTable st, int n_tiles, FwdArgs a, int rev) {
     write_as(seg, valid);
     __syncthreads();
     int n2seg = nseg, n2row0 = nrow0, n2valid = nvalid;
-    if (i + 2 < my_tiles) tile_info(tile_at(i + 2), n2seg, n2row0, n2valid);
+    if (i + 2 < my_tiles) tile_info(tiles.at(i + 2), n2seg, n2row0, n2valid);
     load_src(nrow0, nvalid);  // ahead of this tile's stores in the memory queue
     if (seg != cur_seg) {  // uniform
       cur_seg = seg;
@@ -585,7 +499,7 @@ static bool fwd_fused_on() {
 }
 
 template <int ROWS, int NOPS, int KO, int NOUT, bool TRANS>
-static int launch_fwd(const FwdTable& st, int n_tiles, const FwdArgs& a, hipStream_t sm) {
+static int launch_fwd(const SegTable& st, int n_tiles, const FwdArgs& a, hipStream_t sm) {
   constexpr int NC = NOPS * KO;
   const size_t shmem = sizeof(float) * ROWS * (NC + 4) + sizeof(unsigned short) * (size_t)3 * NOUT * (NC + 8) +
                        sizeof(float) * ROWS * (NOUT + 8);
@@ -599,7 +513,7 @@ static int launch_fwd(const FwdTable& st, int n_tiles, const FwdArgs& a, hipStre
 }
 
 template <int NOPS, int KO, int NOUT, bool TRANS>
-static int launch_fwd_reg(const FwdTable& st, int n_tiles, const FwdArgs& a, hipStream_t sm) {
+static int launch_fwd_reg(const SegTable& st, int n_tiles, const FwdArgs& a, hipStream_t sm) {
   constexpr int NC = NOPS * KO;
   const size_t shmem = sizeof(float) * 64 * (NC + 4);
   auto kern = fwd_reg_kernel<NOPS, KO, NOUT, TRANS>;
@@ -617,8 +531,8 @@ int fwd_fused_gemm(const SegProduct<float>& p, double* d_stats, hipStream_t sm, 
   if (!fwd_fused_on() || !fused_bwd_enabled()) return GCMI_ERR_UNSUPPORTED;
   const FwdShape shape = fwd_shape(p);
   if (shape == kFwdNone) return GCMI_ERR_UNSUPPORTED;
-  FwdTable st;
-  const int64_t tiles = fill_seg_table(st, st.w_off[0], st.w_off[1], st.b_off, p, shape == kFwdConv ? 128 : 64);
+  SegTable st;
+  const int64_t tiles = fill_seg_table(st, p, shape == kFwdConv ? 128 : 64);
   if (tiles == 0) return GCMI_OK;
   FwdArgs a;
   memset(&a, 0, sizeof(a));

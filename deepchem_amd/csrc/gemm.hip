@@ -26,37 +26,11 @@ namespace gcmi {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int kMaxSeg = kMaxProductSeg;
 constexpr int kGBlock = 256;
 constexpr int BM = 64;
 constexpr int BNT = 64;
 constexpr int KC = 32;
 constexpr int BM2 = 128;
-
-struct SegTable {
-  int32_t n_seg;
-  int32_t seg_begin[kMaxSeg];
-  int32_t seg_end[kMaxSeg];
-  int32_t tile_start[kMaxSeg + 1];
-  int64_t w1_off[kMaxSeg];  // < 0: term absent
-  int64_t w2_off[kMaxSeg];
-  int64_t bias_off[kMaxSeg];
-};
-
-__device__ __forceinline__ int seg_of_tile(const SegTable& st, int b) {
-  int s = 0;
-#pragma unroll
-  for (int k = 1; k < kMaxSeg; ++k) s += (k < st.n_seg && b >= st.tile_start[k]) ? 1 : 0;
-  return s;
-}
-
-template <typename T>
-__device__ __forceinline__ T pick_seg(const T* a, int s) {
-  T v = a[0];
-#pragma unroll
-  for (int k = 1; k < kMaxSeg; ++k) v = (s == k) ? a[k] : v;
-  return v;
-}
 
 // stage one K-chunk of A (64 rows x KC) and of W (KC x 64 cols) into LDS
 template <bool VEC4>
@@ -129,8 +103,8 @@ seg_gemm_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1,
   __shared__ float Bs[KC][BNT + 1];
   const int b = blockIdx.x;
   const int s = seg_of_tile(st, b);
-  const int row0 = pick_seg(st.seg_begin, s) + (b - pick_seg(st.tile_start, s)) * BM;
-  const int seg_end = pick_seg(st.seg_end, s);
+  const int row0 = pick_n(st.seg_begin, s) + (b - first_tile(st, s)) * BM;
+  const int seg_end = pick_n(st.seg_end, s);
   const int rows_valid = (seg_end - row0 < BM) ? seg_end - row0 : BM;
   const int col0 = blockIdx.y * BNT;
   const int wave = threadIdx.x >> 6;
@@ -145,7 +119,7 @@ seg_gemm_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1,
     const float* a = p == 0 ? a1 : a2;
     const int64_t lda = p == 0 ? lda1 : lda2;
     const int K = p == 0 ? k1 : k2;
-    const int64_t woff = p == 0 ? pick_seg(st.w1_off, s) : pick_seg(st.w2_off, s);
+    const int64_t woff = p == 0 ? pick_n(st.w_off[0], s) : pick_n(st.w_off[1], s);
     const float* wbase = p == 0 ? w1 : w2;
     if (a == nullptr || wbase == nullptr || woff < 0) continue;  // block-uniform
     const float* w = wbase + woff;
@@ -162,7 +136,7 @@ seg_gemm_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1,
       __syncthreads();
     }
   }
-  const int64_t boff = pick_seg(st.bias_off, s);
+  const int64_t boff = pick_n(st.b_off, s);
   const int col = col0 + wc * 32 + (lane & 31);
   if (col < n_out) {
     const float bv = (bias != nullptr && boff >= 0) ? bias[boff + col] : 0.f;
@@ -201,8 +175,8 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
   __shared__ float Bs[KC][BN2 + 1];
   const int b = blockIdx.x;
   const int s = seg_of_tile(st, b);
-  const int row0 = pick_seg(st.seg_begin, s) + (b - pick_seg(st.tile_start, s)) * BM2;
-  const int seg_end = pick_seg(st.seg_end, s);
+  const int row0 = pick_n(st.seg_begin, s) + (b - first_tile(st, s)) * BM2;
+  const int seg_end = pick_n(st.seg_end, s);
   const int rows_valid = (seg_end - row0 < BM2) ? seg_end - row0 : BM2;
   const int col0 = blockIdx.y * BN2;
   const int tid = threadIdx.x;
@@ -216,7 +190,7 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
 
-  const int64_t woff1 = pick_seg(st.w1_off, s), woff2 = pick_seg(st.w2_off, s);
+  const int64_t woff1 = pick_n(st.w_off[0], s), woff2 = pick_n(st.w_off[1], s);
   const bool on1 = a1 != nullptr && w1 != nullptr && woff1 >= 0;
   const bool on2 = a2 != nullptr && w2 != nullptr && woff2 >= 0;
   const int n1 = on1 ? (k1 + KC - 1) / KC : 0;
@@ -332,7 +306,7 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
       }
     }
   }
-  const int64_t boff = pick_seg(st.bias_off, s);
+  const int64_t boff = pick_n(st.b_off, s);
   const bool has_bias = bias != nullptr && boff >= 0;
   const int r = wrow * 32 + (lane & 31);
   float bv[NT][4][4];
@@ -383,11 +357,9 @@ wgrad_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, int 
              const float* __restrict__ g, int64_t ldg, int n, int ntw, float* __restrict__ dw,
              float* __restrict__ dbias) {
   const int b = blockIdx.x;
-  int s = 0;
-#pragma unroll
-  for (int q = 1; q < kMaxSeg; ++q) s += (q < st.n_seg && b >= st.slab_start[q]) ? 1 : 0;
-  const int seg_end = pick_seg(st.seg_end, s);
-  const int slab0 = pick_seg(st.seg_begin, s) + (b - pick_seg(st.slab_start, s)) * st.slab_rows;
+  const int s = seg_of_slab(st, b);
+  const int seg_end = pick_n(st.seg_end, s);
+  const int slab0 = pick_n(st.seg_begin, s) + (b - first_slab(st, s)) * st.slab_rows;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int nt = blockIdx.y * ntw + (wave % ntw);  // n-tile of this wave
@@ -488,7 +460,7 @@ wgrad_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, int 
     if (rp != 0) return;
   }
   if (slab0 >= seg_end) return;
-  const int64_t woff = pick_seg(st.dw_off, s);
+  const int64_t woff = pick_n(st.dw_off, s);
   if (woff >= 0) {
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
@@ -506,7 +478,7 @@ wgrad_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, int 
     }
   }
   if (dbias != nullptr && kt0 == 0) {
-    const int64_t boff = pick_seg(st.db_off, s);
+    const int64_t boff = pick_n(st.db_off, s);
     bsum += __shfl_xor(bsum, 32);
     if (half == 0 && n_ok && boff >= 0) atomicAdd(dbias + boff + ncol, bsum);
   }
@@ -546,7 +518,7 @@ static std::atomic<int> g_fused_bn_stats{getenv("GCMI_GEMM_STATS") && atoi(geten
 // the argument checks of gcmi_seg_gemm
 static int check_seg_product(const SegProduct<float>& p) {
   const SegOperand<float>&a1 = p.op[0], &a2 = p.op[1];
-  GCMI_CHECK_ARG(p.n_seg >= 1 && p.n_seg <= kMaxSeg, "seg_gemm: n_seg %d outside [1,%d]", p.n_seg, kMaxSeg);
+  GCMI_CHECK_ARG(p.n_seg >= 1 && p.n_seg <= kMaxProductSeg, "seg_gemm: n_seg %d outside [1,%d]", p.n_seg, kMaxProductSeg);
   GCMI_CHECK_ARG(p.seg_begin && p.seg_end, "seg_gemm: NULL segment table");
   GCMI_CHECK_ARG(p.n_out > 0 && p.ldo >= p.n_out && p.out, "seg_gemm: bad output");
   GCMI_CHECK_ARG((a1.a && a1.w && a1.w_off && a1.k > 0 && a1.ld >= a1.k) || (a1.a == nullptr),
@@ -570,7 +542,7 @@ int seg_gemm(const SegProduct<float>& p, hipStream_t sm) {
                     (a2.a == nullptr || (aligned16(a2.a) && a2.ld % 4 == 0));
   const int nt = n_out <= 32 ? 1 : (n_out <= 64 ? 2 : 4);
   SegTable st;
-  const int64_t tiles = fill_seg_table(st, st.w1_off, st.w2_off, st.bias_off, p, vec4 ? BM2 : BM);
+  const int64_t tiles = fill_seg_table(st, p, vec4 ? BM2 : BM);
   if (tiles == 0) return GCMI_OK;
   TimedScope ts(GCMI_K_SEG_GEMM, sm);
   const bool exact = gemm_exact_mode();
@@ -682,7 +654,7 @@ int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* 
                         const float* d_a, int64_t lda, int32_t k, const float* d_g, int64_t ldg,
                         int32_t n, float* d_dw, const int64_t* dw_off, float* d_dbias,
                         const int64_t* dbias_off, int32_t trans_w, void* stream) {
-  GCMI_CHECK_ARG(n_seg >= 1 && n_seg <= kMaxSeg, "wgrad: n_seg %d outside [1,%d]", n_seg, kMaxSeg);
+  GCMI_CHECK_ARG(n_seg >= 1 && n_seg <= kMaxSegW, "wgrad: n_seg %d outside [1,%d]", n_seg, kMaxSegW);
   GCMI_CHECK_ARG(seg_begin && seg_end && dw_off, "wgrad: NULL segment table");
   GCMI_CHECK_ARG(k > 0 && n > 0 && lda >= k && ldg >= n, "wgrad: bad shape");
   GCMI_CHECK_ARG(d_a && d_g && d_dw, "wgrad: NULL buffer");
@@ -720,7 +692,7 @@ int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* 
   }
   st.slab_rows = (int32_t)slab;
   int64_t slabs = 0;
-  for (int s = 0; s < kMaxSeg; ++s) {
+  for (int s = 0; s < kMaxSegW; ++s) {
     st.slab_start[s] = (int32_t)slabs;
     if (s < n_seg) {
       st.seg_begin[s] = seg_begin[s];
@@ -732,7 +704,7 @@ int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* 
       st.dw_off[s] = st.db_off[s] = -1;
     }
   }
-  st.slab_start[kMaxSeg] = (int32_t)slabs;
+  st.slab_start[kMaxSegW] = (int32_t)slabs;
   hipStream_t sm = (hipStream_t)stream;
   const int NT = (n + 31) / 32;
   const int ntw = NT >= 3 ? 4 : NT;  // n-tiles per workgroup: 1, 2 or 4

@@ -26,25 +26,6 @@ namespace gcmi {
 
 constexpr int kS3Block = 256;
 constexpr int kS3Rows = 128;
-constexpr int kS3MaxSeg = kMaxProductSeg;
-
-struct SegTable3 {
-  int32_t n_seg;
-  int32_t seg_begin[kS3MaxSeg];
-  int32_t seg_end[kS3MaxSeg];
-  int32_t tile_start[kS3MaxSeg + 1];
-  int64_t w1_off[kS3MaxSeg];  // < 0: term absent
-  int64_t w2_off[kS3MaxSeg];
-  int64_t bias_off[kS3MaxSeg];
-};
-
-template <typename T>
-__device__ __forceinline__ T pick3(const T* a, int s) {
-  T v = a[0];
-#pragma unroll
-  for (int k = 1; k < kS3MaxSeg; ++k) v = (s == k) ? a[k] : v;
-  return v;
-}
 
 // ------------------------------------------------------------------ forward / dgrad, LDS-staged
 constexpr int kS4KC = 32;          // K chunk
@@ -55,7 +36,7 @@ constexpr int kS4WStride = kS4KC + 8;   // bf16 per staged W column: conflict-fr
 // arithmetic, so the result does not depend on how the caller laid its rows out)
 template <bool TRANS, int NT, bool AVEC>
 __global__ void __launch_bounds__(kS3Block) __attribute__((amdgpu_waves_per_eu(NT <= 2 ? 3 : 2)))
-seg_gemm4_kernel(SegTable3 st, const float* __restrict__ a1, int64_t lda1, int k1, const float* __restrict__ w1,
+seg_gemm4_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1, const float* __restrict__ w1,
                  const float* __restrict__ a2, int64_t lda2, int k2, const float* __restrict__ w2,
                  const float* __restrict__ bias, int n_out, int act, float* __restrict__ out, int64_t ldo,
                  double* __restrict__ stats, int rev) {
@@ -74,19 +55,17 @@ seg_gemm4_kernel(SegTable3 st, const float* __restrict__ a1, int64_t lda1, int k
   __shared__ __attribute__((aligned(16))) float bias_lds[NB];
   __shared__ double col_part[4][2][NB];           // per-wave column sums / sums of squares
   const int b = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;  // last-written rows first on alternate launches
-  int s = 0;
-#pragma unroll
-  for (int k = 1; k < kS3MaxSeg; ++k) s += (k < st.n_seg && b >= st.tile_start[k]) ? 1 : 0;
-  const int row0 = pick3(st.seg_begin, s) + (b - pick3(st.tile_start, s)) * kS3Rows;
-  const int seg_end = pick3(st.seg_end, s);
+  const int s = seg_of_tile(st, b);
+  const int row0 = pick_n(st.seg_begin, s) + (b - first_tile(st, s)) * kS3Rows;
+  const int seg_end = pick_n(st.seg_end, s);
   const int rows_valid = (seg_end - row0 < kS3Rows) ? seg_end - row0 : kS3Rows;
   const int col0 = blockIdx.y * NB;
   const int tid = threadIdx.x;
   const int wave = tid >> 6;
   const int lane = tid & 63;
   const int half = lane >> 5;
-  const int64_t woff1 = pick3(st.w1_off, s), woff2 = pick3(st.w2_off, s);
-  const int64_t boff = pick3(st.bias_off, s);
+  const int64_t woff1 = pick_n(st.w_off[0], s), woff2 = pick_n(st.w_off[1], s);
+  const int64_t boff = pick_n(st.b_off, s);
   const bool on1 = a1 != nullptr && w1 != nullptr && woff1 >= 0;
   const bool on2 = a2 != nullptr && w2 != nullptr && woff2 >= 0;
   const int n1 = on1 ? (k1 + kS4KC - 1) / kS4KC : 0;
@@ -312,13 +291,13 @@ seg_gemm4_kernel(SegTable3 st, const float* __restrict__ a1, int64_t lda1, int k
 int launch_seg_gemm4(const SegProduct<float>& p, hipStream_t sm, double* d_stats) {
   const SegOperand<float>&a1 = p.op[0], &a2 = p.op[1];
   const int32_t n_out = p.n_out;
-  if (p.n_seg > kS3MaxSeg) return GCMI_ERR_UNSUPPORTED;
+  if (p.n_seg > kMaxProductSeg) return GCMI_ERR_UNSUPPORTED;
   if (d_stats && p.act == 2) return GCMI_ERR_UNSUPPORTED;
   const bool avec = !((a1.a && (!aligned16(a1.a) || a1.ld % 4)) || (a2.a && (!aligned16(a2.a) || a2.ld % 4)));
   if (n_out % 4 || p.ldo % 4 || !aligned16(p.out)) return GCMI_ERR_UNSUPPORTED;
   int nt = n_out <= 32 ? 1 : (n_out <= 64 ? 2 : 4);
-  SegTable3 st;
-  const int64_t tiles = fill_seg_table(st, st.w1_off, st.w2_off, st.bias_off, p, kS3Rows);
+  SegTable st;
+  const int64_t tiles = fill_seg_table(st, p, kS3Rows);
   if (tiles == 0) return GCMI_OK;
   // Few row tiles (a per-molecule product: the task heads at a per-GPU batch of a few thousand molecules) leave most
   // of the 256 CUs idle at 128 rows x 128 columns per workgroup: narrower column groups then, until the launch has a
@@ -357,11 +336,9 @@ __global__ void __launch_bounds__(kS3Block)
 wgrad3_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, const float* __restrict__ g,
               int64_t ldg, int n, int ntw, float* __restrict__ dw, float* __restrict__ dbias, int rev) {
   const int b = rev ? gridDim.x - 1 - blockIdx.x : blockIdx.x;  // last-written rows first on alternate launches
-  int s = 0;
-#pragma unroll
-  for (int q = 1; q < kMaxSegW; ++q) s += (q < st.n_seg && b >= st.slab_start[q]) ? 1 : 0;
-  const int seg_end = pick3(st.seg_end, s);
-  const int slab0 = pick3(st.seg_begin, s) + (b - pick3(st.slab_start, s)) * st.slab_rows;
+  const int s = seg_of_slab(st, b);
+  const int seg_end = pick_n(st.seg_end, s);
+  const int slab0 = pick_n(st.seg_begin, s) + (b - first_slab(st, s)) * st.slab_rows;
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int half = lane >> 5;
@@ -467,7 +444,7 @@ wgrad3_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, con
     if (rp != 0) return;
   }
   if (slab0 >= seg_end) return;
-  const int64_t woff = pick3(st.dw_off, s);
+  const int64_t woff = pick_n(st.dw_off, s);
   if (woff >= 0) {
 #pragma unroll
     for (int t = 0; t < KT; ++t) {
@@ -485,7 +462,7 @@ wgrad3_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, con
     }
   }
   if (dbias != nullptr && blockIdx.z == 0) {
-    const int64_t boff = pick3(st.db_off, s);
+    const int64_t boff = pick_n(st.db_off, s);
     bsum += __shfl_xor(bsum, 32);
     if (half == 0 && n_ok && boff >= 0) atomicAdd(dbias + boff + ncol, bsum);
   }

@@ -85,13 +85,4 @@ __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) {
   return __builtin_bit_cast(bf16x8, v);
 }
 
-// a by-value table entry picked with selects (a dynamic index into a kernarg struct would go through scratch)
-template <typename T, int N>
-__device__ __forceinline__ T pick_n(const T (&a)[N], int s) {
-  T v = a[0];
-#pragma unroll
-  for (int k = 1; k < N; ++k) v = (s == k) ? a[k] : v;
-  return v;
-}
-
 }  // namespace gcmi
