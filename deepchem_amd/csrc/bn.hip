@@ -24,21 +24,7 @@ constexpr int kReplicas = kBnReplicas;  // accumulator replicas: same-address fp
 // of 2F partial sums.  The kernels that consume the partial sums zero them again, so a scratch
 // that starts clean stays clean (the whole-model path zeroes it once per pass).
 
-// The gradient w.r.t. the readout input, recomputed instead of read (GraphGather backward fused
-// into the BatchNorm backward that consumes it): with g2[m] = [dsum | dmax] of molecule m (tanh
-// derivative already applied) and arg[m,f] = row of the first maximum,
-//   dy[r, f] = g2[mol(r)][f] + (arg[mol(r)][f] == r) * g2[mol(r)][F + f].
-struct ReadoutGrad {
-  const int32_t* membership;  // N
-  const float* g2;            // n_mols x ldg2 (>= 2F)
-  int64_t ldg2;
-  const int32_t* arg;         // n_mols x F
-  // optional: what the column sums need to come from per-molecule data (readout_bn_sums_kernel)
-  const float* rawsum = nullptr;  // n_mols x 2F: [row sums | arg-max row's value] of the BatchNorm input
-  const int32_t* runs = nullptr;  // n_mols x n_deg x 2 row runs
-  int32_t n_mols = 0, n_deg = 0;
-};
-
+// dy[r, c .. c + V) of the readout gradient (common.h: ReadoutGrad)
 template <int V>
 __device__ __forceinline__ void readout_dy(const ReadoutGrad& rg, int64_t r, int c, int n_feat, float (&dy)[V]) {
   const int m = rg.membership[r];
@@ -519,46 +505,13 @@ static int launch_col_sums(int mode, const float* a, int64_t lda, const float* x
   return GCMI_OK;
 }
 
-int bn_stats_impl(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
-                  const float* d_gamma, const float* d_beta, float eps, float momentum,
-                  float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
-                  float* d_scale, float* d_shift, double* d_acc, bool acc_clean, void* stream,
-                  int64_t* d_batches_tracked) {
-  GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && ldx >= n_feat, "bn_stats: bad shape (n_rows=%lld)",
-                 (long long)n_rows);
-  GCMI_CHECK_ARG(d_x && d_scale && d_shift && d_acc, "bn_stats: NULL buffer");
-  hipStream_t st = (hipStream_t)stream;
-  TimedScope ts(GCMI_K_BATCHNORM, st);
-  int rc = launch_col_sums(0, d_x, ldx, nullptr, 0, nullptr, nullptr, n_rows, n_feat, d_acc, acc_clean, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, n_rows,
-                     n_feat, d_gamma, d_beta, eps, momentum, d_running_mean, d_running_var, d_mean,
-                     d_invstd, d_scale, d_shift, d_batches_tracked);
-  GCMI_CHECK_LAUNCH("bn_finalize");
-  return GCMI_OK;
-}
-
-int bn_finalize_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_beta, float eps,
-                     float momentum, float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
-                     float* d_scale, float* d_shift, double* d_acc, void* stream, int64_t* d_batches_tracked) {
-  GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && d_scale && d_shift && d_acc, "bn_finalize: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  TimedScope ts(GCMI_K_BATCHNORM, st);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, n_rows,
-                     n_feat, d_gamma, d_beta, eps, momentum, d_running_mean, d_running_var, d_mean,
-                     d_invstd, d_scale, d_shift, d_batches_tracked);
-  GCMI_CHECK_LAUNCH("bn_finalize");
-  return GCMI_OK;
-}
-
-// ---- synchronised BatchNorm, host side
-static int bn_sync_collapse(double* d_acc, double* d_psums, int64_t n_rows, int32_t n_feat, const float* d_gamma,
-                            const float* d_beta, float* d_dgamma, float* d_dbeta, double* d_xbuf, hipStream_t st,
-                            double* d_loss_acc = nullptr, int loss_rep = 0, float loss_inv_count = 0.f,
-                            float* d_loss = nullptr) {
+// ---- synchronised BatchNorm, host side (BnPoint{n_feat}: a point that is its width alone -- the collapse of forward
+// sums, which writes no gradient and asks no gamma / beta)
+static int bn_sync_collapse(const BnPoint& p, int64_t n_rows, double* d_acc, double* d_psums, double* d_xbuf, hipStream_t st,
+                            const BnBackward::Loss& loss = {}) {
   static_assert(kReplicas == 32, "bn_collapse_kernel: one lane per replica");
-  hipLaunchKernelGGL(bn_collapse_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, d_psums, n_rows, n_feat, d_gamma,
-                     d_beta, d_dgamma, d_dbeta, d_xbuf, d_loss_acc, loss_rep, loss_inv_count, d_loss);
+  hipLaunchKernelGGL(bn_collapse_kernel, dim3((p.n_feat + 7) / 8), dim3(256), 0, st, d_acc, d_psums, n_rows, p.n_feat, p.gamma,
+                     p.beta, p.dgamma, p.dbeta, d_xbuf, loss.acc, loss.rep, loss.inv_count, loss.out);
   GCMI_CHECK_LAUNCH("bn_collapse");
   return GCMI_OK;
 }
@@ -578,60 +531,64 @@ static int bn_sync_exchange(const BnSync& sy, int64_t n_rows, int32_t n_feat, hi
   return GCMI_OK;
 }
 
-static int bn_sync_finalize(const BnSync& sy, int32_t n_feat, const float* d_gamma, const float* d_beta, float eps,
-                            float momentum, float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
-                            float* d_scale, float* d_shift, hipStream_t st, int64_t* d_batches_tracked) {
-  hipLaunchKernelGGL(bn_finalize_sync_kernel, dim3((n_feat + 255) / 256), dim3(256), 0, st, sy.buf, n_feat, d_gamma, d_beta,
-                     eps, momentum, d_running_mean, d_running_var, d_mean, d_invstd, d_scale, d_shift, d_batches_tracked);
+// the one launch of bn_finalize_sync_kernel: the exchanged buffer -> the point's vectors
+static int bn_sync_finalize(const BnPoint& p, const double* d_xbuf, hipStream_t st) {
+  hipLaunchKernelGGL(bn_finalize_sync_kernel, dim3((p.n_feat + 255) / 256), dim3(256), 0, st, d_xbuf, p.n_feat, p.gamma,
+                     p.beta, p.eps, p.momentum, p.running_mean, p.running_var, p.mean, p.invstd, p.scale, p.shift,
+                     p.batches_tracked);
   GCMI_CHECK_LAUNCH("bn_finalize_sync");
   return GCMI_OK;
 }
 
-int bn_stats_sync_impl(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
-                       const float* d_beta, float eps, float momentum, float* d_running_mean, float* d_running_var,
-                       float* d_mean, float* d_invstd, float* d_scale, float* d_shift, double* d_acc, bool sums_ready,
-                       const BnSync& sy, void* stream, int64_t* d_batches_tracked) {
-  GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && d_scale && d_shift && d_acc && sy.fn && sy.buf, "bn_stats_sync: bad arguments");
-  GCMI_CHECK_ARG(n_rows == 0 || sums_ready || (d_x && ldx >= n_feat), "bn_stats_sync: bad rows");
+int bn_train_forward(const BnPoint& p, const BnForward& f, void* stream) {
+  const int32_t n_feat = p.n_feat;
+  if (f.sync) {
+    GCMI_CHECK_ARG(n_feat > 0 && f.n_rows >= 0 && p.scale && p.shift && f.acc && f.sync->fn && f.sync->buf,
+                   "bn_stats_sync: bad arguments");
+    GCMI_CHECK_ARG(f.n_rows == 0 || f.sums_ready || (f.x && f.ldx >= n_feat), "bn_stats_sync: bad rows");
+  } else if (f.sums_ready) {
+    GCMI_CHECK_ARG(n_feat > 0 && f.n_rows > 0 && p.scale && p.shift && f.acc, "bn_finalize: bad arguments");
+  } else {
+    GCMI_CHECK_ARG(n_feat > 0 && f.n_rows > 0 && f.ldx >= n_feat, "bn_stats: bad shape (n_rows=%lld)", (long long)f.n_rows);
+    GCMI_CHECK_ARG(f.x && p.scale && p.shift && f.acc, "bn_stats: NULL buffer");
+  }
   hipStream_t st = (hipStream_t)stream;
   TimedScope ts(GCMI_K_BATCHNORM, st);
   int rc = GCMI_OK;
-  if (n_rows > 0) {
-    if (!sums_ready) rc = launch_col_sums(0, d_x, ldx, nullptr, 0, nullptr, nullptr, n_rows, n_feat, d_acc, true, st);
-    if (rc == GCMI_OK)
-      rc = bn_sync_collapse(d_acc, nullptr, n_rows, n_feat, nullptr, nullptr, nullptr, nullptr, sy.buf, st);
+  if (f.n_rows > 0 && !f.sums_ready)
+    rc = launch_col_sums(0, f.x, f.ldx, nullptr, 0, nullptr, nullptr, f.n_rows, n_feat, f.acc, f.acc_clean, st);
+  if (rc) return rc;
+  if (!f.sync) {  // the one launch of bn_finalize_kernel
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, f.acc, f.n_rows, n_feat, p.gamma, p.beta,
+                       p.eps, p.momentum, p.running_mean, p.running_var, p.mean, p.invstd, p.scale, p.shift, p.batches_tracked);
+    GCMI_CHECK_LAUNCH("bn_finalize");
+    return GCMI_OK;
   }
-  if (rc == GCMI_OK) rc = bn_sync_exchange(sy, n_rows, n_feat, st);
-  if (rc == GCMI_OK)
-    rc = bn_sync_finalize(sy, n_feat, d_gamma, d_beta, eps, momentum, d_running_mean, d_running_var, d_mean, d_invstd,
-                          d_scale, d_shift, st, d_batches_tracked);
-  return rc;
+  if (f.n_rows > 0) rc = bn_sync_collapse(BnPoint{n_feat}, f.n_rows, f.acc, nullptr, f.sync->buf, st);
+  if (rc == GCMI_OK) rc = bn_sync_exchange(*f.sync, f.n_rows, n_feat, st);
+  if (rc) return rc;
+  return bn_sync_finalize(p, f.sync->buf, st);
 }
 
 // The backward after its sums: dgamma / dbeta of this rank, the exchange, the coefficient vectors of the global batch
-// at the head of d_acc.  n_rows == 0: the exchange alone (zero sums, count 0) -- the other ranks wait for it.
-int bn_bwd_sync_finish(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_beta, const float* d_mean,
-                       const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, double* d_psums,
-                       const BnSync& sy, void* stream, double* d_loss_acc, int loss_rep, float loss_inv_count,
-                       float* d_loss) {
-  GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && sy.fn && sy.buf, "bn_bwd_sync: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  if (n_rows == 0) return bn_sync_exchange(sy, 0, n_feat, st);
-  GCMI_CHECK_ARG(d_mean && d_invstd && d_acc, "bn_bwd_sync: NULL buffer");
-  int rc = bn_sync_collapse(d_acc, d_psums, n_rows, n_feat, d_gamma, d_beta, d_dgamma, d_dbeta, sy.buf, st, d_loss_acc,
-                            loss_rep, loss_inv_count, d_loss);
-  if (rc == GCMI_OK) rc = bn_sync_exchange(sy, n_rows, n_feat, st);
-  if (rc != GCMI_OK) return rc;
-  hipLaunchKernelGGL(bn_bwd_coef_sync_kernel, dim3((n_feat + 255) / 256), dim3(256), 0, st, sy.buf, n_feat, d_gamma, d_mean,
-                     d_invstd, reinterpret_cast<float*>(d_acc));
+// at the head of b.acc
+static int bn_bwd_sync_finish(const BnPoint& p, const BnBackward& b, hipStream_t st) {
+  const BnSync& sy = *b.sync;
+  GCMI_CHECK_ARG(p.n_feat > 0 && b.n_rows > 0 && sy.fn && sy.buf, "bn_bwd_sync: bad arguments");
+  GCMI_CHECK_ARG(p.mean && p.invstd && b.acc, "bn_bwd_sync: NULL buffer");
+  int rc = bn_sync_collapse(p, b.n_rows, b.acc, b.psums, sy.buf, st, b.loss);
+  if (rc == GCMI_OK) rc = bn_sync_exchange(sy, b.n_rows, p.n_feat, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_bwd_coef_sync_kernel, dim3((p.n_feat + 255) / 256), dim3(256), 0, st, sy.buf, p.n_feat, p.gamma, p.mean,
+                     p.invstd, reinterpret_cast<float*>(b.acc));
   GCMI_CHECK_LAUNCH("bn_bwd_coef_sync");
   return GCMI_OK;
 }
 
-int bn_bwd_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows,
-                int32_t n_feat, const float* d_gamma, const float* d_mean,
-                const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
-                int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy);
+int bn_bwd_sync_empty(int32_t n_feat, const BnSync& sy, void* stream) {
+  GCMI_CHECK_ARG(n_feat > 0 && sy.fn && sy.buf, "bn_bwd_sync: bad arguments");
+  return bn_sync_exchange(sy, 0, n_feat, (hipStream_t)stream);
+}
 
 }  // namespace gcmi
 
@@ -643,8 +600,13 @@ int gcmi_bn_stats(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
                   const float* d_gamma, const float* d_beta, float eps, float momentum,
                   float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
                   float* d_scale, float* d_shift, double* d_acc, void* stream) {
-  return bn_stats_impl(d_x, ldx, n_rows, n_feat, d_gamma, d_beta, eps, momentum, d_running_mean,
-                       d_running_var, d_mean, d_invstd, d_scale, d_shift, d_acc, false, stream);
+  BnPoint p{n_feat};
+  p.gamma = d_gamma; p.beta = d_beta;
+  p.eps = eps; p.momentum = momentum; p.running_mean = d_running_mean; p.running_var = d_running_var;
+  p.mean = d_mean; p.invstd = d_invstd; p.scale = d_scale; p.shift = d_shift;
+  BnForward f;
+  f.x = d_x; f.ldx = ldx; f.n_rows = n_rows; f.acc = d_acc;
+  return bn_train_forward(p, f, stream);
 }
 
 int gcmi_bn_fold_eval(const float* d_gamma, const float* d_beta, const float* d_running_mean,
@@ -686,8 +648,13 @@ int gcmi_bn_bwd(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, 
                 int32_t n_feat, const float* d_gamma, const float* d_mean,
                 const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
                 int64_t lddx, int32_t relu_mask, double* d_acc, void* stream) {
-  return bn_bwd_impl(d_dy, lddy, d_x, ldx, n_rows, n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta,
-                     d_dx, lddx, relu_mask, d_acc, false, stream, nullptr);
+  BnPoint p{n_feat};
+  p.gamma = d_gamma; p.dgamma = d_dgamma; p.dbeta = d_dbeta;
+  p.mean = const_cast<float*>(d_mean); p.invstd = const_cast<float*>(d_invstd);  // (the backward only reads them)
+  BnBackward b;
+  b.dy = d_dy; b.lddy = lddy; b.x = d_x; b.ldx = ldx; b.n_rows = n_rows; b.acc = d_acc;
+  b.dx = d_dx; b.lddx = lddx; b.relu_mask = relu_mask;
+  return bn_bwd_impl(p, b, stream);
 }
 
 // ---- synchronised BatchNorm in pieces (gcmi.h): what gcmi_model_*_dp runs around its exchange callback
@@ -698,16 +665,18 @@ int gcmi_bn_sync_sums(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_f
   hipStream_t st = (hipStream_t)stream;
   int rc = launch_col_sums(0, d_x, ldx, nullptr, 0, nullptr, nullptr, n_rows, n_feat, d_acc, false, st);
   if (rc) return rc;
-  return bn_sync_collapse(d_acc, nullptr, n_rows, n_feat, nullptr, nullptr, nullptr, nullptr, d_xbuf, st);
+  return bn_sync_collapse(BnPoint{n_feat}, n_rows, d_acc, nullptr, d_xbuf, st);
 }
 
 int gcmi_bn_sync_finalize(const double* d_xbuf, int32_t n_feat, const float* d_gamma, const float* d_beta, float eps,
                           float momentum, float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
                           float* d_scale, float* d_shift, int64_t* d_batches_tracked, void* stream) {
   GCMI_CHECK_ARG(n_feat > 0 && d_xbuf && d_scale && d_shift, "bn_sync_finalize: bad arguments");
-  BnSync sy{nullptr, nullptr, const_cast<double*>(d_xbuf)};
-  return bn_sync_finalize(sy, n_feat, d_gamma, d_beta, eps, momentum, d_running_mean, d_running_var, d_mean, d_invstd,
-                          d_scale, d_shift, (hipStream_t)stream, d_batches_tracked);
+  BnPoint p{n_feat};
+  p.gamma = d_gamma; p.beta = d_beta;
+  p.eps = eps; p.momentum = momentum; p.running_mean = d_running_mean; p.running_var = d_running_var;
+  p.mean = d_mean; p.invstd = d_invstd; p.scale = d_scale; p.shift = d_shift; p.batches_tracked = d_batches_tracked;
+  return bn_sync_finalize(p, d_xbuf, (hipStream_t)stream);
 }
 
 int gcmi_bn_sync_bwd_sums(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
@@ -719,14 +688,18 @@ int gcmi_bn_sync_bwd_sums(const float* d_dy, int64_t lddy, const float* d_x, int
   hipStream_t st = (hipStream_t)stream;
   int rc = launch_col_sums(1, d_dy, lddy, d_x, ldx, d_mean, d_invstd, n_rows, n_feat, d_acc, false, st);
   if (rc) return rc;
-  return bn_sync_collapse(d_acc, nullptr, n_rows, n_feat, d_gamma, nullptr, d_dgamma, d_dbeta, d_xbuf, st);
+  BnPoint p{n_feat};
+  p.gamma = d_gamma; p.dgamma = d_dgamma; p.dbeta = d_dbeta;
+  return bn_sync_collapse(p, n_rows, d_acc, nullptr, d_xbuf, st);
 }
 
 int gcmi_bn_sync_bwd_pool(double* d_psums, double* d_acc, int64_t n_rows, int32_t n_feat, const float* d_gamma,
                           const float* d_beta, float* d_dgamma, float* d_dbeta, double* d_xbuf, void* stream) {
   GCMI_CHECK_ARG(n_feat > 0 && n_rows >= 0 && d_psums && d_acc && d_xbuf && d_gamma && d_beta,
                  "bn_sync_bwd_pool: bad arguments");
-  return bn_sync_collapse(d_acc, d_psums, n_rows, n_feat, d_gamma, d_beta, d_dgamma, d_dbeta, d_xbuf, (hipStream_t)stream);
+  BnPoint p{n_feat};
+  p.gamma = d_gamma; p.beta = d_beta; p.dgamma = d_dgamma; p.dbeta = d_dbeta;
+  return bn_sync_collapse(p, n_rows, d_acc, d_psums, d_xbuf, (hipStream_t)stream);
 }
 
 int gcmi_bn_sync_bwd_coef(const double* d_xbuf, int32_t n_feat, const float* d_gamma, const float* d_mean,
@@ -741,20 +714,6 @@ int gcmi_bn_sync_bwd_coef(const double* d_xbuf, int32_t n_feat, const float* d_g
 }  // extern "C"
 
 namespace gcmi {
-
-static int bn_bwd_any(const ReadoutGrad* rgp, const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx,
-                      int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
-                      const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx, int64_t lddx,
-                      int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy);
-
-int bn_bwd_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows,
-                int32_t n_feat, const float* d_gamma, const float* d_mean,
-                const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
-                int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy) {
-  GCMI_CHECK_ARG(lddy >= n_feat && d_dy, "bn_bwd: bad dy");
-  return bn_bwd_any(nullptr, d_dy, lddy, d_x, ldx, n_rows, n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta,
-                    d_dx, lddx, relu_mask, d_acc, acc_clean, stream, sy);
-}
 
 // BatchNorm backward whose incoming gradient is the GraphGather backward, recomputed on the fly
 // Column sums of the BatchNorm backward behind a GraphGather, from per-molecule data only.  The gradient of a row is
@@ -809,22 +768,6 @@ readout_bn_sums_kernel(int n_mols, int n_feat, int n_deg, const int32_t* __restr
   }
 }
 
-int bn_bwd_readout_impl(const int32_t* d_membership, const float* d_g2, int64_t ldg2, const int32_t* d_arg,
-                        const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
-                        const float* d_mean, const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
-                        int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream,
-                        const float* d_rawsum, const int32_t* d_mol_runs, int32_t n_mols, int32_t n_deg,
-                        const BnSync* sy) {
-  GCMI_CHECK_ARG(d_membership && d_g2 && d_arg && ldg2 >= 2 * (int64_t)n_feat, "bn_bwd_readout: bad readout gradient");
-  ReadoutGrad rg{d_membership, d_g2, ldg2, d_arg};
-  rg.rawsum = d_rawsum;
-  rg.runs = d_mol_runs;
-  rg.n_mols = n_mols;
-  rg.n_deg = n_deg;
-  return bn_bwd_any(&rg, nullptr, 0, d_x, ldx, n_rows, n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta, d_dx,
-                    lddx, relu_mask, d_acc, acc_clean, stream, sy);
-}
-
 // dbeta = sum dy, dgamma = sum dy * xhat and the coefficient vectors, from the pooled sums (psums) or, where those
 // are ill-conditioned, from the direct sums (sums); both accumulators are left clean
 __global__ void bn_bwd_params_pool_kernel(double* __restrict__ psums, double* __restrict__ sums, int64_t n_rows,
@@ -867,58 +810,60 @@ __global__ void bn_bwd_params_pool_kernel(double* __restrict__ psums, double* __
   }
 }
 
-int bn_bwd_pool_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
-                     const float* d_gamma, const float* d_beta, const float* d_mean, const float* d_invstd,
-                     float* d_dgamma, float* d_dbeta, double* d_psums, double* d_acc, void* stream, int32_t x_bf16,
-                     const BnSync* sy) {
-  GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && d_mean && d_invstd && d_acc && d_psums && d_x && d_gamma && d_beta,
+int bn_bwd_pool_impl(const BnPoint& p, const BnBackward& b, void* stream) {
+  const int32_t n_feat = p.n_feat;
+  GCMI_CHECK_ARG(n_feat > 0 && b.n_rows > 0 && p.mean && p.invstd && b.acc && b.psums && b.x && p.gamma && p.beta,
                  "bn_bwd_pool: bad arguments");
   hipStream_t st = (hipStream_t)stream;
   TimedScope ts(GCMI_K_BATCHNORM, st);
-  if (d_dy != nullptr) {
-    const int rc = launch_col_sums(1, d_dy, lddy, d_x, ldx, d_mean, d_invstd, n_rows, n_feat, d_acc, true, st, nullptr,
-                                   d_gamma, d_beta, x_bf16);
+  if (b.dy != nullptr) {
+    const int rc = launch_col_sums(1, b.dy, b.lddy, b.x, b.ldx, p.mean, p.invstd, b.n_rows, n_feat, b.acc, true, st, nullptr,
+                                   p.gamma, p.beta, b.x_bf16);
     if (rc) return rc;
   }
-  if (sy != nullptr)
-    return bn_bwd_sync_finish(n_rows, n_feat, d_gamma, d_beta, d_mean, d_invstd, d_dgamma, d_dbeta, d_acc, d_psums, *sy,
-                              stream, nullptr, 0, 0.f, nullptr);
+  if (b.sync != nullptr) return bn_bwd_sync_finish(p, b, st);
   static_assert(kReplicas == 32, "bn_bwd_params_pool_kernel: one lane per replica");
-  hipLaunchKernelGGL(bn_bwd_params_pool_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_psums, d_acc, n_rows, n_feat, d_gamma,
-                     d_beta, d_mean, d_invstd, d_dgamma, d_dbeta, reinterpret_cast<float*>(d_acc));
+  hipLaunchKernelGGL(bn_bwd_params_pool_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, b.psums, b.acc, b.n_rows, n_feat,
+                     p.gamma, p.beta, p.mean, p.invstd, p.dgamma, p.dbeta, reinterpret_cast<float*>(b.acc));
   GCMI_CHECK_LAUNCH("bn_bwd_params_pool");
   return GCMI_OK;
 }
 
-int bn_bwd_params_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
-                       const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, void* stream,
-                       double* d_loss_acc, int loss_rep, float loss_inv_count, float* d_loss, const BnSync* sy) {
-  GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && d_mean && d_invstd && d_acc, "bn_bwd_params: bad arguments");
-  hipStream_t st = (hipStream_t)stream;
-  TimedScope ts(GCMI_K_BATCHNORM, st);
-  if (sy != nullptr)
-    return bn_bwd_sync_finish(n_rows, n_feat, d_gamma, nullptr, d_mean, d_invstd, d_dgamma, d_dbeta, d_acc, nullptr, *sy,
-                              stream, d_loss_acc, loss_rep, loss_inv_count, d_loss);
-  hipLaunchKernelGGL(bn_bwd_params_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, n_rows, n_feat,
-                     d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta, reinterpret_cast<float*>(d_acc), d_loss_acc, loss_rep,
-                     loss_inv_count, d_loss);
+// the one launch of bn_bwd_params_kernel: dgamma, dbeta and the coefficient vectors (3F floats, in the first 2F doubles
+// of the scratch) from the sums in b.acc
+static int bn_bwd_params(const BnPoint& p, const BnBackward& b, hipStream_t st) {
+  hipLaunchKernelGGL(bn_bwd_params_kernel, dim3((p.n_feat + 7) / 8), dim3(256), 0, st, b.acc, b.n_rows, p.n_feat, p.gamma,
+                     p.mean, p.invstd, p.dgamma, p.dbeta, reinterpret_cast<float*>(b.acc), b.loss.acc, b.loss.rep,
+                     b.loss.inv_count, b.loss.out);
   GCMI_CHECK_LAUNCH("bn_bwd_params");
   return GCMI_OK;
 }
 
-static int bn_bwd_any(const ReadoutGrad* rgp, const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx,
-                      int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
-                      const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx, int64_t lddx,
-                      int32_t relu_mask, double* d_acc, bool acc_clean, void* stream, const BnSync* sy) {
-  GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && ldx >= n_feat, "bn_bwd: bad shape");
-  GCMI_CHECK_ARG(d_x && d_mean && d_invstd && d_acc, "bn_bwd: NULL buffer");
-  GCMI_CHECK_ARG(d_dx == nullptr || lddx >= n_feat, "bn_bwd: bad lddx");
+int bn_bwd_params_impl(const BnPoint& p, const BnBackward& b, void* stream) {
+  GCMI_CHECK_ARG(p.n_feat > 0 && b.n_rows > 0 && p.mean && p.invstd && b.acc, "bn_bwd_params: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_BATCHNORM, st);
+  return b.sync != nullptr ? bn_bwd_sync_finish(p, b, st) : bn_bwd_params(p, b, st);
+}
+
+int bn_bwd_impl(const BnPoint& p, const BnBackward& b, void* stream) {
+  const int32_t n_feat = p.n_feat;
+  const int64_t n_rows = b.n_rows;
+  const ReadoutGrad* rgp = b.rg;
+  if (rgp)
+    GCMI_CHECK_ARG(rgp->membership && rgp->g2 && rgp->arg && rgp->ldg2 >= 2 * (int64_t)n_feat,
+                   "bn_bwd_readout: bad readout gradient");
+  else
+    GCMI_CHECK_ARG(b.lddy >= n_feat && b.dy, "bn_bwd: bad dy");
+  GCMI_CHECK_ARG(n_feat > 0 && n_rows > 0 && b.ldx >= n_feat, "bn_bwd: bad shape");
+  GCMI_CHECK_ARG(b.x && p.mean && p.invstd && b.acc, "bn_bwd: NULL buffer");
+  GCMI_CHECK_ARG(b.dx == nullptr || b.lddx >= n_feat, "bn_bwd: bad lddx");
   hipStream_t st = (hipStream_t)stream;
   TimedScope ts(GCMI_K_BATCHNORM, st);
   int rc = GCMI_OK;
   if (rgp && rgp->rawsum && rgp->runs && rgp->n_mols > 0) {
-    if (!acc_clean &&
-        hipMemsetAsync(d_acc, 0, sizeof(double) * 2 * n_feat * (1 + kReplicas), st) != hipSuccess) {
+    if (!b.acc_clean &&
+        hipMemsetAsync(b.acc, 0, sizeof(double) * 2 * n_feat * (1 + kReplicas), st) != hipSuccess) {
       set_error("bn: memset failed");
       return GCMI_ERR_LAUNCH;
     }
@@ -928,30 +873,22 @@ static int bn_bwd_any(const ReadoutGrad* rgp, const float* d_dy, int64_t lddy, c
     if (jobs < waves) waves = (int)((jobs + chunks - 1) / chunks * chunks);
     const int blocks = (waves + 3) / 4;  // waves beyond `waves` (at most 3) simply walk from a later molecule
     hipLaunchKernelGGL(readout_bn_sums_kernel, dim3(blocks), dim3(256), 0, st, rgp->n_mols, n_feat, rgp->n_deg,
-                       rgp->runs, rgp->g2, rgp->ldg2, rgp->arg, rgp->rawsum, d_x, ldx, d_mean, d_invstd, chunks,
-                       d_acc);
+                       rgp->runs, rgp->g2, rgp->ldg2, rgp->arg, rgp->rawsum, b.x, b.ldx, p.mean, p.invstd, chunks,
+                       b.acc);
     GCMI_CHECK_LAUNCH("readout_bn_sums");
   } else {
-    rc = launch_col_sums(1, d_dy, lddy, d_x, ldx, d_mean, d_invstd, n_rows, n_feat, d_acc, acc_clean, st, rgp);
+    rc = launch_col_sums(1, b.dy, b.lddy, b.x, b.ldx, p.mean, p.invstd, n_rows, n_feat, b.acc, b.acc_clean, st, rgp);
   }
   if (rc) return rc;
-  // coefficient vectors (3F floats) live in the first 2F doubles of the scratch
-  float* coef = reinterpret_cast<float*>(d_acc);
-  if (sy != nullptr) {
-    rc = bn_bwd_sync_finish(n_rows, n_feat, d_gamma, nullptr, d_mean, d_invstd, d_dgamma, d_dbeta, d_acc, nullptr, *sy, stream,
-                            nullptr, 0, 0.f, nullptr);
-    if (rc) return rc;
-  } else {
-    hipLaunchKernelGGL(bn_bwd_params_kernel, dim3((n_feat + 7) / 8), dim3(256), 0, st, d_acc, n_rows,
-                       n_feat, d_gamma, d_mean, d_invstd, d_dgamma, d_dbeta, coef, nullptr, 0, 0.f, nullptr);
-    GCMI_CHECK_LAUNCH("bn_bwd_params");
-  }
-  if (d_dx) {
+  rc = b.sync != nullptr ? bn_bwd_sync_finish(p, b, st) : bn_bwd_params(p, b, st);
+  if (rc) return rc;
+  if (b.dx) {
+    const float* coef = reinterpret_cast<const float*>(b.acc);
     ReadoutGrad rg{nullptr, nullptr, 0, nullptr};
     if (rgp) rg = *rgp;
     const bool src_ok = rgp ? (aligned16(rg.g2) && rg.ldg2 % 4 == 0 && aligned16(rg.arg))
-                            : vec_width(d_dy, lddy, n_feat) == 4;
-    const int V = (vec_width(d_dx, lddx, n_feat) == 4 && src_ok && vec_width(d_x, ldx, n_feat) == 4) ? 4 : 1;
+                            : vec_width(b.dy, b.lddy, n_feat) == 4;
+    const int V = (vec_width(b.dx, b.lddx, n_feat) == 4 && src_ok && vec_width(b.x, b.ldx, n_feat) == 4) ? 4 : 1;
     const int lpr = n_feat / V;
     const int lx = lpr < kBBlock ? lpr : kBBlock;
     const int64_t round_rows = 4 * (kBBlock / lx);
@@ -961,14 +898,14 @@ static int bn_bwd_any(const ReadoutGrad* rgp, const float* d_dy, int64_t lddy, c
     const int blocks = (int)((n_rows + rpb - 1) / rpb);
     const int rev = next_sweep_direction();
 #define LAUNCH_DX(VV, RR, DD)                                                                     \
-  hipLaunchKernelGGL((bn_bwd_dx_kernel<VV, RR, DD>), dim3(blocks), dim3(kBBlock), 0, st, d_dy, lddy, \
-                     d_x, ldx, n_rows, rpb, n_feat, lpr, lx, coef, d_dx, lddx, rg, rev)
+  hipLaunchKernelGGL((bn_bwd_dx_kernel<VV, RR, DD>), dim3(blocks), dim3(kBBlock), 0, st, b.dy, b.lddy, \
+                     b.x, b.ldx, n_rows, rpb, n_feat, lpr, lx, coef, b.dx, b.lddx, rg, rev)
 #define LAUNCH_DX_R(VV, RR) \
   do { if (rgp) LAUNCH_DX(VV, RR, true); else LAUNCH_DX(VV, RR, false); } while (0)
     if (V == 4) {
-      if (relu_mask) LAUNCH_DX_R(4, true); else LAUNCH_DX_R(4, false);
+      if (b.relu_mask) LAUNCH_DX_R(4, true); else LAUNCH_DX_R(4, false);
     } else {
-      if (relu_mask) LAUNCH_DX_R(1, true); else LAUNCH_DX_R(1, false);
+      if (b.relu_mask) LAUNCH_DX_R(1, true); else LAUNCH_DX_R(1, false);
     }
 #undef LAUNCH_DX_R
 #undef LAUNCH_DX

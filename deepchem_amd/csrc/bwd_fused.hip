@@ -724,41 +724,48 @@ static int launch_fused(const SegTable& st, int n_tiles, const FusedArgs& a, hip
   return GCMI_OK;
 }
 
-// GraphConv block: dW_rel += S^T G, dW_self += X^T G, dbsum += colsum G, and (d_ds != nullptr) dS = G W_rel^T,
-// dXs = G W_self^T.  GCMI_ERR_UNSUPPORTED = shape not covered (the caller runs the separate kernels).
-int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_rel,
-                   const int64_t* w_self, const int64_t* b_off, const float* d_dy, int64_t lddy, const float* d_gc,
-                   int64_t ldgc, const float* d_coef, int32_t width, const float* d_s, int64_t lds, const float* d_x,
-                   int64_t ldx, int32_t k_in, const float* d_w, float* d_dw, float* d_dbsum, float* d_ds_out,
-                   int64_t ldds, float* d_dxs_out, int64_t lddxs, double* d_psums, hipStream_t sm, int32_t act_bf16,
-                   int32_t in_bf16) {
-  if (!fused_bwd_enabled() || n_seg > kMaxProductSeg || width != 64) return GCMI_ERR_UNSUPPORTED;
-  // (in_bf16 without act_bf16: d_s and d_x alone point to bf16 rows that hold their values exactly -- the first
-  // GraphConv, which needs no input gradient)
-  if (in_bf16 && (act_bf16 || d_ds_out != nullptr || k_in <= 64 || k_in > 96)) return GCMI_ERR_UNSUPPORTED;
-  {  // 32-bit element offsets inside the kernel: every array below 2^30 elements
-    int64_t rows = 0;
-    for (int sgi = 0; sgi < n_seg; ++sgi) rows = std::max<int64_t>(rows, seg_end[sgi]);
-    const int64_t ldmax = std::max(std::max(lddy, ldgc), std::max(std::max(lds, ldx), std::max(ldds, lddxs)));
-    if (rows * ldmax >= (int64_t)1 << 30) return GCMI_ERR_UNSUPPORTED;
-  }
-  if (!aligned16(d_dy) || lddy % 4 || !aligned16(d_gc) || ldgc % 4) return GCMI_ERR_UNSUPPORTED;
-  if (d_coef && !aligned16(d_coef)) return GCMI_ERR_UNSUPPORTED;
-  // (act_bf16: d_gc, d_s and d_x point to bf16 rows, their leading dimensions count elements; 8-byte pieces)
-  if ((act_bf16 || in_bf16) && (!aligned16(d_s) || lds % 4 || !aligned16(d_x) || ldx % 4)) return GCMI_ERR_UNSUPPORTED;
-  const bool dgrad = d_ds_out != nullptr;
-  SegTable st;
-  const int tiles = (int)fill_seg_table(st, n_seg, seg_begin, seg_end, w_rel, w_self, b_off, kFRows);
-  if (tiles == 0) return GCMI_OK;
+// The narrowing both launchers share: the BlockBackward fields that mean the same for either block
+static FusedArgs fused_args(const BlockBackward& b) {
   FusedArgs a;
   memset(&a, 0, sizeof(a));
-  a.dy = d_dy; a.lddy = (int32_t)lddy; a.x = d_gc; a.ldx = (int32_t)ldgc; a.coef = d_coef;
-  a.in[0] = d_s; a.ldin[0] = (int32_t)lds; a.in[1] = d_x; a.ldin[1] = (int32_t)ldx; a.k_in = k_in;
-  a.w = d_w; a.dw = d_dw; a.db = d_dbsum;
-  a.dout[0] = d_ds_out; a.lddout[0] = (int32_t)ldds; a.dout[1] = d_dxs_out; a.lddout[1] = (int32_t)lddxs;
-  a.psums = dgrad ? d_psums : nullptr;
+  a.dy = b.dy; a.lddy = (int32_t)b.lddy; a.x = b.gc; a.ldx = (int32_t)b.ldgc; a.coef = b.coef;
+  if (b.rg) { a.membership = b.rg->membership; a.g2 = b.rg->g2; a.ldg2 = (int32_t)b.rg->ldg2; a.arg = b.rg->arg; }
+  for (int o = 0; o < 2; ++o) {
+    a.in[o] = b.in[o].rows; a.ldin[o] = (int32_t)b.in[o].ld;
+    a.dout[o] = b.dout[o].rows; a.lddout[o] = (int32_t)b.dout[o].ld;
+  }
+  a.k_in = b.k_in; a.w = b.w; a.dw = b.dw; a.db = b.db;
+  a.psums = b.dout[0].rows ? b.psums : nullptr;
+  return a;
+}
+
+// GraphConv block: dW_rel += S^T G, dW_self += X^T G, dbsum += colsum G, and (dout[0] given) dS = G W_rel^T,
+// dXs = G W_self^T.  GCMI_ERR_UNSUPPORTED = shape not covered (the caller runs the separate kernels).
+int fused_conv_bwd(const BlockBackward& b, hipStream_t sm) {
+  const int32_t k_in = b.k_in, act_bf16 = b.act_bf16, in_bf16 = b.in_bf16;
+  if (!fused_bwd_enabled() || b.n_seg > kMaxProductSeg || b.width != 64 || b.rg != nullptr) return GCMI_ERR_UNSUPPORTED;
+  // (in_bf16 without act_bf16: BlockBackward::in_bf16)
+  if (in_bf16 && (act_bf16 || b.dout[0].rows != nullptr || k_in <= 64 || k_in > 96)) return GCMI_ERR_UNSUPPORTED;
+  {  // 32-bit element offsets inside the kernel: every array below 2^30 elements
+    int64_t rows = 0;
+    for (int sgi = 0; sgi < b.n_seg; ++sgi) rows = std::max<int64_t>(rows, b.seg_end[sgi]);
+    const int64_t ldmax = std::max(std::max(b.lddy, b.ldgc),
+                                   std::max(std::max(b.in[0].ld, b.in[1].ld), std::max(b.dout[0].ld, b.dout[1].ld)));
+    if (rows * ldmax >= (int64_t)1 << 30) return GCMI_ERR_UNSUPPORTED;
+  }
+  if (!aligned16(b.dy) || b.lddy % 4 || !aligned16(b.gc) || b.ldgc % 4) return GCMI_ERR_UNSUPPORTED;
+  if (b.coef && !aligned16(b.coef)) return GCMI_ERR_UNSUPPORTED;
+  // (act_bf16: gc and in point to bf16 rows, their leading dimensions count elements; 8-byte pieces)
+  if ((act_bf16 || in_bf16) && (!aligned16(b.in[0].rows) || b.in[0].ld % 4 || !aligned16(b.in[1].rows) || b.in[1].ld % 4))
+    return GCMI_ERR_UNSUPPORTED;
+  const bool dgrad = b.dout[0].rows != nullptr;
+  SegTable st;
+  const int tiles = (int)fill_seg_table(st, b.n_seg, b.seg_begin, b.seg_end, b.w_off[0], b.w_off[1], b.b_off, kFRows);
+  if (tiles == 0) return GCMI_OK;
+  const FusedArgs a = fused_args(b);
   if (dgrad) {
-    if (k_in % 4 || ldds % 4 || lddxs % 4 || !aligned16(d_ds_out) || !aligned16(d_dxs_out)) return GCMI_ERR_UNSUPPORTED;
+    if (k_in % 4 || b.dout[0].ld % 4 || b.dout[1].ld % 4 || !aligned16(b.dout[0].rows) || !aligned16(b.dout[1].rows))
+      return GCMI_ERR_UNSUPPORTED;
     // (act_bf16 == 2: dy, dS and dXs are bf16 rows too)
     if (k_in > 32 && k_in <= 64)
       return act_bf16 == 2 ? launch_fused<64, 2, 2, false, false, true, true, true>(st, tiles, a, sm)
@@ -779,31 +786,23 @@ int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_e
 }
 
 // Dense layer behind the GraphGather: dy recomputed from the per-molecule gradient, dW (n_out x k_in, nn.Linear
-// layout) += G^T P, db += colsum G, dP = G W.
-int fused_dense_bwd(int64_t n_rows, const int32_t* d_membership, const float* d_g2, int64_t ldg2,
-                    const int32_t* d_arg, const float* d_dense, int64_t ldd, const float* d_coef, int32_t width,
-                    const float* d_p, int64_t ldp, int32_t k_in, const float* d_w, float* d_dw, float* d_db,
-                    float* d_dp, int64_t lddp, double* d_psums, hipStream_t sm, int32_t act_bf16) {
-  if (!fused_bwd_enabled() || width != 128 || k_in <= 32 || k_in > 64 || d_coef == nullptr) return GCMI_ERR_UNSUPPORTED;
-  if (!aligned16(d_g2) || ldg2 % 4 || !aligned16(d_arg) || !aligned16(d_dense) || ldd % 4 || !aligned16(d_coef))
+// layout) += G^T P, db += colsum G, dP = G W.  One segment, its rows from 0.
+int fused_dense_bwd(const BlockBackward& b, hipStream_t sm) {
+  const int32_t k_in = b.k_in, act_bf16 = b.act_bf16;
+  if (!fused_bwd_enabled() || b.width != 128 || k_in <= 32 || k_in > 64 || b.coef == nullptr) return GCMI_ERR_UNSUPPORTED;
+  if (b.rg == nullptr || b.n_seg != 1 || b.seg_begin[0] != 0) return GCMI_ERR_UNSUPPORTED;
+  const ReadoutGrad& rg = *b.rg;
+  const int64_t n_rows = b.seg_end[0], ldd = b.ldgc, ldp = b.in[0].ld, lddp = b.dout[0].ld;
+  if (!aligned16(rg.g2) || rg.ldg2 % 4 || !aligned16(rg.arg) || !aligned16(b.gc) || ldd % 4 || !aligned16(b.coef))
     return GCMI_ERR_UNSUPPORTED;
-  if (n_rows <= 0 || n_rows > INT32_MAX || k_in % 4 || lddp % 4 || !aligned16(d_dp)) return GCMI_ERR_UNSUPPORTED;
-  if (n_rows * std::max<int64_t>(std::max(ldd, ldg2), std::max(ldp, lddp)) >= (int64_t)1 << 30) return GCMI_ERR_UNSUPPORTED;
-  const int32_t zero = 0, nn = (int32_t)n_rows;
-  const int64_t off0 = 0;
+  if (n_rows <= 0 || k_in % 4 || lddp % 4 || !aligned16(b.dout[0].rows)) return GCMI_ERR_UNSUPPORTED;
+  if (n_rows * std::max<int64_t>(std::max(ldd, rg.ldg2), std::max(ldp, lddp)) >= (int64_t)1 << 30) return GCMI_ERR_UNSUPPORTED;
   SegTable st;
-  const int tiles = (int)fill_seg_table(st, 1, &zero, &nn, &off0, nullptr, &off0, kFRows);
-  FusedArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = d_dense; a.ldx = (int32_t)ldd; a.coef = d_coef;
-  a.membership = d_membership; a.g2 = d_g2; a.ldg2 = (int32_t)ldg2; a.arg = d_arg;
-  a.in[0] = d_p; a.ldin[0] = (int32_t)ldp; a.k_in = k_in;
-  a.w = d_w; a.dw = d_dw; a.db = d_db;
-  a.dout[0] = d_dp; a.lddout[0] = (int32_t)lddp;
-  a.psums = d_psums;
-  if (act_bf16) {  // d_dense and d_p point to bf16 rows
-    if (!aligned16(d_p) || ldp % 4) return GCMI_ERR_UNSUPPORTED;
-    if (act_bf16 == 2) return launch_fused<128, 2, 1, true, true, true, true, true>(st, tiles, a, sm);  // d_dp: bf16 rows
+  const int tiles = (int)fill_seg_table(st, 1, b.seg_begin, b.seg_end, b.w_off[0], nullptr, b.b_off, kFRows);
+  const FusedArgs a = fused_args(b);
+  if (act_bf16) {  // gc and in[0] point to bf16 rows
+    if (!aligned16(b.in[0].rows) || ldp % 4) return GCMI_ERR_UNSUPPORTED;
+    if (act_bf16 == 2) return launch_fused<128, 2, 1, true, true, true, true, true>(st, tiles, a, sm);  // dout[0]: bf16 rows
     return launch_fused<128, 2, 1, true, true, true, true>(st, tiles, a, sm);
   }
   return launch_fused<128, 2, 1, true, true, true>(st, tiles, a, sm);

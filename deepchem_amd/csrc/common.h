@@ -87,26 +87,12 @@ int win_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, i
 bool win_two_stage_usable(const gcmi_graph* g, int n_feat);
 int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int n_feat, float* d_dxs,
                               int64_t lddxs, const uint8_t* d_arg, float* d_dy, int64_t lddy, hipStream_t st);
-// BatchNorm backward from the sums sum dP, sum dP * P over the rows of the block ABOVE (bwd_fused.hip: psums), with
-// P = max over neighbours of the BatchNorm output y = gamma * xhat + beta: sum dy = sum dP and
-// sum dy * xhat = (sum dP * P - beta * sum dP) / gamma, no pass over dy.  Where that division is ill-conditioned
-// (|beta| > 64 |gamma| in some column) the direct column sums are taken instead: the kernels that are only needed
-// for them (column sums; in reference mode also the GraphPool backward) are launched every time and return at once
-// unless the test below says so.  d_dy may be NULL when the caller never produces it (then the direct sums are too).
-int bn_bwd_pool_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat,
-                     const float* d_gamma, const float* d_beta, const float* d_mean, const float* d_invstd,
-                     float* d_dgamma, float* d_dbeta, double* d_psums, double* d_acc, void* stream, int32_t x_bf16 = 0,
-                     const struct BnSync* sy = nullptr);
+// the GraphPool backward that returns at once unless the pooled BatchNorm sums are ill-conditioned (BnBackward::psums)
 int win_gather_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
                               float* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, hipStream_t st);
-// the part of the BatchNorm backward after its column sums (dgamma, dbeta, coefficient vectors at the head of d_acc)
-// (d_loss_acc: also *d_loss = inv_count * sum of the loss_rep accumulator replicas, cleared -- loss_finalize_impl folded in)
-int bn_bwd_params_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_mean,
-                       const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, void* stream,
-                       double* d_loss_acc = nullptr, int loss_rep = 0, float loss_inv_count = 0.f, float* d_loss = nullptr,
-                       const struct BnSync* sy = nullptr);
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline int64_t up4(int64_t n) { return (n + 3) / 4 * 4; }  // floats of a 16-byte aligned block
+inline int64_t up8(int64_t n) { return (n + 7) / 8 * 8; }  // bf16 elements of one
 
 // ---- One segmented forward product,
 //     out[rows of s] = act(a1[rows of s] . w1[s] + a2[rows of s] . w2[s] + bias[s])      for the row segments s,
@@ -223,6 +209,147 @@ inline int64_t fill_seg_table(SegTable& st, const SegProduct<TA, TO>& p, int til
   return fill_seg_table(st, p.n_seg, p.seg_begin, p.seg_end, p.op[0].a ? p.op[0].w_off : nullptr,
                         p.op[1].a ? p.op[1].w_off : nullptr, p.bias ? p.bias_off : nullptr, tile_rows);
 }
+
+// ---- The backward half of the step and every BatchNorm entry point, as their launchers are handed them (bn.hip,
+// bwd_fused.hip, head_bwd.hip).  Host side only: what a kernel takes by value, its launcher builds from these.
+
+// Synchronised BatchNorm (gcmi_model_*_dp): with a BnSync the backward entries below, after their sums, write THIS
+// rank's dgamma / dbeta, exchange [sum dy | sum dy xhat | rows] through the callback and make the coefficient vectors
+// of the global batch; the forward exchanges [sum x | sum x^2 | rows] the same way.  A rank without rows
+// (n_rows == 0) takes part in every exchange with zero sums.  buf: 2F + 1 doubles.
+struct BnSync {
+  gcmi_stat_sync_fn fn;
+  void* ctx;
+  double* buf;
+};
+
+// One BatchNorm point: nn.BatchNorm1d(n_feat) and where its vectors live
+struct BnPoint {
+  int32_t n_feat = 0;
+  const float *gamma = nullptr, *beta = nullptr;  // nullptr: 1 and 0
+  float *dgamma = nullptr, *dbeta = nullptr;      // gradients (optional); synchronised: THIS rank's sums
+  float *mean = nullptr, *invstd = nullptr;  // this batch's statistics: written by the forward (optional there), read by the backward
+  float *scale = nullptr, *shift = nullptr;  // the folded map y = scale * x + shift, for the kernel that reads the rows next
+  float *running_mean = nullptr, *running_var = nullptr;  // optional
+  int64_t* batches_tracked = nullptr;  // optional: num_batches_tracked, bumped by the finalising launch
+  float eps = 0.f, momentum = 0.f;
+};
+
+// The gradient w.r.t. the readout input, recomputed instead of read (GraphGather backward fused into its consumer):
+// with g2[m] = [dsum | dmax] of molecule m (tanh derivative already applied) and arg[m,f] = row of the first maximum,
+//   dy[r, f] = g2[mol(r)][f] + (arg[mol(r)][f] == r) * g2[mol(r)][F + f].
+// Built once per backward; passed BY VALUE to col_sums_kernel and bn_bwd_dx_kernel (bn.hip): the layout is theirs.
+struct ReadoutGrad {
+  const int32_t* membership;  // N
+  const float* g2;            // n_mols x ldg2 (>= 2F)
+  int64_t ldg2;
+  const int32_t* arg;         // n_mols x F
+  // optional: what the column sums need to come from per-molecule data (readout_bn_sums_kernel)
+  const float* rawsum = nullptr;  // n_mols x 2F: [row sums | arg-max row's value] of the BatchNorm input
+  const int32_t* runs = nullptr;  // n_mols x n_deg x 2 row runs
+  int32_t n_mols = 0, n_deg = 0;
+};
+
+// The training forward of a point: the column sums of the rows (or the sums a product's epilogue left in acc),
+// finalised into mean / invstd / scale / shift and the running statistics.  Three routes, each with the argument checks
+// it always had: a pass over the rows; sums_ready (n_rows > 0 either way); sync, where n_rows == 0 is a rank that
+// only takes part in the exchange.
+struct BnForward {
+  const float* x = nullptr;  // rows, n_rows x ldx; not read when sums_ready
+  int64_t ldx = 0;
+  bool sums_ready = false;   // acc already holds sum x, sum x^2 (seg_gemm_stats, fwd_h_gemm)
+  int64_t n_rows = 0;
+  double* acc = nullptr;     // GCMI_BN_ACC_DOUBLES(n_feat) doubles
+  bool acc_clean = false;    // the caller guarantees zeroed accumulators (the whole-model path zeroes its scratch once
+                             // per pass instead of once per call); they are left clean either way
+  const BnSync* sync = nullptr;
+};
+int bn_train_forward(const BnPoint& p, const BnForward& f, void* stream);
+
+// One call's worth of BatchNorm backward over a point: dgamma, dbeta, the coefficient vectors [A | B | C] at the head
+// of acc (bn.hip: dx = A dy + B x + C) and, with dx, the input gradient.
+struct BnBackward {
+  const float* dy = nullptr;  // the incoming gradient rows (bn_bwd_pool_impl: nullptr when the caller never produces
+  int64_t lddy = 0;           // them), or
+  const ReadoutGrad* rg = nullptr;  // the readout gradient they are recomputed from (then dy is not read)
+  const float* x = nullptr;   // the BatchNorm input
+  int64_t ldx = 0;
+  int32_t x_bf16 = 0;         // bn_bwd_pool_impl only: x (1) or x and dy (2) are bf16 rows, leading dimensions in elements
+  int64_t n_rows = 0;
+  float* dx = nullptr;        // optional (bn_bwd_impl only)
+  int64_t lddx = 0;
+  int32_t relu_mask = 0;      // x is a ReLU output and dx is wanted w.r.t. the ReLU input
+  double* acc = nullptr;      // as BnForward's
+  bool acc_clean = false;
+  // bn_bwd_pool_impl: the sums sum dP, sum dP * P over the rows of the block ABOVE (bwd_fused.hip: psums), with
+  // P = max over neighbours of the BatchNorm output y = gamma * xhat + beta: sum dy = sum dP and
+  // sum dy * xhat = (sum dP * P - beta * sum dP) / gamma, no pass over dy.  Where that division is ill-conditioned
+  // (|beta| > 64 |gamma| in some column) the direct column sums are taken instead: the kernels that are only needed
+  // for them (column sums; in reference mode also the GraphPool backward) are launched every time and return at once
+  // unless that test says so.  Without dy the direct sums are missing too.
+  double* psums = nullptr;
+  const BnSync* sync = nullptr;
+  // bn_bwd_params_impl: also *out = inv_count * sum of the rep accumulator replicas, cleared (loss_finalize_impl
+  // folded into the launch that follows the head kernel anyway; synchronised: this rank's own, in the collapse launch)
+  struct Loss { double* acc = nullptr; int rep = 0; float inv_count = 0.f; float* out = nullptr; } loss;
+};
+// sums from a pass over dy (or the readout gradient: from per-molecule data where rg has rawsum and runs), then dx
+int bn_bwd_impl(const BnPoint& p, const BnBackward& b, void* stream);
+// sums from psums (see there); no dx
+int bn_bwd_pool_impl(const BnPoint& p, const BnBackward& b, void* stream);
+// the part after the column sums, which are in acc already (head_bwd.hip left them); no dx
+int bn_bwd_params_impl(const BnPoint& p, const BnBackward& b, void* stream);
+// the backward of a rank without rows: the exchange alone (zero sums, count 0) -- the other ranks wait for it
+int bn_bwd_sync_empty(int32_t n_feat, const BnSync& sy, void* stream);
+
+// One block's backward in one pass over its rows (bwd_fused.hip): the host-side counterpart of FusedArgs, leading
+// dimensions 64-bit (the launchers narrow them and refuse rows x ld >= 2^30).  G = the gradient w.r.t. the block's
+// pre-activation, formed per tile from the gradient source, gc and coef.
+struct BlockBackward {
+  // row segments; w_off / b_off: per segment into w / dw and into db (a nullptr array or an entry < 0: absent).  The
+  // dense layer: one segment of [0, *seg_end) as one_segment makes it for products -- *seg_end must outlive this
+  int32_t n_seg = 0;
+  const int32_t *seg_begin = nullptr, *seg_end = nullptr;
+  const int64_t* w_off[2] = {nullptr, nullptr};  // GraphConv: W_rel[d] against in[0], W_self[d] against in[1]
+  const int64_t* b_off = nullptr;
+  const float* dy = nullptr;        // the gradient source: rows (GraphConv), or
+  int64_t lddy = 0;
+  const ReadoutGrad* rg = nullptr;  // the readout gradient (the dense layer behind the GraphGather)
+  const float* gc = nullptr;    // the block's ReLU output = its BatchNorm's input
+  int64_t ldgc = 0;
+  const float* coef = nullptr;  // [A | B | C] of that BatchNorm's backward; nullptr (GraphConv only): G = relu'(gc) * dy
+  int32_t width = 0;            // columns of G
+  struct In { const float* rows = nullptr; int64_t ld = 0; } in[2];  // GraphConv: S and X; dense: the pooled rows
+  int32_t k_in = 0;
+  const float* w = nullptr;
+  float* dw = nullptr;          // += In^T G (dense: G^T In, nn.Linear layout)
+  float* db = nullptr;          // += colsum G per segment
+  struct Out { float* rows = nullptr; int64_t ld = 0; } dout[2];  // G W^T: dS, the self part of dX; dense: dP.  nullptr: not wanted
+  double* psums = nullptr;      // optional, with dout: sum dP, sum dP * P for the BatchNorm of the block below
+  int32_t act_bf16 = 0;         // gc and in are bf16 rows, leading dimensions in elements (2: dy and dout too)
+  int32_t in_bf16 = 0;          // without act_bf16: in[] alone are bf16 rows that hold their values exactly -- the
+                                // first GraphConv, which needs no input gradient
+};
+
+// head_bwd.hip: loss + d logits + task-head gradients + tanh' of the readout + the dense BatchNorm's backward sums in
+// one kernel over the molecules (<= 32 outputs), or two on the matrix cores (33..256 outputs)
+struct HeadBackward {
+  int32_t kind = 0;  // 0 softmax cross-entropy, 1 L2
+  const float *logits = nullptr, *labels = nullptr, *weights = nullptr;
+  int64_t n_rows = 0;  // molecules that carry a loss
+  int32_t n_tasks = 0, n_classes = 0;
+  const float* fp = nullptr;  // the fingerprint, rg->n_mols x ldfp
+  int64_t ldfp = 0;
+  const float* w = nullptr;   // head weights (nn.Linear), and their gradients:
+  float *dw = nullptr, *db = nullptr;
+  const ReadoutGrad* rg = nullptr;    // n_mols, ldg2, and for the sums runs, n_deg, arg, rawsum
+  float* g2 = nullptr;                // written: the rows rg->g2 names
+  double* loss_acc = nullptr;         // kLossRep replicas, added into
+  const BnPoint* dense_bn = nullptr;  // the dense layer's: its width, and mean / invstd for the sums
+  double* sums = nullptr;             // optional: that BatchNorm's backward sums, added into this accumulator
+  float* dl_scratch = nullptr;        // more than 32 outputs: n_mols x outputs floats, and
+  float* img = nullptr;               // kHeadImgFloats floats, filled with head_prep's images of w first
+};
 
 // row slabs of the weight-gradient kernels (gemm.hip, gemm_split.hip): slabs instead of tiles, other offsets
 constexpr int kMaxSegW = 16;
@@ -387,31 +514,17 @@ int get_fused_bwd();
 bool fused_bwd_enabled();
 int fused_bwd_launches();  // launches of the one-pass kernel so far (tests)
 int one_piece_launches();  // model.hip: launches of the first block's one-piece forward product and backward so far
-int fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_rel,
-                   const int64_t* w_self, const int64_t* b_off, const float* d_dy, int64_t lddy, const float* d_gc,
-                   int64_t ldgc, const float* d_coef, int32_t width, const float* d_s, int64_t lds, const float* d_x,
-                   int64_t ldx, int32_t k_in, const float* d_w, float* d_dw, float* d_dbsum, float* d_ds_out,
-                   int64_t ldds, float* d_dxs_out, int64_t lddxs, double* d_psums, hipStream_t sm, int32_t act_bf16 = 0,
-                   int32_t in_bf16 = 0);
-int fused_dense_bwd(int64_t n_rows, const int32_t* d_membership, const float* d_g2, int64_t ldg2,
-                    const int32_t* d_arg, const float* d_dense, int64_t ldd, const float* d_coef, int32_t width,
-                    const float* d_p, int64_t ldp, int32_t k_in, const float* d_w, float* d_dw, float* d_db,
-                    float* d_dp, int64_t lddp, double* d_psums, hipStream_t sm, int32_t act_bf16 = 0);
+// (GraphConv block: dW_rel += S^T G, dW_self += X^T G, dbsum += colsum G, and with dout dS = G W_rel^T, dXs = G W_self^T;
+// dense layer behind the GraphGather: dW += G^T P, db += colsum G, dP = G W)
+int fused_conv_bwd(const BlockBackward& b, hipStream_t sm);
+int fused_dense_bwd(const BlockBackward& b, hipStream_t sm);
 
 // fwd_fused.hip: the forward product of a block as persistent workgroups with resident weight images (split-bf16 mode,
 // shapes: fwd_shape above); GCMI_ERR_UNSUPPORTED = shape not covered
 int fwd_fused_gemm(const SegProduct<float>& p, double* d_stats, hipStream_t sm, float* d_wimg_scratch = nullptr);
 
-// head_bwd.hip: loss + d logits + task-head gradients + tanh' of the readout + the dense BatchNorm's backward sums in
-// one kernel over the molecules (<= 32 outputs), or two on the matrix cores (33..256 outputs, d_dl_scratch = n_mols x
-// outputs floats, d_img = kHeadImgFloats floats that it fills with head_prep's images of d_w first);
-// GCMI_ERR_UNSUPPORTED = shape not covered (256-column fingerprint)
-int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights, int64_t n_rows,
-                   int32_t n_tasks, int32_t n_classes, int64_t n_mols, const float* d_fp, int64_t ldfp,
-                   const float* d_w, float* d_dw, float* d_db, float* d_g2, int64_t ldg2, double* d_loss_acc,
-                   const int32_t* d_runs, int32_t n_deg, const int32_t* d_arg, const float* d_rawsum,
-                   const float* d_mean, const float* d_invstd, double* d_sums, int32_t dense_width, hipStream_t st,
-                   float* d_dl_scratch = nullptr, float* d_img = nullptr);
+// head_bwd.hip (HeadBackward above); GCMI_ERR_UNSUPPORTED = shape not covered (256-column fingerprint)
+int head_bwd_fused(const HeadBackward& h, hipStream_t st);
 // ... and the forward head with 33..256 outputs (one segment, 256-column rows, nn.Linear weight, no activation); d_img:
 // the fragment images head_prep made of d_w (kHeadImgFloats floats: forward order, then backward order), or nullptr
 constexpr int kHeadImgFloats = 2 * 8 * 16 * 3 * 64 * 4;
@@ -435,46 +548,9 @@ int seg_gemm_stats(const SegProduct<float>& p, double* d_stats, bool* fused, hip
 int readout_fwd_impl(const gcmi_graph* g, const float* d_x, int64_t ldx, int32_t n_feat, const float* d_scale,
                      const float* d_shift, int32_t act, float* d_out, int64_t ldo, int32_t* d_arg, float* d_rawsum,
                      void* stream, int32_t x_bf16 = 0);
-// the part of bn_stats_impl after the column sums
-int bn_finalize_impl(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_beta, float eps,
-                     float momentum, float* d_running_mean, float* d_running_var, float* d_mean, float* d_invstd,
-                     float* d_scale, float* d_shift, double* d_acc, void* stream, int64_t* d_batches_tracked = nullptr);
-
-// BatchNorm / loss with a caller-guaranteed clean accumulator scratch (bn.hip, loss.hip): the
-// whole-model path zeroes its scratch once per pass instead of once per call.
-int bn_stats_impl(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
-                  const float* d_beta, float eps, float momentum, float* d_running_mean,
-                  float* d_running_var, float* d_mean, float* d_invstd, float* d_scale, float* d_shift,
-                  double* d_acc, bool acc_clean, void* stream, int64_t* d_batches_tracked = nullptr);
-int bn_bwd_impl(const float* d_dy, int64_t lddy, const float* d_x, int64_t ldx, int64_t n_rows,
-                int32_t n_feat, const float* d_gamma, const float* d_mean, const float* d_invstd,
-                float* d_dgamma, float* d_dbeta, float* d_dx, int64_t lddx, int32_t relu_mask,
-                double* d_acc, bool acc_clean, void* stream, const struct BnSync* sy = nullptr);
-int bn_bwd_readout_impl(const int32_t* d_membership, const float* d_g2, int64_t ldg2, const int32_t* d_arg,
-                        const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
-                        const float* d_mean, const float* d_invstd, float* d_dgamma, float* d_dbeta, float* d_dx,
-                        int64_t lddx, int32_t relu_mask, double* d_acc, bool acc_clean, void* stream,
-                        const float* d_rawsum = nullptr, const int32_t* d_mol_runs = nullptr, int32_t n_mols = 0,
-                        int32_t n_deg = 0, const struct BnSync* sy = nullptr);
-// Synchronised BatchNorm (gcmi_model_*_dp): with a BnSync the four backward calls above, after their sums, write THIS
-// rank's dgamma / dbeta, exchange [sum dy | sum dy xhat | rows] through the callback and make the coefficient vectors
-// of the global batch; the forward is bn_stats_sync_impl (sums_ready: a product's epilogue left them in d_acc).  A rank
-// without rows (n_rows == 0) takes part in every exchange with zero sums.  buf: 2F + 1 doubles.
-struct BnSync {
-  gcmi_stat_sync_fn fn;
-  void* ctx;
-  double* buf;
-};
-int bn_stats_sync_impl(const float* d_x, int64_t ldx, int64_t n_rows, int32_t n_feat, const float* d_gamma,
-                       const float* d_beta, float eps, float momentum, float* d_running_mean, float* d_running_var,
-                       float* d_mean, float* d_invstd, float* d_scale, float* d_shift, double* d_acc, bool sums_ready,
-                       const BnSync& sy, void* stream, int64_t* d_batches_tracked);
-int bn_bwd_sync_finish(int64_t n_rows, int32_t n_feat, const float* d_gamma, const float* d_beta, const float* d_mean,
-                       const float* d_invstd, float* d_dgamma, float* d_dbeta, double* d_acc, double* d_psums,
-                       const BnSync& sy, void* stream, double* d_loss_acc, int loss_rep, float loss_inv_count,
-                       float* d_loss);
 int readout_grad_prep(float* d_g, int64_t ldg, const float* d_out, int64_t ldo, int64_t n_mols, int n_feat,
                       hipStream_t st);
+// (acc_clean: as BnForward's)
 int loss_impl(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights,
               int64_t n_rows, int32_t n_tasks, int32_t n_classes, float* d_loss, float* d_dlogits,
               float* d_probs, double* d_acc, bool acc_clean, void* stream);

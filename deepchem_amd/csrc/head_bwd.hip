@@ -905,29 +905,31 @@ int head_fwd_wide(const float* d_in, int64_t ldin, int64_t n_rows, int32_t k, co
 }
 
 // GCMI_ERR_UNSUPPORTED: other widths than a 256-column fingerprint; more than 32 task outputs unless head_wide() and
-// there are d_dl_scratch (n_mols x outputs floats) and d_img (room for the images, which are made here of d_w: what a
+// there are dl_scratch (n_mols x outputs floats) and img (room for the images, which are made here of w: what a
 // forward left there may be of other weights, or nothing)
-int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights, int64_t n_rows,
-                   int32_t n_tasks, int32_t n_classes, int64_t n_mols, const float* d_fp, int64_t ldfp,
-                   const float* d_w, float* d_dw, float* d_db, float* d_g2, int64_t ldg2, double* d_loss_acc,
-                   const int32_t* d_runs, int32_t n_deg, const int32_t* d_arg, const float* d_rawsum,
-                   const float* d_mean, const float* d_invstd, double* d_sums, int32_t dense_width, hipStream_t st,
-                   float* d_dl_scratch, float* d_img) {
+int head_bwd_fused(const HeadBackward& h, hipStream_t st) {
   static const bool on = !(getenv("GCMI_FUSED_HEAD") && atoi(getenv("GCMI_FUSED_HEAD")) == 0);
-  const int tc = n_tasks * (kind == 0 ? n_classes : 1);
-  if (!on || !fused_bwd_enabled() || 2 * dense_width != kHB || tc < 1 || n_mols <= 0) return GCMI_ERR_UNSUPPORTED;
-  const bool wide = head_wide(tc) && d_dl_scratch != nullptr && d_img != nullptr && ldfp % 4 == 0 && aligned16(d_fp) &&
+  if (h.rg == nullptr || h.dense_bn == nullptr) return GCMI_ERR_UNSUPPORTED;
+  const ReadoutGrad& rg = *h.rg;
+  const int64_t n_mols = rg.n_mols;
+  const float *d_fp = h.fp, *d_w = h.w;
+  float *d_dw = h.dw, *d_db = h.db, *d_dl_scratch = h.dl_scratch, *d_img = h.img;
+  const int tc = h.n_tasks * (h.kind == 0 ? h.n_classes : 1);
+  if (!on || !fused_bwd_enabled() || 2 * h.dense_bn->n_feat != kHB || tc < 1 || n_mols <= 0) return GCMI_ERR_UNSUPPORTED;
+  const bool wide = head_wide(tc) && d_dl_scratch != nullptr && d_img != nullptr && h.ldfp % 4 == 0 && aligned16(d_fp) &&
                     aligned16(d_w) && aligned16(d_img);
   if (!wide && tc > kHT) return GCMI_ERR_UNSUPPORTED;  // (the caller runs the separate launches)
-  if (d_sums != nullptr && (!d_runs || !d_arg || !d_rawsum || !d_mean || !d_invstd)) return GCMI_ERR_UNSUPPORTED;
+  if (h.sums != nullptr && (!rg.runs || !rg.arg || !rg.rawsum || !h.dense_bn->mean || !h.dense_bn->invstd))
+    return GCMI_ERR_UNSUPPORTED;
   HeadArgs a;
   memset(&a, 0, sizeof(a));
-  a.kind = kind; a.n_tasks = n_tasks; a.n_classes = kind == 0 ? n_classes : 1; a.tc = tc;
-  a.n_rows = n_rows; a.n_mols = n_mols; a.inv_count = 1.f / (float)(n_rows * n_tasks);
-  a.logits = d_logits; a.labels = d_labels; a.weights = d_weights; a.fp = d_fp; a.ldfp = ldfp;
-  a.w = d_w; a.dw = d_dw; a.db = d_db; a.g2 = d_g2; a.ldg2 = ldg2; a.loss_acc = d_loss_acc;
-  a.runs = d_runs; a.n_deg = n_deg; a.arg = d_arg; a.rawsum = d_rawsum; a.mean = d_mean; a.invstd = d_invstd;
-  a.sums = d_sums;
+  a.kind = h.kind; a.n_tasks = h.n_tasks; a.n_classes = h.kind == 0 ? h.n_classes : 1; a.tc = tc;
+  a.n_rows = h.n_rows; a.n_mols = n_mols; a.inv_count = 1.f / (float)(h.n_rows * h.n_tasks);
+  a.logits = h.logits; a.labels = h.labels; a.weights = h.weights; a.fp = d_fp; a.ldfp = h.ldfp;
+  a.w = d_w; a.dw = d_dw; a.db = d_db; a.g2 = h.g2; a.ldg2 = rg.ldg2; a.loss_acc = h.loss_acc;
+  a.runs = rg.runs; a.n_deg = rg.n_deg; a.arg = rg.arg; a.rawsum = rg.rawsum; a.mean = h.dense_bn->mean;
+  a.invstd = h.dense_bn->invstd;
+  a.sums = h.sums;
   if (wide) {
     constexpr size_t shmem = sizeof(unsigned short) * 3 * kHM * kWP + sizeof(float) * (2 * kHM * kHB + kHM * (kHB / 2));
     static LdsLimit lim;
@@ -945,7 +947,7 @@ int head_bwd_fused(int32_t kind, const float* d_logits, const float* d_labels, c
     const int rps = (int)(((n_mols + slabs - 1) / slabs + 31) / 32 * 32);
     slabs = (n_mols + rps - 1) / rps;
     hipLaunchKernelGGL(head_wgrad_wide_kernel, dim3((unsigned)slabs, (unsigned)((tc + 63) / 64), 4), dim3(256), 0, st,
-                       d_dl_scratch, tc, d_fp, (int)ldfp, n_mols, rps, d_dw, d_db);
+                       d_dl_scratch, tc, d_fp, (int)h.ldfp, n_mols, rps, d_dw, d_db);
     GCMI_CHECK_LAUNCH("head_wgrad_wide");
     HD_PRINT("wgrad_wide", 1, st);
     return GCMI_OK;

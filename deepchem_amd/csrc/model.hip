@@ -71,8 +71,6 @@ __global__ void bump_counters_kernel(CounterPtrs c) {
   if (i < c.n && c.p[i] != nullptr) *c.p[i] += 1;
 }
 
-static inline int64_t up4(int64_t n) { return (n + 3) / 4 * 4; }
-
 // Workspace carve-up (floats).  Everything the backward needs from the forward, plus the
 // backward's temporaries.  All blocks start 16-byte aligned.
 struct Ws {
@@ -88,8 +86,6 @@ struct Ws {
   int64_t dlogits, dbsum[kMaxL], lacc, acc, acc2, z_end;
   int64_t xch;   // synchronised BatchNorm: the exchange buffer of one BatchNorm point, 2 wmax + 1 doubles (bn.hip)
 };
-
-static inline int64_t up8(int64_t n) { return (n + 7) / 8 * 8; }
 
 constexpr int64_t kOnePieceLd = 80;  // elements of a bf16 row of S0 / Xb in the first block's one-piece form
 
@@ -287,14 +283,10 @@ int one_piece_launches() { return g_one_piece_launches.load(std::memory_order_re
 struct Block {
   int K, W;                       // input / output columns
   const float *w, *bias;          // bias: the rows the product adds (GraphConv: the per-degree sums pack_biases left)
-  const float *gamma, *beta;      // nullptr without BatchNorm, as everything BatchNorm below
   float *dw, *dbias;              // gradients; nullptr in the forward.  dbias of a GraphConv: per-degree sums in the
   float* dbias_rows;              // workspace, unpacked into the reference's bias rows (dbias_rows) after the loop
-  float *dgamma, *dbeta;
-  float *mean, *invstd, *scale, *shift;  // this batch's statistics and the folded affine map (workspace)
-  float *running_mean, *running_var;
-  int64_t* batches_tracked;
-};
+  BnPoint bn;                     // its BatchNorm, W wide: gamma, beta and their gradients nullptr without BatchNorm;
+};                                // this batch's statistics and the folded affine map in the workspace
 
 static void make_blocks(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, float* d_grads,
                         const gcmi_model_io* io, Block* blk) {
@@ -309,19 +301,18 @@ static void make_blocks(const gcmi_model_desc* m, const Ws& w, float* ws, const 
     b.dw = grad(l == L ? m->off_dense_w : m->off_conv_w[l]);
     b.dbias = l == L ? grad(m->off_dense_b) : ws + w.dbsum[l];
     b.dbias_rows = l == L ? nullptr : grad(m->off_conv_b[l]);
-    const bool bn = m->batch_norm != 0;
-    b.gamma = bn ? d_params + m->off_bn_gamma[l] : nullptr;
-    b.beta = bn ? d_params + m->off_bn_beta[l] : nullptr;
-    b.dgamma = bn ? grad(m->off_bn_gamma[l]) : nullptr;
-    b.dbeta = bn ? grad(m->off_bn_beta[l]) : nullptr;
+    BnPoint& p = b.bn;
+    p = BnPoint();
+    p.n_feat = b.W;
+    if (m->batch_norm) {
+      p.gamma = d_params + m->off_bn_gamma[l]; p.beta = d_params + m->off_bn_beta[l];
+      p.dgamma = grad(m->off_bn_gamma[l]); p.dbeta = grad(m->off_bn_beta[l]);
+    }
     float* bnv = ws + w.bnv[l];
-    b.mean = bnv;
-    b.invstd = bnv + b.W;
-    b.scale = bnv + 2 * b.W;
-    b.shift = bnv + 3 * b.W;
-    b.running_mean = io->d_bn_running_mean[l];
-    b.running_var = io->d_bn_running_var[l];
-    b.batches_tracked = io->d_bn_batches_tracked[l];
+    p.mean = bnv; p.invstd = bnv + b.W; p.scale = bnv + 2 * b.W; p.shift = bnv + 3 * b.W;
+    p.running_mean = io->d_bn_running_mean[l]; p.running_var = io->d_bn_running_var[l];
+    p.batches_tracked = io->d_bn_batches_tracked[l];
+    p.eps = m->bn_eps; p.momentum = m->bn_momentum;
   }
 }
 
@@ -352,22 +343,19 @@ static SegProduct<TA, TO> conv_product(const Segs& sg, const TA* s, int64_t lds,
   return p;
 }
 
-// BatchNorm of block b in the forward, folded into b.scale / b.shift for the kernel that reads the rows next: training
+// BatchNorm of block b in the forward, folded into b.bn.scale / shift for the kernel that reads the rows next: training
 // = this batch's statistics, from the sums the product left in acc (stats_fused) or from a pass over the rows; eval =
 // the running statistics
 // (sy: synchronised BatchNorm, training only -- the statistics of the global batch, also for a rank with N == 0)
-static int bn_forward(const gcmi_model_desc* m, const Block& b, int64_t N, int32_t training, bool stats_fused,
-                      const float* rows, int64_t ld, double* acc, void* stream, const BnSync* sy = nullptr) {
-  if (training && sy)
-    return bn_stats_sync_impl(rows, ld, N, b.W, b.gamma, b.beta, m->bn_eps, m->bn_momentum, b.running_mean, b.running_var,
-                              b.mean, b.invstd, b.scale, b.shift, acc, stats_fused, *sy, stream, b.batches_tracked);
-  if (training && stats_fused)
-    return bn_finalize_impl(N, b.W, b.gamma, b.beta, m->bn_eps, m->bn_momentum, b.running_mean, b.running_var, b.mean,
-                            b.invstd, b.scale, b.shift, acc, stream, b.batches_tracked);
-  if (training)
-    return bn_stats_impl(rows, ld, N, b.W, b.gamma, b.beta, m->bn_eps, m->bn_momentum, b.running_mean, b.running_var,
-                         b.mean, b.invstd, b.scale, b.shift, acc, true, stream, b.batches_tracked);
-  return gcmi_bn_fold_eval(b.gamma, b.beta, b.running_mean, b.running_var, m->bn_eps, b.W, b.scale, b.shift, stream);
+static int bn_forward(const Block& b, int64_t N, int32_t training, bool stats_fused, const float* rows, int64_t ld,
+                      double* acc, void* stream, const BnSync* sy = nullptr) {
+  const BnPoint& p = b.bn;
+  if (!training)
+    return gcmi_bn_fold_eval(p.gamma, p.beta, p.running_mean, p.running_var, p.eps, p.n_feat, p.scale, p.shift, stream);
+  BnForward f;
+  f.x = rows; f.ldx = ld; f.sums_ready = stats_fused; f.n_rows = N; f.acc = acc; f.sync = sy;
+  f.acc_clean = true;  // zeroed once per pass by the caller
+  return bn_train_forward(p, f, stream);
 }
 
 // A training batch without atoms launches no statistics kernel, and those are what bump the counters otherwise
@@ -396,8 +384,7 @@ static BnSync make_sync(gcmi_stat_sync_fn sync, void* sync_ctx, const Ws& w, flo
 // first; reference gradient mode stops behind the last GraphConv block)
 static int empty_backward_syncs(const gcmi_model_desc* m, const Block* blk, const BnSync& sy, void* stream) {
   for (int l = m->n_layers; l >= 0; --l) {
-    RUN(bn_bwd_sync_finish(0, blk[l].W, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, sy, stream,
-                           nullptr, 0, 0.f, nullptr));
+    RUN(bn_bwd_sync_empty(blk[l].W, sy, stream));
     if (m->grad_mode != 1 && l < m->n_layers) break;
   }
   return GCMI_OK;
@@ -475,6 +462,86 @@ static int head_backward_separate(const gcmi_model_desc* m, const Ws& w, float* 
 static bool dense_block_one_pass(const gcmi_model_desc* m, int64_t N) {
   const int Wl = m->conv_width[m->n_layers - 1];
   return m->batch_norm && N > 0 && fused_bwd_enabled() && m->dense_width == 128 && Wl > 32 && Wl <= 64;
+}
+
+// ---- What both backward sequences hand the backward entries (common.h)
+// The per-molecule gradient the head part leaves in dfp (tanh derivative applied), as the dense block's consumers read
+// it: built once per backward
+static ReadoutGrad readout_grad(const gcmi_graph* g, const Ws& w, float* ws, int D) {
+  ReadoutGrad rg{g->d_membership, ws + w.dfp, 2 * (int64_t)D, reinterpret_cast<const int32_t*>(ws + w.arg_r)};
+  rg.rawsum = ws + w.rsum; rg.runs = g->d_mol_runs; rg.n_mols = g->n_mols; rg.n_deg = g->max_deg + 1;
+  return rg;
+}
+
+// A BatchNorm backward over N rows of x on the step's accumulator (zeroed once per call, self-cleaning afterwards);
+// the caller names the gradient source and what else it wants
+static BnBackward bn_backward(const float* x, int64_t ldx, int64_t N, double* acc, const BnSync* sy) {
+  BnBackward q;
+  q.x = x; q.ldx = ldx; q.n_rows = N; q.acc = acc; q.acc_clean = true; q.sync = sy;
+  return q;
+}
+
+// GraphConv block b's BatchNorm backward from a pass over dy, and (dx given) the gradient w.r.t. the ReLU input
+static int bn_bwd_rows(const Block& b, const float* dy, const float* gc, int64_t N, float* dx, double* acc,
+                       const BnSync* sy, void* stream) {
+  BnBackward q = bn_backward(gc, b.W, N, acc, sy);
+  q.dy = dy; q.lddy = b.W; q.dx = dx; q.lddx = b.W; q.relu_mask = 1;
+  return bn_bwd_impl(b.bn, q, stream);
+}
+
+// The per-molecule part of the backward in one kernel where the shapes allow (head_bwd.hip): loss, d logits, head
+// gradients, the gradient w.r.t. GraphGather's pre-activation in rg.g2, and -- sums given: the one-pass dense block
+// follows -- the backward sums of the dense layer's BatchNorm.  *done = false: shape not covered, nothing launched.
+// *with_sums: the sums are in place, and the loss is finalised by the BatchNorm parameter launch that follows.
+static int head_backward_fused(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, float* d_grads,
+                               const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
+                               const ReadoutGrad& rg, const BnPoint& dense_bn, double* sums, void* stream, bool* done,
+                               bool* with_sums) {
+  double* lacc = reinterpret_cast<double*>(ws + w.lacc);
+  HeadBackward h;
+  h.kind = m->mode == 0 ? 0 : 1; h.logits = io->d_logits; h.labels = d_labels; h.weights = d_weights;
+  h.n_rows = n_rows; h.n_tasks = m->n_tasks; h.n_classes = m->n_classes;
+  h.fp = io->d_fingerprint; h.ldfp = 2 * dense_bn.n_feat;
+  h.w = d_params + m->off_head_w; h.dw = d_grads + m->off_head_w; h.db = d_grads + m->off_head_b;
+  h.rg = &rg; h.g2 = ws + w.dfp; h.loss_acc = lacc; h.dense_bn = &dense_bn; h.sums = sums;
+  h.dl_scratch = ws + w.dlogits; h.img = w.himg >= 0 ? ws + w.himg : nullptr;
+  *done = *with_sums = false;
+  const int rc = head_bwd_fused(h, (hipStream_t)stream);
+  if (rc == GCMI_ERR_UNSUPPORTED) return GCMI_OK;
+  RUN(rc);
+  *done = true;
+  *with_sums = sums != nullptr;
+  if (!*with_sums) RUN(loss_finalize_impl(lacc, 1.f / (float)(n_rows * m->n_tasks), io->d_loss, stream, kLossRep));
+  return GCMI_OK;
+}
+
+// The dense block in one pass (fused_dense_bwd): G from the readout gradient, the block's output `dense` and coef;
+// dW, db; dpool = G W, and in psums the pooled sums for the BatchNorm below.  *n_rows must outlive the description.
+static BlockBackward dense_backward(const int32_t* n_rows, const ReadoutGrad& rg, const float* dense, const float* coef,
+                                    const float* pool, const Block& dn, float* dpool, double* psums) {
+  BlockBackward q;
+  q.n_seg = 1; q.seg_begin = &kZero32; q.seg_end = n_rows; q.w_off[0] = &kZero64; q.b_off = &kZero64;
+  q.rg = &rg; q.gc = dense; q.ldgc = dn.W; q.coef = coef; q.width = dn.W;
+  q.in[0] = {pool, dn.K}; q.k_in = dn.K; q.w = dn.w; q.dw = dn.dw; q.db = dn.dbias;
+  q.dout[0] = {dpool, dn.K}; q.psums = psums;
+  return q;
+}
+
+// GraphConv block b in one pass (fused_conv_bwd): G from dy, the block's output gc and coef; dW_rel, dW_self, dbsum
+// over [S | X].  The caller adds the input gradients (dout[].rows, psums) where the block below needs them.
+static BlockBackward conv_backward(const Segs& sg, const float* dy, const float* gc, const float* coef, const Block& b,
+                                   const float* s, int64_t lds, const float* x, int64_t ldx) {
+  BlockBackward q;
+  q.n_seg = sg.n; q.seg_begin = sg.begin; q.seg_end = sg.end; q.w_off[0] = sg.w_rel; q.w_off[1] = sg.w_self; q.b_off = sg.b_off;
+  q.dy = dy; q.lddy = b.W; q.gc = gc; q.ldgc = b.W; q.coef = coef; q.width = b.W;
+  q.in[0] = {s, lds}; q.in[1] = {x, ldx}; q.k_in = b.K; q.w = b.w; q.dw = b.dw; q.db = b.dbias;
+  q.dout[0].ld = q.dout[1].ld = b.K;
+  return q;
+}
+
+// block l's bias gradient sums are in place: unpacked into the reference's bias rows in one launch after the loop
+static void note_bias_grads(BiasLayers& ub, int l, const Block& b) {
+  ub.src[l] = b.dbias; ub.dst[l] = b.dbias_rows; ub.width[l] = b.W;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -556,14 +623,14 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
         if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: GraphConv %d has no bf16 product kernel", l);
         RUN(rc);
       }
-      RUN(bn_forward(m, b, N, training, true, nullptr, 0, acc, stream, sy));
+      RUN(bn_forward(b, N, training, true, nullptr, 0, acc, stream, sy));
       {
         TimedScope ts(GCMI_K_GATHER_MAX, st);
-        RUN(win_gather_max_h(g, H(w.gc[l]), b.W, b.W, b.scale, b.shift, H(w.pool[l]), b.W,
+        RUN(win_gather_max_h(g, H(w.gc[l]), b.W, b.W, b.bn.scale, b.bn.shift, H(w.pool[l]), b.W,
                              training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, st));
       }
     } else if (sy) {
-      RUN(bn_forward(m, b, 0, training, true, nullptr, 0, acc, stream, sy));
+      RUN(bn_forward(b, 0, training, true, nullptr, 0, acc, stream, sy));
     }
     xin = H(w.pool[l]);
     ldin = b.W;
@@ -581,12 +648,12 @@ static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const 
       if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense layer has no bf16 product kernel");
       RUN(rc);
     }
-    RUN(bn_forward(m, dn, N, training, true, nullptr, 0, acc, stream, sy));
+    RUN(bn_forward(dn, N, training, true, nullptr, 0, acc, stream, sy));
   } else if (sy) {
-    RUN(bn_forward(m, dn, 0, training, true, nullptr, 0, acc, stream, sy));
+    RUN(bn_forward(dn, 0, training, true, nullptr, 0, acc, stream, sy));
   }
-  RUN(readout_fwd_impl(g, reinterpret_cast<const float*>(H(w.dense)), D, D, N > 0 ? dn.scale : nullptr,
-                       N > 0 ? dn.shift : nullptr, 1, io->d_fingerprint, 2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
+  RUN(readout_fwd_impl(g, reinterpret_cast<const float*>(H(w.dense)), D, D, N > 0 ? dn.bn.scale : nullptr,
+                       N > 0 ? dn.bn.shift : nullptr, 1, io->d_fingerprint, 2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
                        training ? ws + w.rsum : nullptr, stream, 1));
   RUN(head_forward(m, w, ws, d_params, io, B, stream));
   if (m->mode == 0 && io->d_probs) RUN(gcmi_softmax(io->d_logits, B * m->n_tasks, m->n_classes, io->d_probs, stream));
@@ -627,24 +694,11 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
   // ---- per-molecule part (fp32 throughout: the fingerprint and everything behind it are per-molecule rows)
   const Block& dn = blk[L];
   const int D = dn.W;
-  bool head_sums = false;
-  {
-    const int rc = head_bwd_fused(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks, m->n_classes,
-                                  B, io->d_fingerprint, 2 * D, d_params + m->off_head_w, d_grads + m->off_head_w,
-                                  d_grads + m->off_head_b, ws + w.dfp, 2 * D, lacc, g->d_mol_runs, g->max_deg + 1,
-                                  reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.rsum, dn.mean, dn.invstd,
-                                  (N > 0 && g->d_mol_runs) ? acc : nullptr, D, st, ws + w.dlogits,
-                                  w.himg >= 0 ? ws + w.himg : nullptr);
-    if (rc == GCMI_OK) {
-      head_sums = N > 0 && g->d_mol_runs != nullptr;
-      // (with head_sums the loss is finalised by the BatchNorm parameter launch that follows)
-      if (!head_sums) RUN(loss_finalize_impl(lacc, loss_inv_count, io->d_loss, stream, kLossRep));
-    } else if (rc != GCMI_ERR_UNSUPPORTED) {
-      return rc;
-    } else {
-      RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, true, stream));
-    }
-  }
+  const ReadoutGrad rg = readout_grad(g, w, ws, D);
+  bool head_done = false, head_sums = false;
+  RUN(head_backward_fused(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, rg, dn.bn,
+                          (N > 0 && g->d_mol_runs) ? acc : nullptr, stream, &head_done, &head_sums));
+  if (!head_done) RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, true, stream));
   if (N == 0) return sy ? empty_backward_syncs(m, blk, *sy, stream) : GCMI_OK;
   float* dpool = ws + w.tC;
   const float* coef = ws + w.acc;
@@ -652,20 +706,23 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
   const bool gb = m->storage == 2;
   auto HG = [](float* p) { return reinterpret_cast<bf16_t*>(p); };
   // ---- dense block: BatchNorm sums from per-molecule data, then one pass (dense and pool rows arrive as bf16)
-  if (head_sums) {
-    RUN(bn_bwd_params_impl(N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, acc, stream, lacc, kLossRep,
-                           loss_inv_count, io->d_loss, sy));
-  } else {
+  {
     // (the per-molecule sums kernel reads rawsum, never the atom rows: the bf16 matrix is only passed through)
-    RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, reinterpret_cast<const int32_t*>(ws + w.arg_r),
-                            HF(w.dense), D, N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, nullptr, D, 1, acc,
-                            true, stream, ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1, sy));
+    BnBackward q = bn_backward(HF(w.dense), D, N, acc, sy);
+    if (head_sums) {
+      q.loss = {lacc, kLossRep, loss_inv_count, io->d_loss};
+      RUN(bn_bwd_params_impl(dn.bn, q, stream));
+    } else {
+      q.rg = &rg;
+      RUN(bn_bwd_impl(dn.bn, q, stream));
+    }
   }
   {
     TimedScope ts(GCMI_K_FUSED_BWD, st);
-    const int rc = fused_dense_bwd(N, g->d_membership, ws + w.dfp, 2 * D, reinterpret_cast<const int32_t*>(ws + w.arg_r),
-                                   HF(w.dense), D, coef, D, HF(w.pool[L - 1]), dn.K, dn.K, dn.w, dn.dw, dn.dbias, dpool,
-                                   dn.K, acc2, st, gb ? 2 : 1);
+    const int32_t nN = (int32_t)N;
+    BlockBackward q = dense_backward(&nN, rg, HF(w.dense), coef, HF(w.pool[L - 1]), dn, dpool, acc2);
+    q.act_bf16 = gb ? 2 : 1;
+    const int rc = fused_dense_bwd(q, st);
     if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense block has no one-pass backward");
     RUN(rc);
   }
@@ -689,29 +746,30 @@ static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, 
       // (left by win_gather_sumacc_max_bwd below, one iteration ago)
     } else if (gb) {
       TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_max_bwd_h(g, HG(dpool), W, W, arg, HG(dy), W, full ? nullptr : b.gamma, full ? nullptr : b.beta, st));
+      RUN(win_gather_max_bwd_h(g, HG(dpool), W, W, arg, HG(dy), W, full ? nullptr : b.bn.gamma, full ? nullptr : b.bn.beta, st));
     } else if (full) {
       RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
     } else {
       TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.gamma, b.beta, st));
+      RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.bn.gamma, b.bn.beta, st));
     }
-    RUN(bn_bwd_pool_impl(dy, W, HF(w.gc[l]), W, N, W, b.gamma, b.beta, b.mean, b.invstd, b.dgamma, b.dbeta, acc2, acc,
-                         stream, gb ? 2 : 1, sy));
+    {
+      BnBackward q = bn_backward(HF(w.gc[l]), W, N, acc, sy);
+      q.dy = dy; q.lddy = W; q.x_bf16 = gb ? 2 : 1; q.psums = acc2;
+      RUN(bn_bwd_pool_impl(b.bn, q, stream));
+    }
     dy_ready = false;
     if (!full) break;  // reference semantics: nothing in front of a GraphConv output trains
     {
       TimedScope ts(GCMI_K_FUSED_BWD, st);
-      const int rc = fused_conv_bwd(sg.n, sg.begin, sg.end, sg.w_rel, sg.w_self, sg.b_off, dy, W, HF(w.gc[l]), W, coef, W,
-                                    HF(w.S[l]), w.ldS[l], reinterpret_cast<const float*>(xin), ldx, K, b.w, b.dw, b.dbias,
-                                    l > 0 ? dS : nullptr, K, l > 0 ? dX : nullptr, K, l > 0 ? acc2 : nullptr, st,
-                                    gb ? 2 : 1);
+      BlockBackward q = conv_backward(sg, dy, HF(w.gc[l]), coef, b, HF(w.S[l]), w.ldS[l], reinterpret_cast<const float*>(xin), ldx);
+      q.act_bf16 = gb ? 2 : 1;
+      if (l > 0) { q.dout[0].rows = dS; q.dout[1].rows = dX; q.psums = acc2; }
+      const int rc = fused_conv_bwd(q, st);
       if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: GraphConv %d has no one-pass backward", l);
       RUN(rc);
     }
-    ub.src[l] = b.dbias;  // (unpacked into the reference's bias rows in one launch after the loop)
-    ub.dst[l] = b.dbias_rows;
-    ub.width[l] = W;
+    note_bias_grads(ub, l, b);
     if (l == 0) break;  // the atom features need no gradient
     // dX holds the self part; the neighbour part is added onto it, and where the window kernels can hold a third tile
     // the GraphPool backward of the block below runs in the same pass
@@ -823,9 +881,9 @@ int gcmi_model_forward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const f
                          ws + w.wimg));
     }
     const bool bn = m->batch_norm && N > 0;
-    if (bn || sy) RUN(bn_forward(m, b, N, training, stats_fused, ws + w.gc[l], W, acc, stream, sy));
+    if (bn || sy) RUN(bn_forward(b, N, training, stats_fused, ws + w.gc[l], W, acc, stream, sy));
     if (N > 0)
-      RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, bn ? b.scale : nullptr, bn ? b.shift : nullptr, ws + w.pool[l], W,
+      RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, bn ? b.bn.scale : nullptr, bn ? b.bn.shift : nullptr, ws + w.pool[l], W,
                               training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, stream));
     x = ws + w.pool[l];
     ldx = W;
@@ -840,8 +898,8 @@ int gcmi_model_forward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const f
     RUN(seg_gemm_stats(p, stats, &stats_fused, st));
   }
   const bool bn = m->batch_norm && N > 0;
-  if (bn || sy) RUN(bn_forward(m, dn, N, training, stats_fused, ws + w.dense, D, acc, stream, sy));
-  RUN(readout_fwd_impl(g, ws + w.dense, D, D, bn ? dn.scale : nullptr, bn ? dn.shift : nullptr, 1, io->d_fingerprint,
+  if (bn || sy) RUN(bn_forward(dn, N, training, stats_fused, ws + w.dense, D, acc, stream, sy));
+  RUN(readout_fwd_impl(g, ws + w.dense, D, D, bn ? dn.bn.scale : nullptr, bn ? dn.bn.shift : nullptr, 1, io->d_fingerprint,
                        2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
                        (training && m->batch_norm) ? ws + w.rsum : nullptr, stream));
   RUN(head_forward(m, w, ws, d_params, io, B, stream));
@@ -912,23 +970,11 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
   // gradient w.r.t. GraphGather's pre-activation (tanh derivative applied), and -- when the one-pass dense block
   // follows -- the BatchNorm backward sums of the dense layer
   const bool dense_one_pass = dense_block_one_pass(m, N);
+  const ReadoutGrad rg = readout_grad(g, w, ws, D);
   bool head_done = false, head_sums = false;
-  if (m->batch_norm) {  // (without BatchNorm the readout backward applies the tanh derivative itself)
-    const int rc = head_bwd_fused(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks,
-                                  m->n_classes, B, io->d_fingerprint, 2 * D, d_params + m->off_head_w,
-                                  d_grads + m->off_head_w, d_grads + m->off_head_b, ws + w.dfp, 2 * D, lacc, g->d_mol_runs,
-                                  g->max_deg + 1, reinterpret_cast<const int32_t*>(ws + w.arg_r), ws + w.rsum, dn.mean,
-                                  dn.invstd, (dense_one_pass && g->d_mol_runs) ? acc : nullptr, D, st, ws + w.dlogits,
-                                  w.himg >= 0 ? ws + w.himg : nullptr);
-    if (rc == GCMI_OK) {
-      head_done = true;
-      head_sums = dense_one_pass && g->d_mol_runs != nullptr;
-      // (with head_sums the loss is finalised by the BatchNorm parameter launch that follows)
-      if (!head_sums) RUN(loss_finalize_impl(lacc, loss_inv_count, io->d_loss, stream, kLossRep));
-    } else if (rc != GCMI_ERR_UNSUPPORTED) {
-      return rc;
-    }
-  }
+  if (m->batch_norm)  // (without BatchNorm the readout backward applies the tanh derivative itself)
+    RUN(head_backward_fused(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, rg, dn.bn,
+                            (dense_one_pass && g->d_mol_runs) ? acc : nullptr, stream, &head_done, &head_sums));
   // (the tanh derivative applied in place only for the BatchNorm backward below)
   if (!head_done)
     RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, m->batch_norm && N > 0,
@@ -946,20 +992,23 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
   if (m->batch_norm) {
     // GraphGather backward is recomputed inside the BatchNorm backward from the per-molecule
     // gradient (tanh derivative applied in place): the N x D gradient is never written or re-read
+    auto readout_bn_bwd = [&](float* dx, const BnSync* s) {
+      BnBackward q = bn_backward(ws + w.dense, D, N, acc, s);
+      q.rg = &rg; q.dx = dx; q.lddx = D; q.relu_mask = 1;
+      return bn_bwd_impl(dn.bn, q, stream);
+    };
     if (head_sums) {
       // the sums are in place (head_bwd.hip): dgamma, dbeta and the coefficient vectors
-      RUN(bn_bwd_params_impl(N, D, dn.gamma, dn.mean, dn.invstd, dn.dgamma, dn.dbeta, acc, stream, lacc, kLossRep,
-                             loss_inv_count, io->d_loss, sy));
+      BnBackward q = bn_backward(ws + w.dense, D, N, acc, sy);
+      q.loss = {lacc, kLossRep, loss_inv_count, io->d_loss};
+      RUN(bn_bwd_params_impl(dn.bn, q, stream));
     } else {
-      RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, N, D, dn.gamma, dn.mean,
-                              dn.invstd, dn.dgamma, dn.dbeta, dense_one_pass ? nullptr : dxD, D, 1, acc, true, stream,
-                              ws + w.rsum, g->d_mol_runs, g->n_mols, g->max_deg + 1, sy));
+      RUN(readout_bn_bwd(dense_one_pass ? nullptr : dxD, sy));
     }
     if (dense_one_pass) {
       // one pass: dxD formed per 64-row tile in LDS, dW_dense += dxD^T pool, db += colsum, dpool = dxD W_dense
       TimedScope ts(GCMI_K_FUSED_BWD, st);
-      const int rc = fused_dense_bwd(N, g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, coef, D,
-                                     ws + w.pool[L - 1], Wl, Wl, dn.w, dn.dw, dn.dbias, dpool, Wl, acc2, st);
+      const int rc = fused_dense_bwd(dense_backward(&nN, rg, ws + w.dense, coef, ws + w.pool[L - 1], dn, dpool, acc2), st);
       if (rc == GCMI_OK) {
         dense_done = true;
         have_psums = true;
@@ -967,9 +1016,7 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
       else if (sy) return refuse_second_sync("the one-pass dense block");
       else  // not covered after all (misaligned buffers): the separate pass, with its sums once more
-        RUN(bn_bwd_readout_impl(g->d_membership, ws + w.dfp, 2 * D, arg_r, ws + w.dense, D, N, D, dn.gamma, dn.mean,
-                                dn.invstd, dn.dgamma, dn.dbeta, dxD, D, 1, acc, true, stream, ws + w.rsum, g->d_mol_runs,
-                                g->n_mols, g->max_deg + 1));
+        RUN(readout_bn_bwd(dxD, nullptr));
     }
   } else {
     RUN(gcmi_readout_bwd(g, ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, D, 1, arg_r, dyD, D, stream));
@@ -1018,15 +1065,15 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
         RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
       } else {
         TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-        RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.gamma, b.beta, st));
+        RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.bn.gamma, b.bn.beta, st));
       }
-      RUN(bn_bwd_pool_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.beta, b.mean, b.invstd, b.dgamma, b.dbeta, acc2, acc,
-                           stream, 0, sy));
+      BnBackward q = bn_backward(ws + w.gc[l], W, N, acc, sy);
+      q.dy = dy; q.lddy = W; q.psums = acc2;
+      RUN(bn_bwd_pool_impl(b.bn, q, stream));
     } else {
       if (!dy_ready) RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
       if (m->batch_norm) {
-        RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.mean, b.invstd, b.dgamma, b.dbeta,
-                        (full && !try_fused) ? dgc : nullptr, W, 1, acc, true, stream, sy));
+        RUN(bn_bwd_rows(b, dy, ws + w.gc[l], N, (full && !try_fused) ? dgc : nullptr, acc, sy, stream));
       } else if (full && !try_fused) {
         RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
         dgc = dy;
@@ -1039,10 +1086,10 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
       // one pass over the rows: dgc formed per tile in LDS; dW_rel, dW_self, dbsum; and for l > 0 dS = dgc W_rel^T
       // and the self part of dX
       TimedScope ts(GCMI_K_FUSED_BWD, st);
-      const int rc = fused_conv_bwd(sg.n, sg.begin, sg.end, sg.w_rel, sg.w_self, sg.b_off, dy, W, ws + w.gc[l], W,
-                                    m->batch_norm ? coef : nullptr, W, ws + w.S[l], ldS, xin, ldx, K, b.w, b.dw, b.dbias,
-                                    l > 0 ? dS : nullptr, K, l > 0 ? dX : nullptr, K,
-                                    (l > 0 && sym && m->batch_norm) ? acc2 : nullptr, st, 0, one_piece ? 1 : 0);
+      BlockBackward q = conv_backward(sg, dy, ws + w.gc[l], m->batch_norm ? coef : nullptr, b, ws + w.S[l], ldS, xin, ldx);
+      q.in_bf16 = one_piece ? 1 : 0;
+      if (l > 0) { q.dout[0].rows = dS; q.dout[1].rows = dX; q.psums = (sym && m->batch_norm) ? acc2 : nullptr; }
+      const int rc = fused_conv_bwd(q, st);
       if (rc == GCMI_OK) {
         fused_done = true;
         have_psums = l > 0 && sym && m->batch_norm;
@@ -1051,8 +1098,7 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
       else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
       else if (sy) return refuse_second_sync("the one-pass GraphConv block");
       else if (m->batch_norm) {  // not covered after all (misaligned buffers): the separate pass, sums once more
-        RUN(bn_bwd_impl(dy, W, ws + w.gc[l], W, N, W, b.gamma, b.mean, b.invstd, b.dgamma, b.dbeta, dgc, W, 1, acc, true,
-                        stream));
+        RUN(bn_bwd_rows(b, dy, ws + w.gc[l], N, dgc, acc, nullptr, stream));
       } else {
         RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
         dgc = dy;
@@ -1069,9 +1115,7 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
       RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, xin, ldx, K, dgc, W, W, b.dw, sg.w_self, b.dbias, sg.b_off, 0,
                               stream));
     }
-    ub.src[l] = b.dbias;  // (unpacked into the reference's bias rows in one launch after the loop)
-    ub.dst[l] = b.dbias_rows;
-    ub.width[l] = W;
+    note_bias_grads(ub, l, b);
     if (l == 0) break;  // the atom features need no gradient
     // dS = dgc . W_rel^T ; dX = dgc . W_self^T + (transposed gather of dS)
     if (fused_done) {

@@ -1470,8 +1470,6 @@ small_step_end_kernel(StepEnd s) {
 // ================================================================================================ host side
 namespace gcmi {
 
-static inline int64_t up4s(int64_t n) { return (n + 3) / 4 * 4; }
-
 struct SmallWs {  // offsets in floats into the workspace
   // GraphConv outputs and their BatchNorm sums exist in kSlots copies: in reference gradient mode the conv stack of
   // a later step depends on nothing an earlier step trains, so the stacks of the next kAhead steps run on a second
@@ -1492,7 +1490,7 @@ static SmallWs small_carve(const gcmi_model_desc* m, int64_t N, int64_t B) {
   int64_t off = 0;
   auto take = [&](int64_t n) {
     int64_t o = off;
-    off += up4s(n);
+    off += up4(n);
     return o;
   };
   const int L = m->n_layers;
