@@ -31,7 +31,7 @@ from deepchem_amd.metrics import to_one_hot
 from deepchem_amd.models.losses import L2Loss, SoftmaxCrossEntropy
 from deepchem_amd.models.torch_models.torch_model import TorchModel
 from deepchem_amd.models.torch_models.weave_layers import _csr_from_sorted
-from deepchem_amd.ops import _ptr, _stream
+from deepchem_amd.ops import _ld, _ptr, _stream
 
 
 # ---------------------------------------------------------------------------------------------- autograd pieces
@@ -146,8 +146,9 @@ class AttendFn(torch.autograd.Function):
         dx = torch.empty_like(x)
         dh = torch.empty_like(h)
         n_mols = mol_ptr.numel() - 1
-        _lib.call("gcmi_set2set_attend_bwd", _ptr(x), x.stride(0), x.shape[1], _ptr(mol_ptr), n_mols, _ptr(h), h.stride(0),
-                  _ptr(dq), dq.stride(0), _ptr(dx), dx.stride(0), 0, _ptr(dh), dh.stride(0), _stream())
+        # (ops._ld: the row stride of a one-row tensor means nothing, a (d, 1).t() view reports 1)
+        _lib.call("gcmi_set2set_attend_bwd", _ptr(x), _ld(x), x.shape[1], _ptr(mol_ptr), n_mols, _ptr(h), _ld(h),
+                  _ptr(dq), _ld(dq), _ptr(dx), _ld(dx), 0, _ptr(dh), _ld(dh), _stream())
         return dx, dh, None
 
 
@@ -170,7 +171,7 @@ class LstmCellFn(torch.autograd.Function):
         dh = torch.zeros_like(c_prev) if dh is None else dh.contiguous()
         dz = torch.empty_like(z)
         dc_prev = torch.empty_like(c_prev)
-        _lib.call("gcmi_lstm_cell_bwd", _ptr(z), z.stride(0), H, z.shape[0], _ptr(c_prev), _ptr(dh),
+        _lib.call("gcmi_lstm_cell_bwd", _ptr(z), _ld(z), H, z.shape[0], _ptr(c_prev), _ptr(dh),
                   _ptr(dc.contiguous()) if dc is not None else None, _ptr(dz), _ptr(dc_prev), _stream())
         return dz, dc_prev
 

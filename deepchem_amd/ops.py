@@ -27,7 +27,7 @@ def _mat(t: torch.Tensor, name: str, rows: Optional[int] = None, cols: Optional[
         raise _lib.GcmiError("%s must be a CUDA tensor: the hot path has no CPU implementation" % name)
     if t.dtype != dtype:
         raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
-    if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+    if t.dim() != 2 or (t.numel() > 0 and t.shape[1] > 1 and t.stride(1) != 1):  # (an empty tensor's strides mean nothing)
         raise ValueError("%s must be 2-D with unit column stride (shape %s, strides %s)" %
                          (name, tuple(t.shape), t.stride()))
     if rows is not None and t.shape[0] != rows:
@@ -495,6 +495,16 @@ def edge_network_moments(h: torch.Tensor, pair_feat: torch.Tensor, dst_ptr: torc
     d, K = h.shape[1], pf.shape[1]
     n_dst = dst_ptr.numel() - 1
     t = torch.empty((n_dst, (K + 1) * d), dtype=torch.float32, device=h.device)
+    if pf.shape[0] == 0:  # no pair at all: an empty tensor has no buffer, which the C entry points refuse
+        # the limits below mirror the "bad shape" GCMI_CHECK_ARG of gcmi_edge_network_moments and
+        # gcmi_edge_network_moments_mol in csrc/mpnn.hip, which this return goes past: change them together
+        if not (0 < d <= 128 and 0 < K <= 16):
+            raise _lib.GcmiError("edge_network_moments: bad shape (n_hidden <= 128, n_pair_feat <= 16)")
+        _i32vec(dst_ptr, "dst_ptr")
+        _i32vec(src, "src", 0)
+        if mol_ptr is not None:
+            _i32vec(mol_ptr, "mol_ptr")
+        return t.zero_()
     if mol_ptr is not None:
         mp = _i32vec(mol_ptr, "mol_ptr")
         _lib.call("gcmi_edge_network_moments_mol", _ptr(h), _ld(h), d, K, _ptr(pf), _ld(pf),

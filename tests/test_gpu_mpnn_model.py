@@ -40,11 +40,11 @@ def qm9_like(n_mols, n_atom_feat, n_pair_feat, seed, max_atoms=12):
     return mols
 
 
-def build(mode, T, M, d, B, n_tasks, seed):
+def build(mode, T, M, d, B, n_tasks, seed, n_pair_feat=6):
     import deepchem_amd as dc
     from deepchem_amd.models.torch_models.mpnn import MPNNModel
     torch.manual_seed(seed)
-    model = MPNNModel(n_tasks, n_atom_feat=20, n_pair_feat=6, n_hidden=d, T=T, M=M, mode=mode, batch_size=B,
+    model = MPNNModel(n_tasks, n_atom_feat=20, n_pair_feat=n_pair_feat, n_hidden=d, T=T, M=M, mode=mode, batch_size=B,
                       device=torch.device(DEV), learning_rate=1e-3)
     # biases away from zero so that their gradients are exercised too
     with torch.no_grad():
@@ -54,14 +54,22 @@ def build(mode, T, M, d, B, n_tasks, seed):
     return model
 
 
-@pytest.mark.parametrize("mode,n_tasks", [("regression", 3), ("classification", 2)])
-def test_mpnn_forward_and_gradients_match_the_oracle(mode, n_tasks):
+# (B, d, T, M, n_pair_feat, max_atoms); the second shape is the model's default width: edge_moments_kernel<16, 2> and
+# the second 64-lane feature chunk of the set2set kernels, in both directions
+SMALL, DEFAULT_WIDTH = (6, 32, 3, 4, 6, 12), (4, 100, 2, 2, 8, 10)
+
+
+@pytest.mark.parametrize("mode,n_tasks,shape", [
+    pytest.param("regression", 3, SMALL, id="regression-3"),
+    pytest.param("classification", 2, SMALL, id="classification-2"),
+    pytest.param("regression", 3, DEFAULT_WIDTH, id="regression-3-default-width")])
+def test_mpnn_forward_and_gradients_match_the_oracle(mode, n_tasks, shape):
     import deepchem_amd as dc
     dc.set_gemm_mode("exact")
     try:
-        B, d, T, M = 6, 32, 3, 4
-        model = build(mode, T, M, d, B, n_tasks, seed=1)
-        mols = qm9_like(B, 20, 6, seed=2)
+        B, d, T, M, K, max_atoms = shape
+        model = build(mode, T, M, d, B, n_tasks, seed=1, n_pair_feat=K)
+        mols = qm9_like(B, 20, K, seed=2, max_atoms=max_atoms)
         rng = np.random.RandomState(3)
         y = rng.randn(B, n_tasks) if mode == "regression" else (rng.rand(B, n_tasks) < 0.5).astype(float)
         w = (rng.rand(B, n_tasks) < 0.8).astype(float)
