@@ -30,6 +30,9 @@ def _mat(t: torch.Tensor, name: str, rows: Optional[int] = None, cols: Optional[
     if t.dim() != 2 or (t.numel() > 0 and t.shape[1] > 1 and t.stride(1) != 1):  # (an empty tensor's strides mean nothing)
         raise ValueError("%s must be 2-D with unit column stride (shape %s, strides %s)" %
                          (name, tuple(t.shape), t.stride()))
+    if t.numel() > 0 and t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+        # (_ld would hand the kernel ld = columns: other rows than the view's, and past its end)
+        raise ValueError("%s: rows overlap, row stride %d < %d columns" % (name, t.stride(0), t.shape[1]))
     if rows is not None and t.shape[0] != rows:
         raise ValueError("%s has %d rows, expected %d" % (name, t.shape[0], rows))
     if cols is not None and t.shape[1] != cols:
