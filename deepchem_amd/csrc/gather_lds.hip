@@ -21,19 +21,6 @@
 
 namespace gcmi {
 
-// 16-byte row stores of the window operations.  -DGCMI_WIN_NT=1 (A/B switch, tools/win_nt_ab.sh): as non-temporal stores
-// (streamed past the caches: every output row of a window pass is written once and read by ANOTHER kernel).
-typedef float win_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void win_store4(float* p, const float4 v) {
-#if defined(GCMI_WIN_NT) && GCMI_WIN_NT
-  const win_f4 t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<win_f4*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = v;
-#endif
-}
-
-
 constexpr int kND = GCMI_MAX_DEG + 1;
 constexpr int kLdsPerCU = 160 * 1024;
 constexpr int kRingBytes = 320;                 // 3 descriptors of GCMI_WIN_META_INTS ints, 16-byte padded
@@ -52,13 +39,8 @@ __device__ __forceinline__ unsigned lds_addr(const void* p) {
 __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
   unsigned keep;
   lds_dst = __builtin_amdgcn_readfirstlane(lds_dst);  // wave-uniform by construction
-#if defined(GCMI_WIN_NT) && GCMI_WIN_NT >= 2  // (A/B switch: the row loads non-temporal as well)
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#else
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-#endif
 }
 __device__ __forceinline__ void glds4(const void* gsrc, unsigned lds_dst) {
   unsigned keep;
@@ -126,7 +108,7 @@ struct Layout {
 // (x: rows of LPR 16-byte pieces -- 4 floats or 8 bf16 each --, ldx in BYTES: the DMA moves bytes, not elements)
 // AUX: the byte matrix `aux` (one byte per element) rides along.  Four elements per piece (fp32 rows): one dword per
 // piece, aux32[e].  Eight (bf16 rows, EPP 8): two dwords per piece by two DMA instructions, each of which writes 64
-// lanes x 4 bytes side by side -- so per 64 pieces the image is [64 low dwords][64 high dwords] (aux_lo / aux_hi below).
+// lanes x 4 bytes side by side -- so per 64 pieces the image is [64 low dwords][64 high dwords] (Piece<bf16_t>::arg).
 template <int WT, int LPR, bool AUX, int EPP = 4>
 __device__ __forceinline__ void stage(char* buf, const Layout& L, const WinMeta& m,
                                       const char* __restrict__ x, int64_t ldx,
@@ -177,316 +159,277 @@ __device__ __forceinline__ void stage_extra(char* dst, const Layout& L, const Wi
   }
 }
 
+// ---------------------------------------------------------------- one 16-byte piece of a tile row, per element type
+// The only place that knows how many elements a piece holds, how they become floats and back, and where the arg-max
+// bytes that ride with a piece (stage(), AUX) sit in the LDS image.  Vals / Bytes are indexed v[q]; fp32 keeps the vector types,
+// handed on by reference: from a float[4], or a uchar4 by value, hipcc (ROCm 7.2) no longer forms the fp32 ops' packed adds.
+template <class T>
+struct Piece;
+
+template <>
+struct Piece<float> {
+  static constexpr int kEPP = 4;  // elements per piece = aux bytes per piece
+  using Raw = float4;
+  using Vals = float4;   // the piece as floats, v[q]
+  using Bytes = uchar4;  // a byte per element, b[q]
+  using Arg = uchar4;  // the arg bytes of piece e: one dword, aux32[e]
+  static __device__ __forceinline__ void widen(const Raw& r, Vals& v) { v = r; }
+  static __device__ __forceinline__ Raw narrow(const Vals& v) { return v; }
+  static __device__ __forceinline__ void load_vals(const float* p, Vals& v) { v = *reinterpret_cast<const float4*>(p); }
+  static __device__ __forceinline__ Arg arg(const char* aux, int e) { return reinterpret_cast<const uchar4*>(aux)[e]; }
+  static __device__ __forceinline__ unsigned char arg_byte(const Arg& a, int q) {
+    return q == 0 ? a.x : q == 1 ? a.y : q == 2 ? a.z : a.w;
+  }
+  static __device__ __forceinline__ void store_arg(uint8_t* p, const Bytes& b) { *reinterpret_cast<uchar4*>(p) = b; }
+};
+
+// bf16 rows (gcmi_model_desc.storage >= 1): the LDS-DMA moves bytes, so a bf16 row of 64 is 8 pieces of 8 elements.
+// Sums and maxima are formed in fp32 from the widened elements and rounded once (v_cvt_pk_bf16_f32) at the store.
+template <>
+struct Piece<bf16_t> {
+  static constexpr int kEPP = 8;
+  using Raw = uint4;
+  using Vals = float[8];
+  using Bytes = unsigned char[8];
+  using Arg = uint2;  // two dwords in the split image stage() writes: per 64 pieces [64 low dwords][64 high dwords]
+  static __device__ __forceinline__ void widen(const Raw& r, Vals& v) { widen8(r, v); }
+  static __device__ __forceinline__ Raw narrow(const Vals& v) {
+    uint4 o;
+    o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]);
+    o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
+    return o;
+  }
+  static __device__ __forceinline__ void load_vals(const float* p, Vals& v) {
+    const float4 a = *reinterpret_cast<const float4*>(p);
+    const float4 b = *reinterpret_cast<const float4*>(p + 4);
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+  static __device__ __forceinline__ Arg arg(const char* aux, int e) {
+    const unsigned* a = reinterpret_cast<const unsigned*>(aux) + (e >> 6) * 128 + (e & 63);
+    return make_uint2(a[0], a[64]);
+  }
+  static __device__ __forceinline__ unsigned char arg_byte(const Arg a, int q) {
+    return (unsigned char)((q < 4 ? a.x >> (8 * q) : a.y >> (8 * (q - 4))) & 255u);
+  }
+  static __device__ __forceinline__ void store_arg(uint8_t* p, const Bytes& b) {
+    uint2 av;
+    av.x = (unsigned)b[0] | ((unsigned)b[1] << 8) | ((unsigned)b[2] << 16) | ((unsigned)b[3] << 24);
+    av.y = (unsigned)b[4] | ((unsigned)b[5] << 8) | ((unsigned)b[6] << 16) | ((unsigned)b[7] << 24);
+    *reinterpret_cast<uint2*>(p) = av;
+  }
+};
+
+template <class T>
+__device__ __forceinline__ typename Piece<T>::Raw load_piece(const T* p) {
+  return *reinterpret_cast<const typename Piece<T>::Raw*>(p);
+}
+template <class T>
+__device__ __forceinline__ void store_piece(T* p, const typename Piece<T>::Vals& v) {
+  *reinterpret_cast<typename Piece<T>::Raw*>(p) = Piece<T>::narrow(v);
+}
+
+// One window buffer as a compute phase reads it, and what piece e of it is
+template <class P>
+struct WinBuf {
+  const typename P::Raw* tile;  // [slot][LPR] pieces
+  const char* aux;              // the arg-max bytes of the same pieces (ops launched with AUX)
+  const uint16_t* ent;          // the window's neighbour entries
+  int n16;                      // pieces in the window
+};
+template <class P, int LPR>
+__device__ __forceinline__ WinBuf<P> open_buf(const char* buf, const Layout& L, const WinMeta& m) {
+  return {reinterpret_cast<const typename P::Raw*>(buf), buf + L.tile_bytes,
+          reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes), m.sb[kND] * LPR};
+}
+struct PieceAt {
+  int c;            // piece within the row
+  int d;            // the atom's degree
+  int row;          // its global row
+  int eloc;         // first of its d neighbour entries
+};
+template <int LPR>
+__device__ __forceinline__ PieceAt piece_at(const WinMeta& m, int maxd, int e) {
+  const int slot = e / LPR;
+  PieceAt a;
+  a.c = e - slot * LPR;
+  locate(m, maxd, slot, a.d, a.row, a.eloc);
+  return a;
+}
+
+// ---------------------------------------------------------------- the three inner loops over a piece, each written once
+// Piece c of the rows in `tile` ([slot][LPR]); nb: the atom's d neighbour entries.  Every op below -- and both stages of
+// the two-stage ops -- forms its sums and comparisons here, so the two-stage pass and the separate passes that take
+// its place for oversized windows agree bit for bit by construction.
+
+// acc = sum of the neighbours' pieces, in neighbour order
+template <class P, int LPR>
+__device__ __forceinline__ void neigh_sum(const typename P::Raw* tile, const uint16_t* nb, int d, int c,
+                                          typename P::Vals& acc) {
+#pragma unroll
+  for (int q = 0; q < P::kEPP; ++q) acc[q] = 0.f;  // lone atoms: zero
+  for (int j = 0; j < d; ++j) {
+    const int sl = nb[j] & GCMI_WIN_MAX_SLOTS;
+    typename P::Vals v;
+    P::widen(tile[sl * LPR + c], v);
+#pragma unroll
+    for (int q = 0; q < P::kEPP; ++q) acc[q] += v[q];
+  }
+}
+template <class P>
+__device__ __forceinline__ void add_piece(typename P::Vals& acc, const typename P::Raw& r) {
+  typename P::Vals v;
+  P::widen(r, v);
+#pragma unroll
+  for (int q = 0; q < P::kEPP; ++q) acc[q] += v[q];
+}
+
+// GraphPool: the maximum over the atom's own piece e and its neighbours', BN: of y = x * scale + shift in fp32 (the
+// folded BatchNorm, [scale: 256][shift: 256] floats in LDS); the first maximum wins (self first, then neighbour order).
+// ba: 0 = self, j + 1 = neighbour j
+template <class P, int LPR, bool BN>
+__device__ __forceinline__ void pool_max(const typename P::Raw* tile, const uint16_t* nb, int d, int e, int c,
+                                         const float* sh_lds, typename P::Vals& best, typename P::Bytes& ba) {
+  typename P::Vals sc, sh;
+  if (BN) {
+    P::load_vals(sh_lds + c * P::kEPP, sc);
+    P::load_vals(sh_lds + 256 + c * P::kEPP, sh);
+  }
+  P::widen(tile[e], best);  // self first
+#pragma unroll
+  for (int q = 0; q < P::kEPP; ++q) {
+    if (BN) best[q] = fmaf(best[q], sc[q], sh[q]);
+    ba[q] = 0;
+  }
+  for (int j = 0; j < d; ++j) {
+    const int sl = nb[j] & GCMI_WIN_MAX_SLOTS;
+    typename P::Vals v;
+    P::widen(tile[sl * LPR + c], v);
+    const unsigned char a = (unsigned char)(j + 1);
+#pragma unroll
+    for (int q = 0; q < P::kEPP; ++q) {
+      if (BN) v[q] = fmaf(v[q], sc[q], sh[q]);
+      if (v[q] > best[q]) { best[q] = v[q]; ba[q] = a; }  // strict >: the first maximum wins
+    }
+  }
+}
+
+// GraphPool backward: acc[k] = g[k]*[arg[k]==0] + sum_j g[i_j]*[arg[i_j] == rev_pos(k,j)+1], g = the rows in `tile`,
+// arg = the bytes in `aux`; the reverse slot rides in the high bits of a neighbour entry
+template <class P, int LPR>
+__device__ __forceinline__ void pool_bwd(const typename P::Raw* tile, const char* aux, const uint16_t* nb, int d, int e,
+                                         int c, typename P::Vals& acc) {
+  typename P::Vals g;
+  P::widen(tile[e], g);
+  typename P::Arg a = P::arg(aux, e);
+#pragma unroll
+  for (int q = 0; q < P::kEPP; ++q) acc[q] = P::arg_byte(a, q) == 0 ? g[q] : 0.f;
+  for (int j = 0; j < d; ++j) {
+    const int en = nb[j];
+    const int sl = en & GCMI_WIN_MAX_SLOTS;
+    const unsigned char want = (unsigned char)((en >> GCMI_WIN_SLOT_BITS) + 1);
+    P::widen(tile[sl * LPR + c], g);
+    a = P::arg(aux, sl * LPR + c);
+#pragma unroll
+    for (int q = 0; q < P::kEPP; ++q) acc[q] += P::arg_byte(a, q) == want ? g[q] : 0.f;
+  }
+}
+
 // ---------------------------------------------------------------- per-window compute phases
-// Rows this thread also needs from HBM in the compute phase (the old value of an accumulated output) are requested for
-// up to kPre elements up front, unconditionally from clamped addresses, and used after the LDS work of all of them:
-// the wait for them is also a wait for the LDS-DMA of the next window (one counter, in order), which the loop would
-// wait for at its top anyway.
-constexpr int kPre = 4;
+// A body holds an operation's fields and its walk over the pieces of a window, for rows of T; the op types below it
+// (the names profiles and bench.py know the kernels by) add what was measured per element type:
+//   kThreads  threads per workgroup;
+//   kPre      pieces per thread and round.  kPre = 4 (fp32 SumOp and MaxBwdOp): rows the thread also needs from HBM in
+//             the compute phase (the old value of an accumulated output) are requested for kPre pieces up front,
+//             unconditionally from clamped addresses, and used after the LDS work of all of them: the wait for them is
+//             also a wait for the LDS-DMA of the next window (one counter, in order), which the loop would wait for at
+//             its top anyway.  kPre = 1: one piece at a time, the old piece loaded before its neighbour loop.
 
-struct NoState {};
-
-// ACC: s += sum of the neighbours' rows (the transposed gather of a backward pass onto the self term)
-template <bool ACC>
-struct SumOp {
-  float* __restrict__ s;
+// s = (ACC: s +) sum of the neighbours' rows (ACC: the transposed gather of a backward pass onto the self term)
+template <class Op, class T, bool ACC>
+struct SumBody {
+  using P = Piece<T>;
+  T* __restrict__ s;
   int64_t lds;
-  using State = NoState;
   static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 4;  // elements per 16-byte piece of a tile row
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
+  __device__ __forceinline__ void init(float*, int) const {}
   template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State&) const {
-    const float4* tile = reinterpret_cast<const float4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e0 = threadIdx.x; e0 < n16; e0 += kPre * WT) {
-      float4 old[kPre];
-      if constexpr (ACC) {
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*) const {
+    constexpr int kPre = Op::kPre;
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    for (int e0 = threadIdx.x; e0 < w.n16; e0 += kPre * WT) {
+      typename P::Raw old[kPre];
+      if constexpr (ACC && kPre > 1) {
 #pragma unroll
         for (int k = 0; k < kPre; ++k) {
-          const int e = e0 + k * WT < n16 ? e0 + k * WT : n16 - 1;
+          const int e = e0 + k * WT < w.n16 ? e0 + k * WT : w.n16 - 1;
           const int slot = e / LPR;
           const int c = e - slot * LPR;
-          old[k] = *reinterpret_cast<const float4*>(s + (int64_t)row_of_slot(m, L.maxd, slot) * lds + c * 4);
+          old[k] = load_piece(s + (int64_t)row_of_slot(m, L.maxd, slot) * lds + c * P::kEPP);
         }
       }
 #pragma unroll
       for (int k = 0; k < kPre; ++k) {
         const int e = e0 + k * WT;
-        if (e >= n16) break;
-        const int slot = e / LPR;
-        const int c = e - slot * LPR;
-        int d, row, eloc;
-        locate(m, L.maxd, slot, d, row, eloc);
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);  // lone atoms: zero
-        for (int j = 0; j < d; ++j) {
-          const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-          const float4 v = tile[sl * LPR + c];
-          acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-        }
-        if constexpr (ACC) {
-          acc.x += old[k].x; acc.y += old[k].y; acc.z += old[k].z; acc.w += old[k].w;
-        }
-        win_store4(s + (int64_t)row * lds + c * 4, acc);
+        if (e >= w.n16) break;
+        const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+        T* dst = s + (int64_t)at.row * lds + at.c * P::kEPP;
+        if constexpr (ACC && kPre == 1) old[0] = load_piece(dst);
+        typename P::Vals acc;
+        neigh_sum<P, LPR>(w.tile, w.ent + at.eloc, at.d, at.c, acc);
+        if constexpr (ACC) add_piece<P>(acc, old[k]);
+        store_piece(dst, acc);
       }
     }
   }
 };
 
-template <bool BN>
-struct MaxOp {
-  const float* __restrict__ scale;
-  const float* __restrict__ shift;
-  float* __restrict__ out;
-  int64_t ldo;
-  uint8_t* __restrict__ arg;
-  static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 4;
-  // measured at 1.2 M atoms, 64 columns (us per launch): 256 threads 131 / 137, 512: 151 / 156, 1 024: 137 / 137 (the
-  // gather-sum is the other way round: 179 / 127 / 149 for 76 columns; the GraphPool backward 166 / 126 / 141)
-  static constexpr int kThreads = 256;
-  // the folded BatchNorm vectors live in LDS: a global load in the compute phase would make the
-  // compiler wait for the LDS-DMA in flight as well
-  using State = NoState;
-  __device__ __forceinline__ bool skip(int) const { return false; }
-  template <int WT>
-  __device__ __forceinline__ void init(float* sh_lds, int n_feat, State&) const {
-    if (BN)
-      for (int i = threadIdx.x; i < n_feat; i += WT) {
-        sh_lds[i] = scale[i];
-        sh_lds[256 + i] = shift[i];
-      }
-  }
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m,
-                                      const float* sh_lds, State&) const {
-    const float4* tile = reinterpret_cast<const float4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float4 sc, sh;
-      if (BN) {
-        sc = *reinterpret_cast<const float4*>(sh_lds + c * 4);
-        sh = *reinterpret_cast<const float4*>(sh_lds + 256 + c * 4);
-      }
-      float4 best = tile[e];  // self first
-      if (BN) {
-        best.x = fmaf(best.x, sc.x, sh.x); best.y = fmaf(best.y, sc.y, sh.y);
-        best.z = fmaf(best.z, sc.z, sh.z); best.w = fmaf(best.w, sc.w, sh.w);
-      }
-      uchar4 ba = make_uchar4(0, 0, 0, 0);
-      for (int j = 0; j < d; ++j) {
-        const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-        float4 v = tile[sl * LPR + c];
-        if (BN) {
-          v.x = fmaf(v.x, sc.x, sh.x); v.y = fmaf(v.y, sc.y, sh.y);
-          v.z = fmaf(v.z, sc.z, sh.z); v.w = fmaf(v.w, sc.w, sh.w);
-        }
-        const unsigned char a = (unsigned char)(j + 1);
-        if (v.x > best.x) { best.x = v.x; ba.x = a; }  // strict >: the first maximum wins
-        if (v.y > best.y) { best.y = v.y; ba.y = a; }
-        if (v.z > best.z) { best.z = v.z; ba.z = a; }
-        if (v.w > best.w) { best.w = v.w; ba.w = a; }
-      }
-      win_store4(out + (int64_t)row * ldo + c * 4, best);
-      if (arg) *reinterpret_cast<uchar4*>(arg + (int64_t)row * (LPR * 4) + c * 4) = ba;
-    }
-  }
+template <bool ACC>
+struct SumOp : SumBody<SumOp<ACC>, float, ACC> {
+  static constexpr int kThreads = 512;  // measured (76 columns, us per launch): 179 / 127 / 149 at 256 / 512 / 1 024
+  static constexpr int kPre = 4;
+};
+// GraphConv.sum_neigh over rows stored as bf16 (the pooled rows of the block below): bf16 in, bf16 out
+struct SumOpH : SumBody<SumOpH, bf16_t, false> {
+  static constexpr int kThreads = 256;  // measured (64 columns, 1.2 M atoms): 58.6 us against 74.4 at 512 and 93.4 at 1 024
+  static constexpr int kPre = 1;
+};
+// s += sum of the neighbours' rows, bf16 in and out (the oversized windows of the two-stage pass over bf16 gradients)
+struct SumAccOpH : SumBody<SumAccOpH, bf16_t, true> {
+  static constexpr int kThreads = 512;
+  static constexpr int kPre = 1;
 };
 
-// dx[k] = dout[k]*[arg[k]==0] + sum_j dout[i_j]*[arg[i_j] == rev_pos(k,j)+1]: tile = dout rows,
-// aux = arg rows of the window.
-struct MaxBwdOp {
-  float* __restrict__ dx;
-  int64_t lddx;
-  // optional (bn_bwd_pool_impl): dx is needed only where the pooled BatchNorm sums are ill-conditioned
-  const float* __restrict__ only_if_gamma;
-  const float* __restrict__ only_if_beta;
-  using State = NoState;
-  static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 4;
-  __device__ __forceinline__ bool skip(int n_feat) const {
-    return only_if_gamma != nullptr && !bn_pool_ill_conditioned(only_if_gamma, only_if_beta, n_feat);
-  }
-  template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State&) const {
-    const float4* tile = reinterpret_cast<const float4*>(buf);
-    const uchar4* atile = reinterpret_cast<const uchar4*>(buf + L.tile_bytes);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e0 = threadIdx.x; e0 < n16; e0 += kPre * WT) {
-#pragma unroll
-      for (int k = 0; k < kPre; ++k) {
-        const int e = e0 + k * WT;
-        if (e >= n16) break;
-        const int slot = e / LPR;
-        const int c = e - slot * LPR;
-        int d, row, eloc;
-        locate(m, L.maxd, slot, d, row, eloc);
-        float4 g = tile[e];
-        uchar4 a = atile[e];
-        float4 acc;
-        acc.x = a.x == 0 ? g.x : 0.f;
-        acc.y = a.y == 0 ? g.y : 0.f;
-        acc.z = a.z == 0 ? g.z : 0.f;
-        acc.w = a.w == 0 ? g.w : 0.f;
-        for (int j = 0; j < d; ++j) {
-          const int en = ent[eloc + j];
-          const int sl = en & GCMI_WIN_MAX_SLOTS;
-          const unsigned char want = (unsigned char)((en >> GCMI_WIN_SLOT_BITS) + 1);
-          g = tile[sl * LPR + c];
-          a = atile[sl * LPR + c];
-          acc.x += a.x == want ? g.x : 0.f;
-          acc.y += a.y == want ? g.y : 0.f;
-          acc.z += a.z == want ? g.z : 0.f;
-          acc.w += a.w == want ? g.w : 0.f;
-        }
-        win_store4(dx + (int64_t)row * lddx + c * 4, acc);
-      }
-    }
-  }
-};
-
-// The backward between two GraphConv blocks in one window pass:
-//   dX[k]  = dXs[k] + sum_j dS[i_j]                 (SumOp<true>: the neighbour part onto the self part)
-//   dy[k]  = dX[k]*[arg[k]==0] + sum_j dX[i_j]*[arg[i_j] == rev_pos(k,j)+1]       (MaxBwdOp of the block below)
-// dX is the gradient of the pooled rows and nothing else reads it, so it lives in a third LDS tile only: it is neither
-// written (N*F floats) nor read back (N*F) through HBM.  tile = dS rows, aux = arg rows of the block below.  The price
-// is LDS: one workgroup per CU instead of two.  Oversized windows are not handled (the launcher refuses).
-struct SumAccMaxBwdOp {
-  const float* __restrict__ dxs;  // self part of dX (global rows)
-  int64_t lddxs;
-  float* __restrict__ dy;
-  int64_t lddy;
-  struct State {
-    char* extra;  // the third tile of the window being computed: [slot][LPR] float4, the dXs rows on entry
-  };
-  static constexpr bool kExtraTile = true;
-  // The third tile is double-buffered and filled by the LDS-DMA with the window's dXs rows (stage_extra): read from HBM
-  // in the compute phase they waited, one in-order counter, for the NEXT window's DMA, so that no window's compute
-  // overlapped the next one's load (281 us at 96-atom windows against 181 at 192-atom ones: a fixed ~3.8 us per window).
-  static constexpr bool kExtraDma = true;
-  static constexpr int kExtraScale = 2;
-  static constexpr int kEPP = 4;
-  __device__ __forceinline__ const char* extra_src() const { return reinterpret_cast<const char*>(dxs); }
-  __device__ __forceinline__ int64_t extra_ld_bytes() const { return lddxs * 4; }
-  __device__ __forceinline__ bool skip(int) const { return false; }
-  template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State& st) const {
-    const float4* tile = reinterpret_cast<const float4*>(buf);
-    const uchar4* atile = reinterpret_cast<const uchar4*>(buf + L.tile_bytes);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    float4* t2 = reinterpret_cast<float4*>(st.extra);
-    const int n16 = m.sb[kND] * LPR;
-    // ---- stage 1: dX of the window = gather(dS) + dXs, in place in the third tile
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int j = 0; j < d; ++j) {
-        const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-        const float4 v = tile[sl * LPR + c];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-      }
-      const float4 old = t2[e];
-      acc.x += old.x; acc.y += old.y; acc.z += old.z; acc.w += old.w;  // same order as SumOp<true>
-      t2[e] = acc;
-    }
-    __syncthreads();
-    // ---- stage 2: the GraphPool backward over it
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float4 g = t2[e];
-      uchar4 a = atile[e];
-      float4 acc;
-      acc.x = a.x == 0 ? g.x : 0.f;
-      acc.y = a.y == 0 ? g.y : 0.f;
-      acc.z = a.z == 0 ? g.z : 0.f;
-      acc.w = a.w == 0 ? g.w : 0.f;
-      for (int j = 0; j < d; ++j) {
-        const int en = ent[eloc + j];
-        const int sl = en & GCMI_WIN_MAX_SLOTS;
-        const unsigned char want = (unsigned char)((en >> GCMI_WIN_SLOT_BITS) + 1);
-        g = t2[sl * LPR + c];
-        a = atile[sl * LPR + c];
-        acc.x += a.x == want ? g.x : 0.f;
-        acc.y += a.y == want ? g.y : 0.f;
-        acc.z += a.z == want ? g.z : 0.f;
-        acc.w += a.w == want ? g.w : 0.f;
-      }
-      win_store4(dy + (int64_t)row * lddy + c * 4, acc);
-    }
-    // (the walker's barrier at the top of the next window comes before the third tile is written again)
-  }
-};
-
-// ---------------------------------------------------------------- bf16 activation storage (gcmi_model_desc.storage == 1)
-// The LDS-DMA moves bytes: a bf16 row of 64 is 8 pieces of 16 bytes, a piece holds 8 elements.  Sums and maxima are
-// formed in fp32 from the widened elements and rounded once (v_cvt_pk_bf16_f32) when the row is stored.
-
-// First GraphConv: the atom features arrive as fp32 rows (the caller's matrix); the sum of the neighbours' rows goes
-// out as bf16, and so does a bf16 copy of the atom's OWN row (it is in LDS anyway), so that the product that follows
-// and the backward read two bf16 operands and the fp32 matrix is read exactly once per step.  Output rows are `ldo`
-// elements; the `pad4` groups of four columns behind the LPR pieces are zeroed (76 -> 80 columns: 16-byte rows).
+// First GraphConv at bf16 storage: the atom features arrive as fp32 rows (the caller's matrix); the sum of the
+// neighbours' rows goes out as bf16, and so does a bf16 copy of the atom's OWN row (it is in LDS anyway), so that the
+// product that follows and the backward read two bf16 operands and the fp32 matrix is read exactly once per step.
+// Output rows are `ldo` elements; the `pad4` groups of four columns behind the LPR pieces are zeroed (76 -> 80 columns:
+// 16-byte rows).
 struct SumOpFH {
+  using P = Piece<float>;
   bf16_t* __restrict__ s;
   bf16_t* __restrict__ xcopy;
   int64_t ldo;
   int pad4;
-  using State = NoState;
   static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 4;
+  static constexpr int kThreads = 512;
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
+  __device__ __forceinline__ void init(float*, int) const {}
   template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State&) const {
-    const float4* tile = reinterpret_cast<const float4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);  // lone atoms: zero
-      for (int j = 0; j < d; ++j) {
-        const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-        const float4 v = tile[sl * LPR + c];
-        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-      }
-      const float4 own = tile[e];
-      bf16_t* srow = s + (int64_t)row * ldo + c * 4;
-      bf16_t* xrow = xcopy + (int64_t)row * ldo + c * 4;
-      *reinterpret_cast<uint2*>(srow) = narrow4(acc.x, acc.y, acc.z, acc.w);
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*) const {
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    for (int e = threadIdx.x; e < w.n16; e += WT) {
+      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      P::Vals acc;
+      neigh_sum<P, LPR>(w.tile, w.ent + at.eloc, at.d, at.c, acc);
+      const float4 own = w.tile[e];
+      bf16_t* srow = s + (int64_t)at.row * ldo + at.c * 4;
+      bf16_t* xrow = xcopy + (int64_t)at.row * ldo + at.c * 4;
+      *reinterpret_cast<uint2*>(srow) = narrow4(acc[0], acc[1], acc[2], acc[3]);
       *reinterpret_cast<uint2*>(xrow) = narrow4(own.x, own.y, own.z, own.w);
-      if (c == LPR - 1) {
+      if (at.c == LPR - 1) {
         for (int z = 1; z <= pad4; ++z) {
           *reinterpret_cast<uint2*>(srow + 4 * z) = make_uint2(0u, 0u);
           *reinterpret_cast<uint2*>(xrow + 4 * z) = make_uint2(0u, 0u);
@@ -496,329 +439,179 @@ struct SumOpFH {
   }
 };
 
-// GraphConv.sum_neigh over rows stored as bf16 (the pooled rows of the block below): bf16 in, bf16 out
-struct SumOpH {
-  bf16_t* __restrict__ s;
-  int64_t lds;
-  using State = NoState;
-  static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 8;
-  static constexpr int kThreads = 256;  // measured (64 columns, 1.2 M atoms): 58.6 us against 74.4 at 512 and 93.4 at 1 024
-  __device__ __forceinline__ bool skip(int) const { return false; }
-  template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State&) const {
-    const uint4* tile = reinterpret_cast<const uint4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float acc[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = 0.f;
-      for (int j = 0; j < d; ++j) {
-        const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-        float v[8];
-        widen8(tile[sl * LPR + c], v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] += v[q];
-      }
-      uint4 o;
-      o.x = pack_bf16x2(acc[0], acc[1]); o.y = pack_bf16x2(acc[2], acc[3]);
-      o.z = pack_bf16x2(acc[4], acc[5]); o.w = pack_bf16x2(acc[6], acc[7]);
-      *reinterpret_cast<uint4*>(s + (int64_t)row * lds + c * 8) = o;
-    }
-  }
-};
-
-// GraphPool over bf16 rows with the folded BatchNorm applied on the fly: candidates y = x * scale + shift in fp32,
-// the first maximum wins (self first, then neighbour order), the winner is rounded once when it is stored
-template <bool BN>
-struct MaxOpH {
+// GraphPool.forward with the folded BatchNorm applied on the fly (BN), the winner stored (bf16: rounded once) with its
+// arg-max bytes
+template <class T, bool BN>
+struct MaxBody {
+  using P = Piece<T>;
   const float* __restrict__ scale;
   const float* __restrict__ shift;
-  bf16_t* __restrict__ out;
+  T* __restrict__ out;
   int64_t ldo;
   uint8_t* __restrict__ arg;
   static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 8;
-  using State = NoState;
   __device__ __forceinline__ bool skip(int) const { return false; }
+  // the folded BatchNorm vectors live in LDS: a global load in the compute phase would make the
+  // compiler wait for the LDS-DMA in flight as well
   template <int WT>
-  __device__ __forceinline__ void init(float* sh_lds, int n_feat, State&) const {
+  __device__ __forceinline__ void init(float* sh_lds, int n_feat) const {
     if (BN)
       for (int i = threadIdx.x; i < n_feat; i += WT) {
         sh_lds[i] = scale[i];
         sh_lds[256 + i] = shift[i];
       }
   }
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
   template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m,
-                                      const float* sh_lds, State&) const {
-    const uint4* tile = reinterpret_cast<const uint4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float sc[8], sh[8];
-      if (BN) {
-        const float4 a0 = *reinterpret_cast<const float4*>(sh_lds + c * 8);
-        const float4 a1 = *reinterpret_cast<const float4*>(sh_lds + c * 8 + 4);
-        const float4 b0 = *reinterpret_cast<const float4*>(sh_lds + 256 + c * 8);
-        const float4 b1 = *reinterpret_cast<const float4*>(sh_lds + 256 + c * 8 + 4);
-        sc[0] = a0.x; sc[1] = a0.y; sc[2] = a0.z; sc[3] = a0.w; sc[4] = a1.x; sc[5] = a1.y; sc[6] = a1.z; sc[7] = a1.w;
-        sh[0] = b0.x; sh[1] = b0.y; sh[2] = b0.z; sh[3] = b0.w; sh[4] = b1.x; sh[5] = b1.y; sh[6] = b1.z; sh[7] = b1.w;
-      }
-      float best[8];
-      widen8(tile[e], best);  // self first
-      unsigned char ba[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        if (BN) best[q] = fmaf(best[q], sc[q], sh[q]);
-        ba[q] = 0;
-      }
-      for (int j = 0; j < d; ++j) {
-        const int sl = ent[eloc + j] & GCMI_WIN_MAX_SLOTS;
-        float v[8];
-        widen8(tile[sl * LPR + c], v);
-        const unsigned char a = (unsigned char)(j + 1);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (BN) v[q] = fmaf(v[q], sc[q], sh[q]);
-          if (v[q] > best[q]) { best[q] = v[q]; ba[q] = a; }  // strict >: the first maximum wins
-        }
-      }
-      uint4 o;
-      o.x = pack_bf16x2(best[0], best[1]); o.y = pack_bf16x2(best[2], best[3]);
-      o.z = pack_bf16x2(best[4], best[5]); o.w = pack_bf16x2(best[6], best[7]);
-      *reinterpret_cast<uint4*>(out + (int64_t)row * ldo + c * 8) = o;
-      if (arg) {
-        uint2 av;
-        av.x = (unsigned)ba[0] | ((unsigned)ba[1] << 8) | ((unsigned)ba[2] << 16) | ((unsigned)ba[3] << 24);
-        av.y = (unsigned)ba[4] | ((unsigned)ba[5] << 8) | ((unsigned)ba[6] << 16) | ((unsigned)ba[7] << 24);
-        *reinterpret_cast<uint2*>(arg + (int64_t)row * (LPR * 8) + c * 8) = av;
-      }
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float* sh_lds) const {
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    for (int e = threadIdx.x; e < w.n16; e += WT) {
+      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      typename P::Vals best;
+      typename P::Bytes ba;
+      pool_max<P, LPR, BN>(w.tile, w.ent + at.eloc, at.d, e, at.c, sh_lds, best, ba);
+      store_piece(out + (int64_t)at.row * ldo + at.c * P::kEPP, best);
+      if (arg) P::store_arg(arg + (int64_t)at.row * (LPR * P::kEPP) + at.c * P::kEPP, ba);
     }
   }
 };
 
-// ---------------------------------------------------------------- gradient streams in bf16 (storage == 2)
-// The gradients that travel between kernels (dpool, dy, dS, dXs) as bf16 rows: the same ops as MaxBwdOp, SumOp<true> and
-// SumAccMaxBwdOp over pieces of eight elements, sums in fp32, one rounding at the store.  The arg-max bytes of a piece
-// are two dwords in the split image stage() writes (aux_lo / aux_hi).
-__device__ __forceinline__ uint2 aux8(const char* buf, const Layout& L, int e) {
-  const unsigned* a = reinterpret_cast<const unsigned*>(buf + L.tile_bytes) + (e >> 6) * 128 + (e & 63);
-  return make_uint2(a[0], a[64]);
-}
-__device__ __forceinline__ unsigned char aux_byte(const uint2 a, int q) {
-  return (unsigned char)((q < 4 ? a.x >> (8 * q) : a.y >> (8 * (q - 4))) & 255u);
-}
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-  uint4 o;
-  o.x = pack_bf16x2(v[0], v[1]); o.y = pack_bf16x2(v[2], v[3]);
-  o.z = pack_bf16x2(v[4], v[5]); o.w = pack_bf16x2(v[6], v[7]);
-  return o;
-}
+template <bool BN>
+struct MaxOp : MaxBody<float, BN> {
+  // measured at 1.2 M atoms, 64 columns (us per launch): 256 threads 131 / 137, 512: 151 / 156, 1 024: 137 / 137 (the
+  // gather-sum is the other way round: 179 / 127 / 149 for 76 columns; the GraphPool backward 166 / 126 / 141)
+  static constexpr int kThreads = 256;
+};
+template <bool BN>
+struct MaxOpH : MaxBody<bf16_t, BN> {
+  static constexpr int kThreads = 512;
+};
 
-// dx[k] = dout[k]*[arg[k]==0] + sum_j dout[i_j]*[arg[i_j] == rev_pos(k,j)+1] over bf16 rows
-struct MaxBwdOpH {
-  bf16_t* __restrict__ dx;
+// GraphPool backward via the reverse slots: tile = dout rows, aux = arg rows of the window
+template <class Op, class T>
+struct MaxBwdBody {
+  using P = Piece<T>;
+  T* __restrict__ dx;
   int64_t lddx;
-  const float* __restrict__ only_if_gamma;  // optional (bn_bwd_pool_impl): dx only where the pooled sums are ill-conditioned
+  // optional (bn_bwd_pool_impl): dx is needed only where the pooled BatchNorm sums are ill-conditioned
+  const float* __restrict__ only_if_gamma;
   const float* __restrict__ only_if_beta;
-  using State = NoState;
   static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 8;
-  static constexpr int kThreads = 256;  // measured: 84.4 us against 92.6 at 512 and 119 at 1 024
   __device__ __forceinline__ bool skip(int n_feat) const {
     return only_if_gamma != nullptr && !bn_pool_ill_conditioned(only_if_gamma, only_if_beta, n_feat);
   }
   template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
+  __device__ __forceinline__ void init(float*, int) const {}
   template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State&) const {
-    const uint4* tile = reinterpret_cast<const uint4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float g[8], acc[8];
-      widen8(tile[e], g);
-      uint2 a = aux8(buf, L, e);
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*) const {
+    constexpr int kPre = Op::kPre;
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    for (int e0 = threadIdx.x; e0 < w.n16; e0 += kPre * WT) {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = aux_byte(a, q) == 0 ? g[q] : 0.f;
-      for (int j = 0; j < d; ++j) {
-        const int en = ent[eloc + j];
-        const int sl = en & GCMI_WIN_MAX_SLOTS;
-        const unsigned char want = (unsigned char)((en >> GCMI_WIN_SLOT_BITS) + 1);
-        widen8(tile[sl * LPR + c], g);
-        a = aux8(buf, L, sl * LPR + c);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] += aux_byte(a, q) == want ? g[q] : 0.f;
+      for (int k = 0; k < kPre; ++k) {
+        const int e = e0 + k * WT;
+        if (e >= w.n16) break;
+        const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+        typename P::Vals acc;
+        pool_bwd<P, LPR>(w.tile, w.aux, w.ent + at.eloc, at.d, e, at.c, acc);
+        store_piece(dx + (int64_t)at.row * lddx + at.c * P::kEPP, acc);
       }
-      *reinterpret_cast<uint4*>(dx + (int64_t)row * lddx + c * 8) = pack8(acc);
     }
   }
 };
 
-// s += sum of the neighbours' rows, bf16 in and out (the oversized windows of the two-stage pass)
-struct SumAccOpH {
-  bf16_t* __restrict__ s;
-  int64_t lds;
-  using State = NoState;
-  static constexpr bool kExtraTile = false;
-  static constexpr int kEPP = 8;
-  __device__ __forceinline__ bool skip(int) const { return false; }
-  template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State&) const {
-    const uint4* tile = reinterpret_cast<const uint4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    const int n16 = m.sb[kND] * LPR;
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      bf16_t* dst = s + (int64_t)row * lds + c * 8;
-      const uint4 old = *reinterpret_cast<const uint4*>(dst);
-      float acc[8], v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = 0.f;
-      for (int j = 0; j < d; ++j) {
-        widen8(tile[(ent[eloc + j] & GCMI_WIN_MAX_SLOTS) * LPR + c], v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] += v[q];
-      }
-      widen8(old, v);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] += v[q];  // same order as SumAccMaxBwdOpH's first stage
-      *reinterpret_cast<uint4*>(dst) = pack8(acc);
-    }
-  }
+struct MaxBwdOp : MaxBwdBody<MaxBwdOp, float> {
+  static constexpr int kThreads = 512;  // measured (us per launch): 166 / 126 / 141 at 256 / 512 / 1 024
+  static constexpr int kPre = 4;
+};
+struct MaxBwdOpH : MaxBwdBody<MaxBwdOpH, bf16_t> {
+  static constexpr int kThreads = 256;  // measured: 84.4 us against 92.6 at 512 and 119 at 1 024
+  static constexpr int kPre = 1;
 };
 
-// SumAccMaxBwdOp over bf16 streams: tile = dS rows, aux = arg rows of the block below, dxs / dy bf16; dX of the window
-// stays fp32 in the third LDS tile (it is never stored, so it is never rounded).  With tiles of half the size two
-// 1 024-thread workgroups... do not fit a CU's thread limit, but two 512-thread ones do.
-struct SumAccMaxBwdOpH {
-  const bf16_t* __restrict__ dxs;  // self part of dX (global rows)
+// The backward between two GraphConv blocks in one window pass:
+//   dX[k]  = dXs[k] + sum_j dS[i_j]                 (SumBody<ACC>: the neighbour part onto the self part)
+//   dy[k]  = dX[k]*[arg[k]==0] + sum_j dX[i_j]*[arg[i_j] == rev_pos(k,j)+1]       (MaxBwdBody of the block below)
+// dX is the gradient of the pooled rows and nothing else reads it, so it lives in a third LDS tile only: it is neither
+// written (N*F elements) nor read back (N*F) through HBM.  tile = dS rows, aux = arg rows of the block below.  The
+// price is LDS.  Oversized windows are not handled (the launcher refuses).
+// The third tile is double-buffered and filled by the LDS-DMA with the window's dXs rows (stage_extra): read from HBM
+// in the compute phase they waited, one in-order counter, for the NEXT window's DMA, so that no window's compute
+// overlapped the next one's load (281 us at 96-atom windows against 181 at 192-atom ones: a fixed ~3.8 us per window).
+// dX is completed IN PLACE in it, in the rows' own element type: over bf16 streams it is rounded to bf16 once, exactly
+// what the two separate passes do when they write dX to HBM as a bf16 matrix between them.
+constexpr int kThirdTiles = 2;  // third tiles per workgroup, each the size of a window tile: one per window buffer
+
+template <class T>
+struct SumAccMaxBwdBody {
+  using P = Piece<T>;
+  const T* __restrict__ dxs;  // self part of dX (global rows)
   int64_t lddxs;
-  bf16_t* __restrict__ dy;
+  T* __restrict__ dy;
   int64_t lddy;
-  struct State {
-    char* extra;  // the third tile of the window being computed: [slot][LPR] pieces of 8 bf16, the dXs rows on entry
-  };
   static constexpr bool kExtraTile = true;
-  // As SumAccMaxBwdOp: the third tile comes by LDS-DMA with the window, one per buffer.  It is a bf16 tile and dX is
-  // completed IN PLACE in it -- rounded to bf16 once, exactly what the two separate passes do when they write dX to
-  // HBM as a bf16 matrix between them -- so the LDS footprint stays that of the former single fp32 tile (two 512-thread
-  // workgroups per CU) and the compute phase reads nothing from HBM.
-  static constexpr bool kExtraDma = true;
-  static constexpr int kExtraScale = 2;
-  static constexpr int kEPP = 8;
   __device__ __forceinline__ const char* extra_src() const { return reinterpret_cast<const char*>(dxs); }
-  __device__ __forceinline__ int64_t extra_ld_bytes() const { return lddxs * 2; }
+  __device__ __forceinline__ int64_t extra_ld_bytes() const { return lddxs * (int64_t)sizeof(T); }
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
-  __device__ __forceinline__ void init(float*, int, State&) const {}
-  template <int WT>
-  __device__ __forceinline__ void finish(char*, int, State&) const {}
+  __device__ __forceinline__ void init(float*, int) const {}
+  // extra: the third tile of the window being computed, [slot][LPR] pieces, the dXs rows on entry
   template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*, State& st) const {
-    const uint4* tile = reinterpret_cast<const uint4*>(buf);
-    const uint16_t* ent = reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes);
-    uint4* t2 = reinterpret_cast<uint4*>(st.extra);
-    const int n16 = m.sb[kND] * LPR;
-    // ---- stage 1: dX of the window = gather(dS) + dXs (fp32 sums), rounded into the third tile
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      float acc[8], v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = 0.f;
-      for (int j = 0; j < d; ++j) {
-        widen8(tile[(ent[eloc + j] & GCMI_WIN_MAX_SLOTS) * LPR + c], v);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] += v[q];
-      }
-      widen8(t2[e], v);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] += v[q];
-      t2[e] = pack8(acc);
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, char* extra) const {
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    typename P::Raw* t2 = reinterpret_cast<typename P::Raw*>(extra);
+    // ---- stage 1: dX of the window = gather(dS) + dXs, in place in the third tile
+    for (int e = threadIdx.x; e < w.n16; e += WT) {
+      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      typename P::Vals acc;
+      neigh_sum<P, LPR>(w.tile, w.ent + at.eloc, at.d, at.c, acc);
+      add_piece<P>(acc, t2[e]);
+      t2[e] = P::narrow(acc);
     }
     __syncthreads();
     // ---- stage 2: the GraphPool backward over it
-    for (int e = threadIdx.x; e < n16; e += WT) {
-      const int slot = e / LPR;
-      const int c = e - slot * LPR;
-      int d, row, eloc;
-      locate(m, L.maxd, slot, d, row, eloc);
-      uint2 a = aux8(buf, L, e);
-      float acc[8], g[8];
-      widen8(t2[e], g);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[q] = aux_byte(a, q) == 0 ? g[q] : 0.f;
-      for (int j = 0; j < d; ++j) {
-        const int en = ent[eloc + j];
-        const int sl = en & GCMI_WIN_MAX_SLOTS;
-        const unsigned char want = (unsigned char)((en >> GCMI_WIN_SLOT_BITS) + 1);
-        widen8(t2[sl * LPR + c], g);
-        a = aux8(buf, L, sl * LPR + c);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) acc[q] += aux_byte(a, q) == want ? g[q] : 0.f;
-      }
-      *reinterpret_cast<uint4*>(dy + (int64_t)row * lddy + c * 8) = pack8(acc);
+    for (int e = threadIdx.x; e < w.n16; e += WT) {
+      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      typename P::Vals acc;
+      pool_bwd<P, LPR>(t2, w.aux, w.ent + at.eloc, at.d, e, at.c, acc);
+      store_piece(dy + (int64_t)at.row * lddy + at.c * P::kEPP, acc);
     }
+    // (the walker's barrier at the top of the next window comes before the third tile is written again)
   }
+};
+
+// fp32 tiles hold one workgroup per CU by LDS, so make it a full one (1 024 threads: 292 us against 346 at 512)
+struct SumAccMaxBwdOp : SumAccMaxBwdBody<float> {
+  static constexpr int kThreads = 1024;
+};
+// bf16 tiles are half the size and two 512-thread workgroups share a CU (288 us against 367 at 1 024; two of 1 024
+// would not fit a CU's thread limit)
+struct SumAccMaxBwdOpH : SumAccMaxBwdBody<bf16_t> {
+  static constexpr int kThreads = 512;
 };
 
 // ---------------------------------------------------------------- the persistent window walker
 // Workgroups [0, g_norm) walk the ordinary windows double-buffered; workgroups [g_norm, gridDim)
 // walk the oversized windows (one big molecule each) using both buffers as one.
-// ops whose third tile is filled by the DMA, one per window buffer (kExtraDma)
-template <class Op>
-static constexpr auto extra_dma(int) -> decltype(Op::kExtraDma) { return Op::kExtraDma; }
-template <class Op>
-static constexpr bool extra_dma(long) { return false; }
-
 template <int WT, int LPR, bool AUX, class Op>
 __global__ void __launch_bounds__(WT)
 win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges, int n_norm, int n_win,
            int g_norm, Layout L, Layout Lbig, const char* __restrict__ x, int64_t ldx,
            const uint8_t* __restrict__ aux, Op op, int rev) {
   // ALL LDS is one array (a second __shared__ object beside an LDS-DMA target makes hipcc wait
-  // vmcnt(0) before every ds_read): [window descriptors: it, it+1, it+2][op constants][2 buffers]
+  // vmcnt(0) before every ds_read): [window descriptors: it, it+1, it+2][op constants][2 buffers][third tiles]
   extern __shared__ __attribute__((aligned(16))) char smem_all[];
   int(*ring)[GCMI_WIN_META_INTS] = reinterpret_cast<int(*)[GCMI_WIN_META_INTS]>(smem_all);
   float* op_lds = reinterpret_cast<float*>(smem_all + kRingBytes);
   char* smem = smem_all + kHeadBytes;
-  if (op.skip(LPR * Op::kEPP)) return;  // uniform over the grid
-  typename Op::State ost;
-  if constexpr (Op::kExtraTile) ost.extra = smem + 2 * L.buf_bytes();  // behind the two window buffers
-  constexpr bool kXD = extra_dma<Op>(0);  // the third tile is per window, DMA-filled (two of them, like the buffers)
-  op.template init<WT>(op_lds, LPR * Op::kEPP, ost);
+  constexpr int kEPP = Op::P::kEPP;
+  constexpr bool kXT = Op::kExtraTile;  // a third tile per window buffer, behind the two, DMA-filled with the window
+  if (op.skip(LPR * kEPP)) return;  // uniform over the grid
+  op.template init<WT>(op_lds, LPR * kEPP);
+  // the compute phase of one window: ops with a third tile get it, the others the op constants
+  auto compute = [&](const char* buf, const Layout& l, const WinMeta& m, char* extra) {
+    if constexpr (kXT) op.template run<WT, LPR>(buf, l, m, extra);
+    else op.template run<WT, LPR>(buf, l, m, op_lds);
+  };
   const int t = threadIdx.x;
   if ((int)blockIdx.x >= g_norm) {  // oversized windows: stage, wait, compute
     const int G = gridDim.x - g_norm;
@@ -826,13 +619,12 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
       if (t < GCMI_WIN_META_INTS) ring[0][t] = meta[(size_t)w * GCMI_WIN_META_INTS + t];
       __syncthreads();
       const WinMeta m = read_meta(ring[0]);
-      stage<WT, LPR, AUX, Op::kEPP>(smem, Lbig, m, x, ldx, aux, edges);
+      stage<WT, LPR, AUX, kEPP>(smem, Lbig, m, x, ldx, aux, edges);
       wait_dma();
       __syncthreads();
-      op.template run<WT, LPR>(smem, Lbig, m, op_lds, ost);
+      compute(smem, Lbig, m, smem + 2 * L.buf_bytes());  // (no launcher sends a two-stage op here)
       __syncthreads();
     }
-    op.template finish<WT>(smem, LPR, ost);
     return;
   }
   const int G = g_norm;
@@ -848,8 +640,8 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
     if (w + 2 * G < n_norm) metareg = meta[widx(w + 2 * G) * GCMI_WIN_META_INTS + t];
   }
   __syncthreads();
-  stage<WT, LPR, AUX, Op::kEPP>(smem, L, read_meta(ring[0]), x, ldx, aux, edges);
-  if constexpr (kXD) stage_extra<WT, LPR>(smem + 2 * bb, L, read_meta(ring[0]), op.extra_src(), op.extra_ld_bytes());
+  stage<WT, LPR, AUX, kEPP>(smem, L, read_meta(ring[0]), x, ldx, aux, edges);
+  if constexpr (kXT) stage_extra<WT, LPR>(smem + 2 * bb, L, read_meta(ring[0]), op.extra_src(), op.extra_ld_bytes());
   int it = 0;
   for (;;) {
     wait_dma();
@@ -860,18 +652,16 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
       if (w + 3 * G < n_norm) metareg = meta[widx(w + 3 * G) * GCMI_WIN_META_INTS + t];
     }
     if (has_next) {
-      stage<WT, LPR, AUX, Op::kEPP>(smem + ((it + 1) & 1) * bb, L, read_meta(ring[(it + 1) % 3]), x, ldx, aux, edges);
-      if constexpr (kXD)
+      stage<WT, LPR, AUX, kEPP>(smem + ((it + 1) & 1) * bb, L, read_meta(ring[(it + 1) % 3]), x, ldx, aux, edges);
+      if constexpr (kXT)
         stage_extra<WT, LPR>(smem + 2 * bb + ((it + 1) & 1) * L.tile_bytes, L, read_meta(ring[(it + 1) % 3]), op.extra_src(),
                              op.extra_ld_bytes());
     }
-    if constexpr (kXD) ost.extra = smem + 2 * bb + (it & 1) * L.tile_bytes;
-    op.template run<WT, LPR>(smem + (it & 1) * bb, L, read_meta(ring[it % 3]), op_lds, ost);
+    compute(smem + (it & 1) * bb, L, read_meta(ring[it % 3]), smem + 2 * bb + (it & 1) * L.tile_bytes);
     if (!has_next) break;
     w += G;
     ++it;
   }
-  op.template finish<WT>(smem, LPR, ost);
 }
 
 // ------------------------------------------------------------------ host-side dispatch helpers
@@ -918,31 +708,23 @@ static WinPlan make_plan(const gcmi_graph* g, int n_feat, int aux) {
   return p;
 }
 
-bool win_usable(const gcmi_graph* g, int n_feat, bool aux) {
+// the batch has window plans and a tile row of n_floats floats (+ aux) fits the LDS
+static bool plan_fits(const gcmi_graph* g, int n_floats, int aux) {
   if (windows_disabled() || g->d_win_meta == nullptr || g->n_win <= 0) return false;
   if (g->d_win_edges == nullptr || g->n_win_big < 0 || g->n_win_big > g->n_win) return false;
-  if (n_feat % 4 != 0 || n_feat > 256) return false;
-  return make_plan(g, n_feat, aux ? 4 : 0).ok;
+  return make_plan(g, n_floats, aux).ok;
 }
-
-// threads per workgroup: what an op asks for (kThreads), 512 when it has no preference.  The two-stage ops
-// (kExtraTile): fp32 tiles hold one workgroup per CU by LDS, so make it a full one (1 024 threads: 292 us against 346
-// at 512); bf16 tiles are half the size and two 512-thread workgroups share a CU (288 us against 367 at 1 024).
-template <class Op>
-static constexpr auto op_threads(int) -> decltype(Op::kThreads) { return Op::kThreads; }
-template <class Op>
-static constexpr int op_threads(long) { return 512; }
-template <class Op>
-static constexpr int win_threads() {
-  if constexpr (Op::kExtraTile) return Op::kEPP == 8 ? 512 : 1024;
-  else return op_threads<Op>(0);
+// ... and so do the third tiles of the two-stage pass
+static bool third_tiles_fit(const gcmi_graph* g, int n_floats, int aux) {
+  const WinPlan p = make_plan(g, n_floats, aux);
+  return p.shmem + (size_t)kThirdTiles * p.L.tile_bytes <= (size_t)kLdsPerCU;
 }
 
 // which: 0 all windows, 1 ordinary, 2 oversized only
 template <int LPR, bool AUX, class Op>
 static int launch_lpr(const gcmi_graph* g, const WinPlan& p, const char* x, int64_t ldx, const uint8_t* aux,
                       const Op& op, hipStream_t st, const char* what, int which) {
-  constexpr int WT = win_threads<Op>();
+  constexpr int WT = Op::kThreads;
   auto kern = win_kernel<WT, LPR, AUX, Op>;
   static LdsLimit lim;  // per instantiation
   if (!raise_lds_limit(lim, reinterpret_cast<const void*>(kern), kLdsPerCU)) {
@@ -956,7 +738,7 @@ static int launch_lpr(const gcmi_graph* g, const WinPlan& p, const char* x, int6
       set_error("%s: oversized windows are not handled by the two-stage form", what);
       return GCMI_ERR_UNSUPPORTED;
     }
-    shmem += (size_t)p.L.tile_bytes * Op::kExtraScale;  // the third tile, in units of the window tile
+    shmem += (size_t)p.L.tile_bytes * kThirdTiles;
     if (shmem > (size_t)kLdsPerCU) return GCMI_ERR_UNSUPPORTED;
   }
   const int by_lds = (int)((size_t)kLdsPerCU / shmem);
@@ -971,77 +753,102 @@ static int launch_lpr(const gcmi_graph* g, const WinPlan& p, const char* x, int6
   return GCMI_OK;
 }
 
-template <bool AUX, class Op>
-static int launch(const gcmi_graph* g, int n_feat, const float* x, int64_t ldx, const uint8_t* aux,
-                  const Op& op, hipStream_t st, const char* what, int which = 0) {
-  const WinPlan p = make_plan(g, n_feat, AUX ? 4 : 0);
+// Rows of T, n_feat elements = n_feat / kEPP pieces each (fp32: 64 -> 16, 76 -> 19, 128 -> 32; bf16: 64 -> 8, 80 -> 10,
+// 128 -> 16); AUX: the byte matrix `aux` (one byte per element) rides along.  The DMA moves bytes, so the leading
+// dimension goes down in bytes and the plan counts a tile row in floats.
+template <bool AUX, class T, class Op>
+static int launch(const gcmi_graph* g, int n_feat, const T* x, int64_t ldx, const uint8_t* aux, const Op& op,
+                  hipStream_t st, const char* what, int which = 0) {
+  using P = Piece<T>;
+  constexpr bool kH = P::kEPP == 8;
+  const WinPlan p = make_plan(g, n_feat * (int)sizeof(T) / 4, AUX ? P::kEPP : 0);
   const char* xb = reinterpret_cast<const char*>(x);
-  switch (n_feat / 4) {
-    case 16: return launch_lpr<16, AUX, Op>(g, p, xb, ldx * 4, aux, op, st, what, which);
-    case 19: return launch_lpr<19, AUX, Op>(g, p, xb, ldx * 4, aux, op, st, what, which);
-    case 32: return launch_lpr<32, AUX, Op>(g, p, xb, ldx * 4, aux, op, st, what, which);
+  const int64_t ldb = ldx * (int64_t)sizeof(T);
+  switch (n_feat / P::kEPP) {
+    case 8: if constexpr (kH) return launch_lpr<8, AUX, Op>(g, p, xb, ldb, aux, op, st, what, which); break;
+    case 10: if constexpr (kH) return launch_lpr<10, AUX, Op>(g, p, xb, ldb, aux, op, st, what, which); break;
+    case 16: return launch_lpr<16, AUX, Op>(g, p, xb, ldb, aux, op, st, what, which);
+    case 19: if constexpr (!kH) return launch_lpr<19, AUX, Op>(g, p, xb, ldb, aux, op, st, what, which); break;
+    case 32: if constexpr (!kH) return launch_lpr<32, AUX, Op>(g, p, xb, ldb, aux, op, st, what, which); break;
     default: break;
   }
-  set_error("%s: no window kernel for %d features", what, n_feat);
+  set_error(kH ? "%s: no bf16 window kernel for %d features" : "%s: no window kernel for %d features", what, n_feat);
   return GCMI_ERR_UNSUPPORTED;
 }
 
-// rows of bf16: n_feat elements = n_feat / 8 pieces (64 -> 8, 80 -> 10, 128 -> 16)
-template <class Op, bool AUX = false>
-static int launch_h(const gcmi_graph* g, int n_feat, const bf16_t* x, int64_t ldx, const Op& op, hipStream_t st,
-                    const char* what, int which = 0, const uint8_t* aux = nullptr) {
-  const WinPlan p = make_plan(g, n_feat / 2, AUX ? 8 : 0);
-  const char* xb = reinterpret_cast<const char*>(x);
-  switch (n_feat / 8) {
-    case 8: return launch_lpr<8, AUX, Op>(g, p, xb, ldx * 2, aux, op, st, what, which);
-    case 10: return launch_lpr<10, AUX, Op>(g, p, xb, ldx * 2, aux, op, st, what, which);
-    case 16: return launch_lpr<16, AUX, Op>(g, p, xb, ldx * 2, aux, op, st, what, which);
-    default: break;
-  }
-  set_error("%s: no bf16 window kernel for %d features", what, n_feat);
-  return GCMI_ERR_UNSUPPORTED;
+// d_dxs holds the self part of dX on entry; on return d_dy holds the GraphPool backward of the complete dX.  The
+// ordinary windows take the two-stage pass (dX in LDS only); the few oversized ones (a molecule above the window cap
+// each) take the two separate passes over their own rows, which completes d_dxs there.  GCMI_ERR_UNSUPPORTED: no LDS
+// for the third tiles.  what: the names of the three launches
+template <class TwoStage, class SumAcc, class Bwd, class T>
+static int sumacc_max_bwd(const gcmi_graph* g, const T* d_ds, int64_t ldds, int n_feat, T* d_dxs, int64_t lddxs,
+                          const uint8_t* d_arg, T* d_dy, int64_t lddy, hipStream_t st, const char* const (&what)[3]) {
+  TwoStage op{{d_dxs, lddxs, d_dy, lddy}};
+  int rc = launch<true>(g, n_feat, d_ds, ldds, d_arg, op, st, what[0], 1);
+  if (rc || g->n_win_big == 0) return rc;
+  SumAcc acc{{d_dxs, lddxs}};
+  rc = launch<false>(g, n_feat, d_ds, ldds, nullptr, acc, st, what[1], 2);
+  if (rc) return rc;
+  Bwd mb{{d_dy, lddy, nullptr, nullptr}};
+  return launch<true>(g, n_feat, d_dxs, lddxs, d_arg, mb, st, what[2], 2);
 }
 
+// ------------------------------------------------------------------ entry points (common.h)
 bool win_has_width(int n_feat) { return n_feat == 64 || n_feat == 76 || n_feat == 128; }
+
+bool win_usable(const gcmi_graph* g, int n_feat, bool aux) {
+  if (n_feat % 4 != 0 || n_feat > 256) return false;
+  return plan_fits(g, n_feat, aux ? 4 : 0);
+}
 
 int win_gather_sum(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_feat, float* d_s,
                    int64_t lds, hipStream_t st, bool accumulate) {
   if (accumulate) {
-    SumOp<true> op{d_s, lds};
+    SumOp<true> op{{d_s, lds}};
     return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_sum (accumulate)");
   }
-  SumOp<false> op{d_s, lds};
+  SumOp<false> op{{d_s, lds}};
   return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_sum");
 }
 
 int win_gather_max(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_feat, const float* d_scale,
                    const float* d_shift, float* d_out, int64_t ldo, uint8_t* d_arg, hipStream_t st) {
   if (d_scale) {
-    MaxOp<true> op{d_scale, d_shift, d_out, ldo, d_arg};
+    MaxOp<true> op{{d_scale, d_shift, d_out, ldo, d_arg}};
     return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_max");
   }
-  MaxOp<false> op{nullptr, nullptr, d_out, ldo, d_arg};
+  MaxOp<false> op{{nullptr, nullptr, d_out, ldo, d_arg}};
   return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_max");
 }
 
 int win_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat,
                        const uint8_t* d_arg, float* d_dx, int64_t lddx, hipStream_t st) {
-  MaxBwdOp op{d_dx, lddx, nullptr, nullptr};
+  MaxBwdOp op{{d_dx, lddx, nullptr, nullptr}};
   return launch<true>(g, n_feat, d_dout, lddo, d_arg, op, st, "win_gather_max_bwd");
 }
 
 int win_gather_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
                               float* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, hipStream_t st) {
-  MaxBwdOp op{d_dx, lddx, d_gamma, d_beta};
+  MaxBwdOp op{{d_dx, lddx, d_gamma, d_beta}};
   return launch<true>(g, n_feat, d_dout, lddo, d_arg, op, st, "win_gather_max_bwd (conditional)");
 }
 
-// ---- bf16 activation storage
+bool win_two_stage_usable(const gcmi_graph* g, int n_feat) {
+  return win_has_width(n_feat) && win_usable(g, n_feat, true) && third_tiles_fit(g, n_feat, 4);
+}
+
+int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int n_feat, float* d_dxs,
+                              int64_t lddxs, const uint8_t* d_arg, float* d_dy, int64_t lddy, hipStream_t st) {
+  return sumacc_max_bwd<SumAccMaxBwdOp, SumOp<true>, MaxBwdOp>(
+      g, d_ds, ldds, n_feat, d_dxs, lddxs, d_arg, d_dy, lddy, st,
+      {"win_gather_sumacc_max_bwd", "win_gather_sum (accumulate, oversized windows)",
+       "win_gather_max_bwd (oversized windows)"});
+}
+
+// ---- bf16 activation storage (storage >= 1)
 bool win_usable_h(const gcmi_graph* g, int n_feat) {
-  if (windows_disabled() || g->d_win_meta == nullptr || g->n_win <= 0) return false;
-  if (g->d_win_edges == nullptr || g->n_win_big < 0 || g->n_win_big > g->n_win) return false;
   if (n_feat != 64 && n_feat != 80 && n_feat != 128) return false;
-  return make_plan(g, n_feat / 2, 0).ok;
+  return plan_fits(g, n_feat / 2, 0);
 }
 
 // fp32 rows of n_feat (76) columns -> bf16 neighbour sums and a bf16 copy of the rows, both `ldo` (80) wide
@@ -1057,73 +864,39 @@ int win_gather_sum_fh(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_
 
 int win_gather_sum_h(const gcmi_graph* g, const bf16_t* d_x, int64_t ldx, int n_feat, bf16_t* d_s, int64_t lds,
                      hipStream_t st) {
-  SumOpH op{d_s, lds};
-  return launch_h(g, n_feat, d_x, ldx, op, st, "win_gather_sum (bf16)");
+  SumOpH op{{d_s, lds}};
+  return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_sum (bf16)");
 }
 
 int win_gather_max_h(const gcmi_graph* g, const bf16_t* d_x, int64_t ldx, int n_feat, const float* d_scale,
                      const float* d_shift, bf16_t* d_out, int64_t ldo, uint8_t* d_arg, hipStream_t st) {
   if (d_scale) {
-    MaxOpH<true> op{d_scale, d_shift, d_out, ldo, d_arg};
-    return launch_h(g, n_feat, d_x, ldx, op, st, "win_gather_max (bf16)");
+    MaxOpH<true> op{{d_scale, d_shift, d_out, ldo, d_arg}};
+    return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_max (bf16)");
   }
-  MaxOpH<false> op{nullptr, nullptr, d_out, ldo, d_arg};
-  return launch_h(g, n_feat, d_x, ldx, op, st, "win_gather_max (bf16)");
+  MaxOpH<false> op{{nullptr, nullptr, d_out, ldo, d_arg}};
+  return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_max (bf16)");
 }
 
-// ---- gradient streams in bf16 (storage == 2)
-bool win_usable_gh(const gcmi_graph* g, int n_feat) {
-  if (windows_disabled() || g->d_win_meta == nullptr || g->n_win <= 0) return false;
-  if (g->d_win_edges == nullptr || g->n_win_big < 0 || g->n_win_big > g->n_win || n_feat != 64) return false;
-  return make_plan(g, n_feat / 2, 8).ok;
-}
+// ---- gradient streams in bf16 (storage == 2): dpool, dy, dS and dXs travel between kernels as bf16 rows
+bool win_usable_gh(const gcmi_graph* g, int n_feat) { return n_feat == 64 && plan_fits(g, n_feat / 2, 8); }
 
 int win_gather_max_bwd_h(const gcmi_graph* g, const bf16_t* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
                          bf16_t* d_dx, int64_t lddx, const float* only_if_gamma, const float* only_if_beta, hipStream_t st) {
-  MaxBwdOpH op{d_dx, lddx, only_if_gamma, only_if_beta};
-  return launch_h<MaxBwdOpH, true>(g, n_feat, d_dout, lddo, op, st, "win_gather_max_bwd (bf16)", 0, d_arg);
+  MaxBwdOpH op{{d_dx, lddx, only_if_gamma, only_if_beta}};
+  return launch<true>(g, n_feat, d_dout, lddo, d_arg, op, st, "win_gather_max_bwd (bf16)");
 }
 
 bool win_two_stage_usable_h(const gcmi_graph* g, int n_feat) {
-  if (!win_usable_gh(g, n_feat)) return false;
-  const WinPlan p = make_plan(g, n_feat / 2, 8);
-  return p.shmem + (size_t)2 * p.L.tile_bytes <= (size_t)kLdsPerCU;
+  return win_usable_gh(g, n_feat) && third_tiles_fit(g, n_feat / 2, 8);
 }
 
-// d_dxs holds the self part of dX on entry (bf16); on return d_dy holds the GraphPool backward of the complete dX.
 int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const bf16_t* d_ds, int64_t ldds, int n_feat, bf16_t* d_dxs,
                                 int64_t lddxs, const uint8_t* d_arg, bf16_t* d_dy, int64_t lddy, hipStream_t st) {
-  SumAccMaxBwdOpH op{d_dxs, lddxs, d_dy, lddy};
-  int rc = launch_h<SumAccMaxBwdOpH, true>(g, n_feat, d_ds, ldds, op, st, "win_gather_sumacc_max_bwd (bf16)", 1, d_arg);
-  if (rc || g->n_win_big == 0) return rc;
-  SumAccOpH acc{d_dxs, lddxs};
-  rc = launch_h(g, n_feat, d_ds, ldds, acc, st, "win_gather_sum (bf16, accumulate, oversized windows)", 2);
-  if (rc) return rc;
-  MaxBwdOpH mb{d_dy, lddy, nullptr, nullptr};
-  return launch_h<MaxBwdOpH, true>(g, n_feat, d_dxs, lddxs, mb, st, "win_gather_max_bwd (bf16, oversized windows)", 2, d_arg);
-}
-
-// dy = GraphPool backward of (dXs + gather of dS), dX kept in LDS only.  GCMI_ERR_UNSUPPORTED: oversized windows in
-// the batch, or no LDS for the third tile.
-bool win_two_stage_usable(const gcmi_graph* g, int n_feat) {
-  if (!win_has_width(n_feat) || !win_usable(g, n_feat, true)) return false;
-  const WinPlan p = make_plan(g, n_feat, 4);
-  return p.shmem + (size_t)2 * p.L.tile_bytes <= (size_t)kLdsPerCU;  // two third tiles (SumAccMaxBwdOp::kExtraScale)
-}
-
-// d_dxs holds the self part of dX on entry; on return d_dy holds the GraphPool backward of the complete dX.  The
-// ordinary windows take the two-stage pass (dX in LDS only); the few oversized ones (a molecule above the window cap
-// each) take the two separate passes over their own rows, which completes d_dxs there.
-int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int n_feat, float* d_dxs,
-                              int64_t lddxs, const uint8_t* d_arg, float* d_dy, int64_t lddy, hipStream_t st) {
-  SumAccMaxBwdOp op{d_dxs, lddxs, d_dy, lddy};
-  int rc = launch<true>(g, n_feat, d_ds, ldds, d_arg, op, st, "win_gather_sumacc_max_bwd", 1);
-  if (rc || g->n_win_big == 0) return rc;
-  SumOp<true> acc{d_dxs, lddxs};
-  rc = launch<false>(g, n_feat, d_ds, ldds, nullptr, acc, st, "win_gather_sum (accumulate, oversized windows)", 2);
-  if (rc) return rc;
-  MaxBwdOp mb{d_dy, lddy, nullptr, nullptr};
-  return launch<true>(g, n_feat, d_dxs, lddxs, d_arg, mb, st, "win_gather_max_bwd (oversized windows)", 2);
+  return sumacc_max_bwd<SumAccMaxBwdOpH, SumAccOpH, MaxBwdOpH>(
+      g, d_ds, ldds, n_feat, d_dxs, lddxs, d_arg, d_dy, lddy, st,
+      {"win_gather_sumacc_max_bwd (bf16)", "win_gather_sum (bf16, accumulate, oversized windows)",
+       "win_gather_max_bwd (bf16, oversized windows)"});
 }
 
 }  // namespace gcmi
