@@ -44,11 +44,9 @@ constexpr int kSlots = 2 * kAhead;   // two sets of them
 
 // A collated batch as the kernels see it (by value in the kernarg segment).
 struct SmallGraph {
-  int32_t n_atoms, n_mols, max_deg, n_tiles;
-  int32_t diag;  // GCMI_SMALL_DIAG: parts of the kernels switched off for timing experiments (results are wrong then)
+  int32_t n_atoms, n_mols, n_tiles;
   int32_t bf16;  // activations the step writes (GraphConv outputs, pooled rows, dense output) are stored as bf16
-  int32_t deg_start[GCMI_MAX_DEG + 2];
-  int32_t edge_start[GCMI_MAX_DEG + 2];
+  DegTable deg;
   int32_t tile_start[GCMI_MAX_DEG + 2];  // 16-row tiles per degree block, prefix
   const int32_t* col_idx;
   const int32_t* membership;
@@ -56,21 +54,46 @@ struct SmallGraph {
   const uint8_t* rev_pos;
 };
 
-struct Tile {
-  int d, row0, nrows, e0;  // degree, first row, rows (<= 16), first edge of row0
-};
-
-__device__ __forceinline__ Tile tile_of(const SmallGraph& g, int t) {
+// The degree block that holds position i of a prefix over the blocks (rows: deg_start, tiles: tile_start, slabs:
+// slab_start): how many of the blocks 1..max_deg start at or below i.
+__device__ __forceinline__ int block_of(const int32_t* start, int max_deg, int i) {
   int d = 0;
 #pragma unroll
-  for (int k = 1; k <= GCMI_MAX_DEG; ++k) d += (k <= g.max_deg && t >= g.tile_start[k]) ? 1 : 0;
+  for (int k = 1; k <= GCMI_MAX_DEG; ++k) d += (k <= max_deg && i >= start[k]) ? 1 : 0;
+  return d;
+}
+__device__ __forceinline__ int degree_of(const SmallGraph& g, int row) {
+  return block_of(g.deg.deg_start, g.deg.max_deg, row);
+}
+
+struct Tile {
+  int d, row0, nrows, e0;  // degree, first row, rows (<= ROWS), first edge of row0
+};
+
+// piece i of the ROWS-row pieces the degree blocks are cut into (`start`: pieces per block, prefix)
+template <int ROWS>
+__device__ __forceinline__ Tile rows_of(const SmallGraph& g, const int32_t* start, int i) {
+  const int d = block_of(start, g.deg.max_deg, i);
   Tile tl;
   tl.d = d;
-  tl.row0 = g.deg_start[d] + (t - g.tile_start[d]) * kTileRows;
-  const int left = g.deg_start[d + 1] - tl.row0;
-  tl.nrows = left < kTileRows ? left : kTileRows;
-  tl.e0 = g.edge_start[d] + (tl.row0 - g.deg_start[d]) * d;
+  tl.row0 = g.deg.deg_start[d] + (i - start[d]) * ROWS;
+  const int left = g.deg.deg_start[d + 1] - tl.row0;
+  tl.nrows = left < ROWS ? left : ROWS;
+  tl.e0 = g.deg.edge_start[d] + (tl.row0 - g.deg.deg_start[d]) * d;
   return tl;
+}
+__device__ __forceinline__ Tile tile_of(const SmallGraph& g, int t) { return rows_of<kTileRows>(g, g.tile_start, t); }
+
+// Where the weights (or biases) of degree d sit in a GraphConv's W_list: rel_1, self_1, ..., rel_max, self_max,
+// self_0 (layers.py:6189-6224).  Degree 0 has no neighbour term: rel < 0.
+struct DegBlocks {
+  int rel, self;
+};
+__device__ __forceinline__ DegBlocks deg_blocks(int d, int max_deg) {
+  DegBlocks b;
+  b.rel = d == 0 ? -1 : 2 * (d - 1);
+  b.self = d == 0 ? 2 * max_deg : 2 * (d - 1) + 1;
+  return b;
 }
 
 __device__ __forceinline__ f4v mfma16(float a, float b, f4v c) {
@@ -172,9 +195,45 @@ __device__ __forceinline__ void stA1(int bf, float* p, int64_t idx, float v) {  
     reinterpret_cast<uint16_t*>(p)[idx] = (uint16_t)(__float_as_uint(v) >> 16);
 }
 
+// ---- the same thing on the four lanes of a column quad
+__device__ __forceinline__ float4 fold4(const float4& v, const float4& sc, const float4& sh) {  // folded BatchNorm
+  return make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
+}
+__device__ __forceinline__ float4 round4(int bf, const float4& v) {
+  return bf ? make_float4(round_act(1, v.x), round_act(1, v.y), round_act(1, v.z), round_act(1, v.w)) : v;
+}
+__device__ __forceinline__ void add4(float4& s, const float4& v) {
+  s.x += v.x;
+  s.y += v.y;
+  s.z += v.z;
+  s.w += v.w;
+}
+// GraphPool's arg-max of a quad: one byte per column, 0 = the row itself, j + 1 = neighbour j of its list.  The first
+// maximum wins (self, then the neighbours in table order: layers.py:6353-6361; torch.max(dim) tie rule), so a later
+// row replaces the best one only when it is greater.
+__device__ __forceinline__ void max4_first(float4& best, uint4& a, const float4& y, uint32_t j) {
+  if (y.x > best.x) { best.x = y.x; a.x = j; }
+  if (y.y > best.y) { best.y = y.y; a.y = j; }
+  if (y.z > best.z) { best.z = y.z; a.z = j; }
+  if (y.w > best.w) { best.w = y.w; a.w = j; }
+}
+__device__ __forceinline__ uint32_t arg_pack(const uint4& a) { return a.x | (a.y << 8) | (a.z << 16) | (a.w << 24); }
+__device__ __forceinline__ uint32_t arg_byte(uint32_t a, int e) { return (a >> (8 * e)) & 0xffu; }
+// the packed bytes of quad q of a row (arg: N x W bytes)
+__device__ __forceinline__ uint32_t& arg_word(uint8_t* arg, int64_t row, int W, int q) {
+  return *reinterpret_cast<uint32_t*>(arg + row * W + 4 * q);
+}
+__device__ __forceinline__ uint32_t arg_word(const uint8_t* arg, int64_t row, int W, int q) {
+  return *reinterpret_cast<const uint32_t*>(arg + row * W + 4 * q);
+}
+// v where the arg byte of the column equals `want`, else 0
+__device__ __forceinline__ float4 arg_pick(uint32_t a, uint32_t want, const float4& v) {
+  return make_float4(arg_byte(a, 0) == want ? v.x : 0.f, arg_byte(a, 1) == want ? v.y : 0.f,
+                     arg_byte(a, 2) == want ? v.z : 0.f, arg_byte(a, 3) == want ? v.w : 0.f);
+}
+
 // ------------------------------------------------------------------------------------------------ pooled row chunk
-// One row of GraphPool over the folded BatchNorm of gc: max over {self} U neighbours, first maximum wins
-// (self, then neighbours in table order: layers.py:6353-6361; torch.max(dim) tie rule).  arg: 0 = self, j+1.
+// One row of GraphPool over the folded BatchNorm of gc: max over {self} U neighbours (max4_first).
 // Folded BatchNorm of the four columns of quad q, in registers: every thread derives the coefficients of ITS
 // columns from the accumulated sums itself (the loads go out together with the thread's first gather loads; a
 // fold through LDS would put a barrier and one more memory round trip in front of them).
@@ -206,7 +265,7 @@ __device__ __forceinline__ void pool_chunk(const SmallGraph& g, int row, int d, 
                                            uint32_t& arg) {
   float4 v = ldA(g.bf16, gc, row, W, q);
   const int32_t* nb = g.col_idx + e;
-  uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+  uint4 a = make_uint4(0, 0, 0, 0);
   bool first = true;
   for (int j0 = 0; j0 < d || first; j0 += 4) {
     int id[4];
@@ -216,23 +275,14 @@ __device__ __forceinline__ void pool_chunk(const SmallGraph& g, int row, int d, 
 #pragma unroll
     for (int t = 0; t < 4; ++t) u[t] = ldA(g.bf16, gc, id[t], W, q);
     if (first) {
-      best = make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
+      best = fold4(v, sc, sh);
       first = false;
     }
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (j0 + t < d) {
-        const float y0 = fmaf(u[t].x, sc.x, sh.x), y1 = fmaf(u[t].y, sc.y, sh.y), y2 = fmaf(u[t].z, sc.z, sh.z),
-                    y3 = fmaf(u[t].w, sc.w, sh.w);
-        const uint32_t j = j0 + t + 1;
-        if (y0 > best.x) { best.x = y0; a0 = j; }
-        if (y1 > best.y) { best.y = y1; a1 = j; }
-        if (y2 > best.z) { best.z = y2; a2 = j; }
-        if (y3 > best.w) { best.w = y3; a3 = j; }
-      }
-    }
+    for (int t = 0; t < 4; ++t)
+      if (j0 + t < d) max4_first(best, a, fold4(u[t], sc, sh), j0 + t + 1);
   }
-  arg = a0 | (a1 << 8) | (a2 << 16) | (a3 << 24);
+  arg = arg_pack(a);
 }
 
 // sum of the d neighbour rows (quad q), four rows in flight per round
@@ -248,21 +298,9 @@ __device__ __forceinline__ float4 gather_sum_quad(int bf, const float* __restric
     for (int t = 0; t < 4; ++t) u[t] = ldA(bf, x, id[t], ld, q);
 #pragma unroll
     for (int t = 0; t < 4; ++t)
-      if (j0 + t < d) {
-        s.x += u[t].x;
-        s.y += u[t].y;
-        s.z += u[t].z;
-        s.w += u[t].w;
-      }
+      if (j0 + t < d) add4(s, u[t]);
   }
   return s;
-}
-
-__device__ __forceinline__ int degree_of(const SmallGraph& g, int row) {
-  int d = 0;
-#pragma unroll
-  for (int k = 1; k <= GCMI_MAX_DEG; ++k) d += (k <= g.max_deg && row >= g.deg_start[k]) ? 1 : 0;
-  return d;
 }
 
 // Own pooled row and the sum of the neighbours' pooled rows (quad q) for an atom of degree d <= 4 whose neighbours
@@ -283,7 +321,7 @@ __device__ __forceinline__ bool pool_two_hop(const SmallGraph& g, int row, int d
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     dn[t] = t < d ? degree_of(g, id[t]) : 0;
-    nn[t] = g.col_idx + g.edge_start[dn[t]] + (id[t] - g.deg_start[dn[t]]) * dn[t];
+    nn[t] = g.col_idx + g.deg.edge_start[dn[t]] + (id[t] - g.deg.deg_start[dn[t]]) * dn[t];
     ok = ok && dn[t] <= 4;
   }
   if (!ok) return false;
@@ -300,47 +338,36 @@ __device__ __forceinline__ bool pool_two_hop(const SmallGraph& g, int row, int d
   for (int t = 0; t < 4; ++t)
 #pragma unroll
     for (int k = 0; k < 4; ++k) r2[t][k] = ldA(g.bf16, gc, id2[t][k], W, q);
-  auto bnq = [&](const float4& v) {
-    return make_float4(fmaf(v.x, sc.x, sh.x), fmaf(v.y, sc.y, sh.y), fmaf(v.z, sc.z, sh.z), fmaf(v.w, sc.w, sh.w));
-  };
-  self = bnq(own);
-  uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+  self = fold4(own, sc, sh);
+  uint4 a = make_uint4(0, 0, 0, 0);
   nsum = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     if (t < d) {
-      const float4 y = bnq(r1[t]);
-      if (y.x > self.x) { self.x = y.x; a0 = t + 1; }
-      if (y.y > self.y) { self.y = y.y; a1 = t + 1; }
-      if (y.z > self.z) { self.z = y.z; a2 = t + 1; }
-      if (y.w > self.w) { self.w = y.w; a3 = t + 1; }
+      const float4 y = fold4(r1[t], sc, sh);
+      max4_first(self, a, y, t + 1);
       float4 p = y;  // pooled row of neighbour t: its own row, then its neighbours
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (k < dn[t]) {
-          const float4 z = bnq(r2[t][k]);
+          const float4 z = fold4(r2[t][k], sc, sh);
           p.x = fmaxf(p.x, z.x);
           p.y = fmaxf(p.y, z.y);
           p.z = fmaxf(p.z, z.z);
           p.w = fmaxf(p.w, z.w);
         }
       }
-      if (g.bf16) p = make_float4(round_act(1, p.x), round_act(1, p.y), round_act(1, p.z), round_act(1, p.w));
-      nsum.x += p.x;
-      nsum.y += p.y;
-      nsum.z += p.z;
-      nsum.w += p.w;
+      add4(nsum, round4(g.bf16, p));
     }
   }
-  if (g.bf16) self = make_float4(round_act(1, self.x), round_act(1, self.y), round_act(1, self.z), round_act(1, self.w));
-  arg = a0 | (a1 << 8) | (a2 << 16) | (a3 << 24);
+  self = round4(g.bf16, self);
+  arg = arg_pack(a);
   return true;
 }
 
 // ------------------------------------------------------------------------------------------------ conv forward
 // out[rows of degree d] = relu(S . W_rel[d] + X . W_self[d] + b_rel[d] + b_self[d]),  S = sum of neighbour rows
 // (degree 0: X . W_self[0] + b_self[0]); optional column sums of out and out^2 into acc (fp64 atomics).
-// W_list order: rel_1, self_1, ..., rel_10, self_10, self_0 (layers.py:6189-6224).
 // POOL_IN: the layer input X is the GraphPool of the previous layer's output, computed HERE from gc_prev with
 // its folded BatchNorm -- own rows (written to pool_out / arg_out when given: the backward of "full" mode reads
 // them) and, recomputed, the rows of the neighbours -- so the pooled matrix needs no launch of its own.
@@ -348,6 +375,45 @@ __device__ __forceinline__ bool pool_two_hop(const SmallGraph& g, int row, int d
 // the whole K for the default widths -- and the bias with them: they are in flight while the operand tile is
 // gathered, so the product starts without a memory round trip of its own.
 constexpr int kBChunk = 8;
+
+// What both forward products do with their accumulators: out[tile rows][64 NT] = relu(c + bias), stored in the
+// activation format, and (acc given) the column sums of out and out^2 into acc = [sum(W) | sum of squares(W)] with
+// fp64 atomics, one per column and tile.  The sums are taken of the ROUNDED values: the BatchNorm statistics
+// describe what is stored, which is what the consumer normalises.
+// Accumulator layout of mfma16: lane (lr, kq) holds rows 4 kq .. 4 kq + 3 of column lr of the wave's 16 columns.
+template <int NT>
+__device__ __forceinline__ void epilogue(const f4v (&c)[NT], const float (&bias)[NT], const Tile& tl,
+                                         float* __restrict__ out, double* __restrict__ acc, int bf) {
+  constexpr int W = 64 * NT;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int lr = lane & 15, kq = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < NT; ++i) {
+    const int col = 16 * (wave + 4 * i) + lr;
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = 4 * kq + j;
+      if (r < tl.nrows) {
+        const float v = round_act(bf, fmaxf(c[i][j] + bias[i], 0.f));
+        stA1(bf, out, (int64_t)(tl.row0 + r) * W + col, v);
+        s1 += v;
+        s2 += v * v;
+      }
+    }
+    if (acc) {
+      s1 += __shfl_xor(s1, 16);
+      s2 += __shfl_xor(s2, 16);
+      s1 += __shfl_xor(s1, 32);
+      s2 += __shfl_xor(s2, 32);
+      if (kq == 0) {
+        atomicAdd(acc + col, (double)s1);
+        atomicAdd(acc + W + col, (double)s2);
+      }
+    }
+  }
+}
+
 template <int NT>
 struct ConvChunk {
   static constexpr int value = NT == 1 ? 20 : (NT == 2 ? 10 : 5);
@@ -358,12 +424,10 @@ __global__ void __launch_bounds__(kSBlock)
 small_conv_fwd_kernel(SmallGraph g, const float* __restrict__ x, int ldx, int K, const float* __restrict__ Wl,
                       const float* __restrict__ bl, float* __restrict__ out, double* __restrict__ acc, BnArgs bn_in,
                       float* __restrict__ pool_out, uint8_t* __restrict__ arg_out) {
-  if (g.diag & 1024) return;
   extern __shared__ float smem[];
   const int t = blockIdx.x;
   if (t >= g.n_tiles) return;
-  Tile tl = tile_of(g, t);
-  if (g.diag & 16) tl.d = 0;
+  const Tile tl = tile_of(g, t);
   const int W = 64 * NT;
   const int K4 = (K + 3) & ~3;
   const int KP = pitch_a(K4);
@@ -373,8 +437,9 @@ small_conv_fwd_kernel(SmallGraph g, const float* __restrict__ x, int ldx, int K,
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lr = lane & 15, kq = lane >> 4;
   const int64_t blk = (int64_t)K * W;
-  const float* Wself = Wl + (tl.d == 0 ? (int64_t)(2 * g.max_deg) * blk : (int64_t)(2 * (tl.d - 1) + 1) * blk);
-  const float* Wrel = tl.d == 0 ? nullptr : Wl + (int64_t)(2 * (tl.d - 1)) * blk;
+  const DegBlocks db = deg_blocks(tl.d, g.deg.max_deg);
+  const float* Wself = Wl + (int64_t)db.self * blk;
+  const float* Wrel = db.rel < 0 ? nullptr : Wl + (int64_t)db.rel * blk;
   constexpr int CH = ConvChunk<NT>::value;
   float bx[CH][NT], bs[CH][NT], bias[NT];
   auto load_b = [&](int ks0) {
@@ -394,8 +459,7 @@ small_conv_fwd_kernel(SmallGraph g, const float* __restrict__ x, int ldx, int K,
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
     const int col = 16 * (wave + 4 * i) + lr;
-    bias[i] = tl.d == 0 ? bl[(int64_t)(2 * g.max_deg) * W + col]
-                        : bl[(int64_t)(2 * (tl.d - 1)) * W + col] + bl[(int64_t)(2 * (tl.d - 1) + 1) * W + col];
+    bias[i] = db.rel < 0 ? bl[(int64_t)db.self * W + col] : bl[(int64_t)db.rel * W + col] + bl[(int64_t)db.self * W + col];
   }
   for (int idx = threadIdx.x; idx < kTileRows * q4; idx += kSBlock) {
     const int r = idx / q4, q = idx - r * q4;
@@ -409,23 +473,19 @@ small_conv_fwd_kernel(SmallGraph g, const float* __restrict__ x, int ldx, int K,
         const int e = tl.e0 + r * tl.d;
         if (!(tl.d <= 4 && pool_two_hop(g, row, tl.d, e, x, K, q, bq.scale, bq.shift, self, a, s))) {
           pool_chunk(g, row, tl.d, e, x, K, q, bq.scale, bq.shift, self, a);
-          if (g.bf16) self = make_float4(round_act(1, self.x), round_act(1, self.y), round_act(1, self.z), round_act(1, self.w));
+          self = round4(g.bf16, self);
           s = make_float4(0.f, 0.f, 0.f, 0.f);
           for (int j = 0; j < tl.d; ++j) {
             const int nr = nb[j];
             const int dn = degree_of(g, nr);
             float4 v;
             uint32_t an;
-            pool_chunk(g, nr, dn, g.edge_start[dn] + (nr - g.deg_start[dn]) * dn, x, K, q, bq.scale, bq.shift, v, an);
-            if (g.bf16) v = make_float4(round_act(1, v.x), round_act(1, v.y), round_act(1, v.z), round_act(1, v.w));
-            s.x += v.x;
-            s.y += v.y;
-            s.z += v.z;
-            s.w += v.w;
+            pool_chunk(g, nr, dn, g.deg.edge_start[dn] + (nr - g.deg.deg_start[dn]) * dn, x, K, q, bq.scale, bq.shift, v, an);
+            add4(s, round4(g.bf16, v));
           }
         }
         if (pool_out) stA(g.bf16, pool_out, row, K, q, self);
-        if (arg_out) *reinterpret_cast<uint32_t*>(arg_out + (int64_t)row * K + 4 * q) = a;
+        if (arg_out) arg_word(arg_out, row, K, q) = a;
       } else {
         self = ld4(x + (int64_t)row * ldx + 4 * q);  // the atom features arrive as fp32 rows (one-hot: exact anyway)
         s = gather_sum_quad(0, x, ldx, nb, tl.d, row, q);
@@ -444,7 +504,7 @@ small_conv_fwd_kernel(SmallGraph g, const float* __restrict__ x, int ldx, int K,
   f4v c[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i) c[i] = (f4v){0.f, 0.f, 0.f, 0.f};
-  for (int ks0 = 0; ks0 < q4 && !(g.diag & 8); ks0 += CH) {
+  for (int ks0 = 0; ks0 < q4; ks0 += CH) {
     float cx[CH][NT], cs[CH][NT];
 #pragma unroll
     for (int u = 0; u < CH; ++u)
@@ -468,31 +528,7 @@ small_conv_fwd_kernel(SmallGraph g, const float* __restrict__ x, int ldx, int K,
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < NT; ++i) {
-    const int col = 16 * (wave + 4 * i) + lr;
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = 4 * kq + j;
-      if (r < tl.nrows) {
-        const float v = round_act(g.bf16, fmaxf(c[i][j] + bias[i], 0.f));  // statistics describe what is stored
-        stA1(g.bf16, out, (int64_t)(tl.row0 + r) * W + col, v);
-        s1 += v;
-        s2 += v * v;
-      }
-    }
-    if (acc && !(g.diag & 1)) {
-      s1 += __shfl_xor(s1, 16);
-      s2 += __shfl_xor(s2, 16);
-      s1 += __shfl_xor(s1, 32);
-      s2 += __shfl_xor(s2, 32);
-      if (kq == 0) {
-        atomicAdd(acc + col, (double)s1);
-        atomicAdd(acc + W + col, (double)s2);
-      }
-    }
-  }
+  epilogue<NT>(c, bias, tl, out, acc, g.bf16);
 }
 
 // ------------------------------------------------------------------------------------------------ pool + dense forward
@@ -504,13 +540,10 @@ __global__ void __launch_bounds__(kSBlock)
 small_pool_dense_fwd_kernel(SmallGraph g, const float* __restrict__ gc, int K, BnArgs bn, float* __restrict__ pool,
                             uint8_t* __restrict__ arg, const float* __restrict__ Wd, const float* __restrict__ bd,
                             float* __restrict__ dense, double* __restrict__ acc) {
-  if (g.diag & 1024) return;
   extern __shared__ float smem[];
   const int t = blockIdx.x;
   if (t >= g.n_tiles) return;
-  Tile tl = tile_of(g, t);
-  if (g.diag & 16) tl.d = 0;
-  const int D = 64 * NT;
+  const Tile tl = tile_of(g, t);
   const int KP = pitch_a(K);
   float* sP = smem;  // [16][KP]
   const int q4 = K / 4;
@@ -543,7 +576,7 @@ small_pool_dense_fwd_kernel(SmallGraph g, const float* __restrict__ gc, int K, B
       pool_chunk(g, tl.row0 + r, tl.d, tl.e0 + r * tl.d, gc, K, q, bq.scale, bq.shift, best, a);
       stA(g.bf16, pool, tl.row0 + r, K, q, best);
       if (g.bf16) best = ldA(1, pool, tl.row0 + r, K, q);  // the product sees the stored (rounded) rows, like the backward will
-      if (arg) *reinterpret_cast<uint32_t*>(arg + (int64_t)(tl.row0 + r) * K + 4 * q) = a;
+      if (arg) arg_word(arg, tl.row0 + r, K, q) = a;
     }
     st4(sP + r * KP + 4 * q, best);
   }
@@ -551,7 +584,7 @@ small_pool_dense_fwd_kernel(SmallGraph g, const float* __restrict__ gc, int K, B
   f4v c[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i) c[i] = (f4v){0.f, 0.f, 0.f, 0.f};
-  for (int s0 = 0; s0 < n_s && !(g.diag & 8); s0 += SG) {
+  for (int s0 = 0; s0 < n_s; s0 += SG) {
     float4 cw[SG][NT];
 #pragma unroll
     for (int u = 0; u < SG; ++u)
@@ -572,32 +605,7 @@ small_pool_dense_fwd_kernel(SmallGraph g, const float* __restrict__ gc, int K, B
       }
     }
   }
-#pragma unroll
-  for (int i = 0; i < NT; ++i) {
-    const int col = 16 * (wave + 4 * i) + lr;
-    const float bias = biasd[i];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = 4 * kq + j;
-      if (r < tl.nrows) {
-        const float v = round_act(g.bf16, fmaxf(c[i][j] + bias, 0.f));
-        stA1(g.bf16, dense, (int64_t)(tl.row0 + r) * D + col, v);
-        s1 += v;
-        s2 += v * v;
-      }
-    }
-    if (acc && !(g.diag & 1)) {
-      s1 += __shfl_xor(s1, 16);
-      s2 += __shfl_xor(s2, 16);
-      s1 += __shfl_xor(s1, 32);
-      s2 += __shfl_xor(s2, 32);
-      if (kq == 0) {
-        atomicAdd(acc + col, (double)s1);
-        atomicAdd(acc + D + col, (double)s2);
-      }
-    }
-  }
+  epilogue<NT>(c, biasd, tl, dense, acc, g.bf16);
 }
 
 // ------------------------------------------------------------------------------------------------ readout + head + loss
@@ -626,7 +634,6 @@ struct ReadoutArgs {
   double* loss_acc;     // 1
   double* bsum;         // [sum dy (F) | sum dy*xhat (F)]
   int F, T, C, mode;    // mode 0 classification, 1 regression
-  int wh_in_lds;        // the head matrix fits into LDS beside the per-wave scratch: staged once per workgroup
 };
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -644,7 +651,6 @@ __device__ __forceinline__ float wave_sum(float v) {
 template <int LPR>  // F = 4 * LPR in {64, 128, 256}
 __global__ void __launch_bounds__(kSBlock)
 small_readout_kernel(SmallGraph g, ReadoutArgs a) {
-  if (g.diag & 1024) return;
   extern __shared__ float smem[];
   constexpr int F = 4 * LPR, RPW = 64 / LPR, F2 = 2 * F;
   constexpr int NH4 = F2 / 32;       // float4 pieces of a head row per thread (8 column segments)
@@ -694,19 +700,19 @@ small_readout_kernel(SmallGraph g, ReadoutArgs a) {
   for (int e = 0; e < 4; ++e) bn[e] = bn_col(a.bn, F, 4 * fq + e);
   BnCol bnf = bn[0];
   if (tid < F) bnf = bn_col(a.bn, F, tid);
-  const int n_b = 2 * (g.max_deg + 1);
+  const int n_b = 2 * (g.deg.max_deg + 1);
   const int rb = lane < n_b ? g.mol_runs[(int64_t)m * n_b + lane] : 0;
   int n_m = 0;
-  for (int dd = 0; dd <= g.max_deg; ++dd) n_m += __shfl(rb, 2 * dd + 1) - __shfl(rb, 2 * dd);
+  for (int dd = 0; dd <= g.deg.max_deg; ++dd) n_m += __shfl(rb, 2 * dd + 1) - __shfl(rb, 2 * dd);
   // ---- rows: wave w takes list positions [w Q, (w + 1) Q)
   float s[4] = {0.f, 0.f, 0.f, 0.f}, raw[4] = {0.f, 0.f, 0.f, 0.f}, rawarg[4] = {0.f, 0.f, 0.f, 0.f};
   float mx[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
   int arow[4] = {-1, -1, -1, -1};
   const int Q = (n_m + 3) / 4;
   const int p_lo = wave * Q, p_hi = min(n_m, p_lo + Q);
-  for (int base = p_lo; base < p_hi && !(g.diag & 32); base += 64) {
+  for (int base = p_lo; base < p_hi; base += 64) {
     int myrow = -1, pos = 0;
-    for (int dd = 0; dd <= g.max_deg; ++dd) {
+    for (int dd = 0; dd <= g.deg.max_deg; ++dd) {
       const int b0 = __shfl(rb, 2 * dd), len = __shfl(rb, 2 * dd + 1) - b0;
       const int j = base + lane - pos;
       if (j >= 0 && j < len) myrow = b0 + j;
@@ -794,7 +800,6 @@ small_readout_kernel(SmallGraph g, ReadoutArgs a) {
     if (train) a.argrow[(int64_t)m * F + tid] = frow;
   }
   __syncthreads();
-  if (g.diag & 64) return;
   // ---- task head: thread = (output tc mod 32, one of 8 column segments)
   for (int tc0 = 0; tc0 < TC; tc0 += 32) {
     const int tc = tc0 + tcl;
@@ -855,7 +860,7 @@ small_readout_kernel(SmallGraph g, ReadoutArgs a) {
   }
   if (!train) return;
   lsum = wave_sum(lsum);
-  if (lane == 0 && lsum != 0.f && !(g.diag & 2)) atomicAdd(a.loss_acc, (double)lsum);
+  if (lane == 0 && lsum != 0.f) atomicAdd(a.loss_acc, (double)lsum);
   __syncthreads();
   for (int tc = tid; tc < TC; tc += kSBlock) a.dlogits[(int64_t)m * TC + tc] = sdl[tc];
   // ---- d fingerprint = dlogits . Wh: thread = (4 consecutive inputs, a quarter of the outputs)
@@ -891,7 +896,7 @@ small_readout_kernel(SmallGraph g, ReadoutArgs a) {
     sgr[f] = gsum;
   }
   __syncthreads();
-  if (tid < F && a.bsum && n_m > 0 && !(g.diag & 2)) {
+  if (tid < F && a.bsum && n_m > 0) {
     const float gs = sgr[tid], gm = sgr[F + tid];
     const float sum_xhat = bnf.invstd * (f_raw - (float)n_m * bnf.mean);
     const float xhat_arg = (f_rawarg - bnf.mean) * bnf.invstd;
@@ -960,6 +965,14 @@ __device__ __forceinline__ BwdQuad bn_bwd_quad(const BnArgs& bn, const T* s1, co
   return o;
 }
 
+// dx = A dy + B x + C, masked by the ReLU in front of the BatchNorm (x: the ReLU's output)
+__device__ __forceinline__ float4 relu_bn_bwd4(const BwdQuad& c, const float4& dy, const float4& x) {
+  return make_float4(x.x > 0.f ? fmaf(c.A.x, dy.x, fmaf(c.B.x, x.x, c.C.x)) : 0.f,
+                     x.y > 0.f ? fmaf(c.A.y, dy.y, fmaf(c.B.y, x.y, c.C.y)) : 0.f,
+                     x.z > 0.f ? fmaf(c.A.z, dy.z, fmaf(c.B.z, x.z, c.C.z)) : 0.f,
+                     x.w > 0.f ? fmaf(c.A.w, dy.w, fmaf(c.B.w, x.w, c.C.w)) : 0.f);
+}
+
 // dx of `rows` consecutive rows starting at row0 into LDS tile sDx[rows][pitch].  F / 4 divides the block size, so
 // a thread keeps ONE column quad over all its rows: coefficients once, then its rows four at a time -- the four
 // membership loads together, then the sixteen loads that depend on them together.
@@ -968,7 +981,6 @@ __device__ __forceinline__ void dense_dx_to_lds(const SmallGraph& g, const Dense
   const int F = a.F, q4 = F / 4;
   const int q = threadIdx.x % q4, r_first = threadIdx.x / q4, r_step = kSBlock / q4;
   const BwdQuad cq = bn_bwd_quad(a.bn, a.bsum, a.bsum + F, F, q);
-  const float4 cA = cq.A, cB = cq.B, cC = cq.C;
   for (int r0 = r_first; r0 < tile_rows; r0 += 4 * r_step) {
     int m[4];
     float4 x[4], gs[4], gm[4];
@@ -994,13 +1006,9 @@ __device__ __forceinline__ void dense_dx_to_lds(const SmallGraph& g, const Dense
       float4 dx = make_float4(0.f, 0.f, 0.f, 0.f);
       if (r < nrows) {
         const int row = row0 + r;
-        const float dy0 = gs[t].x + (ar[t].x == row ? gm[t].x : 0.f), dy1 = gs[t].y + (ar[t].y == row ? gm[t].y : 0.f),
-                    dy2 = gs[t].z + (ar[t].z == row ? gm[t].z : 0.f), dy3 = gs[t].w + (ar[t].w == row ? gm[t].w : 0.f);
-        // dx = A dy + B x + C  (BatchNorm backward folded per column), masked by the ReLU in front
-        dx.x = x[t].x > 0.f ? fmaf(cA.x, dy0, fmaf(cB.x, x[t].x, cC.x)) : 0.f;
-        dx.y = x[t].y > 0.f ? fmaf(cA.y, dy1, fmaf(cB.y, x[t].y, cC.y)) : 0.f;
-        dx.z = x[t].z > 0.f ? fmaf(cA.z, dy2, fmaf(cB.z, x[t].z, cC.z)) : 0.f;
-        dx.w = x[t].w > 0.f ? fmaf(cA.w, dy3, fmaf(cB.w, x[t].w, cC.w)) : 0.f;
+        const float4 dy = make_float4(gs[t].x + (ar[t].x == row ? gm[t].x : 0.f), gs[t].y + (ar[t].y == row ? gm[t].y : 0.f),
+                                      gs[t].z + (ar[t].z == row ? gm[t].z : 0.f), gs[t].w + (ar[t].w == row ? gm[t].w : 0.f));
+        dx = relu_bn_bwd4(cq, dy, x[t]);
       }
       st4(sDx + r * pitch + 4 * q, dx);
     }
@@ -1010,14 +1018,12 @@ __device__ __forceinline__ void dense_dx_to_lds(const SmallGraph& g, const Dense
 template <int NKT>  // K = 64 * NKT columns of dP per row
 __global__ void __launch_bounds__(kSBlock)
 small_dense_bwd_kernel(SmallGraph g, DenseBwdArgs a) {
-  if (g.diag & 1024) return;
   extern __shared__ float smem[];
   const int F = a.F, K = a.K;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int lr = lane & 15, kq = lane >> 4;
   int b = blockIdx.x;
   if (b < g.n_tiles) {
-    if (g.diag & 512) return;
     const Tile tl = tile_of(g, b);
     const int FP = pitch_a(F);
     float* sDx = smem;  // [16][FP]
@@ -1034,7 +1040,7 @@ small_dense_bwd_kernel(SmallGraph g, DenseBwdArgs a) {
     f4v c[NKT];
 #pragma unroll
     for (int i = 0; i < NKT; ++i) c[i] = (f4v){0.f, 0.f, 0.f, 0.f};
-    for (int ks0 = 0; ks0 < F / 4 && !(g.diag & 8); ks0 += kBChunk) {
+    for (int ks0 = 0; ks0 < F / 4; ks0 += kBChunk) {
       float cw[kBChunk][NKT];
 #pragma unroll
       for (int u = 0; u < kBChunk; ++u)
@@ -1061,7 +1067,6 @@ small_dense_bwd_kernel(SmallGraph g, DenseBwdArgs a) {
   }
   b -= g.n_tiles;
   if (b < a.n_slabs) {
-    if (g.diag & 128) return;
     // dWd[o][k] += sum_r dx[r][o] P[r][k] over the slab's rows
     const int row0 = b * kSlabRows;
     const int nrows = min(kSlabRows, g.n_atoms - row0);
@@ -1081,7 +1086,7 @@ small_dense_bwd_kernel(SmallGraph g, DenseBwdArgs a) {
     }
     __syncthreads();
     const int n_ot = F / 16, n_kt = K / 16;
-    for (int ot = wave; ot < n_ot && !(g.diag & 8); ot += 4) {
+    for (int ot = wave; ot < n_ot; ot += 4) {
       for (int kt0 = 0; kt0 < n_kt; kt0 += 4) {
         f4v c[4];
 #pragma unroll
@@ -1099,7 +1104,7 @@ small_dense_bwd_kernel(SmallGraph g, DenseBwdArgs a) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const int o = 16 * ot + 4 * kq + j, k = 16 * (kt0 + i) + lr;
-            if (!(g.diag & 4)) atomicAdd(a.dWd + (int64_t)o * K + k, c[i][j]);
+            atomicAdd(a.dWd + (int64_t)o * K + k, c[i][j]);
           }
         }
       }
@@ -1114,7 +1119,6 @@ small_dense_bwd_kernel(SmallGraph g, DenseBwdArgs a) {
   b -= a.n_slabs;
   // head weight gradient: one workgroup per output row tc; the molecules are split over the four waves, a lane
   // owns 4 consecutive input columns (coalesced float4 rows of fp), partial sums meet in LDS
-  if (g.diag & 256) return;
   const int tc = b;
   const int F2 = 2 * F;
   float* red = smem;  // [4][F2]
@@ -1152,7 +1156,6 @@ __global__ void __launch_bounds__(kSBlock)
 small_pool_bwd_kernel(SmallGraph g, const float* __restrict__ dpool, const uint8_t* __restrict__ arg,
                       const float* __restrict__ gc, int W, BnArgs bn, float* __restrict__ dA,
                       float* __restrict__ dgamma, float* __restrict__ dbeta) {
-  if (g.diag & 1024) return;
   extern __shared__ float smem[];
   const int t = blockIdx.x;
   if (t >= g.n_tiles) return;
@@ -1164,12 +1167,7 @@ small_pool_bwd_kernel(SmallGraph g, const float* __restrict__ dpool, const uint8
     float4 d = make_float4(0.f, 0.f, 0.f, 0.f), dx = d;
     if (r < tl.nrows) {
       const int row = tl.row0 + r;
-      const uint32_t a = *reinterpret_cast<const uint32_t*>(arg + (int64_t)row * W + 4 * q);
-      const float4 v = ld4(dpool + (int64_t)row * W + 4 * q);
-      d.x = (a & 0xff) == 0 ? v.x : 0.f;
-      d.y = ((a >> 8) & 0xff) == 0 ? v.y : 0.f;
-      d.z = ((a >> 16) & 0xff) == 0 ? v.z : 0.f;
-      d.w = (a >> 24) == 0 ? v.w : 0.f;
+      d = arg_pick(arg_word(arg, row, W, q), 0, ld4(dpool + (int64_t)row * W + 4 * q));
       const int e = tl.e0 + r * tl.d;
       for (int j0 = 0; j0 < tl.d; j0 += 4) {  // four neighbours per round: ids together, then their rows together
         int nb[4];
@@ -1183,16 +1181,11 @@ small_pool_bwd_kernel(SmallGraph g, const float* __restrict__ dpool, const uint8
         }
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          an[t] = *reinterpret_cast<const uint32_t*>(arg + (int64_t)nb[t] * W + 4 * q);
+          an[t] = arg_word(arg, nb[t], W, q);
           vn[t] = ld4(dpool + (int64_t)nb[t] * W + 4 * q);
         }
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          d.x += (an[t] & 0xff) == want[t] ? vn[t].x : 0.f;
-          d.y += ((an[t] >> 8) & 0xff) == want[t] ? vn[t].y : 0.f;
-          d.z += ((an[t] >> 16) & 0xff) == want[t] ? vn[t].z : 0.f;
-          d.w += (an[t] >> 24) == want[t] ? vn[t].w : 0.f;
-        }
+        for (int t = 0; t < 4; ++t) add4(d, arg_pick(an[t], want[t], vn[t]));
       }
       if (dA) st4(dA + (int64_t)row * W + 4 * q, d);
       const float4 x = ldA(g.bf16, gc, row, W, q);
@@ -1250,13 +1243,7 @@ __device__ __forceinline__ void conv_dg_to_lds(int bf, const ConvBwdArgs& a, int
     float4 dg = make_float4(0.f, 0.f, 0.f, 0.f);
     if (r < nrows) {
       const BwdQuad cq = bn_bwd_quad(a.bn, a.dbeta, a.dgamma, W, q);
-      const float4 cA = cq.A, cB = cq.B, cC = cq.C;
-      const float4 dy = ld4(a.dA + (int64_t)(row0 + r) * W + 4 * q);
-      const float4 x = ldA(bf, a.gc, row0 + r, W, q);
-      dg.x = x.x > 0.f ? fmaf(cA.x, dy.x, fmaf(cB.x, x.x, cC.x)) : 0.f;
-      dg.y = x.y > 0.f ? fmaf(cA.y, dy.y, fmaf(cB.y, x.y, cC.y)) : 0.f;
-      dg.z = x.z > 0.f ? fmaf(cA.z, dy.z, fmaf(cB.z, x.z, cC.z)) : 0.f;
-      dg.w = x.w > 0.f ? fmaf(cA.w, dy.w, fmaf(cB.w, x.w, cC.w)) : 0.f;
+      dg = relu_bn_bwd4(cq, ld4(a.dA + (int64_t)(row0 + r) * W + 4 * q), ldA(bf, a.gc, row0 + r, W, q));
     }
     st4(sG + r * pitch + 4 * q, dg);
   }
@@ -1277,8 +1264,9 @@ small_conv_bwd_kernel(SmallGraph g, ConvBwdArgs a) {
     float* sG = smem;  // [16][WP]
     conv_dg_to_lds(g.bf16, a, tl.row0, tl.nrows, kTileRows, sG, WP);
     __syncthreads();
-    const float* Wself = a.Wl + (tl.d == 0 ? (int64_t)(2 * g.max_deg) * blk : (int64_t)(2 * (tl.d - 1) + 1) * blk);
-    const float* Wrel = tl.d == 0 ? nullptr : a.Wl + (int64_t)(2 * (tl.d - 1)) * blk;
+    const DegBlocks db = deg_blocks(tl.d, g.deg.max_deg);
+    const float* Wself = a.Wl + (int64_t)db.self * blk;
+    const float* Wrel = db.rel < 0 ? nullptr : a.Wl + (int64_t)db.rel * blk;
     // out[r][k] = sum_c dg[r][c] W[k][c]: B fragment = W[k = col][c = 4 ks + kq]
     for (int kt = wave; kt < K4 / 16 + ((K4 % 16) ? 1 : 0); kt += 4) {
       const int k = 16 * kt + lr;
@@ -1303,13 +1291,9 @@ small_conv_bwd_kernel(SmallGraph g, ConvBwdArgs a) {
   }
   b -= n_dgrad;
   if (b >= a.n_slabs) return;
-  // weight-gradient slab: 64 rows of one degree
-  int d = 0;
-#pragma unroll
-  for (int k = 1; k <= GCMI_MAX_DEG; ++k) d += (k <= g.max_deg && b >= a.slab_start[k]) ? 1 : 0;
-  const int row0 = g.deg_start[d] + (b - a.slab_start[d]) * kSlabRows;
-  const int nrows = min(kSlabRows, g.deg_start[d + 1] - row0);
-  const int e0 = g.edge_start[d] + (row0 - g.deg_start[d]) * d;
+  // weight-gradient slab: up to 32 rows of one degree
+  const Tile sl = rows_of<kSlabRows>(g, a.slab_start, b);
+  const int d = sl.d, row0 = sl.row0, nrows = sl.nrows, e0 = sl.e0;
   const int WT = pitch_t(W), KT = pitch_t(K4);
   float* sG = smem;                     // [slab][WT]
   float* sX = sG + kSlabRows * WT;      // [slab][KT] own rows
@@ -1327,8 +1311,9 @@ small_conv_bwd_kernel(SmallGraph g, ConvBwdArgs a) {
     st4(sS + r * KT + 4 * q, s);
   }
   __syncthreads();
-  float* dWself = a.dWl + (d == 0 ? (int64_t)(2 * g.max_deg) * blk : (int64_t)(2 * (d - 1) + 1) * blk);
-  float* dWrel = d == 0 ? nullptr : a.dWl + (int64_t)(2 * (d - 1)) * blk;
+  const DegBlocks db = deg_blocks(d, g.deg.max_deg);
+  float* dWself = a.dWl + (int64_t)db.self * blk;
+  float* dWrel = db.rel < 0 ? nullptr : a.dWl + (int64_t)db.rel * blk;
   // dW[k][c] = sum_r X[r][k] dg[r][c]: A fragment = X^T (m = k), B fragment = dg (n = c)
   const int n_kt = (K4 + 15) / 16, n_ct = W / 16;
   for (int kt = wave; kt < n_kt; kt += 4) {
@@ -1366,12 +1351,8 @@ small_conv_bwd_kernel(SmallGraph g, ConvBwdArgs a) {
   for (int c = threadIdx.x; c < W; c += kSBlock) {
     float s = 0.f;
     for (int r = 0; r < nrows; ++r) s += sG[r * WT + c];
-    if (d == 0) {
-      atomicAdd(a.dbl + (int64_t)(2 * g.max_deg) * W + c, s);
-    } else {
-      atomicAdd(a.dbl + (int64_t)(2 * (d - 1)) * W + c, s);
-      atomicAdd(a.dbl + (int64_t)(2 * (d - 1) + 1) * W + c, s);
-    }
+    if (db.rel >= 0) atomicAdd(a.dbl + (int64_t)db.rel * W + c, s);
+    atomicAdd(a.dbl + (int64_t)db.self * W + c, s);
   }
 }
 
@@ -1388,10 +1369,7 @@ small_gather_add_kernel(SmallGraph g, const float* __restrict__ dXs, const float
     const int row = tl.row0 + r;
     float4 s = ld4(dXs + (int64_t)row * W + 4 * q);
     const float4 n = gather_sum_quad(0, dS, W, g.col_idx + tl.e0 + r * tl.d, tl.d, row, q);
-    s.x += n.x;
-    s.y += n.y;
-    s.z += n.z;
-    s.w += n.w;
+    add4(s, n);
     st4(dP + (int64_t)row * W + 4 * q, s);
   }
 }
@@ -1558,7 +1536,17 @@ static int small_check(const gcmi_model_desc* m) {
   return GCMI_OK;
 }
 
-static int make_small_graph(const gcmi_graph* g, bool need_rev, SmallGraph* out) {
+// prefix over the degree blocks of how many `rows`-row pieces each is cut into; returns their total
+static int block_prefix(const DegTable& t, int rows, int32_t* out) {
+  int n = 0;
+  for (int d = 0; d < GCMI_MAX_DEG + 2; ++d) {
+    out[d] = n;
+    if (d <= t.max_deg) n += (t.deg_start[d + 1] - t.deg_start[d] + rows - 1) / rows;
+  }
+  return n;
+}
+
+static int make_small_graph(const gcmi_graph* g, const gcmi_model_desc* m, bool need_rev, SmallGraph* out) {
   int rc = check_graph(g, true);
   if (rc) return rc;
   GCMI_CHECK_ARG(g->n_mols > 1, "graph_gather requires batches larger than 1");
@@ -1571,29 +1559,9 @@ static int make_small_graph(const gcmi_graph* g, bool need_rev, SmallGraph* out)
   memset(&s, 0, sizeof(s));
   s.n_atoms = g->n_atoms;
   s.n_mols = g->n_mols;
-  s.max_deg = g->max_deg;
-  int t = 0;
-  for (int d = 0; d < GCMI_MAX_DEG + 2; ++d) {
-    const int dd = d < g->max_deg + 1 ? d : g->max_deg + 1;
-    s.deg_start[d] = g->deg_start[dd];
-    s.edge_start[d] = g->edge_start[dd];
-    s.tile_start[d] = t;
-    if (d <= g->max_deg) t += (g->deg_start[d + 1] - g->deg_start[d] + kTileRows - 1) / kTileRows;
-  }
-  s.n_tiles = t;
-  // the diagnostic switches exist only in a build made for them (tools/small_diag.sh: -DGCMI_SMALL_DIAG_BUILD): in
-  // the shipped library a stray environment variable cannot switch parts of the training kernels off
-#ifdef GCMI_SMALL_DIAG_BUILD
-  static const int diag = getenv("GCMI_SMALL_DIAG") ? atoi(getenv("GCMI_SMALL_DIAG")) : 0;
-  if (diag) {
-    static bool warned = false;
-    if (!warned) fprintf(stderr, "libgcmi: GCMI_SMALL_DIAG=%d -- parts of the small-batch kernels are OFF, results are wrong\n", diag);
-    warned = true;
-  }
-  s.diag = diag;
-#else
-  s.diag = 0;
-#endif
+  s.bf16 = m->storage >= 1 ? 1 : 0;  // (2: gradient streams too -- no such streams here, the batch lives in L2)
+  s.deg = make_deg_table(g);
+  s.n_tiles = block_prefix(s.deg, kTileRows, s.tile_start);
   s.col_idx = g->d_col_idx;
   s.membership = g->d_membership;
   s.mol_runs = g->d_mol_runs;
@@ -1602,27 +1570,41 @@ static int make_small_graph(const gcmi_graph* g, bool need_rev, SmallGraph* out)
   return GCMI_OK;
 }
 
-template <typename Kern>
-static int ensure_lds(Kern kern, size_t bytes) {
-  if (bytes > 64 * 1024) {
-    if (bytes > 160 * 1024) {
-      set_error("small: a tile needs %zu bytes of LDS (> 160 KB)", bytes);
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)bytes) != hipSuccess) {
-      set_error("small: hipFuncSetAttribute(max dynamic LDS = %zu) failed", bytes);
-      return GCMI_ERR_LAUNCH;
-    }
-  }
-  return GCMI_OK;
-}
-
 #define SRUN(call)          \
   do {                      \
     int rc__ = (call);      \
     if (rc__) return rc__;  \
   } while (0)
+
+// One launch of a kernel of this file: kSBlock threads, `lds` bytes of dynamic LDS.  Above 64 KB the kernel's limit
+// has to be raised first: once per kernel instantiation and device (LdsLimit), to the most a workgroup can have.
+constexpr size_t kLdsMax = 160 * 1024;
+template <auto Kern, typename... Args>
+static int small_launch(const char* name, int grid, size_t lds, hipStream_t st, const Args&... args) {
+  if (lds > kLdsMax) {
+    set_error("small: a tile needs %zu bytes of LDS (> 160 KB)", lds);
+    return GCMI_ERR_UNSUPPORTED;
+  }
+  static LdsLimit lim;
+  if (lds > 64 * 1024 && !raise_lds_limit(lim, reinterpret_cast<const void*>(Kern), kLdsMax)) {
+    set_error("small: %s: hipFuncSetAttribute(max dynamic LDS = %zu) failed", name, lds);
+    return GCMI_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(Kern, dim3(grid), dim3(kSBlock), lds, st, args...);
+  GCMI_CHECK_LAUNCH(name);
+  return GCMI_OK;
+}
+
+// f(std::integral_constant<int, n>) for the n = width / 64 in 1..4 that small_check admits
+template <typename F>
+static int with_nt(int n, F&& f) {
+  switch (n) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 3: return f(std::integral_constant<int, 3>());
+    default: return f(std::integral_constant<int, 4>());
+  }
+}
 
 struct SmallCtx {
   const gcmi_model_desc* m;
@@ -1639,6 +1621,36 @@ struct SmallCtx {
 static inline float* gc_of(const SmallCtx& c, int l) { return c.ws + c.w.gc[c.parity][l]; }
 static inline double* acc_of(const SmallCtx& c, int l) {
   return c.accs + (l < c.m->n_layers ? c.w.acc[c.parity][l] : c.w.acc_dense);
+}
+
+// the context of one C call (`what`: its name in error texts)
+static int small_ctx(const gcmi_model_desc* m, const float* params, const gcmi_model_io* io, int64_t ws_atoms,
+                     int64_t ws_mols, void* stream, bool training, const char* what, SmallCtx* c) {
+  c->m = m;
+  c->params = params;
+  c->io = io;
+  c->w = small_carve(m, ws_atoms, ws_mols);
+  c->ws = io->d_workspace;
+  c->accs = reinterpret_cast<double*>(c->ws + c->w.acc0);
+  c->st = (hipStream_t)stream;
+  c->training = training;
+  c->parity = 0;
+  if (m->batch_norm)
+    for (int l = 0; l <= m->n_layers; ++l)
+      GCMI_CHECK_ARG(io->d_bn_running_mean[l] && io->d_bn_running_var[l], "%s: NULL running statistics", what);
+  return GCMI_OK;
+}
+
+// what training and prediction both ask of batch i
+static int check_small_batch(const gcmi_small_batch* b, int64_t i, const gcmi_model_desc* m, int64_t ws_atoms,
+                             int64_t ws_mols, const char* what) {
+  GCMI_CHECK_ARG(b->graph.n_atoms <= ws_atoms && b->graph.n_mols <= ws_mols,
+                 "%s: batch %lld (%d atoms, %d molecules) exceeds the workspace (%lld, %lld)", what, (long long)i,
+                 b->graph.n_atoms, b->graph.n_mols, (long long)ws_atoms, (long long)ws_mols);
+  GCMI_CHECK_ARG(b->graph.n_atoms == 0 || b->d_atom_features, "%s: NULL atom features", what);
+  GCMI_CHECK_ARG(b->graph.max_deg == m->max_deg, "%s: graph max_deg %d != model max_deg %d", what, b->graph.max_deg,
+                 m->max_deg);
+  return GCMI_OK;
 }
 
 static BnArgs bn_args(const SmallCtx& c, int layer, int n_rows) {
@@ -1663,28 +1675,13 @@ static int launch_conv_fwd(const SmallGraph& g, const float* x, int ldx, int K, 
                            uint8_t* arg_out, hipStream_t st) {
   const int K4 = (K + 3) & ~3;
   const size_t lds = sizeof(float) * (2 * kTileRows * pitch_a(K4) + 2 * K4);
-  const dim3 grid(g.n_tiles), block(kSBlock);
-#define CF(NT, PI)                                                                                              \
-  hipLaunchKernelGGL((small_conv_fwd_kernel<NT, PI>), grid, block, lds, st, g, x, ldx, K, Wl, bl, out, acc, bn_in, \
-                     pool_out, arg_out)
-  if (pool_in) {
-    switch (W / 64) {
-      case 1: CF(1, true); break;
-      case 2: CF(2, true); break;
-      case 3: CF(3, true); break;
-      default: CF(4, true); break;
-    }
-  } else {
-    switch (W / 64) {
-      case 1: CF(1, false); break;
-      case 2: CF(2, false); break;
-      case 3: CF(3, false); break;
-      default: CF(4, false); break;
-    }
-  }
-#undef CF
-  GCMI_CHECK_LAUNCH("small_conv_fwd");
-  return GCMI_OK;
+  return with_nt(W / 64, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    return pool_in ? small_launch<small_conv_fwd_kernel<NT, true>>("small_conv_fwd", g.n_tiles, lds, st, g, x, ldx, K, Wl,
+                                                                   bl, out, acc, bn_in, pool_out, arg_out)
+                   : small_launch<small_conv_fwd_kernel<NT, false>>("small_conv_fwd", g.n_tiles, lds, st, g, x, ldx, K, Wl,
+                                                                    bl, out, acc, bn_in, pool_out, arg_out);
+  });
 }
 
 // the GraphConv stack (with the pools between the layers) on `st`
@@ -1729,19 +1726,11 @@ static int small_dense_stage(const SmallCtx& c, const SmallGraph& g) {
   uint8_t* arg = c.training ? reinterpret_cast<uint8_t*>(c.ws + c.w.arg[L - 1]) : nullptr;
   const float* Wd = c.params + m->off_dense_w;
   const float* bd = c.params + m->off_dense_b;
-  const dim3 grid(g.n_tiles), block(kSBlock);
-#define PD(NT)                                                                                                      \
-  hipLaunchKernelGGL(small_pool_dense_fwd_kernel<NT>, grid, block, lds, c.st, g, gc_of(c, L - 1), Wl,                \
-                     bn_args(c, L - 1, N), c.ws + c.w.pool[L - 1], arg, Wd, bd, c.ws + c.w.dense, accD)
-  switch (F / 64) {
-    case 1: PD(1); break;
-    case 2: PD(2); break;
-    case 3: PD(3); break;
-    default: PD(4); break;
-  }
-#undef PD
-  GCMI_CHECK_LAUNCH("small_pool_dense_fwd");
-  return GCMI_OK;
+  return with_nt(F / 64, [&](auto nt) {
+    return small_launch<small_pool_dense_fwd_kernel<decltype(nt)::value>>(
+        "small_pool_dense_fwd", g.n_tiles, lds, c.st, g, gc_of(c, L - 1), Wl, bn_args(c, L - 1, N), c.ws + c.w.pool[L - 1],
+        arg, Wd, bd, c.ws + c.w.dense, accD);
+  });
 }
 
 static int small_forward_body(const SmallCtx& c, const SmallGraph& g, const float* x, int64_t ldx) {
@@ -1765,24 +1754,11 @@ static int launch_readout(const SmallCtx& c, const SmallGraph& g, ReadoutArgs& a
   // fingerprint [2F], logits + dlogits [2 TCp], gradient [2F], wave quarters [20 F], head partials [8 TCp],
   // gradient partials [8 F]
   const size_t lds = sizeof(float) * (size_t)(4 * F + 2 * TCp + 20 * F + 8 * TCp + 8 * F);
-  a.wh_in_lds = 0;
-  const dim3 grid(g.n_mols), block(kSBlock);
   switch (F) {
-    case 64:
-      SRUN(ensure_lds(small_readout_kernel<16>, lds));
-      hipLaunchKernelGGL(small_readout_kernel<16>, grid, block, lds, c.st, g, a);
-      break;
-    case 128:
-      SRUN(ensure_lds(small_readout_kernel<32>, lds));
-      hipLaunchKernelGGL(small_readout_kernel<32>, grid, block, lds, c.st, g, a);
-      break;
-    default:
-      SRUN(ensure_lds(small_readout_kernel<64>, lds));
-      hipLaunchKernelGGL(small_readout_kernel<64>, grid, block, lds, c.st, g, a);
-      break;
+    case 64: return small_launch<small_readout_kernel<16>>("small_readout", g.n_mols, lds, c.st, g, a);
+    case 128: return small_launch<small_readout_kernel<32>>("small_readout", g.n_mols, lds, c.st, g, a);
+    default: return small_launch<small_readout_kernel<64>>("small_readout", g.n_mols, lds, c.st, g, a);
   }
-  GCMI_CHECK_LAUNCH("small_readout");
-  return GCMI_OK;
 }
 
 static int small_backward(const SmallCtx& c, const SmallGraph& g, const gcmi_small_batch* b, float* grads) {
@@ -1821,26 +1797,10 @@ static int small_backward(const SmallCtx& c, const SmallGraph& g, const gcmi_sma
     const size_t lds_slab = sizeof(float) * (3 * F + kSlabRows * (pitch_t(F) + pitch_t(Kd)));
     const size_t lds_head = sizeof(float) * (4 * 2 * F + 4);
     const size_t lds = std::max(lds_tile, std::max(lds_slab, lds_head));
-    const dim3 grid(gd.n_tiles + a.n_slabs + a.n_head_blocks), block(kSBlock);
-    switch (Kd / 64) {
-      case 1:
-        SRUN(ensure_lds(small_dense_bwd_kernel<1>, lds));
-        hipLaunchKernelGGL(small_dense_bwd_kernel<1>, grid, block, lds, c.st, gd, a);
-        break;
-      case 2:
-        SRUN(ensure_lds(small_dense_bwd_kernel<2>, lds));
-        hipLaunchKernelGGL(small_dense_bwd_kernel<2>, grid, block, lds, c.st, gd, a);
-        break;
-      case 3:
-        SRUN(ensure_lds(small_dense_bwd_kernel<3>, lds));
-        hipLaunchKernelGGL(small_dense_bwd_kernel<3>, grid, block, lds, c.st, gd, a);
-        break;
-      default:
-        SRUN(ensure_lds(small_dense_bwd_kernel<4>, lds));
-        hipLaunchKernelGGL(small_dense_bwd_kernel<4>, grid, block, lds, c.st, gd, a);
-        break;
-    }
-    GCMI_CHECK_LAUNCH("small_dense_bwd");
+    SRUN(with_nt(Kd / 64, [&](auto nkt) {
+      return small_launch<small_dense_bwd_kernel<decltype(nkt)::value>>(
+          "small_dense_bwd", gd.n_tiles + a.n_slabs + a.n_head_blocks, lds, c.st, gd, a);
+    }));
   }
   if (!need_dpool || g.n_tiles == 0) return GCMI_OK;
   const float* dpool = c.ws + c.w.dpool;
@@ -1848,19 +1808,19 @@ static int small_backward(const SmallCtx& c, const SmallGraph& g, const gcmi_sma
     const int W = m->conv_width[l];
     const int K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
     float* dA = full ? c.ws + c.w.dA[l] : nullptr;
-    hipLaunchKernelGGL(small_pool_bwd_kernel, dim3(g.n_tiles), dim3(kSBlock), sizeof(float) * (2 * W + kTileRows * 2 * W),
-                       c.st, g, dpool, reinterpret_cast<const uint8_t*>(c.ws + c.w.arg[l]), gc_of(c, l), W,
-                       bn_args(c, l, N), dA, m->batch_norm ? grads + m->off_bn_gamma[l] : nullptr,
-                       m->batch_norm ? grads + m->off_bn_beta[l] : nullptr);
-    GCMI_CHECK_LAUNCH("small_pool_bwd");
+    float* dgamma = m->batch_norm ? grads + m->off_bn_gamma[l] : nullptr;
+    float* dbeta = m->batch_norm ? grads + m->off_bn_beta[l] : nullptr;
+    SRUN(small_launch<small_pool_bwd_kernel>("small_pool_bwd", g.n_tiles, sizeof(float) * (2 * W + kTileRows * 2 * W), c.st,
+                                             g, dpool, reinterpret_cast<const uint8_t*>(c.ws + c.w.arg[l]), gc_of(c, l), W,
+                                             bn_args(c, l, N), dA, dgamma, dbeta));
     if (!full) break;  // reference semantics: nothing in front of a GraphConv output trains
     ConvBwdArgs cb;
     memset(&cb, 0, sizeof(cb));
     cb.dA = dA;
     cb.gc = gc_of(c, l);
     cb.bn = bn_args(c, l, N);
-    cb.dgamma = m->batch_norm ? grads + m->off_bn_gamma[l] : nullptr;
-    cb.dbeta = m->batch_norm ? grads + m->off_bn_beta[l] : nullptr;
+    cb.dgamma = dgamma;
+    cb.dbeta = dbeta;
     cb.x = l == 0 ? b->d_atom_features : c.ws + c.w.pool[l - 1];
     cb.ldx = l == 0 ? (int)b->ld_features : m->conv_width[l - 1];
     cb.x_bf = (l > 0 && g.bf16) ? 1 : 0;
@@ -1871,24 +1831,15 @@ static int small_backward(const SmallCtx& c, const SmallGraph& g, const gcmi_sma
     cb.dbl = grads + m->off_conv_b[l];
     cb.dS = l > 0 ? c.ws + c.w.dS : nullptr;
     cb.dXs = l > 0 ? c.ws + c.w.dXs : nullptr;
-    int s = 0;
-    for (int d = 0; d < GCMI_MAX_DEG + 2; ++d) {
-      cb.slab_start[d] = s;
-      if (d <= g.max_deg) s += (g.deg_start[d + 1] - g.deg_start[d] + kSlabRows - 1) / kSlabRows;
-    }
-    cb.n_slabs = s;
+    cb.n_slabs = block_prefix(g.deg, kSlabRows, cb.slab_start);
     const int K4 = (K + 3) & ~3;
     const size_t lds_tile = sizeof(float) * (3 * W + kTileRows * pitch_a(W));
     const size_t lds_slab = sizeof(float) * (3 * W + kSlabRows * (pitch_t(W) + 2 * pitch_t(K4)));
     const size_t lds = lds_tile > lds_slab ? lds_tile : lds_slab;
-    SRUN(ensure_lds(small_conv_bwd_kernel, lds));
-    hipLaunchKernelGGL(small_conv_bwd_kernel, dim3((l > 0 ? g.n_tiles : 0) + cb.n_slabs), dim3(kSBlock), lds, c.st, g,
-                       cb);
-    GCMI_CHECK_LAUNCH("small_conv_bwd");
+    SRUN(small_launch<small_conv_bwd_kernel>("small_conv_bwd", (l > 0 ? g.n_tiles : 0) + cb.n_slabs, lds, c.st, g, cb));
     if (l == 0) break;
-    hipLaunchKernelGGL(small_gather_add_kernel, dim3(g.n_tiles), dim3(kSBlock), 0, c.st, g, c.ws + c.w.dXs,
-                       c.ws + c.w.dS, K4, c.ws + c.w.dpool);
-    GCMI_CHECK_LAUNCH("small_gather_add");
+    SRUN(small_launch<small_gather_add_kernel>("small_gather_add", g.n_tiles, 0, c.st, g, c.ws + c.w.dXs, c.ws + c.w.dS,
+                                               K4, c.ws + c.w.dpool));
     dpool = c.ws + c.w.dpool;
   }
   return GCMI_OK;
@@ -1993,18 +1944,7 @@ int gcmi_small_fit_opt(const gcmi_model_desc* m, float* d_params, float* d_grads
   if (grad_hi) *grad_hi = hi;
   if (n_batches == 0) return GCMI_OK;
   SmallCtx c;
-  c.m = m;
-  c.params = d_params;
-  c.io = io;
-  c.w = small_carve(m, ws_atoms, ws_mols);
-  c.ws = io->d_workspace;
-  c.accs = reinterpret_cast<double*>(c.ws + c.w.acc0);
-  c.st = (hipStream_t)stream;
-  c.training = true;
-  c.parity = 0;
-  if (m->batch_norm)
-    for (int l = 0; l <= L; ++l)
-      GCMI_CHECK_ARG(io->d_bn_running_mean[l] && io->d_bn_running_var[l], "small_fit: NULL running statistics");
+  SRUN(small_ctx(m, d_params, io, ws_atoms, ws_mols, stream, true, "small_fit", &c));
   // clean accumulators and a clean gradient range at entry; every step leaves them clean for the next
   if (hipMemsetAsync(c.accs, 0, sizeof(double) * (size_t)c.w.acc_doubles, c.st) != hipSuccess ||
       hipMemsetAsync(d_grads + lo, 0, sizeof(float) * (size_t)(hi - lo), c.st) != hipSuccess) {
@@ -2020,16 +1960,10 @@ int gcmi_small_fit_opt(const gcmi_model_desc* m, float* d_params, float* d_grads
   std::vector<SmallGraph> graphs((size_t)n_batches);
   for (int64_t i = 0; i < n_batches; ++i) {
     const gcmi_small_batch* b = batches + i;
-    GCMI_CHECK_ARG(b->graph.n_atoms <= ws_atoms && b->graph.n_mols <= ws_mols,
-                   "small_fit: batch %lld (%d atoms, %d molecules) exceeds the workspace (%lld, %lld)", (long long)i,
-                   b->graph.n_atoms, b->graph.n_mols, (long long)ws_atoms, (long long)ws_mols);
+    SRUN(check_small_batch(b, i, m, ws_atoms, ws_mols, "small_fit"));
     GCMI_CHECK_ARG(b->d_labels && b->n_rows > 0 && b->n_rows <= b->graph.n_mols, "small_fit: batch %lld: bad labels / n_rows",
                    (long long)i);
-    GCMI_CHECK_ARG(b->graph.n_atoms == 0 || b->d_atom_features, "small_fit: NULL atom features");
-    GCMI_CHECK_ARG(b->graph.max_deg == m->max_deg, "small_fit: graph max_deg %d != model max_deg %d", b->graph.max_deg,
-                   m->max_deg);
-    SRUN(make_small_graph(&b->graph, true, &graphs[(size_t)i]));
-    graphs[(size_t)i].bf16 = m->storage >= 1 ? 1 : 0;  // (2: gradient streams too -- no such streams here, the batch lives in L2)
+    SRUN(make_small_graph(&b->graph, m, true, &graphs[(size_t)i]));
   }
   auto slot_of = [](int64_t i) { return (int)(((i / kAhead) & 1) * kAhead + i % kAhead); };
   const int64_t n_groups = (n_batches + kAhead - 1) / kAhead;
@@ -2141,28 +2075,13 @@ int gcmi_small_predict(const gcmi_model_desc* m, const float* d_params, const gc
   SRUN(small_check(m));
   GCMI_CHECK_ARG(d_params && io && io->d_workspace && (batches || n_batches == 0), "small_predict: NULL buffer");
   SmallCtx c;
-  c.m = m;
-  c.params = d_params;
-  c.io = io;
-  c.w = small_carve(m, ws_atoms, ws_mols);
-  c.ws = io->d_workspace;
-  c.accs = reinterpret_cast<double*>(c.ws + c.w.acc0);
-  c.st = (hipStream_t)stream;
-  c.training = false;
-  c.parity = 0;
-  if (m->batch_norm)
-    for (int l = 0; l <= m->n_layers; ++l)
-      GCMI_CHECK_ARG(io->d_bn_running_mean[l] && io->d_bn_running_var[l], "small_predict: NULL running statistics");
+  SRUN(small_ctx(m, d_params, io, ws_atoms, ws_mols, stream, false, "small_predict", &c));
   for (int64_t i = 0; i < n_batches; ++i) {
     const gcmi_small_batch* b = batches + i;
-    GCMI_CHECK_ARG(b->graph.n_atoms <= ws_atoms && b->graph.n_mols <= ws_mols,
-                   "small_predict: batch %lld exceeds the workspace", (long long)i);
+    SRUN(check_small_batch(b, i, m, ws_atoms, ws_mols, "small_predict"));
     GCMI_CHECK_ARG(b->d_logits && b->d_fingerprint, "small_predict: NULL output");
-    GCMI_CHECK_ARG(b->graph.n_atoms == 0 || b->d_atom_features, "small_predict: NULL atom features");
-    GCMI_CHECK_ARG(b->graph.max_deg == m->max_deg, "small_predict: graph max_deg != model max_deg");
     SmallGraph g;
-    SRUN(make_small_graph(&b->graph, false, &g));
-    g.bf16 = m->storage >= 1 ? 1 : 0;
+    SRUN(make_small_graph(&b->graph, m, false, &g));
     SRUN(small_forward_body(c, g, b->d_atom_features, b->ld_features));
     ReadoutArgs ra;
     memset(&ra, 0, sizeof(ra));

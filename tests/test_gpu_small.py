@@ -165,11 +165,19 @@ def test_small_engine_prediction_matches_the_oracle(mode, T, B, n, bn):
             assert np.abs(fp.cpu().numpy() - ref[1].numpy()).max() < 1e-4
 
 
-def test_small_engine_other_widths():
-    """[128, 128] GraphConv layers and a 256-wide dense layer (MolNet's regression preset,
-    molnet/preset_hyper_parameters.py:128-135)."""
+# (192, 256) / 64 and (256, 192) / 128 would reach the three- and four-tile forms of the product kernels and the 64-wide
+# readout, but the per-batch path this test compares against does not hold the bounds below at those widths (DESIGN
+# section 33 has the figures), so they are not cases here.
+OTHER_WIDTHS = [((128, 128), 256)]
+
+
+@pytest.mark.parametrize("widths,dense", OTHER_WIDTHS)
+def test_small_engine_other_widths(widths, dense):
+    """GraphConv and dense widths other than the default 64/64/128: [128, 128] with a 256-wide dense layer is MolNet's
+    regression preset (molnet/preset_hyper_parameters.py:128-135).  Training against the per-batch path from the same
+    state, then the eval-mode forward of one batch against the per-batch forward."""
     from deepchem_amd.small import SmallBatchEngine
-    packed, y, w, cfg, state, model = _setup("regression", 1, 12, 44, True, "full", seed=11, widths=(128, 128), dense=256)
+    packed, y, w, cfg, state, model = _setup("regression", 1, 12, 44, True, "full", seed=11, widths=widths, dense=dense)
     model._ensure_built()
     model.model.train()
     native = model.model._native_net()
@@ -182,25 +190,43 @@ def test_small_engine_other_widths():
     import deepchem_amd as dc
     dc.set_gemm_mode("exact")
     try:
-        ref_model = dc.models.torch_models.GraphConvModel(1, number_input_features=[75, 128], graph_conv_layers=[128, 128],
-                                                          dense_layer_size=256, mode="regression", batch_size=12,
-                                                          grad_mode="full", device=torch.device(DEV), learning_rate=1e-3)
+        ref_model = dc.models.torch_models.GraphConvModel(1, number_input_features=[75, widths[0]],
+                                                          graph_conv_layers=list(widths), dense_layer_size=dense,
+                                                          mode="regression", batch_size=12, grad_mode="full",
+                                                          device=torch.device(DEV), learning_rate=1e-3)
         ref_model.model.load_state_dict({k: v.clone() for k, v in state.items()})
         ref_model._ensure_built()
         ref_model.model.train()
         ref = []
         for b, l, ww, _, _ in batches:
             ref.append(float(ref_model._train_step(b, [l], [ww], ref_model._loss_fn, ref_model._pytorch_optimizer)))
+        # the first step has no history: tight.  From the second on Adam has moved entries whose gradient is at rounding
+        # level by lr * sign(noise), in any arithmetic (the per-batch path's own two product modes drift by 2e-4 here)
+        assert abs(losses[0] - ref[0]) <= 1e-5 * abs(ref[0]), (losses, ref)
+        assert np.allclose(losses, ref, rtol=2e-3, atol=1e-6), (losses, ref)
+        sd, rsd = model.model.state_dict(), ref_model.model.state_dict()
+        for k in sd:
+            a, b = sd[k].float().cpu().numpy(), rsd[k].float().cpu().numpy()
+            _same_after_adam(k, a, b, len(batches), "running" not in k and "num_batches" not in k)
+        # the forward of one batch in eval mode: the engine against the per-batch path, both from the reference state
+        # (the engine reads the parameters of `model`: give it the reference model's)
+        model.model.load_state_dict({k: v.clone() for k, v in rsd.items()})
+        model.model.eval()
+        ref_model.model.eval()
+        batch = batches[0][0]
+        d = engine.describe(batch)
+        lo = torch.empty((12, 1), device=DEV)
+        fp = torch.empty((12, 2 * dense), device=DEV)
+        d.d_logits, d.d_fingerprint = lo.data_ptr(), fp.data_ptr()
+        engine.predict([d], batch.n_atoms, 12)
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            want = ref_model.model(batch)
     finally:
         dc.set_gemm_mode("fast")
-    # the first step has no history: tight.  From the second on Adam has moved entries whose gradient is at rounding
-    # level by lr * sign(noise), in any arithmetic (the per-batch path's own two product modes drift by 2e-4 here)
-    assert abs(losses[0] - ref[0]) <= 1e-5 * abs(ref[0]), (losses, ref)
-    assert np.allclose(losses, ref, rtol=2e-3, atol=1e-6), (losses, ref)
-    sd, rsd = model.model.state_dict(), ref_model.model.state_dict()
-    for k in sd:
-        a, b = sd[k].float().cpu().numpy(), rsd[k].float().cpu().numpy()
-        _same_after_adam(k, a, b, len(batches), "running" not in k and "num_batches" not in k)
+    want_lo, want_fp = want[0].detach().float().cpu().numpy(), want[-1].detach().float().cpu().numpy()
+    assert np.abs(lo.cpu().numpy().reshape(want_lo.shape) - want_lo).max() < 1e-4 * max(1.0, float(np.abs(want_lo).max()))
+    assert np.abs(fp.cpu().numpy() - want_fp).max() < 1e-4
 
 
 # ------------------------------------------------------------------ bf16 activation storage (opt-in)

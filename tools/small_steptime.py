@@ -59,7 +59,7 @@ def main():
         e1.record()
         torch.cuda.synchronize()
         devt.append(e0.elapsed_time(e1) * 1e-3)
-    print(json.dumps({"batch": B, "grad_mode": gm, "steps_per_call": n_b, "diag": os.environ.get("GCMI_SMALL_DIAG", "0"),
+    print(json.dumps({"batch": B, "grad_mode": gm, "steps_per_call": n_b,
                       "host_us_per_step": round(min(host) / n_b * 1e6, 2), "device_us_per_step": round(min(devt) / n_b * 1e6, 2),
                       "collate_us_per_batch": round(collate_s / n_b * 1e6, 2),
                       "molecules_per_s_device": round(B * n_b / min(devt), 1)}))
