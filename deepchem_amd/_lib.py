@@ -25,6 +25,7 @@ GCMI_OPT_FUSED_BWD = 3
 GCMI_OPT_FUSED_BWD_LAUNCHES = 4
 GCMI_OPT_READOUT_PIPELINED = 5
 GCMI_OPT_ONE_PIECE_LAUNCHES = 6
+GCMI_OPT_MAX_SUM_LAUNCHES = 7
 GCMI_METRIC_ROC_AUC, GCMI_METRIC_PRC_AUC = 0, 1
 GCMI_METRIC_MOMENTS, GCMI_METRIC_ACCURACY = 0, 1
 GCMI_METRIC_MOMENT_DOUBLES = 12
@@ -166,6 +167,7 @@ _SIGNATURES = {
     "gcmi_scatter_add": [_G, _P, c_int64, c_int32, _P, c_int64, _P],
     "gcmi_gather_max_fwd": [_G, _P, c_int64, c_int32, _P, _P, _P, c_int64, _P, _P],
     "gcmi_gather_max_bwd": [_G, _P, c_int64, c_int32, _P, _P, c_int64, _P],
+    "gcmi_gather_max_sum_fwd": [_G, _P, c_int64, c_int32, _P, _P, _P, c_int64, _P, _P, c_int64, _P],
     "gcmi_readout_fwd": [_G, _P, c_int64, c_int32, _P, _P, c_int32, _P, c_int64, _P, _P],
     "gcmi_readout_bwd": [_G, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P],
     "gcmi_bn_stats": [_P, c_int64, c_int64, c_int32, _P, _P, c_float, c_float, _P, _P, _P, _P, _P,

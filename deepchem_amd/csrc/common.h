@@ -87,6 +87,13 @@ int win_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, i
 bool win_two_stage_usable(const gcmi_graph* g, int n_feat);
 int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int n_feat, float* d_dxs,
                               int64_t lddxs, const uint8_t* d_arg, float* d_dy, int64_t lddy, hipStream_t st);
+// GraphPool followed by the neighbour sum of the block above in one window pass (n_feat 64 / 128): the pooled rows are
+// written but not read back
+bool win_max_sum_usable(const gcmi_graph* g, int n_feat);
+int win_gather_max_sum(const gcmi_graph* g, const float* d_y, int64_t ldy, int n_feat, const float* d_scale,
+                       const float* d_shift, float* d_pool, int64_t ldp, uint8_t* d_arg, float* d_s, int64_t lds,
+                       hipStream_t st);
+int max_sum_launches();  // launches of that pass so far (tests)
 // the GraphPool backward that returns at once unless the pooled BatchNorm sums are ill-conditioned (BnBackward::psums)
 int win_gather_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
                               float* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, hipStream_t st);

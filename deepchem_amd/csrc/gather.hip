@@ -449,6 +449,30 @@ int gcmi_gather_max_fwd(const gcmi_graph* g, const float* d_x, int64_t ldx, int3
   return GCMI_OK;
 }
 
+int gcmi_gather_max_sum_fwd(const gcmi_graph* g, const float* d_y, int64_t ldy, int32_t n_feat,
+                            const float* d_scale, const float* d_shift, float* d_pool, int64_t ldp,
+                            uint8_t* d_arg, float* d_s, int64_t lds, void* stream) {
+  int rc = check_graph(g, true);
+  if (rc) return rc;
+  GCMI_CHECK_ARG(n_feat > 0 && ldy >= n_feat && ldp >= n_feat && lds >= n_feat, "gather_max_sum: bad n_feat/ld");
+  GCMI_CHECK_ARG(g->n_atoms == 0 || (d_y && d_pool && d_s), "gather_max_sum: NULL buffer");
+  GCMI_CHECK_ARG((d_scale == nullptr) == (d_shift == nullptr), "gather_max_sum: scale/shift must come together");
+  if (g->n_atoms == 0) return GCMI_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const bool v4 = vec_width(d_y, ldy, n_feat) == 4 && vec_width(d_pool, ldp, n_feat) == 4 &&
+                  vec_width(d_s, lds, n_feat) == 4 && (d_arg == nullptr || (reinterpret_cast<uintptr_t>(d_arg) & 3u) == 0) &&
+                  (d_scale == nullptr || (aligned16(d_scale) && aligned16(d_shift)));
+  if (v4 && win_max_sum_usable(g, n_feat)) {
+    // (timed with the gather-sum family: the pass stands where a gather-sum launch stood, and bench.py prices the
+    // gather-sum bytes of a step against that timer)
+    TimedScope ts(GCMI_K_GATHER_SUM, st);
+    return win_gather_max_sum(g, d_y, ldy, n_feat, d_scale, d_shift, d_pool, ldp, d_arg, d_s, lds, st);
+  }
+  rc = gcmi_gather_max_fwd(g, d_y, ldy, n_feat, d_scale, d_shift, d_pool, ldp, d_arg, stream);
+  if (rc) return rc;
+  return gcmi_gather_sum_fwd(g, d_pool, ldp, n_feat, d_s, lds, 0, stream);
+}
+
 int gcmi_build_rev_pos(const gcmi_graph* g, uint8_t* d_rev_pos, int32_t* d_flag, void* stream) {
   int rc = check_graph(g, true);
   if (rc) return rc;

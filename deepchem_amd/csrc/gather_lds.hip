@@ -344,13 +344,20 @@ __device__ __forceinline__ void pool_bwd(const typename P::Raw* tile, const char
 //             also a wait for the LDS-DMA of the next window (one counter, in order), which the loop would wait for at
 //             its top anyway.  kPre = 1: one piece at a time, the old piece loaded before its neighbour loop.
 
+
+// What a two-stage op keeps behind the two window buffers, in tiles the size of a window tile (Op::kThird):
+//   dma_pair  one per window buffer, filled by the LDS-DMA with the window's rows of a second matrix (stage_extra);
+//   scratch   one per workgroup, written and read by the compute phase of one window only.
+enum class Third { none, dma_pair, scratch };
+constexpr int third_tiles(Third k) { return k == Third::dma_pair ? 2 : k == Third::scratch ? 1 : 0; }
+
 // s = (ACC: s +) sum of the neighbours' rows (ACC: the transposed gather of a backward pass onto the self term)
 template <class Op, class T, bool ACC>
 struct SumBody {
   using P = Piece<T>;
   T* __restrict__ s;
   int64_t lds;
-  static constexpr bool kExtraTile = false;
+  static constexpr Third kThird = Third::none;
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
   __device__ __forceinline__ void init(float*, int) const {}
@@ -412,7 +419,7 @@ struct SumOpFH {
   bf16_t* __restrict__ xcopy;
   int64_t ldo;
   int pad4;
-  static constexpr bool kExtraTile = false;
+  static constexpr Third kThird = Third::none;
   static constexpr int kThreads = 512;
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
@@ -449,7 +456,7 @@ struct MaxBody {
   T* __restrict__ out;
   int64_t ldo;
   uint8_t* __restrict__ arg;
-  static constexpr bool kExtraTile = false;
+  static constexpr Third kThird = Third::none;
   __device__ __forceinline__ bool skip(int) const { return false; }
   // the folded BatchNorm vectors live in LDS: a global load in the compute phase would make the
   // compiler wait for the LDS-DMA in flight as well
@@ -495,7 +502,7 @@ struct MaxBwdBody {
   // optional (bn_bwd_pool_impl): dx is needed only where the pooled BatchNorm sums are ill-conditioned
   const float* __restrict__ only_if_gamma;
   const float* __restrict__ only_if_beta;
-  static constexpr bool kExtraTile = false;
+  static constexpr Third kThird = Third::none;
   __device__ __forceinline__ bool skip(int n_feat) const {
     return only_if_gamma != nullptr && !bn_pool_ill_conditioned(only_if_gamma, only_if_beta, n_feat);
   }
@@ -539,8 +546,6 @@ struct MaxBwdOpH : MaxBwdBody<MaxBwdOpH, bf16_t> {
 // overlapped the next one's load (281 us at 96-atom windows against 181 at 192-atom ones: a fixed ~3.8 us per window).
 // dX is completed IN PLACE in it, in the rows' own element type: over bf16 streams it is rounded to bf16 once, exactly
 // what the two separate passes do when they write dX to HBM as a bf16 matrix between them.
-constexpr int kThirdTiles = 2;  // third tiles per workgroup, each the size of a window tile: one per window buffer
-
 template <class T>
 struct SumAccMaxBwdBody {
   using P = Piece<T>;
@@ -548,7 +553,7 @@ struct SumAccMaxBwdBody {
   int64_t lddxs;
   T* __restrict__ dy;
   int64_t lddy;
-  static constexpr bool kExtraTile = true;
+  static constexpr Third kThird = Third::dma_pair;
   __device__ __forceinline__ const char* extra_src() const { return reinterpret_cast<const char*>(dxs); }
   __device__ __forceinline__ int64_t extra_ld_bytes() const { return lddxs * (int64_t)sizeof(T); }
   __device__ __forceinline__ bool skip(int) const { return false; }
@@ -589,6 +594,60 @@ struct SumAccMaxBwdOpH : SumAccMaxBwdBody<bf16_t> {
   static constexpr int kThreads = 512;
 };
 
+// The forward between two GraphConv blocks in one window pass: GraphPool of the block below (MaxBody), then the
+// neighbour sum of the block above (SumBody) over the pooled rows of the window.
+//   P[k] = max(y[k], y[i_j])   -> out (+ arg bytes),  and, as stored (narrow), into the third tile
+//   S[k] = sum_j P[i_j]        -> s
+// The pooled rows are still written (the product above and the backward read them) but not read back: the second
+// launch's N*F elements from HBM, its neighbour entries and its window walk go.  The third tile is one scratch tile per
+// workgroup: the DMA never touches it, and the walker's barrier at the top of the next window separates stage 2 of
+// this window from stage 1 of the next.  Both stages call the loops the separate ops call, on the same values, so the
+// pass equals MaxOp followed by SumOp bit for bit.  Oversized windows are not handled (the launcher refuses).
+template <class T, bool BN>
+struct MaxSumBody {
+  using P = Piece<T>;
+  MaxBody<T, BN> pool;  // scale, shift, out, ldo, arg
+  T* __restrict__ s;
+  int64_t lds;
+  static constexpr Third kThird = Third::scratch;
+  __device__ __forceinline__ bool skip(int) const { return false; }
+  template <int WT>
+  __device__ __forceinline__ void init(float* sh_lds, int n_feat) const { pool.template init<WT>(sh_lds, n_feat); }
+  template <int WT, int LPR>
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float* sh_lds,
+                                      char* extra) const {
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    typename P::Raw* t2 = reinterpret_cast<typename P::Raw*>(extra);
+    // ---- stage 1: the GraphPool of the window, to HBM and into the third tile
+    for (int e = threadIdx.x; e < w.n16; e += WT) {
+      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      typename P::Vals best;
+      typename P::Bytes ba;
+      pool_max<P, LPR, BN>(w.tile, w.ent + at.eloc, at.d, e, at.c, sh_lds, best, ba);
+      store_piece(pool.out + (int64_t)at.row * pool.ldo + at.c * P::kEPP, best);
+      if (pool.arg) P::store_arg(pool.arg + (int64_t)at.row * (LPR * P::kEPP) + at.c * P::kEPP, ba);
+      t2[e] = P::narrow(best);
+    }
+    __syncthreads();
+    // ---- stage 2: the neighbour sum over the pooled rows
+    for (int e = threadIdx.x; e < w.n16; e += WT) {
+      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      typename P::Vals acc;
+      neigh_sum<P, LPR>(t2, w.ent + at.eloc, at.d, at.c, acc);
+      store_piece(s + (int64_t)at.row * lds + at.c * P::kEPP, acc);
+    }
+  }
+};
+
+// measured at 1.2 M atoms (us per launch, with arg bytes; MaxOp + SumOp on the same rows: 248 and 752):
+//   64 columns (two workgroups per CU by LDS):  253 / 186 / 206 at 256 / 512 / 1 024 threads
+//   128 columns (one workgroup per CU by LDS):  846 / 477 / 378
+// so the launcher picks WT by the width (max_sum below)
+template <bool BN, int WT>
+struct MaxSumOp : MaxSumBody<float, BN> {
+  static constexpr int kThreads = WT;
+};
+
 // ---------------------------------------------------------------- the persistent window walker
 // Workgroups [0, g_norm) walk the ordinary windows double-buffered; workgroups [g_norm, gridDim)
 // walk the oversized windows (one big molecule each) using both buffers as one.
@@ -604,12 +663,14 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
   float* op_lds = reinterpret_cast<float*>(smem_all + kRingBytes);
   char* smem = smem_all + kHeadBytes;
   constexpr int kEPP = Op::P::kEPP;
-  constexpr bool kXT = Op::kExtraTile;  // a third tile per window buffer, behind the two, DMA-filled with the window
+  constexpr bool kXT = Op::kThird == Third::dma_pair;  // a third tile per window buffer, DMA-filled with the window
+  constexpr bool kScratch = Op::kThird == Third::scratch;  // one third tile, the compute phase's own
   if (op.skip(LPR * kEPP)) return;  // uniform over the grid
   op.template init<WT>(op_lds, LPR * kEPP);
-  // the compute phase of one window: ops with a third tile get it, the others the op constants
+  // the compute phase of one window: ops with a third tile get it, the others the op constants (scratch: both)
   auto compute = [&](const char* buf, const Layout& l, const WinMeta& m, char* extra) {
     if constexpr (kXT) op.template run<WT, LPR>(buf, l, m, extra);
+    else if constexpr (kScratch) op.template run<WT, LPR>(buf, l, m, op_lds, extra);
     else op.template run<WT, LPR>(buf, l, m, op_lds);
   };
   const int t = threadIdx.x;
@@ -657,7 +718,7 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
         stage_extra<WT, LPR>(smem + 2 * bb + ((it + 1) & 1) * L.tile_bytes, L, read_meta(ring[(it + 1) % 3]), op.extra_src(),
                              op.extra_ld_bytes());
     }
-    compute(smem + (it & 1) * bb, L, read_meta(ring[it % 3]), smem + 2 * bb + (it & 1) * L.tile_bytes);
+    compute(smem + (it & 1) * bb, L, read_meta(ring[it % 3]), smem + 2 * bb + (kXT ? (it & 1) * L.tile_bytes : 0));
     if (!has_next) break;
     w += G;
     ++it;
@@ -714,10 +775,10 @@ static bool plan_fits(const gcmi_graph* g, int n_floats, int aux) {
   if (g->d_win_edges == nullptr || g->n_win_big < 0 || g->n_win_big > g->n_win) return false;
   return make_plan(g, n_floats, aux).ok;
 }
-// ... and so do the third tiles of the two-stage pass
-static bool third_tiles_fit(const gcmi_graph* g, int n_floats, int aux) {
+// ... and so do the third tiles of a two-stage pass
+static bool third_tiles_fit(const gcmi_graph* g, int n_floats, int aux, Third kind) {
   const WinPlan p = make_plan(g, n_floats, aux);
-  return p.shmem + (size_t)kThirdTiles * p.L.tile_bytes <= (size_t)kLdsPerCU;
+  return p.shmem + (size_t)third_tiles(kind) * p.L.tile_bytes <= (size_t)kLdsPerCU;
 }
 
 // which: 0 all windows, 1 ordinary, 2 oversized only
@@ -733,12 +794,12 @@ static int launch_lpr(const gcmi_graph* g, const WinPlan& p, const char* x, int6
   }
   const int n_norm = g->n_win - g->n_win_big;
   size_t shmem = p.shmem;
-  if constexpr (Op::kExtraTile) {
+  if constexpr (Op::kThird != Third::none) {
     if (which != 1) {
       set_error("%s: oversized windows are not handled by the two-stage form", what);
       return GCMI_ERR_UNSUPPORTED;
     }
-    shmem += (size_t)p.L.tile_bytes * kThirdTiles;
+    shmem += (size_t)p.L.tile_bytes * third_tiles(Op::kThird);
     if (shmem > (size_t)kLdsPerCU) return GCMI_ERR_UNSUPPORTED;
   }
   const int by_lds = (int)((size_t)kLdsPerCU / shmem);
@@ -747,8 +808,13 @@ static int launch_lpr(const gcmi_graph* g, const WinPlan& p, const char* x, int6
   const int g_norm = which == 2 ? 0 : std::min(n_norm, 256 * per_cu);
   const int g_big = which == 1 ? 0 : std::min(g->n_win_big, 64);
   if (g_norm + g_big == 0) return GCMI_OK;
+  const int rev = next_sweep_direction();
+  // The forward two-stage pass stands where two launches stood and takes both their turns (it walks in the first one's
+  // direction, from the end its producer finished at): every later kernel keeps the direction, and with it the order
+  // of its partial sums, that it has after the two separate launches.  Measured against taking one turn: §34.
+  if constexpr (Op::kThird == Third::scratch) (void)next_sweep_direction();
   hipLaunchKernelGGL(kern, dim3(g_norm + g_big), dim3(WT), shmem, st, g->d_win_meta, g->d_win_edges, n_norm,
-                     g->n_win, g_norm, p.L, p.Lbig, x, ldx, aux, op, next_sweep_direction());
+                     g->n_win, g_norm, p.L, p.Lbig, x, ldx, aux, op, rev);
   GCMI_CHECK_LAUNCH(what);
   return GCMI_OK;
 }
@@ -834,7 +900,7 @@ int win_gather_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t 
 }
 
 bool win_two_stage_usable(const gcmi_graph* g, int n_feat) {
-  return win_has_width(n_feat) && win_usable(g, n_feat, true) && third_tiles_fit(g, n_feat, 4);
+  return win_has_width(n_feat) && win_usable(g, n_feat, true) && third_tiles_fit(g, n_feat, 4, Third::dma_pair);
 }
 
 int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int n_feat, float* d_dxs,
@@ -843,6 +909,56 @@ int win_gather_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ld
       g, d_ds, ldds, n_feat, d_dxs, lddxs, d_arg, d_dy, lddy, st,
       {"win_gather_sumacc_max_bwd", "win_gather_sum (accumulate, oversized windows)",
        "win_gather_max_bwd (oversized windows)"});
+}
+
+bool win_max_sum_usable(const gcmi_graph* g, int n_feat) {
+  return win_has_width(n_feat) && (n_feat == 64 || n_feat == 128) && win_usable(g, n_feat, false) &&
+         third_tiles_fit(g, n_feat, 0, Third::scratch);
+}
+
+static std::atomic<int> g_max_sum_launches{0};
+int max_sum_launches() { return g_max_sum_launches.load(std::memory_order_relaxed); }
+
+// the two-stage pass over the ordinary windows
+template <bool BN>
+static int max_sum(const gcmi_graph* g, const float* d_y, int64_t ldy, int n_feat, const MaxBody<float, BN>& pool,
+                   float* d_s, int64_t lds, hipStream_t st) {
+  // (launch_lpr directly: two widths, a thread count each -- launch<> would instantiate both for every piece count)
+  const WinPlan p = make_plan(g, n_feat, 0);
+  const char* yb = reinterpret_cast<const char*>(d_y);
+  const int64_t ldb = ldy * (int64_t)sizeof(float);
+  if (n_feat == 128) {  // one workgroup per CU by LDS: a full one
+    MaxSumOp<BN, 1024> op{{pool, d_s, lds}};
+    return launch_lpr<32, false>(g, p, yb, ldb, nullptr, op, st, "win_gather_max_sum", 1);
+  }
+  if (n_feat == 64) {
+    MaxSumOp<BN, 512> op{{pool, d_s, lds}};
+    return launch_lpr<16, false>(g, p, yb, ldb, nullptr, op, st, "win_gather_max_sum", 1);
+  }
+  set_error("win_gather_max_sum: no window kernel for %d features", n_feat);
+  return GCMI_ERR_UNSUPPORTED;
+}
+
+// d_pool = GraphPool of the rows of d_y (+ arg bytes), d_s = the neighbour sums of d_pool.  The ordinary windows take
+// the two-stage pass; the few oversized ones the two separate passes over their own rows.
+int win_gather_max_sum(const gcmi_graph* g, const float* d_y, int64_t ldy, int n_feat, const float* d_scale,
+                       const float* d_shift, float* d_pool, int64_t ldp, uint8_t* d_arg, float* d_s, int64_t lds,
+                       hipStream_t st) {
+  int rc = d_scale ? max_sum<true>(g, d_y, ldy, n_feat, {d_scale, d_shift, d_pool, ldp, d_arg}, d_s, lds, st)
+                   : max_sum<false>(g, d_y, ldy, n_feat, {nullptr, nullptr, d_pool, ldp, d_arg}, d_s, lds, st);
+  if (rc) return rc;
+  if (g->n_win > g->n_win_big) g_max_sum_launches.fetch_add(1, std::memory_order_relaxed);
+  if (g->n_win_big == 0) return rc;
+  if (d_scale) {
+    MaxOp<true> mx{{d_scale, d_shift, d_pool, ldp, d_arg}};
+    rc = launch<false>(g, n_feat, d_y, ldy, nullptr, mx, st, "win_gather_max (oversized windows)", 2);
+  } else {
+    MaxOp<false> mx{{nullptr, nullptr, d_pool, ldp, d_arg}};
+    rc = launch<false>(g, n_feat, d_y, ldy, nullptr, mx, st, "win_gather_max (oversized windows)", 2);
+  }
+  if (rc) return rc;
+  SumOp<false> sm{{d_s, lds}};
+  return launch<false>(g, n_feat, d_pool, ldp, nullptr, sm, st, "win_gather_sum (oversized windows)", 2);
 }
 
 // ---- bf16 activation storage (storage >= 1)
@@ -888,7 +1004,7 @@ int win_gather_max_bwd_h(const gcmi_graph* g, const bf16_t* d_dout, int64_t lddo
 }
 
 bool win_two_stage_usable_h(const gcmi_graph* g, int n_feat) {
-  return win_usable_gh(g, n_feat) && third_tiles_fit(g, n_feat / 2, 8);
+  return win_usable_gh(g, n_feat) && third_tiles_fit(g, n_feat / 2, 8, Third::dma_pair);
 }
 
 int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const bf16_t* d_ds, int64_t ldds, int n_feat, bf16_t* d_dxs,

@@ -628,13 +628,14 @@ int gcmi_set_option(int32_t option, int32_t value) {
 int gcmi_get_option(int32_t option, int32_t* value) {
   GCMI_CHECK_ARG((option == GCMI_OPT_GEMM_EXACT || option == GCMI_OPT_FUSED_BN_STATS || option == GCMI_OPT_FUSED_BWD ||
                   option == GCMI_OPT_FUSED_BWD_LAUNCHES || option == GCMI_OPT_READOUT_PIPELINED ||
-                  option == GCMI_OPT_ONE_PIECE_LAUNCHES) && value,
+                  option == GCMI_OPT_ONE_PIECE_LAUNCHES || option == GCMI_OPT_MAX_SUM_LAUNCHES) && value,
                  "get_option: unknown option %d", option);
   if (option == GCMI_OPT_GEMM_EXACT) *value = g_gemm_exact.load(std::memory_order_relaxed);
   else if (option == GCMI_OPT_FUSED_BN_STATS) *value = g_fused_bn_stats.load(std::memory_order_relaxed);
   else if (option == GCMI_OPT_FUSED_BWD) *value = get_fused_bwd();
   else if (option == GCMI_OPT_READOUT_PIPELINED) *value = get_readout_pipelined();
   else if (option == GCMI_OPT_ONE_PIECE_LAUNCHES) *value = one_piece_launches();
+  else if (option == GCMI_OPT_MAX_SUM_LAUNCHES) *value = max_sum_launches();
   else *value = fused_bwd_launches();
   return GCMI_OK;
 }

@@ -876,15 +876,22 @@ int gcmi_model_forward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const f
       RUN(one_piece_forward(g, w, ws, b, sg, io, stats, st));
       stats_fused = training != 0;
     } else if (N > 0) {
-      RUN(gcmi_gather_sum_fwd(g, x, ldx, (int32_t)w.ngather[l], ws + w.S[l], w.ldS[l], 0, stream));
+      // (l > 0: the GraphPool of the block below left the neighbour sums of its output with it)
+      if (l == 0) RUN(gcmi_gather_sum_fwd(g, x, ldx, (int32_t)w.ngather[l], ws + w.S[l], w.ldS[l], 0, stream));
       RUN(seg_gemm_stats(conv_product(sg, ws + w.S[l], w.ldS[l], x, ldx, b, ws + w.gc[l]), stats, &stats_fused, st,
                          ws + w.wimg));
     }
     const bool bn = m->batch_norm && N > 0;
     if (bn || sy) RUN(bn_forward(b, N, training, stats_fused, ws + w.gc[l], W, acc, stream, sy));
-    if (N > 0)
-      RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, bn ? b.bn.scale : nullptr, bn ? b.bn.shift : nullptr, ws + w.pool[l], W,
-                              training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, stream));
+    if (N > 0) {
+      uint8_t* arg = training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr;
+      const float* sc = bn ? b.bn.scale : nullptr;
+      const float* sh = bn ? b.bn.shift : nullptr;
+      if (l + 1 < L)  // GraphPool and the neighbour sums of the block above in one window pass
+        RUN(gcmi_gather_max_sum_fwd(g, ws + w.gc[l], W, W, sc, sh, ws + w.pool[l], W, arg, ws + w.S[l + 1], w.ldS[l + 1], stream));
+      else
+        RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, sc, sh, ws + w.pool[l], W, arg, stream));
+    }
     x = ws + w.pool[l];
     ldx = W;
   }

@@ -93,6 +93,28 @@ def gather_max(g: BatchGraph, x: torch.Tensor, scale=None, shift=None, want_arg:
     return out, arg
 
 
+def gather_max_sum(g: BatchGraph, y: torch.Tensor, scale=None, shift=None, want_arg: bool = True):
+    """``gather_max`` of ``y`` and ``gather_sum`` of its result, bit for bit, in one window pass where the batch allows.
+    Returns (pooled rows, arg bytes or None, neighbour sums of the pooled rows)."""
+    _mat(y, "y", rows=g.n_atoms)
+    F_ = y.shape[1]
+    _vec(scale, "scale", F_)
+    _vec(shift, "shift", F_)
+    pool = torch.empty((g.n_atoms, F_), dtype=torch.float32, device=y.device)
+    arg = torch.empty((g.n_atoms, F_), dtype=torch.uint8, device=y.device) if want_arg else None
+    s = torch.empty((g.n_atoms, F_), dtype=torch.float32, device=y.device)
+    _lib.call("gcmi_gather_max_sum_fwd", g.ref, _ptr(y), _ld(y), F_, _ptr(scale), _ptr(shift), _ptr(pool),
+              _ld(pool), _ptr(arg), _ptr(s), _ld(s), _stream())
+    return pool, arg, s
+
+
+def max_sum_launches() -> int:
+    """Launches so far of the window pass behind ``gather_max_sum`` (and the model forward between two blocks)."""
+    v = ctypes.c_int32(0)
+    _lib.call("gcmi_get_option", _lib.GCMI_OPT_MAX_SUM_LAUNCHES, ctypes.byref(v))
+    return v.value
+
+
 def gather_max_bwd(g: BatchGraph, dout: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
     _mat(dout, "dout", rows=g.n_atoms)
     F_ = dout.shape[1]

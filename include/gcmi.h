@@ -128,7 +128,10 @@ enum {
   GCMI_OPT_READOUT_PIPELINED = 5,
   /* read-only (gcmi_get_option): launches so far of the first GraphConv block's one-piece kernels (forward product and
    * backward each count one), taken when gcmi_model_io.features_small_int holds                                  */
-  GCMI_OPT_ONE_PIECE_LAUNCHES = 6
+  GCMI_OPT_ONE_PIECE_LAUNCHES = 6,
+  /* read-only (gcmi_get_option): launches so far of the window pass that forms a GraphPool and the neighbour sums of
+   * its output together (gcmi_gather_max_sum_fwd, and the model forward between two GraphConv blocks)              */
+  GCMI_OPT_MAX_SUM_LAUNCHES = 7
 };
 int gcmi_set_option(int32_t option, int32_t value);
 int gcmi_get_option(int32_t option, int32_t* value);
@@ -257,6 +260,14 @@ int gcmi_gather_max_fwd(const gcmi_graph* g, const float* d_x, int64_t ldx, int3
                         uint8_t* d_arg, void* stream);
 int gcmi_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, int32_t n_feat,
                         const uint8_t* d_arg, float* d_dx, int64_t lddx, void* stream);
+/* GraphPool followed by GraphConv.sum_neigh of its output (the forward between two GraphConv blocks):
+ *   d_pool, d_arg = gcmi_gather_max_fwd(d_y, scale, shift);   d_s = gcmi_gather_sum_fwd(d_pool)
+ * bit for bit.  Where the batch has molecule windows and n_feat is 64 or 128 (16-byte addressable rows) both are
+ * formed in one pass over d_y, the pooled rows of a window held in LDS between the two; otherwise the two calls
+ * above run one after the other.  d_arg may be NULL (evaluation).                                              */
+int gcmi_gather_max_sum_fwd(const gcmi_graph* g, const float* d_y, int64_t ldy, int32_t n_feat,
+                            const float* d_scale, const float* d_shift, float* d_pool, int64_t ldp,
+                            uint8_t* d_arg, float* d_s, int64_t lds, void* stream);
 
 /* ---------------------------------------------------------------- K4 readout
  * GraphGather.forward (layers.py:6450-6479) = unsorted_segment_sum
