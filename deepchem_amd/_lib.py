@@ -168,6 +168,13 @@ _SIGNATURES = {
     "gcmi_gather_max_fwd": [_G, _P, c_int64, c_int32, _P, _P, _P, c_int64, _P, _P],
     "gcmi_gather_max_bwd": [_G, _P, c_int64, c_int32, _P, _P, c_int64, _P],
     "gcmi_gather_max_sum_fwd": [_G, _P, c_int64, c_int32, _P, _P, _P, c_int64, _P, _P, c_int64, _P],
+    "gcmi_win_sum_h": [_G, _P, c_int64, c_int32, _P, c_int64, c_int32, _P],
+    "gcmi_win_sum_fh": [_G, _P, c_int64, c_int32, _P, _P, c_int64, _P],
+    "gcmi_win_max_h": [_G, _P, c_int64, c_int32, _P, _P, _P, c_int64, _P, _P],
+    "gcmi_win_max_bwd_h": [_G, _P, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P],
+    "gcmi_win_max_bwd_if_ill": [_G, _P, c_int64, c_int32, _P, _P, c_int64, _P, _P, _P],
+    "gcmi_win_sumacc_max_bwd": [_G, _P, c_int64, c_int32, _P, c_int64, _P, _P, c_int64, _P],
+    "gcmi_win_sumacc_max_bwd_h": [_G, _P, c_int64, c_int32, _P, c_int64, _P, _P, c_int64, _P],
     "gcmi_readout_fwd": [_G, _P, c_int64, c_int32, _P, _P, c_int32, _P, c_int64, _P, _P],
     "gcmi_readout_bwd": [_G, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, c_int64, _P],
     "gcmi_bn_stats": [_P, c_int64, c_int64, c_int32, _P, _P, c_float, c_float, _P, _P, _P, _P, _P,

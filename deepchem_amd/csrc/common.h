@@ -481,7 +481,7 @@ bool win_usable_h(const gcmi_graph* g, int n_feat);
 int win_gather_sum_fh(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_feat, unsigned short* d_s,
                       unsigned short* d_xcopy, int64_t ldo, hipStream_t st);
 int win_gather_sum_h(const gcmi_graph* g, const unsigned short* d_x, int64_t ldx, int n_feat, unsigned short* d_s,
-                     int64_t lds, hipStream_t st);
+                     int64_t lds, hipStream_t st, bool accumulate = false);
 int win_gather_max_h(const gcmi_graph* g, const unsigned short* d_x, int64_t ldx, int n_feat, const float* d_scale,
                      const float* d_shift, unsigned short* d_out, int64_t ldo, uint8_t* d_arg, hipStream_t st);
 // gradient streams in bf16 (storage == 2)
@@ -490,6 +490,9 @@ int win_gather_max_bwd_h(const gcmi_graph* g, const unsigned short* d_dout, int6
                          unsigned short* d_dx, int64_t lddx, const float* only_if_gamma, const float* only_if_beta,
                          hipStream_t st);
 bool win_two_stage_usable_h(const gcmi_graph* g, int n_feat);
+// ... at every bf16 width with a kernel (64 / 80 / 128), for the operation-level entry points
+bool win_usable_bwd_h(const gcmi_graph* g, int n_feat);
+bool win_two_stage_usable_bwd_h(const gcmi_graph* g, int n_feat);
 int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const unsigned short* d_ds, int64_t ldds, int n_feat,
                                 unsigned short* d_dxs, int64_t lddxs, const uint8_t* d_arg, unsigned short* d_dy,
                                 int64_t lddy, hipStream_t st);

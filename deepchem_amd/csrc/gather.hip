@@ -533,4 +533,124 @@ int gcmi_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, 
   return GCMI_OK;
 }
 
+// ---------------------------------------------------------------- the window kernels, one operation per entry point
+// gather_lds.hip's operations as the model step launches them, each callable alone.  No other kernel stands behind
+// these: where the batch has no window plan, the width no window kernel or the LDS no room, they set an error text,
+// return GCMI_ERR_UNSUPPORTED and launch nothing.  Rows are 16-byte pieces to the LDS-DMA, so every row pointer must be
+// 16-byte aligned and every leading dimension a whole number of pieces.
+static bool rows16(const void* p, int64_t ld, int per_piece) { return aligned16(p) && ld % per_piece == 0; }
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+static int win_refused(const char* what, int n_feat) {
+  set_error("%s: no window pass for this batch at %d features (window plan, width or LDS)", what, n_feat);
+  return GCMI_ERR_UNSUPPORTED;
+}
+
+int gcmi_win_sum_h(const gcmi_graph* g, const uint16_t* d_x, int64_t ldx, int32_t n_feat, uint16_t* d_s, int64_t lds,
+                   int32_t accumulate, void* stream) {
+  int rc = check_graph(g, true);
+  if (rc) return rc;
+  GCMI_CHECK_ARG(n_feat > 0 && ldx >= n_feat && lds >= n_feat, "win_sum_h: bad n_feat/ld");
+  GCMI_CHECK_ARG(g->n_atoms == 0 || (d_x && d_s), "win_sum_h: NULL buffer");
+  if (g->n_atoms == 0) return GCMI_OK;
+  GCMI_CHECK_ARG(rows16(d_x, ldx, 8) && rows16(d_s, lds, 8), "win_sum_h: rows must be 16-byte aligned, ld %% 8 == 0");
+  if (!win_usable_h(g, n_feat)) return win_refused("win_sum_h", n_feat);
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_GATHER_SUM, st);
+  return win_gather_sum_h(g, d_x, ldx, n_feat, d_s, lds, st, accumulate != 0);
+}
+
+int gcmi_win_sum_fh(const gcmi_graph* g, const float* d_x, int64_t ldx, int32_t n_feat, uint16_t* d_s,
+                    uint16_t* d_xcopy, int64_t ldo, void* stream) {
+  int rc = check_graph(g, true);
+  if (rc) return rc;
+  GCMI_CHECK_ARG(n_feat > 0 && ldx >= n_feat && ldo >= n_feat, "win_sum_fh: bad n_feat/ld");
+  GCMI_CHECK_ARG(g->n_atoms == 0 || (d_x && d_s && d_xcopy), "win_sum_fh: NULL buffer");
+  if (g->n_atoms == 0) return GCMI_OK;
+  GCMI_CHECK_ARG(rows16(d_x, ldx, 4), "win_sum_fh: input rows must be 16-byte aligned, ld %% 4 == 0");
+  if (!win_has_width(n_feat) || !win_usable(g, n_feat, false)) return win_refused("win_sum_fh", n_feat);
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_GATHER_SUM, st);
+  return win_gather_sum_fh(g, d_x, ldx, n_feat, d_s, d_xcopy, ldo, st);  // (refuses a bad ldo / output alignment itself)
+}
+
+int gcmi_win_max_h(const gcmi_graph* g, const uint16_t* d_x, int64_t ldx, int32_t n_feat, const float* d_scale,
+                   const float* d_shift, uint16_t* d_out, int64_t ldo, uint8_t* d_arg, void* stream) {
+  int rc = check_graph(g, true);
+  if (rc) return rc;
+  GCMI_CHECK_ARG(n_feat > 0 && ldx >= n_feat && ldo >= n_feat, "win_max_h: bad n_feat/ld");
+  GCMI_CHECK_ARG(g->n_atoms == 0 || (d_x && d_out), "win_max_h: NULL buffer");
+  GCMI_CHECK_ARG((d_scale == nullptr) == (d_shift == nullptr), "win_max_h: scale/shift must come together");
+  if (g->n_atoms == 0) return GCMI_OK;
+  GCMI_CHECK_ARG(rows16(d_x, ldx, 8) && rows16(d_out, ldo, 8), "win_max_h: rows must be 16-byte aligned, ld %% 8 == 0");
+  GCMI_CHECK_ARG(d_arg == nullptr || aligned4(d_arg), "win_max_h: arg rows must be 4-byte aligned");
+  GCMI_CHECK_ARG(d_scale == nullptr || (aligned16(d_scale) && aligned16(d_shift)),
+                 "win_max_h: scale/shift must be 16-byte aligned");
+  if (!win_usable_h(g, n_feat)) return win_refused("win_max_h", n_feat);
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_GATHER_MAX, st);
+  return win_gather_max_h(g, d_x, ldx, n_feat, d_scale, d_shift, d_out, ldo, d_arg, st);
+}
+
+// the checks the three GraphPool backward forms share; piece: elements per 16 bytes of a row
+static int win_bwd_checks(const gcmi_graph* g, const char* what, int32_t n_feat, const void* d_in, int64_t ldi,
+                          const uint8_t* d_arg, const void* d_out, int64_t ldo, int piece) {
+  int rc = check_graph(g, true);
+  if (rc) return rc;
+  GCMI_CHECK_ARG(n_feat > 0 && ldi >= n_feat && ldo >= n_feat, "%s: bad n_feat/ld", what);
+  GCMI_CHECK_ARG(g->n_atoms == 0 || (d_in && d_arg && d_out), "%s: NULL buffer", what);
+  if (g->n_atoms == 0) return GCMI_OK;
+  GCMI_CHECK_ARG(rows16(d_in, ldi, piece) && rows16(d_out, ldo, piece),
+                 "%s: rows must be 16-byte aligned, ld %% %d == 0", what, piece);
+  GCMI_CHECK_ARG(aligned4(d_arg) && n_feat % 4 == 0, "%s: arg rows (n_feat bytes) must be 4-byte aligned", what);
+  GCMI_CHECK_ARG(g->d_rev_pos != nullptr || g->n_edges == 0, "%s: the graph has no reverse slots", what);
+  return GCMI_OK;
+}
+
+int gcmi_win_max_bwd_h(const gcmi_graph* g, const uint16_t* d_dout, int64_t lddo, int32_t n_feat, const uint8_t* d_arg,
+                       uint16_t* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, void* stream) {
+  int rc = win_bwd_checks(g, "win_max_bwd_h", n_feat, d_dout, lddo, d_arg, d_dx, lddx, 8);
+  if (rc || g->n_atoms == 0) return rc;
+  GCMI_CHECK_ARG((d_gamma == nullptr) == (d_beta == nullptr), "win_max_bwd_h: gamma/beta must come together");
+  if (!win_usable_bwd_h(g, n_feat)) return win_refused("win_max_bwd_h", n_feat);
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
+  return win_gather_max_bwd_h(g, d_dout, lddo, n_feat, d_arg, d_dx, lddx, d_gamma, d_beta, st);
+}
+
+int gcmi_win_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int32_t n_feat,
+                            const uint8_t* d_arg, float* d_dx, int64_t lddx, const float* d_gamma,
+                            const float* d_beta, void* stream) {
+  int rc = win_bwd_checks(g, "win_max_bwd_if_ill", n_feat, d_dout, lddo, d_arg, d_dx, lddx, 4);
+  if (rc || g->n_atoms == 0) return rc;
+  GCMI_CHECK_ARG(d_gamma && d_beta, "win_max_bwd_if_ill: gamma/beta are NULL");
+  if (!win_has_width(n_feat) || !win_usable(g, n_feat, true)) return win_refused("win_max_bwd_if_ill", n_feat);
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
+  return win_gather_max_bwd_if_ill(g, d_dout, lddo, n_feat, d_arg, d_dx, lddx, d_gamma, d_beta, st);
+}
+
+int gcmi_win_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int32_t n_feat, float* d_dxs,
+                            int64_t lddxs, const uint8_t* d_arg, float* d_dy, int64_t lddy, void* stream) {
+  int rc = win_bwd_checks(g, "win_sumacc_max_bwd", n_feat, d_ds, ldds, d_arg, d_dy, lddy, 4);
+  if (rc || g->n_atoms == 0) return rc;
+  GCMI_CHECK_ARG(d_dxs && lddxs >= n_feat && rows16(d_dxs, lddxs, 4),
+                 "win_sumacc_max_bwd: dxs rows must be 16-byte aligned, ld %% 4 == 0, ld >= n_feat");
+  if (!win_two_stage_usable(g, n_feat)) return win_refused("win_sumacc_max_bwd", n_feat);
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
+  return win_gather_sumacc_max_bwd(g, d_ds, ldds, n_feat, d_dxs, lddxs, d_arg, d_dy, lddy, st);
+}
+
+int gcmi_win_sumacc_max_bwd_h(const gcmi_graph* g, const uint16_t* d_ds, int64_t ldds, int32_t n_feat, uint16_t* d_dxs,
+                              int64_t lddxs, const uint8_t* d_arg, uint16_t* d_dy, int64_t lddy, void* stream) {
+  int rc = win_bwd_checks(g, "win_sumacc_max_bwd_h", n_feat, d_ds, ldds, d_arg, d_dy, lddy, 8);
+  if (rc || g->n_atoms == 0) return rc;
+  GCMI_CHECK_ARG(d_dxs && lddxs >= n_feat && rows16(d_dxs, lddxs, 8),
+                 "win_sumacc_max_bwd_h: dxs rows must be 16-byte aligned, ld %% 8 == 0, ld >= n_feat");
+  if (!win_two_stage_usable_bwd_h(g, n_feat)) return win_refused("win_sumacc_max_bwd_h", n_feat);
+  hipStream_t st = (hipStream_t)stream;
+  TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
+  return win_gather_sumacc_max_bwd_h(g, d_ds, ldds, n_feat, d_dxs, lddxs, d_arg, d_dy, lddy, st);
+}
+
 }  // extern "C"

@@ -979,7 +979,11 @@ int win_gather_sum_fh(const gcmi_graph* g, const float* d_x, int64_t ldx, int n_
 }
 
 int win_gather_sum_h(const gcmi_graph* g, const bf16_t* d_x, int64_t ldx, int n_feat, bf16_t* d_s, int64_t lds,
-                     hipStream_t st) {
+                     hipStream_t st, bool accumulate) {
+  if (accumulate) {  // SumAccOpH over all windows (the two-stage backward runs it over the oversized ones only)
+    SumAccOpH op{{d_s, lds}};
+    return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_sum (bf16, accumulate)");
+  }
   SumOpH op{{d_s, lds}};
   return launch<false>(g, n_feat, d_x, ldx, nullptr, op, st, "win_gather_sum (bf16)");
 }
@@ -1005,6 +1009,16 @@ int win_gather_max_bwd_h(const gcmi_graph* g, const bf16_t* d_dout, int64_t lddo
 
 bool win_two_stage_usable_h(const gcmi_graph* g, int n_feat) {
   return win_usable_gh(g, n_feat) && third_tiles_fit(g, n_feat / 2, 8, Third::dma_pair);
+}
+
+// The same two questions for every width launch<> has a bf16 kernel with arg bytes for (the model step keeps its bf16
+// gradient streams at 64 columns: win_usable_gh): the operation-level entry points of gather.hip
+bool win_usable_bwd_h(const gcmi_graph* g, int n_feat) {
+  if (n_feat != 64 && n_feat != 80 && n_feat != 128) return false;
+  return plan_fits(g, n_feat / 2, 8);
+}
+bool win_two_stage_usable_bwd_h(const gcmi_graph* g, int n_feat) {
+  return win_usable_bwd_h(g, n_feat) && third_tiles_fit(g, n_feat / 2, 8, Third::dma_pair);
 }
 
 int win_gather_sumacc_max_bwd_h(const gcmi_graph* g, const bf16_t* d_ds, int64_t ldds, int n_feat, bf16_t* d_dxs,

@@ -81,28 +81,48 @@ def scatter_add(g: BatchGraph, ds: torch.Tensor, dx: torch.Tensor) -> torch.Tens
     return dx
 
 
-def gather_max(g: BatchGraph, x: torch.Tensor, scale=None, shift=None, want_arg: bool = True):
+def _arg_rows(arg, n_atoms: int, n_feat: int):
+    if arg.dtype != torch.uint8 or tuple(arg.shape) != (n_atoms, n_feat) or not arg.is_contiguous() or not arg.is_cuda:
+        raise ValueError("bad arg tensor")
+    return arg
+
+
+def _out_rows(out, like: torch.Tensor, n_atoms: int, n_feat: int, name: str = "out"):
+    """The caller's output rows (checked), or fresh ones of ``like``'s type."""
+    if out is None:
+        return torch.empty((n_atoms, n_feat), dtype=like.dtype, device=like.device)
+    return _mat(out, name, rows=n_atoms, cols=n_feat, dtype=like.dtype)
+
+
+def gather_max(g: BatchGraph, x: torch.Tensor, scale=None, shift=None, want_arg: bool = True, out=None, arg=None):
     _mat(x, "x", rows=g.n_atoms)
     F_ = x.shape[1]
     _vec(scale, "scale", F_)
     _vec(shift, "shift", F_)
-    out = torch.empty((g.n_atoms, F_), dtype=torch.float32, device=x.device)
-    arg = torch.empty((g.n_atoms, F_), dtype=torch.uint8, device=x.device) if want_arg else None
+    out = _out_rows(out, x, g.n_atoms, F_)
+    if arg is not None:
+        _arg_rows(arg, g.n_atoms, F_)
+    elif want_arg:
+        arg = torch.empty((g.n_atoms, F_), dtype=torch.uint8, device=x.device)
     _lib.call("gcmi_gather_max_fwd", g.ref, _ptr(x), _ld(x), F_, _ptr(scale), _ptr(shift), _ptr(out),
               _ld(out), _ptr(arg), _stream())
     return out, arg
 
 
-def gather_max_sum(g: BatchGraph, y: torch.Tensor, scale=None, shift=None, want_arg: bool = True):
+def gather_max_sum(g: BatchGraph, y: torch.Tensor, scale=None, shift=None, want_arg: bool = True, pool=None, arg=None,
+                   s=None):
     """``gather_max`` of ``y`` and ``gather_sum`` of its result, bit for bit, in one window pass where the batch allows.
     Returns (pooled rows, arg bytes or None, neighbour sums of the pooled rows)."""
     _mat(y, "y", rows=g.n_atoms)
     F_ = y.shape[1]
     _vec(scale, "scale", F_)
     _vec(shift, "shift", F_)
-    pool = torch.empty((g.n_atoms, F_), dtype=torch.float32, device=y.device)
-    arg = torch.empty((g.n_atoms, F_), dtype=torch.uint8, device=y.device) if want_arg else None
-    s = torch.empty((g.n_atoms, F_), dtype=torch.float32, device=y.device)
+    pool = _out_rows(pool, y, g.n_atoms, F_, "pool")
+    if arg is not None:
+        _arg_rows(arg, g.n_atoms, F_)
+    elif want_arg:
+        arg = torch.empty((g.n_atoms, F_), dtype=torch.uint8, device=y.device)
+    s = _out_rows(s, y, g.n_atoms, F_, "s")
     _lib.call("gcmi_gather_max_sum_fwd", g.ref, _ptr(y), _ld(y), F_, _ptr(scale), _ptr(shift), _ptr(pool),
               _ld(pool), _ptr(arg), _ptr(s), _ld(s), _stream())
     return pool, arg, s
@@ -115,18 +135,123 @@ def max_sum_launches() -> int:
     return v.value
 
 
-def gather_max_bwd(g: BatchGraph, dout: torch.Tensor, arg: torch.Tensor) -> torch.Tensor:
+def gather_max_bwd(g: BatchGraph, dout: torch.Tensor, arg: torch.Tensor, out=None) -> torch.Tensor:
+    """``out``: the caller's dx rows -- only with reverse slots, where every row is written once (the atomic form
+    adds into rows this function zeroes)."""
     _mat(dout, "dout", rows=g.n_atoms)
     F_ = dout.shape[1]
     if arg.dtype != torch.uint8 or tuple(arg.shape) != (g.n_atoms, F_) or not arg.is_contiguous():
         raise ValueError("bad arg tensor")
     if g.ensure_rev_pos():  # gather form: every row written once, no atomics
-        dx = torch.empty((g.n_atoms, F_), dtype=torch.float32, device=dout.device)
+        dx = _out_rows(out, dout, g.n_atoms, F_, "out")
     else:
+        if out is not None:
+            raise ValueError("out needs a graph with reverse slots")
         dx = torch.zeros((g.n_atoms, F_), dtype=torch.float32, device=dout.device)
     _lib.call("gcmi_gather_max_bwd", g.ref, _ptr(dout), _ld(dout), F_, _ptr(arg), _ptr(dx), _ld(dx),
               _stream())
     return dx
+
+
+# ------------------------------------------------------------------ the window passes, one operation each
+# (include/gcmi.h, "the molecule-window passes"): bf16 rows are torch.bfloat16 tensors.  No other kernel stands behind
+# these: a batch, width or LDS size without window pass raises GcmiError (status GCMI_ERR_UNSUPPORTED).
+_BF16 = torch.bfloat16
+
+
+def win_sum_h(g: BatchGraph, x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """Neighbour sums of bf16 rows, bf16 out (``accumulate``: added to ``out``)."""
+    _mat(x, "x", rows=g.n_atoms, dtype=_BF16)
+    F_ = x.shape[1]
+    if out is None and accumulate:
+        raise ValueError("accumulate needs an output")
+    out = _out_rows(out, x, g.n_atoms, F_)
+    _lib.call("gcmi_win_sum_h", g.ref, _ptr(x), _ld(x), F_, _ptr(out), _ld(out), 1 if accumulate else 0, _stream())
+    return out
+
+
+def win_sum_fh(g: BatchGraph, x: torch.Tensor, ldo: int, s=None, xcopy=None):
+    """float rows -> (bf16 neighbour sums, bf16 copy of the rows), both ``ldo`` columns wide, zero beyond x's."""
+    _mat(x, "x", rows=g.n_atoms)
+    F_ = x.shape[1]
+    outs = []
+    for t, name in ((s, "s"), (xcopy, "xcopy")):
+        if t is None:
+            t = torch.empty((g.n_atoms, ldo), dtype=_BF16, device=x.device)
+        _mat(t, name, rows=g.n_atoms, cols=ldo, dtype=_BF16)
+        if _ld(t) != ldo:  # (one number is the row pitch and the end of the zeroed columns)
+            raise ValueError("%s: row stride %d, expected %d" % (name, _ld(t), ldo))
+        outs.append(t)
+    _lib.call("gcmi_win_sum_fh", g.ref, _ptr(x), _ld(x), F_, _ptr(outs[0]), _ptr(outs[1]), int(ldo), _stream())
+    return outs[0], outs[1]
+
+
+def win_max_h(g: BatchGraph, x: torch.Tensor, scale=None, shift=None, want_arg: bool = True, out=None, arg=None):
+    """``gather_max`` over bf16 rows: (bf16 pooled rows, arg bytes or None)."""
+    _mat(x, "x", rows=g.n_atoms, dtype=_BF16)
+    F_ = x.shape[1]
+    _vec(scale, "scale", F_)
+    _vec(shift, "shift", F_)
+    out = _out_rows(out, x, g.n_atoms, F_)
+    if arg is not None:
+        _arg_rows(arg, g.n_atoms, F_)
+    elif want_arg:
+        arg = torch.empty((g.n_atoms, F_), dtype=torch.uint8, device=x.device)
+    _lib.call("gcmi_win_max_h", g.ref, _ptr(x), _ld(x), F_, _ptr(scale), _ptr(shift), _ptr(out), _ld(out), _ptr(arg),
+              _stream())
+    return out, arg
+
+
+def _need_rev_pos(g: BatchGraph):
+    if not g.ensure_rev_pos():
+        raise _lib.GcmiError("the window backward passes need reverse slots (a symmetric adjacency)")
+
+
+def win_max_bwd_h(g: BatchGraph, dout: torch.Tensor, arg: torch.Tensor, gamma=None, beta=None, out=None):
+    """GraphPool backward over bf16 rows.  With ``gamma``/``beta`` the rows are written only where some column has
+    |beta| > 64 |gamma| (pass ``out`` to see which)."""
+    _mat(dout, "dout", rows=g.n_atoms, dtype=_BF16)
+    F_ = dout.shape[1]
+    _arg_rows(arg, g.n_atoms, F_)
+    _vec(gamma, "gamma", F_)
+    _vec(beta, "beta", F_)
+    _need_rev_pos(g)
+    out = _out_rows(out, dout, g.n_atoms, F_)
+    _lib.call("gcmi_win_max_bwd_h", g.ref, _ptr(dout), _ld(dout), F_, _ptr(arg), _ptr(out), _ld(out), _ptr(gamma),
+              _ptr(beta), _stream())
+    return out
+
+
+def win_max_bwd_if_ill(g: BatchGraph, dout: torch.Tensor, arg: torch.Tensor, gamma, beta, out=None):
+    """GraphPool backward over float rows, written only where some column has |beta| > 64 |gamma|."""
+    _mat(dout, "dout", rows=g.n_atoms)
+    F_ = dout.shape[1]
+    _arg_rows(arg, g.n_atoms, F_)
+    if gamma is None or beta is None:
+        raise ValueError("gamma and beta are needed")
+    _vec(gamma, "gamma", F_)
+    _vec(beta, "beta", F_)
+    _need_rev_pos(g)
+    out = _out_rows(out, dout, g.n_atoms, F_)
+    _lib.call("gcmi_win_max_bwd_if_ill", g.ref, _ptr(dout), _ld(dout), F_, _ptr(arg), _ptr(out), _ld(out), _ptr(gamma),
+              _ptr(beta), _stream())
+    return out
+
+
+def win_sumacc_max_bwd(g: BatchGraph, ds: torch.Tensor, dxs: torch.Tensor, arg: torch.Tensor, out=None):
+    """The backward between two GraphConv blocks over float or bf16 rows: dy = GraphPool backward (by ``arg``) of
+    dX = dxs + neighbour sums of ds.  ``dxs`` is completed in place on the rows of oversized windows only."""
+    if ds.dtype not in (torch.float32, _BF16):
+        raise TypeError("ds must be float32 or bfloat16, got %s" % ds.dtype)
+    _mat(ds, "ds", rows=g.n_atoms, dtype=ds.dtype)
+    F_ = ds.shape[1]
+    _mat(dxs, "dxs", rows=g.n_atoms, cols=F_, dtype=ds.dtype)
+    _arg_rows(arg, g.n_atoms, F_)
+    _need_rev_pos(g)
+    out = _out_rows(out, ds, g.n_atoms, F_)
+    name = "gcmi_win_sumacc_max_bwd" if ds.dtype == torch.float32 else "gcmi_win_sumacc_max_bwd_h"
+    _lib.call(name, g.ref, _ptr(ds), _ld(ds), F_, _ptr(dxs), _ld(dxs), _ptr(arg), _ptr(out), _ld(out), _stream())
+    return out
 
 
 def readout(g: BatchGraph, x: torch.Tensor, n_mols: int, scale=None, shift=None, tanh: bool = False):

@@ -269,6 +269,44 @@ int gcmi_gather_max_sum_fwd(const gcmi_graph* g, const float* d_y, int64_t ldy, 
                             const float* d_scale, const float* d_shift, float* d_pool, int64_t ldp,
                             uint8_t* d_arg, float* d_s, int64_t lds, void* stream);
 
+/* ---------------------------------------------------------------- the molecule-window passes, one operation each
+ * The operations the whole-model entry points run over the molecule windows of a batch (gcmi_collate_plans), callable
+ * alone: for tests and for a caller that keeps bf16 activations itself.  bf16 rows are raw 16-bit patterns (uint16_t),
+ * leading dimensions count elements.  Every row pointer must be 16-byte aligned with a leading dimension of whole
+ * 16-byte pieces (ld % 4 == 0 for float rows, ld % 8 == 0 for bf16 rows), arg rows are n_feat bytes at a 4-byte
+ * aligned pointer, and the backward forms need g->d_rev_pos (or n_edges == 0): else GCMI_ERR_ARG.  NO other kernel
+ * stands behind these: a batch without window plan, a width without window kernel (float rows: 64, 76, 128; bf16
+ * rows: 64, 80, 128) or windows too large for the LDS give GCMI_ERR_UNSUPPORTED with an error text and no launch.
+ * Sums and comparisons are formed in fp32 in neighbour order; a bf16 result is rounded once (to nearest even) where it
+ * is stored.
+ *   gcmi_win_sum_h            s = (accumulate: s +) sum of the neighbours' rows; bf16 in, bf16 out
+ *   gcmi_win_sum_fh           float rows in; d_s = their neighbour sums and d_xcopy = the rows themselves, both bf16
+ *                             with ldo columns per row (ldo % 8 == 0, (ldo - n_feat) % 4 == 0), columns >= n_feat zero
+ *   gcmi_win_max_h            gcmi_gather_max_fwd over bf16 rows (scale/shift float, optional; d_arg optional)
+ *   gcmi_win_max_bwd_h        the gather form of gcmi_gather_max_bwd over bf16 rows.  With d_gamma/d_beta (both or
+ *                             neither) nothing is written unless some column has |beta| > 64 |gamma|
+ *   gcmi_win_max_bwd_if_ill   the same over float rows, d_gamma/d_beta required
+ *   gcmi_win_sumacc_max_bwd   the backward between two GraphConv blocks: with dX = d_dxs + neighbour sums of d_ds,
+ *     (_h: bf16 rows)         d_dy = GraphPool backward of dX by d_arg.  dX of an ordinary window exists in LDS only
+ *                             (bf16: rounded once there): d_dxs is left as it was on the rows of ordinary windows and
+ *                             holds the complete dX on the rows of oversized windows, which take the two separate
+ *                             passes.                                                                              */
+int gcmi_win_sum_h(const gcmi_graph* g, const uint16_t* d_x, int64_t ldx, int32_t n_feat, uint16_t* d_s, int64_t lds,
+                   int32_t accumulate, void* stream);
+int gcmi_win_sum_fh(const gcmi_graph* g, const float* d_x, int64_t ldx, int32_t n_feat, uint16_t* d_s,
+                    uint16_t* d_xcopy, int64_t ldo, void* stream);
+int gcmi_win_max_h(const gcmi_graph* g, const uint16_t* d_x, int64_t ldx, int32_t n_feat, const float* d_scale,
+                   const float* d_shift, uint16_t* d_out, int64_t ldo, uint8_t* d_arg, void* stream);
+int gcmi_win_max_bwd_h(const gcmi_graph* g, const uint16_t* d_dout, int64_t lddo, int32_t n_feat, const uint8_t* d_arg,
+                       uint16_t* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, void* stream);
+int gcmi_win_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int32_t n_feat,
+                            const uint8_t* d_arg, float* d_dx, int64_t lddx, const float* d_gamma,
+                            const float* d_beta, void* stream);
+int gcmi_win_sumacc_max_bwd(const gcmi_graph* g, const float* d_ds, int64_t ldds, int32_t n_feat, float* d_dxs,
+                            int64_t lddxs, const uint8_t* d_arg, float* d_dy, int64_t lddy, void* stream);
+int gcmi_win_sumacc_max_bwd_h(const gcmi_graph* g, const uint16_t* d_ds, int64_t ldds, int32_t n_feat, uint16_t* d_dxs,
+                              int64_t lddxs, const uint8_t* d_arg, uint16_t* d_dy, int64_t lddy, void* stream);
+
 /* ---------------------------------------------------------------- K4 readout
  * GraphGather.forward (layers.py:6450-6479) = unsorted_segment_sum
  * (utils/pytorch_utils.py:20-74) ++ unsorted_segment_max (:473-528) (+tanh):

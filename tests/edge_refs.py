@@ -3,6 +3,10 @@ the formulas of the layers they replace and used by tests/test_gpu_bn_edges.py, 
 tests/test_gpu_loss_edges.py.  Plain numpy on the CPU: no kernel of this project and no float32 library routine.
 tests/test_edge_refs_host.py checks them without a device (against torch in float64 and the oracle) together with
 the exactness conditions the GPU tests lean on.
+
+The last section restates the operations of the molecule-window kernels (csrc/gather_lds.hip) for
+tests/test_gpu_win_ops.py -- in the kernels' own arithmetic (float32 adds in neighbour-table order), so that those
+comparisons are bit for bit; tests/test_win_refs_host.py checks them against the oracle and autograd.
 """
 import numpy as np
 
@@ -227,3 +231,193 @@ def readout_case_id(n_feat, n_deg, n_mols, layout="c", vec4=True):
     return "f%d-%s-ndeg%d-mols%d-V%d-gl%d-mpb%d-idle%d-colpasses%d-%s-lastwg%d" % (
         n_feat, layout, n_deg, n_mols, b["V"], b["gl"], b["mpb"], b["idle"], b["col_passes"],
         "pipelined" if b["pipelined"] else "plain", n_mols - (-(-n_mols // b["mpb"]) - 1) * b["mpb"])
+
+
+# ------------------------------------------------------------------------------------------------ window gather ops
+# GraphConv.sum_neigh, GraphPool and its backward over the degree blocks of a collated batch, vectorised per degree
+# block.  Every function works in the dtype of its input: float32 rows give the kernels' arithmetic (one float32 add
+# per neighbour, in neighbour-table order, starting from 0), float64 rows the value the oracle and autograd give.
+class HostGraph:
+    """deg_counts[d] atoms of degree d, rows sorted by degree; col_idx: the neighbour tables of the degrees 1, 2, ...
+    back to back, (n_d, d) global rows each.  ``rev[d][r, j]``: the position of row r of block d in the neighbour
+    list of its j-th neighbour, the n-th bond between two atoms paired with the n-th one seen from the other end --
+    found here from the tables alone."""
+
+    def __init__(self, deg_counts, col_idx):
+        self.deg_counts = [int(c) for c in deg_counts]
+        col_idx = np.asarray(col_idx, np.int64)
+        self.n_atoms = sum(self.deg_counts)
+        self.row0, self.nb = [], []
+        r = e = 0
+        for d, c in enumerate(self.deg_counts):
+            self.row0.append(r)
+            self.nb.append(col_idx[e:e + c * d].reshape(c, d))
+            r += c
+            e += c * d
+        assert e == col_idx.shape[0]
+        self.max_present = max([d for d, c in enumerate(self.deg_counts) if c] + [0])
+        width = max(self.max_present, 1)
+        table = np.full((self.n_atoms, width), -1, np.int64)
+        for d, c in enumerate(self.deg_counts):
+            if c:
+                table[self.row0[d]:self.row0[d] + c, :d] = self.nb[d]
+        self.rev = []
+        for d, c in enumerate(self.deg_counts):
+            rev = np.zeros((c, d), np.int64)
+            k = self.rows(d)
+            for j in range(d):
+                i = self.nb[d][:, j]
+                nth = (self.nb[d][:, :j] == i[:, None]).sum(1)
+                hit = table[i] == k[:, None]
+                want = hit & (np.cumsum(hit, 1) == (nth + 1)[:, None])
+                assert want.any(1).all(), "a bond is not listed from both ends"
+                rev[:, j] = want.argmax(1)
+            self.rev.append(rev)
+
+    def rows(self, d):
+        return np.arange(self.row0[d], self.row0[d] + self.deg_counts[d])
+
+    def degree_blocks(self):
+        return [(d, self.rows(d), self.nb[d], self.rev[d]) for d, c in enumerate(self.deg_counts) if c]
+
+
+def bf16_round(x):
+    """float32 values rounded to the nearest bf16 (ties to even, as torch's .to(torch.bfloat16)), kept as float32."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    r = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    return r.view(np.float32)
+
+
+def neigh_sum(hg, x, old=None):
+    """s[i] = sum_j x[nb(i, j)], accumulated from 0 in neighbour order; ``old`` (accumulate) is added LAST."""
+    out = np.zeros_like(x)
+    for d, rows, nb, _ in hg.degree_blocks():
+        acc = np.zeros((rows.shape[0], x.shape[1]), x.dtype)
+        for j in range(d):
+            acc = acc + x[nb[:, j]]
+        out[rows] = acc
+    if old is not None:
+        out = out + old
+    assert out.dtype == x.dtype
+    return out
+
+
+def pool_max(hg, y):
+    """(values, arg bytes): the maximum over the atom's own row and its neighbours' -- self first, then the neighbours
+    in order, a later candidate wins only if strictly greater; arg 0 = self, j + 1 = neighbour j."""
+    best = y.copy()
+    arg = np.zeros(y.shape, np.uint8)
+    for d, rows, nb, _ in hg.degree_blocks():
+        b, a = y[rows], np.zeros((rows.shape[0], y.shape[1]), np.uint8)
+        for j in range(d):
+            v = y[nb[:, j]]
+            m = v > b
+            b = np.where(m, v, b)
+            a = np.where(m, np.uint8(j + 1), a)
+        best[rows], arg[rows] = b, a
+    return best, arg
+
+
+def pool_bwd(hg, g, arg):
+    """dx[k] = g[k] where arg[k] == 0, then += g[i_j] per neighbour j in order where arg[i_j] names k (reverse
+    position + 1)."""
+    out = np.zeros_like(g)
+    zero = g.dtype.type(0)
+    for d, rows, nb, rev in hg.degree_blocks():
+        acc = np.where(arg[rows] == 0, g[rows], zero)
+        for j in range(d):
+            i = nb[:, j]
+            acc = acc + np.where(arg[i] == (rev[:, j] + 1)[:, None], g[i], zero)
+        out[rows] = acc
+    assert out.dtype == g.dtype
+    return out
+
+
+def two_stage_bwd(hg, ds, dxs, arg, bf16=False):
+    """(dX, dy): dX = neigh_sum(dS) + dXs, dy = pool_bwd(dX, arg); ``bf16``: dX and dy each rounded once."""
+    dx = neigh_sum(hg, ds, old=dxs)
+    if bf16:
+        dx = bf16_round(dx)
+    dy = pool_bwd(hg, dx, arg)
+    return dx, (bf16_round(dy) if bf16 else dy)
+
+
+def exact_rows(rng, n, width):
+    """Rows k / 4, k in [-3, 3]: ties everywhere; sums of <= 11 of them are < 2^8 quarter-units (exact in bf16)."""
+    return (rng.randint(-3, 4, size=(n, width)) / 4.0).astype(np.float32)
+
+
+def plant_winners(hg, x):
+    """Around the first atom of the highest degree D present, make candidate c % (D + 1) the only maximum of column
+    c (0: a tie of all, which the atom itself wins): every arg byte 0..D then occurs.  x is changed in place."""
+    d = hg.max_present
+    k, nb = hg.row0[d], hg.nb[d][0]
+    lo, hi = x.dtype.type(-0.75), x.dtype.type(0.75)
+    x[k] = lo
+    x[nb] = lo
+    for c in range(x.shape[1]):
+        if c % (d + 1):
+            x[nb[c % (d + 1) - 1], c] = hi
+    return x
+
+
+def exact_bn(rng, width):
+    """(scale, shift): scales from {+-0.5, +-1, +-1.5, +-2}, shifts m / 4 with |m| <= 8, both signs present.  With
+    ``exact_rows`` every x * scale + shift is a multiple of 1/8 of magnitude <= 3.5: six significant bits, exact in
+    float32 and in bf16 whether the product is rounded before the sum (numpy) or not (fmaf)."""
+    scale = (rng.choice([0.5, 1.0, 1.5, 2.0], size=width) * rng.choice([-1.0, 1.0], size=width)).astype(np.float32)
+    shift = (rng.randint(-8, 9, size=width) / 4.0).astype(np.float32)
+    scale[:2] = [-1.5, 0.5]
+    shift[:2] = [0.75, -2.0]
+    return scale, shift
+
+
+def ulp(v, bf16=False):
+    """The spacing of float32 (bf16) numbers at |v|: one unit in the last of 24 (8) significant bits."""
+    a = np.maximum(np.abs(np.asarray(v, np.float64)), 2.0 ** -126)
+    return 2.0 ** (np.floor(np.log2(a)) - (7 if bf16 else 23))
+
+
+def window_rows(meta_row):
+    """The global rows of one window descriptor (include/gcmi.h, d_win_meta): slot s of degree d is row base[d] + s."""
+    m = [int(v) for v in meta_row]
+    base, start = m[:11], [0] + m[11:22]
+    return np.concatenate([np.arange(start[d], start[d + 1]) + base[d] for d in range(11)] + [np.zeros(0, np.int64)])
+
+
+def candidate_value(hg, y, arg):
+    """y of the candidate each arg byte names (0: the atom's own row, j + 1: its neighbour j); a byte above the
+    atom's degree names nothing and fails."""
+    out = np.empty_like(y)
+    cols = np.arange(y.shape[1])[None, :]
+    for d, rows, nb, _ in hg.degree_blocks():
+        a = arg[rows].astype(np.int64)
+        assert a.max(initial=0) <= d, "arg byte above the degree"
+        src = np.concatenate([rows[:, None], nb], 1)  # (n_d, d + 1) candidate rows
+        out[rows] = y[np.take_along_axis(src, a, 1), cols]
+    return out
+
+
+# What make_plan / launch_lpr (csrc/gather_lds.hip) decide from a batch's window sizes, restated so that a test knows
+# which launches run over windows and which two-stage forms must refuse.  c: the gcmi_graph of the batch.
+WIN_LDS_BYTES = 160 * 1024
+WIN_HEAD_BYTES = 320 + 2048  # the ring of three window descriptors and 512 floats of per-op constants
+
+
+def win_plan_bytes(c, row_bytes, aux, third_tiles=0):
+    """Dynamic LDS of one workgroup: two window buffers [rows | arg bytes | neighbour entries] and ``third_tiles``
+    more row tiles.  aux: 0 none, 4 / 8 = arg bytes per 16-byte piece (float / bf16 rows).  The two buffers of the
+    ordinary windows together also hold one oversized window: they grow by 8 atoms until they do."""
+    def buf(alloc, ecap):
+        tile = alloc * row_bytes
+        a = 0 if not aux else (-(-(tile // 4) // 16) * 16 if aux == 4 else -(-(alloc * (row_bytes // 16)) // 64) * 512)
+        return tile + a + max(ecap, 8) * 2
+    alloc = max(c.win_alloc, 1)
+    if c.n_win_big > 0:
+        while 2 * buf(alloc, c.win_ecap) < buf(c.win_alloc_big, c.win_ecap_big):
+            alloc += 8
+    return 2 * buf(alloc, c.win_ecap) + WIN_HEAD_BYTES + third_tiles * alloc * row_bytes, alloc
+
+
+def win_fits(c, row_bytes, aux, third_tiles=0):
+    return c.n_win > 0 and win_plan_bytes(c, row_bytes, aux, third_tiles)[0] <= WIN_LDS_BYTES

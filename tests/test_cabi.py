@@ -46,6 +46,56 @@ def test_bad_arguments_return_an_error_not_a_crash():
     assert rc == -1
     with pytest.raises(_lib.GcmiError):
         _lib.call("gcmi_adam_step", None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 0, None)
+    _window_entries_reject_bad_arguments(lib)
+
+
+def _window_entries_reject_bad_arguments(lib):
+    """The operation-level entries of the window kernels (gcmi_win_*): every check runs before any launch, and a
+    batch without window plan is GCMI_ERR_UNSUPPORTED, not another kernel.  Pointers are never followed here."""
+    A, OFF = 1 << 20, (1 << 20) + 4  # a 16-byte aligned address and one 4 bytes off
+    F = 64
+
+    def graph(max_deg=10, rev=True):  # two atoms bonded to each other
+        g = _lib.GcmiGraph()
+        g.max_deg, g.n_atoms, g.n_edges = max_deg, 2, 2
+        for d in range(2, 12):
+            g.deg_start[d], g.edge_start[d] = 2, 2
+        g.d_col_idx = A
+        g.d_rev_pos = A if rev else None
+        return g
+
+    # name -> arguments after the graph, as a function of (rows pointer, ld); stream last
+    entries = {
+        "gcmi_win_sum_h": lambda p, ld: (p, ld, F, p, ld, 0, None),
+        "gcmi_win_sum_fh": lambda p, ld: (p, ld, F, A, A, 64, None),
+        "gcmi_win_max_h": lambda p, ld: (p, ld, F, None, None, p, ld, A, None),
+        "gcmi_win_max_bwd_h": lambda p, ld: (p, ld, F, A, p, ld, None, None, None),
+        "gcmi_win_max_bwd_if_ill": lambda p, ld: (p, ld, F, A, p, ld, A, A, None),
+        "gcmi_win_sumacc_max_bwd": lambda p, ld: (p, ld, F, p, ld, A, p, ld, None),
+        "gcmi_win_sumacc_max_bwd_h": lambda p, ld: (p, ld, F, p, ld, A, p, ld, None),
+    }
+    backward = [n for n in entries if "bwd" in n]
+    for name, args in entries.items():
+        fn = getattr(lib, name)
+        bf16 = name.endswith("_h")
+        assert fn(ctypes.byref(graph(max_deg=99)), *args(A, F)) == -1 and b"max_deg" in lib.gcmi_last_error(), name
+        assert fn(ctypes.byref(graph()), *args(None, F)) == -1 and b"NULL" in lib.gcmi_last_error(), name
+        assert fn(ctypes.byref(graph()), *args(A, F - 4)) == -1 and b"ld" in lib.gcmi_last_error(), name
+        assert fn(ctypes.byref(graph()), *args(OFF, F)) == -1 and b"aligned" in lib.gcmi_last_error(), name
+        if bf16:  # 68 bf16 elements: rows of 136 bytes, no whole number of 16-byte pieces
+            assert fn(ctypes.byref(graph()), *args(A, 68)) == -1 and b"ld % 8" in lib.gcmi_last_error(), name
+        if name in backward:
+            assert fn(ctypes.byref(graph(rev=False)), *args(A, F)) == -1 and b"reverse" in lib.gcmi_last_error(), name
+        # all in order, but the graph carries no window plan: refused, nothing launched
+        assert fn(ctypes.byref(graph()), *args(A, F)) == -3 and b"no window pass" in lib.gcmi_last_error(), name
+    g = ctypes.byref(graph())
+    assert lib.gcmi_win_max_h(g, A, F, F, A, None, A, F, A, None) == -1  # scale without shift
+    assert lib.gcmi_win_max_h(g, A, F, F, None, None, A, F, A + 2, None) == -1  # arg rows 2 bytes off
+    assert lib.gcmi_win_max_h(g, A, F, F, OFF, OFF, A, F, A, None) == -1  # scale / shift 4 bytes off
+    assert lib.gcmi_win_max_bwd_h(g, A, F, F, A, A, F, A, None, None) == -1  # gamma without beta
+    assert lib.gcmi_win_max_bwd_if_ill(g, A, F, F, A, A, F, None, None, None) == -1  # no gamma / beta
+    assert lib.gcmi_win_sumacc_max_bwd(g, A, F, F, None, F, A, A, F, None) == -1  # dxs NULL
+    assert lib.gcmi_win_sumacc_max_bwd_h(g, A, F, F, OFF, F, A, A, F, None) == -1  # dxs 4 bytes off
 
 
 def native_collate(packed, sel, out_ld=None, max_deg=10):
