@@ -343,11 +343,16 @@ def _i64arr(vals):
 
 def seg_gemm(seg_begin, seg_end, a1, w1, w1_off, a2, w2, w2_off, bias, bias_off, n_out: int,
              trans_w: bool, relu: bool, n_rows: int, k1: int = 0, k2: int = 0,
-             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
     """out[n_rows, n_out]; rows not covered by any segment are left undefined.
     w1 / w2 / bias are flat float32 CUDA tensors holding the blocks at the
     given offsets (in floats).  ``out``: write into this (n_rows, n_out) matrix (a column block of a
-    wider one is fine) instead of a fresh one."""
+    wider one is fine) instead of a fresh one.  ``accumulate``: out += result (act = 2 of gcmi_seg_gemm) instead
+    of out = result; needs ``out`` and excludes ``relu``."""
+    if accumulate and relu:
+        raise ValueError("accumulate and relu are mutually exclusive")
+    if accumulate and out is None:
+        raise ValueError("accumulate needs the matrix to add to: pass out")
     n_seg = len(seg_begin)
     dev = (a1 if a1 is not None else a2).device
     for s in range(n_seg):
@@ -378,7 +383,7 @@ def seg_gemm(seg_begin, seg_end, a1, w1, w1_off, a2, w2, w2_off, bias, bias_off,
               _ptr(a2), _ld(a2) if a2 is not None else 0, k2, _ptr(w2),
               _i64arr(w2_off) if a2 is not None else None,
               _ptr(bias), _i64arr(bias_off) if bias is not None else None, n_out,
-              1 if trans_w else 0, 1 if relu else 0, _ptr(out), _ld(out), _stream())
+              1 if trans_w else 0, 2 if accumulate else (1 if relu else 0), _ptr(out), _ld(out), _stream())
     return out
 
 

@@ -7,6 +7,10 @@ the exactness conditions the GPU tests lean on.
 The last section restates the operations of the molecule-window kernels (csrc/gather_lds.hip) for
 tests/test_gpu_win_ops.py -- in the kernels' own arithmetic (float32 adds in neighbour-table order), so that those
 comparisons are bit for bit; tests/test_win_refs_host.py checks them against the oracle and autograd.
+
+The section after it restates the segmented products (csrc/gemm.hip, csrc/gemm_split.hip) for
+tests/test_gpu_product_edges.py: the two contracts in float64, the float32 arithmetic each product mode claims, and the
+operands that tell a lost piece product; tests/test_product_refs_host.py checks them.
 """
 import numpy as np
 
@@ -421,3 +425,149 @@ def win_plan_bytes(c, row_bytes, aux, third_tiles=0):
 
 def win_fits(c, row_bytes, aux, third_tiles=0):
     return c.n_win > 0 and win_plan_bytes(c, row_bytes, aux, third_tiles)[0] <= WIN_LDS_BYTES
+
+
+# ------------------------------------------------------------------------------------------------ segmented products
+# The two product entry points of csrc/gemm.hip restated in float64 from that file's header comment, the two float32
+# arithmetics the product modes claim (exact: a k-ordered float32 chain; fast: the three-way bf16 split of
+# csrc/split_bf16.h with six piece products), and operands built so that one missing piece product changes the result.
+# tests/test_gpu_product_edges.py compares the kernels with these; tests/test_product_refs_host.py checks them here.
+U24 = 2.0 ** -24  # one float32 rounding of a value in [1, 2): the unit of every accuracy figure
+SIX_TERMS = ((0, 2), (2, 0), (1, 1), (1, 0), (0, 1), (0, 0))  # (piece of a, piece of w) the kernels multiply
+
+
+def seg_product_ref(begin, end, operands, bias, bias_off, n_out, trans, act, out0):
+    """gcmi_seg_gemm: out[rows_s] = act(a1[rows_s] . w1[s] + a2[rows_s] . w2[s] + bias[s]) in float64.
+    operands: up to two (a, w_flat, w_off, k) or None; a is (rows, >= k), the block of segment s starts at
+    w_flat[w_off[s]] and is k x n_out (trans: n_out x k, nn.Linear's layout); an offset of -1 means the term is absent.
+    bias: flat or None, bias_off[s] = -1: none.  act 0: none, 1: ReLU, 2: out0 + result.  Rows outside every segment
+    keep out0.  Returns (out, S): S is the same sum of absolute values (and |out0| under act 2), 0 on untouched rows."""
+    out, S = f64(out0).copy(), np.zeros(np.shape(out0), np.float64)
+    operands = [None if op is None or op[0] is None else (f64(op[0]), f64(op[1]), op[2], op[3]) for op in operands]
+    for s in range(len(begin)):
+        r = slice(begin[s], end[s])
+        acc = np.zeros((end[s] - begin[s], n_out), np.float64)
+        mag = np.zeros_like(acc)
+        for op in operands:
+            if op is None or op[2][s] < 0:
+                continue
+            a, w, off, k = op
+            blk = w[off[s]:off[s] + k * n_out]
+            ws = blk.reshape(n_out, k).T if trans else blk.reshape(k, n_out)
+            acc += a[r, :k] @ ws
+            mag += np.abs(a[r, :k]) @ np.abs(ws)
+        if bias is not None and bias_off[s] >= 0:
+            b = f64(bias)[bias_off[s]:bias_off[s] + n_out]
+            acc += b
+            mag += np.abs(b)
+        if act == 1:
+            acc = np.maximum(acc, 0.0)
+        elif act == 2:
+            acc += f64(out0)[r]
+            mag += np.abs(f64(out0)[r])
+        out[r], S[r] = acc, mag
+    return out, S
+
+
+def seg_wgrad_ref(begin, end, a, g, k, n, dw0, dw_off, dbias0, dbias_off, trans):
+    """gcmi_seg_gemm_wgrad: dw[s] += a[rows_s]^T . g[rows_s] (k x n; trans: n x k), dbias[s] += colsum g[rows_s], in
+    float64, onto the flat dw0 / dbias0 (dbias0 None: no bias gradient); an offset of -1: not written.  Segments may
+    share a block.  Returns (dw, dbias, S_dw, S_dbias): S the same sums of absolute values, starting values included."""
+    dw, S = f64(dw0).copy(), np.abs(f64(dw0))
+    db = None if dbias0 is None else f64(dbias0).copy()
+    Sb = None if dbias0 is None else np.abs(f64(dbias0))
+    for s in range(len(begin)):
+        ar, gr = f64(a[begin[s]:end[s], :k]), f64(g[begin[s]:end[s], :n])
+        if dw_off[s] >= 0:
+            p, m = ar.T @ gr, np.abs(ar).T @ np.abs(gr)
+            sl = slice(dw_off[s], dw_off[s] + k * n)
+            dw[sl] += (p.T if trans else p).reshape(-1)
+            S[sl] += (m.T if trans else m).reshape(-1)
+        if db is not None and dbias_off[s] >= 0:
+            sl = slice(dbias_off[s], dbias_off[s] + n)
+            db[sl] += gr.sum(0)
+            Sb[sl] += np.abs(gr).sum(0)
+    return dw, db, S, Sb
+
+
+def any_order_exact(S, lsb):
+    """The any-order exactness condition: when every term is a multiple of lsb (a power of two) and the sum of their
+    absolute values stays below 2^24 lsb, every partial sum in any order is a float32 number -- atomics included."""
+    return float(np.max(S, initial=0.0)) < 2.0 ** 24 * lsb
+
+
+def is_multiple(x, lsb):
+    q = f64(x)[np.isfinite(f64(x))] / lsb
+    return bool(np.all(q == np.round(q)))
+
+
+def seq32_product(a, w, acc=None):
+    """a . w in float32, accumulated sequentially in contraction order with two roundings per term (the product, then
+    the sum), as a loop of numpy float32 operations: deterministic on any host.  acc: continue this sum."""
+    a, w = np.asarray(a, np.float32), np.asarray(w, np.float32)
+    acc = np.zeros((a.shape[0], w.shape[1]), np.float32) if acc is None else np.asarray(acc, np.float32).copy()
+    for kk in range(a.shape[1]):
+        acc = (acc + (a[:, kk, None] * w[None, kk, :]).astype(np.float32)).astype(np.float32)
+    return acc
+
+
+def bf16_round(x):
+    """float32 -> the nearest bf16 value (ties to even), as a float32 (finite inputs)."""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16
+    return r.astype(np.uint32).view(np.float32).reshape(np.shape(x))
+
+
+def split3_np(x):
+    """split3_pair of csrc/split_bf16.h: three bf16 pieces by round to nearest even with exact residuals."""
+    x = np.asarray(x, np.float32)
+    p1 = bf16_round(x)
+    r1 = (x - p1).astype(np.float32)
+    p2 = bf16_round(r1)
+    r2 = (r1 - p2).astype(np.float32)
+    return p1, p2, bf16_round(r2)
+
+
+def split_product_np(a, w, terms=SIX_TERMS, acc=None):
+    """a . w assembled from the piece products ``terms`` (pairs (i, j): piece i of a times piece j of w), one float32
+    accumulation per term and 16-wide contraction step, in the order given -- the kernels' loop with each
+    32x32x16 product formed exactly and rounded once.  acc: continue this sum."""
+    A, W = split3_np(a), split3_np(w)
+    acc = np.zeros((np.shape(a)[0], np.shape(w)[1]), np.float32) if acc is None else np.asarray(acc, np.float32).copy()
+    for k0 in range(0, np.shape(a)[1], 16):
+        for i, j in terms:
+            blk = A[i][:, k0:k0 + 16].astype(np.float64) @ W[j][k0:k0 + 16].astype(np.float64)
+            acc = (acc + blk.astype(np.float32)).astype(np.float32)
+    return acc
+
+
+# Piece probes: entries +-(1 + p 2^-9 + q 2^-17) with random bits p, q split into the pieces (1, p 2^-9, q 2^-17) when
+# p = 1 (and (1, q 2^-17, 0) when p = 0), so every product of pieces is a multiple of 2^-17 (2^-18 for two-piece times
+# two-piece) and a sum over at most 96 (48) of them meets the any-order condition.  name: (pieces of a, pieces of w,
+# longest contraction, lsb, the terms the pair is built to see).  No term outside SIX_TERMS is ever non-zero.
+PROBES = {
+    "a3w1": (3, 1, 96, 2.0 ** -17, ((0, 0), (1, 0), (2, 0))),
+    "a1w3": (1, 3, 96, 2.0 ** -17, ((0, 0), (0, 1), (0, 2))),
+    "a2w2": (2, 2, 48, 2.0 ** -18, ((0, 0), (0, 1), (1, 0), (1, 1))),
+}
+
+
+def probe_values(rng, shape, pieces):
+    sign = rng.choice(np.array([-1.0, 1.0]), shape)
+    p = rng.integers(0, 2, shape) if pieces >= 2 else 0
+    q = rng.integers(0, 2, shape) if pieces >= 3 else 0
+    return (sign * (1.0 + p * 2.0 ** -9 + q * 2.0 ** -17)).astype(np.float32)
+
+
+def probe_operands(name, rows, k, n_out, seed, nnz=None):
+    """(a (rows, k), w (k, n_out)) of one probe.  nnz: only that many columns of every row of a are non-zero (the
+    head's 256-column rows keep the contraction at the probe's length that way)."""
+    pa, pw = PROBES[name][:2]
+    rng = np.random.default_rng(seed)
+    a, w = probe_values(rng, (rows, k), pa), probe_values(rng, (k, n_out), pw)
+    if nnz is not None and nnz < k:
+        keep = np.argsort(rng.random((rows, k)), axis=1)[:, :nnz]
+        mask = np.zeros((rows, k), bool)
+        np.put_along_axis(mask, keep, True, 1)
+        a = np.where(mask, a, np.float32(0.0))
+    return a, w
