@@ -149,51 +149,6 @@ static Ws carve(const gcmi_model_desc* m, int64_t N, int64_t B, int64_t ld_featu
   return w;
 }
 
-// b_rel_d + b_self_d of every GraphConv layer (the products add ONE bias row per degree): one launch for all layers
-static int pack_biases(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, hipStream_t st) {
-  BiasLayers bl;
-  memset(&bl, 0, sizeof(bl));
-  for (int l = 0; l < m->n_layers; ++l) {
-    bl.src[l] = d_params + m->off_conv_b[l];
-    bl.dst[l] = ws + w.bsum[l];
-    bl.width[l] = m->conv_width[l];
-  }
-  hipLaunchKernelGGL(bias_pack_kernel, dim3(4, m->n_layers), dim3(256), 0, st, bl, m->max_deg);
-  GCMI_CHECK_LAUNCH("bias_pack");
-  return GCMI_OK;
-}
-
-// ... and the per-degree bias gradients back into the reference's (2 max_deg + 1) rows, for the layers whose block ran
-static int unpack_bias_grads(const gcmi_model_desc* m, const BiasLayers& bl, int n_layers, hipStream_t st) {
-  bool any = false;
-  for (int l = 0; l < n_layers; ++l) any = any || bl.src[l] != nullptr;
-  if (!any) return GCMI_OK;
-  hipLaunchKernelGGL(bias_unpack_kernel, dim3(4, n_layers), dim3(256), 0, st, bl, m->max_deg);
-  GCMI_CHECK_LAUNCH("bias_unpack");
-  return GCMI_OK;
-}
-
-// The task head's forward product: with more than 32 outputs on the prepared images (head_bwd.hip; the backward makes
-// its own of the weights it is given); otherwise (and in the exact product mode) the segmented product.
-static int head_forward(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, const gcmi_model_io* io,
-                        int64_t B, void* stream) {
-  const int D = m->dense_width;
-  const int TC = m->n_tasks * m->n_classes;
-  const int32_t nB = (int32_t)B;
-  hipStream_t st = (hipStream_t)stream;
-  if (w.himg >= 0 && B > 0) {
-    int rc = head_prep(d_params + m->off_head_w, TC, ws + w.himg, st);
-    if (rc == GCMI_OK)
-      rc = head_fwd_wide(io->d_fingerprint, 2 * D, B, 2 * D, d_params + m->off_head_w, d_params + m->off_head_b, TC, 0,
-                         io->d_logits, TC, st, ws + w.himg);
-    if (rc != GCMI_ERR_UNSUPPORTED) return rc;
-  }
-  SegProduct<float> p = one_segment(&nB, io->d_fingerprint, 2 * D, 2 * D, d_params + m->off_head_w,
-                                    d_params + m->off_head_b, TC, io->d_logits, TC);
-  p.trans_w = 1;
-  return seg_gemm(p, st);
-}
-
 static int check_desc(const gcmi_model_desc* m) {
   GCMI_CHECK_ARG(m != nullptr, "model desc is NULL");
   GCMI_CHECK_ARG(m->n_layers >= 1 && m->n_layers <= kMaxL, "n_layers %d outside [1,%d]", m->n_layers, kMaxL);
@@ -278,6 +233,7 @@ int one_piece_launches() { return g_one_piece_launches.load(std::memory_order_re
     if (rc__) return rc__;   \
   } while (0)
 
+
 // Block l of the step (l < n_layers: GraphConv + BatchNorm + GraphPool; l == n_layers: the atom-level dense layer and
 // its BatchNorm): its widths and where its parameters, their gradients and its BatchNorm vectors live.
 struct Block {
@@ -288,32 +244,114 @@ struct Block {
   BnPoint bn;                     // its BatchNorm, W wide: gamma, beta and their gradients nullptr without BatchNorm;
 };                                // this batch's statistics and the folded affine map in the workspace
 
-static void make_blocks(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, float* d_grads,
-                        const gcmi_model_io* io, Block* blk) {
+// One call of the step, forward or backward: what the caller handed over, the workspace carved up, the blocks, the
+// accumulators and the statistics exchange.  Built once per call (make_step; begin_forward / begin_backward add what
+// only their direction has) and handed to every helper below.  storage: 0 = fp32 rows, 1 = the matrices the step
+// writes and reads back are bf16, 2 = the gradient streams between the backward's kernels too.
+struct Step {
+  const gcmi_model_desc* m;
+  const gcmi_graph* g;
+  const gcmi_model_io* io;
+  const float* d_params;
+  float* d_grads;  // nullptr in the forward
+  hipStream_t st;
+  int L, storage;
+  int64_t N, B;
+  int32_t nN;      // N as the one segment of the dense products (outlives their descriptions)
+  Ws w;
+  float* ws;
+  Block blk[kMaxL + 1];
+  double *acc, *acc2, *lacc;
+  BnSync sync_s;
+  const BnSync* sy;  // synchronised BatchNorm: &sync_s where this call exchanges statistics, else nullptr
+  // forward
+  int32_t training;
+  double* stats;   // training with BatchNorm: a product's epilogue also adds the column sums of its output into the
+                   // BatchNorm accumulators (clean: zeroed once per pass, self-cleaning afterwards)
+  // backward
+  const float *d_labels, *d_weights;
+  int64_t n_rows;
+  int64_t *grad_lo, *grad_hi;  // optional: where the caller learns the range of d_grads this call writes
+  float loss_inv_count;
+  bool full;       // grad_mode 1: everything trains (else the reference's: nothing in front of a GraphConv output)
+  bool sym;        // reverse slots: the scatter over the bonds is a gather
+  bool one_piece;  // what the last training forward on this workspace left of the first block (g_one_piece_ws)
+  ReadoutGrad rg;  // the per-molecule gradient the head part leaves in dfp, as the dense block's consumers read it
+  BiasLayers ub;   // the blocks whose bias gradient sums are in place: unpacked in one launch after the loop
+
+  Step() = default;
+  Step(const Step&) = delete;
+  bool bn() const { return m->batch_norm != 0; }
+  bf16_t* H(int64_t off) const { return reinterpret_cast<bf16_t*>(ws + off); }  // a bf16 matrix of the workspace
+  const float* HF(int64_t off) const { return ws + off; }  // a matrix of the step's storage behind a float* parameter
+  static bf16_t* HG(float* p) { return reinterpret_cast<bf16_t*>(p); }  // storage 2: a gradient stream as bf16 rows
+  // the backward's temporaries (storage 2: bf16 rows in the same fp32-sized blocks, ld in elements)
+  float* dpool() const { return ws + w.tC; }  // grad w.r.t. a GraphPool's output; the block below finds its own here
+  float* dX() const { return ws + w.tC; }     // grad w.r.t. a GraphConv's input rows (= dpool of the block below)
+  float* dS() const { return ws + w.tE; }     // grad w.r.t. its neighbour sums
+  float* dy() const { return ws + w.tD; }     // grad w.r.t. the (normalised) GraphPool input
+  float* dgc() const { return bn() ? ws + w.tA : dy(); }  // grad w.r.t. the GraphConv pre-activation, where it is
+                                                          // written out (no BatchNorm: the ReLU mask on dy in place)
+  const float* coef() const { return ws + w.acc; }  // [A | B | C] of the BatchNorm backward just computed (bn.hip)
+  const uint8_t* arg(int l) const { return reinterpret_cast<const uint8_t*>(ws + w.arg[l]); }
+  int zero(void* p, size_t bytes, const char* who) const {
+    if (bytes && hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
+      set_error("%s: memset failed", who);
+      return GCMI_ERR_LAUNCH;
+    }
+    return GCMI_OK;
+  }
+};
+
+static void make_blocks(Step& s) {
+  const gcmi_model_desc* m = s.m;
   const int L = m->n_layers;
-  auto grad = [&](int64_t off) { return d_grads ? d_grads + off : nullptr; };
+  auto grad = [&](int64_t off) { return s.d_grads ? s.d_grads + off : nullptr; };
   for (int l = 0; l <= L; ++l) {
-    Block& b = blk[l];
+    Block& b = s.blk[l];
     b.K = l == 0 ? m->n_feat_in : m->conv_width[l - 1];
     b.W = l == L ? m->dense_width : m->conv_width[l];
-    b.w = d_params + (l == L ? m->off_dense_w : m->off_conv_w[l]);
-    b.bias = l == L ? d_params + m->off_dense_b : ws + w.bsum[l];
+    b.w = s.d_params + (l == L ? m->off_dense_w : m->off_conv_w[l]);
+    b.bias = l == L ? s.d_params + m->off_dense_b : s.ws + s.w.bsum[l];
     b.dw = grad(l == L ? m->off_dense_w : m->off_conv_w[l]);
-    b.dbias = l == L ? grad(m->off_dense_b) : ws + w.dbsum[l];
+    b.dbias = l == L ? grad(m->off_dense_b) : s.ws + s.w.dbsum[l];
     b.dbias_rows = l == L ? nullptr : grad(m->off_conv_b[l]);
     BnPoint& p = b.bn;
     p = BnPoint();
     p.n_feat = b.W;
     if (m->batch_norm) {
-      p.gamma = d_params + m->off_bn_gamma[l]; p.beta = d_params + m->off_bn_beta[l];
+      p.gamma = s.d_params + m->off_bn_gamma[l]; p.beta = s.d_params + m->off_bn_beta[l];
       p.dgamma = grad(m->off_bn_gamma[l]); p.dbeta = grad(m->off_bn_beta[l]);
     }
-    float* bnv = ws + w.bnv[l];
+    float* bnv = s.ws + s.w.bnv[l];
     p.mean = bnv; p.invstd = bnv + b.W; p.scale = bnv + 2 * b.W; p.shift = bnv + 3 * b.W;
-    p.running_mean = io->d_bn_running_mean[l]; p.running_var = io->d_bn_running_var[l];
-    p.batches_tracked = io->d_bn_batches_tracked[l];
+    p.running_mean = s.io->d_bn_running_mean[l]; p.running_var = s.io->d_bn_running_var[l];
+    p.batches_tracked = s.io->d_bn_batches_tracked[l];
     p.eps = m->bn_eps; p.momentum = m->bn_momentum;
   }
+}
+
+// exchange: this call takes part in the statistics exchange of synchronised BatchNorm (sync given; the forward: training)
+static void make_step(Step& s, const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, float* d_grads,
+                      const gcmi_model_io* io, gcmi_stat_sync_fn sync, void* sync_ctx, bool exchange, void* stream) {
+  s.m = m; s.g = g; s.io = io; s.d_params = d_params; s.d_grads = d_grads;
+  s.st = (hipStream_t)stream;
+  s.L = m->n_layers; s.storage = m->storage;
+  s.N = g->n_atoms; s.B = g->n_mols; s.nN = (int32_t)s.N;
+  s.w = carve(m, s.N, s.B, io->ld_features);
+  s.ws = io->d_workspace;
+  make_blocks(s);
+  s.acc = reinterpret_cast<double*>(s.ws + s.w.acc);
+  s.acc2 = reinterpret_cast<double*>(s.ws + s.w.acc2);
+  s.lacc = reinterpret_cast<double*>(s.ws + s.w.lacc);
+  s.sync_s = BnSync{sync, sync_ctx, reinterpret_cast<double*>(s.ws + s.w.xch)};  // (the exchange buffer of one point)
+  s.sy = exchange ? &s.sync_s : nullptr;
+  s.training = 0; s.stats = nullptr;
+  s.d_labels = s.d_weights = nullptr; s.n_rows = 0; s.grad_lo = s.grad_hi = nullptr; s.loss_inv_count = 0.f;
+  s.full = m->grad_mode == 1;
+  s.sym = g->d_rev_pos != nullptr || g->n_edges == 0;
+  s.one_piece = false;
+  memset(&s.ub, 0, sizeof(s.ub));
 }
 
 // A product over the degree segments with the first operand's weight blocks at w_off (sg.w_rel / sg.w_self)
@@ -343,93 +381,142 @@ static SegProduct<TA, TO> conv_product(const Segs& sg, const TA* s, int64_t lds,
   return p;
 }
 
-// BatchNorm of block b in the forward, folded into b.bn.scale / shift for the kernel that reads the rows next: training
-// = this batch's statistics, from the sums the product left in acc (stats_fused) or from a pass over the rows; eval =
-// the running statistics
-// (sy: synchronised BatchNorm, training only -- the statistics of the global batch, also for a rank with N == 0)
-static int bn_forward(const Block& b, int64_t N, int32_t training, bool stats_fused, const float* rows, int64_t ld,
-                      double* acc, void* stream, const BnSync* sy = nullptr) {
+
+// b_rel_d + b_self_d of every GraphConv layer (the products add ONE bias row per degree): one launch for all layers
+static int pack_biases(const Step& s) {
+  BiasLayers bl;
+  memset(&bl, 0, sizeof(bl));
+  for (int l = 0; l < s.L; ++l) {
+    bl.src[l] = s.d_params + s.m->off_conv_b[l];
+    bl.dst[l] = s.ws + s.w.bsum[l];
+    bl.width[l] = s.m->conv_width[l];
+  }
+  hipLaunchKernelGGL(bias_pack_kernel, dim3(4, s.L), dim3(256), 0, s.st, bl, s.m->max_deg);
+  GCMI_CHECK_LAUNCH("bias_pack");
+  return GCMI_OK;
+}
+
+// ... and the per-degree bias gradients back into the reference's (2 max_deg + 1) rows, for the layers whose block ran
+static int unpack_bias_grads(const Step& s) {
+  bool any = false;
+  for (int l = 0; l < s.L; ++l) any = any || s.ub.src[l] != nullptr;
+  if (!any) return GCMI_OK;
+  hipLaunchKernelGGL(bias_unpack_kernel, dim3(4, s.L), dim3(256), 0, s.st, s.ub, s.m->max_deg);
+  GCMI_CHECK_LAUNCH("bias_unpack");
+  return GCMI_OK;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Forward
+
+// BatchNorm of block b, folded into b.bn.scale / shift for the kernel that reads the rows next: training = this
+// batch's statistics, from the sums the product left in acc (stats_fused) or from a pass over the rows; eval = the
+// running statistics
+// (s.sy: synchronised BatchNorm, training only -- the statistics of the global batch, also for a rank with N == 0)
+static int bn_forward(const Step& s, const Block& b, bool stats_fused, const float* rows, int64_t ld) {
   const BnPoint& p = b.bn;
-  if (!training)
-    return gcmi_bn_fold_eval(p.gamma, p.beta, p.running_mean, p.running_var, p.eps, p.n_feat, p.scale, p.shift, stream);
+  if (!s.training)
+    return gcmi_bn_fold_eval(p.gamma, p.beta, p.running_mean, p.running_var, p.eps, p.n_feat, p.scale, p.shift, s.st);
   BnForward f;
-  f.x = rows; f.ldx = ld; f.sums_ready = stats_fused; f.n_rows = N; f.acc = acc; f.sync = sy;
-  f.acc_clean = true;  // zeroed once per pass by the caller
-  return bn_train_forward(p, f, stream);
+  f.x = rows; f.ldx = ld; f.sums_ready = stats_fused; f.n_rows = s.N; f.acc = s.acc; f.sync = s.sy;
+  f.acc_clean = true;  // zeroed once per pass (begin_forward)
+  return bn_train_forward(p, f, s.st);
 }
 
 // A training batch without atoms launches no statistics kernel, and those are what bump the counters otherwise
-static int bump_counters(const gcmi_model_desc* m, const gcmi_model_io* io, hipStream_t st) {
+static int bump_counters(const Step& s) {
   CounterPtrs c;
-  c.n = m->n_layers + 1;
+  c.n = s.L + 1;
   bool any = false;
   for (int i = 0; i <= kMaxL; ++i) {
-    c.p[i] = i <= m->n_layers ? io->d_bn_batches_tracked[i] : nullptr;
+    c.p[i] = i <= s.L ? s.io->d_bn_batches_tracked[i] : nullptr;
     any = any || c.p[i] != nullptr;
   }
   if (any) {
-    hipLaunchKernelGGL(bump_counters_kernel, dim3(1), dim3(64), 0, st, c);
+    hipLaunchKernelGGL(bump_counters_kernel, dim3(1), dim3(64), 0, s.st, c);
     GCMI_CHECK_LAUNCH("bump_counters");
   }
   return GCMI_OK;
 }
 
-// Synchronised BatchNorm: the caller's exchange callback and the exchange buffer in the workspace
-static BnSync make_sync(gcmi_stat_sync_fn sync, void* sync_ctx, const Ws& w, float* ws) {
-  return BnSync{sync, sync_ctx, reinterpret_cast<double*>(ws + w.xch)};
+// What both forward sequences start with: the accumulators zeroed once, the bias rows packed
+static int begin_forward(Step& s, int32_t training) {
+  s.training = training;
+  s.stats = (s.bn() && training) ? s.acc : nullptr;
+  if (training && s.bn() && s.N > 0)
+    RUN(s.zero(s.ws + s.w.acc, sizeof(float) * (size_t)(s.w.z_end - s.w.acc), "model_forward"));
+  return pack_biases(s);
 }
 
-// ... and the backward of a rank whose batch has no atoms: no BatchNorm kernel runs, but the other ranks wait in the
-// exchange of every BatchNorm point their backward computes (the dense block's, then the GraphConv blocks' last to
-// first; reference gradient mode stops behind the last GraphConv block)
-static int empty_backward_syncs(const gcmi_model_desc* m, const Block* blk, const BnSync& sy, void* stream) {
-  for (int l = m->n_layers; l >= 0; --l) {
-    RUN(bn_bwd_sync_empty(blk[l].W, sy, stream));
-    if (m->grad_mode != 1 && l < m->n_layers) break;
+// The task head's forward product: with more than 32 outputs on the prepared images (head_bwd.hip; the backward makes
+// its own of the weights it is given); otherwise (and in the exact product mode) the segmented product.
+static int head_forward(const Step& s) {
+  const gcmi_model_desc* m = s.m;
+  const int D = m->dense_width;
+  const int TC = m->n_tasks * m->n_classes;
+  const int32_t nB = (int32_t)s.B;
+  const float* hw = s.d_params + m->off_head_w;
+  const float* hb = s.d_params + m->off_head_b;
+  if (s.w.himg >= 0 && s.B > 0) {
+    int rc = head_prep(hw, TC, s.ws + s.w.himg, s.st);
+    if (rc == GCMI_OK)
+      rc = head_fwd_wide(s.io->d_fingerprint, 2 * D, s.B, 2 * D, hw, hb, TC, 0, s.io->d_logits, TC, s.st, s.ws + s.w.himg);
+    if (rc != GCMI_ERR_UNSUPPORTED) return rc;
   }
+  SegProduct<float> p = one_segment(&nB, s.io->d_fingerprint, 2 * D, 2 * D, hw, hb, TC, s.io->d_logits, TC);
+  p.trans_w = 1;
+  return seg_gemm(p, s.st);
+}
+
+// Everything behind the last GraphPool, for both storages: the dense product over its rows, BatchNorm, the readout,
+// the task head, softmax and -- a training batch without atoms -- the counters
+static int forward_tail(const Step& s) {
+  const gcmi_model_desc* m = s.m;
+  const Ws& w = s.w;
+  const Block& dn = s.blk[s.L];
+  const int D = dn.W;
+  const bool h = s.storage != 0;
+  bool stats_fused = h;  // (the bf16 product always leaves the sums; it has no rows for a pass over them)
+  if (s.N > 0 && h) {
+    TimedScope ts(GCMI_K_SEG_GEMM, s.st);
+    SegProduct<bf16_t> p = one_segment(&s.nN, (const bf16_t*)s.H(w.pool[s.L - 1]), (int64_t)dn.K, dn.K, dn.w, dn.bias, D,
+                                       s.H(w.dense), D);
+    p.trans_w = 1;
+    p.act = 1;
+    const int rc = fwd_h_gemm(p, s.stats, s.ws + w.wimg, s.st);
+    if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense layer has no bf16 product kernel");
+    RUN(rc);
+  } else if (s.N > 0) {
+    SegProduct<float> p = one_segment(&s.nN, s.HF(w.pool[s.L - 1]), (int64_t)dn.K, dn.K, dn.w, dn.bias, D, s.ws + w.dense, D);
+    p.trans_w = 1;
+    p.act = 1;
+    RUN(seg_gemm_stats(p, s.stats, &stats_fused, s.st));
+  }
+  const bool bn = s.bn() && s.N > 0;
+  if (bn || s.sy) RUN(bn_forward(s, dn, stats_fused, h ? nullptr : s.ws + w.dense, h ? 0 : D));
+  RUN(readout_fwd_impl(s.g, s.HF(w.dense), D, D, bn ? dn.bn.scale : nullptr, bn ? dn.bn.shift : nullptr, 1,
+                       s.io->d_fingerprint, 2 * D, reinterpret_cast<int32_t*>(s.ws + w.arg_r),
+                       (s.training && s.bn()) ? s.ws + w.rsum : nullptr, s.st, h ? 1 : 0));
+  RUN(head_forward(s));
+  if (m->mode == 0 && s.io->d_probs) RUN(gcmi_softmax(s.io->d_logits, s.B * m->n_tasks, m->n_classes, s.io->d_probs, s.st));
+  if (s.training && s.bn() && s.N == 0 && !s.sy) RUN(bump_counters(s));  // (sy: every exchange's finalisation did)
   return GCMI_OK;
-}
-
-// Synchronised BatchNorm: what makes a one-pass block kernel refuse its buffers after dispatch is known before the
-// first launch -- a workspace that is not 16-byte aligned (every block of it then is not), or rows x leading dimension
-// beyond the kernels' 32-bit element offsets.  Refused at the entry of both calls, before this rank makes any exchange
-// of the step.
-static int check_sync_buffers(const gcmi_model_desc* m, const gcmi_graph* g, const gcmi_model_io* io) {
-  if (!aligned16(io->d_workspace)) {
-    set_error("synchronised BatchNorm: the workspace must be 16-byte aligned");
-    return GCMI_ERR_UNSUPPORTED;
-  }
-  const int64_t ldmax = std::max<int64_t>(2 * (int64_t)m->dense_width, std::max<int64_t>(io->ld_features, kOnePieceLd));
-  if (fused_bwd_enabled() && (int64_t)g->n_atoms * ldmax >= (int64_t)1 << 30) {
-    set_error("synchronised BatchNorm: %lld atoms per rank are beyond the one-pass block kernels (rows x row length "
-              "below 2^30); use smaller shards", (long long)g->n_atoms);
-    return GCMI_ERR_UNSUPPORTED;
-  }
-  return GCMI_OK;
-}
-
-// The backstop of check_sync_buffers (a kernel that cannot get its LDS).  One more pass of a BatchNorm backward's sums
-// (a one-pass block kernel refused its buffers after all) would be one
-// more exchange than the other ranks make
-static int refuse_second_sync(const char* what) {
-  set_error("synchronised BatchNorm: %s refused its buffers, and the separate pass would exchange this BatchNorm's sums "
-            "twice (16-byte aligned workspace and feature rows needed)", what);
-  return GCMI_ERR_UNSUPPORTED;
 }
 
 // The first block's forward in its one-piece form (one_piece_block0 above): the window pass writes S0 and Xb as bf16
 // rows, the product reads them as they are and leaves fp32 rows (and, training, the BatchNorm sums in acc)
-static int one_piece_forward(const gcmi_graph* g, const Ws& w, float* ws, const Block& b, const Segs& sg,
-                             const gcmi_model_io* io, double* stats, hipStream_t st) {
-  bf16_t* s0 = reinterpret_cast<bf16_t*>(ws + w.S[0]);
-  bf16_t* xb = reinterpret_cast<bf16_t*>(ws + w.xb);
+static int one_piece_forward(const Step& s, const Segs& sg) {
+  bf16_t* s0 = s.H(s.w.S[0]);
+  bf16_t* xb = s.H(s.w.xb);
   {
-    TimedScope ts(GCMI_K_GATHER_SUM, st);
-    RUN(win_gather_sum_fh(g, io->d_atom_features, io->ld_features, 76, s0, xb, kOnePieceLd, st));
+    TimedScope ts(GCMI_K_GATHER_SUM, s.st);
+    RUN(win_gather_sum_fh(s.g, s.io->d_atom_features, s.io->ld_features, 76, s0, xb, kOnePieceLd, s.st));
   }
   {
-    TimedScope ts(GCMI_K_SEG_GEMM, st);
-    const int rc = fwd_h_gemm(conv_product(sg, s0, kOnePieceLd, xb, kOnePieceLd, b, ws + w.gc[0]), stats, ws + w.wimg, st);
+    TimedScope ts(GCMI_K_SEG_GEMM, s.st);
+    const int rc = fwd_h_gemm(conv_product(sg, (const bf16_t*)s0, kOnePieceLd, (const bf16_t*)xb, kOnePieceLd, s.blk[0],
+                                           s.ws + s.w.gc[0]),
+                              s.stats, s.ws + s.w.wimg, s.st);
     if (rc == GCMI_ERR_UNSUPPORTED) set_error("model_forward: the one-piece product of GraphConv 0 refused its shape");
     RUN(rc);
   }
@@ -437,111 +524,48 @@ static int one_piece_forward(const gcmi_graph* g, const Ws& w, float* ws, const 
   return GCMI_OK;
 }
 
-// The per-molecule part of the backward as separate launches (what head_bwd_fused does in one, for the shapes it does
-// not cover): loss and d logits of the first n_rows molecules, the head's gradients, the gradient w.r.t. the
-// fingerprint in dfp; prep: the tanh derivative applied to it in place, for a BatchNorm backward that recomputes the
-// GraphGather backward from it
-static int head_backward_separate(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, float* d_grads,
-                                  const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
-                                  int64_t B, bool prep, void* stream) {
-  const int D = m->dense_width;
-  const int TC = m->n_tasks * m->n_classes;
-  const int32_t nB = (int32_t)B;
-  RUN(loss_impl(m->mode == 0 ? 0 : 1, io->d_logits, d_labels, d_weights, n_rows, m->n_tasks, m->n_classes, io->d_loss,
-                ws + w.dlogits, nullptr, reinterpret_cast<double*>(ws + w.lacc), true, stream));
-  RUN(gcmi_seg_gemm_wgrad(1, &kZero32, &nB, io->d_fingerprint, 2 * D, 2 * D, ws + w.dlogits, TC, TC,
-                          d_grads + m->off_head_w, &kZero64, d_grads + m->off_head_b, &kZero64, 1, stream));
-  hipStream_t st = (hipStream_t)stream;
-  RUN(seg_gemm(one_segment(&nB, ws + w.dlogits, TC, TC, d_params + m->off_head_w, nullptr, 2 * D, ws + w.dfp, 2 * D), st));
-  if (prep) RUN(readout_grad_prep(ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, B, D, st));
-  return GCMI_OK;
-}
-
-// the dense block's backward takes the one-pass kernel (bwd_fused.hip: fused_dense_bwd) -- asked once per call: the
-// head kernel in front of it leaves the BatchNorm sums only for that kernel
-static bool dense_block_one_pass(const gcmi_model_desc* m, int64_t N) {
-  const int Wl = m->conv_width[m->n_layers - 1];
-  return m->batch_norm && N > 0 && fused_bwd_enabled() && m->dense_width == 128 && Wl > 32 && Wl <= 64;
-}
-
-// ---- What both backward sequences hand the backward entries (common.h)
-// The per-molecule gradient the head part leaves in dfp (tanh derivative applied), as the dense block's consumers read
-// it: built once per backward
-static ReadoutGrad readout_grad(const gcmi_graph* g, const Ws& w, float* ws, int D) {
-  ReadoutGrad rg{g->d_membership, ws + w.dfp, 2 * (int64_t)D, reinterpret_cast<const int32_t*>(ws + w.arg_r)};
-  rg.rawsum = ws + w.rsum; rg.runs = g->d_mol_runs; rg.n_mols = g->n_mols; rg.n_deg = g->max_deg + 1;
-  return rg;
-}
-
-// A BatchNorm backward over N rows of x on the step's accumulator (zeroed once per call, self-cleaning afterwards);
-// the caller names the gradient source and what else it wants
-static BnBackward bn_backward(const float* x, int64_t ldx, int64_t N, double* acc, const BnSync* sy) {
-  BnBackward q;
-  q.x = x; q.ldx = ldx; q.n_rows = N; q.acc = acc; q.acc_clean = true; q.sync = sy;
-  return q;
-}
-
-// GraphConv block b's BatchNorm backward from a pass over dy, and (dx given) the gradient w.r.t. the ReLU input
-static int bn_bwd_rows(const Block& b, const float* dy, const float* gc, int64_t N, float* dx, double* acc,
-                       const BnSync* sy, void* stream) {
-  BnBackward q = bn_backward(gc, b.W, N, acc, sy);
-  q.dy = dy; q.lddy = b.W; q.dx = dx; q.lddx = b.W; q.relu_mask = 1;
-  return bn_bwd_impl(b.bn, q, stream);
-}
-
-// The per-molecule part of the backward in one kernel where the shapes allow (head_bwd.hip): loss, d logits, head
-// gradients, the gradient w.r.t. GraphGather's pre-activation in rg.g2, and -- sums given: the one-pass dense block
-// follows -- the backward sums of the dense layer's BatchNorm.  *done = false: shape not covered, nothing launched.
-// *with_sums: the sums are in place, and the loss is finalised by the BatchNorm parameter launch that follows.
-static int head_backward_fused(const gcmi_model_desc* m, const Ws& w, float* ws, const float* d_params, float* d_grads,
-                               const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
-                               const ReadoutGrad& rg, const BnPoint& dense_bn, double* sums, void* stream, bool* done,
-                               bool* with_sums) {
-  double* lacc = reinterpret_cast<double*>(ws + w.lacc);
-  HeadBackward h;
-  h.kind = m->mode == 0 ? 0 : 1; h.logits = io->d_logits; h.labels = d_labels; h.weights = d_weights;
-  h.n_rows = n_rows; h.n_tasks = m->n_tasks; h.n_classes = m->n_classes;
-  h.fp = io->d_fingerprint; h.ldfp = 2 * dense_bn.n_feat;
-  h.w = d_params + m->off_head_w; h.dw = d_grads + m->off_head_w; h.db = d_grads + m->off_head_b;
-  h.rg = &rg; h.g2 = ws + w.dfp; h.loss_acc = lacc; h.dense_bn = &dense_bn; h.sums = sums;
-  h.dl_scratch = ws + w.dlogits; h.img = w.himg >= 0 ? ws + w.himg : nullptr;
-  *done = *with_sums = false;
-  const int rc = head_bwd_fused(h, (hipStream_t)stream);
-  if (rc == GCMI_ERR_UNSUPPORTED) return GCMI_OK;
-  RUN(rc);
-  *done = true;
-  *with_sums = sums != nullptr;
-  if (!*with_sums) RUN(loss_finalize_impl(lacc, 1.f / (float)(n_rows * m->n_tasks), io->d_loss, stream, kLossRep));
-  return GCMI_OK;
-}
-
-// The dense block in one pass (fused_dense_bwd): G from the readout gradient, the block's output `dense` and coef;
-// dW, db; dpool = G W, and in psums the pooled sums for the BatchNorm below.  *n_rows must outlive the description.
-static BlockBackward dense_backward(const int32_t* n_rows, const ReadoutGrad& rg, const float* dense, const float* coef,
-                                    const float* pool, const Block& dn, float* dpool, double* psums) {
-  BlockBackward q;
-  q.n_seg = 1; q.seg_begin = &kZero32; q.seg_end = n_rows; q.w_off[0] = &kZero64; q.b_off = &kZero64;
-  q.rg = &rg; q.gc = dense; q.ldgc = dn.W; q.coef = coef; q.width = dn.W;
-  q.in[0] = {pool, dn.K}; q.k_in = dn.K; q.w = dn.w; q.dw = dn.dw; q.db = dn.dbias;
-  q.dout[0] = {dpool, dn.K}; q.psums = psums;
-  return q;
-}
-
-// GraphConv block b in one pass (fused_conv_bwd): G from dy, the block's output gc and coef; dW_rel, dW_self, dbsum
-// over [S | X].  The caller adds the input gradients (dout[].rows, psums) where the block below needs them.
-static BlockBackward conv_backward(const Segs& sg, const float* dy, const float* gc, const float* coef, const Block& b,
-                                   const float* s, int64_t lds, const float* x, int64_t ldx) {
-  BlockBackward q;
-  q.n_seg = sg.n; q.seg_begin = sg.begin; q.seg_end = sg.end; q.w_off[0] = sg.w_rel; q.w_off[1] = sg.w_self; q.b_off = sg.b_off;
-  q.dy = dy; q.lddy = b.W; q.gc = gc; q.ldgc = b.W; q.coef = coef; q.width = b.W;
-  q.in[0] = {s, lds}; q.in[1] = {x, ldx}; q.k_in = b.K; q.w = b.w; q.dw = b.dw; q.db = b.dbias;
-  q.dout[0].ld = q.dout[1].ld = b.K;
-  return q;
-}
-
-// block l's bias gradient sums are in place: unpacked into the reference's bias rows in one launch after the loop
-static void note_bias_grads(BiasLayers& ub, int l, const Block& b) {
-  ub.src[l] = b.dbias; ub.dst[l] = b.dbias_rows; ub.width[l] = b.W;
+// storage == 0: split-fp32 products (seg_gemm_stats picks the kernel), GraphPool and the next block's neighbour sums in
+// one window pass; what a kernel does not cover falls back to the general one
+static int model_forward_f(Step& s, int32_t training) {
+  const gcmi_model_desc* m = s.m;
+  const gcmi_graph* g = s.g;
+  const Ws& w = s.w;
+  float* ws = s.ws;
+  const int64_t N = s.N;
+  const bool one_piece = one_piece_block0(m, g, s.io);
+  note_one_piece(ws, one_piece);
+  RUN(begin_forward(s, training));
+  const float* x = s.io->d_atom_features;
+  int64_t ldx = s.io->ld_features;
+  for (int l = 0; l < s.L; ++l) {
+    const Block& b = s.blk[l];
+    const int W = b.W;
+    const Segs sg = make_segs(g, b.K, W);
+    bool stats_fused = false;
+    if (l == 0 && one_piece) {
+      RUN(one_piece_forward(s, sg));
+      stats_fused = training != 0;
+    } else if (N > 0) {
+      // (l > 0: the GraphPool of the block below left the neighbour sums of its output with it)
+      if (l == 0) RUN(gcmi_gather_sum_fwd(g, x, ldx, (int32_t)w.ngather[l], ws + w.S[l], w.ldS[l], 0, s.st));
+      RUN(seg_gemm_stats(conv_product(sg, s.HF(w.S[l]), w.ldS[l], x, ldx, b, ws + w.gc[l]), s.stats, &stats_fused, s.st,
+                         ws + w.wimg));
+    }
+    const bool bn = s.bn() && N > 0;
+    if (bn || s.sy) RUN(bn_forward(s, b, stats_fused, ws + w.gc[l], W));
+    if (N > 0) {
+      uint8_t* arg = training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr;
+      const float* sc = bn ? b.bn.scale : nullptr;
+      const float* sh = bn ? b.bn.shift : nullptr;
+      if (l + 1 < s.L)  // GraphPool and the neighbour sums of the block above in one window pass
+        RUN(gcmi_gather_max_sum_fwd(g, ws + w.gc[l], W, W, sc, sh, ws + w.pool[l], W, arg, ws + w.S[l + 1], w.ldS[l + 1], s.st));
+      else
+        RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, sc, sh, ws + w.pool[l], W, arg, s.st));
+    }
+    x = ws + w.pool[l];
+    ldx = W;
+  }
+  return forward_tail(s);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -581,218 +605,454 @@ static int require_h(const gcmi_model_desc* m, const gcmi_graph* g, const gcmi_m
   return GCMI_OK;
 }
 
-static int model_forward_h(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, const gcmi_model_io* io,
-                           int32_t training, gcmi_stat_sync_fn sync, void* sync_ctx, void* stream) {
-  RUN(require_h(m, g, io, false));
-  hipStream_t st = (hipStream_t)stream;
-  const int L = m->n_layers;
-  const int64_t N = g->n_atoms, B = g->n_mols;
-  const Ws w = carve(m, N, B, io->ld_features);
-  float* ws = io->d_workspace;
-  Block blk[kMaxL + 1];
-  make_blocks(m, w, ws, d_params, nullptr, io, blk);
-  auto H = [&](int64_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
-  double* acc = reinterpret_cast<double*>(ws + w.acc);
-  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
-  const BnSync* sy = (sync && training) ? &sync_s : nullptr;
-  if (training && N > 0 && hipMemsetAsync(ws + w.acc, 0, sizeof(float) * (size_t)(w.z_end - w.acc), st) != hipSuccess) {
-    set_error("model_forward: memset failed");
-    return GCMI_ERR_LAUNCH;
-  }
+
+static int model_forward_h(Step& s, int32_t training) {
+  RUN(require_h(s.m, s.g, s.io, false));
+  const gcmi_graph* g = s.g;
+  const Ws& w = s.w;
+  RUN(begin_forward(s, training));
   const bf16_t* xin = nullptr;
   int64_t ldin = 0;
-  RUN(pack_biases(m, w, ws, d_params, st));
-  for (int l = 0; l < L; ++l) {
-    const Block& b = blk[l];
+  for (int l = 0; l < s.L; ++l) {
+    const Block& b = s.blk[l];
     const Segs sg = make_segs(g, b.K, b.W);
-    if (N > 0) {
+    if (s.N > 0) {
       {
-        TimedScope ts(GCMI_K_GATHER_SUM, st);
+        TimedScope ts(GCMI_K_GATHER_SUM, s.st);
         if (l == 0) {  // fp32 atom features -> bf16 neighbour sums + a bf16 copy of the rows themselves
-          RUN(win_gather_sum_fh(g, io->d_atom_features, io->ld_features, (int)w.ngather[0], H(w.S[0]), H(w.xb), w.ldS[0], st));
-          xin = H(w.xb);
+          RUN(win_gather_sum_fh(g, s.io->d_atom_features, s.io->ld_features, (int)w.ngather[0], s.H(w.S[0]), s.H(w.xb),
+                                w.ldS[0], s.st));
+          xin = s.H(w.xb);
           ldin = w.ldS[0];
         } else {
-          RUN(win_gather_sum_h(g, xin, ldin, b.K, H(w.S[l]), w.ldS[l], st));
+          RUN(win_gather_sum_h(g, xin, ldin, b.K, s.H(w.S[l]), w.ldS[l], s.st));
         }
       }
       {
-        TimedScope ts(GCMI_K_SEG_GEMM, st);
-        const int rc = fwd_h_gemm(conv_product(sg, H(w.S[l]), w.ldS[l], xin, ldin, b, H(w.gc[l])),
-                                  training ? acc : nullptr, ws + w.wimg, st);
+        TimedScope ts(GCMI_K_SEG_GEMM, s.st);
+        const int rc = fwd_h_gemm(conv_product(sg, (const bf16_t*)s.H(w.S[l]), w.ldS[l], xin, ldin, b, s.H(w.gc[l])),
+                                  s.stats, s.ws + w.wimg, s.st);
         if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: GraphConv %d has no bf16 product kernel", l);
         RUN(rc);
       }
-      RUN(bn_forward(b, N, training, true, nullptr, 0, acc, stream, sy));
+      RUN(bn_forward(s, b, true, nullptr, 0));
       {
-        TimedScope ts(GCMI_K_GATHER_MAX, st);
-        RUN(win_gather_max_h(g, H(w.gc[l]), b.W, b.W, b.bn.scale, b.bn.shift, H(w.pool[l]), b.W,
-                             training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr, st));
+        TimedScope ts(GCMI_K_GATHER_MAX, s.st);
+        RUN(win_gather_max_h(g, s.H(w.gc[l]), b.W, b.W, b.bn.scale, b.bn.shift, s.H(w.pool[l]), b.W,
+                             training ? reinterpret_cast<uint8_t*>(s.ws + w.arg[l]) : nullptr, s.st));
       }
-    } else if (sy) {
-      RUN(bn_forward(b, 0, training, true, nullptr, 0, acc, stream, sy));
+    } else if (s.sy) {
+      RUN(bn_forward(s, b, true, nullptr, 0));
     }
-    xin = H(w.pool[l]);
+    xin = s.H(w.pool[l]);
     ldin = b.W;
   }
-  const Block& dn = blk[L];
-  const int D = dn.W;
-  if (N > 0) {
-    const int32_t nN = (int32_t)N;
-    {
-      TimedScope ts(GCMI_K_SEG_GEMM, st);
-      SegProduct<bf16_t> p = one_segment(&nN, xin, ldin, dn.K, dn.w, dn.bias, D, H(w.dense), D);
-      p.trans_w = 1;
-      p.act = 1;
-      const int rc = fwd_h_gemm(p, training ? acc : nullptr, ws + w.wimg, st);
-      if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense layer has no bf16 product kernel");
-      RUN(rc);
-    }
-    RUN(bn_forward(dn, N, training, true, nullptr, 0, acc, stream, sy));
-  } else if (sy) {
-    RUN(bn_forward(dn, 0, training, true, nullptr, 0, acc, stream, sy));
-  }
-  RUN(readout_fwd_impl(g, reinterpret_cast<const float*>(H(w.dense)), D, D, N > 0 ? dn.bn.scale : nullptr,
-                       N > 0 ? dn.bn.shift : nullptr, 1, io->d_fingerprint, 2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
-                       training ? ws + w.rsum : nullptr, stream, 1));
-  RUN(head_forward(m, w, ws, d_params, io, B, stream));
-  if (m->mode == 0 && io->d_probs) RUN(gcmi_softmax(io->d_logits, B * m->n_tasks, m->n_classes, io->d_probs, stream));
-  if (training && N == 0 && !sy) RUN(bump_counters(m, io, st));  // (sy: the finalisation of every exchange did)
+  return forward_tail(s);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Loss + backward.  One walk over the blocks for both storages: the per-molecule head part, the dense block, then
+// GraphConv / BatchNorm / GraphPool last to first.  Each block takes the route block_route picks for it; bf16 storage
+// has one route, and a kernel of it that refuses is an error where fp32 storage falls back.
+
+// What the backward starts with: the range of the gradient arena it writes, zeroed; [dlogits (rows beyond n_rows carry
+// no gradient) | the bias-gradient sums | every accumulator] zeroed; the readout gradient's description
+static int begin_backward(Step& s) {
+  const gcmi_model_desc* m = s.m;
+  s.loss_inv_count = 1.f / (float)(s.n_rows * m->n_tasks);
+  s.one_piece = s.storage == 0 && noted_one_piece(s.ws);
+  const int64_t lo = s.full ? 0 : (s.bn() ? m->off_bn_gamma[s.L - 1] : m->off_dense_w);
+  const int64_t hi = m->n_params;
+  if (s.grad_lo) *s.grad_lo = lo;
+  if (s.grad_hi) *s.grad_hi = hi;
+  RUN(s.zero(s.d_grads + lo, sizeof(float) * (size_t)(hi - lo), "model_loss_backward"));
+  RUN(s.zero(s.ws + s.w.dlogits, sizeof(float) * (size_t)(s.w.z_end - s.w.dlogits), "model_loss_backward"));
+  const int D = m->dense_width;
+  s.rg = ReadoutGrad{s.g->d_membership, s.ws + s.w.dfp, 2 * (int64_t)D, reinterpret_cast<const int32_t*>(s.ws + s.w.arg_r)};
+  s.rg.rawsum = s.ws + s.w.rsum; s.rg.runs = s.g->d_mol_runs; s.rg.n_mols = s.g->n_mols; s.rg.n_deg = s.g->max_deg + 1;
   return GCMI_OK;
 }
 
-static int model_loss_backward_h(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params, float* d_grads,
-                                 const gcmi_model_io* io, const float* d_labels, const float* d_weights, int64_t n_rows,
-                                 int64_t* grad_lo, int64_t* grad_hi, gcmi_stat_sync_fn sync, void* sync_ctx,
-                                 void* stream) {
-  RUN(require_h(m, g, io, true));
-  hipStream_t st = (hipStream_t)stream;
-  const int L = m->n_layers;
-  const int64_t N = g->n_atoms, B = g->n_mols;
-  const Ws w = carve(m, N, B, io->ld_features);
-  float* ws = io->d_workspace;
-  Block blk[kMaxL + 1];
-  make_blocks(m, w, ws, d_params, d_grads, io, blk);
-  auto H = [&](int64_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
-  auto HF = [&](int64_t off) { return reinterpret_cast<const float*>(ws + off); };  // a bf16 matrix behind a float* parameter
-  const bool full = m->grad_mode == 1;
-  const int64_t lo = full ? 0 : m->off_bn_gamma[L - 1];
-  const int64_t hi = m->n_params;
-  if (grad_lo) *grad_lo = lo;
-  if (grad_hi) *grad_hi = hi;
-  if (hipMemsetAsync(d_grads + lo, 0, sizeof(float) * (size_t)(hi - lo), st) != hipSuccess ||
-      hipMemsetAsync(ws + w.dlogits, 0, sizeof(float) * (size_t)(w.z_end - w.dlogits), st) != hipSuccess) {
-    set_error("model_loss_backward: memset failed");
-    return GCMI_ERR_LAUNCH;
+// The backward of a rank whose batch has no atoms: no BatchNorm kernel runs, but the other ranks wait in the exchange
+// of every BatchNorm point their backward computes (the dense block's, then the GraphConv blocks' last to first;
+// reference gradient mode stops behind the last GraphConv block)
+static int empty_backward_syncs(const Step& s) {
+  for (int l = s.L; l >= 0; --l) {
+    RUN(bn_bwd_sync_empty(s.blk[l].W, *s.sy, s.st));
+    if (!s.full && l < s.L) break;
   }
-  double* acc = reinterpret_cast<double*>(ws + w.acc);
-  double* acc2 = reinterpret_cast<double*>(ws + w.acc2);
-  double* lacc = reinterpret_cast<double*>(ws + w.lacc);
-  const float loss_inv_count = 1.f / (float)(n_rows * m->n_tasks);
-  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
-  const BnSync* sy = sync ? &sync_s : nullptr;
-  // ---- per-molecule part (fp32 throughout: the fingerprint and everything behind it are per-molecule rows)
-  const Block& dn = blk[L];
-  const int D = dn.W;
-  const ReadoutGrad rg = readout_grad(g, w, ws, D);
-  bool head_done = false, head_sums = false;
-  RUN(head_backward_fused(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, rg, dn.bn,
-                          (N > 0 && g->d_mol_runs) ? acc : nullptr, stream, &head_done, &head_sums));
-  if (!head_done) RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, true, stream));
-  if (N == 0) return sy ? empty_backward_syncs(m, blk, *sy, stream) : GCMI_OK;
-  float* dpool = ws + w.tC;
-  const float* coef = ws + w.acc;
-  // storage == 2: dpool, dy, dS and dXs are bf16 rows (in the same fp32-sized workspace blocks, ld in elements)
-  const bool gb = m->storage == 2;
-  auto HG = [](float* p) { return reinterpret_cast<bf16_t*>(p); };
-  // ---- dense block: BatchNorm sums from per-molecule data, then one pass (dense and pool rows arrive as bf16)
-  {
-    // (the per-molecule sums kernel reads rawsum, never the atom rows: the bf16 matrix is only passed through)
-    BnBackward q = bn_backward(HF(w.dense), D, N, acc, sy);
-    if (head_sums) {
-      q.loss = {lacc, kLossRep, loss_inv_count, io->d_loss};
-      RUN(bn_bwd_params_impl(dn.bn, q, stream));
-    } else {
-      q.rg = &rg;
-      RUN(bn_bwd_impl(dn.bn, q, stream));
-    }
-  }
-  {
-    TimedScope ts(GCMI_K_FUSED_BWD, st);
-    const int32_t nN = (int32_t)N;
-    BlockBackward q = dense_backward(&nN, rg, HF(w.dense), coef, HF(w.pool[L - 1]), dn, dpool, acc2);
-    q.act_bf16 = gb ? 2 : 1;
-    const int rc = fused_dense_bwd(q, st);
-    if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: the dense block has no one-pass backward");
-    RUN(rc);
-  }
-  // ---- GraphConv / BatchNorm / GraphPool blocks, last to first (gradient streams fp32: the window kernels as they are)
-  bool dy_ready = false;
-  BiasLayers ub;
-  memset(&ub, 0, sizeof(ub));
-  for (int l = L - 1; l >= 0; --l) {
-    const Block& b = blk[l];
-    const int W = b.W, K = b.K;
-    float* dy = ws + w.tD;
-    const Segs sg = make_segs(g, K, W);
-    const bf16_t* xin = l == 0 ? H(w.xb) : H(w.pool[l - 1]);
-    const int64_t ldx = l == 0 ? w.ldS[0] : m->conv_width[l - 1];
-    float* dS = ws + w.tE;
-    float* dX = ws + w.tC;
-    const uint8_t* arg = reinterpret_cast<const uint8_t*>(ws + w.arg[l]);
-    // the block above left sum dP and sum dP * P: this BatchNorm's backward needs no pass over dy (bn_bwd_pool_impl);
-    // dy itself only when the GraphConv below trains, or where the pooled sums are ill-conditioned
-    if (dy_ready) {
-      // (left by win_gather_sumacc_max_bwd below, one iteration ago)
-    } else if (gb) {
-      TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_max_bwd_h(g, HG(dpool), W, W, arg, HG(dy), W, full ? nullptr : b.bn.gamma, full ? nullptr : b.bn.beta, st));
-    } else if (full) {
-      RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
-    } else {
-      TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.bn.gamma, b.bn.beta, st));
-    }
-    {
-      BnBackward q = bn_backward(HF(w.gc[l]), W, N, acc, sy);
-      q.dy = dy; q.lddy = W; q.x_bf16 = gb ? 2 : 1; q.psums = acc2;
-      RUN(bn_bwd_pool_impl(b.bn, q, stream));
-    }
-    dy_ready = false;
-    if (!full) break;  // reference semantics: nothing in front of a GraphConv output trains
-    {
-      TimedScope ts(GCMI_K_FUSED_BWD, st);
-      BlockBackward q = conv_backward(sg, dy, HF(w.gc[l]), coef, b, HF(w.S[l]), w.ldS[l], reinterpret_cast<const float*>(xin), ldx);
-      q.act_bf16 = gb ? 2 : 1;
-      if (l > 0) { q.dout[0].rows = dS; q.dout[1].rows = dX; q.psums = acc2; }
-      const int rc = fused_conv_bwd(q, st);
-      if (rc == GCMI_ERR_UNSUPPORTED) set_error("bf16 activation storage: GraphConv %d has no one-pass backward", l);
-      RUN(rc);
-    }
-    note_bias_grads(ub, l, b);
-    if (l == 0) break;  // the atom features need no gradient
-    // dX holds the self part; the neighbour part is added onto it, and where the window kernels can hold a third tile
-    // the GraphPool backward of the block below runs in the same pass
-    const uint8_t* arg_below = reinterpret_cast<const uint8_t*>(ws + w.arg[l - 1]);
-    if (gb) {
-      if (!win_two_stage_usable_h(g, K)) {
-        set_error("bf16 gradient streams: no LDS for the two-stage window pass");
-        return GCMI_ERR_UNSUPPORTED;
-      }
-      TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_sumacc_max_bwd_h(g, HG(dS), K, K, HG(dX), K, arg_below, HG(ws + w.tD), K, st));
-      dy_ready = true;
-    } else if (win_two_stage_usable(g, K) && aligned16(dS) && aligned16(dX) && aligned16(ws + w.tD)) {
-      TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-      RUN(win_gather_sumacc_max_bwd(g, dS, K, K, dX, K, arg_below, ws + w.tD, K, st));
-      dy_ready = true;
-    } else {
-      RUN(gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 1, stream));
-    }
-    dpool = dX;
-  }
-  RUN(unpack_bias_grads(m, ub, L, st));
   return GCMI_OK;
+}
+
+// Synchronised BatchNorm: what makes a one-pass block kernel refuse its buffers after dispatch is known before the
+// first launch -- a workspace that is not 16-byte aligned (every block of it then is not), or rows x leading dimension
+// beyond the kernels' 32-bit element offsets.  Refused at the entry of both calls, before this rank makes any exchange
+// of the step.
+static int check_sync_buffers(const gcmi_model_desc* m, const gcmi_graph* g, const gcmi_model_io* io) {
+  if (!aligned16(io->d_workspace)) {
+    set_error("synchronised BatchNorm: the workspace must be 16-byte aligned");
+    return GCMI_ERR_UNSUPPORTED;
+  }
+  const int64_t ldmax = std::max<int64_t>(2 * (int64_t)m->dense_width, std::max<int64_t>(io->ld_features, kOnePieceLd));
+  if (fused_bwd_enabled() && (int64_t)g->n_atoms * ldmax >= (int64_t)1 << 30) {
+    set_error("synchronised BatchNorm: %lld atoms per rank are beyond the one-pass block kernels (rows x row length "
+              "below 2^30); use smaller shards", (long long)g->n_atoms);
+    return GCMI_ERR_UNSUPPORTED;
+  }
+  return GCMI_OK;
+}
+
+// The backstop of check_sync_buffers (a kernel that cannot get its LDS).  One more pass of a BatchNorm backward's sums
+// (a one-pass block kernel refused its buffers after all) would be one
+// more exchange than the other ranks make
+static int refuse_second_sync(const char* what) {
+  set_error("synchronised BatchNorm: %s refused its buffers, and the separate pass would exchange this BatchNorm's sums "
+            "twice (16-byte aligned workspace and feature rows needed)", what);
+  return GCMI_ERR_UNSUPPORTED;
+}
+
+
+// A BatchNorm backward over the N rows of x on the step's accumulator (zeroed once per call, self-cleaning afterwards);
+// the caller names the gradient source and what else it wants
+static BnBackward bn_backward(const Step& s, const float* x, int64_t ldx, const BnSync* sy) {
+  BnBackward q;
+  q.x = x; q.ldx = ldx; q.n_rows = s.N; q.acc = s.acc; q.acc_clean = true; q.sync = sy;
+  return q;
+}
+
+// ---- the per-molecule part (fp32 in every storage: the fingerprint and everything behind it are per-molecule rows)
+// In one kernel where the shapes allow (head_bwd.hip): loss, d logits, head gradients, the gradient w.r.t.
+// GraphGather's pre-activation in rg.g2, and -- sums given: the one-pass dense block follows -- the backward sums of
+// the dense layer's BatchNorm.  *done = false: shape not covered, nothing launched.  *with_sums: the sums are in
+// place, and the loss is finalised by the BatchNorm parameter launch that follows.
+static int head_backward_fused(const Step& s, double* sums, bool* done, bool* with_sums) {
+  const gcmi_model_desc* m = s.m;
+  const BnPoint& dense_bn = s.blk[s.L].bn;
+  HeadBackward h;
+  h.kind = m->mode == 0 ? 0 : 1; h.logits = s.io->d_logits; h.labels = s.d_labels; h.weights = s.d_weights;
+  h.n_rows = s.n_rows; h.n_tasks = m->n_tasks; h.n_classes = m->n_classes;
+  h.fp = s.io->d_fingerprint; h.ldfp = 2 * dense_bn.n_feat;
+  h.w = s.d_params + m->off_head_w; h.dw = s.d_grads + m->off_head_w; h.db = s.d_grads + m->off_head_b;
+  h.rg = &s.rg; h.g2 = s.ws + s.w.dfp; h.loss_acc = s.lacc; h.dense_bn = &dense_bn; h.sums = sums;
+  h.dl_scratch = s.ws + s.w.dlogits; h.img = s.w.himg >= 0 ? s.ws + s.w.himg : nullptr;
+  *done = *with_sums = false;
+  const int rc = head_bwd_fused(h, s.st);
+  if (rc == GCMI_ERR_UNSUPPORTED) return GCMI_OK;
+  RUN(rc);
+  *done = true;
+  *with_sums = sums != nullptr;
+  if (!*with_sums) RUN(loss_finalize_impl(s.lacc, s.loss_inv_count, s.io->d_loss, s.st, kLossRep));
+  return GCMI_OK;
+}
+
+// ... as separate launches (the shapes head_bwd_fused does not cover): loss and d logits of the first n_rows
+// molecules, the head's gradients, the gradient w.r.t. the fingerprint in dfp; prep: the tanh derivative applied to it
+// in place, for a BatchNorm backward that recomputes the GraphGather backward from it
+static int head_backward_separate(const Step& s, bool prep) {
+  const gcmi_model_desc* m = s.m;
+  const Ws& w = s.w;
+  float* ws = s.ws;
+  const int D = m->dense_width;
+  const int TC = m->n_tasks * m->n_classes;
+  const int32_t nB = (int32_t)s.B;
+  RUN(loss_impl(m->mode == 0 ? 0 : 1, s.io->d_logits, s.d_labels, s.d_weights, s.n_rows, m->n_tasks, m->n_classes,
+                s.io->d_loss, ws + w.dlogits, nullptr, s.lacc, true, s.st));
+  RUN(gcmi_seg_gemm_wgrad(1, &kZero32, &nB, s.io->d_fingerprint, 2 * D, 2 * D, ws + w.dlogits, TC, TC,
+                          s.d_grads + m->off_head_w, &kZero64, s.d_grads + m->off_head_b, &kZero64, 1, s.st));
+  RUN(seg_gemm(one_segment(&nB, s.HF(w.dlogits), TC, TC, s.d_params + m->off_head_w, nullptr, 2 * D, ws + w.dfp, 2 * D), s.st));
+  if (prep) RUN(readout_grad_prep(ws + w.dfp, 2 * D, s.io->d_fingerprint, 2 * D, s.B, D, s.st));
+  return GCMI_OK;
+}
+
+// the dense block's backward takes the one-pass kernel (bwd_fused.hip: fused_dense_bwd) -- asked once per call: the
+// head kernel in front of it leaves the BatchNorm sums only for that kernel
+// (bf16 storage: true whenever there are atoms -- check_desc and require_h leave no other shape)
+static bool dense_block_one_pass(const gcmi_model_desc* m, int64_t N) {
+  const int Wl = m->conv_width[m->n_layers - 1];
+  return m->batch_norm && N > 0 && fused_bwd_enabled() && m->dense_width == 128 && Wl > 32 && Wl <= 64;
+}
+
+// *head_sums: the dense BatchNorm's backward sums are in acc
+static int head_backward(const Step& s, bool dense_one_pass, bool* head_sums) {
+  bool done = false;
+  *head_sums = false;
+  if (s.bn())  // (without BatchNorm the readout backward applies the tanh derivative itself)
+    RUN(head_backward_fused(s, (dense_one_pass && s.g->d_mol_runs) ? s.acc : nullptr, &done, head_sums));
+  // (the tanh derivative applied in place only for the BatchNorm backward that follows; bf16 storage: always)
+  if (!done) RUN(head_backward_separate(s, s.storage != 0 || (s.bn() && s.N > 0)));
+  return GCMI_OK;
+}
+
+// ---- the dense block
+// Its BatchNorm's parameters (dgamma, dbeta, the coefficient vectors): from the sums the head kernel left in place
+// (which also finalises the loss), else with the GraphGather backward recomputed from the per-molecule gradient -- the
+// N x D gradient is never written or re-read.  dx: also the gradient w.r.t. the dense pre-activation (separate route).
+static int dense_bn_backward(const Step& s, bool head_sums, float* dx, const BnSync* sy) {
+  const Block& dn = s.blk[s.L];
+  // (per-molecule sums read rawsum, never the atom rows: a bf16 matrix is only passed through)
+  BnBackward q = bn_backward(s, s.HF(s.w.dense), dn.W, sy);
+  if (head_sums) {
+    q.loss = {s.lacc, kLossRep, s.loss_inv_count, s.io->d_loss};
+    return bn_bwd_params_impl(dn.bn, q, s.st);
+  }
+  q.rg = &s.rg; q.dx = dx; q.lddx = dn.W; q.relu_mask = 1;
+  return bn_bwd_impl(dn.bn, q, s.st);
+}
+
+// The dense block in one pass (fused_dense_bwd): G from the readout gradient, the block's output `dense` and coef;
+// dW, db; dpool = G W, and in acc2 the pooled sums for the BatchNorm below.
+static BlockBackward dense_backward(const Step& s) {
+  const Block& dn = s.blk[s.L];
+  BlockBackward q;
+  q.n_seg = 1; q.seg_begin = &kZero32; q.seg_end = &s.nN; q.w_off[0] = &kZero64; q.b_off = &kZero64;
+  q.rg = &s.rg; q.gc = s.HF(s.w.dense); q.ldgc = dn.W; q.coef = s.coef(); q.width = dn.W;
+  q.in[0] = {s.HF(s.w.pool[s.L - 1]), dn.K}; q.k_in = dn.K; q.w = dn.w; q.dw = dn.dw; q.db = dn.dbias;
+  q.dout[0] = {s.dpool(), dn.K}; q.psums = s.acc2;
+  q.act_bf16 = s.storage;
+  return q;
+}
+
+// BatchNorm parameters, then dW, db and dpool: in one pass over the rows (dxD formed per 64-row tile in LDS) where
+// dense_one_pass says so, else as separate launches.  *have_psums: acc2 holds sum dP, sum dP * P for the BatchNorm of
+// the last GraphConv block.
+static int dense_block_backward(const Step& s, bool dense_one_pass, bool head_sums, bool* have_psums) {
+  const Ws& w = s.w;
+  float* ws = s.ws;
+  const Block& dn = s.blk[s.L];
+  const int D = dn.W, Wl = dn.K;
+  float* dxD = ws + w.tB;  // grad w.r.t. the dense pre-activation
+  *have_psums = false;
+  if (s.bn()) {
+    RUN(dense_bn_backward(s, head_sums, dense_one_pass ? nullptr : dxD, s.sy));
+    if (dense_one_pass) {
+      int rc;
+      {
+        TimedScope ts(GCMI_K_FUSED_BWD, s.st);
+        rc = fused_dense_bwd(dense_backward(s), s.st);
+      }
+      *have_psums = rc == GCMI_OK;
+      if (rc != GCMI_ERR_UNSUPPORTED) return rc;
+      if (s.storage != 0) {
+        set_error("bf16 activation storage: the dense block has no one-pass backward");
+        return rc;
+      }
+      if (s.sy) return refuse_second_sync("the one-pass dense block");
+      // not covered after all (misaligned buffers): the separate pass, with its sums once more
+      RUN(dense_bn_backward(s, false, dxD, nullptr));
+    }
+  } else {
+    dxD = ws + w.tA;  // grad w.r.t. the readout input, then the ReLU mask in place
+    RUN(gcmi_readout_bwd(s.g, ws + w.dfp, 2 * D, s.io->d_fingerprint, 2 * D, D, 1, s.rg.arg, dxD, D, s.st));
+    RUN(gcmi_relu_bwd(dxD, D, ws + w.dense, D, s.N, D, s.st));
+  }
+  RUN(gcmi_seg_gemm_wgrad(1, &kZero32, &s.nN, ws + w.pool[s.L - 1], Wl, Wl, dxD, D, D, dn.dw, &kZero64, dn.dbias, &kZero64,
+                          1, s.st));
+  return seg_gemm(one_segment(&s.nN, (const float*)dxD, D, D, dn.w, nullptr, Wl, s.dpool(), Wl), s.st);
+}
+
+// ---- a GraphConv / BatchNorm / GraphPool block
+// The rows block l's GraphConv read: S and X with their leading dimensions, in the form the forward left them
+// (one-piece form of the first block: S0 and the copy Xb of the atom features are bf16 rows)
+struct BlockIn {
+  const float* x;
+  int64_t ldx, ldS;
+};
+static BlockIn block_in(const Step& s, int l) {
+  if (l > 0) return {s.HF(s.w.pool[l - 1]), s.m->conv_width[l - 1], s.w.ldS[l]};
+  if (s.storage != 0) return {s.HF(s.w.xb), s.w.ldS[0], s.w.ldS[0]};
+  if (s.one_piece) return {s.HF(s.w.xb), kOnePieceLd, kOnePieceLd};
+  return {s.io->d_atom_features, s.io->ld_features, s.w.ldS[0]};
+}
+
+// The route block l's backward takes, decided once, before its first launch.
+struct BlockRoute {
+  bool one_pass;     // dW_rel, dW_self, dbsum (and for l > 0 dS and the self part of dX) in one pass over the rows
+                     // (bwd_fused.hip); else the separate launches
+  bool pooled_sums;  // its BatchNorm's backward sums from the pooled sums the block above left in acc2; else from a
+                     // pass over dy
+  bool two_stage;    // after the one pass: the neighbour part and the GraphPool backward of the block below in one
+                     // window pass (dX in LDS only); else the accumulating gather, without reverse slots the scatter
+  bool one_piece;    // the first block on the bf16 rows its one-piece forward left
+};
+// have_psums: the block above ran in one pass and left the pooled sums
+static BlockRoute block_route(const Step& s, int l, const BlockIn& in, bool have_psums) {
+  const gcmi_graph* g = s.g;
+  const int W = s.blk[l].W, K = s.blk[l].K;
+  BlockRoute r;
+  r.one_piece = l == 0 && s.one_piece;
+  if (s.storage != 0) {  // the one route of bf16 storage (require_h); a kernel that refuses ends the call
+    r.one_pass = s.full;
+    r.pooled_sums = true;
+  } else {
+    // the one pass covers the default widths in split-bf16 mode; it wants 16-byte rows of every operand
+    r.one_pass = s.full && fused_bwd_enabled() && W == 64 && in.ldx % 4 == 0 && aligned16(in.x) &&
+                 ((l == 0 && K > 32 && K <= 96) || (l > 0 && K > 32 && K <= 64));
+    r.pooled_sums = have_psums && s.bn() && s.sym && (r.one_pass || !s.full) && win_usable(g, W, true) && win_has_width(W);
+  }
+  // ... when the window kernels can hold a third tile
+  r.two_stage = r.one_pass && l > 0 &&
+                (s.storage == 2 ? win_two_stage_usable_h(g, K)
+                                : s.sym && fused_bwd_enabled() && win_two_stage_usable(g, K) && aligned16(s.dS()) &&
+                                      aligned16(s.dX()) && aligned16(s.dy()));
+  return r;
+}
+
+// dgc, the gradient w.r.t. block l's pre-activation, written out in rows (what the one pass forms per tile): with
+// BatchNorm by its backward over dy, which also leaves dgamma, dbeta and coef and runs for those alone when dgc is not
+// wanted; without, the ReLU mask on dy in place
+static int bn_relu_backward_rows(const Step& s, int l, bool want_dgc, const BnSync* sy) {
+  const Block& b = s.blk[l];
+  if (s.bn()) {
+    BnBackward q = bn_backward(s, s.ws + s.w.gc[l], b.W, sy);
+    q.dy = s.dy(); q.lddy = b.W; q.dx = want_dgc ? s.dgc() : nullptr; q.lddx = b.W; q.relu_mask = 1;
+    return bn_bwd_impl(b.bn, q, s.st);
+  }
+  return want_dgc ? gcmi_relu_bwd(s.dy(), b.W, s.ws + s.w.gc[l], b.W, s.N, b.W, s.st) : GCMI_OK;
+}
+
+// GraphPool backward of block l (dpool -> dy) and its BatchNorm backward.  Pooled sums: the block above left sum dP
+// and sum dP * P, so this BatchNorm's backward needs no pass over dy (bn.hip, bn_bwd_pool_impl); dy itself is needed
+// when the GraphConv below trains, otherwise only by the ill-conditioned fallback, and those kernels return at once
+// unless that applies.  dy_ready: the two-stage pass of the block above already left dy.
+static int pool_bn_backward(const Step& s, int l, const BlockRoute& r, bool dy_ready) {
+  const gcmi_graph* g = s.g;
+  const Block& b = s.blk[l];
+  const int W = b.W;
+  float* dy = s.dy();
+  if (!s.sym) RUN(s.zero(dy, sizeof(float) * (size_t)(s.N * W), "model_loss_backward"));  // (the atomic form adds)
+  if (!r.pooled_sums) {
+    if (!dy_ready) RUN(gcmi_gather_max_bwd(g, s.dpool(), W, W, s.arg(l), dy, W, s.st));
+    return bn_relu_backward_rows(s, l, s.full && !r.one_pass, s.sy);
+  }
+  if (dy_ready) {
+  } else if (s.storage == 2) {
+    TimedScope ts(GCMI_K_GATHER_MAX_BWD, s.st);
+    RUN(win_gather_max_bwd_h(g, s.HG(s.dpool()), W, W, s.arg(l), s.HG(dy), W, s.full ? nullptr : b.bn.gamma,
+                             s.full ? nullptr : b.bn.beta, s.st));
+  } else if (s.full) {
+    RUN(gcmi_gather_max_bwd(g, s.dpool(), W, W, s.arg(l), dy, W, s.st));
+  } else {
+    TimedScope ts(GCMI_K_GATHER_MAX_BWD, s.st);
+    RUN(win_gather_max_bwd_if_ill(g, s.dpool(), W, W, s.arg(l), dy, W, b.bn.gamma, b.bn.beta, s.st));
+  }
+  BnBackward q = bn_backward(s, s.HF(s.w.gc[l]), W, s.sy);
+  q.dy = dy; q.lddy = W; q.x_bf16 = s.storage; q.psums = s.acc2;
+  return bn_bwd_pool_impl(b.bn, q, s.st);
+}
+
+// Block l in one pass (fused_conv_bwd): G from dy, the block's output gc and coef, formed per tile in LDS; dW_rel,
+// dW_self, dbsum over [S | X]; for l > 0 dS = G W_rel^T, the self part of dX and the pooled sums for the BatchNorm
+// below.  *done = false: the kernel refused its buffers after all (misaligned ones) and the separate pass has left dgc
+// in rows, its sums taken once more -- which bf16 storage and synchronised BatchNorm refuse.
+static int conv_one_pass(const Step& s, int l, const Segs& sg, const BlockIn& in, const BlockRoute& r, bool* done) {
+  const Block& b = s.blk[l];
+  int rc;
+  {
+    TimedScope ts(GCMI_K_FUSED_BWD, s.st);
+    BlockBackward q;
+    q.n_seg = sg.n; q.seg_begin = sg.begin; q.seg_end = sg.end; q.w_off[0] = sg.w_rel; q.w_off[1] = sg.w_self; q.b_off = sg.b_off;
+    q.dy = s.dy(); q.lddy = b.W; q.gc = s.HF(s.w.gc[l]); q.ldgc = b.W; q.coef = s.bn() ? s.coef() : nullptr; q.width = b.W;
+    q.in[0] = {s.HF(s.w.S[l]), in.ldS}; q.in[1] = {in.x, in.ldx}; q.k_in = b.K; q.w = b.w; q.dw = b.dw; q.db = b.dbias;
+    q.dout[0].ld = q.dout[1].ld = b.K;
+    q.act_bf16 = s.storage;
+    q.in_bf16 = r.one_piece ? 1 : 0;
+    if (l > 0) { q.dout[0].rows = s.dS(); q.dout[1].rows = s.dX(); q.psums = (s.sym && s.bn()) ? s.acc2 : nullptr; }
+    rc = fused_conv_bwd(q, s.st);
+  }
+  *done = rc == GCMI_OK;
+  if (*done && r.one_piece) g_one_piece_launches.fetch_add(1, std::memory_order_relaxed);
+  if (rc != GCMI_ERR_UNSUPPORTED) return rc;
+  if (s.storage != 0) {
+    set_error("bf16 activation storage: GraphConv %d has no one-pass backward", l);
+    return rc;
+  }
+  if (s.sy) return refuse_second_sync("the one-pass GraphConv block");
+  return bn_relu_backward_rows(s, l, true, nullptr);
+}
+
+// After the one pass dX holds the self part: the neighbour part is added onto it (bonds listed from both ends: the
+// scatter of dS is a gather), and on the two-stage route the GraphPool backward of the block below runs in the same
+// pass -- dX = dXs + gather(dS) is consumed in LDS and never exists in HBM (*dy_ready: that block's dy is in place)
+static int neighbour_part(const Step& s, int l, const BlockRoute& r, bool* dy_ready) {
+  const gcmi_graph* g = s.g;
+  const int K = s.blk[l].K;
+  float *dS = s.dS(), *dX = s.dX();
+  *dy_ready = r.two_stage;
+  if (r.two_stage) {
+    TimedScope ts(GCMI_K_GATHER_MAX_BWD, s.st);
+    if (s.storage == 2) return win_gather_sumacc_max_bwd_h(g, s.HG(dS), K, K, s.HG(dX), K, s.arg(l - 1), s.HG(s.dy()), K, s.st);
+    return win_gather_sumacc_max_bwd(g, dS, K, K, dX, K, s.arg(l - 1), s.dy(), K, s.st);
+  }
+  if (s.storage == 2) {
+    set_error("bf16 gradient streams: no LDS for the two-stage window pass");
+    return GCMI_ERR_UNSUPPORTED;
+  }
+  if (s.sym) return gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 1, s.st);
+  return gcmi_scatter_add(g, dS, K, K, dX, K, s.st);
+}
+
+// Block l as separate launches over dgc in rows: dW_rel += S^T dgc; dW_self += X^T dgc and dbsum; for l > 0
+// dS = dgc . W_rel[d]^T and dX = dgc . W_self[d]^T + (transposed gather of dS)
+static int conv_separate(const Step& s, int l, const Segs& sg, const BlockIn& in) {
+  const gcmi_graph* g = s.g;
+  const Block& b = s.blk[l];
+  const int W = b.W, K = b.K;
+  float *dgc = s.dgc(), *dS = s.dS(), *dX = s.dX();
+  RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, s.ws + s.w.S[l], s.w.ldS[l], K, dgc, W, W, b.dw, sg.w_rel, nullptr, nullptr,
+                          0, s.st));
+  RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, in.x, in.ldx, K, dgc, W, W, b.dw, sg.w_self, b.dbias, sg.b_off, 0, s.st));
+  if (l == 0) return GCMI_OK;  // the atom features need no gradient
+  SegProduct<float> dg = seg_product(sg, (const float*)dgc, W, W, b.w, sg.w_rel, K, dS);
+  dg.trans_w = 1;
+  RUN(seg_gemm(dg, s.st));
+  // bonds listed from both ends: the scatter of dS is a gather (LDS-window kernel), and the self term accumulates
+  // onto it in the GEMM epilogue
+  if (s.sym) RUN(gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 0, s.st));
+  dg.op[0].w_off = sg.w_self;  // dX (+)= dgc . W_self[d]^T
+  dg.act = s.sym ? 2 : 0;
+  dg.out = dX;
+  RUN(seg_gemm(dg, s.st));
+  if (!s.sym) RUN(gcmi_scatter_add(g, dS, K, K, dX, K, s.st));
+  return GCMI_OK;
+}
+
+static int model_loss_backward_f(Step& s) {
+  RUN(begin_backward(s));
+  const bool dense_one_pass = dense_block_one_pass(s.m, s.N);
+  bool head_sums = false;
+  RUN(head_backward(s, dense_one_pass, &head_sums));
+  if (s.N == 0) return s.sy ? empty_backward_syncs(s) : GCMI_OK;
+  bool have_psums = false;  // acc2 holds sum dP, sum dP * P for the BatchNorm below the block just processed
+  bool dy_ready = false;    // the two-stage pass of the block above already left this block's dy
+  RUN(dense_block_backward(s, dense_one_pass, head_sums, &have_psums));
+  for (int l = s.L - 1; l >= 0; --l) {
+    if (!s.full && !s.bn()) break;  // nothing trainable in front of the dense layer
+    const Block& b = s.blk[l];
+    const Segs sg = make_segs(s.g, b.K, b.W);
+    const BlockIn in = block_in(s, l);
+    const BlockRoute r = block_route(s, l, in, have_psums);
+    RUN(pool_bn_backward(s, l, r, dy_ready));
+    have_psums = dy_ready = false;
+    if (!s.full) break;  // reference semantics: nothing in front of a GraphConv output trains
+    bool one_pass_done = false;
+    if (r.one_pass) RUN(conv_one_pass(s, l, sg, in, r, &one_pass_done));
+    if (!one_pass_done && r.one_piece) {  // (the one-pass backward was switched off between the forward and this call)
+      set_error("model_loss_backward: the forward left the first block's operands as bf16 rows, and the one-pass "
+                "backward that reads them is not available now (GCMI_OPT_FUSED_BWD / GCMI_OPT_GEMM_EXACT changed?)");
+      return GCMI_ERR_UNSUPPORTED;
+    }
+    if (!one_pass_done) RUN(conv_separate(s, l, sg, in));
+    else if (l > 0) RUN(neighbour_part(s, l, r, &dy_ready));
+    have_psums = one_pass_done && l > 0 && s.sym && s.bn();
+    s.ub.src[l] = b.dbias; s.ub.dst[l] = b.dbias_rows; s.ub.width[l] = b.W;  // unpacked in one launch below
+  }
+  return unpack_bias_grads(s);
+}
+
+// bf16 storage: the same walk; what its kernels do not cover is refused up front
+static int model_loss_backward_h(Step& s) {
+  RUN(require_h(s.m, s.g, s.io, true));
+  return model_loss_backward_f(s);
 }
 
 }  // namespace gcmi
@@ -824,6 +1084,7 @@ int64_t gcmi_model_workspace_floats(const gcmi_model_desc* m, int64_t n_atoms, i
   return carve(m, n_atoms, n_mols, up4(m->n_feat_in)).total;
 }
 
+
 int gcmi_model_forward(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params,
                        const gcmi_model_io* io, int32_t training, void* stream) {
   return gcmi_model_forward_dp(m, g, d_params, io, training, nullptr, nullptr, stream);
@@ -842,78 +1103,9 @@ int gcmi_model_forward_dp(const gcmi_model_desc* m, const gcmi_graph* g, const f
   GCMI_CHECK_ARG(g->n_atoms == 0 || io->d_atom_features, "model_forward: NULL atom features");
   GCMI_CHECK_ARG(io->ld_features >= m->n_feat_in, "ld_features < n_feat_in");
   if (sync && training) RUN(check_sync_buffers(m, g, io));
-  if (m->storage >= 1) return model_forward_h(m, g, d_params, io, training, sync, sync_ctx, stream);
-  hipStream_t st = (hipStream_t)stream;
-  const int L = m->n_layers;
-  const int64_t N = g->n_atoms, B = g->n_mols;
-  const Ws w = carve(m, N, B, io->ld_features);
-  float* ws = io->d_workspace;
-  Block blk[kMaxL + 1];
-  make_blocks(m, w, ws, d_params, nullptr, io, blk);
-  const float* x = io->d_atom_features;
-  int64_t ldx = io->ld_features;
-  if (training && m->batch_norm && N > 0 &&
-      hipMemsetAsync(ws + w.acc, 0, sizeof(float) * (size_t)(w.z_end - w.acc), st) != hipSuccess) {
-    set_error("model_forward: memset failed");
-    return GCMI_ERR_LAUNCH;
-  }
-  // training with BatchNorm: a product's epilogue also adds the column sums of its output into the BatchNorm
-  // accumulators (clean: zeroed above, self-cleaning afterwards), so the layer output is not read again
-  double* acc = reinterpret_cast<double*>(ws + w.acc);
-  double* stats = (m->batch_norm && training) ? acc : nullptr;
-  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
-  const BnSync* sy = (sync && training) ? &sync_s : nullptr;
-  bool stats_fused = false;
-  const bool one_piece = one_piece_block0(m, g, io);
-  note_one_piece(ws, one_piece);
-  RUN(pack_biases(m, w, ws, d_params, st));
-  for (int l = 0; l < L; ++l) {
-    const Block& b = blk[l];
-    const int W = b.W;
-    const Segs sg = make_segs(g, b.K, W);
-    stats_fused = false;
-    if (l == 0 && one_piece) {
-      RUN(one_piece_forward(g, w, ws, b, sg, io, stats, st));
-      stats_fused = training != 0;
-    } else if (N > 0) {
-      // (l > 0: the GraphPool of the block below left the neighbour sums of its output with it)
-      if (l == 0) RUN(gcmi_gather_sum_fwd(g, x, ldx, (int32_t)w.ngather[l], ws + w.S[l], w.ldS[l], 0, stream));
-      RUN(seg_gemm_stats(conv_product(sg, ws + w.S[l], w.ldS[l], x, ldx, b, ws + w.gc[l]), stats, &stats_fused, st,
-                         ws + w.wimg));
-    }
-    const bool bn = m->batch_norm && N > 0;
-    if (bn || sy) RUN(bn_forward(b, N, training, stats_fused, ws + w.gc[l], W, acc, stream, sy));
-    if (N > 0) {
-      uint8_t* arg = training ? reinterpret_cast<uint8_t*>(ws + w.arg[l]) : nullptr;
-      const float* sc = bn ? b.bn.scale : nullptr;
-      const float* sh = bn ? b.bn.shift : nullptr;
-      if (l + 1 < L)  // GraphPool and the neighbour sums of the block above in one window pass
-        RUN(gcmi_gather_max_sum_fwd(g, ws + w.gc[l], W, W, sc, sh, ws + w.pool[l], W, arg, ws + w.S[l + 1], w.ldS[l + 1], stream));
-      else
-        RUN(gcmi_gather_max_fwd(g, ws + w.gc[l], W, W, sc, sh, ws + w.pool[l], W, arg, stream));
-    }
-    x = ws + w.pool[l];
-    ldx = W;
-  }
-  const Block& dn = blk[L];
-  const int D = dn.W;
-  if (N > 0) {
-    const int32_t nN = (int32_t)N;
-    SegProduct<float> p = one_segment(&nN, x, ldx, dn.K, dn.w, dn.bias, D, ws + w.dense, D);
-    p.trans_w = 1;
-    p.act = 1;
-    RUN(seg_gemm_stats(p, stats, &stats_fused, st));
-  }
-  const bool bn = m->batch_norm && N > 0;
-  if (bn || sy) RUN(bn_forward(dn, N, training, stats_fused, ws + w.dense, D, acc, stream, sy));
-  RUN(readout_fwd_impl(g, ws + w.dense, D, D, bn ? dn.bn.scale : nullptr, bn ? dn.bn.shift : nullptr, 1, io->d_fingerprint,
-                       2 * D, reinterpret_cast<int32_t*>(ws + w.arg_r),
-                       (training && m->batch_norm) ? ws + w.rsum : nullptr, stream));
-  RUN(head_forward(m, w, ws, d_params, io, B, stream));
-  if (m->mode == 0 && io->d_probs)
-    RUN(gcmi_softmax(io->d_logits, B * m->n_tasks, m->n_classes, io->d_probs, stream));
-  if (training && m->batch_norm && N == 0 && !sy) RUN(bump_counters(m, io, st));  // (sy: every exchange's finalisation did)
-  return GCMI_OK;
+  Step s;
+  make_step(s, m, g, d_params, nullptr, io, sync, sync_ctx, sync && training, stream);
+  return m->storage >= 1 ? model_forward_h(s, training) : model_forward_f(s, training);
 }
 
 int gcmi_model_loss_backward(const gcmi_model_desc* m, const gcmi_graph* g, const float* d_params,
@@ -938,225 +1130,10 @@ int gcmi_model_loss_backward_dp(const gcmi_model_desc* m, const gcmi_graph* g, c
   GCMI_CHECK_ARG(n_rows > 0 && n_rows <= g->n_mols, "n_rows %lld outside (0, n_mols=%d]", (long long)n_rows,
                  g->n_mols);
   if (sync) RUN(check_sync_buffers(m, g, io));
-  if (m->storage >= 1)
-    return model_loss_backward_h(m, g, d_params, d_grads, io, d_labels, d_weights, n_rows, grad_lo, grad_hi, sync,
-                                 sync_ctx, stream);
-  hipStream_t st = (hipStream_t)stream;
-  const int L = m->n_layers;
-  const int64_t N = g->n_atoms, B = g->n_mols;
-  const Ws w = carve(m, N, B, io->ld_features);
-  float* ws = io->d_workspace;
-  Block blk[kMaxL + 1];
-  make_blocks(m, w, ws, d_params, d_grads, io, blk);
-  const bool full = m->grad_mode == 1;
-  const bool sym = g->d_rev_pos != nullptr || g->n_edges == 0;
-  const int64_t lo = full ? 0 : (m->batch_norm ? m->off_bn_gamma[L - 1] : m->off_dense_w);
-  const int64_t hi = m->n_params;
-  if (grad_lo) *grad_lo = lo;
-  if (grad_hi) *grad_hi = hi;
-  auto zero = [&](void* p, size_t bytes) -> int {
-    if (bytes && hipMemsetAsync(p, 0, bytes, st) != hipSuccess) {
-      set_error("model_loss_backward: memset failed");
-      return GCMI_ERR_LAUNCH;
-    }
-    return GCMI_OK;
-  };
-  RUN(zero(d_grads + lo, sizeof(float) * (size_t)(hi - lo)));
-  // dlogits (rows beyond n_rows carry no gradient), the bias-gradient sums and every accumulator
-  RUN(zero(ws + w.dlogits, sizeof(float) * (size_t)(w.z_end - w.dlogits)));
-  double* acc = reinterpret_cast<double*>(ws + w.acc);
-  double* acc2 = reinterpret_cast<double*>(ws + w.acc2);
-  double* lacc = reinterpret_cast<double*>(ws + w.lacc);
-  const float loss_inv_count = 1.f / (float)(n_rows * m->n_tasks);
-  const BnSync sync_s = make_sync(sync, sync_ctx, w, ws);
-  const BnSync* sy = sync ? &sync_s : nullptr;
-  const Block& dn = blk[L];
-  const int D = dn.W, Wl = dn.K;
-  const int32_t nN = (int32_t)N;
-  // ---- per-molecule part in one kernel where the shapes allow (head_bwd.hip): loss, d logits, head gradients, the
-  // gradient w.r.t. GraphGather's pre-activation (tanh derivative applied), and -- when the one-pass dense block
-  // follows -- the BatchNorm backward sums of the dense layer
-  const bool dense_one_pass = dense_block_one_pass(m, N);
-  const ReadoutGrad rg = readout_grad(g, w, ws, D);
-  bool head_done = false, head_sums = false;
-  if (m->batch_norm)  // (without BatchNorm the readout backward applies the tanh derivative itself)
-    RUN(head_backward_fused(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, rg, dn.bn,
-                            (dense_one_pass && g->d_mol_runs) ? acc : nullptr, stream, &head_done, &head_sums));
-  // (the tanh derivative applied in place only for the BatchNorm backward below)
-  if (!head_done)
-    RUN(head_backward_separate(m, w, ws, d_params, d_grads, io, d_labels, d_weights, n_rows, B, m->batch_norm && N > 0,
-                               stream));
-  if (N == 0) return sy ? empty_backward_syncs(m, blk, *sy, stream) : GCMI_OK;
-  // ---- readout (+ folded BatchNorm of the dense layer, + its ReLU mask)
-  float* dyD = ws + w.tA;   // grad w.r.t. the (normalised) readout input
-  float* dxD = ws + w.tB;   // grad w.r.t. the dense pre-activation
-  float* dpool = ws + w.tC;  // grad w.r.t. the output of the last GraphPool
-  const float* coef = ws + w.acc;  // [A | B | C] of the BatchNorm backward just computed (bn.hip: head of its scratch)
-  const int32_t* arg_r = reinterpret_cast<const int32_t*>(ws + w.arg_r);
-  bool dense_done = false;
-  bool have_psums = false;  // acc2 holds sum dP, sum dP * P for the BatchNorm below the block just processed
-  bool dy_ready = false;  // the gather of the block above already left this block's dy (two-stage window pass)
-  if (m->batch_norm) {
-    // GraphGather backward is recomputed inside the BatchNorm backward from the per-molecule
-    // gradient (tanh derivative applied in place): the N x D gradient is never written or re-read
-    auto readout_bn_bwd = [&](float* dx, const BnSync* s) {
-      BnBackward q = bn_backward(ws + w.dense, D, N, acc, s);
-      q.rg = &rg; q.dx = dx; q.lddx = D; q.relu_mask = 1;
-      return bn_bwd_impl(dn.bn, q, stream);
-    };
-    if (head_sums) {
-      // the sums are in place (head_bwd.hip): dgamma, dbeta and the coefficient vectors
-      BnBackward q = bn_backward(ws + w.dense, D, N, acc, sy);
-      q.loss = {lacc, kLossRep, loss_inv_count, io->d_loss};
-      RUN(bn_bwd_params_impl(dn.bn, q, stream));
-    } else {
-      RUN(readout_bn_bwd(dense_one_pass ? nullptr : dxD, sy));
-    }
-    if (dense_one_pass) {
-      // one pass: dxD formed per 64-row tile in LDS, dW_dense += dxD^T pool, db += colsum, dpool = dxD W_dense
-      TimedScope ts(GCMI_K_FUSED_BWD, st);
-      const int rc = fused_dense_bwd(dense_backward(&nN, rg, ws + w.dense, coef, ws + w.pool[L - 1], dn, dpool, acc2), st);
-      if (rc == GCMI_OK) {
-        dense_done = true;
-        have_psums = true;
-      }
-      else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
-      else if (sy) return refuse_second_sync("the one-pass dense block");
-      else  // not covered after all (misaligned buffers): the separate pass, with its sums once more
-        RUN(readout_bn_bwd(dxD, nullptr));
-    }
-  } else {
-    RUN(gcmi_readout_bwd(g, ws + w.dfp, 2 * D, io->d_fingerprint, 2 * D, D, 1, arg_r, dyD, D, stream));
-    RUN(gcmi_relu_bwd(dyD, D, ws + w.dense, D, N, D, stream));
-    dxD = dyD;
-  }
-  // ---- dense layer
-  if (!dense_done) {
-    RUN(gcmi_seg_gemm_wgrad(1, &kZero32, &nN, ws + w.pool[L - 1], Wl, Wl, dxD, D, D, dn.dw, &kZero64, dn.dbias, &kZero64,
-                            1, stream));
-    RUN(seg_gemm(one_segment(&nN, dxD, D, D, dn.w, nullptr, Wl, dpool, Wl), st));
-  }
-  // ---- GraphConv / BatchNorm / GraphPool blocks, last to first
-  BiasLayers ub;
-  memset(&ub, 0, sizeof(ub));
-  for (int l = L - 1; l >= 0; --l) {
-    if (!full && !m->batch_norm) break;  // nothing trainable in front of the dense layer
-    const Block& b = blk[l];
-    const int W = b.W, K = b.K;
-    float* dy = ws + w.tD;  // grad w.r.t. the (normalised) pool input
-    float* dgc = ws + w.tA;  // grad w.r.t. the GraphConv pre-activation
-    const Segs sg = make_segs(g, K, W);
-    // (one-piece form of the first block: S0 and the copy Xb of the atom features are bf16 rows, as the forward left them)
-    const bool one_piece = l == 0 && noted_one_piece(ws);
-    const float* xin = one_piece ? ws + w.xb : l == 0 ? io->d_atom_features : ws + w.pool[l - 1];
-    const int64_t ldx = one_piece ? kOnePieceLd : l == 0 ? io->ld_features : m->conv_width[l - 1];
-    const int64_t ldS = one_piece ? kOnePieceLd : w.ldS[l];
-    float* dS = ws + w.tE;
-    float* dX = ws + w.tC;
-    const uint8_t* arg = reinterpret_cast<const uint8_t*>(ws + w.arg[l]);
-    // the fused pass covers the default widths in split-bf16 mode; it wants 16-byte rows of every operand
-    const bool try_fused = full && fused_bwd_enabled() && W == 64 && ldx % 4 == 0 && aligned16(xin) &&
-                           ((l == 0 && K > 32 && K <= 96) || (l > 0 && K > 32 && K <= 64));
-    // GraphPool backward
-    if (!sym) RUN(zero(dy, sizeof(float) * (size_t)(N * W)));
-    const bool pool_sums = have_psums && m->batch_norm && sym && (try_fused || !full) && win_usable(g, W, true) &&
-                           win_has_width(W);
-    have_psums = false;
-    if (pool_sums) {
-      // The block above left sum dP and sum dP * P: this BatchNorm's backward needs no pass over dy (bn.hip,
-      // bn_bwd_pool_impl).  dy itself is needed when the GraphConv below trains; otherwise only by the
-      // ill-conditioned fallback, and the kernel returns at once unless that applies.
-      if (dy_ready) {
-        // (left by win_gather_sumacc_max_bwd below, one iteration ago)
-      } else if (full) {
-        RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
-      } else {
-        TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-        RUN(win_gather_max_bwd_if_ill(g, dpool, W, W, arg, dy, W, b.bn.gamma, b.bn.beta, st));
-      }
-      BnBackward q = bn_backward(ws + w.gc[l], W, N, acc, sy);
-      q.dy = dy; q.lddy = W; q.psums = acc2;
-      RUN(bn_bwd_pool_impl(b.bn, q, stream));
-    } else {
-      if (!dy_ready) RUN(gcmi_gather_max_bwd(g, dpool, W, W, arg, dy, W, stream));
-      if (m->batch_norm) {
-        RUN(bn_bwd_rows(b, dy, ws + w.gc[l], N, (full && !try_fused) ? dgc : nullptr, acc, sy, stream));
-      } else if (full && !try_fused) {
-        RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
-        dgc = dy;
-      }
-    }
-    dy_ready = false;
-    if (!full) break;  // reference semantics: nothing in front of a GraphConv output trains
-    bool fused_done = false;
-    if (try_fused) {
-      // one pass over the rows: dgc formed per tile in LDS; dW_rel, dW_self, dbsum; and for l > 0 dS = dgc W_rel^T
-      // and the self part of dX
-      TimedScope ts(GCMI_K_FUSED_BWD, st);
-      BlockBackward q = conv_backward(sg, dy, ws + w.gc[l], m->batch_norm ? coef : nullptr, b, ws + w.S[l], ldS, xin, ldx);
-      q.in_bf16 = one_piece ? 1 : 0;
-      if (l > 0) { q.dout[0].rows = dS; q.dout[1].rows = dX; q.psums = (sym && m->batch_norm) ? acc2 : nullptr; }
-      const int rc = fused_conv_bwd(q, st);
-      if (rc == GCMI_OK) {
-        fused_done = true;
-        have_psums = l > 0 && sym && m->batch_norm;
-        if (one_piece) g_one_piece_launches.fetch_add(1, std::memory_order_relaxed);
-      }
-      else if (rc != GCMI_ERR_UNSUPPORTED) return rc;
-      else if (sy) return refuse_second_sync("the one-pass GraphConv block");
-      else if (m->batch_norm) {  // not covered after all (misaligned buffers): the separate pass, sums once more
-        RUN(bn_bwd_rows(b, dy, ws + w.gc[l], N, dgc, acc, nullptr, stream));
-      } else {
-        RUN(gcmi_relu_bwd(dy, W, ws + w.gc[l], W, N, W, stream));
-        dgc = dy;
-      }
-    }
-    if (!fused_done && one_piece) {  // (the one-pass backward was switched off between the forward and this call)
-      set_error("model_loss_backward: the forward left the first block's operands as bf16 rows, and the one-pass "
-                "backward that reads them is not available now (GCMI_OPT_FUSED_BWD / GCMI_OPT_GEMM_EXACT changed?)");
-      return GCMI_ERR_UNSUPPORTED;
-    }
-    if (!fused_done) {
-      RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, ws + w.S[l], w.ldS[l], K, dgc, W, W, b.dw, sg.w_rel, nullptr,
-                              nullptr, 0, stream));
-      RUN(gcmi_seg_gemm_wgrad(sg.n, sg.begin, sg.end, xin, ldx, K, dgc, W, W, b.dw, sg.w_self, b.dbias, sg.b_off, 0,
-                              stream));
-    }
-    note_bias_grads(ub, l, b);
-    if (l == 0) break;  // the atom features need no gradient
-    // dS = dgc . W_rel^T ; dX = dgc . W_self^T + (transposed gather of dS)
-    if (fused_done) {
-      // dX holds the self part: the neighbour part is added onto it (bonds listed from both ends: the scatter
-      // of dS is a gather)
-      // ... and when the window kernels can hold a third tile, the GraphPool backward of the block below in the
-      // same pass: dX = dXs + gather(dS) is consumed in LDS and never exists in HBM
-      const bool two_stage = sym && fused_bwd_enabled() && win_two_stage_usable(g, K) &&
-                             aligned16(dS) && aligned16(dX) && aligned16(ws + w.tD);
-      if (two_stage) {
-        TimedScope ts(GCMI_K_GATHER_MAX_BWD, st);
-        RUN(win_gather_sumacc_max_bwd(g, dS, K, K, dX, K, reinterpret_cast<const uint8_t*>(ws + w.arg[l - 1]),
-                                      ws + w.tD, K, st));
-        dy_ready = true;
-      } else if (sym) RUN(gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 1, stream));
-      else RUN(gcmi_scatter_add(g, dS, K, K, dX, K, stream));
-    } else {
-      // dS = dgc . W_rel[d]^T
-      SegProduct<float> dg = seg_product(sg, dgc, W, W, b.w, sg.w_rel, K, dS);
-      dg.trans_w = 1;
-      RUN(seg_gemm(dg, st));
-      // bonds listed from both ends: the scatter of dS is a gather (LDS-window kernel), and the
-      // self term accumulates onto it in the GEMM epilogue
-      if (sym) RUN(gcmi_gather_sum_fwd(g, dS, K, K, dX, K, 0, stream));
-      dg.op[0].w_off = sg.w_self;  // dX (+)= dgc . W_self[d]^T
-      dg.act = sym ? 2 : 0;
-      dg.out = dX;
-      RUN(seg_gemm(dg, st));
-      if (!sym) RUN(gcmi_scatter_add(g, dS, K, K, dX, K, stream));
-    }
-    dpool = dX;
-  }
-  RUN(unpack_bias_grads(m, ub, L, st));
-  return GCMI_OK;
+  Step s;
+  make_step(s, m, g, d_params, d_grads, io, sync, sync_ctx, sync != nullptr, stream);
+  s.d_labels = d_labels; s.d_weights = d_weights; s.n_rows = n_rows; s.grad_lo = grad_lo; s.grad_hi = grad_hi;
+  return m->storage >= 1 ? model_loss_backward_h(s) : model_loss_backward_f(s);
 }
 
 }  // extern "C"
