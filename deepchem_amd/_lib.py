@@ -187,6 +187,14 @@ _SIGNATURES = {
                       _P, _I64P, _P, _I64P, c_int32, c_int32, c_int32, _P, c_int64, _P],
     "gcmi_seg_gemm_wgrad": [c_int32, _I32P, _I32P, _P, c_int64, c_int32, _P, c_int64, c_int32, _P,
                             _I64P, _P, _I64P, c_int32, _P],
+    "gcmi_fwd_fused_gemm": [c_int32, _I32P, _I32P, _P, c_int64, c_int32, _P, _I64P, _P, c_int64, c_int32,
+                            _P, _I64P, _P, _I64P, c_int32, c_int32, c_int32, _P, c_int64, _P, _P, _P],
+    "gcmi_fwd_fused_gemm_h": [c_int32, _I32P, _I32P, _P, c_int64, c_int32, _P, _I64P, _P, c_int64, c_int32,
+                              _P, _I64P, _P, _I64P, c_int32, c_int32, c_int32, _P, c_int64, c_int32, _P, _P, _P],
+    "gcmi_fused_conv_bwd": [c_int32, _I32P, _I32P, _I64P, _I64P, _I64P, _P, c_int64, _P, c_int64, _P, _P, c_int64,
+                            _P, c_int64, c_int32, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int32, c_int32, _P],
+    "gcmi_fused_dense_bwd": [c_int32, _I32P, _I32P, _I64P, _I64P, _P, _P, c_int64, _P, c_int32, _P, c_int64, _P,
+                             _P, c_int64, c_int32, _P, _P, _P, _P, c_int64, _P, c_int32, _P],
     "gcmi_task_head_forward": [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, _P, _P, c_int64, _P],
     "gcmi_relu_bwd": [_P, c_int64, _P, c_int64, c_int64, c_int32, _P],
     "gcmi_loss_fwd_bwd": [c_int32, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P],
@@ -247,7 +255,7 @@ _SIGNATURES = {
 }
 
 EXPORTS = ["gcmi_version", "gcmi_last_error", "gcmi_model_workspace_floats", "gcmi_small_workspace_floats",
-           "gcmi_task_head_scratch_floats", "gcmi_lamb_scratch_floats", "gcmi_metrics_workspace_bytes",
+           "gcmi_task_head_scratch_floats", "gcmi_fwd_fused_scratch_floats", "gcmi_lamb_scratch_floats", "gcmi_metrics_workspace_bytes",
            "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout"] + sorted(_SIGNATURES)
 
 _lib = None
@@ -291,6 +299,7 @@ def load():
         "gcmi_smiles_check": (c_char_p, [c_char_p]),
         "gcmi_collate_plan_words": (c_int64, [c_int64]),
         "gcmi_task_head_scratch_floats": (c_int64, []),
+        "gcmi_fwd_fused_scratch_floats": (c_int64, []),
         "gcmi_lamb_scratch_floats": (c_int64, [c_int64, c_int64]),
         "gcmi_metrics_workspace_bytes": (c_int64, [c_int64, c_int32]),
     }

@@ -809,3 +809,89 @@ int fused_dense_bwd(const BlockBackward& b, hipStream_t sm) {
 }
 
 }  // namespace gcmi
+
+using namespace gcmi;
+
+// The one-pass backward kernels alone: the argument checks, the BlockBackward description, the launcher -- and no
+// separate kernels behind a refusal.
+static int check_block_backward(const BlockBackward& b, const char* who, bool dense) {
+  GCMI_CHECK_ARG(b.n_seg >= 1 && b.n_seg <= kMaxProductSeg, "%s: n_seg %d outside [1,%d]", who, b.n_seg, kMaxProductSeg);
+  GCMI_CHECK_ARG(b.seg_begin && b.seg_end && b.w_off[0] && (dense || b.w_off[1]), "%s: NULL segment table", who);
+  for (int s = 0; s < b.n_seg; ++s)
+    GCMI_CHECK_ARG(b.seg_end[s] >= b.seg_begin[s] && b.seg_begin[s] >= 0, "%s: bad segment %d", who, s);
+  GCMI_CHECK_ARG(b.act_bf16 >= 0 && b.act_bf16 <= 2 && (b.in_bf16 == 0 || b.in_bf16 == 1), "%s: bad storage flags", who);
+  GCMI_CHECK_ARG(b.gc && b.in[0].rows && (dense || b.in[1].rows) && b.w && b.dw && (dense || b.dy), "%s: NULL buffer", who);
+  GCMI_CHECK_ARG(b.db == nullptr || b.b_off != nullptr, "%s: db without offsets", who);
+  GCMI_CHECK_ARG(b.k_in > 0 && b.in[0].ld >= b.k_in && (dense || b.in[1].ld >= b.k_in), "%s: ld < k_in in the input rows",
+                 who);
+  // (fp32 input rows are read as 16-byte pieces; the launchers look at this for bf16 rows only)
+  GCMI_CHECK_ARG(b.act_bf16 || b.in_bf16 || (aligned16(b.in[0].rows) && b.in[0].ld % 4 == 0 &&
+                                              (dense || (aligned16(b.in[1].rows) && b.in[1].ld % 4 == 0))),
+                 "%s: float input rows must be 16-byte aligned with ld %% 4 == 0", who);
+  GCMI_CHECK_ARG(b.ldgc >= b.width && (dense || b.lddy >= b.width), "%s: ld < %d in the rows of dy / gc", who, b.width);
+  GCMI_CHECK_ARG(dense || (b.dout[0].rows == nullptr) == (b.dout[1].rows == nullptr), "%s: both input gradients or neither",
+                 who);
+  GCMI_CHECK_ARG(!dense || b.dout[0].rows != nullptr, "%s: NULL input gradient", who);
+  GCMI_CHECK_ARG(b.dout[0].rows == nullptr || (b.dout[0].ld >= b.k_in && (dense || b.dout[1].ld >= b.k_in)),
+                 "%s: ld < k_in in the input-gradient rows", who);
+  GCMI_CHECK_ARG(b.psums == nullptr || b.dout[0].rows != nullptr, "%s: psums without input gradients", who);
+  if (dense) {
+    const ReadoutGrad& rg = *b.rg;
+    GCMI_CHECK_ARG(rg.membership && rg.g2 && rg.arg, "%s: NULL readout gradient", who);
+    GCMI_CHECK_ARG(rg.n_mols > 0 && rg.ldg2 >= 2 * (int64_t)b.width, "%s: ldg2 < 2 x %d or no molecules", who, b.width);
+  }
+  return GCMI_OK;
+}
+
+extern "C" {
+
+int gcmi_fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_rel_off,
+                        const int64_t* w_self_off, const int64_t* b_off, const void* d_dy, int64_t lddy,
+                        const void* d_gc, int64_t ldgc, const float* d_coef, const void* d_s, int64_t lds,
+                        const void* d_x, int64_t ldx, int32_t k_in, const float* d_w, float* d_dw, float* d_db,
+                        void* d_ds, int64_t ldds, void* d_dxs, int64_t lddxs, double* d_psums, int32_t act_bf16,
+                        int32_t in_bf16, void* stream) {
+  BlockBackward b;
+  b.n_seg = n_seg; b.seg_begin = seg_begin; b.seg_end = seg_end;
+  b.w_off[0] = w_rel_off; b.w_off[1] = w_self_off; b.b_off = b_off;
+  b.dy = static_cast<const float*>(d_dy); b.lddy = lddy;
+  b.gc = static_cast<const float*>(d_gc); b.ldgc = ldgc; b.coef = d_coef; b.width = 64;
+  b.in[0] = {static_cast<const float*>(d_s), lds}; b.in[1] = {static_cast<const float*>(d_x), ldx};
+  b.k_in = k_in; b.w = d_w; b.dw = d_dw; b.db = d_db;
+  b.dout[0] = {static_cast<float*>(d_ds), ldds}; b.dout[1] = {static_cast<float*>(d_dxs), lddxs};
+  b.psums = d_psums; b.act_bf16 = act_bf16; b.in_bf16 = in_bf16;
+  const int rc_args = check_block_backward(b, "fused_conv_bwd", false);
+  if (rc_args != GCMI_OK) return rc_args;
+  const int rc = fused_conv_bwd(b, (hipStream_t)stream);
+  if (rc == GCMI_ERR_UNSUPPORTED)
+    set_error("fused_conv_bwd: exact mode, the one-pass kernels switched off, or a shape they do not cover (no other "
+              "kernel stands behind this entry)");
+  return rc;
+}
+
+int gcmi_fused_dense_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_off,
+                         const int64_t* b_off, const int32_t* d_membership, const float* d_g2, int64_t ldg2,
+                         const int32_t* d_arg, int32_t n_mols, const void* d_gc, int64_t ldgc, const float* d_coef,
+                         const void* d_p, int64_t ldp, int32_t k_in, const float* d_w, float* d_dw, float* d_db,
+                         void* d_dp, int64_t lddp, double* d_psums, int32_t act_bf16, void* stream) {
+  ReadoutGrad rg;
+  memset(&rg, 0, sizeof(rg));
+  rg.membership = d_membership; rg.g2 = d_g2; rg.ldg2 = ldg2; rg.arg = d_arg; rg.n_mols = n_mols;
+  BlockBackward b;
+  b.n_seg = n_seg; b.seg_begin = seg_begin; b.seg_end = seg_end;
+  b.w_off[0] = w_off; b.b_off = b_off; b.rg = &rg;
+  b.gc = static_cast<const float*>(d_gc); b.ldgc = ldgc; b.coef = d_coef; b.width = 128;
+  b.in[0] = {static_cast<const float*>(d_p), ldp};
+  b.k_in = k_in; b.w = d_w; b.dw = d_dw; b.db = d_db;
+  b.dout[0] = {static_cast<float*>(d_dp), lddp};
+  b.psums = d_psums; b.act_bf16 = act_bf16;
+  const int rc_args = check_block_backward(b, "fused_dense_bwd", true);
+  if (rc_args != GCMI_OK) return rc_args;
+  const int rc = fused_dense_bwd(b, (hipStream_t)stream);
+  if (rc == GCMI_ERR_UNSUPPORTED)
+    set_error("fused_dense_bwd: exact mode, the one-pass kernels switched off, or a shape they do not cover (no other "
+              "kernel stands behind this entry)");
+  return rc;
+}
+
+}  // extern "C"

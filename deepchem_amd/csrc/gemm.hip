@@ -516,8 +516,9 @@ bool gemm_exact_mode() { return g_gemm_exact.load(std::memory_order_relaxed) != 
 static std::atomic<int> g_fused_bn_stats{getenv("GCMI_GEMM_STATS") && atoi(getenv("GCMI_GEMM_STATS")) == 0 ? 0 : 1};
 
 // the argument checks of gcmi_seg_gemm
-static int check_seg_product(const SegProduct<float>& p) {
-  const SegOperand<float>&a1 = p.op[0], &a2 = p.op[1];
+template <typename TA, typename TO>
+static int check_seg_product(const SegProduct<TA, TO>& p) {
+  const SegOperand<TA>&a1 = p.op[0], &a2 = p.op[1];
   GCMI_CHECK_ARG(p.n_seg >= 1 && p.n_seg <= kMaxProductSeg, "seg_gemm: n_seg %d outside [1,%d]", p.n_seg, kMaxProductSeg);
   GCMI_CHECK_ARG(p.seg_begin && p.seg_end, "seg_gemm: NULL segment table");
   GCMI_CHECK_ARG(p.n_out > 0 && p.ldo >= p.n_out && p.out, "seg_gemm: bad output");
@@ -649,6 +650,60 @@ int gcmi_seg_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_en
   const SegProduct<float> p{n_seg, seg_begin, seg_end, {{d_a1, lda1, k1, d_w1, w1_off}, {d_a2, lda2, k2, d_w2, w2_off}},
                             d_bias, bias_off, n_out, trans_w, act, d_out, ldo};
   return seg_gemm(p, (hipStream_t)stream);
+}
+
+// The persistent forward kernels alone (fwd_fused.hip, fwd_bf16.hip): the checks of gcmi_seg_gemm, the description,
+// the launcher -- and no other kernel behind a refusal.
+int64_t gcmi_fwd_fused_scratch_floats(void) { return kFwdHWimgFloats; }
+
+int gcmi_fwd_fused_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end,
+                        const float* d_a1, int64_t lda1, int32_t k1, const float* d_w1,
+                        const int64_t* w1_off, const float* d_a2, int64_t lda2, int32_t k2,
+                        const float* d_w2, const int64_t* w2_off, const float* d_bias,
+                        const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act,
+                        float* d_out, int64_t ldo, double* d_stats, float* d_wimg_scratch, void* stream) {
+  const SegProduct<float> p{n_seg, seg_begin, seg_end, {{d_a1, lda1, k1, d_w1, w1_off}, {d_a2, lda2, k2, d_w2, w2_off}},
+                            d_bias, bias_off, n_out, trans_w, act, d_out, ldo};
+  const int rc_args = check_seg_product(p);
+  if (rc_args != GCMI_OK) return rc_args;
+  GCMI_CHECK_ARG(d_wimg_scratch == nullptr || aligned16(d_wimg_scratch), "fwd_fused_gemm: the scratch must be 16-byte aligned");
+  const int rc = fwd_fused_gemm(p, d_stats, (hipStream_t)stream, d_wimg_scratch);
+  if (rc == GCMI_ERR_UNSUPPORTED)
+    set_error("fwd_fused_gemm: exact mode, the one-pass kernels switched off, or a shape the persistent forward kernels "
+              "do not cover (no other kernel stands behind this entry)");
+  return rc;
+}
+
+int gcmi_fwd_fused_gemm_h(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end,
+                          const uint16_t* d_a1, int64_t lda1, int32_t k1, const float* d_w1,
+                          const int64_t* w1_off, const uint16_t* d_a2, int64_t lda2, int32_t k2,
+                          const float* d_w2, const int64_t* w2_off, const float* d_bias,
+                          const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act,
+                          void* d_out, int64_t ldo, int32_t out_f32, double* d_stats, float* d_wimg_scratch,
+                          void* stream) {
+  GCMI_CHECK_ARG(out_f32 == 0 || out_f32 == 1, "fwd_fused_gemm_h: out_f32 must be 0 (bf16 rows) or 1 (float rows)");
+  GCMI_CHECK_ARG(d_wimg_scratch != nullptr && aligned16(d_wimg_scratch),
+                 "fwd_fused_gemm_h: NULL or misaligned weight-image scratch");
+  int rc;
+  if (out_f32) {
+    const SegProduct<uint16_t, float> p{n_seg, seg_begin, seg_end,
+                                        {{d_a1, lda1, k1, d_w1, w1_off}, {d_a2, lda2, k2, d_w2, w2_off}},
+                                        d_bias, bias_off, n_out, trans_w, act, static_cast<float*>(d_out), ldo};
+    const int rc_args = check_seg_product(p);
+    if (rc_args != GCMI_OK) return rc_args;
+    rc = fwd_h_gemm(p, d_stats, d_wimg_scratch, (hipStream_t)stream);
+  } else {
+    const SegProduct<uint16_t, uint16_t> p{n_seg, seg_begin, seg_end,
+                                           {{d_a1, lda1, k1, d_w1, w1_off}, {d_a2, lda2, k2, d_w2, w2_off}},
+                                           d_bias, bias_off, n_out, trans_w, act, static_cast<uint16_t*>(d_out), ldo};
+    const int rc_args = check_seg_product(p);
+    if (rc_args != GCMI_OK) return rc_args;
+    rc = fwd_h_gemm(p, d_stats, d_wimg_scratch, (hipStream_t)stream);
+  }
+  if (rc == GCMI_ERR_UNSUPPORTED)
+    set_error("fwd_fused_gemm_h: exact mode, or a shape the bf16-row forward kernel does not cover (no other kernel "
+              "stands behind this entry)");
+  return rc;
 }
 
 int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end,

@@ -409,6 +409,139 @@ def task_head_scratch_floats() -> int:
     return int(_lib.load().gcmi_task_head_scratch_floats())
 
 
+# ---- the persistent block kernels alone (gcmi_fwd_fused_gemm*, gcmi_fused_*_bwd): no other kernel behind a refusal,
+# which raises GcmiError with status -3
+def fwd_fused_scratch_floats() -> int:
+    return int(_lib.load().gcmi_fwd_fused_scratch_floats())
+
+
+def _flat(t, name, dtype=torch.float32):
+    if t is None or t.dtype != dtype or not t.is_cuda or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s CUDA tensor" % (name, dtype))
+    return t
+
+
+def _blocks_inside(off, size, buf, name):
+    for s, o in enumerate(off):
+        if o >= 0 and o + size > buf.numel():
+            raise ValueError("%s block %d runs past the buffer" % (name, s))
+
+
+def _segments_inside(seg_begin, seg_end, n_rows):
+    for s in range(len(seg_begin)):
+        if not (0 <= seg_begin[s] <= seg_end[s] <= n_rows):
+            raise ValueError("segment %d = [%d,%d) outside [0,%d]" % (s, seg_begin[s], seg_end[s], n_rows))
+
+
+def _acc(t, name, n_feat):
+    if t is not None and (t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or
+                          t.numel() < _lib.bn_acc_doubles(n_feat)):
+        raise ValueError("%s must be a contiguous float64 CUDA tensor of >= %d" % (name, _lib.bn_acc_doubles(n_feat)))
+    return t
+
+
+def fwd_fused_gemm(seg_begin, seg_end, a1, w1, w1_off, a2, w2, w2_off, bias, bias_off, n_out: int, trans_w: bool,
+                   relu: bool, n_rows: int, k1: int, k2: int, out: torch.Tensor, stats=None, scratch=None):
+    """gcmi_seg_gemm's contract on the persistent forward kernels alone.  float32 operand rows: gcmi_fwd_fused_gemm;
+    bfloat16 operand rows: gcmi_fwd_fused_gemm_h, ``out`` bfloat16 or float32.  ``stats``: 66 * n_out doubles the
+    column sums of out and out^2 are added into; ``scratch``: fwd_fused_scratch_floats() floats."""
+    _segments_inside(seg_begin, seg_end, n_rows)
+    half = a1.dtype == torch.bfloat16
+    for a, w, off, k, nm in ((a1, w1, w1_off, k1, "a1"), (a2, w2, w2_off, k2, "a2")):
+        if a is None:
+            continue
+        _mat(a, nm, rows=n_rows, cols=k, dtype=a1.dtype)
+        _blocks_inside(off, k * n_out, _flat(w, "weights of " + nm), "weight")
+    if bias is not None:
+        _blocks_inside(bias_off, n_out, _flat(bias, "bias"), "bias")
+    _mat(out, "out", rows=n_rows, cols=n_out, dtype=out.dtype if half else torch.float32)
+    if half and out.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError("out must be bfloat16 or float32")
+    _acc(stats, "stats", n_out)
+    if scratch is not None and (_flat(scratch, "scratch").numel() < fwd_fused_scratch_floats()):
+        raise ValueError("scratch must hold fwd_fused_scratch_floats() floats")
+    head = (len(seg_begin), _i32arr(seg_begin), _i32arr(seg_end),
+            _ptr(a1), _ld(a1), k1, _ptr(w1), _i64arr(w1_off),
+            _ptr(a2), _ld(a2) if a2 is not None else 0, k2, _ptr(w2), _i64arr(w2_off) if a2 is not None else None,
+            _ptr(bias), _i64arr(bias_off) if bias is not None else None, n_out, 1 if trans_w else 0, 1 if relu else 0,
+            _ptr(out), _ld(out))
+    if half:
+        _lib.call("gcmi_fwd_fused_gemm_h", *head, 1 if out.dtype == torch.float32 else 0, _ptr(stats), _ptr(scratch),
+                  _stream())
+    else:
+        _lib.call("gcmi_fwd_fused_gemm", *head, _ptr(stats), _ptr(scratch), _stream())
+    return out
+
+
+def fused_bwd_launches() -> int:
+    v = ctypes.c_int32(0)
+    _lib.call("gcmi_get_option", _lib.GCMI_OPT_FUSED_BWD_LAUNCHES, ctypes.byref(v))
+    return int(v.value)
+
+
+def _rows_dtype(flag):
+    return torch.bfloat16 if flag else torch.float32
+
+
+def fused_conv_bwd(seg_begin, seg_end, w_rel_off, w_self_off, b_off, dy, gc, coef, s, x, w, dw, db, ds=None, dxs=None,
+                   psums=None, act_bf16: int = 0, in_bf16: int = 0):
+    """The one-pass backward of a 64-column GraphConv block (gcmi_fused_conv_bwd): dw / db are added into, ds / dxs
+    written.  act_bf16 1: gc, s, x bfloat16; 2: dy, ds, dxs too; in_bf16: s and x alone."""
+    n = gc.shape[0]
+    k = s.shape[1]
+    _segments_inside(seg_begin, seg_end, n)
+    _mat(dy, "dy", rows=n, cols=64, dtype=_rows_dtype(act_bf16 == 2))
+    _mat(gc, "gc", rows=n, cols=64, dtype=_rows_dtype(act_bf16))
+    _mat(s, "s", rows=n, cols=k, dtype=_rows_dtype(act_bf16 or in_bf16))
+    _mat(x, "x", rows=n, cols=k, dtype=_rows_dtype(act_bf16 or in_bf16))
+    for t, nm in ((ds, "ds"), (dxs, "dxs")):
+        if t is not None:
+            _mat(t, nm, rows=n, cols=k, dtype=_rows_dtype(act_bf16 == 2))
+    _vec(coef, "coef", 192)
+    _flat(w, "w"), _flat(dw, "dw")
+    for off in (w_rel_off, w_self_off):
+        _blocks_inside(off, k * 64, w, "weight")
+        _blocks_inside(off, k * 64, dw, "dw")
+    if db is not None:
+        _blocks_inside(b_off, 64, _flat(db, "db"), "db")
+    _acc(psums, "psums", k)
+    _lib.call("gcmi_fused_conv_bwd", len(seg_begin), _i32arr(seg_begin), _i32arr(seg_end), _i64arr(w_rel_off),
+              _i64arr(w_self_off), _i64arr(b_off) if b_off is not None else None, _ptr(dy), _ld(dy), _ptr(gc), _ld(gc),
+              _ptr(coef), _ptr(s), _ld(s), _ptr(x), _ld(x), k, _ptr(w), _ptr(dw), _ptr(db),
+              _ptr(ds), _ld(ds) if ds is not None else 0, _ptr(dxs), _ld(dxs) if dxs is not None else 0, _ptr(psums),
+              int(act_bf16), int(in_bf16), _stream())
+
+
+def fused_dense_bwd(seg_begin, seg_end, w_off, b_off, membership, g2, arg, gc, coef, p, w, dw, db, dp, psums=None,
+                    act_bf16: int = 0):
+    """The one-pass backward of the 128-column dense block behind the readout (gcmi_fused_dense_bwd): dy is recomputed
+    from g2 = [dsum | dmax] per molecule and arg; dw (128 x k) / db are added into, dp written."""
+    n = gc.shape[0]
+    k = p.shape[1]
+    n_mols = g2.shape[0]
+    _segments_inside(seg_begin, seg_end, n)
+    _mat(g2, "g2", cols=256)
+    if arg.dtype != torch.int32 or not arg.is_cuda or not arg.is_contiguous() or tuple(arg.shape) != (n_mols, 128):
+        raise ValueError("arg must be a contiguous int32 CUDA tensor of shape (%d, 128)" % n_mols)
+    _vec(membership, "membership", n, dtype=torch.int32)
+    if n and not (0 <= int(membership.min()) and int(membership.max()) < n_mols):
+        raise ValueError("membership outside [0, %d)" % n_mols)
+    _mat(gc, "gc", rows=n, cols=128, dtype=_rows_dtype(act_bf16))
+    _mat(p, "p", rows=n, cols=k, dtype=_rows_dtype(act_bf16))
+    _mat(dp, "dp", rows=n, cols=k, dtype=_rows_dtype(act_bf16 == 2))
+    _vec(coef, "coef", 384)
+    _flat(w, "w"), _flat(dw, "dw")
+    _blocks_inside(w_off, k * 128, w, "weight")
+    _blocks_inside(w_off, k * 128, dw, "dw")
+    if db is not None:
+        _blocks_inside(b_off, 128, _flat(db, "db"), "db")
+    _acc(psums, "psums", k)
+    _lib.call("gcmi_fused_dense_bwd", len(seg_begin), _i32arr(seg_begin), _i32arr(seg_end), _i64arr(w_off),
+              _i64arr(b_off) if b_off is not None else None, _ptr(membership), _ptr(g2), _ld(g2), _ptr(arg), n_mols,
+              _ptr(gc), _ld(gc), _ptr(coef), _ptr(p), _ld(p), k, _ptr(w), _ptr(dw), _ptr(db), _ptr(dp), _ld(dp),
+              _ptr(psums), int(act_bf16), _stream())
+
+
 def seg_gemm_wgrad(seg_begin, seg_end, a, g, dw, dw_off, dbias, dbias_off, trans_w: bool):
     """dw (+)= a^T g per segment; dw / dbias are flat, pre-zeroed, accumulated in place."""
     n_seg = len(seg_begin)

@@ -381,6 +381,66 @@ int gcmi_seg_gemm_wgrad(int32_t n_seg, const int32_t* seg_begin, const int32_t* 
                         const float* d_a, int64_t lda, int32_t k, const float* d_g, int64_t ldg,
                         int32_t n, float* d_dw, const int64_t* dw_off, float* d_dbias,
                         const int64_t* dbias_off, int32_t trans_w, void* stream);
+/* ---------------------------------------------------------------- the persistent block kernels, one operation each
+ * The kernels the large-batch model step runs for a GraphConv / dense block (fwd_fused.hip, fwd_bf16.hip,
+ * bwd_fused.hip), callable alone: for tests.  NO other kernel stands behind these: exact mode
+ * (GCMI_OPT_GEMM_EXACT), GCMI_OPT_FUSED_BWD off or a shape outside the ones below give GCMI_ERR_UNSUPPORTED with an
+ * error text, launch nothing and write nothing.  bf16 rows are raw 16-bit patterns, leading dimensions count elements.
+ *
+ * gcmi_fwd_fused_gemm: gcmi_seg_gemm's arguments and contract (act 0 / 1) for
+ *   two operands of 33..64 columns -> 64 outputs (128-row tiles), one operand of 33..64 columns -> 128 outputs in
+ *   nn.Linear layout (trans_w), two operands of 65..80 columns -> 64 outputs (needs d_wimg_scratch:
+ *   gcmi_fwd_fused_scratch_floats() floats, 16-byte aligned); k1 == k2, rows 16-byte aligned with ld % 4 == 0,
+ *   ldo % 4 == 0.  Rows narrower than the kernel's padded width (64 / 80) are fine: columns >= k are masked.
+ *   d_stats (optional): GCMI_BN_ACC_DOUBLES(n_out) doubles; the column sums of out and out^2 are ADDED into its 32
+ *   replicas [2 n_out + r * 2 n_out, ...) as [sum | sum of squares]; the first 2 n_out doubles are not touched.
+ * gcmi_fwd_fused_gemm_h: the same over bf16 operand rows (ld % 8 == 0; columns [k, min(ld, 64 / 80)) must be ZERO; the
+ *   rows of an operand whose weight offset is < 0 in a segment must be finite), bf16 output rows (ldo % 8 == 0) rounded
+ *   once, sums of the rounded values; out_f32 = 1: float output rows and sums of the unrounded values, the 65..80
+ *   column shape only (operands that hold their values exactly).  The scratch is required.
+ * gcmi_fused_conv_bwd: the backward of a GraphConv block of 64 columns in one pass over its rows,
+ *     G = (gc > 0) * (A dy + B gc + C)   ([A | B | C] = d_coef, 3 x 64 floats; NULL: G = (gc > 0) * dy)
+ *     dW_rel[s] += S^T G, dW_self[s] += X^T G (k_in x 64 blocks at d_dw + w_rel_off[s] / w_self_off[s]; the same offsets
+ *     address the weights in d_w), db[s] += column sums of G (d_db + b_off[s]; optional),
+ *     dS = G W_rel[s]^T, dXs = G W_self[s]^T (both or neither; an offset < 0: that term is absent, its input-gradient
+ *     rows are written as zeros).
+ *   d_psums (optional, with the input gradients): GCMI_BN_ACC_DOUBLES(k_in) doubles in the layout above; ADDED per input
+ *   column: sum over the rows of (s * dS + dXs) and of (dS * S + dXs * X), where s is the SEGMENT INDEX of the row --
+ *   the segment is the degree block, and a row of dS is gathered by `degree` neighbours -- so a caller's table must
+ *   list degree d as segment d.  act_bf16 1: gc, S and X are bf16 rows; 2: dy, dS and dXs too (the sums then describe
+ *   the rounded values).  in_bf16 1 (act_bf16 0, no input gradients, 65..96 columns): S and X alone are bf16 rows.
+ *   k_in 33..64 (with input gradients: a multiple of 4), or 65..96 without input gradients.
+ * gcmi_fused_dense_bwd: the dense block (128 columns, nn.Linear layout) behind the readout, one segment from row 0:
+ *     dy[r, f] = g2[mol(r), f] + (arg[mol(r), f] == r) * g2[mol(r), 128 + f]  recomputed from the readout gradient,
+ *     G as above (d_coef required), dW += G^T P (128 x k_in), db += column sums of G, dP = G W; d_psums: sum dP,
+ *     sum dP * P.  k_in 33..64, a multiple of 4.
+ * GCMI_OPT_FUSED_BWD_LAUNCHES counts the launches of the two backward entries.                                       */
+int64_t gcmi_fwd_fused_scratch_floats(void);
+int gcmi_fwd_fused_gemm(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end,
+                        const float* d_a1, int64_t lda1, int32_t k1, const float* d_w1,
+                        const int64_t* w1_off, const float* d_a2, int64_t lda2, int32_t k2,
+                        const float* d_w2, const int64_t* w2_off, const float* d_bias,
+                        const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act,
+                        float* d_out, int64_t ldo, double* d_stats, float* d_wimg_scratch, void* stream);
+int gcmi_fwd_fused_gemm_h(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end,
+                          const uint16_t* d_a1, int64_t lda1, int32_t k1, const float* d_w1,
+                          const int64_t* w1_off, const uint16_t* d_a2, int64_t lda2, int32_t k2,
+                          const float* d_w2, const int64_t* w2_off, const float* d_bias,
+                          const int64_t* bias_off, int32_t n_out, int32_t trans_w, int32_t act,
+                          void* d_out, int64_t ldo, int32_t out_f32, double* d_stats, float* d_wimg_scratch,
+                          void* stream);
+int gcmi_fused_conv_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_rel_off,
+                        const int64_t* w_self_off, const int64_t* b_off, const void* d_dy, int64_t lddy,
+                        const void* d_gc, int64_t ldgc, const float* d_coef, const void* d_s, int64_t lds,
+                        const void* d_x, int64_t ldx, int32_t k_in, const float* d_w, float* d_dw, float* d_db,
+                        void* d_ds, int64_t ldds, void* d_dxs, int64_t lddxs, double* d_psums, int32_t act_bf16,
+                        int32_t in_bf16, void* stream);
+int gcmi_fused_dense_bwd(int32_t n_seg, const int32_t* seg_begin, const int32_t* seg_end, const int64_t* w_off,
+                         const int64_t* b_off, const int32_t* d_membership, const float* d_g2, int64_t ldg2,
+                         const int32_t* d_arg, int32_t n_mols, const void* d_gc, int64_t ldgc, const float* d_coef,
+                         const void* d_p, int64_t ldp, int32_t k_in, const float* d_w, float* d_dw, float* d_db,
+                         void* d_dp, int64_t lddp, double* d_psums, int32_t act_bf16, void* stream);
+
 /* The task head's forward product as the whole-model path runs it (graphconvmodel.py:177-179, :230-236:
  * logits = fingerprint . W^T + b with nn.Linear's (n_out x 256) weight).  With 33..256 outputs -- PCBA: 128 tasks x 2 --
  * the head matrix is first split once into fragment images in d_img_scratch (gcmi_task_head_scratch_floats() floats; the

@@ -562,7 +562,7 @@ def probe_values(rng, shape, pieces):
 def probe_operands(name, rows, k, n_out, seed, nnz=None):
     """(a (rows, k), w (k, n_out)) of one probe.  nnz: only that many columns of every row of a are non-zero (the
     head's 256-column rows keep the contraction at the probe's length that way)."""
-    pa, pw = PROBES[name][:2]
+    pa, pw = (PROBES[name] if name in PROBES else BLOCK_PROBES[name])[:2]
     rng = np.random.default_rng(seed)
     a, w = probe_values(rng, (rows, k), pa), probe_values(rng, (k, n_out), pw)
     if nnz is not None and nnz < k:
@@ -571,3 +571,199 @@ def probe_operands(name, rows, k, n_out, seed, nnz=None):
         np.put_along_axis(mask, keep, True, 1)
         a = np.where(mask, a, np.float32(0.0))
     return a, w
+
+
+# ------------------------------------------------------------------------------------------------ persistent block kernels
+# The forward products of csrc/fwd_fused.hip / csrc/fwd_bf16.hip keep gcmi_seg_gemm's contract (seg_product_ref above) and
+# add the column sums of what they store; the one-pass backward of csrc/bwd_fused.hip is restated here from that file's
+# header.  tests/test_gpu_fused_edges.py compares the kernels with these; tests/test_fused_refs_host.py checks them here.
+BN_REPLICAS = 32  # kBnReplicas: the sums are added into 32 replicas behind 2F unused doubles
+# (piece of a, piece of w) each form multiplies, in the kernels' order (small terms first); a = the left operand of the
+# product AS WRITTEN HERE: dW = In^T . G (a = In^T, w = G), dIn = G . W^T (a = G, w = W^T), out = a . W
+HD_TERMS = ((0, 2), (0, 1), (0, 0))       # fwd_hd_kernel: the stored operand is its own piece x three weight pieces
+HB_DW_TERMS = ((0, 1), (0, 0))            # HB: In one piece x the two leading pieces of G
+HB_DIN_TERMS = ((1, 0), (0, 1), (0, 0))   # HB: g1 w1 + g1 w2 + g2 w1 (pieces counted from 0 here)
+IB_DW_TERMS = ((0, 2), (0, 1), (0, 0))    # IB: In one piece x all three pieces of G
+# two-piece against one-piece probes, by the rule of PROBES: products are multiples of 2^-9.  (A table of their own: the
+# product tests run every entry of PROBES.)
+BLOCK_PROBES = {
+    "a2w1": (2, 1, 96, 2.0 ** -9, ((0, 0), (1, 0))),
+    "a1w2": (1, 2, 96, 2.0 ** -9, ((0, 0), (0, 1))),
+}
+
+
+def probe_spec(name):
+    return PROBES[name] if name in PROBES else BLOCK_PROBES[name]
+
+
+def readout_dy_ref(g2, arg, membership, n_feat):
+    """dy[r, f] = g2[mol(r), f] + (arg[mol(r), f] == r) * g2[mol(r), F + f] in float64; also its magnitude."""
+    g2, m = f64(g2), np.asarray(membership, np.int64)
+    rows = np.arange(m.shape[0])[:, None]
+    hit = np.asarray(arg)[m][:, :n_feat] == rows
+    dy = g2[m, :n_feat] + np.where(hit, g2[m, n_feat:2 * n_feat], 0.0)
+    return dy, np.abs(g2[m, :n_feat]) + np.where(hit, np.abs(g2[m, n_feat:2 * n_feat]), 0.0)
+
+
+def block_bwd_ref(begin, end, w_off, b_off, dy, gc, coef, ins, k_in, w, dw0, db0, width, dense, dy_mag=None):
+    """The header of csrc/bwd_fused.hip in float64.  G = (gc > 0) (A dy + B gc + C) with coef = [A | B | C] (None:
+    (gc > 0) dy); per segment s and operand o (w_off[o][s] >= 0): dW[s][o] += In_o^T G (k_in x width; dense: G^T In,
+    width x k_in), dIn_o = G W_o[s]^T; db[s] += colsum G (b_off[s] >= 0; db0 None: no bias gradient).  An absent term
+    adds nothing to dW and leaves ZEROS in its rows of dIn_o (the kernel writes the tile it owns); rows outside every
+    segment are NaN in dIn.  Returns a dict: G, dw, db, din (list) and the same sums over absolute values S_dw, S_db,
+    S_din, where |G| counts |A dy| + |B gc| + |C| (dy_mag: the magnitude of a recomputed dy)."""
+    dy, gc = f64(dy), f64(gc)
+    n = gc.shape[0]
+    dmag = np.abs(dy) if dy_mag is None else f64(dy_mag)
+    if coef is None:
+        G, Gm = dy.copy(), dmag.copy()
+    else:
+        A, B, C = (f64(coef)[i * width:(i + 1) * width] for i in range(3))
+        G, Gm = A * dy + B * gc + C, np.abs(A) * dmag + np.abs(B * gc) + np.abs(C)
+    G, Gm = np.where(gc > 0, G, 0.0), np.where(gc > 0, Gm, 0.0)
+    dw, S_dw = f64(dw0).copy(), np.abs(f64(dw0))
+    db = None if db0 is None else f64(db0).copy()
+    S_db = None if db0 is None else np.abs(f64(db0))
+    din = [np.full((n, k_in), np.nan) for _ in ins]
+    S_din = [np.zeros((n, k_in)) for _ in ins]
+    wf = f64(w)
+    for s in range(len(begin)):
+        r = slice(begin[s], end[s])
+        if end[s] == begin[s]:
+            continue
+        for o, a in enumerate(ins):
+            din[o][r] = 0.0
+            off = w_off[o][s]
+            if off < 0:
+                continue
+            ar = f64(a)[r, :k_in]
+            p, m = ar.T @ G[r], np.abs(ar).T @ Gm[r]
+            sl = slice(off, off + k_in * width)
+            dw[sl] += (p.T if dense else p).reshape(-1)
+            S_dw[sl] += (m.T if dense else m).reshape(-1)
+            ws = wf[sl].reshape(width, k_in).T if dense else wf[sl].reshape(k_in, width)
+            din[o][r] = G[r] @ ws.T
+            S_din[o][r] = Gm[r] @ np.abs(ws).T
+        if db is not None and b_off[s] >= 0:
+            db[b_off[s]:b_off[s] + width] += G[r].sum(0)
+            S_db[b_off[s]:b_off[s] + width] += Gm[r].sum(0)
+    return dict(G=G, Gmag=Gm, dw=dw, db=db, din=din, S_dw=S_dw, S_db=S_db, S_din=S_din)
+
+
+def g_float32(dy, gc, coef, width):
+    """G formed in float32 numpy: (gc > 0) (A dy + (B gc + C)), two roundings where the kernel's fmaf has one."""
+    f32 = np.float32
+    dy, gc = np.asarray(dy, f32), np.asarray(gc, f32)
+    if coef is None:
+        G = dy.copy()
+    else:
+        A, B, C = (np.asarray(coef, f32)[i * width:(i + 1) * width] for i in range(3))
+        G = (A * dy + (B * gc + C)).astype(f32)
+    return np.where(gc > 0, G, f32(0))
+
+
+def block_bwd_f32(begin, end, w_off, dy, gc, coef, ins, k_in, w, n_w, width, dense, dw_product, din_product):
+    """The same contract with G formed in float32 numpy (two roundings where the kernel fuses) and the products by
+    ``dw_product(In^T, G)`` / ``din_product(G, W^T)`` (seq32_product, or split_product_np with a term subset): dW from
+    zero (no shared blocks) and the dIn list."""
+    f32 = np.float32
+    G = g_float32(dy, gc, coef, width)
+    dw = np.zeros(n_w, f32)
+    din = [np.zeros((G.shape[0], k_in), f32) for _ in ins]
+    for s in range(len(begin)):
+        r = slice(begin[s], end[s])
+        if end[s] == begin[s]:
+            continue
+        for o, a in enumerate(ins):
+            off = w_off[o][s]
+            if off < 0:
+                continue
+            ar = np.asarray(a, f32)[r, :k_in]
+            p = dw_product(np.ascontiguousarray(ar.T), G[r])
+            sl = slice(off, off + k_in * width)
+            dw[sl] += (p.T if dense else p).reshape(-1)
+            ws = np.asarray(w, f32)[sl]
+            ws = ws.reshape(width, k_in).T if dense else ws.reshape(k_in, width)
+            din[o][r] = din_product(G[r], np.ascontiguousarray(ws.T))
+    return dw, din
+
+
+def psums_ref(begin, end, din, ins, k_in, conv):
+    """(2, k_in) float64: conv -- sum over the rows of (s dS + dXs) and of (dS S + dXs X), s = the row's SEGMENT INDEX
+    (the degree); dense -- sum dP and sum dP P.  din: the input gradients AS STORED (rounded under GB)."""
+    out = np.zeros((2, k_in))
+    for s in range(len(begin)):
+        r = slice(begin[s], end[s])
+        for o, (d, a) in enumerate(zip(din, ins)):
+            wgt = float(s) if (conv and o == 0) else 1.0
+            out[0] += wgt * f64(d)[r, :k_in].sum(0)
+            out[1] += (f64(d)[r, :k_in] * f64(a)[r, :k_in]).sum(0)
+    return out
+
+
+def psums_mag(begin, end, din, ins, k_in, conv):
+    out = np.zeros((2, k_in))
+    for s in range(len(begin)):
+        r = slice(begin[s], end[s])
+        for o, (d, a) in enumerate(zip(din, ins)):
+            wgt = float(s) if (conv and o == 0) else 1.0
+            out[0] += wgt * np.abs(f64(d)[r, :k_in]).sum(0)
+            out[1] += np.abs(f64(d)[r, :k_in] * f64(a)[r, :k_in]).sum(0)
+    return out
+
+
+def bn_sums_ref(out_stored, covered):
+    """(2, F) float64: column sums of out and out^2 over the covered rows, of the values as stored."""
+    v = f64(out_stored)[np.asarray(covered, bool)]
+    return np.stack([v.sum(0), (v * v).sum(0)])
+
+
+def read_acc(acc, n_feat, sentinel):
+    """An accumulator in the layout [2F unused][BN_REPLICAS][F | F] that started as: sentinel in the first 2F doubles,
+    zeros in the replicas, sentinel in everything behind them.  Returns the (2, F) sum of the replicas after asserting
+    that both sentinel regions are untouched."""
+    acc = f64(acc).reshape(-1)
+    F2 = 2 * n_feat
+    assert np.all(acc[:F2] == sentinel), "the first 2F doubles of an accumulator were written"
+    assert np.all(acc[F2 * (1 + BN_REPLICAS):] == sentinel), "doubles past the last replica were written"
+    return acc[F2:F2 * (1 + BN_REPLICAS)].reshape(BN_REPLICAS, 2, n_feat).sum(0)
+
+
+def fresh_acc(n_feat, sentinel, pad=64):
+    acc = np.full(2 * n_feat * (1 + BN_REPLICAS) + pad, sentinel, np.float64)
+    acc[2 * n_feat:2 * n_feat * (1 + BN_REPLICAS)] = 0.0
+    return acc
+
+
+def seq32_colsum(values, chunk, weights=None, other=None):
+    """Column sums as a float32 chain over ``chunk`` rows at a time (one rounding per add; with ``other`` the terms are
+    values * other, with ``weights`` weights * values, each rounded once as a fused multiply-add does), the chunks added
+    in float64: the arithmetic of the kernels' periodic flush with one thread per column."""
+    v = np.asarray(values, np.float32).astype(np.float64)
+    if other is not None:
+        v = v * np.asarray(other, np.float32).astype(np.float64)
+    if weights is not None:
+        v = v * np.asarray(weights, np.float64)[:, None]
+    total = np.zeros(v.shape[1])
+    for c0 in range(0, v.shape[0], chunk):
+        acc = np.zeros(v.shape[1], np.float32)
+        for row in v[c0:c0 + chunk]:
+            acc = (acc.astype(np.float64) + row).astype(np.float32)
+        total += acc
+    return total
+
+
+def cancelling_probe(rng, rows, k, n_out, piece):
+    """(a (rows, k), w (k, n_out)) for a kernel that rounds its output to bf16, where a plain probe's sum of up to 96
+    terms would not survive the rounding: a = +-1 in equal adjacent pairs, w in adjacent pairs of opposite sign, so
+    that the leading parts cancel and the result is a small multiple of one power of two, exact in bf16.
+    piece 1: w = +-(1 + p 2^-9), the result is n 2^-9 and sees (0, 1); piece 2: w = +-(1 + 2^-9 + q 2^-17), the result
+    is m 2^-17 and sees (0, 2).  |n|, |m| <= k / 2 <= 48.  Returns (a, w, lsb)."""
+    assert k % 2 == 0 and k <= 96
+    a = np.repeat(rng.choice(np.array([-1.0, 1.0]), (rows, k // 2)), 2, axis=1)
+    s = np.repeat(rng.choice(np.array([-1.0, 1.0]), (k // 2, n_out)), 2, axis=0)
+    s[1::2] *= -1.0
+    bit = rng.integers(0, 2, (k, n_out))
+    if piece == 1:
+        return a.astype(np.float32), (s * (1.0 + bit * 2.0 ** -9)).astype(np.float32), 2.0 ** -9
+    return a.astype(np.float32), (s * (1.0 + 2.0 ** -9 + bit * 2.0 ** -17)).astype(np.float32), 2.0 ** -17

@@ -47,6 +47,7 @@ def test_bad_arguments_return_an_error_not_a_crash():
     with pytest.raises(_lib.GcmiError):
         _lib.call("gcmi_adam_step", None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 0, None)
     _window_entries_reject_bad_arguments(lib)
+    _block_entries_reject_bad_arguments(lib)
 
 
 def _window_entries_reject_bad_arguments(lib):
@@ -96,6 +97,67 @@ def _window_entries_reject_bad_arguments(lib):
     assert lib.gcmi_win_max_bwd_if_ill(g, A, F, F, A, A, F, None, None, None) == -1  # no gamma / beta
     assert lib.gcmi_win_sumacc_max_bwd(g, A, F, F, None, F, A, A, F, None) == -1  # dxs NULL
     assert lib.gcmi_win_sumacc_max_bwd_h(g, A, F, F, OFF, F, A, A, F, None) == -1  # dxs 4 bytes off
+
+
+def _block_entries_reject_bad_arguments(lib):
+    """The operation-level entries of the persistent block kernels (gcmi_fwd_fused_gemm, gcmi_fwd_fused_gemm_h,
+    gcmi_fused_conv_bwd, gcmi_fused_dense_bwd): NULL pointers, ld < k, n_seg 0 and 17 and a bad segment are
+    GCMI_ERR_ARG, a shape without persistent kernel is GCMI_ERR_UNSUPPORTED with an error text -- all before any
+    launch.  Device pointers are never followed here; the segment and offset tables are host arrays."""
+    A = 1 << 20  # a 16-byte aligned address
+    i32, i64 = (lambda v: (ctypes.c_int32 * len(v))(*v)), (lambda v: (ctypes.c_int64 * len(v))(*v))
+
+    def table(n_seg, rows=10, begin0=0):
+        n = max(n_seg, 1)
+        return n_seg, i32([begin0] + [rows] * (n - 1)), i32([rows] * n), i64([0] * n)
+
+    def fwd(name, n_seg=1, a=A, ld=64, k=64, n_out=64, out=A, ldo=64, scratch=A, rows=10):
+        ns, b, e, off = table(n_seg, rows)
+        tail = (0, None, scratch, None) if name.endswith("_h") else (None, scratch, None)
+        return getattr(lib, name)(ns, b, e, a, ld, k, A, off, a, ld, k, A, off, A, off, n_out, 0, 1, out, ldo, *tail)
+
+    def conv(n_seg=1, gc=A, lds=64, k=64, rows=10, act_bf16=0):
+        ns, b, e, off = table(n_seg, rows)
+        return lib.gcmi_fused_conv_bwd(ns, b, e, off, off, off, A, 64, gc, 64, A, A, lds, A, max(lds, 64), k, A, A, A, None, 0,
+                                       None, 0, None, act_bf16, 0, None)
+
+    def dense(n_seg=1, membership=A, ldp=64, k=64, begin0=0, coef=A, ldg2=256):
+        ns, b, e, off = table(n_seg, 10, begin0)
+        return lib.gcmi_fused_dense_bwd(ns, b, e, off, off, membership, A, ldg2, A, 3, A, 128, coef, A, ldp, k, A, A, A,
+                                        A, 64, None, 0, None)
+
+    unsupported = b"no other kernel stands behind this entry"
+    for name in ("gcmi_fwd_fused_gemm", "gcmi_fwd_fused_gemm_h"):
+        assert fwd(name, out=None) == -1 and b"bad output" in lib.gcmi_last_error(), name
+        assert fwd(name, a=None) == -1 and b"no operand" in lib.gcmi_last_error(), name
+        assert fwd(name, ld=60) == -1 and b"operand" in lib.gcmi_last_error(), name
+        assert fwd(name, ldo=60) == -1, name
+        for n_seg in (0, 17):
+            assert fwd(name, n_seg=n_seg) == -1 and b"n_seg" in lib.gcmi_last_error(), name
+        assert fwd(name, rows=-1) == -1 and b"bad segment" in lib.gcmi_last_error(), name
+        assert fwd(name, n_out=60, ldo=60) == -3 and unsupported in lib.gcmi_last_error(), name  # no 60-column kernel
+        assert fwd(name, k=32) == -3 and unsupported in lib.gcmi_last_error(), name
+    assert fwd("gcmi_fwd_fused_gemm_h", scratch=None) == -1 and b"scratch" in lib.gcmi_last_error()
+    assert fwd("gcmi_fwd_fused_gemm_h", ld=68, k=64) == -3  # bf16 rows of 136 bytes
+    assert fwd("gcmi_fwd_fused_gemm", ld=80, k=80, scratch=None) == -3  # the 80-column shape without its scratch
+
+    assert conv(gc=None) == -1 and b"NULL" in lib.gcmi_last_error()
+    assert conv(lds=60) == -1 and b"ld < k_in" in lib.gcmi_last_error()
+    for n_seg in (0, 17):
+        assert conv(n_seg=n_seg) == -1 and b"n_seg" in lib.gcmi_last_error()
+    assert conv(rows=-1) == -1 and b"bad segment" in lib.gcmi_last_error()
+    assert conv(act_bf16=3) == -1
+    assert conv(k=32, lds=32) == -3 and unsupported in lib.gcmi_last_error()  # no kernel of one 32-column tile
+    assert conv(k=97, lds=100) == -3
+
+    assert dense(membership=None) == -1 and b"NULL" in lib.gcmi_last_error()
+    assert dense(ldp=60) == -1 and b"ld < k_in" in lib.gcmi_last_error()
+    assert dense(ldg2=255) == -1 and b"ldg2" in lib.gcmi_last_error()
+    for n_seg in (0, 17):
+        assert dense(n_seg=n_seg) == -1 and b"n_seg" in lib.gcmi_last_error()
+    assert dense(begin0=4) == -3 and unsupported in lib.gcmi_last_error()  # the dense block starts at row 0
+    assert dense(coef=None) == -3
+    assert dense(k=32, ldp=32) == -3
 
 
 def native_collate(packed, sel, out_ld=None, max_deg=10):

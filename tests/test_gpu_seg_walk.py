@@ -14,7 +14,10 @@ Which kernel a case reaches, from the dispatch in csrc/gemm.hip (``seg_gemm``) a
     to ``seg_gemm_kernel`` (64-row tiles) for the 50-column shape.
 
 So this file pins the table, its fill, the tile -> segment search and the reversed sweep; the cursor of the persistent
-kernels is walked by the model tests (test_gpu_fused_bwd, test_gpu_bf16_stream, test_gpu_width_edges, test_gpu_scale).
+kernels (``SegCursor``, ``tile_range``) is walked by tests/test_gpu_fused_edges.py, which reaches ``fwd_fused_kernel``,
+``fwd_reg_kernel``, ``fwd_hd_kernel`` and ``fused_bwd_kernel`` through entries of their own (``ops.fwd_fused_gemm``,
+``ops.fused_conv_bwd``, ``ops.fused_dense_bwd``) on SMALL, on a 16-segment table and on tables of more tiles than three
+times the largest grid.
 """
 import numpy as np
 import pytest
