@@ -196,6 +196,8 @@ _SIGNATURES = {
     "gcmi_fused_dense_bwd": [c_int32, _I32P, _I32P, _I64P, _I64P, _P, _P, c_int64, _P, c_int32, _P, c_int64, _P,
                              _P, c_int64, c_int32, _P, _P, _P, _P, c_int64, _P, c_int32, _P],
     "gcmi_task_head_forward": [_P, c_int64, c_int64, c_int32, _P, _P, c_int32, _P, _P, c_int64, _P],
+    "gcmi_head_backward": [c_int32, _P, _P, _P, c_int64, c_int32, c_int32, _P, c_int64, c_int32, _P, _P, _P, _P, c_int64,
+                           _P, _P, _P, c_int32, _P, _P, _P, _P, _P, _P, _I32P, _P],
     "gcmi_relu_bwd": [_P, c_int64, _P, c_int64, c_int64, c_int32, _P],
     "gcmi_loss_fwd_bwd": [c_int32, _P, _P, _P, c_int64, c_int32, c_int32, _P, _P, _P, _P, _P],
     "gcmi_softmax": [_P, c_int64, c_int32, _P, _P],

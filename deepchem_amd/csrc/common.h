@@ -356,6 +356,7 @@ struct HeadBackward {
   double* sums = nullptr;             // optional: that BatchNorm's backward sums, added into this accumulator
   float* dl_scratch = nullptr;        // more than 32 outputs: n_mols x outputs floats, and
   float* img = nullptr;               // kHeadImgFloats floats, filled with head_prep's images of w first
+  int32_t* route = nullptr;           // optional, on the host (gcmi_head_backward): 0 head_bwd_kernel, 1 the wide pair
 };
 
 // row slabs of the weight-gradient kernels (gemm.hip, gemm_split.hip): slabs instead of tiles, other offsets

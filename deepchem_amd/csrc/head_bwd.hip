@@ -950,6 +950,7 @@ int head_bwd_fused(const HeadBackward& h, hipStream_t st) {
                        d_dl_scratch, tc, d_fp, (int)h.ldfp, n_mols, rps, d_dw, d_db);
     GCMI_CHECK_LAUNCH("head_wgrad_wide");
     HD_PRINT("wgrad_wide", 1, st);
+    if (h.route != nullptr) *h.route = 1;
     return GCMI_OK;
   }
   // three workgroups are resident per CU (~130 VGPRs): 3 x 256 CUs, every workgroup in the first wave.  Measured at
@@ -957,7 +958,57 @@ int head_bwd_fused(const HeadBackward& h, hipStream_t st) {
   const int grid = (int)std::min<int64_t>(768, (n_mols + kHM - 1) / kHM);
   hipLaunchKernelGGL(head_bwd_kernel, dim3(grid), dim3(kHB), 0, st, a);
   GCMI_CHECK_LAUNCH("head_bwd");
+  if (h.route != nullptr) *h.route = 0;
   return GCMI_OK;
 }
 
 }  // namespace gcmi
+
+using namespace gcmi;
+
+extern "C" {
+
+// The head backward kernels alone (for tests): the argument checks the model step never needed, the HeadBackward
+// description, head_bwd_fused -- and no separate launches behind a refusal.
+int gcmi_head_backward(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights, int64_t n_rows,
+                       int32_t n_tasks, int32_t n_classes, const float* d_fp, int64_t ldfp, int32_t n_mols,
+                       const float* d_w, float* d_dw, float* d_db, float* d_g2, int64_t ldg2, double* d_loss_acc,
+                       double* d_sums, const int32_t* d_runs, int32_t n_deg, const int32_t* d_arg, const float* d_rawsum,
+                       const float* d_mean, const float* d_invstd, float* d_dl_scratch, float* d_img_scratch,
+                       int32_t* route, void* stream) {
+  GCMI_CHECK_ARG(kind == 0 || kind == 1, "head_backward: kind %d is neither 0 (cross-entropy) nor 1 (L2)", kind);
+  GCMI_CHECK_ARG(d_logits && d_labels && d_fp && d_w && d_dw && d_g2 && d_loss_acc && route, "head_backward: NULL buffer");
+  GCMI_CHECK_ARG(n_mols >= 1 && n_rows >= 1 && n_rows <= n_mols, "head_backward: n_rows %lld outside [1, n_mols = %d]",
+                 (long long)n_rows, n_mols);
+  GCMI_CHECK_ARG(n_tasks >= 1, "head_backward: n_tasks %d < 1", n_tasks);
+  GCMI_CHECK_ARG(kind != 0 || n_classes >= 1, "head_backward: n_classes %d < 1", n_classes);
+  GCMI_CHECK_ARG(ldfp >= kHB && ldg2 >= kHB, "head_backward: ldfp %lld or ldg2 %lld < %d", (long long)ldfp, (long long)ldg2,
+                 kHB);
+  GCMI_CHECK_ARG(d_sums == nullptr || (n_deg >= 1 && n_deg <= GCMI_MAX_DEG + 1), "head_backward: n_deg %d outside [1,%d]",
+                 n_deg, GCMI_MAX_DEG + 1);
+  // (the two-class loads are 8-byte pairs, the wide kernel stages rawsum and arg as 16-byte pieces and reads a run as one
+  // 8-byte pair)
+  GCMI_CHECK_ARG(aligned16(d_logits) && aligned16(d_labels) && aligned16(d_dl_scratch) && aligned16(d_rawsum) &&
+                     aligned16(d_arg) && aligned16(d_runs),
+                 "head_backward: logits, labels, dl_scratch, rawsum, arg and runs must be 16-byte aligned");
+  ReadoutGrad rg;
+  memset(&rg, 0, sizeof(rg));
+  rg.ldg2 = ldg2; rg.arg = d_arg; rg.rawsum = d_rawsum; rg.runs = d_runs; rg.n_mols = n_mols; rg.n_deg = n_deg;
+  BnPoint bn;
+  bn.n_feat = kHB / 2; bn.mean = const_cast<float*>(d_mean); bn.invstd = const_cast<float*>(d_invstd);
+  HeadBackward h;
+  h.kind = kind; h.logits = d_logits; h.labels = d_labels; h.weights = d_weights; h.n_rows = n_rows;
+  h.n_tasks = n_tasks; h.n_classes = n_classes; h.fp = d_fp; h.ldfp = ldfp; h.w = d_w; h.dw = d_dw; h.db = d_db;
+  h.rg = &rg; h.g2 = d_g2; h.loss_acc = d_loss_acc; h.dense_bn = &bn; h.sums = d_sums;
+  h.dl_scratch = d_dl_scratch; h.img = d_img_scratch; h.route = route;
+  // (the product of the two counts in 64 bits: head_bwd_fused forms it as an int)
+  const int64_t tc = (int64_t)n_tasks * (kind == 0 ? n_classes : 1);
+  const int rc = tc > kWTC ? GCMI_ERR_UNSUPPORTED : head_bwd_fused(h, (hipStream_t)stream);
+  if (rc == GCMI_ERR_UNSUPPORTED)
+    set_error("head_backward: exact mode with more than %d outputs, the one-pass kernels switched off, more than %d "
+              "outputs, a wide shape without its scratch or with ldfp %% 4 != 0, or sums without their inputs (no other "
+              "kernel stands behind this entry)", kHT, kWTC);
+  return rc;
+}
+
+}  // extern "C"

@@ -542,6 +542,58 @@ def fused_dense_bwd(seg_begin, seg_end, w_off, b_off, membership, g2, arg, gc, c
               _ptr(psums), int(act_bf16), _stream())
 
 
+def head_backward(kind: int, logits, labels, weights, n_rows: int, n_tasks: int, n_classes: int, fp, w, dw, db, g2,
+                  loss_acc, sums=None, runs=None, arg=None, rawsum=None, mean=None, invstd=None, dl_scratch=None,
+                  img_scratch=None) -> int:
+    """The per-molecule head backward kernels alone (gcmi_head_backward): loss (the sum of w l, ADDED into the 16
+    doubles of ``loss_acc``), d logits, dw (outputs x 256) / db added into, g2 written for every row of ``fp``, and
+    with ``sums`` (66 * 128 doubles) the dense BatchNorm's backward sums added from ``runs`` (n_mols, n_deg, 2),
+    ``arg`` (n_mols, 128), ``rawsum`` (n_mols, 256), ``mean`` and ``invstd`` (128).  logits / labels hold at least
+    n_rows x outputs floats, weights n_rows x n_tasks.  Returns the route: 0 head_bwd_kernel, 1 the wide pair
+    (which needs ``dl_scratch``, n_mols x outputs floats, and ``img_scratch``, task_head_scratch_floats() floats)."""
+    n_out = n_tasks * (n_classes if kind == 0 else 1)
+    _mat(fp, "fp", cols=256)
+    n_mols = fp.shape[0]
+    _mat(g2, "g2", rows=n_mols, cols=256)
+    if not 1 <= n_rows <= n_mols:
+        raise ValueError("n_rows %d outside [1, %d]" % (n_rows, n_mols))
+    for t, nm, need in ((logits, "logits", n_rows * n_out), (labels, "labels", n_rows * n_out)):
+        if _flat(t, nm).numel() < need:
+            raise ValueError("%s holds fewer than n_rows x outputs = %d floats" % (nm, need))
+    if weights is not None and _flat(weights, "weights").numel() < n_rows * n_tasks:
+        raise ValueError("weights holds fewer than n_rows x n_tasks = %d floats" % (n_rows * n_tasks))
+    if _flat(w, "w").numel() < n_out * 256 or _flat(dw, "dw").numel() < n_out * 256:
+        raise ValueError("w and dw must hold outputs x 256 = %d floats" % (n_out * 256))
+    if db is not None and _flat(db, "db").numel() < n_out:
+        raise ValueError("db must hold %d floats" % n_out)
+    if _flat(loss_acc, "loss_acc", torch.float64).numel() < 16:
+        raise ValueError("loss_acc must hold 16 doubles")
+    n_deg = 1  # (sums without runs: the entry's refusal, not an argument error)
+    if sums is not None:
+        _acc(sums, "sums", 128)
+        if runs is not None:
+            if runs.dtype != torch.int32 or not runs.is_cuda or not runs.is_contiguous() or runs.dim() != 3 or \
+                    runs.shape[0] != n_mols or runs.shape[2] != 2:
+                raise ValueError("runs must be a contiguous int32 CUDA tensor of shape (%d, n_deg, 2)" % n_mols)
+            n_deg = runs.shape[1]
+        if arg is not None and (arg.dtype != torch.int32 or not arg.is_cuda or not arg.is_contiguous() or
+                                tuple(arg.shape) != (n_mols, 128)):
+            raise ValueError("arg must be a contiguous int32 CUDA tensor of shape (%d, 128)" % n_mols)
+        if rawsum is not None and not _mat(rawsum, "rawsum", rows=n_mols, cols=256).is_contiguous():
+            raise ValueError("rawsum must be contiguous")
+        _vec(mean, "mean", 128), _vec(invstd, "invstd", 128)
+    if dl_scratch is not None and _flat(dl_scratch, "dl_scratch").numel() < n_mols * n_out:
+        raise ValueError("dl_scratch must hold n_mols x outputs = %d floats" % (n_mols * n_out))
+    if img_scratch is not None and _flat(img_scratch, "img_scratch").numel() < task_head_scratch_floats():
+        raise ValueError("img_scratch must hold task_head_scratch_floats() floats")
+    route = ctypes.c_int32(-1)
+    _lib.call("gcmi_head_backward", int(kind), _ptr(logits), _ptr(labels), _ptr(weights), n_rows, n_tasks, n_classes,
+              _ptr(fp), _ld(fp), n_mols, _ptr(w), _ptr(dw), _ptr(db), _ptr(g2), _ld(g2), _ptr(loss_acc), _ptr(sums),
+              _ptr(runs), n_deg, _ptr(arg), _ptr(rawsum), _ptr(mean), _ptr(invstd), _ptr(dl_scratch), _ptr(img_scratch),
+              ctypes.byref(route), _stream())
+    return int(route.value)
+
+
 def seg_gemm_wgrad(seg_begin, seg_end, a, g, dw, dw_off, dbias, dbias_off, trans_w: bool):
     """dw (+)= a^T g per segment; dw / dbias are flat, pre-zeroed, accumulated in place."""
     n_seg = len(seg_begin)

@@ -450,6 +450,37 @@ int64_t gcmi_task_head_scratch_floats(void);
 int gcmi_task_head_forward(const float* d_fingerprint, int64_t ld, int64_t n_rows, int32_t k, const float* d_w,
                            const float* d_bias, int32_t n_out, float* d_img_scratch, float* d_out, int64_t ldo,
                            void* stream);
+/* The per-molecule head backward kernels of the large-batch model step (head_bwd.hip), callable alone: for tests.  NO
+ * other kernel stands behind this entry: exact mode (GCMI_OPT_GEMM_EXACT) with more than 32 outputs, GCMI_OPT_FUSED_BWD
+ * off, more than 256 outputs, 33..256 outputs without both scratches or with ldfp % 4 != 0, and d_sums without its
+ * inputs give GCMI_ERR_UNSUPPORTED with an error text, launch nothing and write nothing.
+ *   outputs = n_tasks x n_classes (kind 0, softmax cross-entropy over the classes of a task) or n_tasks (kind 1, L2);
+ *   logits / labels: n_rows x outputs, weights: n_rows x n_tasks or NULL (all ones).  The first n_rows of the n_mols
+ *   molecules carry a loss, 1 <= n_rows <= n_mols; the others are padding with a zero gradient (their fingerprint rows
+ *   are still read and must be finite).
+ *     loss = sum w l / (n_rows n_tasks): the SUM w l is ADDED into the 16 doubles at d_loss_acc (any of them; their sum
+ *       is the value) and returned raw -- the caller divides
+ *     dl   = d loss / d logits; on route 1 written to d_dl_scratch (n_mols x outputs, zeros in the padding rows)
+ *     dW  += dl^T fp (outputs x 256, nn.Linear layout), db += column sums of dl (d_db may be NULL)
+ *     g2   = (dl W) * (1 - fp^2): written for all n_mols rows of d_g2 (ldg2 >= 256), fp = the tanh output (ldfp >= 256)
+ *   d_sums (optional): GCMI_BN_ACC_DOUBLES(128) doubles in the layout of gcmi_fwd_fused_gemm's d_stats; ADDED per
+ *   column f of the dense BatchNorm (mean, invstd: 128 floats): the sums over the atom rows of dy and of dy * xhat for
+ *   the dy of gcmi_fused_dense_bwd, taken from per-molecule data -- with n = the atoms of the molecule (d_runs:
+ *   n_mols x n_deg x 2 row runs [begin, end), 1 <= n_deg <= GCMI_MAX_DEG + 1), d_rawsum (n_mols x 256) = [sum over the
+ *   molecule's rows | the arg-max row's value] of the BatchNorm input and d_arg (n_mols x 128; < 0: no atoms, that
+ *   entry of d_rawsum is not used):
+ *     sum dy        = sum over molecules of n g2[f] + (arg[f] >= 0) g2[128 + f]
+ *     sum dy * xhat = sum of g2[f] (rawsum[f] - n mean) invstd + (arg[f] >= 0) g2[128 + f] (rawsum[128 + f] - mean) invstd
+ *   d_dl_scratch (n_mols x outputs floats), d_img_scratch (gcmi_task_head_scratch_floats() floats): both needed for
+ *   33..256 outputs, written there; what they held before does not matter.
+ *   *route (host): 0 = head_bwd_kernel (at most 32 outputs), 1 = head_prep + head_bwd_wide + head_wgrad_wide.
+ *   logits, labels, d_dl_scratch, d_rawsum, d_arg, d_runs: 16-byte aligned.                                         */
+int gcmi_head_backward(int32_t kind, const float* d_logits, const float* d_labels, const float* d_weights,
+                       int64_t n_rows, int32_t n_tasks, int32_t n_classes, const float* d_fp, int64_t ldfp,
+                       int32_t n_mols, const float* d_w, float* d_dw, float* d_db, float* d_g2, int64_t ldg2,
+                       double* d_loss_acc, double* d_sums, const int32_t* d_runs, int32_t n_deg, const int32_t* d_arg,
+                       const float* d_rawsum, const float* d_mean, const float* d_invstd, float* d_dl_scratch,
+                       float* d_img_scratch, int32_t* route, void* stream);
 /* elementwise g *= (y > 0): ReLU derivative, in place on g. */
 int gcmi_relu_bwd(float* d_g, int64_t ldg, const float* d_y, int64_t ldy, int64_t n_rows,
                   int32_t n_feat, void* stream);

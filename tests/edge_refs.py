@@ -11,6 +11,9 @@ comparisons are bit for bit; tests/test_win_refs_host.py checks them against the
 The section after it restates the segmented products (csrc/gemm.hip, csrc/gemm_split.hip) for
 tests/test_gpu_product_edges.py: the two contracts in float64, the float32 arithmetic each product mode claims, and the
 operands that tell a lost piece product; tests/test_product_refs_host.py checks them.
+
+The last section restates the per-molecule head backward (csrc/head_bwd.hip) for tests/test_gpu_head_bwd.py;
+tests/test_head_refs_host.py checks it against torch autograd and the row-level definition of the BatchNorm sums.
 """
 import numpy as np
 
@@ -528,16 +531,24 @@ def split3_np(x):
     return p1, p2, bf16_round(r2)
 
 
-def split_product_np(a, w, terms=SIX_TERMS, acc=None):
+def split_product_np(a, w, terms=SIX_TERMS, acc=None, group=16):
     """a . w assembled from the piece products ``terms`` (pairs (i, j): piece i of a times piece j of w), one float32
     accumulation per term and 16-wide contraction step, in the order given -- the kernels' loop with each
-    32x32x16 product formed exactly and rounded once.  acc: continue this sum."""
+    32x32x16 product formed exactly and rounded once.  acc: continue this sum.
+    group = 8: the 16 products of a step enter the accumulator as two exact sums of 8 with a rounding after each,
+    which is what v_mfma_f32_32x32x16_bf16 does on gfx950 (measured through head_bwd_wide_kernel, DESIGN 39: 86 % of
+    76 000 outputs bit for bit and 1.2 ulp apart on average, against 15 % and 53 ulp for one rounding per step)."""
     A, W = split3_np(a), split3_np(w)
     acc = np.zeros((np.shape(a)[0], np.shape(w)[1]), np.float32) if acc is None else np.asarray(acc, np.float32).copy()
     for k0 in range(0, np.shape(a)[1], 16):
         for i, j in terms:
-            blk = A[i][:, k0:k0 + 16].astype(np.float64) @ W[j][k0:k0 + 16].astype(np.float64)
-            acc = (acc + blk.astype(np.float32)).astype(np.float32)
+            if group == 16:
+                blk = A[i][:, k0:k0 + 16].astype(np.float64) @ W[j][k0:k0 + 16].astype(np.float64)
+                acc = (acc + blk.astype(np.float32)).astype(np.float32)
+                continue
+            for g0 in range(k0, k0 + 16, group):
+                blk = A[i][:, g0:g0 + group].astype(np.float64) @ W[j][g0:g0 + group].astype(np.float64)
+                acc = (acc.astype(np.float64) + blk).astype(np.float32)
     return acc
 
 
@@ -767,3 +778,196 @@ def cancelling_probe(rng, rows, k, n_out, piece):
     if piece == 1:
         return a.astype(np.float32), (s * (1.0 + bit * 2.0 ** -9)).astype(np.float32), 2.0 ** -9
     return a.astype(np.float32), (s * (1.0 + 2.0 ** -9 + bit * 2.0 ** -17)).astype(np.float32), 2.0 ** -17
+
+
+# ------------------------------------------------------------------------------------------------ per-molecule head backward
+# csrc/head_bwd.hip (head_bwd_kernel; head_prep_kernel + head_bwd_wide_kernel + head_wgrad_wide_kernel) restated from the
+# formulas of the layers it replaces: the loss of models/losses.py on logits = tanh(pre) . W^T + b, the gradients w.r.t.
+# W, b and pre, and the column sums of the dense BatchNorm's backward taken from per-molecule data.
+# tests/test_gpu_head_bwd.py compares the kernels with these; tests/test_head_refs_host.py checks them on the host.
+LOSS_REPLICAS = 16  # kLossRep: the loss is added into any of 16 doubles
+HEAD_K = 256        # fingerprint columns: [sum half | max half] of the 128-column dense layer
+MFMA_GROUP = 8      # contraction columns per rounding inside one 32x32x16 bf16 product (split_product_np)
+TINY32 = 2.0 ** -102  # a magnitude below it cannot be resolved to 2^-24 of itself inside float32's normal range (2^-126)
+
+
+def head_bwd_ref(kind, logits, labels, weights, n_rows, fp, w, sums_inputs=None):
+    """kind 0: logits / labels (>= n_rows, n_tasks, n_classes), softmax cross-entropy over the classes; kind 1: (>= n_rows,
+    n_tasks), L2; weights (>= n_rows, n_tasks) or None.  The first n_rows of the fp.shape[0] molecules carry a loss;
+    fp (n_mols, 256) = tanh(pre), w (outputs, 256).  Float64 throughout.  Returns a dict:
+      loss  the SUM of w l over rows and tasks (the mean loss times n_rows n_tasks, which is what the kernels add into
+            their accumulator), dl (n_mols, outputs) = d mean loss / d logits, zero rows for the padding molecules,
+      g2 = (dl W) (1 - fp^2) = d / d pre, dw = dl^T fp, db = column sums of dl,
+      sums  (2, 128), with sums_inputs = dict(runs, arg, rawsum, mean, invstd): head_sums_ref of this g2,
+    and for every output the sum of the absolute values of its terms as S_loss, S_dl, S_g2, S_dw, S_db, S_sums."""
+    x, y = f64(logits)[:n_rows], f64(labels)[:n_rows]
+    wt = None if weights is None else f64(weights)[:n_rows]
+    n_mols = fp.shape[0]
+    count = x.shape[0] * x.shape[1]
+    wa = np.ones(x.shape[:2]) if wt is None else np.abs(wt)
+    if kind == 0:
+        _, dl_rows, p = ce_loss_ref(x, y, wt)
+        terms = (wa if wt is None else wt) * -(y * log_softmax_ref(x)).sum(-1)
+        S_loss = float((wa * np.abs(y * log_softmax_ref(x)).sum(-1)).sum())
+        S_rows = wa[..., None] * (p * np.abs(y.sum(-1, keepdims=True)) + np.abs(y)) / count
+    else:
+        _, dl_rows = l2_loss_ref(x, y, wt)
+        terms = (wa if wt is None else wt) * (x - y) ** 2
+        S_loss = float((wa * (x - y) ** 2).sum())
+        S_rows = 2.0 * wa * (np.abs(x) + np.abs(y)) / count
+    tc = dl_rows[0].size
+    dl, S_dl = np.zeros((n_mols, tc)), np.zeros((n_mols, tc))
+    dl[:n_rows], S_dl[:n_rows] = dl_rows.reshape(n_rows, tc), S_rows.reshape(n_rows, tc)
+    fp, w = f64(fp), f64(w)
+    out = dict(loss=float(terms.sum()), S_loss=S_loss, dl=dl, S_dl=S_dl)  # (the sum itself: no division to undo)
+    out.update(head_linear_ref(dl, S_dl, fp, w))
+    if sums_inputs is not None:
+        out["sums"], out["S_sums"] = head_sums_ref(out["g2"], sums_inputs)
+    return out
+
+
+def head_linear_ref(dl, S_dl, fp, w):
+    """The outputs that are linear in d logits, from ANY d logits (the reference's, or the ones a kernel returned): g2,
+    dw, db and their magnitudes in float64."""
+    dl, S_dl, fp, w = f64(dl), f64(S_dl), f64(fp), f64(w)
+    return dict(g2=(dl @ w) * (1.0 - fp * fp), S_g2=(S_dl @ np.abs(w)) * (1.0 + fp * fp),
+                dw=dl.T @ fp, S_dw=S_dl.T @ np.abs(fp), db=dl.sum(0), S_db=S_dl.sum(0))
+
+
+def _head_sums_terms(g2, si, dtype):
+    """Per molecule and column the four terms of the two sums: (n g_sum, [arg >= 0] g_max, g_sum xhat_sum, [arg >= 0] g_max
+    xhat_max) with xhat_sum = (rawsum - n mean) invstd, xhat_max = (rawmax - mean) invstd, and the magnitudes of the last
+    two.  rawsum's max half is not looked at where arg < 0."""
+    g = np.asarray(g2, dtype)
+    runs = np.asarray(si["runs"], np.int64)
+    n = (runs[:, :, 1] - runs[:, :, 0]).sum(1).astype(dtype)[:, None]
+    rs, mu, ist = np.asarray(si["rawsum"], dtype), np.asarray(si["mean"], dtype), np.asarray(si["invstd"], dtype)
+    has = np.asarray(si["arg"]) >= 0
+    F = HEAD_K // 2
+    rmax = np.where(has, rs[:, F:], dtype(0))
+    gs, gm = g[:, :F], np.where(has, g[:, F:], dtype(0))
+    terms = (n * gs, gm, gs * ((rs[:, :F] - n * mu) * ist), gm * ((rmax - mu) * ist))
+    mags = (np.abs(gs) * (np.abs(rs[:, :F]) + n * np.abs(mu)) * np.abs(ist), np.abs(gm) * (np.abs(rmax) + np.abs(mu)) * np.abs(ist))
+    return terms, mags
+
+
+def head_sums_ref(g2, si):
+    """(2, 128): sum over the atom rows of dy and of dy * xhat from per-molecule data, formed and added pairwise in the
+    host's extended precision (64-bit significand: a sum of 25 000 terms is good to a hundredth of 2^-53 of S), returned
+    in that precision; and S (float64)."""
+    assert np.finfo(np.longdouble).nmant >= 63, "no extended precision on this host"
+    (a1, b1, a2, b2), (ma, mb) = _head_sums_terms(g2, si, np.longdouble)
+    sums = np.stack([a1.sum(0) + b1.sum(0), a2.sum(0) + b2.sum(0)])
+    S = np.stack([np.abs(a1).sum(0) + np.abs(b1).sum(0), ma.sum(0) + mb.sum(0)]).astype(np.float64)
+    return sums, S
+
+
+def head_sums_seq64(g2, si, reverse=True):
+    """The same sums as two sequential float64 chains per column (the sum half, the max half; one rounding per
+    operation), over the molecules in reversed order, added at the end: the e_ref of the kernels' fp64 sums."""
+    (a1, b1, a2, b2), _ = _head_sums_terms(g2, si, np.float64)
+    order = range(a1.shape[0] - 1, -1, -1) if reverse else range(a1.shape[0])
+    t = np.zeros((4, HEAD_K // 2))
+    for m in order:
+        t[0] += a1[m]
+        t[1] += b1[m]
+        t[2] += a2[m]
+        t[3] += b2[m]
+    return np.stack([t[0] + t[1], t[2] + t[3]])
+
+
+def _fma32(a, b, c):
+    """fmaf: a * b is exact in float64, the sum is rounded to float64 and then to float32 (a double rounding is rare)."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(np.float32)
+
+
+def head_dl_f32(kind, logits, labels, weights, n_rows, two_class_fast):
+    """Loss and d logits in float32 numpy, one rounding per operation, in the order of head_bwd_kernel's phase 1;
+    two_class_fast: the one-exponential form of head_bwd_wide_kernel for two classes.  Returns (sum of the float32
+    terms w l in float64, dl_rows (n_rows, outputs) float32)."""
+    f32 = np.float32
+    x, y = np.asarray(logits, f32)[:n_rows], np.asarray(labels, f32)[:n_rows]
+    w = np.ones(x.shape[:2], f32) if weights is None else np.asarray(weights, f32)[:n_rows]
+    inv = f32(1.0) / f32(x.shape[0] * x.shape[1])
+    if kind == 1:
+        dlt = x - y
+        loss = float(((w * dlt) * dlt).astype(np.float64).sum())
+        return loss, (((f32(2.0) * dlt) * w) * inv).reshape(n_rows, -1)
+    C = x.shape[2]
+    if two_class_fast and C == 2:
+        x0, x1, y0, y1 = x[..., 0], x[..., 1], y[..., 0], y[..., 1]
+        first = x0 >= x1
+        dd = np.where(first, x1 - x0, x0 - x1)
+        e = np.exp(dd)
+        se = f32(1.0) + e
+        lse = np.log(se)
+        invs = f32(1.0) / se
+        lp_max, lp_oth, p_max, p_oth = -lse, dd - lse, invs, e * invs
+        lp = np.stack([np.where(first, lp_max, lp_oth), np.where(first, lp_oth, lp_max)], -1)
+        p = np.stack([np.where(first, p_max, p_oth), np.where(first, p_oth, p_max)], -1)
+        ysum = y0 + y1
+        l = -(y0 * lp[..., 0]) - y1 * lp[..., 1]
+    else:
+        mx = x.max(-1)
+        se, ysum = np.zeros(mx.shape, f32), np.zeros(mx.shape, f32)
+        for c in range(C):
+            se = se + np.exp(x[..., c] - mx)
+            ysum = ysum + y[..., c]
+        lse = np.log(se)
+        lp = (x - mx[..., None]) - lse[..., None]
+        p = np.exp(lp)
+        l = np.zeros(mx.shape, f32)
+        for c in range(C):
+            l = l - y[..., c] * lp[..., c]
+    assert lp.dtype == f32 and p.dtype == f32 and l.dtype == f32
+    dl = (w[..., None] * (p * ysum[..., None] - y)) * inv
+    return float((w * l).astype(np.float64).sum()), dl.reshape(n_rows, -1)
+
+
+def head_bwd_f32(kind, logits, labels, weights, n_rows, fp, w, wide):
+    """head_bwd_ref's chain in sequential float32 (numpy's float32 exp / log, one rounding per operation): the e_ref of
+    the accuracy bounds.  wide False: the order of head_bwd_kernel -- dfp a fused-multiply-add chain over the outputs,
+    dw such a chain over the molecules, db a chain of adds.  wide True: the two products by split_product_np with the six
+    piece terms and the instruction's two roundings per step (dl . W over the outputs, dl^T . fp over the molecules),
+    the two-class loss in its one-exponential form.  Returns dict(loss, dl, g2, dw, db)."""
+    f32 = np.float32
+    fp, w = np.asarray(fp, f32), np.asarray(w, f32)
+    n_mols = fp.shape[0]
+    loss, dl_rows = head_dl_f32(kind, logits, labels, weights, n_rows, wide)
+    dl = np.zeros((n_mols, dl_rows.shape[1]), f32)
+    dl[:n_rows] = dl_rows
+    return dict(loss=loss, dl=dl, **head_linear_f32(dl, fp, w, wide))
+
+
+def head_linear_f32(dl, fp, w, wide):
+    """g2, dw, db from given float32 d logits in the float32 arithmetic head_bwd_f32 describes."""
+    f32 = np.float32
+    dl, fp, w = np.asarray(dl, f32), np.asarray(fp, f32), np.asarray(w, f32)
+    n_mols, tc = dl.shape
+    if wide:
+        dfp = split_product_np(dl, w, group=MFMA_GROUP)
+        dw = split_product_np(np.ascontiguousarray(dl.T), fp, group=MFMA_GROUP)
+    else:
+        dfp = np.zeros((n_mols, HEAD_K), f32)
+        for t in range(tc):
+            dfp = _fma32(dl[:, t, None], w[None, t, :], dfp)
+        dw = np.zeros((tc, HEAD_K), f32)
+        for m in range(n_mols):
+            dw = _fma32(dl[m, :, None], fp[None, m, :], dw)
+    db = np.zeros(tc, f32)
+    for m in range(n_mols):
+        db = db + dl[m]
+    g2 = dfp * (f32(1.0) - fp * fp)
+    assert g2.dtype == f32 and db.dtype == f32
+    return dict(g2=g2, dw=dw, db=db)
+
+
+def head_err_units(got, ref, S, unit=U24):
+    """max |got - ref| / max(S, TINY32) over the elements with S > 0, in units of ``unit``; the others must be zero."""
+    got, S = np.asarray(got), f64(S)
+    m = S > 0
+    assert np.all(got[~m] == 0), "an output without any term is not zero"
+    if not m.any():
+        return 0.0
+    diff = np.abs(np.asarray(got[m], np.longdouble) - np.asarray(ref, np.longdouble)[m]).astype(np.float64)
+    return float((diff / np.maximum(S[m], TINY32)).max() / unit)

@@ -48,6 +48,60 @@ def test_bad_arguments_return_an_error_not_a_crash():
         _lib.call("gcmi_adam_step", None, None, None, None, 10, 1e-3, 0.9, 0.999, 1e-8, 0, None)
     _window_entries_reject_bad_arguments(lib)
     _block_entries_reject_bad_arguments(lib)
+    _head_entry_rejects_bad_arguments(lib)
+
+
+def _head_entry_rejects_bad_arguments(lib):
+    """gcmi_head_backward: the argument checks are GCMI_ERR_ARG, and whatever head_bwd_fused refuses -- exact mode with
+    more than 32 outputs, the one-pass kernels off, more than 256 outputs, a wide shape without its scratch or with
+    ldfp % 4 != 0, sums without their inputs -- is GCMI_ERR_UNSUPPORTED with an error text: all before any launch.
+    Device pointers are never followed here, and the route stays as it was."""
+    A, OFF = 1 << 20, (1 << 20) + 4
+    route = ctypes.c_int32(-7)
+
+    def head(kind=1, logits=A, n_rows=10, n_tasks=4, n_classes=1, ldfp=256, n_mols=10, dw=A, ldg2=256, sums=None, runs=A,
+             n_deg=11, arg=A, mean=A, dl=A, img=A, rt=route):
+        return lib.gcmi_head_backward(kind, logits, A, None, n_rows, n_tasks, n_classes, A, ldfp, n_mols, A, dw, None, A,
+                                      ldg2, A, sums, runs, n_deg, arg, A, mean, A, dl, img,
+                                      None if rt is None else ctypes.byref(rt), None)
+
+    def err():
+        return lib.gcmi_last_error()
+
+    assert head(kind=2) == -1 and b"kind" in err()
+    assert head(logits=None) == -1 and b"NULL" in err()
+    assert head(dw=None) == -1 and b"NULL" in err()
+    assert head(rt=None) == -1 and b"NULL" in err()
+    for n_rows in (0, -1, 11):
+        assert head(n_rows=n_rows) == -1 and b"n_rows" in err(), n_rows
+    assert head(n_mols=0, n_rows=0) == -1 and b"n_rows" in err()
+    assert head(n_tasks=0) == -1 and b"n_tasks" in err()
+    assert head(kind=0, n_classes=0) == -1 and b"n_classes" in err()
+    assert head(ldfp=255) == -1 and b"ldfp" in err()
+    assert head(ldg2=255) == -1 and b"ldg2" in err()
+    for n_deg in (0, 12):
+        assert head(sums=A, n_deg=n_deg) == -1 and b"n_deg" in err(), n_deg
+    assert head(logits=OFF) == -1 and b"aligned" in err()
+    assert head(sums=A, arg=OFF) == -1 and b"aligned" in err()
+
+    unsupported = b"no other kernel stands behind this entry"
+    assert head(n_tasks=257) == -3 and unsupported in err()
+    assert head(kind=0, n_tasks=129, n_classes=2) == -3 and unsupported in err()
+    assert head(kind=0, n_tasks=1 << 20, n_classes=1 << 20) == -3 and unsupported in err()  # (no 32-bit product)
+    assert head(n_tasks=40, dl=None) == -3 and unsupported in err()
+    assert head(n_tasks=40, img=None) == -3 and unsupported in err()
+    assert head(n_tasks=40, ldfp=257) == -3 and unsupported in err()
+    assert head(sums=A, runs=None) == -3 and unsupported in err()
+    assert head(sums=A, mean=None) == -3 and unsupported in err()
+    for option, value, n_tasks in ((_lib.GCMI_OPT_GEMM_EXACT, 1, 33), (_lib.GCMI_OPT_FUSED_BWD, 0, 4)):
+        was = ctypes.c_int32(0)
+        assert lib.gcmi_get_option(option, ctypes.byref(was)) == 0
+        try:
+            assert lib.gcmi_set_option(option, value) == 0
+            assert head(n_tasks=n_tasks) == -3 and unsupported in err(), option
+        finally:
+            assert lib.gcmi_set_option(option, was.value) == 0
+    assert route.value == -7
 
 
 def _window_entries_reject_bad_arguments(lib):
