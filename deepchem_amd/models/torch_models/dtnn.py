@@ -1,0 +1,248 @@
+"""``DTNN`` / ``DTNNModel``: Deep Tensor Neural Network (Schuett et al. 2017) with the interface of the reference's
+``deepchem/models/torch_models/dtnn.py``: constructor arguments and errors, ``L2Loss``, ``["prediction"]``, the 17
+state-dict keys (``linear`` is the reference's ``LazyLinear(n_tasks)`` materialised: ``nn.Linear(n_tasks, n_tasks)``)
+and ``default_generator``'s batches.  The model takes Coulomb-matrix arrays ``(n, A, A)``; ``CoulombMatrix``
+featurization (3-D conformers) is out of scope.
+
+Two input routes.  ``default_generator`` yields the reference's five arrays, Gaussian matrix included (800 bytes per
+pair, float64, built on the host); ``DTNN.forward`` runs them through the pair kernel's matrix form.  ``fit`` /
+``predict`` on a ``NumpyDataset`` or ``DiskDataset`` of Coulomb matrices instead keep a RESIDENT SET on the device (atom
+numbers and one fp32 distance per pair, derived in float64 exactly as the reference does, uploaded once per dataset); a batch is then
+collated by a small kernel from the molecule indices and the Gaussians are generated in registers.  Same batches,
+order, shuffles and padding: the indices come from the dataset's own ``iterbatches``.
+
+Dropout quirk, kept: the reference applies a FRESH ``nn.Dropout(p)`` per call, which is always in training mode, so a
+non-zero ``dropout`` is active in ``predict`` too.  It is applied by torch between the native ops.
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+
+from deepchem_amd import ops
+from deepchem_amd.data.datasets import DiskDataset, NumpyDataset, pad_batch
+from deepchem_amd.models.losses import L2Loss
+from deepchem_amd.models.torch_models import dtnn_layers as layers
+from deepchem_amd.models.torch_models.torch_model import TorchModel
+from deepchem_amd.utils.batch_utils import batch_coulomb_matrix_features, coulomb_matrix_atoms
+
+
+class ResidentCoulombSet:
+    """A Coulomb-matrix dataset in HBM: per molecule the atom count, the padded atom numbers and the A x A distance
+    matrix (fp32; -100 on the diagonal).  Atom numbers are validated against the embedding table HERE, once."""
+
+    def __init__(self, X: np.ndarray, device, periodic_table_length: int):
+        num_atoms, z, dist = coulomb_matrix_atoms(X)
+        A = z.shape[1]
+        if A > ops.DTNN_MAX_ATOMS:
+            raise ValueError("DTNNModel covers molecules of up to %d atoms (got matrices of %d)" %
+                             (ops.DTNN_MAX_ATOMS, A))
+        if z.size and (z.min() < 0 or z.max() >= periodic_table_length):
+            raise ValueError("atom number %d outside the embedding table of %d rows" %
+                             (int(z.max() if z.max() >= periodic_table_length else z.min()), periodic_table_length))
+        self.num_atoms = num_atoms  # host: the batch sizes are known without a read-back
+        self.max_atoms = A
+        self.z = torch.as_tensor(z.astype(np.int32), device=device).contiguous()
+        self.dist = torch.as_tensor(dist.astype(np.float32), device=device).contiguous()
+        self.n_atoms_dev = torch.as_tensor(num_atoms.astype(np.int32), device=device).contiguous()
+        self.device = device
+
+    def batch(self, mol_idx: np.ndarray) -> "DtnnBatch":
+        mol_idx = np.ascontiguousarray(mol_idx, np.int64)
+        if mol_idx.size and (mol_idx.min() < 0 or mol_idx.max() >= self.num_atoms.shape[0]):
+            raise ValueError("molecule index outside the resident set")
+        n = self.num_atoms[mol_idx]
+        n_atoms, n_pairs = int(n.sum()), int((n * n).sum())
+        idx = torch.as_tensor(mol_idx.astype(np.int32), device=self.device)
+        atom_off, pair_off, z, d, mem_i, mem_j = ops.dtnn_collate(self.z, self.dist, self.n_atoms_dev, idx, n_atoms, n_pairs)
+        return DtnnBatch(z, d, mem_i, mem_j, atom_off, pair_off, len(mol_idx))
+
+
+class DtnnBatch:
+    """One collated batch on the device (``gcmi_dtnn_collate``): atom numbers, per pair the distance and both
+    memberships (sorted by first atom by construction), atom offsets (the molecules' CSR) and pair offsets."""
+
+    def __init__(self, atom_number, distance, mem_i, mem_j, atom_off, pair_off, n_mols):
+        self.atom_number, self.distance, self.mem_i, self.mem_j = atom_number, distance, mem_i, mem_j
+        self.atom_off, self.pair_off, self.n_mols = atom_off, pair_off, int(n_mols)
+        self._membership = None
+
+    @property
+    def atom_membership(self) -> torch.Tensor:
+        if self._membership is None:
+            counts = (self.atom_off[1:] - self.atom_off[:-1]).to(torch.int64)
+            self._membership = torch.repeat_interleave(torch.arange(self.n_mols, device=counts.device), counts,
+                                                       output_size=int(self.atom_number.numel()))
+        return self._membership
+
+
+class DTNN(nn.Module):
+    """The reference's module: embedding, ``n_steps`` interaction steps, gather, final linear layer."""
+
+    def __init__(self, n_tasks: int, n_embedding: int = 30, n_hidden: int = 100, n_distance: int = 100,
+                 distance_min: float = -1, distance_max: float = 18, output_activation: bool = True,
+                 mode: str = "regression", dropout: float = 0.0, n_steps: int = 2):
+        super(DTNN, self).__init__()
+        self.n_tasks = n_tasks
+        self.n_embedding = n_embedding
+        self.n_hidden = n_hidden
+        self.n_distance = n_distance
+        self.distance_min = distance_min
+        self.distance_max = distance_max
+        self.output_activation = output_activation
+        self.mode = mode
+        self.dropout = dropout
+        self.n_steps = n_steps
+        self.dtnn_embedding = layers.DTNNEmbedding(n_embedding=self.n_embedding)
+        self.dtnn_step = nn.ModuleList()
+        for _ in range(self.n_steps):
+            self.dtnn_step.append(layers.DTNNStep(n_embedding=self.n_embedding, n_distance=self.n_distance))
+        self.dtnn_gather = layers.DTNNGather(n_embedding=self.n_embedding, layer_sizes=[self.n_hidden],
+                                             n_outputs=self.n_tasks, output_activation=self.output_activation)
+        self.linear = nn.Linear(self.n_tasks, self.n_tasks)
+
+    def _drop(self, x):
+        # a fresh module per call, as in the reference: always in training mode (see the module docstring)
+        return nn.Dropout(self.dropout)(x) if self.dropout else x
+
+    def forward(self, inputs):
+        dev = self.linear.weight.device
+        if isinstance(inputs, DtnnBatch):
+            step = (self.distance_max - self.distance_min) / self.n_distance
+            x = self.dtnn_embedding(inputs.atom_number, validated=True)
+            plan = layers.PairPlan(inputs.distance, True, inputs.mem_i, inputs.mem_j, x.shape[0], self.distance_min, step)
+            membership, n_mols, mol_ptr = inputs.atom_membership, inputs.n_mols, inputs.atom_off
+        else:
+            if len(inputs) != 5:
+                raise ValueError("DTNN takes [atom_number, distance, atom_membership, distance_membership_i, "
+                                 "distance_membership_j]")
+            atom_number, distance, membership, mem_i, mem_j = inputs
+            x = self.dtnn_embedding(atom_number)
+            distance = torch.as_tensor(distance)
+            if distance.dim() != 2 or distance.shape[1] != self.n_distance:
+                raise ValueError("DTNN: distance must be the (pairs, %d) Gaussian matrix" % self.n_distance)
+            distance = ops.rowmajor(distance.to(device=dev, dtype=torch.float32))
+            if distance.shape[0] != torch.as_tensor(mem_i).numel():
+                raise ValueError("DTNN: one Gaussian row per pair of the memberships")
+            plan = layers.PairPlan.checked(distance, False, mem_i, mem_j, x.shape[0], dev)
+            n_mols, mol_ptr = None, None
+        if not x.is_cuda:
+            raise ValueError("DTNN: the model must live on the GPU (there is no CPU path)")
+        for i in range(self.n_steps):
+            x = self.dtnn_step[i].interact(self._drop(x), plan)
+        gathered = self.dtnn_gather([self._drop(x), membership], n_molecules=n_mols, mol_ptr=mol_ptr)
+        gathered = self._drop(gathered)
+        return ops.LinearFn.apply(gathered, self.linear.weight, self.linear.bias, False, False)
+
+
+class DTNNModel(TorchModel):
+    """DTNN for regression on Coulomb-matrix datasets (QM7 / QM8 / QM9 presets of the reference)."""
+
+    def __init__(self, n_tasks: int, n_embedding: int = 30, n_hidden: int = 100, n_distance: int = 100,
+                 distance_min: float = -1, distance_max: float = 18, output_activation: bool = True,
+                 mode: str = "regression", dropout: float = 0.0, n_steps: int = 2, **kwargs):
+        if dropout < 0 or dropout > 1:
+            raise ValueError("dropout probability has to be between 0 and 1, " "but got {}".format(dropout))
+        model = DTNN(n_tasks=n_tasks, n_embedding=n_embedding, n_hidden=n_hidden, n_distance=n_distance,
+                     distance_min=distance_min, distance_max=distance_max, output_activation=output_activation,
+                     mode=mode, dropout=dropout, n_steps=n_steps)
+        if mode not in ['regression']:
+            raise ValueError("Only 'regression' mode is currently supported")
+        super(DTNNModel, self).__init__(model, L2Loss(), ["prediction"], **kwargs)
+        self._flat_step = True  # parameters, gradients and optimizer state in flat buffers (TorchModel._ensure_built)
+        self._resident = None   # (the X array it was built from, ResidentCoulombSet)
+
+    def _to_device(self, x):
+        # index arrays stay on the host: they are validated there before any launch
+        if not torch.is_tensor(x) and np.asarray(x).dtype.kind in "iu":
+            return np.asarray(x)
+        return super(DTNNModel, self)._to_device(x)
+
+    def _prepare_batch(self, batch):
+        inputs, labels, weights = batch
+        if isinstance(inputs, DtnnBatch):
+            return (inputs, [self._to_device(x) for x in labels or ()], [self._to_device(x) for x in weights or ()])
+        return super(DTNNModel, self)._prepare_batch(batch)
+
+    def default_generator(self, dataset, epochs: int = 1, mode: str = 'fit', deterministic: bool = True,
+                          pad_batches: bool = True):
+        """``(batch_coulomb_matrix_features(X_b, ...), [y_b], [w_b])`` per batch: the reference's contract, Gaussian
+        matrix included."""
+        for _ in range(epochs):
+            for (X_b, y_b, w_b, _ids) in dataset.iterbatches(batch_size=self.batch_size, deterministic=deterministic,
+                                                             pad_batches=pad_batches):
+                yield (batch_coulomb_matrix_features(X_b, self.model.distance_max, self.model.distance_min,
+                                                     self.model.n_distance), [y_b], [w_b])
+
+    def resident_set(self, X: np.ndarray, key=None) -> ResidentCoulombSet:
+        """The resident set of ``X``, kept until another array (``key``: another dataset state) is asked for."""
+        key = X if key is None else key
+        held = self._resident
+        same = held is not None and (held[0] is key or
+                                     (isinstance(key, tuple) and isinstance(held[0], tuple) and held[0] == key))
+        if not same:
+            self._resident = (key, ResidentCoulombSet(X, self.device, self.model.dtnn_embedding.periodic_table_length))
+        return self._resident[1]
+
+    @staticmethod
+    def _is_coulomb(shape, dtype) -> bool:
+        return len(shape) == 3 and shape[1] == shape[2] and 0 < shape[1] <= ops.DTNN_MAX_ATOMS and np.dtype(dtype).kind == "f"
+
+    def _index_batches(self, dataset, epochs, deterministic, pad_batches):
+        """(resident set, iterator of (molecule indices, y_b, w_b)) in the order, with the shuffles and the padding of
+        the dataset's own ``iterbatches``; None when the dataset is not an in-memory or on-disk Coulomb-matrix set."""
+        if self.device.type != "cuda":
+            return None
+        if isinstance(dataset, NumpyDataset):
+            X = dataset.X
+            if not (isinstance(X, np.ndarray) and self._is_coulomb(X.shape, X.dtype)):
+                return None
+            rs = self.resident_set(X)
+            index_set = NumpyDataset(np.arange(X.shape[0]), dataset.y, dataset.w, dataset.ids)
+
+            def walk():
+                for _ in range(epochs):
+                    for (idx, y_b, w_b, _ids) in index_set.iterbatches(batch_size=self.batch_size,
+                                                                       deterministic=deterministic,
+                                                                       pad_batches=pad_batches):
+                        yield idx, y_b, w_b
+            return rs, walk()
+        if isinstance(dataset, DiskDataset):
+            shards = list(dataset.itershards())
+            if not shards or not all(isinstance(sh[0], np.ndarray) and self._is_coulomb(sh[0].shape, sh[0].dtype)
+                                     for sh in shards) or len({sh[0].shape[1] for sh in shards}) != 1:
+                return None
+            lens = [len(sh[0]) for sh in shards]
+            offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+            X = np.concatenate([sh[0] for sh in shards], axis=0)
+            y = None if shards[0][1] is None else np.concatenate([sh[1] for sh in shards], axis=0)
+            w = None if shards[0][2] is None else np.concatenate([sh[2] for sh in shards], axis=0)
+            # (an array read from disk is a new object every time: the set is kept per dataset directory and contents)
+            import hashlib
+            key = (dataset.data_dir, X.shape, hashlib.blake2b(np.ascontiguousarray(X).data, digest_size=16).hexdigest())
+            rs = self.resident_set(X, key)
+            ids = np.arange(X.shape[0])
+
+            def walk():
+                for _ in range(epochs):  # one pass per epoch, as default_generator asks iterbatches for
+                    for shard_of_row, row_in_shard, bs in dataset.batch_plan(None, self.batch_size, 1, deterministic):
+                        idx = offsets[shard_of_row] + row_in_shard
+                        y_b, w_b = (None if y is None else y[idx]), (None if w is None else w[idx])
+                        if pad_batches:
+                            idx, y_b, w_b, _ = pad_batch(bs, idx, y_b, w_b, ids[idx])
+                        yield idx, y_b, w_b
+            return rs, walk()
+        return None
+
+    def _batch_generator(self, dataset, epochs: int = 1, mode: str = 'fit', deterministic: bool = True,
+                         pad_batches: bool = True):
+        """The resident-set route for a ``NumpyDataset`` / ``DiskDataset`` of ``(n, A, A)`` Coulomb matrices: the
+        molecule INDICES follow the dataset's own batch walk (same permutations from ``np.random``, same padding), the
+        device collates.  Anything else: ``default_generator``."""
+        routed = self._index_batches(dataset, epochs, deterministic, pad_batches)
+        if routed is None:
+            yield from self.default_generator(dataset, epochs=epochs, mode=mode, deterministic=deterministic,
+                                              pad_batches=pad_batches)
+            return
+        rs, walk = routed
+        for idx, y_b, w_b in walk:
+            yield (rs.batch(idx), [y_b], [w_b])

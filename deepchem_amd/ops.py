@@ -797,6 +797,76 @@ def tanh_(x: torch.Tensor) -> torch.Tensor:
     return x
 
 
+# ------------------------------------------------------------------ DTNN
+DTNN_MAX_EMBEDDING, DTNN_MAX_HIDDEN, DTNN_MAX_DISTANCE, DTNN_MAX_ATOMS = 64, 64, 128, 64
+
+
+def _dtnn_common(src, from_distance, mem_i, mem_j, ah, w_df, b_df, w_fc):
+    """The argument list both directions of the pair interaction share, checked against each other."""
+    ah = _mat(ah, "ah")
+    w_df, w_fc = _mat(w_df, "W_df"), _mat(w_fc, "W_fc")
+    K, H = w_df.shape
+    E = w_fc.shape[1]
+    if w_fc.shape[0] != H or ah.shape[1] != H:
+        raise ValueError("dtnn_pair: W_df (%d, %d), W_fc %s and atom rows of %d columns do not chain" %
+                         (K, H, tuple(w_fc.shape), ah.shape[1]))
+    if E > DTNN_MAX_EMBEDDING or H > DTNN_MAX_HIDDEN or K > DTNN_MAX_DISTANCE:
+        raise ValueError("dtnn_pair covers n_embedding <= %d, n_hidden <= %d, n_distance <= %d (got %d, %d, %d)" %
+                         (DTNN_MAX_EMBEDDING, DTNN_MAX_HIDDEN, DTNN_MAX_DISTANCE, E, H, K))
+    if not (w_df.is_contiguous() and w_fc.is_contiguous()):
+        raise ValueError("dtnn_pair: weights must be contiguous")
+    P = mem_i.numel()
+    _i32vec(mem_i, "mem_i"), _i32vec(mem_j, "mem_j", P)
+    if from_distance:
+        _vec(src, "distance", P)
+        ld_src = 1
+    else:
+        _mat(src, "gaussian", rows=P, cols=K)
+        ld_src = _ld(src)
+    return (_ptr(src), ld_src, 1 if from_distance else 0, _ptr(mem_i), _ptr(mem_j), P, ah.shape[0], _ptr(ah), _ld(ah), H,
+            _ptr(w_df), _ptr(_vec(b_df, "b_df", H)), K, _ptr(w_fc), E), (P, ah.shape[0], K, H, E)
+
+
+def dtnn_pair_fwd(src, from_distance: bool, mem_i, mem_j, ah, w_df, b_df, w_fc, distance_min: float = 0.0,
+                  step: float = 1.0) -> torch.Tensor:
+    """Y[i] = sum_{p: mem_i[p] = i} tanh(((g_p . W_df + b_df) * ah[mem_j[p]]) . W_fc); ``src`` = the distances
+    (``from_distance``) or the Gaussian matrix.  The memberships must have been validated (inside [0, N), mem_i sorted)."""
+    args, (P, N, K, H, E) = _dtnn_common(src, from_distance, mem_i, mem_j, ah, w_df, b_df, w_fc)
+    y = torch.empty((N, E), dtype=torch.float32, device=ah.device)
+    _lib.call("gcmi_dtnn_pair_fwd", *args, float(distance_min), float(step), _ptr(y), _ld(y), _stream())
+    return y
+
+
+def dtnn_pair_bwd(src, from_distance: bool, mem_i, mem_j, ah, w_df, b_df, w_fc, distance_min: float, step: float,
+                  dy, dw_df, db_df, dw_fc) -> torch.Tensor:
+    """d_ah (returned); dW_df, db_df, dW_fc are ADDED into the given buffers."""
+    args, (P, N, K, H, E) = _dtnn_common(src, from_distance, mem_i, mem_j, ah, w_df, b_df, w_fc)
+    dy = _mat(dy, "dy", rows=N, cols=E)
+    dah = torch.empty((N, H), dtype=torch.float32, device=ah.device)
+    _lib.call("gcmi_dtnn_pair_bwd", *args, float(distance_min), float(step), _ptr(dy), _ld(dy), _ptr(dah), _ld(dah),
+              _ptr(_vec(dw_df.reshape(-1), "dW_df", K * H)), _ptr(_vec(db_df, "db_df", H)),
+              _ptr(_vec(dw_fc.reshape(-1), "dW_fc", H * E)), _stream())
+    return dah
+
+
+def dtnn_collate(z_all, dist_all, n_atoms_all, mol_idx, n_atoms: int, n_pairs: int):
+    """One batch from a resident Coulomb-matrix set: (atom_off, pair_off, z, d, mem_i, mem_j) on the device."""
+    M, A = z_all.shape
+    dev = z_all.device
+    _i32vec(z_all.reshape(-1), "z_all"), _i32vec(n_atoms_all, "n_atoms_all", M), _i32vec(mol_idx, "mol_idx")
+    _vec(dist_all.reshape(-1), "dist_all", M * A * A)
+    B = mol_idx.numel()
+    atom_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    pair_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+    z = torch.zeros(n_atoms, dtype=torch.int32, device=dev)
+    d = torch.zeros(n_pairs, dtype=torch.float32, device=dev)
+    mem_i = torch.zeros(n_pairs, dtype=torch.int32, device=dev)
+    mem_j = torch.zeros(n_pairs, dtype=torch.int32, device=dev)
+    _lib.call("gcmi_dtnn_collate", _ptr(z_all), _ptr(dist_all), _ptr(n_atoms_all), M, A, _ptr(mol_idx), B, n_atoms, n_pairs,
+              _ptr(atom_off), _ptr(pair_off), _ptr(z), _ptr(d), _ptr(mem_i), _ptr(mem_j), _stream())
+    return atom_off, pair_off, z, d, mem_i, mem_j
+
+
 # ------------------------------------------------------------------ message passing
 def edge_network_sum(g: torch.Tensor, n_hidden: int, pair_feat: torch.Tensor, dst_ptr: torch.Tensor,
                      src: torch.Tensor) -> torch.Tensor:

@@ -930,6 +930,40 @@ int gcmi_small_bind(gcmi_small_batch* out, const gcmi_graph* graphs, const int64
                     const float* d_weights, int64_t weight_stride, float* d_logits, float* d_probs,
                     int64_t logit_stride, float* d_fingerprint, int64_t fp_stride);
 
+/* ---------------------------------------------------------------- DTNN (csrc/dtnn.hip)
+ * gcmi_dtnn_pair_fwd: the fused pair interaction of DTNNStep (models/torch_models/layers.py:3844-3881 of the
+ *   reference, without its self term and residual).  For n_pairs pairs sorted by first atom (d_mem_i non-decreasing,
+ *   d_mem_j; both inside [0, n_atoms): the CALLER validates them, the kernel only clamps) and atom rows
+ *   d_ah [n_atoms x n_hidden] = C . W_cf + b_cf:
+ *       y[i] = sum over pairs p with mem_i[p] = i of tanh(((g_p . W_df + b_df) (.) ah[mem_j[p]]) . W_fc)
+ *   from_distance != 0: d_src holds one distance per pair and g_p[k] = exp(-(d - distance_min - k step)^2 / (2 step^2))
+ *   is generated in registers; else d_src is the n_pairs x n_distance Gaussian matrix (leading dimension ld_src).
+ *   d_w_df [n_distance x n_hidden], d_b_df [n_hidden], d_w_fc [n_hidden x n_embedding], contiguous.  y
+ *   [n_atoms x n_embedding] is cleared here (float atomics: a run of pairs adds once per 32-pair tile it touches).
+ *   n_embedding <= 64, n_hidden <= 64, n_distance <= 128, else GCMI_ERR_ARG.  Nothing of size n_pairs is written.
+ * gcmi_dtnn_pair_bwd: given d_dy [n_atoms x n_embedding], recomputes the forward from the same inputs and writes
+ *   d_dah [n_atoms x n_hidden] (cleared here, atomics by mem_j) and ADDS dW_df, db_df, dW_fc into their buffers.
+ * gcmi_dtnn_collate: a batch from a resident set (d_z_all [n_mols_all x max_atoms] atom numbers, d_dist_all
+ *   [n_mols_all x max_atoms x max_atoms] distances, d_n_atoms_all [n_mols_all]; max_atoms <= 64): for the molecules
+ *   d_mol_idx [n_batch], atom and pair offsets [n_batch + 1], atom numbers [n_atoms], and per pair, in row-major (i, j)
+ *   order per molecule, the distance and both memberships.  n_atoms / n_pairs: the sizes of the outputs (the caller
+ *   knows the atom counts); a molecule that would not fit them is left out.                                        */
+int gcmi_dtnn_pair_fwd(const float* d_src, int64_t ld_src, int32_t from_distance, const int32_t* d_mem_i,
+                       const int32_t* d_mem_j, int64_t n_pairs, int32_t n_atoms, const float* d_ah, int64_t ldah,
+                       int32_t n_hidden, const float* d_w_df, const float* d_b_df, int32_t n_distance,
+                       const float* d_w_fc, int32_t n_embedding, double distance_min, double step, float* d_y,
+                       int64_t ldy, void* stream);
+int gcmi_dtnn_pair_bwd(const float* d_src, int64_t ld_src, int32_t from_distance, const int32_t* d_mem_i,
+                       const int32_t* d_mem_j, int64_t n_pairs, int32_t n_atoms, const float* d_ah, int64_t ldah,
+                       int32_t n_hidden, const float* d_w_df, const float* d_b_df, int32_t n_distance,
+                       const float* d_w_fc, int32_t n_embedding, double distance_min, double step, const float* d_dy,
+                       int64_t lddy, float* d_dah, int64_t lddah, float* d_dw_df, float* d_db_df, float* d_dw_fc,
+                       void* stream);
+int gcmi_dtnn_collate(const int32_t* d_z_all, const float* d_dist_all, const int32_t* d_n_atoms_all,
+                      int32_t n_mols_all, int32_t max_atoms, const int32_t* d_mol_idx, int32_t n_batch,
+                      int32_t n_atoms, int64_t n_pairs, int32_t* d_atom_off, int32_t* d_pair_off, int32_t* d_z,
+                      float* d_d, int32_t* d_mem_i, int32_t* d_mem_j, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Optional per-kernel timing with hipEvents recorded on `stream` around the
  * launches of one kernel family (bench.py roofline).  id: see GCMI_K_*.       */
