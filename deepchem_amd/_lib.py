@@ -230,6 +230,9 @@ _SIGNATURES = {
     "gcmi_dtnn_pair_bwd": [_P, c_int64, c_int32, _P, _P, c_int64, c_int32, _P, c_int64, c_int32, _P, _P, c_int32, _P,
                            c_int32, c_double, c_double, _P, c_int64, _P, c_int64, _P, _P, _P, _P],
     "gcmi_dtnn_collate": [_P, _P, _P, c_int32, c_int32, _P, c_int32, c_int32, c_int64, _P, _P, _P, _P, _P, _P, _P],
+    "gcmi_dmpnn_message": [c_int32, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+    "gcmi_dmpnn_update_fwd": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int64,
+                              _P, c_int64, _P],
     "gcmi_model_forward": [_MD, _G, _P, _MIO, c_int32, _P],
     "gcmi_model_loss_backward": [_MD, _G, _P, _P, _MIO, _P, _P, c_int64, _I64P, _I64P, _P],
     # (the two pointers before the stream: gcmi_stat_sync_fn and its context)

@@ -222,3 +222,37 @@ class WeaveFeaturizer(_SmilesFeaturizer):
             edges = np.stack([np.repeat(np.arange(n), n), np.tile(np.arange(n), n)])
             out[i] = WeaveMol(feats[a0:a1], pairs, edges)
         return out
+
+
+class NativeGraphFeaturizer(_SmilesFeaturizer):
+    """A ``GraphData`` per SMILES from this package's own reader, for ``DMPNNModel``: the 75 atom features of
+    ``ConvMolFeaturizer``, the 6 bond features of ``WeaveFeaturizer``'s bond type block, and every bond as the two
+    directed rows ``2k`` (a -> b) and ``2k + 1`` (b -> a), so that row ``b`` and row ``b ^ 1`` are each other's
+    reverse -- the pairing ``DMPNNModel`` expects.  ``global_features`` is empty.
+
+    This is NOT the reference's ``DMPNNFeaturizer`` (133 atom and 14 bond features from rdkit's atomic masses, chiral
+    tags and bond stereo): use it with ``DMPNNModel(use_default_fdim=False, atom_fdim=75, bond_fdim=6)``.  A model
+    trained on one featurization does not read the other."""
+    name = ['native_graph']
+
+    def __init__(self, n_threads: Optional[int] = None):
+        self.dtype = object
+        self.n_threads = n_threads
+
+    def featurize(self, datapoints, log_every_n: int = 1000, **kwargs) -> np.ndarray:
+        from deepchem_amd.feat.graph_data import GraphData
+        smiles = _as_list(datapoints)
+        r = read_smiles(smiles, adjacency=False, bonds=True, n_threads=self.n_threads)
+        out = np.empty(len(smiles), dtype=object)
+        for i in range(len(smiles)):
+            if not r["valid"][i]:
+                out[i] = np.array([])
+                continue
+            a0, a1 = int(r["atom_off"][i]), int(r["atom_off"][i + 1])
+            b0, b1 = int(r["bond_off"][i]), int(r["bond_off"][i + 1])
+            ends = r["bond_atoms"][b0:b1].astype(np.int64)  # (B, 2), atoms local to the molecule
+            edge_index = np.stack([ends.reshape(-1), ends[:, ::-1].reshape(-1)])  # rows 2k: a -> b, 2k + 1: b -> a
+            out[i] = GraphData(r["atom_features"][a0:a1].copy(), edge_index,
+                               np.repeat(r["bond_features"][b0:b1], 2, axis=0),
+                               global_features=np.empty(0, np.float32))
+        return out

@@ -60,3 +60,19 @@ class SoftmaxCrossEntropy(Loss):
 
     _gcmi_kind = 0
     _criterion = staticmethod(_label_weighted_log_softmax)
+
+
+class SparseSoftmaxCrossEntropy(Loss):
+    """Cross entropy of INTEGER class labels, shape (batch) or (batch, tasks) (a trailing unit axis is dropped), against
+    softmax(logits) of shape (batch, classes) or (batch, tasks, classes) (losses.py:262-296 of the reference).  The
+    criterion is torch's: one number per molecule and task, no kernel of its own."""
+
+    def _create_pytorch_loss(self):
+        def loss(output, labels):
+            if output.dim() == 3:
+                output = output.permute(0, 2, 1)  # cross_entropy wants (batch, classes, tasks)
+            if labels.dim() == output.dim():
+                labels = labels.squeeze(-1)
+            return F.cross_entropy(output, labels.long(), reduction='none')
+
+        return loss

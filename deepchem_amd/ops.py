@@ -868,6 +868,76 @@ def dtnn_collate(z_all, dist_all, n_atoms_all, mol_idx, n_atoms: int, n_pairs: i
 
 
 # ------------------------------------------------------------------ message passing
+# ------------------------------------------------------------------ D-MPNN
+DMPNN_MAX_DEGREE = 32
+
+
+def dmpnn_message(x: Optional[torch.Tensor], out_ptr: torch.Tensor, rev: torch.Tensor, transposed: bool = False,
+                  add: Optional[torch.Tensor] = None, want_s: bool = False, want_q: bool = True,
+                  q_out: Optional[torch.Tensor] = None):
+    """``gcmi_dmpnn_message`` over a VALIDATED bond plan (``out_ptr`` of n_atoms + 1 entries, ``rev`` of n_bonds:
+    ``DmpnnBatch`` checks both before any launch).  Forward: ``q[b] = S[a] - x[rev[b]]``, ``S[a]`` = the sum of the rows
+    arriving at atom ``a``; transposed: ``q[rev[b]] = T[a] - x[b] + add[a]``, ``T[a]`` = the sum over a's outgoing run
+    (``x`` or ``add`` may be None = zeros).  Returns ``(S or T | None, q | None)``; ``q_out``: write q there."""
+    n_atoms, n_bonds = out_ptr.numel() - 1, rev.numel()
+    _i32vec(out_ptr, "out_ptr"), _i32vec(rev, "rev")
+    if n_atoms < 0:
+        raise ValueError("dmpnn_message: out_ptr needs n_atoms + 1 entries")
+    if add is not None and not transposed:
+        raise ValueError("dmpnn_message: add (the gradient of the atom sums) belongs to the transposed direction")
+    src = x if x is not None else add
+    if src is None:
+        raise ValueError("dmpnn_message: no input rows")
+    if x is not None:
+        _mat(x, "x", rows=n_bonds)
+    d = src.shape[1]
+    if add is not None:
+        _mat(add, "add", rows=n_atoms, cols=d)
+    s = torch.empty((n_atoms, d), dtype=torch.float32, device=src.device) if want_s else None
+    q = None
+    if want_q:
+        q = q_out if q_out is not None else torch.empty((n_bonds, d), dtype=torch.float32, device=src.device)
+        _mat(q, "q", rows=n_bonds, cols=d)
+    if n_bonds == 0 or n_atoms == 0:  # nothing to launch: the sums of a batch without bonds are zero rows
+        return (s.zero_() if s is not None else None), q
+    _lib.call("gcmi_dmpnn_message", 1 if transposed else 0, _ptr(x), _ld(x) if x is not None else 0, d, _ptr(out_ptr),
+              _ptr(rev), n_atoms, n_bonds, _ptr(add), _ld(add) if add is not None else 0, _ptr(s),
+              _ld(s) if s is not None else 0, _ptr(q), _ld(q) if q is not None else 0, _stream())
+    return s, q
+
+
+DMPNN_UPDATE_MAX_HIDDEN = 320
+
+
+def dmpnn_update_scratch_floats(d: int) -> int:
+    """Floats of the weight-image scratch of ``gcmi_dmpnn_update_fwd`` at width d."""
+    return ((d + 15) // 16) * ((d + 31) // 32) * 768
+
+
+def dmpnn_update_fwd(x: torch.Tensor, inp: torch.Tensor, weight: torch.Tensor, out_ptr: torch.Tensor, rev: torch.Tensor,
+                     bond_src: torch.Tensor, relu: bool, scratch: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``h[b] = act(inp[b] + (S[a] - x[rev[b]]) . weight^T)`` over a VALIDATED bond plan, the aggregated rows never
+    written (``gcmi_dmpnn_update_fwd``; d <= 320, nn.Linear weight).  ``scratch``: a contiguous float32 CUDA vector of
+    at least ``dmpnn_update_scratch_floats(d)``, overwritten with the split image of ``weight``."""
+    n_atoms, n_bonds = out_ptr.numel() - 1, rev.numel()
+    _i32vec(out_ptr, "out_ptr"), _i32vec(rev, "rev"), _i32vec(bond_src, "bond_src", n_bonds)
+    _mat(x, "x", rows=n_bonds)
+    d = x.shape[1]
+    if d > DMPNN_UPDATE_MAX_HIDDEN:
+        raise ValueError("dmpnn_update_fwd covers d_hidden <= %d (got %d)" % (DMPNN_UPDATE_MAX_HIDDEN, d))
+    _mat(inp, "input", rows=n_bonds, cols=d), _mat(weight, "weight", rows=d, cols=d)
+    if not (scratch.is_cuda and scratch.dtype == torch.float32 and scratch.is_contiguous()):
+        raise ValueError("dmpnn_update_fwd: scratch must be a contiguous float32 CUDA tensor")
+    h = torch.empty((n_bonds, d), dtype=torch.float32, device=x.device) if out is None else _mat(out, "out", n_bonds, d)
+    if n_bonds == 0:
+        return h
+    _lib.call("gcmi_dmpnn_update_fwd", _ptr(x), _ld(x), _ptr(inp), _ld(inp), _ptr(weight), _ld(weight), d, 1 if relu else 0,
+              _ptr(out_ptr), _ptr(rev), _ptr(bond_src), n_atoms, n_bonds, _ptr(scratch), scratch.numel(), _ptr(h), _ld(h),
+              _stream())
+    return h
+
+
 def edge_network_sum(g: torch.Tensor, n_hidden: int, pair_feat: torch.Tensor, dst_ptr: torch.Tensor,
                      src: torch.Tensor) -> torch.Tensor:
     g = _mat(g, "g")

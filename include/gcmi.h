@@ -964,6 +964,39 @@ int gcmi_dtnn_collate(const int32_t* d_z_all, const float* d_dist_all, const int
                       int32_t n_atoms, int64_t n_pairs, int32_t* d_atom_off, int32_t* d_pair_off, int32_t* d_z,
                       float* d_d, int32_t* d_mem_i, int32_t* d_mem_j, void* stream);
 
+/* ---------------------------------------------------------------- D-MPNN (dmpnn.hip)
+ * The message aggregation of the directed message-passing network (deepchem/models/torch_models/layers.py:1629,
+ * `message[mapping].sum(1)`, and :1539, `h_message[atom_to_incoming_bonds].sum(1)`) over a batch whose directed bonds
+ * are sorted by SOURCE atom.  d_out_ptr [n_atoms + 1]: the outgoing bonds of atom a are the run
+ * R(a) = [out_ptr[a], out_ptr[a+1]); d_rev [n_bonds]: the position of the reverse bond, an involution without fixed
+ * points (the bonds arriving at a are rev[b], b in R(a)).  Both must have been validated by the caller; the kernel skips
+ * rows outside [0, n_bonds).  Rows are float32 with ld >= d, any d >= 1 (16-byte aligned rows of whole 16-byte pieces
+ * take the vector path, anything 4-byte aligned the scalar one).
+ *   transposed = 0:  S[a] = sum_{b in R(a)} x[rev[b]]  -> d_s [n_atoms x d] (optional);
+ *                    q[b] = S[a] - x[rev[b]]           -> d_q [n_bonds x d] (optional).  d_add must be NULL.
+ *   transposed = 1:  the adjoint.  T[a] = sum_{b in R(a)} x[b] -> d_s (optional);
+ *                    q[rev[b]] = T[a] - x[b] + add[a]  -> d_q (optional): every bond row is written exactly once, no
+ *                    atomics.  d_x (the gradient of q) or d_add (the gradient of S, [n_atoms x d]) may be NULL = zeros.
+ * d_q must not be d_x.  An atom without bonds gets a zero d_s row and nothing else; n_bonds == 0 launches no kernel
+ * (d_s is cleared).  NULL pointers, ld < d and buffers off a 4-byte boundary: GCMI_ERR_ARG before any launch.  */
+int gcmi_dmpnn_message(int32_t transposed, const float* d_x, int64_t ldx, int32_t d, const int32_t* d_out_ptr,
+                       const int32_t* d_rev, int32_t n_atoms, int32_t n_bonds, const float* d_add, int64_t ldadd,
+                       float* d_s, int64_t lds, float* d_q, int64_t ldq, void* stream);
+/* The fused bond update of a message-passing round, forward only:
+ *     h[b] = act( input[b] + (S[a] - x[rev[b]]) . W^T ),   a = d_bond_src[b], act 0 none / 1 ReLU,
+ * with d_w [d_hidden x d_hidden] in nn.Linear layout (out x in, leading dimension ldw).  The aggregated rows are built
+ * in LDS as the A operand of the product and never written to memory; the product is the six-product split-bf16 on
+ * v_mfma_f32_32x32x16_bf16, float32 accuracy.  1 <= d_hidden <= 320 (zero-padded to the tile); above: GCMI_ERR_UNSUPPORTED
+ * with an error text -- no other kernel stands behind this entry.  d_bond_src [n_bonds]: the source atom of every bond
+ * (non-decreasing, consistent with d_out_ptr); every atom's degree must be at most 32 (validated by the caller).
+ * d_img_scratch: 16-byte aligned, scratch_floats >= ceil(d/16) * ceil(d/32) * 768 floats; it receives the split image of
+ * d_w, rebuilt by every call.  d_h may be d_input, not d_x.  NULL pointers, ld < d_hidden, misaligned buffers and a short
+ * scratch: GCMI_ERR_ARG before any launch; n_bonds == 0 launches nothing.                                             */
+int gcmi_dmpnn_update_fwd(const float* d_x, int64_t ldx, const float* d_input, int64_t ldi, const float* d_w, int64_t ldw,
+                          int32_t d_hidden, int32_t act, const int32_t* d_out_ptr, const int32_t* d_rev,
+                          const int32_t* d_bond_src, int32_t n_atoms, int32_t n_bonds, float* d_img_scratch,
+                          int64_t scratch_floats, float* d_h, int64_t ldh, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Optional per-kernel timing with hipEvents recorded on `stream` around the
  * launches of one kernel family (bench.py roofline).  id: see GCMI_K_*.       */
