@@ -272,3 +272,79 @@ def e2e_steps(graphs, y, w):
     one = [(DmpnnBatch.from_graphs(list(graphs[i:i + bs])).host, y[i:i + bs], w[i:i + bs])
            for i in range(0, len(graphs), bs)]
     return one * E2E["epochs"]
+
+
+# ------------------------------------------------------------------------------------------------ fused update: edges
+# What follows restates the index arithmetic of dmpnn_update_kernel / gcmi_dmpnn_update_fwd (csrc/dmpnn.hip) and builds
+# the cases of tests/test_gpu_dmpnn_edges.py.
+UPD_NB = (1, 2, 3, 5, 8, 10)  # the instantiated accumulator widths, in 32-column blocks
+UPD_STAGE, UPD_MAX_D, UPD_WAVES, UPD_GRID_CAP = 96, 320, 2, 2048
+
+
+def dmpnn_update_branch(d):
+    """(NB, n_chunks, n_ks): the instantiation ``gcmi_dmpnn_update_fwd`` launches at width d (the smallest NB holding
+    ceil(d / 32) column blocks), the 64-column staging chunks and the 16-wide k-steps."""
+    if not 1 <= d <= UPD_MAX_D:
+        raise ValueError("no fused update kernel at d = %d" % d)
+    n_nb = (d + 31) // 32
+    return min(nb for nb in UPD_NB if nb >= n_nb), (d + 63) // 64, (d + 15) // 16
+
+
+def update_passes(n_bonds):
+    """(tiles, workgroups, passes) of the fused update's launch."""
+    tiles = (n_bonds + 31) // 32
+    grid = max(1, min((tiles + UPD_WAVES - 1) // UPD_WAVES, UPD_GRID_CAP))
+    return tiles, grid, (tiles + grid * UPD_WAVES - 1) // (grid * UPD_WAVES)
+
+
+def staged_rows(out_ptr, bond_src, n_bonds):
+    """Per 32-row tile, the ``n_stage`` the update kernel computes: the rows from the start of the run of the tile's
+    first row's atom to the end of the run of its last row's atom, at most UPD_STAGE."""
+    out_ptr, bond_src = np.asarray(out_ptr, np.int64), np.asarray(bond_src, np.int64)
+    n_atoms = out_ptr.shape[0] - 1
+    out = []
+    for r0 in range(0, n_bonds, 32):
+        valid = min(32, n_bonds - r0)
+        a_lo = min(max(int(bond_src[r0]), 0), n_atoms - 1)
+        a_hi = min(max(int(bond_src[r0 + valid - 1]), a_lo), n_atoms - 1)
+        s0 = min(max(int(out_ptr[a_lo]), 0), r0)
+        s1 = max(min(int(out_ptr[a_hi + 1]), n_bonds), r0 + valid)
+        out.append(min(s1 - s0, UPD_STAGE))
+    return np.asarray(out, np.int64)
+
+
+def update_ref(dtype, x, inp, W, out_ptr, rev, relu):
+    """h = act(inp + (S[a] - x[rev[b]]) . W^T) through ``message``, every operation in ``dtype``."""
+    t = lambda a: torch.as_tensor(np.asarray(a)).to(dtype)  # noqa: E731
+    q, _ = message(t(x), out_ptr, torch.as_tensor(np.asarray(rev), dtype=torch.int64))
+    h = t(inp) + q @ t(W).t()
+    return (torch.relu(h) if relu else h).numpy()
+
+
+def update_f32(x, inp, W, out_ptr, rev, relu):
+    """The D-MPNN bond update in float32 on the CPU: the yardstick of the edge tests' bar."""
+    return update_ref(torch.float32, x, inp, W, out_ptr, rev, relu)
+
+
+def update_f64(x, inp, W, out_ptr, rev, relu):
+    return update_ref(torch.float64, x, inp, W, out_ptr, rev, relu)
+
+
+def cap_pair():
+    """One molecule of 126 bond rows with two degree-32 atoms A = 1 and B = 32 whose runs end on / begin at the two
+    ends of its second 32-row tile: row 0 is a leaf of A, rows 1..32 are A's run, rows 33..62 thirty more leaves of A,
+    rows 63..94 B's run (B is bonded to A), rows 95..125 B's 31 leaves.  Placed after a multiple of 32 rows, the tile
+    of rows 32..63 stages 31 + 32 + 31 = 94 rows.  (bonds, atoms)."""
+    A, B = 1, 32
+    bonds = [(A, 0)] + [(A, k) for k in range(2, 32)] + [(A, B)] + [(B, k) for k in range(33, 64)]
+    return bonds, 64
+
+
+def ring_arrays(n_rings, n):
+    """The batch arrays (mol_ptr, out_ptr, bond_src, rev) of ``n_rings`` rings of ``n`` atoms, built without a loop: atom
+    a owns rows 2a (to a + 1) and 2a + 1 (to a - 1)."""
+    a = np.arange(n_rings * n, dtype=np.int64)
+    base, loc = (a // n) * n, a % n
+    nxt, prv = base + (loc + 1) % n, base + (loc - 1) % n
+    rev = np.stack([2 * nxt + 1, 2 * prv], 1).reshape(-1)
+    return np.arange(n_rings + 1, dtype=np.int64) * n, 2 * np.arange(n_rings * n + 1, dtype=np.int64), np.repeat(a, 2), rev

@@ -102,3 +102,117 @@ def rel_err(got, want):
     """max |got - want| relative to the largest entry of ``want`` (at least tiny, so that an all-zero tensor compares)."""
     got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
     return float(np.max(np.abs(got - want)) / max(float(np.max(np.abs(want))), 1e-30)) if want.size else 0.0
+
+
+# ------------------------------------------------------------------------------------------------ kernel edges
+# What follows restates csrc/dtnn.hip's dispatch and launch arithmetic and builds the cases of tests/test_gpu_dtnn_edges.py.
+DTNN_MAX = (64, 64, 128)  # n_embedding, n_hidden, n_distance
+FWD_TILES_PER_WG, FWD_GRID_CAP = 8, 512    # launch_dtnn: kDtnnWaves * 2 tiles per workgroup, at most 512 workgroups
+BWD_TILES_PER_WG, BWD_GRID_CAP = 16, 256   # ... kDtnnWaves * 4, at most 256
+DTNN_WAVES = 4
+
+
+def dtnn_branch(E, H, K, from_distance):
+    """(nth, nte, KS, KT) of dispatch_dtnn: 32-column blocks of the hidden and the output width (the template
+    arguments beside ``from_distance``), 16-wide k-steps of the K -> H product, 32-row blocks of dW_df."""
+    if not (1 <= E <= DTNN_MAX[0] and 1 <= H <= DTNN_MAX[1] and 1 <= K <= DTNN_MAX[2]):
+        raise ValueError("no DTNN kernel for (E, H, K) = (%d, %d, %d)" % (E, H, K))
+    bool(from_distance)  # (an instantiation is (from_distance, nth, nte); the four counts do not depend on it)
+    return (H + 31) // 32, (E + 31) // 32, (K + 15) // 16, (K + 31) // 32
+
+
+def dtnn_grid(n_pairs, backward):
+    """(workgroups, uncapped workgroups, tiles, rounds of the busiest wave) of launch_dtnn."""
+    tiles = (n_pairs + 31) // 32
+    per, cap = (BWD_TILES_PER_WG, BWD_GRID_CAP) if backward else (FWD_TILES_PER_WG, FWD_GRID_CAP)
+    want = max(1, (tiles + per - 1) // per)
+    grid = min(want, cap)
+    waves = grid * DTNN_WAVES
+    return grid, want, tiles, (tiles + waves - 1) // waves
+
+
+def pair_list(runs, N, rng, same_j=None):
+    """(mem_i, mem_j) int64 from ``(atom, run length)`` entries with ascending atoms: mem_i repeats each atom over its
+    run, mem_j is random inside [0, N) or everywhere ``same_j``.  Valid under ``PairPlan.checked``."""
+    atoms = [int(a) for a, _ in runs]
+    if any(a < 0 or a >= N for a in atoms) or any(b < a for a, b in zip(atoms, atoms[1:])) or any(n < 0 for _, n in runs):
+        raise ValueError("pair_list: atoms must ascend inside [0, %d) and run lengths must not be negative" % N)
+    mem_i = np.repeat(np.asarray(atoms, np.int64), [int(n) for _, n in runs]) if runs else np.zeros(0, np.int64)
+    P = mem_i.shape[0]
+    if same_j is not None:
+        if not 0 <= same_j < N:
+            raise ValueError("pair_list: same_j outside [0, %d)" % N)
+        mem_j = np.full(P, int(same_j), np.int64)
+    else:
+        mem_j = rng.randint(0, max(N, 1), P).astype(np.int64)
+    return mem_i, mem_j
+
+
+def random_runs(P, N, rng):
+    """P pairs over random first atoms of [0, N), as the ``runs`` of ``pair_list``."""
+    atoms, counts = np.unique(np.sort(rng.randint(0, N, P)), return_counts=True)
+    return [(int(a), int(n)) for a, n in zip(atoms, counts)]
+
+
+def pair_case(mem_i, mem_j, N, E, H, K, rng):
+    """Operands of one pair-interaction case: distances (diagonal pairs at -100, as the model's batches have them),
+    atom rows, the three parameters and the upstream gradient, float32."""
+    P = mem_i.shape[0]
+    d = rng.uniform(0.9, 12.0, P)
+    d[mem_i == mem_j] = -100.0
+    return {"N": N, "mem_i": mem_i, "mem_j": mem_j, "d": d.astype(np.float32),
+            "ah": rng.normal(0, 1, (N, H)).astype(np.float32), "W_df": rng.normal(0, 0.15, (K, H)).astype(np.float32),
+            "b_df": rng.normal(0, 0.3, H).astype(np.float32), "W_fc": rng.normal(0, 0.2, (H, E)).astype(np.float32),
+            "dY": rng.normal(0, 1, (N, E)).astype(np.float32)}
+
+
+PAIR_TENSORS = ("Y", "d_ah", "d_W_df", "d_b_df", "d_W_fc")
+
+
+def pair_grads(dtype, gauss, c, chunk=32768):
+    """Y and the four gradients for the upstream gradient ``c["dY"]`` from ``pair_sum`` and its autograd, all in
+    ``dtype``, the pairs taken ``chunk`` at a time (Y and every gradient are sums over the pairs)."""
+    t = {k: torch.tensor(np.asarray(c[k]), dtype=dtype, requires_grad=True) for k in ("ah", "W_df", "b_df", "W_fc")}
+    gauss = torch.as_tensor(gauss).to(dtype)
+    mem_i, mem_j = torch.as_tensor(c["mem_i"], dtype=torch.int64), torch.as_tensor(c["mem_j"], dtype=torch.int64)
+    dY = torch.tensor(np.asarray(c["dY"]), dtype=dtype)
+    N, P = c["N"], mem_i.numel()
+    Y = torch.zeros((N, t["W_fc"].shape[1]), dtype=dtype)
+    for k in t.values():
+        k.grad = torch.zeros_like(k)
+    for p0 in range(0, P, chunk):
+        sl = slice(p0, min(P, p0 + chunk))
+        y = pair_sum(gauss[sl], t["ah"], mem_i[sl], mem_j[sl], t["W_df"], t["b_df"], t["W_fc"], N)
+        y.backward(dY)
+        Y += y.detach()
+    out = {"Y": Y.numpy()}
+    out.update({"d_" + k: v.grad.numpy() for k, v in t.items()})
+    return out
+
+
+def pair_f64(gauss, c, chunk=32768):
+    return pair_grads(torch.float64, gauss, c, chunk)
+
+
+def pair_f32(gauss, c, chunk=32768):
+    """The same restatement in float32 on the CPU, forward and autograd backward: the yardstick of the edge tests' bar
+    (what plain float32 arithmetic makes of the case)."""
+    return pair_grads(torch.float32, gauss, c, chunk)
+
+
+def collate_ref(z_all, dist_all, n_all, mol_idx):
+    """What ``gcmi_dtnn_collate`` must produce for valid and invalid (outside [0, M): no atoms, no pairs) entries of
+    ``mol_idx``: (atom_off, pair_off, z, d, mem_i, mem_j), from ``coulomb_matrix_pairs`` and the resident arrays."""
+    from deepchem_amd.utils.batch_utils import coulomb_matrix_pairs
+    mol_idx = np.asarray(mol_idx, np.int64)
+    M = n_all.shape[0]
+    ok = (mol_idx >= 0) & (mol_idx < M)
+    safe = np.where(ok, mol_idx, 0)
+    num = np.where(ok, n_all[safe], 0).astype(np.int64)
+    atom_mem, pair_mol, i, j, atom_off = coulomb_matrix_pairs(num)
+    pair_off = np.concatenate([[0], np.cumsum(num * num)])
+    local = np.arange(atom_off[-1]) - atom_off[atom_mem]
+    z = z_all[safe[atom_mem], local]
+    d = dist_all[safe[pair_mol], i, j]
+    return (atom_off.astype(np.int32), pair_off.astype(np.int32), z.astype(np.int32), d.astype(np.float32),
+            (i + atom_off[pair_mol]).astype(np.int32), (j + atom_off[pair_mol]).astype(np.int32))
