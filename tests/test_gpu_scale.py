@@ -52,24 +52,15 @@ def _native_step(packed, y, w, tasks, grad_mode, state, use_codes=False, widths=
 
 def _oracle_step(packed, y, w, tasks, grad_mode, state, double=False, widths=(64, 64), dense=128, mode="classification",
                  n_classes=2, n_feat=75):
-    """One training-mode forward + loss + backward of the oracle.  ``double``: the same op sequence in float64 (the
-    yardstick: how far the reference's own float32 accumulation is from exact arithmetic at this batch size)."""
-    import contextlib
+    """One training-mode forward + loss + backward of the oracle on the whole set as one batch
+    (tests/small_refs.py::oracle_step).  ``double``: the same op sequence in float64 (the yardstick: how far the
+    reference's own float32 accumulation is from exact arithmetic at this batch size)."""
     from oracle import graphconv_oracle as O
-    from tests.util import oracle_batch, oracle_convmols
+    from tests.small_refs import oracle_step
     n = packed.n_mols
     cfg = O.ModelConfig(tasks, graph_conv_layers=tuple(widths), number_input_features=(n_feat,) + tuple(widths[:-1]),
                         dense_layer_size=dense, mode=mode, n_classes=n_classes, batch_size=n)
-    inputs, labels, weights = oracle_batch(cfg, oracle_convmols(packed), y, w, np.arange(n), n, True)
-    if double:
-        state = {k: (v.double() if v.is_floating_point() else v) for k, v in state.items()}
-        inputs = [inputs[0].double()] + list(inputs[1:])
-        labels, weights = labels.double(), weights.double()
-    tr = O.OracleTrainer(cfg, state, grad_mode=grad_mode, faithful=False)
-    with (O.precision(torch.float64) if double else contextlib.nullcontext()):
-        ref, outs = tr.loss(inputs, labels, weights)
-        ref.backward()
-    return float(ref.detach()), [o.detach() for o in outs], tr.grads(), tr
+    return oracle_step(packed, y, w, cfg, state, grad_mode, n, double)
 
 
 def _check(native, oracle32, oracle64, tol=1e-4, slack=1.0):

@@ -166,8 +166,9 @@ def test_small_engine_prediction_matches_the_oracle(mode, T, B, n, bn):
 
 
 # (192, 256) / 64 and (256, 192) / 128 would reach the three- and four-tile forms of the product kernels and the 64-wide
-# readout, but the per-batch path this test compares against does not hold the bounds below at those widths (DESIGN
-# section 33 has the figures), so they are not cases here.
+# readout, but the per-batch path this test compares against does not hold the after-Adam bounds below at those widths
+# (DESIGN section 33 has the figures), so they are not cases here.  Those forms are held to the float64 oracle step by
+# step, gradient by gradient, in tests/test_gpu_small_grads.py (cases B and C).
 OTHER_WIDTHS = [((128, 128), 256)]
 
 
@@ -185,8 +186,10 @@ def test_small_engine_other_widths(widths, dense):
     batches = _device_batches(model, packed, y, w, cfg, 12)
     descs = [engine.describe(b, l, ww, 12) for b, l, ww, _, _ in batches]
     losses = engine.fit(descs, model._pytorch_optimizer, max(b.n_atoms for b, *_ in batches), 12).cpu().tolist()
-    # the oracle hard-codes 64-wide BatchNorm like the reference (graphconvmodel.py:151): compare with the
-    # per-batch native path of this repository instead, from the same state
+    # this test is about the two native paths agreeing: compare with the per-batch native path of this repository, from
+    # the same state.  (The oracle could run these widths too: O.init_state sizes BatchNorm and the dense layer from
+    # graph_conv_layers, and tests/test_gpu_scale.py and tests/test_gpu_small_grads.py run it at them; it is the
+    # reference's TORCH model that hard-codes 64, graphconvmodel.py:151.)
     import deepchem_amd as dc
     dc.set_gemm_mode("exact")
     try:
