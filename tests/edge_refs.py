@@ -971,3 +971,227 @@ def head_err_units(got, ref, S, unit=U24):
         return 0.0
     diff = np.abs(np.asarray(got[m], np.longdouble) - np.asarray(ref, np.longdouble)[m]).astype(np.float64)
     return float((diff / np.maximum(S[m], TINY32)).max() / unit)
+
+
+# ------------------------------------------------------------------------------------------------ direct gather kernels
+# csrc/gather.hip: the kernels behind gcmi_gather_sum_fwd, gcmi_scatter_add, gcmi_gather_max_fwd, gcmi_gather_max_bwd and
+# gcmi_build_rev_pos wherever no window pass runs.  neigh_sum, pool_max, pool_bwd and candidate_value above are their
+# restatements too (the direct kernels add in float32 in neighbour-table order); below: the two scatter forms, which need
+# no reverse table, the launch geometry, the vector-width rule, and the named batches of tests/test_gpu_direct_ops.py.
+# tests/test_direct_refs_host.py checks all of it without a device.
+DIRECT_SLOTS = 256 * 4  # kBlock * kUnroll lane slots per workgroup; one row takes lpr = n_feat / V of them
+
+
+def direct_tiles(deg_counts, lpr, skip_deg0):
+    """make_tiles: per degree (first workgroup, workgroups, slots in the last workgroup); a block without rows (or the
+    skipped degree-0 block of the accumulate and scatter forms) has no workgroup and shares its start with the next."""
+    out, first = [], 0
+    for d, c in enumerate(deg_counts):
+        slots = 0 if (skip_deg0 and d == 0) else int(c) * lpr
+        n = -(-slots // DIRECT_SLOTS)
+        out.append((first, n, slots - (n - 1) * DIRECT_SLOTS if n else 0))
+        first += n
+    return out
+
+
+def direct_vec(ptr, ld, n_feat):
+    """vec_width: four floats per lane only for a 16-byte aligned pointer, ld % 4 == 0 and n_feat % 4 == 0."""
+    return 4 if (ptr % 16 == 0 and ld % 4 == 0 and n_feat % 4 == 0) else 1
+
+
+class NeighbourTables:
+    """HostGraph without the reverse positions: only ``nb``, so a bond may be listed from one end.  neigh_sum, pool_max,
+    candidate_value, plant_winners, scatter_ref and pool_bwd_scatter take either."""
+
+    def __init__(self, deg_counts, col_idx):
+        self.deg_counts = [int(c) for c in deg_counts]
+        col_idx = np.asarray(col_idx, np.int64)
+        self.n_atoms = sum(self.deg_counts)
+        self.row0, self.nb = [], []
+        r = e = 0
+        for d, c in enumerate(self.deg_counts):
+            self.row0.append(r)
+            self.nb.append(col_idx[e:e + c * d].reshape(c, d))
+            r += c
+            e += c * d
+        assert e == col_idx.shape[0]
+        self.max_present = max([d for d, c in enumerate(self.deg_counts) if c] + [0])
+
+    def rows(self, d):
+        return np.arange(self.row0[d], self.row0[d] + self.deg_counts[d])
+
+    def degree_blocks(self):
+        return [(d, self.rows(d), self.nb[d], None) for d, c in enumerate(self.deg_counts) if c]
+
+
+def scatter_ref(hg, ds, dx0=None):
+    """dx[nb(i, j)] += ds[i] for every neighbour entry, onto dx0 (zeros), in the dtype of ds: the transpose of neigh_sum
+    whatever the adjacency.  (The order of the additions is numpy's; compare bit for bit only where any order is exact.)"""
+    dx = np.zeros_like(ds) if dx0 is None else np.array(dx0, ds.dtype)
+    for d, rows, nb, _ in hg.degree_blocks():
+        for j in range(d):
+            np.add.at(dx, nb[:, j], ds[rows])
+    assert dx.dtype == ds.dtype
+    return dx
+
+
+def pool_bwd_scatter(hg, g, arg):
+    """The GraphPool backward as a scatter: g[i, f] goes to row i where arg[i, f] == 0 and to neighbour arg[i, f] - 1 of
+    i otherwise, in the dtype of g.  No reverse table."""
+    dx = np.zeros_like(g)
+    cols = np.broadcast_to(np.arange(g.shape[1])[None, :], (1, g.shape[1]))
+    for d, rows, nb, _ in hg.degree_blocks():
+        a = arg[rows].astype(np.int64)
+        assert a.max(initial=0) <= d, "arg byte above the degree"
+        src = np.concatenate([rows[:, None], nb], 1)
+        target = np.take_along_axis(src, a, 1)
+        np.add.at(dx, (target, np.broadcast_to(cols, target.shape)), g[rows])
+    assert dx.dtype == g.dtype
+    return dx
+
+
+def collate_adjs(adjs, max_deg=10):
+    """Per-molecule adjacency lists (molecule-local ids) -> (deg_counts, col_idx, membership) in the collated layout:
+    rows sorted by degree, then by molecule, then by the atom's place in its molecule -- one stable sort by degree."""
+    sizes = np.array([len(a) for a in adjs], np.int64)
+    off = np.concatenate([[0], np.cumsum(sizes)])
+    lists = [[int(off[m]) + int(j) for j in nb] for m, a in enumerate(adjs) for nb in a]
+    deg = np.array([len(l) for l in lists], np.int64)
+    assert deg.max(initial=0) <= max_deg
+    order = np.argsort(deg, kind="stable")
+    new = np.empty(deg.shape[0], np.int64)
+    new[order] = np.arange(deg.shape[0])
+    col = np.array([new[j] for k in order for j in lists[k]], np.int32)
+    membership = np.repeat(np.arange(len(adjs)), sizes)[order].astype(np.int32)
+    return [int(c) for c in np.bincount(deg, minlength=max_deg + 1)], col, membership
+
+
+def packed_from_adjs(adjs, n_feat=4):
+    """The same molecules as a PackedMols (zero features), for the project's own host collations."""
+    from deepchem_amd.utils.synthetic import PackedMols
+    sizes = np.array([len(a) for a in adjs], np.int64)
+    atom_ptr = np.zeros(len(adjs) + 1, np.int64)
+    np.cumsum(sizes, out=atom_ptr[1:])
+    deg = np.array([len(nb) for a in adjs for nb in a], np.int64)
+    adj_ptr = np.zeros(deg.shape[0] + 1, np.int64)
+    np.cumsum(deg, out=adj_ptr[1:])
+    adj_idx = np.array([j for a in adjs for nb in a for j in nb], np.int32)
+    return PackedMols(np.zeros((int(atom_ptr[-1]), n_feat), np.float32), atom_ptr, adj_ptr, adj_idx)
+
+
+def adjs_of_packed(packed):
+    return [packed.molecule(m)[1] for m in range(packed.n_mols)]
+
+
+def chain_adj(n):
+    return [[j for j in (i - 1, i + 1) if 0 <= j < n] for i in range(n)]
+
+
+def star_adj(arms):
+    return [list(range(1, arms + 1))] + [[0] for _ in range(arms)]
+
+
+LONE_ADJ = [[]]
+DOUBLE_BOND_ADJ = [[1, 1, 2], [0, 0], [0]]  # a lists b twice and b lists a twice; c hangs on a
+
+
+def null_adj(max_deg=10):
+    """The reference's null molecule: one atom per degree, bonded to itself that many times."""
+    return [d * [d] for d in range(max_deg + 1)]
+
+
+TILE_ROWS = {"tile_exact": 64, "tile_plus": 65, "tile_minus": 63}  # rows in the degree-0, -1 and -2 blocks
+
+
+def _tile_adjs(k):
+    """Lone atoms, two-atom molecules, two chains and stars of three such that the blocks of degree 0, 1 and 2 hold
+    exactly k rows each: 2 stars for an even k and 1 for an odd one (3 degree-1 rows each), two chains (4), the rest of
+    the degree-1 rows in pairs; the chains carry the k degree-2 rows.  Shuffled by a fixed seed."""
+    stars = 2 - k % 2
+    pairs = (k - 4 - 3 * stars) // 2
+    mols = [LONE_ADJ] * k + [star_adj(3)] * stars + [chain_adj(2)] * pairs + [chain_adj(2 + k // 2), chain_adj(2 + k - k // 2)]
+    order = np.random.RandomState(k).permutation(len(mols))
+    return [mols[i] for i in order]
+
+
+def direct_batch_adjs(name):
+    """(adjacency lists, max_deg) of the named batches of tests/test_gpu_direct_ops.py."""
+    from deepchem_amd.utils.synthetic import concat_packed, single_atom_and_edge_cases, synthetic_molecules
+    if name == "mixed":
+        return adjs_of_packed(concat_packed([synthetic_molecules(40, seed=3, max_atoms=40),
+                                             single_atom_and_edge_cases(75, 1)])), 10
+    if name in TILE_ROWS:
+        return _tile_adjs(TILE_ROWS[name]), 10
+    if name == "gappy":
+        return ([LONE_ADJ] * 3 + [star_adj(4)] * 4) * 5, 10
+    if name == "high_only":
+        return [star_adj(10)] * 7, 10
+    if name == "lone":
+        return [LONE_ADJ] * 300, 10
+    if name == "shallow2":
+        return [chain_adj(n) for n in (2, 3, 5, 8, 13, 21, 2, 40, 7)], 2
+    if name == "shallow0":
+        return [LONE_ADJ] * 37, 0
+    ordinary = [chain_adj(5), star_adj(3), chain_adj(2), LONE_ADJ, star_adj(10), chain_adj(9)]
+    if name == "multi":
+        return ordinary[:3] + [null_adj(), DOUBLE_BOND_ADJ] + ordinary[3:] + [null_adj(), DOUBLE_BOND_ADJ, chain_adj(4)], 10
+    if name == "one_sided":
+        return ordinary + [[[1], []]] + adjs_of_packed(synthetic_molecules(12, seed=5, max_atoms=30)), 10
+    raise KeyError(name)
+
+
+DIRECT_BATCHES = ("mixed", "tile_exact", "tile_plus", "tile_minus", "gappy", "high_only", "lone", "shallow2", "shallow0",
+                  "multi", "one_sided")
+DIRECT_LPR = (1, 16, 17, 19, 64, 2, 7, 75)  # the widths 4, 64, 68, 76, 256 in fours and 1, 2, 7, 75 (and 64) singly
+
+
+def direct_batch_check(name, deg_counts, col_idx):
+    """What the named batch is there for, asserted from its degree counts, direct_tiles and the neighbour tables."""
+    counts = [int(c) for c in deg_counts]
+    present = [d for d, c in enumerate(counts) if c]
+    n_edges = sum(d * c for d, c in enumerate(counts))
+    assert n_edges == len(col_idx)
+    t16, t16s = direct_tiles(counts, 16, False), direct_tiles(counts, 16, True)
+    if name == "mixed":
+        assert present == [0, 1, 2, 3, 4, 6, 10]
+        assert direct_tiles(counts, 64, False)[2][1] > 1  # a degree block of several workgroups at 256 columns
+    elif name in TILE_ROWS:
+        k = TILE_ROWS[name]
+        assert counts[:3] == [k, k, k]
+        # lpr 16: 64 rows are 1024 slots -- one full workgroup; one slot-row more or fewer
+        last = {64: (1, DIRECT_SLOTS), 65: (2, 16), 63: (1, DIRECT_SLOTS - 16)}[k]
+        assert [t[1:] for t in t16[:3]] == [last] * 3
+        assert t16[1][0] == last[0] and t16s[1][0] == 0 and t16s[0][1:] == (0, 0)
+        for lpr in (17, 19, 75):  # a row straddles two unroll steps (256 slots) and, at these counts, two workgroups
+            assert 256 % lpr and DIRECT_SLOTS % lpr and k * lpr > DIRECT_SLOTS
+            assert direct_tiles(counts, lpr, False)[1][1] == -(-k * lpr // DIRECT_SLOTS) >= 2
+        assert direct_tiles(counts, 1, False)[1][1:] == (1, k)
+    elif name == "gappy":
+        assert present == [0, 1, 4]
+    elif name == "high_only":
+        assert present == [1, 10] and counts[0] == 0
+        assert t16s[0][1] == 0 and t16[0][1] == 0  # an empty degree-0 block, skipped or not
+        assert all(t16[d][1] == 0 and t16[d][0] == t16[10][0] for d in range(2, 10))  # block_degree jumps 2..9
+    elif name == "lone":
+        assert present == [0] and len(counts) == 11 and n_edges == 0
+        assert sum(t[1] for t in t16s) == 0 and t16[0][1] > 1  # the accumulate form launches nothing
+    elif name == "shallow2":
+        assert len(counts) == 3 and present == [1, 2]
+    elif name == "shallow0":
+        assert len(counts) == 1 and present == [0] and n_edges == 0
+    elif name == "multi":
+        nt = NeighbourTables(counts, col_idx)
+        assert present == list(range(11))
+        loops = [int((nt.nb[d] == nt.rows(d)[:, None]).all(1).sum()) for d in range(11)]
+        assert loops[1:] == [2] * 10  # two null molecules: per degree d two atoms listing themselves d times
+        twice = sum(int(((nb[:, :, None] == nb[:, None, :]).sum((1, 2)) > nb.shape[1]).sum()) for nb in nt.nb[2:])
+        assert twice >= 2 * 2 + 2 * 9  # rows with a repeated neighbour: both ends of both double bonds, and the loops
+    elif name == "one_sided":
+        nt = NeighbourTables(counts, col_idx)
+        src = np.concatenate([np.repeat(nt.rows(d), d) for d in range(len(counts))])
+        dst = np.concatenate([nb.reshape(-1) for nb in nt.nb])
+        fwd, bwd = np.sort(src * nt.n_atoms + dst), np.sort(dst * nt.n_atoms + src)
+        assert len(np.setdiff1d(fwd, bwd)) == 1 and counts[0] > 0 and counts[10] > 0  # exactly one bond without its mate
+    else:
+        raise KeyError(name)
+    return True
