@@ -214,9 +214,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
   constexpr int NACC = (DGRAD && TPW > KT) ? TPW : KT;
   f32x16 accs[NACC];
 #pragma unroll
-  for (int t = 0; t < NACC; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) accs[t][i] = 0.f;
+  for (int t = 0; t < NACC; ++t) accs[t] = zero_acc();
   float bsum = 0.f;
   auto flush_w = [&](int seg) {
     const int64_t woff = tl.w[NOPS == 2 ? wo : 0][seg];
@@ -231,7 +229,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
       for (int t = 0; t < KT; ++t) {
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
-          const int r8 = (reg & 3) + 8 * (reg >> 2);  // + 4 * half: row of the accumulator tile
+          const int r8 = acc_row(reg, 0);  // (the half: in woff_lane)
           if constexpr (TRANS) {  // dW stored NG x k_in: the accumulator holds (column of G) x (column of In)
             if (t * 32 + l31 < a.k_in) atomicAdd(wp + (int64_t)r8 * a.k_in + t * 32, accs[t][reg]);
           } else {                // dW stored k_in x NG
@@ -241,9 +239,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
       }
     }
 #pragma unroll
-    for (int t = 0; t < KT; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) accs[t][i] = 0.f;
+    for (int t = 0; t < KT; ++t) accs[t] = zero_acc();
     if (wo == 0) {
       const int64_t boff = tl.b[seg];
       const float s = bsum + __shfl_xor(bsum, 32);
@@ -423,9 +419,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
       if constexpr (DGRAD) {
         // input gradients of this tile: `accs` starts from zero (the weight-gradient waves keep theirs across tiles)
 #pragma unroll
-        for (int t = 0; t < TPW; ++t)
-#pragma unroll
-          for (int k = 0; k < 16; ++k) accs[t][k] = 0.f;
+        for (int t = 0; t < TPW; ++t) accs[t] = zero_acc();
         bool on[TPW];
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
@@ -436,7 +430,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
         // with two waves per SIMD nobody else hides a read's latency
         constexpr int NKS = NG / 16, NU = NKS * TPW;
         float4 glo, ghi;
-        u32x4 wv[2][3];
+        Frag3 wv[2];
         auto read_g = [&](int ks) {
           const float* grow = Gs + (rb * 32 + l31) * GP + ks * 16 + 8 * half;
           glo = *reinterpret_cast<const float4*>(grow);
@@ -447,9 +441,9 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
           const int ot = cg * TPW + t;
           const int o = ot / KT, kt = ot - o * KT;
           const unsigned short* wrow = Wimg + ((size_t)(o * 3) * KP + kt * 32 + l31) * WP + ks * 16 + 8 * half;
-          wv[u & 1][0] = *reinterpret_cast<const u32x4*>(wrow);
-          wv[u & 1][1] = *reinterpret_cast<const u32x4*>(wrow + (size_t)KP * WP);
-          if constexpr (!HB) wv[u & 1][2] = *reinterpret_cast<const u32x4*>(wrow + (size_t)2 * KP * WP);
+          wv[u & 1].p[0] = *reinterpret_cast<const u32x4*>(wrow);
+          wv[u & 1].p[1] = *reinterpret_cast<const u32x4*>(wrow + (size_t)KP * WP);
+          if constexpr (!HB) wv[u & 1].p[2] = *reinterpret_cast<const u32x4*>(wrow + (size_t)2 * KP * WP);
         };
         read_g(0);
         read_w(0);
@@ -457,26 +451,15 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
           const int ks = u / TPW, t = u - ks * TPW;
-          if (t == 0) {  // this k-step's rows of G: split, then its registers take the next k-step's
-            const float v[8] = {glo.x, glo.y, glo.z, glo.w, ghi.x, ghi.y, ghi.z, ghi.w};
-            fg = split_frag(v);
-          }
+          if (t == 0) fg = split_frag(glo, ghi);  // this k-step's rows of G; its registers then take the next k-step's
           if (u + 1 < NU) {
             read_w(u + 1);
             if (t == TPW - 1) read_g(ks + 1);
           }
           if (on[t]) {  // uniform
-            const u32x4 w1 = wv[u & 1][0], w2 = wv[u & 1][1];
-            // rows of G x input columns: lane = input column, registers = rows; small terms first
-            if constexpr (!HB) {
-              const u32x4 w3 = wv[u & 1][2];
-              accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fg.p[2]), as_bf16x8(w1), accs[t], 0, 0, 0);
-              accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fg.p[0]), as_bf16x8(w3), accs[t], 0, 0, 0);
-              accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fg.p[1]), as_bf16x8(w2), accs[t], 0, 0, 0);
-            }
-            accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fg.p[1]), as_bf16x8(w1), accs[t], 0, 0, 0);
-            accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fg.p[0]), as_bf16x8(w2), accs[t], 0, 0, 0);
-            accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fg.p[0]), as_bf16x8(w1), accs[t], 0, 0, 0);
+            // rows of G x input columns: lane = input column, registers = rows; HB: without the 2^-16 terms
+            if constexpr (!HB) mfma_split3_small(accs[t], fg, wv[u & 1]);
+            mfma_split3_large(accs[t], fg, wv[u & 1]);
           }
           __builtin_amdgcn_sched_barrier(0);  // units stay in order: one set of fragments live besides the one in flight
         }
@@ -485,7 +468,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
         for (int t = 0; t < TPW; ++t) {
           float* orow = Outs + (rb * 32 + 4 * half) * OP + (cg * TPW + t) * 32 + l31;
 #pragma unroll
-          for (int reg = 0; reg < 16; ++reg) orow[((reg & 3) + 8 * (reg >> 2)) * OP] = accs[t][reg];
+          for (int reg = 0; reg < 16; ++reg) orow[acc_row(reg, 0) * OP] = accs[t][reg];  // (orow holds the half)
         }
       }
     } else {
@@ -566,8 +549,8 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
           const int t = w_ - 1;
           const Frag3& L = TRANS ? fg : cur;
           const Frag3& R = TRANS ? cur : fg;
-          // MFMA, a quarter of the next fragment's split, MFMA, ...: the order is pinned (the scheduler would put the
-          // six dependent MFMAs back to back)
+          // mfma_split6(accs[t], L, R) unrolled by hand, and it must keep that order: MFMA, a quarter of the next
+          // fragment's split, MFMA, ... (pinned: the scheduler would put the six dependent MFMAs back to back)
           accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[2]), as_bf16x8(R.p[0]), accs[t], 0, 0, 0);
           __builtin_amdgcn_sched_barrier(0);
           pair_split(0);
@@ -640,12 +623,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
           const Frag3 fa = split_frag(raw[f & 1]);
           const Frag3& L = TRANS ? fg : fa;
           const Frag3& R = TRANS ? fa : fg;
-          accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[2]), as_bf16x8(R.p[0]), accs[t], 0, 0, 0);
-          accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[2]), accs[t], 0, 0, 0);
-          accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[1]), as_bf16x8(R.p[1]), accs[t], 0, 0, 0);
-          accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[1]), as_bf16x8(R.p[0]), accs[t], 0, 0, 0);
-          accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[1]), accs[t], 0, 0, 0);
-          accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[0]), accs[t], 0, 0, 0);
+          mfma_split6(accs[t], L, R);
         }
         __builtin_amdgcn_sched_barrier(0);
       }

@@ -128,7 +128,6 @@ __global__ __launch_bounds__(kDmpnnThreads) void dmpnn_message_kernel(const Dmpn
 // ---------------------------------------------------------------------------------------------------- fused update
 constexpr int kUpdThreads = 128;
 constexpr int kUpdWaves = kUpdThreads / 64;
-constexpr int kUpdPitch = 68;   // floats per staged row (17 16-byte pieces: the fragment reads are conflict-free)
 constexpr int kUpdStage = 96;   // staged rows per wave: 32 + 2 * 31 at the degree cap, rounded up
 constexpr int kUpdMaxD = 320;
 
@@ -143,18 +142,6 @@ struct UpdArgs {
   const int32_t *out_ptr, *rev, *src;
   int32_t n_atoms, n_bonds, d, n_tiles, act;
 };
-
-__device__ __forceinline__ int upd_reg_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-// acc += A . B with both operands split three ways (small terms first)
-__device__ __forceinline__ void upd_mfma6(f32x16& acc, const Frag3& a, const Frag3& b) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a.p[2]), as_bf16x8(b.p[0]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a.p[0]), as_bf16x8(b.p[2]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a.p[1]), as_bf16x8(b.p[1]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a.p[1]), as_bf16x8(b.p[0]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a.p[0]), as_bf16x8(b.p[1]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a.p[0]), as_bf16x8(b.p[0]), acc, 0, 0, 0);
-}
 
 // W (d x d, nn.Linear layout, out x in) -> B fragments of h = q . W^T: entry ((ks * NB + nb) * 3 + piece) * 64 + lane holds
 // W[32 nb + (lane & 31)][16 ks + 8 (lane >> 5) + 0..7], zero past either edge
@@ -176,7 +163,7 @@ __global__ __launch_bounds__(256) void dmpnn_wprep_kernel(const float* __restric
 
 template <int NB>
 __global__ __launch_bounds__(kUpdThreads) void dmpnn_update_kernel(const UpdArgs a) {
-  __shared__ __attribute__((aligned(16))) float upd_smem[kUpdWaves][kUpdStage * kUpdPitch];
+  __shared__ __attribute__((aligned(16))) float upd_smem[kUpdWaves][kUpdStage * kTilePitch];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
   float* X = upd_smem[wave];
   const int n_chunks = (a.d + 63) / 64, n_ks = (a.d + 15) / 16, n_nb = (a.d + 31) / 32;
@@ -217,10 +204,10 @@ __global__ __launch_bounds__(kUpdThreads) void dmpnn_update_kernel(const UpdArgs
           for (int j = i; j < e; ++j) {
             const int r = a.rev[s0 + j];
             const float v = (in && (unsigned)r < (unsigned)a.n_bonds) ? a.x[(int64_t)r * a.ldx + c] : 0.f;
-            X[j * kUpdPitch + lane] = v;
+            X[j * kTilePitch + lane] = v;
             sum += v;
           }
-          for (int j = i; j < e; ++j) X[j * kUpdPitch + lane] = sum - X[j * kUpdPitch + lane];
+          for (int j = i; j < e; ++j) X[j * kTilePitch + lane] = sum - X[j * kTilePitch + lane];
           i = e;
         }
       }
@@ -236,7 +223,7 @@ __global__ __launch_bounds__(kUpdThreads) void dmpnn_update_kernel(const UpdArgs
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = 0.f;
             if (have) {
-              const float4* src = reinterpret_cast<const float4*>(X + row * kUpdPitch + kk * 16 + 8 * half);
+              const float4* src = reinterpret_cast<const float4*>(X + row * kTilePitch + kk * 16 + 8 * half);
               const float4 u0 = src[0], u1 = src[1];
               v[0] = u0.x; v[1] = u0.y; v[2] = u0.z; v[3] = u0.w;
               v[4] = u1.x; v[5] = u1.y; v[6] = u1.z; v[7] = u1.w;
@@ -245,12 +232,7 @@ __global__ __launch_bounds__(kUpdThreads) void dmpnn_update_kernel(const UpdArgs
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
               if (nb < n_nb) {
-                const u32x4* w = a.img + ((int64_t)(ks * n_nb + nb) * 3) * 64 + lane;
-                Frag3 fb;
-                fb.p[0] = w[0];
-                fb.p[1] = w[64];
-                fb.p[2] = w[128];
-                upd_mfma6(acc[nb], fa, fb);
+                mfma_split6(acc[nb], fa, load_frag3(a.img + ((int64_t)(ks * n_nb + nb) * 3) * 64 + lane));
               }
             }
           }
@@ -265,7 +247,7 @@ __global__ __launch_bounds__(kUpdThreads) void dmpnn_update_kernel(const UpdArgs
         if (n < a.d) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int m = upd_reg_row(r, half);
+            const int m = acc_row(r, half);
             if (m < valid) {
               float v = a.inp[(int64_t)(r0 + m) * a.ldi + n] + acc[nb][r];
               if (a.act) v = v > 0.f ? v : 0.f;
@@ -284,8 +266,6 @@ void launch_update(const UpdArgs& a, int grid, hipStream_t st) {
 }
 
 inline int64_t update_scratch_floats(int d) { return (int64_t)((d + 15) / 16) * ((d + 31) / 32) * 3 * 64 * 4; }
-
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 
 }  // namespace
 }  // namespace gcmi

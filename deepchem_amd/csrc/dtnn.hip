@@ -33,8 +33,7 @@ namespace {
 constexpr int kDtnnThreads = 256;
 constexpr int kDtnnWaves = kDtnnThreads / 64;
 constexpr int kDtnnKS = 8;       // k-steps of 16 Gaussians: n_distance <= 128
-constexpr int kDtnnPitch = 68;   // floats per row of the transposition tile (17 16-byte pieces: conflict-free)
-constexpr int kDtnnTileFloats = 32 * kDtnnPitch + 64;  // + 32 doubles: the pairs' scaled distances
+constexpr int kDtnnTileFloats = 32 * kTilePitch + 64;  // + 32 doubles: the pairs' scaled distances
 constexpr float kHalfLog2e = 0.72134752044448170368f;
 
 struct DtnnArgs {
@@ -58,29 +57,12 @@ struct DtnnArgs {
 
 __device__ __forceinline__ bool dev_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-__device__ __forceinline__ f32x16 zero16() {
-  f32x16 z;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) z[i] = 0.f;
-  return z;
-}
-
-// acc += A . B with both operands split three ways (small terms first)
-__device__ __forceinline__ void mfma6(f32x16& acc, const u32x4 a1, const u32x4 a2, const u32x4 a3, const Frag3& b) {
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a3), as_bf16x8(b.p[0]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a1), as_bf16x8(b.p[2]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a2), as_bf16x8(b.p[1]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a2), as_bf16x8(b.p[0]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a1), as_bf16x8(b.p[1]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(a1), as_bf16x8(b.p[0]), acc, 0, 0, 0);
-}
-
 // the feature a lane's accumulator register r holds inside a 32-column block (its other index is on the lane)
-__device__ __forceinline__ int reg_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 // k slot (half, j) of k-step s of a product that takes accumulator registers as its operand -> the feature index
 __device__ __forceinline__ int slot_feat(int s, int half, int j) { return 16 * s + 8 * (j >> 2) + 4 * half + (j & 3); }
 
-// Fragment images of the weights, built once per workgroup:
+// Fragment images of the weights, built once per workgroup, piece-major (s = the piece: a whole image apart, indexed
+// by hand where they are written and read):
 //   WDF[s][nt][ks][lane]: A[row h = 32 nt + (lane & 31)][k = 16 ks + 8 half + j] = W_df[k][h]
 //   FC1[s][et][ks][lane]: row / column e = 32 et + (lane & 31), slots h = slot_feat(ks, half, j): W_fc[h][e]
 //   FC2[s][ht][ks][lane]: row h = 32 ht + (lane & 31), slots e = slot_feat(ks, half, j): W_fc[h][e]
@@ -181,25 +163,23 @@ __device__ __forceinline__ void tile_hidden(const DtnnArgs& a, const u32x4* WDF,
   const int KS = (a.K + 15) >> 4;
   const bool gvec = !FROM_D && (a.ldg % 4 == 0) && dev_aligned16(a.src);
 #pragma unroll
-  for (int nt = 0; nt < NTH; ++nt) dh[nt] = zero16();
+  for (int nt = 0; nt < NTH; ++nt) dh[nt] = zero_acc();
   for (int ks = 0; ks < KS; ++ks) {
-    float v[8];
+    Frag3 fb;
     const int k0 = 16 * ks + 8 * half;
     if constexpr (FROM_D) {
+      float v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = gaussian_of(q.u0, k0 + j);
+      fb = split_frag(v);
     } else {
-      const float4 lo = load4(q.grow, k0, a.K, gvec), hi = load4(q.grow, k0 + 4, a.K, gvec);
-      v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w;
-      v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+      fb = split_frag(load4(q.grow, k0, a.K, gvec), load4(q.grow, k0 + 4, a.K, gvec));
     }
-    const Frag3 fb = split_frag(v);
 #pragma unroll
     for (int nt = 0; nt < NTH; ++nt) {
-      const u32x4 w1 = WDF[((0 * NTH + nt) * kDtnnKS + ks) * 64 + lane];
-      const u32x4 w2 = WDF[((1 * NTH + nt) * kDtnnKS + ks) * 64 + lane];
-      const u32x4 w3 = WDF[((2 * NTH + nt) * kDtnnKS + ks) * 64 + lane];
-      mfma6(dh[nt], w1, w2, w3, fb);
+      const Frag3 w = {{WDF[((0 * NTH + nt) * kDtnnKS + ks) * 64 + lane], WDF[((1 * NTH + nt) * kDtnnKS + ks) * 64 + lane],
+                        WDF[((2 * NTH + nt) * kDtnnKS + ks) * 64 + lane]}};
+      mfma_split6(dh[nt], w, fb);
     }
   }
   const bool avec = (a.ldah % 4 == 0) && dev_aligned16(a.ah);
@@ -246,7 +226,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_fwd_kernel(const DtnnArgs a
     // z (rows = pairs in the registers, lane = output column): A = m taken from the accumulators, B = FC1
     f32x16 z[NTE];
 #pragma unroll
-    for (int et = 0; et < NTE; ++et) z[et] = zero16();
+    for (int et = 0; et < NTE; ++et) z[et] = zero_acc();
 #pragma unroll
     for (int s = 0; s < 2 * NTH; ++s) {
       const Frag3 fa = acc_frag<NTH>(dh, s);
@@ -255,7 +235,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_fwd_kernel(const DtnnArgs a
         Frag3 w;
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) w.p[pc] = FC1[((pc * NTE + et) * 2 * NTH + s) * 64 + lane];
-        mfma6(z[et], fa.p[0], fa.p[1], fa.p[2], w);
+        mfma_split6(z[et], fa, w);
       }
     }
 #pragma unroll
@@ -274,7 +254,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_fwd_kernel(const DtnnArgs a
         float s = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int rr = reg_row(r, half);
+          const int rr = acc_row(r, half);
           s += (rr >= row && rr < end) ? z[et][r] : 0.f;
         }
         s += __shfl_xor(s, 32);
@@ -295,14 +275,14 @@ __device__ __forceinline__ void tile_store(float* T, const f32x16 (&x)[NT], int 
   for (int t = 0; t < NT; ++t)
 #pragma unroll
     for (int g = 0; g < 4; ++g)
-      *reinterpret_cast<float4*>(T + l31 * kDtnnPitch + 32 * t + 8 * g + 4 * half) =
+      *reinterpret_cast<float4*>(T + l31 * kTilePitch + 32 * t + 8 * g + 4 * half) =
           make_float4(x[t][4 * g], x[t][4 * g + 1], x[t][4 * g + 2], x[t][4 * g + 3]);
 }
 // the fragment with this lane's column c and the 8 pairs 16 ks + 8 half + j as its k slots
 __device__ __forceinline__ Frag3 tile_frag(const float* T, int ks, int c, int half) {
   float v[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) v[j] = T[(16 * ks + 8 * half + j) * kDtnnPitch + c];
+  for (int j = 0; j < 8; ++j) v[j] = T[(16 * ks + 8 * half + j) * kTilePitch + c];
   return split_frag(v);
 }
 
@@ -314,7 +294,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
   u32x4* FC2 = FC1 + 3 * NTE * 2 * NTH * 64;
   const int wave = threadIdx.x >> 6;
   float* T = reinterpret_cast<float*>(FC2 + 3 * NTH * 2 * NTE * 64) + wave * kDtnnTileFloats;
-  double* U0 = reinterpret_cast<double*>(T + 32 * kDtnnPitch);
+  double* U0 = reinterpret_cast<double*>(T + 32 * kTilePitch);
   build_images<NTH, NTE, true>(a, WDF, FC1, FC2);
   __syncthreads();
   const int lane = threadIdx.x & 63, half = lane >> 5, l31 = lane & 31;
@@ -324,11 +304,11 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
   f32x16 accdf[4][NTH], accfc[NTH][NTE], accb[NTH];
 #pragma unroll
   for (int nt = 0; nt < NTH; ++nt) {
-    accb[nt] = zero16();
+    accb[nt] = zero_acc();
 #pragma unroll
-    for (int kt = 0; kt < 4; ++kt) accdf[kt][nt] = zero16();
+    for (int kt = 0; kt < 4; ++kt) accdf[kt][nt] = zero_acc();
 #pragma unroll
-    for (int et = 0; et < NTE; ++et) accfc[nt][et] = zero16();
+    for (int et = 0; et < NTE; ++et) accfc[nt][et] = zero_acc();
   }
   const int rounds = (a.n_tiles + nw - 1) / nw;  // the same for every wave of the workgroup: barriers inside
   for (int it = 0; it < rounds; ++it) {
@@ -344,14 +324,16 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
       for (int nt = 0; nt < NTH; ++nt) m[nt] = dh[nt] * ahv[nt];
       // z^T (lane = pair, registers = output columns): A = FC1, B = m from the accumulators
 #pragma unroll
-      for (int et = 0; et < NTE; ++et) dz[et] = zero16();
+      for (int et = 0; et < NTE; ++et) dz[et] = zero_acc();
 #pragma unroll
       for (int s = 0; s < 2 * NTH; ++s) {
         const Frag3 fb = acc_frag<NTH>(m, s);
 #pragma unroll
-        for (int et = 0; et < NTE; ++et)
-          mfma6(dz[et], FC1[((0 * NTE + et) * 2 * NTH + s) * 64 + lane], FC1[((1 * NTE + et) * 2 * NTH + s) * 64 + lane],
-                FC1[((2 * NTE + et) * 2 * NTH + s) * 64 + lane], fb);
+        for (int et = 0; et < NTE; ++et) {
+          const Frag3 w = {{FC1[((0 * NTE + et) * 2 * NTH + s) * 64 + lane], FC1[((1 * NTE + et) * 2 * NTH + s) * 64 + lane],
+                            FC1[((2 * NTE + et) * 2 * NTH + s) * 64 + lane]}};
+          mfma_split6(dz[et], w, fb);
+        }
       }
       // dz = dY[i] (.) (1 - tanh^2); zero where there is no pair or no column
       const float* dyrow = q.i >= 0 ? a.dy + (int64_t)q.i * a.lddy : nullptr;
@@ -370,14 +352,16 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
       // dm^T (lane = pair, registers = hidden columns): A = FC2, B = dz from the accumulators
       f32x16 dm[NTH];
 #pragma unroll
-      for (int nt = 0; nt < NTH; ++nt) dm[nt] = zero16();
+      for (int nt = 0; nt < NTH; ++nt) dm[nt] = zero_acc();
 #pragma unroll
       for (int s = 0; s < 2 * NTE; ++s) {
         const Frag3 fb = acc_frag<NTE>(dz, s);
 #pragma unroll
-        for (int nt = 0; nt < NTH; ++nt)
-          mfma6(dm[nt], FC2[((0 * NTH + nt) * 2 * NTE + s) * 64 + lane], FC2[((1 * NTH + nt) * 2 * NTE + s) * 64 + lane],
-                FC2[((2 * NTH + nt) * 2 * NTE + s) * 64 + lane], fb);
+        for (int nt = 0; nt < NTH; ++nt) {
+          const Frag3 w = {{FC2[((0 * NTH + nt) * 2 * NTE + s) * 64 + lane], FC2[((1 * NTH + nt) * 2 * NTE + s) * 64 + lane],
+                            FC2[((2 * NTH + nt) * 2 * NTE + s) * 64 + lane]}};
+          mfma_split6(dm[nt], w, fb);
+        }
       }
       // d_ah[j] += dm (.) dh; ddh = dm (.) ah[j]; db_df += ddh
       float* drow = a.dah + (int64_t)q.j * a.lddah;
@@ -385,7 +369,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
       for (int nt = 0; nt < NTH; ++nt) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int h = 32 * nt + reg_row(r, half);
+          const int h = 32 * nt + acc_row(r, half);
           if (q.i >= 0 && h < a.H) unsafeAtomicAdd(drow + h, dm[nt][r] * dh[nt][r]);
         }
         ddh[nt] = dm[nt] * ahv[nt];
@@ -412,7 +396,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
         for (int et = 0; et < NTE; ++et) {
           const Frag3 fz = tile_frag(T, ks, 32 * et + l31, half);
 #pragma unroll
-          for (int nt = 0; nt < NTH; ++nt) mfma6(accfc[nt][et], fm[ks][nt].p[0], fm[ks][nt].p[1], fm[ks][nt].p[2], fz);
+          for (int nt = 0; nt < NTH; ++nt) mfma_split6(accfc[nt][et], fm[ks][nt], fz);
         }
     }
     __syncthreads();
@@ -447,7 +431,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
             }
             const Frag3 fg = split_frag(v);
 #pragma unroll
-            for (int nt = 0; nt < NTH; ++nt) mfma6(accdf[kt][nt], fg.p[0], fg.p[1], fg.p[2], fd[nt]);
+            for (int nt = 0; nt < NTH; ++nt) mfma_split6(accdf[kt][nt], fg, fd[nt]);
           }
         }
       }
@@ -462,14 +446,14 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
     for (int kt = 0; kt < 4; ++kt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int k = 32 * kt + reg_row(r, half);
+        const int k = 32 * kt + acc_row(r, half);
         if (kt < KT && k < a.K && c < a.H) unsafeAtomicAdd(a.dw_df + (int64_t)k * a.H + c, accdf[kt][nt][r]);
       }
 #pragma unroll
     for (int et = 0; et < NTE; ++et)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int h = 32 * nt + reg_row(r, half), e = 32 * et + l31;
+        const int h = 32 * nt + acc_row(r, half), e = 32 * et + l31;
         if (h < a.H && e < a.E) unsafeAtomicAdd(a.dw_fc + (int64_t)h * a.E + e, accfc[nt][et][r]);
       }
     // db_df: the registers hold hidden columns, the lanes of a half the pairs
@@ -478,7 +462,7 @@ __global__ __launch_bounds__(kDtnnThreads) void dtnn_bwd_kernel(const DtnnArgs a
       float s = accb[nt][r];
 #pragma unroll
       for (int o = 1; o < 32; o <<= 1) s += __shfl_xor(s, o);
-      const int h = 32 * nt + reg_row(r, half);
+      const int h = 32 * nt + acc_row(r, half);
       if (l31 == 0 && h < a.H) unsafeAtomicAdd(a.db_df + h, s);
     }
   }
@@ -535,6 +519,20 @@ int check_dtnn(const char* what, const float* d_src, int64_t ld_src, int32_t fro
   GCMI_CHECK_ARG(d_w_df && d_b_df && d_w_fc, "%s: NULL weights", what);
   GCMI_CHECK_ARG(n_pairs == 0 || (d_src && d_mem_i && d_mem_j && d_ah), "%s: NULL buffer", what);
   return GCMI_OK;
+}
+
+// the fields both directions fill alike: the pair list, the atom rows, the weights (arguments as check_dtnn's)
+DtnnArgs dtnn_inputs(const float* d_src, int64_t ld_src, int32_t from_distance, const int32_t* d_mem_i,
+                     const int32_t* d_mem_j, int64_t n_pairs, int32_t n_atoms, const float* d_ah, int64_t ldah,
+                     int32_t n_hidden, const float* d_w_df, const float* d_b_df, int32_t n_distance, const float* d_w_fc,
+                     int32_t n_embedding, double distance_min, double step) {
+  DtnnArgs a = {};
+  a.src = d_src; a.ldg = ld_src; a.mem_i = d_mem_i; a.mem_j = d_mem_j;
+  a.P = (int32_t)n_pairs; a.N = n_atoms; a.K = n_distance; a.H = n_hidden; a.E = n_embedding;
+  a.n_tiles = (int32_t)((n_pairs + 31) / 32);
+  a.ah = d_ah; a.ldah = ldah; a.w_df = d_w_df; a.b_df = d_b_df; a.w_fc = d_w_fc;
+  a.dmin = distance_min; a.inv_step = from_distance ? 1.0 / step : 0.0;
+  return a;
 }
 
 // ---------------------------------------------------------------------------------------------------- collation
@@ -631,12 +629,8 @@ int gcmi_dtnn_pair_fwd(const float* d_src, int64_t ld_src, int32_t from_distance
     return GCMI_ERR_LAUNCH;
   }
   if (n_pairs == 0) return GCMI_OK;
-  DtnnArgs a = {};
-  a.src = d_src; a.ldg = ld_src; a.mem_i = d_mem_i; a.mem_j = d_mem_j;
-  a.P = (int32_t)n_pairs; a.N = n_atoms; a.K = n_distance; a.H = n_hidden; a.E = n_embedding;
-  a.n_tiles = (int32_t)((n_pairs + 31) / 32);
-  a.ah = d_ah; a.ldah = ldah; a.w_df = d_w_df; a.b_df = d_b_df; a.w_fc = d_w_fc;
-  a.dmin = distance_min; a.inv_step = from_distance ? 1.0 / step : 0.0;
+  DtnnArgs a = dtnn_inputs(d_src, ld_src, from_distance, d_mem_i, d_mem_j, n_pairs, n_atoms, d_ah, ldah, n_hidden, d_w_df,
+                           d_b_df, n_distance, d_w_fc, n_embedding, distance_min, step);
   a.y = d_y; a.ldy = ldy;
   return dispatch_dtnn<false>(a, from_distance != 0, st);
 }
@@ -660,12 +654,8 @@ int gcmi_dtnn_pair_bwd(const float* d_src, int64_t ld_src, int32_t from_distance
     return GCMI_ERR_LAUNCH;
   }
   if (n_pairs == 0) return GCMI_OK;
-  DtnnArgs a = {};
-  a.src = d_src; a.ldg = ld_src; a.mem_i = d_mem_i; a.mem_j = d_mem_j;
-  a.P = (int32_t)n_pairs; a.N = n_atoms; a.K = n_distance; a.H = n_hidden; a.E = n_embedding;
-  a.n_tiles = (int32_t)((n_pairs + 31) / 32);
-  a.ah = d_ah; a.ldah = ldah; a.w_df = d_w_df; a.b_df = d_b_df; a.w_fc = d_w_fc;
-  a.dmin = distance_min; a.inv_step = from_distance ? 1.0 / step : 0.0;
+  DtnnArgs a = dtnn_inputs(d_src, ld_src, from_distance, d_mem_i, d_mem_j, n_pairs, n_atoms, d_ah, ldah, n_hidden, d_w_df,
+                           d_b_df, n_distance, d_w_fc, n_embedding, distance_min, step);
   a.dy = d_dy; a.lddy = lddy; a.dah = d_dah; a.lddah = lddah;
   a.dw_df = d_dw_df; a.db_df = d_db_df; a.dw_fc = d_dw_fc;
   return dispatch_dtnn<true>(a, from_distance != 0, st);

@@ -74,9 +74,7 @@ wprep_kernel(SegTable st, const float* __restrict__ w0, const float* __restrict_
     }
     const Frag3 f = split_frag(v);
     u32x4* dst = wimg + (size_t)((seg * TW + tw) * NKS + ks) * 3 * 64 + lane;
-    dst[0] = f.p[0];
-    dst[64] = f.p[1];
-    dst[128] = f.p[2];
+    store_frag3(dst, f);
   }
 }
 
@@ -247,9 +245,7 @@ fwd_hd_kernel(SegTable st, int n_tiles, FwdHArgs a, int rev) {
   auto products = [&](int it) {
     f32x16 acc[TPW];
 #pragma unroll
-    for (int j = 0; j < TPW; ++j)
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc[j][k] = 0.f;
+    for (int j = 0; j < TPW; ++j) acc[j] = zero_acc();
     const unsigned char* arow = As + (size_t)(it % NBUF) * TILE_BYTES + (size_t)my_row * RQ * 16;
     auto frag = [&](int ks) { return *reinterpret_cast<const u32x4*>(arow + (((2 * ks + half) ^ my_swz) * 16)); };
     u32x4 xa = frag(0);

@@ -189,11 +189,9 @@ fwd_fused_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
     if (i + 2 < my_tiles) tile_info(tiles.at(i + 2), n2seg, n2row0, n2valid);
     load_src(nrow0, nvalid);
     {
-      f32x16 acc;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc[k] = 0.f;
+      f32x16 acc = zero_acc();
       float4 glo, ghi;
-      u32x4 wv[2][3];
+      Frag3 wv[2];
       auto read_a = [&](int ks) {
         const float* arow = As + (rb * 32 + l31) * AP + ks * 16 + 8 * half;
         glo = *reinterpret_cast<const float4*>(arow);
@@ -201,28 +199,20 @@ fwd_fused_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
       };
       auto read_w = [&](int ks) {
         const unsigned short* wrow = Wimg + (size_t)(tw * 32 + l31) * WP + ks * 16 + 8 * half;
-        wv[ks & 1][0] = *reinterpret_cast<const u32x4*>(wrow);
-        wv[ks & 1][1] = *reinterpret_cast<const u32x4*>(wrow + (size_t)NOUT * WP);
-        wv[ks & 1][2] = *reinterpret_cast<const u32x4*>(wrow + (size_t)2 * NOUT * WP);
+        wv[ks & 1].p[0] = *reinterpret_cast<const u32x4*>(wrow);
+        wv[ks & 1].p[1] = *reinterpret_cast<const u32x4*>(wrow + (size_t)NOUT * WP);
+        wv[ks & 1].p[2] = *reinterpret_cast<const u32x4*>(wrow + (size_t)2 * NOUT * WP);
       };
       read_a(0);
       read_w(0);
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
-        const float v[8] = {glo.x, glo.y, glo.z, glo.w, ghi.x, ghi.y, ghi.z, ghi.w};
-        const Frag3 fa = split_frag(v);
+        const Frag3 fa = split_frag(glo, ghi);
         if (ks + 1 < NKS) {  // the next k-step's LDS reads, issued before this k-step's MFMAs
           read_w(ks + 1);
           read_a(ks + 1);
         }
-        const u32x4 w1 = wv[ks & 1][0], w2 = wv[ks & 1][1], w3 = wv[ks & 1][2];
-        // rows x output columns: lane = output column, registers = rows; small terms first
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[2]), as_bf16x8(w1), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[0]), as_bf16x8(w3), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[1]), as_bf16x8(w2), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[1]), as_bf16x8(w1), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[0]), as_bf16x8(w2), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[0]), as_bf16x8(w1), acc, 0, 0, 0);
+        mfma_split6(acc, fa, wv[ks & 1]);  // rows x output columns: lane = output column, registers = rows
         __builtin_amdgcn_sched_barrier(0);
       }
       // bias, ReLU -> LDS [row][column]: 32 consecutive banks per half-wave
@@ -232,7 +222,7 @@ fwd_fused_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
       for (int reg = 0; reg < 16; ++reg) {
         float v = acc[reg] + bv;
         if (a.relu) v = v > 0.f ? v : 0.f;
-        orow[((reg & 3) + 8 * (reg >> 2)) * OP] = v;
+        orow[acc_row(reg, 0) * OP] = v;  // (orow holds the half)
       }
     }
     __syncthreads();
@@ -365,7 +355,7 @@ fwd_reg_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
   };
 
   // ---- this wave's weight fragments of the segment, split, and its bias column(s)
-  u32x4 wf[TPW][NKS][3];
+  Frag3 wf[TPW][NKS];
   float bv[TPW];
   auto load_w = [&](int seg_) {
     // prepared images ([segment][32-column tile][k-step][piece][lane], fwd_weight_images): coalesced 1 KiB wave loads
@@ -378,7 +368,7 @@ fwd_reg_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) wf[j][ks][pc] = base[(size_t)(((twb + 2 * j) * NKS + ks) * 3 + pc) * 64];
+        for (int pc = 0; pc < 3; ++pc) wf[j][ks].p[pc] = base[(size_t)(((twb + 2 * j) * NKS + ks) * 3 + pc) * 64];
       const int64_t boff = tl.b[seg_];
       bv[j] = (a.bias != nullptr && boff >= 0) ? a.bias[boff + (twb + 2 * j) * 32 + l31] : 0.f;
     }
@@ -401,9 +391,7 @@ fwd_reg_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
   auto products = [&](int row0_, int valid_) {
     f32x16 acc[TPW];
 #pragma unroll
-    for (int j = 0; j < TPW; ++j)
-#pragma unroll
-      for (int k = 0; k < 16; ++k) acc[j][k] = 0.f;
+    for (int j = 0; j < TPW; ++j) acc[j] = zero_acc();
     float4 glo, ghi;
     auto read_a = [&](int ks) {
       const float* arow = As + (rb * 32 + l31) * AP + ks * 16 + 8 * half;
@@ -413,20 +401,10 @@ fwd_reg_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
     read_a(0);
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
-      const float v[8] = {glo.x, glo.y, glo.z, glo.w, ghi.x, ghi.y, ghi.z, ghi.w};
-      const Frag3 fa = split_frag(v);
+      const Frag3 fa = split_frag(glo, ghi);
       if (ks + 1 < NKS) read_a(ks + 1);  // the next k-step's LDS read, issued before this k-step's MFMAs
 #pragma unroll
-      for (int j = 0; j < TPW; ++j) {
-        const u32x4 w1 = wf[j][ks][0], w2 = wf[j][ks][1], w3 = wf[j][ks][2];
-        // rows x output columns: lane = output column, registers = rows; small terms first
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[2]), as_bf16x8(w1), acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[0]), as_bf16x8(w3), acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[1]), as_bf16x8(w2), acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[1]), as_bf16x8(w1), acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[0]), as_bf16x8(w2), acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(fa.p[0]), as_bf16x8(w1), acc[j], 0, 0, 0);
-      }
+      for (int j = 0; j < TPW; ++j) mfma_split6(acc[j], fa, wf[j][ks]);  // lane = output column, registers = rows
       __builtin_amdgcn_sched_barrier(0);
     }
     const int rl0 = rb * 32 + 4 * half;
@@ -441,7 +419,7 @@ fwd_reg_kernel(SegTable st, int n_tiles, FwdArgs a, int rev) {
       // all of them instead of s_waitcnt vmcnt(16 + ...): the stores' latency would be serialised with the next tile.)
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int r8 = (reg & 3) + 8 * (reg >> 2);
+        const int r8 = acc_row(reg, 0);  // (rl0 holds the half)
         const bool live = rl0 + r8 < valid_;
         float v = acc[j][reg] + bv[j];
         if (a.relu) v = v > 0.f ? v : 0.f;

@@ -539,7 +539,6 @@ int gcmi_gather_max_bwd(const gcmi_graph* g, const float* d_dout, int64_t lddo, 
 // return GCMI_ERR_UNSUPPORTED and launch nothing.  Rows are 16-byte pieces to the LDS-DMA, so every row pointer must be
 // 16-byte aligned and every leading dimension a whole number of pieces.
 static bool rows16(const void* p, int64_t ld, int per_piece) { return aligned16(p) && ld % per_piece == 0; }
-static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 static int win_refused(const char* what, int n_feat) {
   set_error("%s: no window pass for this batch at %d features (window plan, width or LDS)", what, n_feat);
   return GCMI_ERR_UNSUPPORTED;

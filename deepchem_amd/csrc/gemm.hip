@@ -21,10 +21,9 @@
 #include <atomic>
 
 #include "common.h"
+#include "split_bf16.h"  // f32x16, acc_row: the fp32 MFMA has the bf16 one's accumulator layout
 
 namespace gcmi {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int kGBlock = 256;
 constexpr int BM = 64;
@@ -142,6 +141,7 @@ seg_gemm_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1,
     const float bv = (bias != nullptr && boff >= 0) ? bias[boff + col] : 0.f;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
+      // acc_row(reg, lane >> 5), written out: summed in the helper's order this kernel compiles to other code
       const int r = wr * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
       if (r < rows_valid) {
         float v = acc[reg] + bv;
@@ -186,9 +186,7 @@ seg_gemm2_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
   const int wrow = wave;  // 4 waves x 32 rows, each over all NT 32-column tiles
   f32x16 acc[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+  for (int t = 0; t < NT; ++t) acc[t] = zero_acc();
 
   const int64_t woff1 = pick_n(st.w_off[0], s), woff2 = pick_n(st.w_off[1], s);
   const bool on1 = a1 != nullptr && w1 != nullptr && woff1 >= 0;
@@ -374,9 +372,7 @@ wgrad_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, int 
   const int half = lane >> 5;
   f32x16 acc[KT];
 #pragma unroll
-  for (int t = 0; t < KT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+  for (int t = 0; t < KT; ++t) acc[t] = zero_acc();
   float bsum = 0.f;
   bool k_ok[KT];
   int kcol[KT];
@@ -466,7 +462,7 @@ wgrad_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, int 
     for (int t = 0; t < KT; ++t) {
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int rix = (reg & 3) + 8 * (reg >> 2) + 4 * half;  // accumulator row of this register
+        const int rix = acc_row(reg, half);
         if constexpr (TRANS) {
           const int nc = nt * 32 + rix;  // rows of dW^T = output columns n
           if (nc < n && k_ok[t]) atomicAdd(dw + woff + (int64_t)nc * k + kcol[t], acc[t][reg]);
@@ -849,9 +845,7 @@ namespace gcmi {
 __global__ void __launch_bounds__(256) mfma_peak_kernel(int iters, float* out) {
   f32x16 acc[4];
 #pragma unroll
-  for (int t = 0; t < 4; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+  for (int t = 0; t < 4; ++t) acc[t] = zero_acc();
   float a = (float)(threadIdx.x & 7) * 0.25f, b = (float)(threadIdx.x & 3) * 0.5f;
   for (int it = 0; it < iters; ++it) {
 #pragma unroll

@@ -177,15 +177,9 @@ seg_gemm4_kernel(SegTable st, const float* __restrict__ a1, int64_t lda1, int k1
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
           const int j = t * 32 + (lane & 31);
-          const u32x4 b1 = *reinterpret_cast<const u32x4*>(&Ws[0][j][kk0]);
-          const u32x4 b2 = *reinterpret_cast<const u32x4*>(&Ws[1][j][kk0]);
-          const u32x4 b3 = *reinterpret_cast<const u32x4*>(&Ws[2][j][kk0]);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(b3), as_bf16x8(fa.p[0]), acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(b1), as_bf16x8(fa.p[2]), acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(b2), as_bf16x8(fa.p[1]), acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(b2), as_bf16x8(fa.p[0]), acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(b1), as_bf16x8(fa.p[1]), acc[t], 0, 0, 0);
-          acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(b1), as_bf16x8(fa.p[0]), acc[t], 0, 0, 0);
+          const Frag3 fw = {{*reinterpret_cast<const u32x4*>(&Ws[0][j][kk0]), *reinterpret_cast<const u32x4*>(&Ws[1][j][kk0]),
+                             *reinterpret_cast<const u32x4*>(&Ws[2][j][kk0])}};
+          mfma_split6(acc[t], fw, fa);  // W is the A operand: the accumulator holds out^T
         }
       }
       __syncthreads();
@@ -353,9 +347,7 @@ wgrad3_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, con
   const bool n_ok = ncol < n;
   f32x16 acc[KT];
 #pragma unroll
-  for (int t = 0; t < KT; ++t)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[t][i] = 0.f;
+  for (int t = 0; t < KT; ++t) acc[t] = zero_acc();
   float bsum = 0.f;
   bool k_ok[KT];
   int kcol[KT];
@@ -396,12 +388,7 @@ wgrad3_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, con
       // and its lane index is the contiguous index of the destination (see wgrad_kernel)
       const Frag3& L = TRANS ? fg : fa;
       const Frag3& R = TRANS ? fa : fg;
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[2]), as_bf16x8(R.p[0]), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[2]), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[1]), as_bf16x8(R.p[1]), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[1]), as_bf16x8(R.p[0]), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[1]), acc[t], 0, 0, 0);
-      acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[0]), acc[t], 0, 0, 0);
+      mfma_split6(acc[t], L, R);
     }
   };
   if (r_begin < r_end) {
@@ -450,7 +437,7 @@ wgrad3_kernel(SlabTable st, const float* __restrict__ a, int64_t lda, int k, con
     for (int t = 0; t < KT; ++t) {
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int rix = (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        const int rix = acc_row(reg, half);
         if constexpr (TRANS) {
           const int nc = nt * 32 + rix;
           if (nc < n && k_ok[t]) atomicAdd(dw + woff + (int64_t)nc * k + kcol[t], acc[t][reg]);

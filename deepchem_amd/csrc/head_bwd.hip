@@ -215,17 +215,6 @@ constexpr int kImgTiles = kHB / 32, kImgKs = kWTC / 16;
 constexpr int kImgEntries = kImgTiles * kImgKs * 3 * 64;  // u32x4 entries of one image (393 KB)
 static_assert(kHeadImgFloats == 2 * kImgEntries * 4, "common.h: workspace floats of the two head images");
 
-__device__ __forceinline__ f32x16 six_products(const u32x4 (&r)[3], const Frag3& c, f32x16 acc) {
-  // rows fragment r (lane = row), columns fragment c (lane = column); small terms first
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r[2]), as_bf16x8(c.p[0]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r[0]), as_bf16x8(c.p[2]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r[1]), as_bf16x8(c.p[1]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r[1]), as_bf16x8(c.p[0]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r[0]), as_bf16x8(c.p[1]), acc, 0, 0, 0);
-  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(r[0]), as_bf16x8(c.p[0]), acc, 0, 0, 0);
-  return acc;
-}
-
 #ifdef GCMI_HEAD_DIAG_BUILD  // diagnostic build only (tools/head_diag.sh): phase clocks of workgroup 0, thread 0
 __device__ unsigned long long g_head_clk[3][8];
 #define HD_BEGIN() unsigned long long hd_t0 = 0, hd_t1 = 0; const bool hd_on = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0; \
@@ -444,19 +433,16 @@ __global__ void __launch_bounds__(kWT) head_bwd_wide_kernel(HeadArgs a, float* _
   __syncthreads();
   HD_T(0, 4);
   // ---- phase 2: d fingerprint[32 x 256] = d logits[32 x TC] . W[TC x 256], this wave's 32 columns
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  f32x16 acc = zero_acc();
 #pragma unroll
   for (int ks = 0; ks < kWTC / 16; ++ks) {
     if (ks < nks) {
-      u32x4 r[3];
+      Frag3 r, fw;
 #pragma unroll
-      for (int p = 0; p < 3; ++p) r[p] = *reinterpret_cast<const u32x4*>(&dlp[p][l31][ks * 16 + 8 * half]);
-      Frag3 fw;
+      for (int p = 0; p < 3; ++p) r.p[p] = *reinterpret_cast<const u32x4*>(&dlp[p][l31][ks * 16 + 8 * half]);
 #pragma unroll
       for (int p = 0; p < 3; ++p) fw.p[p] = wr[ks][p];
-      acc = six_products(r, fw, acc);
+      mfma_split6(acc, r, fw);
     }
   }
   HD_T(0, 5);
@@ -467,7 +453,7 @@ __global__ void __launch_bounds__(kWT) head_bwd_wide_kernel(HeadArgs a, float* _
     float* grow = a.g2 + c0 * a.ldg2 + k;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int m = acc_row(r, half);
       if (m < nm) {
         const float fvr = fp_s[m * kHB + k];
         const float g = acc[r] * (1.f - fvr * fvr);
@@ -558,8 +544,9 @@ head_wgrad_wide_kernel(const float* __restrict__ dl, int TC, const float* __rest
       }
       const Frag3 fa = split_frag(ca[s]);
       const Frag3 fb = split_frag(cb[s]);
-      const u32x4 r[3] = {fa.p[0], fa.p[1], fa.p[2]};
-      acc = six_products(r, fb, acc);
+      f32x16 t = acc;  // (a copy, here and below: with acc itself passed by reference this kernel compiles to other code)
+      mfma_split6(t, fa, fb);
+      acc = t;
     }
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -589,16 +576,17 @@ head_wgrad_wide_kernel(const float* __restrict__ dl, int TC, const float* __rest
       }
       const Frag3 fa = split_frag(va[s]);
       const Frag3 fb = split_frag(vb[s]);
-      const u32x4 r[3] = {fa.p[0], fa.p[1], fa.p[2]};
-      acc = six_products(r, fb, acc);
+      f32x16 t = acc;
+      mfma_split6(t, fa, fb);
+      acc = t;
     }
   }
   HD_T(1, 0);
-  const int row0 = blockIdx.y * 64 + (wave & 1) * 32 + 4 * half;
+  const int row0 = blockIdx.y * 64 + (wave & 1) * 32;
   float* dcol = dw + k;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int row = row0 + (r & 3) + 8 * (r >> 2);
+    const int row = row0 + acc_row(r, half);
     if (row < TC && acc[r] != 0.f) atomicAdd(dcol + row * kHB, acc[r]);
   }
   if (bias_wave) {
@@ -694,22 +682,19 @@ __global__ void __launch_bounds__(kWT) head_fwd_wide_kernel(const float* __restr
   store_chunk(0);
   __syncthreads();
   HD_T(2, 0);
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  f32x16 acc = zero_acc();
   // one barrier per k-step: while a wave multiplies chunk c, the others split chunk c + 1 into the other buffer
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     if (c + 1 < NCH) store_chunk(c + 1);
     if (tile) {
-      u32x4 r[3];
-      Frag3 fw;
+      Frag3 r, fw;
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
-        r[p] = *reinterpret_cast<const u32x4*>(&ap[p][l31][c * kFWC + 8 * half]);
+        r.p[p] = *reinterpret_cast<const u32x4*>(&ap[p][l31][c * kFWC + 8 * half]);
         fw.p[p] = *reinterpret_cast<const u32x4*>(&wp[c & 1][p][n][8 * half]);
       }
-      acc = six_products(r, fw, acc);
+      mfma_split6(acc, r, fw);
     }
     __syncthreads();
   }
@@ -718,7 +703,7 @@ __global__ void __launch_bounds__(kWT) head_fwd_wide_kernel(const float* __restr
     float* ocol = out + row0 * ldo + n;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int m = acc_row(r, half);
       if (m < valid) ocol[m * ldo] = acc[r] + bv;
     }
   }
@@ -758,9 +743,7 @@ __global__ void __launch_bounds__(256) head_prep_kernel(const float* __restrict_
   }
   const Frag3 f = split_frag(v);
   u32x4* dst = img + (size_t)which * kImgEntries + ((size_t)(tile * kImgKs + ks) * 3) * 64 + lane;
-  dst[0] = f.p[0];
-  dst[64] = f.p[1];
-  dst[128] = f.p[2];
+  store_frag3(dst, f);
 }
 
 // The forward over the prepared image: a workgroup = 32 rows, eight waves = the eight 32-column tiles of the output;
@@ -789,12 +772,10 @@ __global__ void __launch_bounds__(kWT) head_fwd_img_kernel(const float* __restri
   const float bv = (bias != nullptr && n < TC) ? bias[n] : 0.f;
   constexpr int NKS = kHB / 16, HK = NKS / 2;
   const u32x4* wsrc = img + ((size_t)wave * kImgKs * 3) * 64 + lane;
-  u32x4 wa[HK][3], wb[HK][3];
+  Frag3 wa[HK], wb[HK];
   if (tile) {
 #pragma unroll
-    for (int ks = 0; ks < HK; ++ks)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) wa[ks][p] = wsrc[(ks * 3 + p) * 64];
+    for (int ks = 0; ks < HK; ++ks) wa[ks] = load_frag3(wsrc + ks * 3 * 64);
   }
 #pragma unroll
   for (int p = 0; p < kHM * (kHB / 4) / kWT; ++p) {
@@ -809,32 +790,25 @@ __global__ void __launch_bounds__(kWT) head_fwd_img_kernel(const float* __restri
   }
   if (tile) {
 #pragma unroll
-    for (int ks = 0; ks < HK; ++ks)
-#pragma unroll
-      for (int p = 0; p < 3; ++p) wb[ks][p] = wsrc[((HK + ks) * 3 + p) * 64];
+    for (int ks = 0; ks < HK; ++ks) wb[ks] = load_frag3(wsrc + (HK + ks) * 3 * 64);
   }
   __syncthreads();
   HD_T(2, 0);
   if (!tile) return;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  f32x16 acc = zero_acc();
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) {
-    u32x4 r[3];
+    Frag3 r;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) r[p] = *reinterpret_cast<const u32x4*>(&ap[p][l31][ks * 16 + 8 * half]);
-    Frag3 fw;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) fw.p[p] = ks < HK ? wa[ks < HK ? ks : 0][p] : wb[ks >= HK ? ks - HK : 0][p];
-    acc = six_products(r, fw, acc);
+    for (int p = 0; p < 3; ++p) r.p[p] = *reinterpret_cast<const u32x4*>(&ap[p][l31][ks * 16 + 8 * half]);
+    mfma_split6(acc, r, ks < HK ? wa[ks < HK ? ks : 0] : wb[ks >= HK ? ks - HK : 0]);
   }
   HD_T(2, 1);
   if (n < TC) {
     float* ocol = out + row0 * ldo + n;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const int m = (r & 3) + 8 * (r >> 2) + 4 * half;
+      const int m = acc_row(r, half);
       if (m < valid) ocol[m * ldo] = acc[r] + bv;
     }
   }
