@@ -233,6 +233,10 @@ _SIGNATURES = {
     "gcmi_dmpnn_message": [c_int32, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
     "gcmi_dmpnn_update_fwd": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int64,
                               _P, c_int64, _P],
+    "gcmi_dmpnn_collate": [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int32, c_int32, c_int32,
+                           _P, c_int64, _P],
+    "gcmi_dmpnn_collate_host": [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, _P, c_int32, c_int32,
+                                c_int32, _P, c_int64],
     "gcmi_model_forward": [_MD, _G, _P, _MIO, c_int32, _P],
     "gcmi_model_loss_backward": [_MD, _G, _P, _P, _MIO, _P, _P, c_int64, _I64P, _I64P, _P],
     # (the two pointers before the stream: gcmi_stat_sync_fn and its context)
@@ -266,7 +270,8 @@ _SIGNATURES = {
 
 EXPORTS = ["gcmi_version", "gcmi_last_error", "gcmi_model_workspace_floats", "gcmi_small_workspace_floats",
            "gcmi_task_head_scratch_floats", "gcmi_fwd_fused_scratch_floats", "gcmi_lamb_scratch_floats", "gcmi_metrics_workspace_bytes",
-           "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout"] + sorted(_SIGNATURES)
+           "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout",
+           "gcmi_dmpnn_collate_words"] + sorted(_SIGNATURES)
 
 _lib = None
 
@@ -312,6 +317,7 @@ def load():
         "gcmi_fwd_fused_scratch_floats": (c_int64, []),
         "gcmi_lamb_scratch_floats": (c_int64, [c_int64, c_int64]),
         "gcmi_metrics_workspace_bytes": (c_int64, [c_int64, c_int32]),
+        "gcmi_dmpnn_collate_words": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _I64P]),
     }
     for name, (restype, argtypes) in special.items():
         if host_only and not hasattr(lib, name):

@@ -6,12 +6,15 @@ The reference builds, per molecule and in Python, padded index arrays (``_Mapper
 gathers a ``(bonds, max_degree, hidden)`` tensor per message-passing round.  Here a batch is a ``DmpnnBatch``: atoms in
 dataset order, directed bonds stably sorted by SOURCE atom (``out_ptr``), ``rev[b]`` the position of the reverse bond,
 no pad rows, one upload.  ``fit`` / ``predict`` on a ``NumpyDataset`` of ``GraphData`` keep the flat arrays of the whole
-dataset (built once, cached like ``DTNNModel.resident_set``); a batch is then an index gather over them.  The arithmetic
+dataset (built once, cached like ``DTNNModel.resident_set``); a batch is then an index gather over them: in numpy
+(``DmpnnGraphSet.batch``) or, from ``DMPNN_DEVICE_COLLATE_MIN`` molecules per batch up, by ``gcmi_dmpnn_collate`` over a
+``ResidentDmpnnSet`` in device memory -- the same bytes either way (``DMPNNModel(collate=...)``).  The arithmetic
 is in ``dmpnn_layers`` (which also documents the reference's message-loop quirk, kept by default, and ``bias=True``).
 
 ``_MapperDMPNN`` is kept with the reference's attributes and ``values`` (its per-atom loop vectorised): the torch path
 and the tests read it through ``DmpnnBatch.to_reference_arrays()``.
 """
+import os
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -148,6 +151,32 @@ class DmpnnGraphSet(object):
         return DmpnnBatch(self, np.asarray(mol_idx, np.int64).reshape(-1))
 
 
+_FLOAT_BLOCKS = ("atoms_per_mol", "atom_features", "f_ini_atoms_bonds", "global_features")
+
+
+def pack_batch_words(host):
+    """The nine host arrays of a batch as ONE vector of 4-byte words in the layout of ``ops.dmpnn_batch_layout`` (the
+    one routine that places the blocks, for ``DmpnnBatch.to`` and for ``gcmi_dmpnn_collate``), pad words zero:
+    ``(words, layout)``."""
+    n_mols, n_atoms, n_bonds = len(host["mol_ptr"]) - 1, host["atom_features"].shape[0], len(host["rev"])
+    fa = host["atom_features"].shape[1]
+    total, layout = ops.dmpnn_batch_layout(n_mols, n_atoms, n_bonds, fa, host["f_ini_atoms_bonds"].shape[1] - fa,
+                                           host["global_features"].shape[1])
+    words = np.zeros(total, np.int32)
+    for k, (o, shape) in layout.items():
+        a = host[k]
+        if a.shape != shape or a.dtype != (np.float32 if k in _FLOAT_BLOCKS else np.int32):
+            raise ValueError("DmpnnBatch: %s is %s %s, the layout has %s" % (k, a.dtype, a.shape, shape))
+        words[o:o + a.size] = np.ascontiguousarray(a).reshape(-1).view(np.int32)
+    return words, layout
+
+
+def split_batch_words(words: np.ndarray, layout):
+    """The inverse of ``pack_batch_words``: the nine arrays, as copies."""
+    return {k: words[o:o + int(np.prod(shape))].view(np.float32 if k in _FLOAT_BLOCKS else np.int32).reshape(shape).copy()
+            for k, (o, shape) in layout.items()}
+
+
 class DmpnnBatch(object):
     """One batch in the layout ``gcmi_dmpnn_message`` reads, gathered from a ``DmpnnGraphSet`` by molecule index:
 
@@ -180,7 +209,7 @@ class DmpnnBatch(object):
         mol_ptr, out_ptr, bond_src, rev, atom_features, bond_features, global_features = _arrays
         self.n_mols, self.n_atoms, self.n_bonds = len(mol_ptr) - 1, atom_features.shape[0], len(rev)
         self._validate(np.asarray(mol_ptr), np.asarray(out_ptr), np.asarray(bond_src), np.asarray(rev))
-        self.host = {
+        self._host = {
             "mol_ptr": np.asarray(mol_ptr, np.int32), "out_ptr": np.asarray(out_ptr, np.int32),
             "bond_src": np.asarray(bond_src, np.int32), "rev": np.asarray(rev, np.int32),
             "atom_membership": np.repeat(np.arange(self.n_mols, dtype=np.int32), np.diff(mol_ptr)),
@@ -192,6 +221,45 @@ class DmpnnBatch(object):
         }
         self.device = None
         self.plan = None
+        self._words = None
+
+    @property
+    def host(self):
+        """The nine arrays of the batch on the host.  A batch collated by the device (``from_device``) downloads and
+        splits its buffer on first use."""
+        if self._host is None:
+            self._host = split_batch_words(self._words.cpu().numpy(), self._layout)
+        return self._host
+
+    @host.setter
+    def host(self, arrays):
+        self._host = arrays
+
+    @classmethod
+    def from_device(cls, graphs: "DmpnnGraphSet", mol_idx: np.ndarray, words: torch.Tensor, n_atoms: int,
+                    n_bonds: int) -> "DmpnnBatch":
+        """Around a buffer ``gcmi_dmpnn_collate`` wrote from a ``ResidentDmpnnSet`` of ``graphs``: the attributes of
+        ``to()``, nothing on the host until ``host`` is asked for.  Not validated per batch: see ``ResidentDmpnnSet``."""
+        self = cls.__new__(cls)
+        self.graphs, self.mol_idx = graphs, mol_idx
+        self.n_mols, self.n_atoms, self.n_bonds = int(mol_idx.size), int(n_atoms), int(n_bonds)
+        self._host, self.device, self.plan = None, None, None
+        total, layout = ops.dmpnn_batch_layout(self.n_mols, self.n_atoms, self.n_bonds, graphs.atom_fdim,
+                                               graphs.bond_fdim, graphs.global_features.shape[1])
+        if words.dtype != torch.int32 or words.dim() != 1 or words.numel() != total:
+            raise ValueError("DmpnnBatch.from_device: the buffer must hold the %d int32 words of the layout" % total)
+        self._adopt(words, layout, words.device)
+        return self
+
+    def _adopt(self, words: torch.Tensor, layout, device):
+        """The attributes as views of the packed buffer on its device."""
+        for k, (o, shape) in layout.items():
+            t = words[o:o + int(np.prod(shape))]
+            if k in _FLOAT_BLOCKS:
+                t = t.view(torch.float32)
+            setattr(self, k, t.reshape(shape))
+        self.plan = layers.BondPlan(self.out_ptr, self.rev, self.bond_src)
+        self._words, self._layout, self.device = words, layout, device
 
     def _validate(self, mol_ptr, out_ptr, bond_src, rev):
         A, B = self.n_atoms, self.n_bonds
@@ -236,25 +304,8 @@ class DmpnnBatch(object):
         if self.device == device:
             return self
         # one buffer of 4-byte words, every block at a 16-byte boundary: ONE host-to-device copy
-        names, offset, words = list(self.host), 0, []
-        where = {}
-        for k in names:
-            a = self.host[k]
-            where[k] = (offset, a.size)
-            words.append(a.reshape(-1).view(np.int32))
-            pad = (-a.size) % 4
-            if pad:
-                words.append(np.zeros(pad, np.int32))
-            offset += a.size + pad
-        buf = torch.from_numpy(np.concatenate(words) if offset else np.zeros(0, np.int32)).to(device)
-        for k in names:
-            o, n = where[k]
-            t = buf[o:o + n]
-            if self.host[k].dtype == np.float32:
-                t = t.view(torch.float32)
-            setattr(self, k, t.reshape(self.host[k].shape))
-        self.plan = layers.BondPlan(self.out_ptr, self.rev, self.bond_src)
-        self.device = device
+        words, layout = pack_batch_words(self.host)
+        self._adopt(torch.from_numpy(words).to(device), layout, device)
         return self
 
     @property
@@ -280,6 +331,105 @@ class DmpnnBatch(object):
         cat = np.concatenate
         return (cat(af).astype(np.float32), cat(f_ini).astype(np.float32), cat(a2b).astype(np.int64),
                 cat(mapping).astype(np.int64), cat(gf).astype(np.float32))
+
+
+class ResidentDmpnnSet(object):
+    """A ``DmpnnGraphSet`` in device memory, uploaded once per dataset; ``batch(mol_idx)`` is then O(n_mols) work on the
+    host -- the counts of the selected molecules, their two prefix sums, one pinned staging buffer ``[mol_idx ; atom_off
+    ; bond_off]`` in one copy -- and ``gcmi_dmpnn_collate`` writes the packed batch buffer on the device, the same
+    bytes ``DmpnnGraphSet.batch(mol_idx).to(device)`` uploads.
+
+    Arrays (``ops.DMPNN_SET_ARRAYS``): ``atom_ptr``, ``bond_ptr`` (int64, M + 1), ``atom_features`` (A x Fa),
+    ``bond_features`` ALREADY in the kernels' order (``bond_features[order]``, B x Fb), ``sorted_src`` / ``sorted_rev``
+    (int32, local to the molecule), ``out_start`` (int32 per atom: the exclusive prefix of ``out_degree`` inside the
+    molecule, so that ``out_ptr[atom_off[m] + i] = bond_off[m] + out_start[atom_ptr[sel[m]] + i]`` without a scan per
+    batch) and ``global_features`` (M x G).  The per-molecule counts stay on the host.
+
+    What ``DmpnnBatch._validate`` checks per batch is a property of the SET and is checked here, once:
+
+    * no atom has more than ``ops.DMPNN_MAX_DEGREE`` bonds (the same ``ValueError``), and a batch's atoms are atoms of
+      the set;
+    * ``rev`` is an involution without fixed points inside every molecule: ``DmpnnGraphSet`` builds ``sorted_rev`` as
+      ``position[order ^ 1] - bond_ptr[mol]``, the position of the partner ``b ^ 1``, which lies in the same molecule
+      (every molecule has an even number of bonds), differs from ``b`` and has ``b`` as ITS partner.  A batch places
+      every selected molecule -- a repeated one once per occurrence -- in a block of its own, ``[bond_off[m],
+      bond_off[m + 1])``, and adds ``bond_off[m]`` to the local positions: the batch's ``rev`` is the direct sum of
+      involutions over disjoint blocks, hence an involution without fixed points, for EVERY selection;
+    * ``out_ptr`` rises from 0 to the number of bonds and agrees with ``bond_src``: inside a molecule ``out_start`` is
+      the prefix sum of the out-degrees of bonds sorted by source atom, and the blocks are laid end to end;
+    * the set holds fewer than 2^31 atoms and bonds (local and batch indices are int32; addressing into the set's
+      feature arrays is 64-bit).
+
+    ``device`` may be the CPU: the arrays then stay there, for ``plan`` and ``ops.dmpnn_collate_host``."""
+
+    def __init__(self, graphs: DmpnnGraphSet, device):
+        self.graphs, self.device = graphs, torch.device(device)
+        self.host_arrays = self.arrays_of(graphs)
+        self.n_atoms_of = np.diff(graphs.atom_ptr)
+        self.n_bonds_of = np.diff(graphs.bond_ptr)
+        self.arrays = {k: torch.from_numpy(a).to(self.device) for k, a in self.host_arrays.items()}
+        self.nbytes = self.bytes_needed(graphs)
+
+    @staticmethod
+    def bytes_needed(graphs: DmpnnGraphSet) -> int:
+        A, B, M = int(graphs.atom_ptr[-1]), int(graphs.bond_ptr[-1]), graphs.n_mols
+        return 16 * (M + 1) + 4 * (A * (graphs.atom_fdim + 1) + B * (graphs.bond_fdim + 2) +
+                                   M * graphs.global_features.shape[1])
+
+    @staticmethod
+    def arrays_of(graphs: DmpnnGraphSet):
+        """The set's arrays on the host, validated (see the class)."""
+        A, B = int(graphs.atom_ptr[-1]), int(graphs.bond_ptr[-1])
+        if max(A, B, graphs.n_mols) > 2 ** 31 - 2:
+            raise ValueError("ResidentDmpnnSet: the set holds %d atoms and %d directed bonds; the device collation "
+                             "covers fewer than 2^31 - 1 of each" % (A, B))
+        degree = graphs.out_degree
+        if A and degree.max() > ops.DMPNN_MAX_DEGREE:
+            raise ValueError("DmpnnBatch: an atom has %d bonds; the D-MPNN kernels cover a degree of at most %d" %
+                             (int(degree.max()), ops.DMPNN_MAX_DEGREE))
+        mol_of_atom = np.repeat(np.arange(graphs.n_mols), np.diff(graphs.atom_ptr))
+        out_start = np.cumsum(degree) - degree - graphs.bond_ptr[mol_of_atom]
+        c = np.ascontiguousarray
+        return {"atom_ptr": c(graphs.atom_ptr, np.int64), "bond_ptr": c(graphs.bond_ptr, np.int64),
+                "atom_features": c(graphs.atom_features.reshape(A, graphs.atom_fdim), np.float32),
+                "bond_features": c(graphs.bond_features[graphs.order].reshape(B, graphs.bond_fdim), np.float32),
+                "sorted_src": c(graphs.sorted_src, np.int32), "sorted_rev": c(graphs.sorted_rev, np.int32),
+                "out_start": c(out_start, np.int32),
+                "global_features": c(graphs.global_features.reshape(graphs.n_mols, -1), np.float32)}
+
+    def plan(self, mol_idx, pinned: bool = False):
+        """``(plan, n_atoms, n_bonds)``: the int32 words ``[mol_idx ; atom_off ; bond_off]`` of a batch (a torch tensor,
+        in pinned memory if asked) and its totals.  O(n_mols); a molecule index outside the set is a ``ValueError``."""
+        sel = np.asarray(mol_idx, np.int64).reshape(-1)
+        n = sel.size
+        if n and (sel.min() < 0 or sel.max() >= self.graphs.n_mols):
+            raise ValueError("DmpnnBatch: molecule index outside the graph set")
+        na, nb = self.n_atoms_of[sel], self.n_bonds_of[sel]
+        n_atoms, n_bonds = int(na.sum()), int(nb.sum())
+        if max(n, n_atoms, n_bonds) > 2 ** 31 - 2:
+            raise ValueError("DmpnnBatch: a batch holds fewer than 2^31 - 1 molecules, atoms and bonds")
+        staging = torch.empty(3 * n + 2, dtype=torch.int32, pin_memory=pinned)
+        words = staging.numpy()
+        words[:n] = sel
+        words[n], words[2 * n + 1] = 0, 0
+        np.cumsum(na, out=words[n + 1:2 * n + 1])
+        np.cumsum(nb, out=words[2 * n + 2:])
+        return staging, n_atoms, n_bonds
+
+    def batch(self, mol_idx) -> "DmpnnBatch":
+        """The batch of the molecules ``mol_idx`` (in order, repeats allowed), collated on the current stream."""
+        if self.device.type != "cuda":
+            raise ValueError("ResidentDmpnnSet.batch: the set is not on a GPU (there is no CPU path)")
+        staging, n_atoms, n_bonds = self.plan(mol_idx, pinned=True)
+        n = (staging.numel() - 2) // 3
+        words = ops.dmpnn_collate(self.arrays, staging.to(self.device, non_blocking=True), n, n_atoms, n_bonds)
+        return DmpnnBatch.from_device(self.graphs, np.asarray(mol_idx, np.int64).reshape(-1), words, n_atoms, n_bonds)
+
+
+# Batches of at least this many molecules are collated on the device by collate="auto".  Measured (DESIGN section 45):
+# the device-collated training step was the faster one at every batch size tried, 32 included; smaller batches were not
+# measured and stay on the host route
+DMPNN_DEVICE_COLLATE_MIN = 32
 
 
 class DMPNN(nn.Module):
@@ -323,7 +473,11 @@ class DMPNN(nn.Module):
 class DMPNNModel(TorchModel):
     """D-MPNN on datasets of ``GraphData`` (``feat.NativeGraphFeaturizer``, or graphs featurized elsewhere with the
     reference's ``DMPNNFeaturizer``: 133 atom and 14 bond features, ``use_default_fdim=True``).  The reference's arguments
-    plus ``message_mode`` (see ``dmpnn_layers``)."""
+    plus ``message_mode`` (see ``dmpnn_layers``) and ``collate``: where the batches of ``fit`` / ``predict`` / ``evaluate``
+    on a ``NumpyDataset`` of graphs are gathered -- ``"host"`` (numpy over the ``DmpnnGraphSet``, one upload per batch),
+    ``"device"`` (``gcmi_dmpnn_collate`` over a ``ResidentDmpnnSet``; a ``ValueError`` naming the reason where that
+    cannot be done) or ``"auto"``: the device where ``_device_collate_refusal`` finds nothing against it and the batch
+    size is at least ``DMPNN_DEVICE_COLLATE_MIN``."""
 
     def __init__(self, mode: str = 'regression', n_classes: int = 3, n_tasks: int = 1, batch_size: int = 1,
                  global_features_size: int = 0, use_default_fdim: bool = True, atom_fdim: int = 133,
@@ -331,7 +485,9 @@ class DMPNNModel(TorchModel):
                  enc_activation: str = 'relu', enc_dropout_p: float = 0.0, aggregation: str = 'mean',
                  aggregation_norm: Union[int, float] = 100, ffn_hidden: int = 300, ffn_activation: str = 'relu',
                  ffn_layers: int = 3, ffn_dropout_p: float = 0.0, ffn_dropout_at_input_no_act: bool = True,
-                 message_mode: str = "reference", **kwargs):
+                 message_mode: str = "reference", collate: str = "auto", **kwargs):
+        if collate not in ("auto", "host", "device"):
+            raise ValueError("collate must be 'auto', 'host' or 'device' (got %r)" % (collate,))
         model = DMPNN(mode=mode, n_classes=n_classes, n_tasks=n_tasks, global_features_size=global_features_size,
                       use_default_fdim=use_default_fdim, atom_fdim=atom_fdim, bond_fdim=bond_fdim,
                       enc_hidden=enc_hidden, depth=depth, bias=bias, enc_activation=enc_activation,
@@ -346,6 +502,8 @@ class DMPNNModel(TorchModel):
         super(DMPNNModel, self).__init__(model, loss=loss, output_types=output_types, batch_size=batch_size, **kwargs)
         self._flat_step = True  # parameters, gradients and optimizer state in flat buffers (TorchModel._ensure_built)
         self._graph_set = None  # (the X array it was built from, DmpnnGraphSet)
+        self.collate = collate
+        self._resident = None   # (that X array, ResidentDmpnnSet or the reason why there is none)
 
     def _prepare_batch(self, batch):
         """A list of ``GraphData`` (``default_generator``) becomes a ``DmpnnBatch``; one made by ``_batch_generator``
@@ -372,19 +530,71 @@ class DMPNNModel(TorchModel):
             self._graph_set = (X, DmpnnGraphSet(X))
         return self._graph_set[1]
 
+    def _device_collate_refusal(self) -> Optional[str]:
+        """What, apart from the dataset, keeps the batches from being collated on the device; None: nothing."""
+        if self.device.type != "cuda":
+            return "the model is on %s, not on a GPU" % self.device
+        if self.model.encoder.W_i.bias is not None:
+            return "bias=True runs plain torch over to_reference_arrays(), which reads the batch on the host"
+        if os.environ.get("GCMI_RESIDENT_SET", "1") == "0":
+            return "GCMI_RESIDENT_SET=0 switches resident sets off"
+        return None
+
+    def _resident_for(self, X):
+        """The ``ResidentDmpnnSet`` of ``X``, uploaded once and kept until another array is asked for -- or, as a string,
+        why there is none: the set must fit into a quarter of the device memory that is free when it is built."""
+        held = self._resident
+        if held is None or held[0] is not X:
+            graphs = self.graph_set(X)
+            need = ResidentDmpnnSet.bytes_needed(graphs)
+            free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
+            if need > free // 4:
+                made = "the set needs %d bytes, more than a quarter of the %d free on the device" % (need, free)
+            else:
+                made = ResidentDmpnnSet(graphs, self.device)
+            self._resident = (X, made)
+        return self._resident[1]
+
+    def resident_set(self, X) -> ResidentDmpnnSet:
+        """The graphs of ``X`` in device memory (cached); a ``ValueError`` where the set does not fit there."""
+        made = self._resident_for(X)
+        if isinstance(made, str):
+            raise ValueError("DMPNNModel: no resident graph set: " + made)
+        return made
+
+    def _route(self, X) -> Optional[ResidentDmpnnSet]:
+        """The resident set that collates the batches of ``X`` on the device, or None: the host collates them."""
+        if self.collate == "host":
+            return None
+        why = self._device_collate_refusal()
+        if why is None:
+            if self.collate == "auto" and self.batch_size < DMPNN_DEVICE_COLLATE_MIN:
+                return None  # (a preference, not an obstacle: collate="device" goes below it)
+            made = self._resident_for(X)
+            if not isinstance(made, str):
+                return made
+            why = made
+        if self.collate == "device":
+            raise ValueError("DMPNNModel(collate='device'): " + why)
+        return None
+
     def _batch_generator(self, dataset, epochs: int = 1, mode: str = 'fit', deterministic: bool = True,
                          pad_batches: bool = False):
         """For a ``NumpyDataset`` of graphs: the molecule INDICES follow the dataset's own batch walk (same order,
-        same shuffles from ``np.random``), a batch is an index gather over the cached flat arrays.  Anything else:
+        same shuffles from ``np.random``), a batch is an index gather over the cached flat arrays: by numpy
+        (``DmpnnGraphSet.batch``) or, where ``_route`` says so, by the device over the resident set.  Anything else:
         ``default_generator``.  ``pad_batches`` defaults to False as in the reference."""
         X = getattr(dataset, "X", None) if isinstance(dataset, NumpyDataset) else None
         if not (isinstance(X, np.ndarray) and X.dtype == object and X.ndim == 1):
+            if self.collate == "device":
+                raise ValueError("DMPNNModel(collate='device'): the dataset is not a NumpyDataset of GraphData")
             yield from self.default_generator(dataset, epochs=epochs, mode=mode, deterministic=deterministic,
                                               pad_batches=pad_batches)
             return
         graphs = self.graph_set(X)
+        resident = self._route(X)
         index_set = NumpyDataset(np.arange(X.shape[0]), dataset.y, dataset.w, dataset.ids)
         for _ in range(epochs):
             for (idx, y_b, w_b, _ids) in index_set.iterbatches(batch_size=self.batch_size, deterministic=deterministic,
                                                                pad_batches=pad_batches):
-                yield (graphs.batch(idx), [y_b], [w_b])
+                yield ((graphs if resident is None else resident).batch(idx), [y_b], [w_b])

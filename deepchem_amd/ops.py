@@ -9,6 +9,7 @@ every byte of the hot path moves in libgcmi.so.
 import ctypes
 from typing import Optional
 
+import numpy as np
 import torch
 
 from deepchem_amd import _lib
@@ -936,6 +937,91 @@ def dmpnn_update_fwd(x: torch.Tensor, inp: torch.Tensor, weight: torch.Tensor, o
               _ptr(out_ptr), _ptr(rev), _ptr(bond_src), n_atoms, n_bonds, _ptr(scratch), scratch.numel(), _ptr(h), _ld(h),
               _stream())
     return h
+
+
+DMPNN_BATCH_BLOCKS = ("mol_ptr", "out_ptr", "bond_src", "rev", "atom_membership", "atoms_per_mol", "atom_features",
+                      "f_ini_atoms_bonds", "global_features")
+# dmpnn_collate_kernel: one workgroup of DMPNN_COLLATE_THREADS threads per molecule; a pass of the workgroup covers that
+# many per-atom / per-bond words and flat atom-row words, and DMPNN_COLLATE_ROWS_PER_PASS f_ini rows (one per wave)
+DMPNN_COLLATE_MOLS_PER_WORKGROUP = 1
+DMPNN_COLLATE_THREADS = 256
+DMPNN_COLLATE_ROWS_PER_PASS = DMPNN_COLLATE_THREADS // 64
+
+
+def dmpnn_batch_layout(n_mols: int, n_atoms: int, n_bonds: int, atom_fdim: int, bond_fdim: int, global_fdim: int):
+    """The packed D-MPNN batch buffer (``gcmi_dmpnn_collate_words``): ``(words, {block: (offset, shape)})`` for the
+    nine blocks of ``DMPNN_BATCH_BLOCKS``, 4-byte words, every block at a 16-byte boundary."""
+    sizes = (n_mols, n_atoms, n_bonds, atom_fdim, bond_fdim, global_fdim)
+    if min(sizes) < 0 or max(sizes) > 2 ** 31 - 1:
+        raise ValueError("dmpnn_batch_layout: sizes must be within [0, 2^31): %r" % (sizes,))
+    off = (ctypes.c_int64 * len(DMPNN_BATCH_BLOCKS))()
+    words = int(_lib.load().gcmi_dmpnn_collate_words(*[int(s) for s in sizes], off))
+    if words < 0:
+        raise _lib.GcmiError("gcmi_dmpnn_collate_words: %s" % _lib.load().gcmi_last_error().decode())
+    shapes = ((n_mols + 1,), (n_atoms + 1,), (n_bonds,), (n_bonds,), (n_atoms,), (n_mols, 1), (n_atoms, atom_fdim),
+              (n_bonds, atom_fdim + bond_fdim), (n_mols, global_fdim))
+    return words, {k: (int(off[i]), shapes[i]) for i, k in enumerate(DMPNN_BATCH_BLOCKS)}
+
+
+DMPNN_SET_ARRAYS = ("atom_ptr", "bond_ptr", "atom_features", "bond_features", "sorted_src", "sorted_rev", "out_start",
+                    "global_features")
+
+
+def _dmpnn_collate_sizes(arrays, n_mols: int, n_atoms: int, n_bonds: int):
+    M = arrays["atom_ptr"].shape[0] - 1
+    fa, fb, fg = (int(arrays[k].shape[1]) for k in ("atom_features", "bond_features", "global_features"))
+    if M < 0 or arrays["bond_ptr"].shape[0] != M + 1 or arrays["global_features"].shape[0] != M:
+        raise ValueError("dmpnn_collate: atom_ptr, bond_ptr and global_features must cover the same molecules")
+    A, B = arrays["atom_features"].shape[0], arrays["bond_features"].shape[0]
+    if arrays["out_start"].shape[0] != A or arrays["sorted_src"].shape[0] != B or arrays["sorted_rev"].shape[0] != B:
+        raise ValueError("dmpnn_collate: out_start needs one entry per atom, sorted_src and sorted_rev one per bond")
+    if min(n_mols, n_atoms, n_bonds) < 0 or max(n_mols, n_atoms, n_bonds) > 2 ** 31 - 2:
+        raise ValueError("dmpnn_collate: a batch holds at most 2^31 - 2 molecules, atoms and bonds")
+    return M, fa, fb, fg
+
+
+def dmpnn_collate(arrays, plan: torch.Tensor, n_mols: int, n_atoms: int, n_bonds: int) -> torch.Tensor:
+    """``gcmi_dmpnn_collate``: the packed batch buffer (int32 words, ``dmpnn_batch_layout``) of the molecules named by
+    ``plan`` = ``[mol_idx ; atom_off ; bond_off]`` (int32, on the device), gathered from the resident set ``arrays``
+    (``DMPNN_SET_ARRAYS``: contiguous CUDA tensors, the two offset arrays int64, indices int32, features float32 2-D).
+    The molecule indices must have been validated by the caller: the kernel skips a bad one, it does not report it."""
+    M, fa, fb, fg = _dmpnn_collate_sizes(arrays, n_mols, n_atoms, n_bonds)
+    want = {"atom_ptr": torch.int64, "bond_ptr": torch.int64, "sorted_src": torch.int32, "sorted_rev": torch.int32,
+            "out_start": torch.int32}
+    for k in DMPNN_SET_ARRAYS:
+        t = arrays[k]
+        if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == want.get(k, torch.float32)):
+            raise _lib.GcmiError("dmpnn_collate: %s must be a contiguous %s CUDA tensor" % (k, want.get(k, torch.float32)))
+    _i32vec(plan, "plan", 3 * n_mols + 2)
+    words, _ = dmpnn_batch_layout(n_mols, n_atoms, n_bonds, fa, fb, fg)
+    out = torch.empty(words, dtype=torch.int32, device=plan.device)
+    _lib.call("gcmi_dmpnn_collate", *[_ptr(arrays[k]) for k in DMPNN_SET_ARRAYS], M, fa, fb, fg, _ptr(plan), n_mols, n_atoms,
+              n_bonds, _ptr(out), words, _stream())
+    return out
+
+
+def dmpnn_collate_host(arrays, plan: np.ndarray, n_mols: int, n_atoms: int, n_bonds: int,
+                       out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``gcmi_dmpnn_collate_host``: the same routine over numpy arrays, for tests without a GPU.  ``out``: an int32
+    vector to write into (at least the layout's words)."""
+    M, fa, fb, fg = _dmpnn_collate_sizes(arrays, n_mols, n_atoms, n_bonds)
+    want = {"atom_ptr": np.int64, "bond_ptr": np.int64, "sorted_src": np.int32, "sorted_rev": np.int32,
+            "out_start": np.int32}
+    for k in DMPNN_SET_ARRAYS:
+        a = arrays[k]
+        if not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == want.get(k, np.float32)):
+            raise ValueError("dmpnn_collate_host: %s must be a C-contiguous %s array" % (k, np.dtype(want.get(k, np.float32))))
+    if not (isinstance(plan, np.ndarray) and plan.dtype == np.int32 and plan.flags.c_contiguous and
+            plan.size == 3 * n_mols + 2):
+        raise ValueError("dmpnn_collate_host: plan must hold 3 * n_mols + 2 int32 words")
+    words, _ = dmpnn_batch_layout(n_mols, n_atoms, n_bonds, fa, fb, fg)
+    if out is None:
+        out = np.empty(words, np.int32)
+    if not (out.dtype == np.int32 and out.flags.c_contiguous and out.ndim == 1):
+        raise ValueError("dmpnn_collate_host: out must be a contiguous int32 vector")
+    _lib.call("gcmi_dmpnn_collate_host", *[_vp(arrays[k].ctypes.data) for k in DMPNN_SET_ARRAYS], M, fa, fb, fg,
+              _vp(plan.ctypes.data), n_mols, n_atoms, n_bonds, _vp(out.ctypes.data), out.size)
+    return out
 
 
 def edge_network_sum(g: torch.Tensor, n_hidden: int, pair_feat: torch.Tensor, dst_ptr: torch.Tensor,

@@ -997,6 +997,38 @@ int gcmi_dmpnn_update_fwd(const float* d_x, int64_t ldx, const float* d_input, i
                           const int32_t* d_bond_src, int32_t n_atoms, int32_t n_bonds, float* d_img_scratch,
                           int64_t scratch_floats, float* d_h, int64_t ldh, void* stream);
 
+/* ---------------------------------------------------------------- D-MPNN batch collation (dmpnn_collate.hip)
+ * A batch of the D-MPNN kernels above, gathered on the device from a graph set that stays in device memory.  The set,
+ * M = n_mols_all molecules with A atoms and B directed bonds in all: d_atom_ptr, d_bond_ptr [M + 1]; d_atom_features
+ * [A x atom_fdim]; d_bond_features [B x bond_fdim] with the bonds of every molecule stably sorted by source atom;
+ * d_sorted_src [B] the source atom and d_sorted_rev [B] the position of the reverse bond, both local to the molecule;
+ * d_out_start [A]: where the atom's run of outgoing bonds begins, relative to the molecule's first bond;
+ * d_global_features [M x global_fdim].  d_plan: int32 words [mol_idx (n_mols) ; atom_off (n_mols + 1) ; bond_off
+ * (n_mols + 1)], the offsets being the exclusive prefix sums of the selected molecules' atom and bond counts, totals
+ * last (= n_atoms, n_bonds).
+ * d_out receives nine blocks of 4-byte words, each starting at a 16-byte boundary, pad words zero:
+ *   mol_ptr (n_mols + 1), out_ptr (n_atoms + 1), bond_src (n_bonds), rev (n_bonds), atom_membership (n_atoms),
+ *   atoms_per_mol (n_mols, float), atom_features (n_atoms x atom_fdim), f_ini_atoms_bonds (n_bonds x (atom_fdim +
+ *   bond_fdim): [features of the source atom ; bond features]), global_features (n_mols x global_fdim).
+ * gcmi_dmpnn_collate_words returns the words of that buffer and, with offsets != NULL, the nine block offsets (-1: a
+ * negative size).  Every word is written exactly once, pad words included; no atomics.  A molecule index outside
+ * [0, M), or a molecule that would not fit the totals, is skipped and not read through (its words stay unwritten: the
+ * caller validates the indices).  NULL pointers, negative sizes, misaligned buffers and out_words below the layout's:
+ * GCMI_ERR_ARG before any launch.
+ * gcmi_dmpnn_collate_host: the same routine run by host loops over host buffers, for tests without a GPU.           */
+int64_t gcmi_dmpnn_collate_words(int32_t n_mols, int32_t n_atoms, int32_t n_bonds, int32_t atom_fdim, int32_t bond_fdim,
+                                 int32_t global_fdim, int64_t* offsets);
+int gcmi_dmpnn_collate(const int64_t* d_atom_ptr, const int64_t* d_bond_ptr, const float* d_atom_features,
+                       const float* d_bond_features, const int32_t* d_sorted_src, const int32_t* d_sorted_rev,
+                       const int32_t* d_out_start, const float* d_global_features, int64_t n_mols_all,
+                       int32_t atom_fdim, int32_t bond_fdim, int32_t global_fdim, const int32_t* d_plan, int32_t n_mols,
+                       int32_t n_atoms, int32_t n_bonds, int32_t* d_out, int64_t out_words, void* stream);
+int gcmi_dmpnn_collate_host(const int64_t* atom_ptr, const int64_t* bond_ptr, const float* atom_features,
+                            const float* bond_features, const int32_t* sorted_src, const int32_t* sorted_rev,
+                            const int32_t* out_start, const float* global_features, int64_t n_mols_all, int32_t atom_fdim,
+                            int32_t bond_fdim, int32_t global_fdim, const int32_t* plan, int32_t n_mols, int32_t n_atoms,
+                            int32_t n_bonds, int32_t* out, int64_t out_words);
+
 /* ---------------------------------------------------------------- measurement
  * Optional per-kernel timing with hipEvents recorded on `stream` around the
  * launches of one kernel family (bench.py roofline).  id: see GCMI_K_*.       */

@@ -9,7 +9,9 @@ Synthetic molecules from ``deepchem_amd.utils.synthetic`` (18.5 atoms on average
 the default model (enc_hidden 300, depth 3).  Per configuration: warm-up steps, then the MEDIAN of repeated steps,
 each ended by a device synchronise; peak memory = ``torch.cuda.max_memory_allocated`` over the timed steps.
 ``native_ms`` has its batch on the device already, like the torch step; ``native_collate_ms`` also gathers the batch
-from the cached graph set and uploads it every step (what ``fit`` does).  One JSON line per batch size and mode.
+from the cached graph set in numpy and uploads it every step (what ``fit`` does with ``collate="host"``);
+``native_devcollate_ms`` collates it on the device from the resident set instead, index upload included (what ``fit``
+does from ``DMPNN_DEVICE_COLLATE_MIN`` molecules per batch up).  One JSON line per batch size and mode.
 """
 import argparse
 import gc
@@ -87,11 +89,17 @@ def main():
                 model._train_step(graphs.batch(idx).to(model.device), labels, weights, model._loss_fn,
                                   model._pytorch_optimizer)
 
+            resident = model.resident_set(X)
+
+            def native_devcollate_step():
+                model._train_step(resident.batch(idx), labels, weights, model._loss_fn, model._pytorch_optimizer)
+
             t_native, m_native = timed(native_step, args.warmup, args.steps)
             t_collate, _ = timed(native_collate_step, args.warmup, args.steps)
+            t_devcollate, _ = timed(native_devcollate_step, args.warmup, args.steps)
             state = {k: v.detach().cpu().numpy() for k, v in model.model.state_dict().items()}
             host, n_atoms, n_bonds = batch.host, batch.n_atoms, batch.n_bonds
-            del model, batch, graphs, native_step, native_collate_step
+            del model, batch, graphs, resident, native_step, native_collate_step, native_devcollate_step
             gc.collect()
             torch.cuda.empty_cache()
 
@@ -111,6 +119,7 @@ def main():
             torch.cuda.empty_cache()
             print(json.dumps({"batch": B, "mode": mode, "atoms": n_atoms, "bond_rows": n_bonds,
                               "native_ms": round(t_native, 4), "native_collate_ms": round(t_collate, 4),
+                              "native_devcollate_ms": round(t_devcollate, 4),
                               "torch_ms": round(t_torch, 4), "ratio": round(t_torch / t_native, 3),
                               "native_peak_mib": round(m_native, 1), "torch_peak_mib": round(m_torch, 1)}), flush=True)
 
