@@ -1,5 +1,6 @@
 """Batches, oracle steps and the qualification rule for the per-step gradient tests of the small-batch engine
-(tests/test_small_refs_host.py on the CPU, tests/test_gpu_small_grads.py on the device).  No test is collected here.
+(tests/test_small_refs_host.py on the CPU, tests/test_gpu_small_grads.py on the device) and of the large-batch step
+(tests/test_large_refs_host.py, tests/test_gpu_large_grads.py).  No test is collected here.
 
 Why batches are qualified.  The gradient of this model is only piecewise smooth: a ReLU gate, a GraphPool route or a
 GraphGather route flips when two numbers come within rounding of each other, and away from flips the backward amplifies
@@ -90,6 +91,35 @@ def shaped_molecules(seed, pad=0):
     return packed
 
 
+_K4 = [[1, 2, 3], [0, 2, 3], [0, 1, 3], [0, 1, 2]]
+TILED_KINDS = [("atom", _ATOM, 7), ("ring4", _RING4, 16), ("k4", _K4, 15), ("star3", _star(3), 3), ("star10", _star(10), 1),
+               ("pair", _PAIR, 55)]
+# rows per degree: the 64-row tiles (kFRows) and 128-row slabs (kS3Rows) of the large-batch step
+TILED_HISTOGRAM = {0: 7, 1: 129, 2: 64, 3: 63, 4: 0, 5: 0, 6: 0, 7: 0, 8: 0, 9: 0, 10: 1}
+
+
+def tiled_molecules(seed):
+    """97 molecules (three head rounds of kHM = 32, plus one), 264 atoms, degree blocks on the tile edges of the
+    large-batch step: degree 0: 7 rows, degree 1: 129 (a 128-row slab + 1, two 64-row tiles + 1), degree 2: 64 (exactly
+    one tile), degree 3: 63 (a tile less one row), degrees 4..9 empty, degree 10: one row.  Molecule order shuffled by
+    ``RandomState(seed)``; features as in ``shaped_molecules``: 0/1 at density 0.1, 75 columns."""
+    rng = np.random.RandomState(seed)
+    kinds = [adj for _, adj, count in TILED_KINDS for _ in range(count)]
+    adjs = [kinds[i] for i in rng.permutation(len(kinds))]
+    sizes = np.array([len(a) for a in adjs], np.int64)
+    atom_ptr = np.zeros(len(adjs) + 1, np.int64)
+    np.cumsum(sizes, out=atom_ptr[1:])
+    deg = np.array([len(nb) for a in adjs for nb in a], np.int64)
+    adj_ptr = np.zeros(deg.shape[0] + 1, np.int64)
+    np.cumsum(deg, out=adj_ptr[1:])
+    adj_idx = np.array([j for a in adjs for nb in a for j in nb], np.int32)
+    feats = (rng.random_sample((int(atom_ptr[-1]), 75)) < 0.1).astype(np.float32)
+    packed = PackedMols(feats, atom_ptr, adj_ptr, adj_idx)
+    assert packed.n_mols == 97 and packed.n_atoms == 264
+    assert degree_histogram(packed) == TILED_HISTOGRAM, degree_histogram(packed)
+    return packed
+
+
 def ordinary_molecules(seed):
     """34 molecules, about 500 atoms: 28 Tox21-like ones and the six edge cases; some degree blocks span many tiles."""
     return concat_packed([synthetic_molecules(28, seed=seed, max_atoms=40), single_atom_and_edge_cases(75, seed)])
@@ -104,6 +134,9 @@ MODELS = {
     "D": Model("regression", 1, (128, 128), 256, True),          # two-tile forms; readout <64>; pool+dense <4>; T C = 1
     "E": Model("classification", 12, (64, 128, 64, 64), 64, False),  # four layers, no BatchNorm, 24 head blocks
     "F": Model("classification", 1, (256,), 256, True),          # one layer: no pool-in conv
+    # large-batch step only (LARGE_NEW): the dense block and GraphConv 1 run as separate launches, GraphConv 0 in one
+    # pass below them, with BatchNorm -- the one order in which a stale `have_psums` of the walk would be consumed
+    "G": Model("classification", 3, (64, 128), 128, True),
 }
 GRAD_MODES = ("full", "reference")
 KINDS = ("shaped", "padded", "ordinary")
@@ -133,6 +166,9 @@ def batch_of(kind, seed):
     if kind == "padded":
         p = shaped_molecules(seed, pad=PAD)
         return p, p.n_mols - PAD
+    if kind == "tiled":
+        p = tiled_molecules(seed)
+        return p, p.n_mols
     assert kind == "ordinary"
     p = ordinary_molecules(seed)
     return p, p.n_mols
@@ -142,6 +178,9 @@ def batch_of(kind, seed):
 def case_inputs(model_id, kind, seed):
     """packed, y, w (float64, whole batch), cfg, state, n_real.  Rows from n_real on repeat the first rows; their weights
     are zeroed where the batch is formed (``oracle_step`` / the device batches), as pad_batch does."""
+    if kind.startswith("width"):
+        assert model_id == "A"
+        return width_inputs(int(kind[len("width"):]), seed)
     m = MODELS[model_id]
     packed, n_real = batch_of(kind, seed)
     n = packed.n_mols
@@ -151,6 +190,23 @@ def case_inputs(model_id, kind, seed):
     cfg = model_cfg(model_id, n)
     state = O.init_state(cfg, seed)
     return packed, y, w, cfg, state, n_real
+
+
+WIDTHS = (33, 64, 65, 96, 97)  # layer-0 input columns on the K-chunk edges of the large step's one-pass backward
+
+
+def width_inputs(k, seed):
+    """``case_inputs`` of model A at ``k`` input columns: the topology of ``shaped_molecules(seed)``, features
+    continuous (uniform in [-1, 1]) so that a column dropped, swapped or read from the padding moves the result."""
+    t = shaped_molecules(seed)
+    feats = np.random.RandomState(7000 + 100 * seed + k).uniform(-1, 1, (t.n_atoms, k)).astype(np.float32)
+    packed = PackedMols(feats, t.atom_ptr, t.adj_ptr, t.adj_idx)
+    m = MODELS["A"]
+    n = packed.n_mols
+    y, w = synthetic_labels(n, m.T, m.mode, seed, pos_rate=0.4)
+    cfg = O.ModelConfig(m.T, graph_conv_layers=m.widths, number_input_features=(k,) + tuple(m.widths[:-1]),
+                        dense_layer_size=m.dense, mode=m.mode, batch_normalize=m.bn, batch_size=n)
+    return packed, y, w, cfg, O.init_state(cfg, seed), n
 
 
 # ---------------------------------------------------------------------------------------------- the oracle
@@ -268,20 +324,32 @@ def worst_distance(got, want):
     return worst, name
 
 
-def qualify(model_id, kind, seed, grad_mode):
-    """(q1, q2) of one case and gradient mode.  q1: the worst tensor_distance of the float32 oracle's gradient from the
-    float64 oracle's.  q2: the worst tensor_distance, over ``Q2_DRAWS`` draws of ``perturbed(mag=2^-21)`` from
-    ``RandomState(1000 + seed)``, of the perturbed float64 gradient from the unperturbed one."""
-    packed, y, w, cfg, state, n_real = case_inputs(model_id, kind, seed)
-    r64, r32 = references(model_id, kind, seed, grad_mode)
+def qualify_inputs(packed, y, w, cfg, state, n_real, grad_mode, draw_seed=0, refs=None):
+    """The rule itself, on any batch and model: (q1, q2) of one step.  q1: the worst tensor_distance of the float32
+    oracle's gradient from the float64 oracle's.  q2: the worst tensor_distance, over ``Q2_DRAWS`` draws of
+    ``perturbed(mag=2^-21)`` from ``RandomState(1000 + draw_seed)``, of the perturbed float64 gradient from the
+    unperturbed one.  ``refs``: the (float64, float32) oracle steps where the caller already has them."""
+    if refs is None:
+        r64 = _reference(oracle_step(packed, y, w, cfg, state, grad_mode, n_real, double=True))
+        with _torch_threads(F32_THREADS):
+            r32 = _reference(oracle_step(packed, y, w, cfg, state, grad_mode, n_real, double=False))
+    else:
+        r64, r32 = refs
     q1 = worst_distance(r32.grads, r64.grads)[0]
-    rng = np.random.RandomState(1000 + seed)
+    rng = np.random.RandomState(1000 + draw_seed)
     q2 = 0.0
     for _ in range(Q2_DRAWS):
         p, st = perturbed(packed, state, rng, Q2_MAG)
         g = oracle_step(p, y, w, cfg, st, grad_mode, n_real, double=True)[2]
         q2 = max(q2, worst_distance(g, r64.grads)[0])
     return q1, q2
+
+
+def qualify(model_id, kind, seed, grad_mode):
+    """(q1, q2) of one case and gradient mode: ``qualify_inputs`` on ``case_inputs``, the perturbations drawn from
+    ``RandomState(1000 + seed)``."""
+    return qualify_inputs(*case_inputs(model_id, kind, seed), grad_mode, draw_seed=seed,
+                          refs=references(model_id, kind, seed, grad_mode))
 
 
 def qualifies(q1, q2):
@@ -314,3 +382,19 @@ ONE_STEP = [next(c for c in CASES if (c.model, c.kind) == mk) for mk in
             [("A", "ordinary"), ("B", "ordinary"), ("C", "ordinary")]]
 SEQUENCE = {"A": 64, "B": 7}   # model -> the seed whose three batch kinds all qualify
 SEQUENCE_KINDS = ("ordinary", "shaped", "padded")
+
+# What the per-route gradient tests of the large-batch step run (tests/test_gpu_large_grads.py):
+# every one-step case above, the tiled batch on the default model, on the four-layer one without BatchNorm and on model
+# G, and the five layer-0 widths.  The seed of each new entry is the first of 1, 2, ... that met q1 and q2 in both gradient modes
+# on the CPU (tests/test_large_refs_host.py re-checks them).
+LARGE_NEW = [
+    Case("A", "tiled", 2, GRAD_MODES),
+    Case("E", "tiled", 3, GRAD_MODES),
+    Case("G", "tiled", 1, GRAD_MODES),
+    Case("A", "width33", 1, GRAD_MODES),
+    Case("A", "width64", 2, GRAD_MODES),
+    Case("A", "width65", 4, GRAD_MODES),
+    Case("A", "width96", 2, GRAD_MODES),
+    Case("A", "width97", 1, GRAD_MODES),
+]
+LARGE_CASES = list(ONE_STEP) + LARGE_NEW

@@ -16,38 +16,59 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
 
 
-def _native_step(packed, y, w, tasks, grad_mode, state, use_codes=False, widths=(64, 64), dense=128, mode="classification",
-                 n_classes=2, n_feat=75):
-    """forward + loss + backward through the whole-model C entry points on ONE natively collated batch.
-    Returns loss, logits, fingerprint, the gradient arena, (name, slice) pairs, the trained range, running stats."""
-    import deepchem_amd as dc
-    from deepchem_amd.data.collate import collate_to_device
+def _device_labels(y, w, tasks, mode="classification", n_classes=2):
+    """Labels (one-hot for classification) and weights of one batch on the device."""
     from deepchem_amd.metrics import to_one_hot
-    n = packed.n_mols
-    dbatch = collate_to_device(packed, None, DEV)
     if mode == "classification":
         labels = torch.as_tensor(to_one_hot(y.flatten(), n_classes).reshape(-1, tasks, n_classes).astype(np.float32),
                                  device=DEV)
     else:
         labels = torch.as_tensor(y.astype(np.float32), device=DEV)
-    weights = torch.as_tensor(w.astype(np.float32), device=DEV)
+    return labels, torch.as_tensor(w.astype(np.float32), device=DEV)
+
+
+def _native_model(n, tasks, grad_mode, state, widths=(64, 64), dense=128, mode="classification", n_classes=2, n_feat=75,
+                  batch_norm=True):
+    """The model on the device from ``state`` and its NativeNet (the whole-model C entry points)."""
+    import deepchem_amd as dc
     model = dc.models.torch_models.GraphConvModel(tasks, number_input_features=[n_feat] + list(widths[:-1]),
                                                   graph_conv_layers=list(widths), dense_layer_size=dense, mode=mode,
-                                                  n_classes=n_classes, batch_size=n, grad_mode=grad_mode, device=DEV)
+                                                  n_classes=n_classes, batch_size=n, grad_mode=grad_mode,
+                                                  batch_normalize=batch_norm, device=DEV)
     model.model.load_state_dict({k: v.clone() for k, v in state.items()})
     native = model.model._native_net()
     assert native is not None
+    return model, native
+
+
+def _run_step(model, native, features, g, labels, weights, n_rows):
+    """forward(training) + loss + backward of ``native`` on one batch (features, graph ``g`` with its readout plan).
+    Returns loss, logits, fingerprint, the gradient arena, (name, slice) pairs, the trained range, running stats, g."""
+    model.model.train()
+    logits, _, fp = native.forward(features, g, True, want_probs=False)
+    loss = native.loss_backward(labels, weights, n_rows)
+    torch.cuda.synchronize()
+    names = [k for k, _ in model.model.named_parameters()]
+    stats = [(bn.running_mean.clone().cpu(), bn.running_var.clone().cpu()) for bn in model.model.batch_norms
+             if hasattr(bn, "running_mean")]
+    return (float(loss), logits.cpu(), fp.cpu(), native.grad_flat.clone().cpu(), list(zip(names, native._slices)),
+            native.grad_range, stats, g)
+
+
+def _native_step(packed, y, w, tasks, grad_mode, state, use_codes=False, widths=(64, 64), dense=128, mode="classification",
+                 n_classes=2, n_feat=75):
+    """forward + loss + backward through the whole-model C entry points on ONE natively collated batch.
+    Returns loss, logits, fingerprint, the gradient arena, (name, slice) pairs, the trained range, running stats.
+    (tests/test_gpu_large_grads.py runs the same three pieces with the route switched between them.)"""
+    from deepchem_amd.data.collate import collate_to_device
+    n = packed.n_mols
+    dbatch = collate_to_device(packed, None, DEV)
+    labels, weights = _device_labels(y, w, tasks, mode, n_classes)
+    model, native = _native_model(n, tasks, grad_mode, state, widths, dense, mode, n_classes, n_feat)
     g = dbatch.graph
     g.set_mols(n)
     assert g.c.n_win > 0, "the batch must carry window plans: this test is about the LDS-window kernels"
-    model.model.train()
-    logits, _, fp = native.forward(dbatch.atom_features, g, True, want_probs=False)
-    loss = native.loss_backward(labels, weights, n)
-    torch.cuda.synchronize()
-    names = [k for k, _ in model.model.named_parameters()]
-    stats = [(bn.running_mean.clone().cpu(), bn.running_var.clone().cpu()) for bn in model.model.batch_norms]
-    return (float(loss), logits.cpu(), fp.cpu(), native.grad_flat.clone().cpu(), list(zip(names, native._slices)),
-            native.grad_range, stats, g)
+    return _run_step(model, native, dbatch.atom_features, g, labels, weights, n)
 
 
 def _oracle_step(packed, y, w, tasks, grad_mode, state, double=False, widths=(64, 64), dense=128, mode="classification",
