@@ -230,6 +230,10 @@ _SIGNATURES = {
     "gcmi_dtnn_pair_bwd": [_P, c_int64, c_int32, _P, _P, c_int64, c_int32, _P, c_int64, c_int32, _P, _P, c_int32, _P,
                            c_int32, c_double, c_double, _P, c_int64, _P, c_int64, _P, _P, _P, _P],
     "gcmi_dtnn_collate": [_P, _P, _P, c_int32, c_int32, _P, c_int32, c_int32, c_int64, _P, _P, _P, _P, _P, _P, _P],
+    "gcmi_mat_bias": [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_float, c_float, c_float, _P, _P],
+    "gcmi_mat_attention_fwd": [_P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, c_int64, _P],
+    "gcmi_mat_attention_bwd": [_P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, c_int64,
+                               _P, _P, _P, c_int64, c_int32, _P],
     "gcmi_dmpnn_message": [c_int32, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
     "gcmi_dmpnn_update_fwd": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int64,
                               _P, c_int64, _P],

@@ -5,3 +5,4 @@ from deepchem_amd.models.torch_models.weavemodel_pytorch import Weave, WeaveMode
 from deepchem_amd.models.torch_models.mpnn import MPNNModel
 from deepchem_amd.models.torch_models.dtnn import DTNN, DTNNModel
 from deepchem_amd.models.torch_models.dmpnn import DMPNN, DMPNNModel
+from deepchem_amd.models.torch_models.mat import MAT, MATModel, MatBatch

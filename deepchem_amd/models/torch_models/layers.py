@@ -174,3 +174,5 @@ from deepchem_amd.models.torch_models.weave_layers import WeaveGather, WeaveLaye
 from deepchem_amd.models.torch_models.mpnn_layers import EdgeNetwork, GatedRecurrentUnit, SetGather  # noqa: E402,F401
 from deepchem_amd.models.torch_models.dtnn_layers import DTNNEmbedding, DTNNGather, DTNNStep  # noqa: E402,F401
 from deepchem_amd.models.torch_models.dmpnn_layers import DMPNNEncoderLayer, PositionwiseFeedForward  # noqa: E402,F401
+from deepchem_amd.models.torch_models.mat_layers import (MATEmbedding, MATEncoderLayer, MATGenerator,  # noqa: E402,F401
+                                                         MultiHeadedMATAttention, SublayerConnection)

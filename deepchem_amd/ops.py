@@ -868,6 +868,153 @@ def dtnn_collate(z_all, dist_all, n_atoms_all, mol_idx, n_atoms: int, n_pairs: i
     return atom_off, pair_off, z, d, mem_i, mem_j
 
 
+# ------------------------------------------------------------------ Molecule Attention Transformer
+MAT_MAX_ATOMS, MAT_MAX_DK = 128, 64
+MAT_DIST_KERNELS = {"softmax": 0, "exp": 1}
+
+
+class MatOffsets:
+    """The molecules of a pad-free batch: atom offsets and pair offsets (exclusive sums of n and n^2), on the host
+    (validated HERE, and again by every C entry before a launch) and on the device (what the kernels read)."""
+
+    def __init__(self, n_atoms_per_mol, device, uploaded: Optional[torch.Tensor] = None):
+        n = np.ascontiguousarray(n_atoms_per_mol, np.int64).reshape(-1)
+        if n.size == 0 or n.min() <= 0:
+            raise ValueError("MatOffsets: at least one molecule, every molecule with at least one atom")
+        if int((n * n).sum()) >= 2**31:
+            raise ValueError("MatOffsets: the pair blocks of a batch must stay below 2^31 entries")
+        self.n = n
+        self.atom_off = np.concatenate([[0], np.cumsum(n)]).astype(np.int32)
+        self.pair_off = np.concatenate([[0], np.cumsum(n * n)]).astype(np.int32)
+        self.n_mols, self.n_atoms, self.n_pairs = int(n.size), int(self.atom_off[-1]), int(self.pair_off[-1])
+        self.n_max = int(n.max())
+        self.device = torch.device(device)
+        # uploaded: [atom_off | pair_off] as int32 on the device already (part of the caller's own packed upload)
+        both = uploaded if uploaded is not None else torch.as_tensor(self.host_words(n), device=self.device)
+        if both.dtype != torch.int32 or both.numel() != 2 * self.n_mols + 2 or both.device.type != self.device.type or \
+                not both.is_contiguous():
+            raise ValueError("MatOffsets: the uploaded offsets must be 2 (n_mols + 1) contiguous int32 words on the device")
+        self.d_atom_off, self.d_pair_off = both[:self.n_mols + 1], both[self.n_mols + 1:]
+
+    @staticmethod
+    def host_words(n_atoms_per_mol) -> np.ndarray:
+        """[atom_off | pair_off] as int32: what the device copy holds."""
+        n = np.asarray(n_atoms_per_mol, np.int64).reshape(-1)
+        return np.concatenate([[0], np.cumsum(n), [0], np.cumsum(n * n)]).astype(np.int32)
+
+    def _args(self):
+        return (_vp(self.atom_off.ctypes.data), _vp(self.pair_off.ctypes.data), _ptr(self.d_atom_off),
+                _ptr(self.d_pair_off), self.n_mols)
+
+
+def _mat_offsets(offs, what: str) -> MatOffsets:
+    if not isinstance(offs, MatOffsets) or offs.device.type != "cuda":
+        raise _lib.GcmiError("%s: offsets must be a MatOffsets on the GPU" % what)
+    return offs
+
+
+def mat_bias(adj: torch.Tensor, dist: torch.Tensor, offs: MatOffsets, dist_kernel: str, lambda_distance: float,
+             lambda_adjacency: float, eps: float = 1e-6) -> torch.Tensor:
+    """One float per atom pair of the batch: lambda_distance * g(D) + lambda_adjacency * A / (rowsum(A) + eps)."""
+    offs = _mat_offsets(offs, "mat_bias")
+    if dist_kernel not in MAT_DIST_KERNELS:
+        raise ValueError("mat_bias: dist_kernel must be 'softmax' or 'exp'")
+    _vec(adj, "adjacency blocks", offs.n_pairs), _vec(dist, "distance blocks", offs.n_pairs)
+    bias = torch.empty(offs.n_pairs, dtype=torch.float32, device=adj.device)
+    _lib.call("gcmi_mat_bias", _ptr(adj), _ptr(dist), *offs._args(), MAT_DIST_KERNELS[dist_kernel], float(lambda_distance),
+              float(lambda_adjacency), float(eps), _ptr(bias), _stream())
+    return bias
+
+
+def _mat_rows(t, name, offs, width, ld=None):
+    t = _mat(t, name, rows=offs.n_atoms, cols=width)
+    if _ld(t) % 4 or t.data_ptr() % 16:
+        raise ValueError("%s: rows must be 16-byte aligned with a leading dimension of whole 16-byte pieces" % name)
+    if ld is not None and _ld(t) != ld:
+        raise ValueError("%s: leading dimension %d, expected %d" % (name, _ld(t), ld))
+    return t
+
+
+def _mat_attention_common(q, k, v, bias, offs, n_heads: int, d_k: int):
+    offs = _mat_offsets(offs, "mat_attention")
+    if n_heads <= 0 or d_k <= 0 or d_k % 4 or d_k > MAT_MAX_DK:
+        raise ValueError("mat_attention covers d_k a multiple of 4 up to %d (got %d heads of %d)" % (MAT_MAX_DK, n_heads, d_k))
+    if offs.n_max > MAT_MAX_ATOMS:
+        raise ValueError("mat_attention covers molecules of up to %d atoms (got %d)" % (MAT_MAX_ATOMS, offs.n_max))
+    width = n_heads * d_k
+    q = _mat_rows(q, "q", offs, width)
+    k, v = _mat_rows(k, "k", offs, width, _ld(q)), _mat_rows(v, "v", offs, width, _ld(q))
+    _vec(bias, "bias", offs.n_pairs)
+    return (_ptr(q), _ptr(k), _ptr(v), _ld(q), _ptr(bias)) + offs._args() + (n_heads, d_k), width
+
+
+def mat_attention_fwd(q, k, v, bias, offs: MatOffsets, n_heads: int, d_k: int, lambda_attention: float,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """O = (lambda_attention * softmax(Q K^T / sqrt(d_k)) + bias) V per (molecule, head); q, k, v: (atoms, n_heads * d_k)
+    views (they may be one tensor).  ``out``: write into these rows (columns of a wider matrix are left alone)."""
+    args, width = _mat_attention_common(q, k, v, bias, offs, n_heads, d_k)
+    o = torch.empty((offs.n_atoms, width), dtype=torch.float32, device=q.device) if out is None else \
+        _mat_rows(out, "out", offs, width)
+    _lib.call("gcmi_mat_attention_fwd", *args, float(lambda_attention), _ptr(o), _ld(o), _stream())
+    return o
+
+
+def mat_attention_bwd(q, k, v, bias, offs: MatOffsets, n_heads: int, d_k: int, lambda_attention: float, dO,
+                      shared: bool = False, out=None):
+    """(dQ, dK, dV), or with ``shared`` (q, k, v one tensor) their sum.  ``out``: the buffer(s) to write into."""
+    args, width = _mat_attention_common(q, k, v, bias, offs, n_heads, d_k)
+    dO = _mat_rows(dO, "dO", offs, width)
+    if shared and not (q.data_ptr() == k.data_ptr() == v.data_ptr()):
+        raise ValueError("mat_attention_bwd: shared needs q, k and v to be one tensor")
+    n_out = 1 if shared else 3
+    if out is None:
+        bufs = [torch.empty((offs.n_atoms, width), dtype=torch.float32, device=q.device) for _ in range(n_out)]
+    else:
+        bufs = [out] if torch.is_tensor(out) else list(out)
+        if len(bufs) != n_out:
+            raise ValueError("mat_attention_bwd: %d output buffer(s) expected" % n_out)
+        bufs = [_mat_rows(b, "gradient buffer", offs, width, _ld(bufs[0])) for b in bufs]
+        if len({b.data_ptr() for b in bufs}) != n_out:
+            raise ValueError("mat_attention_bwd: the gradient buffers must be distinct")
+    ptrs = [_ptr(b) for b in bufs] + [None] * (3 - n_out)
+    _lib.call("gcmi_mat_attention_bwd", *args, float(lambda_attention), _ptr(dO), _ld(dO), *ptrs, _ld(bufs[0]),
+              1 if shared else 0, _stream())
+    return bufs[0] if shared else tuple(bufs)
+
+
+class MatAttentionFn(torch.autograd.Function):
+    """(q, k, v) -> O of csrc/mat.hip.  Nothing is saved beyond the inputs; the backward recomputes the attention matrix.
+    Called with ONE tensor three times, the backward forms dQ + dK + dV in one buffer."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, offs: MatOffsets, n_heads: int, lambda_attention: float):
+        shared = q is k and k is v
+        q = rowmajor(q)
+        k, v = (q, q) if shared else (rowmajor(k), rowmajor(v))
+        d_k = q.shape[1] // n_heads
+        if d_k * n_heads != q.shape[1]:
+            raise ValueError("MatAttentionFn: %d columns are not %d heads" % (q.shape[1], n_heads))
+        ctx.meta = (offs, n_heads, d_k, float(lambda_attention), shared)
+        if shared:
+            ctx.save_for_backward(q, bias)
+        else:
+            ctx.save_for_backward(q, bias, k, v)
+        return mat_attention_fwd(q, k, v, bias, offs, n_heads, d_k, lambda_attention)
+
+    @staticmethod
+    def backward(ctx, dO):
+        offs, n_heads, d_k, lam, shared = ctx.meta
+        dO = rowmajor(dO)
+        if dO.data_ptr() % 16 or _ld(dO) % 4:
+            dO = dO.contiguous()
+        if shared:
+            q, bias = ctx.saved_tensors
+            return mat_attention_bwd(q, q, q, bias, offs, n_heads, d_k, lam, dO, True), None, None, None, None, None, None
+        q, bias, k, v = ctx.saved_tensors
+        dq, dk, dv = mat_attention_bwd(q, k, v, bias, offs, n_heads, d_k, lam, dO, False)
+        return dq, dk, dv, None, None, None, None
+
+
 # ------------------------------------------------------------------ message passing
 # ------------------------------------------------------------------ D-MPNN
 DMPNN_MAX_DEGREE = 32

@@ -964,6 +964,41 @@ int gcmi_dtnn_collate(const int32_t* d_z_all, const float* d_dist_all, const int
                       int32_t n_atoms, int64_t n_pairs, int32_t* d_atom_off, int32_t* d_pair_off, int32_t* d_z,
                       float* d_d, int32_t* d_mem_i, int32_t* d_mem_j, void* stream);
 
+/* ---------------------------------------------------------------- Molecule Attention Transformer (mat.hip)
+ * A pad-free batch: the atoms of its n_mols molecules concatenated, atom offsets [n_mols + 1] strictly increasing from
+ * 0, and per molecule a row-major n x n block of pair data at pair offsets [n_mols + 1] (the exclusive sums of n^2).
+ * The offsets are passed TWICE: h_atom_off / h_pair_off on the HOST, which every entry validates before any launch
+ * (and sizes its grid and LDS from), and d_atom_off / d_pair_off, the same numbers on the device, which the kernels
+ * read and trust only inside the bounds the host copy gives.
+ * gcmi_mat_bias: d_bias[p] = lambda_distance * g(D)[p] + lambda_adjacency * A[p] / (row sum of A + eps), g = the row
+ *   softmax of -D (GCMI_MAT_DIST_SOFTMAX; the row minimum is subtracted, so a row of equal distances is uniform and a
+ *   distance 1e6 above the row minimum gives an exact 0) or exp(-D) (GCMI_MAT_DIST_EXP).  Any molecule size.
+ * gcmi_mat_attention_fwd: O = (lambda_attention * softmax(Q K^T / sqrt(d_k)) + bias) V per (molecule, head); d_q, d_k,
+ *   d_v (they may be equal) are rows of ld floats with head h in columns [h d_k, (h + 1) d_k), d_o rows of ldo floats in
+ *   the same layout.  Columns past n_heads * d_k are neither read nor written.  Nothing of size n x n is written.
+ * gcmi_mat_attention_bwd: from the same inputs and d_do (rows of lddo floats) writes d_dq, d_dk, d_dv (rows of ldg
+ *   floats); shared != 0 (then d_q == d_k == d_v is required): their SUM into d_dq, d_dk / d_dv unused.  The attention
+ *   matrix is recomputed; no atomics, so two calls agree bit for bit.
+ * d_k a multiple of 4 up to 64 and molecules of at most GCMI_MAT_MAX_ATOMS atoms, else GCMI_ERR_UNSUPPORTED; NULL
+ * pointers, ld < n_heads * d_k, rows that are not 16-byte addressable (pointer or ld % 4), atoms x ld >= 2^31 (rows are
+ * indexed with 32-bit element offsets), n_mols <= 0, offsets that do not increase and, without shared, gradient
+ * buffers that are not three distinct ones are GCMI_ERR_ARG.                                                       */
+#define GCMI_MAT_MAX_ATOMS 128
+#define GCMI_MAT_DIST_SOFTMAX 0
+#define GCMI_MAT_DIST_EXP 1
+int gcmi_mat_bias(const float* d_adj, const float* d_dist, const int32_t* h_atom_off, const int32_t* h_pair_off,
+                  const int32_t* d_atom_off, const int32_t* d_pair_off, int32_t n_mols, int32_t dist_kernel,
+                  float lambda_distance, float lambda_adjacency, float eps, float* d_bias, void* stream);
+int gcmi_mat_attention_fwd(const float* d_q, const float* d_k, const float* d_v, int64_t ld, const float* d_bias,
+                           const int32_t* h_atom_off, const int32_t* h_pair_off, const int32_t* d_atom_off,
+                           const int32_t* d_pair_off, int32_t n_mols, int32_t n_heads, int32_t head_dim,
+                           float lambda_attention, float* d_o, int64_t ldo, void* stream);
+int gcmi_mat_attention_bwd(const float* d_q, const float* d_k, const float* d_v, int64_t ld, const float* d_bias,
+                           const int32_t* h_atom_off, const int32_t* h_pair_off, const int32_t* d_atom_off,
+                           const int32_t* d_pair_off, int32_t n_mols, int32_t n_heads, int32_t head_dim,
+                           float lambda_attention, const float* d_do, int64_t lddo, float* d_dq, float* d_dk, float* d_dv,
+                           int64_t ldg, int32_t shared, void* stream);
+
 /* ---------------------------------------------------------------- D-MPNN (dmpnn.hip)
  * The message aggregation of the directed message-passing network (deepchem/models/torch_models/layers.py:1629,
  * `message[mapping].sum(1)`, and :1539, `h_message[atom_to_incoming_bonds].sum(1)`) over a batch whose directed bonds
