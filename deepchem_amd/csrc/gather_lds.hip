@@ -11,7 +11,10 @@
 //     lane-linear) while window i is being computed from the other LDS buffer;
 //   * the neighbour lists of the window (uint16 LDS slots, window-major in HBM) arrive the same
 //     way, so the compute phase touches HBM only to store results;
-//   * the window descriptors (24 ints) are fetched three windows ahead into an LDS ring.
+//   * the window descriptors (24 ints) are fetched three windows ahead into an LDS ring;
+//   * while window i+1 is staged, thread = slot looks up each of its slots' degree and first neighbour entry once
+//     and leaves them in a table in LDS (WinSlots): the compute phase reads the table per 16-byte piece and does
+//     not search the degree blocks 16 to 32 times per atom.
 //
 // HBM traffic drops from E*(4F+4) + N*4F (every neighbour row fetched once per edge) to
 // N*4F + 2E + N*4F: each row is read ONCE; the (1+E/N)-fold re-reads are served by LDS.  The
@@ -24,7 +27,14 @@ namespace gcmi {
 constexpr int kND = GCMI_MAX_DEG + 1;
 constexpr int kLdsPerCU = 160 * 1024;
 constexpr int kRingBytes = 320;                 // 3 descriptors of GCMI_WIN_META_INTS ints, 16-byte padded
-constexpr int kHeadBytes = kRingBytes + 2048;   // + 512 floats of per-op constants
+constexpr int kHeadBytes = kRingBytes + 2048;   // + the per-op constants and the two slot tables
+// the 2 048 bytes behind the ring: [scale: 128 floats][shift: 128 floats][slot table of buffer 0][of buffer 1]
+// (no window kernel has rows above 128 columns: win_has_width, win_usable_h)
+constexpr int kShiftAt = 128;                   // floats
+constexpr int kTabSlots = 128;                  // slots of one table: ordinary windows above it search per piece
+constexpr int kTabAt = 2 * kShiftAt * 4;        // bytes
+static_assert(kTabAt + 2 * kTabSlots * 4 <= 2048, "the slot tables live inside the head");
+static_assert(kTabSlots * GCMI_MAX_DEG < (1 << 28), "a table entry is degree | first entry << 4");
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
@@ -98,8 +108,9 @@ __device__ __forceinline__ int row_of_slot(const WinMeta& m, int maxd, int slot)
 }
 
 // LDS image of one buffer: [tile: alloc*LPR float4][aux: alloc*LPR*4 bytes (optional)][edges]
+// tab: every window of this shape has at most kTabSlots slots (the compute phase reads a slot table: WinSlots)
 struct Layout {
-  int tile_bytes, aux_bytes, edge_bytes, maxd;
+  int tile_bytes, aux_bytes, edge_bytes, maxd, tab;
   __host__ __device__ int buf_bytes() const { return tile_bytes + aux_bytes + edge_bytes; }
 };
 
@@ -237,22 +248,65 @@ struct WinBuf {
   int n16;                      // pieces in the window
 };
 template <class P, int LPR>
-__device__ __forceinline__ WinBuf<P> open_buf(const char* buf, const Layout& L, const WinMeta& m) {
+__device__ __forceinline__ WinBuf<P> open_buf(const char* buf, const Layout& L, int n_slots) {
   return {reinterpret_cast<const typename P::Raw*>(buf), buf + L.tile_bytes,
-          reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes), m.sb[kND] * LPR};
+          reinterpret_cast<const uint16_t*>(buf + L.tile_bytes + L.aux_bytes), n_slots * LPR};
 }
+
+// What a compute phase knows about the slots of its window.
+//   TAB   the window's slot table in LDS: the degree of a slot is looked up ONCE per window, by thread = slot while
+//         the window is staged (fill_slot_table), not once per 16-byte piece of its row -- 16 to 32 times per atom;
+//   !TAB  the descriptor itself, searched per piece (locate): oversized windows, and ordinary windows of a batch whose
+//         largest one has more than kTabSlots atoms (Layout::tab, uniform over the grid).
+template <bool TAB>
+struct WinSlots;
+template <>
+struct WinSlots<true> {
+  const unsigned* tab;  // [slot] degree | first neighbour entry << 4
+  const int* rb;        // the window's descriptor in the ring: row of slot s (degree d) = rb[d] + s
+  int n;                // atoms in the window
+};
+template <>
+struct WinSlots<false> {
+  WinMeta m;
+  int maxd;
+  int n;
+};
+
+// thread = slot; the barrier that publishes the window's buffer publishes its table
+__device__ __forceinline__ void fill_slot_table(unsigned* tab, const WinMeta& m, int maxd) {
+  const int slot = threadIdx.x;
+  if (slot < m.sb[kND]) {
+    int d, row, eloc;
+    locate(m, maxd, slot, d, row, eloc);
+    tab[slot] = (unsigned)d | ((unsigned)eloc << 4);
+  }
+}
+
 struct PieceAt {
   int c;            // piece within the row
   int d;            // the atom's degree
   int row;          // its global row
   int eloc;         // first of its d neighbour entries
 };
+// the single place a compute phase gets (c, d, row, eloc) of piece e from
 template <int LPR>
-__device__ __forceinline__ PieceAt piece_at(const WinMeta& m, int maxd, int e) {
+__device__ __forceinline__ PieceAt piece_at(const WinSlots<true>& w, int e) {
+  const int slot = e / LPR;
+  const unsigned v = w.tab[slot];
+  PieceAt a;
+  a.c = e - slot * LPR;
+  a.d = (int)(v & 15u);
+  a.eloc = (int)(v >> 4);
+  a.row = w.rb[a.d] + slot;
+  return a;
+}
+template <int LPR>
+__device__ __forceinline__ PieceAt piece_at(const WinSlots<false>& w, int e) {
   const int slot = e / LPR;
   PieceAt a;
   a.c = e - slot * LPR;
-  locate(m, maxd, slot, a.d, a.row, a.eloc);
+  locate(w.m, w.maxd, slot, a.d, a.row, a.eloc);
   return a;
 }
 
@@ -284,7 +338,7 @@ __device__ __forceinline__ void add_piece(typename P::Vals& acc, const typename 
 }
 
 // GraphPool: the maximum over the atom's own piece e and its neighbours', BN: of y = x * scale + shift in fp32 (the
-// folded BatchNorm, [scale: 256][shift: 256] floats in LDS); the first maximum wins (self first, then neighbour order).
+// folded BatchNorm, [scale: 128][shift: 128] floats in LDS); the first maximum wins (self first, then neighbour order).
 // ba: 0 = self, j + 1 = neighbour j
 template <class P, int LPR, bool BN>
 __device__ __forceinline__ void pool_max(const typename P::Raw* tile, const uint16_t* nb, int d, int e, int c,
@@ -292,7 +346,7 @@ __device__ __forceinline__ void pool_max(const typename P::Raw* tile, const uint
   typename P::Vals sc, sh;
   if (BN) {
     P::load_vals(sh_lds + c * P::kEPP, sc);
-    P::load_vals(sh_lds + 256 + c * P::kEPP, sh);
+    P::load_vals(sh_lds + kShiftAt + c * P::kEPP, sh);
   }
   P::widen(tile[e], best);  // self first
 #pragma unroll
@@ -361,26 +415,25 @@ struct SumBody {
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
   __device__ __forceinline__ void init(float*, int) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*) const {
+  template <int WT, int LPR, class S>
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const S& sl, const float*) const {
     constexpr int kPre = Op::kPre;
-    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, sl.n);
     for (int e0 = threadIdx.x; e0 < w.n16; e0 += kPre * WT) {
       typename P::Raw old[kPre];
       if constexpr (ACC && kPre > 1) {
 #pragma unroll
         for (int k = 0; k < kPre; ++k) {
           const int e = e0 + k * WT < w.n16 ? e0 + k * WT : w.n16 - 1;
-          const int slot = e / LPR;
-          const int c = e - slot * LPR;
-          old[k] = load_piece(s + (int64_t)row_of_slot(m, L.maxd, slot) * lds + c * P::kEPP);
+          const PieceAt at = piece_at<LPR>(sl, e);
+          old[k] = load_piece(s + (int64_t)at.row * lds + at.c * P::kEPP);
         }
       }
 #pragma unroll
       for (int k = 0; k < kPre; ++k) {
         const int e = e0 + k * WT;
         if (e >= w.n16) break;
-        const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+        const PieceAt at = piece_at<LPR>(sl, e);
         T* dst = s + (int64_t)at.row * lds + at.c * P::kEPP;
         if constexpr (ACC && kPre == 1) old[0] = load_piece(dst);
         typename P::Vals acc;
@@ -424,11 +477,11 @@ struct SumOpFH {
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
   __device__ __forceinline__ void init(float*, int) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*) const {
-    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+  template <int WT, int LPR, class S>
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const S& sl, const float*) const {
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, sl.n);
     for (int e = threadIdx.x; e < w.n16; e += WT) {
-      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      const PieceAt at = piece_at<LPR>(sl, e);
       P::Vals acc;
       neigh_sum<P, LPR>(w.tile, w.ent + at.eloc, at.d, at.c, acc);
       const float4 own = w.tile[e];
@@ -465,14 +518,14 @@ struct MaxBody {
     if (BN)
       for (int i = threadIdx.x; i < n_feat; i += WT) {
         sh_lds[i] = scale[i];
-        sh_lds[256 + i] = shift[i];
+        sh_lds[kShiftAt + i] = shift[i];
       }
   }
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float* sh_lds) const {
-    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+  template <int WT, int LPR, class S>
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const S& sl, const float* sh_lds) const {
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, sl.n);
     for (int e = threadIdx.x; e < w.n16; e += WT) {
-      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      const PieceAt at = piece_at<LPR>(sl, e);
       typename P::Vals best;
       typename P::Bytes ba;
       pool_max<P, LPR, BN>(w.tile, w.ent + at.eloc, at.d, e, at.c, sh_lds, best, ba);
@@ -508,16 +561,16 @@ struct MaxBwdBody {
   }
   template <int WT>
   __device__ __forceinline__ void init(float*, int) const {}
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float*) const {
+  template <int WT, int LPR, class S>
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const S& sl, const float*) const {
     constexpr int kPre = Op::kPre;
-    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, sl.n);
     for (int e0 = threadIdx.x; e0 < w.n16; e0 += kPre * WT) {
 #pragma unroll
       for (int k = 0; k < kPre; ++k) {
         const int e = e0 + k * WT;
         if (e >= w.n16) break;
-        const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+        const PieceAt at = piece_at<LPR>(sl, e);
         typename P::Vals acc;
         pool_bwd<P, LPR>(w.tile, w.aux, w.ent + at.eloc, at.d, e, at.c, acc);
         store_piece(dx + (int64_t)at.row * lddx + at.c * P::kEPP, acc);
@@ -560,13 +613,13 @@ struct SumAccMaxBwdBody {
   template <int WT>
   __device__ __forceinline__ void init(float*, int) const {}
   // extra: the third tile of the window being computed, [slot][LPR] pieces, the dXs rows on entry
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, char* extra) const {
-    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+  template <int WT, int LPR, class S>
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const S& sl, char* extra) const {
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, sl.n);
     typename P::Raw* t2 = reinterpret_cast<typename P::Raw*>(extra);
     // ---- stage 1: dX of the window = gather(dS) + dXs, in place in the third tile
     for (int e = threadIdx.x; e < w.n16; e += WT) {
-      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      const PieceAt at = piece_at<LPR>(sl, e);
       typename P::Vals acc;
       neigh_sum<P, LPR>(w.tile, w.ent + at.eloc, at.d, at.c, acc);
       add_piece<P>(acc, t2[e]);
@@ -575,7 +628,7 @@ struct SumAccMaxBwdBody {
     __syncthreads();
     // ---- stage 2: the GraphPool backward over it
     for (int e = threadIdx.x; e < w.n16; e += WT) {
-      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      const PieceAt at = piece_at<LPR>(sl, e);
       typename P::Vals acc;
       pool_bwd<P, LPR>(t2, w.aux, w.ent + at.eloc, at.d, e, at.c, acc);
       store_piece(dy + (int64_t)at.row * lddy + at.c * P::kEPP, acc);
@@ -613,14 +666,14 @@ struct MaxSumBody {
   __device__ __forceinline__ bool skip(int) const { return false; }
   template <int WT>
   __device__ __forceinline__ void init(float* sh_lds, int n_feat) const { pool.template init<WT>(sh_lds, n_feat); }
-  template <int WT, int LPR>
-  __device__ __forceinline__ void run(const char* buf, const Layout& L, const WinMeta& m, const float* sh_lds,
+  template <int WT, int LPR, class S>
+  __device__ __forceinline__ void run(const char* buf, const Layout& L, const S& sl, const float* sh_lds,
                                       char* extra) const {
-    const WinBuf<P> w = open_buf<P, LPR>(buf, L, m);
+    const WinBuf<P> w = open_buf<P, LPR>(buf, L, sl.n);
     typename P::Raw* t2 = reinterpret_cast<typename P::Raw*>(extra);
     // ---- stage 1: the GraphPool of the window, to HBM and into the third tile
     for (int e = threadIdx.x; e < w.n16; e += WT) {
-      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      const PieceAt at = piece_at<LPR>(sl, e);
       typename P::Vals best;
       typename P::Bytes ba;
       pool_max<P, LPR, BN>(w.tile, w.ent + at.eloc, at.d, e, at.c, sh_lds, best, ba);
@@ -631,7 +684,7 @@ struct MaxSumBody {
     __syncthreads();
     // ---- stage 2: the neighbour sum over the pooled rows
     for (int e = threadIdx.x; e < w.n16; e += WT) {
-      const PieceAt at = piece_at<LPR>(m, L.maxd, e);
+      const PieceAt at = piece_at<LPR>(sl, e);
       typename P::Vals acc;
       neigh_sum<P, LPR>(t2, w.ent + at.eloc, at.d, at.c, acc);
       store_piece(s + (int64_t)at.row * lds + at.c * P::kEPP, acc);
@@ -657,7 +710,7 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
            int g_norm, Layout L, Layout Lbig, const char* __restrict__ x, int64_t ldx,
            const uint8_t* __restrict__ aux, Op op, int rev) {
   // ALL LDS is one array (a second __shared__ object beside an LDS-DMA target makes hipcc wait
-  // vmcnt(0) before every ds_read): [window descriptors: it, it+1, it+2][op constants][2 buffers][third tiles]
+  // vmcnt(0) before every ds_read): [window descriptors: it, it+1, it+2][op constants, 2 slot tables][2 buffers][third tiles]
   extern __shared__ __attribute__((aligned(16))) char smem_all[];
   int(*ring)[GCMI_WIN_META_INTS] = reinterpret_cast<int(*)[GCMI_WIN_META_INTS]>(smem_all);
   float* op_lds = reinterpret_cast<float*>(smem_all + kRingBytes);
@@ -668,10 +721,10 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
   if (op.skip(LPR * kEPP)) return;  // uniform over the grid
   op.template init<WT>(op_lds, LPR * kEPP);
   // the compute phase of one window: ops with a third tile get it, the others the op constants (scratch: both)
-  auto compute = [&](const char* buf, const Layout& l, const WinMeta& m, char* extra) {
-    if constexpr (kXT) op.template run<WT, LPR>(buf, l, m, extra);
-    else if constexpr (kScratch) op.template run<WT, LPR>(buf, l, m, op_lds, extra);
-    else op.template run<WT, LPR>(buf, l, m, op_lds);
+  auto compute = [&](const char* buf, const Layout& l, const auto& sl, char* extra) {
+    if constexpr (kXT) op.template run<WT, LPR>(buf, l, sl, extra);
+    else if constexpr (kScratch) op.template run<WT, LPR>(buf, l, sl, op_lds, extra);
+    else op.template run<WT, LPR>(buf, l, sl, op_lds);
   };
   const int t = threadIdx.x;
   if ((int)blockIdx.x >= g_norm) {  // oversized windows: stage, wait, compute
@@ -683,7 +736,8 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
       stage<WT, LPR, AUX, kEPP>(smem, Lbig, m, x, ldx, aux, edges);
       wait_dma();
       __syncthreads();
-      compute(smem, Lbig, m, smem + 2 * L.buf_bytes());  // (no launcher sends a two-stage op here)
+      // (no launcher sends a two-stage op here)
+      compute(smem, Lbig, WinSlots<false>{m, Lbig.maxd, m.sb[kND]}, smem + 2 * L.buf_bytes());
       __syncthreads();
     }
     return;
@@ -694,6 +748,14 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
   // rows the previous kernel wrote last are the ones still in the Infinity Cache
   auto widx = [&](int v) { return (size_t)(rev ? n_norm - 1 - v : v); };
   const int bb = L.buf_bytes();
+  unsigned* tabs = reinterpret_cast<unsigned*>(smem_all + kRingBytes + kTabAt);  // [buffer][kTabSlots]
+  // everything a window needs before its compute phase: the DMA of its rows and entries, and its slot table
+  auto prepare = [&](int slot3, int b) {
+    const WinMeta m = read_meta(ring[slot3]);
+    stage<WT, LPR, AUX, kEPP>(smem + b * bb, L, m, x, ldx, aux, edges);
+    if constexpr (kXT) stage_extra<WT, LPR>(smem + 2 * bb + b * L.tile_bytes, L, m, op.extra_src(), op.extra_ld_bytes());
+    if (L.tab) fill_slot_table(tabs + b * kTabSlots, m, L.maxd);
+  };
   int metareg = 0;
   if (t < GCMI_WIN_META_INTS) {
     ring[0][t] = meta[widx(w) * GCMI_WIN_META_INTS + t];
@@ -701,24 +763,23 @@ win_kernel(const int32_t* __restrict__ meta, const uint16_t* __restrict__ edges,
     if (w + 2 * G < n_norm) metareg = meta[widx(w + 2 * G) * GCMI_WIN_META_INTS + t];
   }
   __syncthreads();
-  stage<WT, LPR, AUX, kEPP>(smem, L, read_meta(ring[0]), x, ldx, aux, edges);
-  if constexpr (kXT) stage_extra<WT, LPR>(smem + 2 * bb, L, read_meta(ring[0]), op.extra_src(), op.extra_ld_bytes());
+  prepare(0, 0);
   int it = 0;
   for (;;) {
     wait_dma();
-    __syncthreads();  // buffer it&1 has landed, the other one is free
+    __syncthreads();  // buffer it&1 and its slot table have landed, the other pair is free
     const bool has_next = w + G < n_norm;
     if (t < GCMI_WIN_META_INTS) {
       ring[(it + 2) % 3][t] = metareg;  // read from the next round on
       if (w + 3 * G < n_norm) metareg = meta[widx(w + 3 * G) * GCMI_WIN_META_INTS + t];
     }
-    if (has_next) {
-      stage<WT, LPR, AUX, kEPP>(smem + ((it + 1) & 1) * bb, L, read_meta(ring[(it + 1) % 3]), x, ldx, aux, edges);
-      if constexpr (kXT)
-        stage_extra<WT, LPR>(smem + 2 * bb + ((it + 1) & 1) * L.tile_bytes, L, read_meta(ring[(it + 1) % 3]), op.extra_src(),
-                             op.extra_ld_bytes());
-    }
-    compute(smem + (it & 1) * bb, L, read_meta(ring[it % 3]), smem + 2 * bb + (kXT ? (it & 1) * L.tile_bytes : 0));
+    if (has_next) prepare((it + 1) % 3, (it + 1) & 1);
+    const int* desc = ring[it % 3];
+    char* extra = smem + 2 * bb + (kXT ? (it & 1) * L.tile_bytes : 0);
+    if (L.tab)  // the compute phase reads the atom count of the descriptor and nothing else of it
+      compute(smem + (it & 1) * bb, L, WinSlots<true>{tabs + (it & 1) * kTabSlots, desc, desc[2 * kND - 1]}, extra);
+    else
+      compute(smem + (it & 1) * bb, L, WinSlots<false>{read_meta(desc), L.maxd, desc[2 * kND - 1]}, extra);
     if (!has_next) break;
     w += G;
     ++it;
@@ -740,6 +801,7 @@ static Layout make_layout(int alloc, int ecap, int maxd, int n_feat, int aux) {
   L.aux_bytes = aux == 4 ? (alloc * n_feat + 15) / 16 * 16 : aux == 8 ? (alloc * (n_feat / 4) + 63) / 64 * 512 : 0;
   L.edge_bytes = (ecap > 8 ? ecap : 8) * 2;
   L.maxd = maxd;
+  L.tab = 0;
   return L;
 }
 
@@ -764,6 +826,7 @@ static WinPlan make_plan(const gcmi_graph* g, int n_feat, int aux) {
       p.L = make_layout(alloc, g->win_ecap, maxd, n_feat, aux);
     }
   }
+  p.L.tab = g->win_alloc <= kTabSlots ? 1 : 0;  // by the largest WINDOW: the buffers may have grown beyond it
   p.shmem = 2 * (size_t)p.L.buf_bytes() + kHeadBytes;
   p.ok = p.shmem <= (size_t)kLdsPerCU;
   return p;
