@@ -140,8 +140,16 @@ class GcmiSmallBatch(Structure):
     ]
 
 
+class GcmiGnGraph(Structure):
+    """struct gcmi_gn_graph (include/gcmi.h)."""
+    _fields_ = [(k, c_int32) for k in ("n_nodes", "n_edges", "n_graphs", "undirected", "n_inc")] + \
+        [(k, c_void_p) for k in ("src", "dst", "node_graph", "node_ptr", "edge_ptr", "inc_ptr", "inc_edge", "inc_other",
+                                 "out_ptr", "out_edge", "out_other")]
+
+
 _P = c_void_p
 _G = POINTER(GcmiGraph)
+_GN = POINTER(GcmiGnGraph)
 _MD = POINTER(GcmiModelDesc)
 _MIO = POINTER(GcmiModelIO)
 _I32P = POINTER(c_int32)
@@ -234,6 +242,13 @@ _SIGNATURES = {
     "gcmi_mat_attention_fwd": [_P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, c_int64, _P],
     "gcmi_mat_attention_bwd": [_P, _P, _P, c_int64, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, _P, c_int64,
                                _P, _P, _P, c_int64, c_int32, _P],
+    "gcmi_gn_graph_check": [_GN],
+    "gcmi_gn_edge_fwd": [_GN, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+    "gcmi_gn_node_fwd": [_GN, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P],
+    "gcmi_gn_edge_bwd": [_GN, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P],
+    "gcmi_gn_node_bwd": [_GN, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P],
+    "gcmi_gn_seg_reduce": [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P],
+    "gcmi_gn_seg_spread": [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P],
     "gcmi_dmpnn_message": [c_int32, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
     "gcmi_dmpnn_update_fwd": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int64,
                               _P, c_int64, _P],

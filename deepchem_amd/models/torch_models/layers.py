@@ -176,3 +176,4 @@ from deepchem_amd.models.torch_models.dtnn_layers import DTNNEmbedding, DTNNGath
 from deepchem_amd.models.torch_models.dmpnn_layers import DMPNNEncoderLayer, PositionwiseFeedForward  # noqa: E402,F401
 from deepchem_amd.models.torch_models.mat_layers import (MATEmbedding, MATEncoderLayer, MATGenerator,  # noqa: E402,F401
                                                          MultiHeadedMATAttention, SublayerConnection)
+from deepchem_amd.models.torch_models.megnet_layers import GraphNetwork, Set2Set  # noqa: E402,F401

@@ -1015,6 +1015,275 @@ class MatAttentionFn(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None
 
 
+# ------------------------------------------------------------------ graph-network block (MEGNet)
+GN_WIDTH, GN_ROWS_PER_WG = 32, 32
+
+
+class GnGraph:
+    """The graphs of one batch for csrc/megnet.hip: ``src``, ``dst``, ``node_graph``, ``node_ptr``, ``edge_ptr``, the
+    incidence list of every node (``inc_ptr``, ``inc_edge``, ``inc_other``: the edges ARRIVING there; undirected: every
+    edge at both its ends, in the order of the reference's doubled edge list) and, directed, the list of the edges
+    LEAVING every node.  Built on the host in numpy, validated there by ``gcmi_gn_graph_check``, uploaded in ONE
+    packed transfer together with ``floats`` (arrays that travel along, e.g. the features: ``self.floats``).
+
+    ``batch``: the graph of every node, non-decreasing; every graph of ``range(n_graphs)`` holds a node; the edges are
+    grouped by graph in the same order (what concatenating graphs gives).  Anything else: ``ValueError``."""
+
+    _INT_FIELDS = ("src", "dst", "node_graph", "node_ptr", "edge_ptr", "inc_ptr", "inc_edge", "inc_other", "out_ptr",
+                   "out_edge", "out_other")
+
+    def __init__(self, edge_index, batch, n_graphs: int, undirected: bool, device, floats=()):
+        ei = np.asarray(edge_index)
+        if ei.ndim != 2 or ei.shape[0] != 2:
+            raise ValueError("GnGraph: edge_index must be (2, n_edges), got %s" % (ei.shape,))
+        src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
+        batch = np.asarray(batch, np.int64).reshape(-1)
+        N, E, G = int(batch.size), int(src.size), int(n_graphs)
+        if N == 0 or G <= 0:
+            raise ValueError("GnGraph: at least one node and one graph")
+        if E and (min(src.min(), dst.min()) < 0 or max(src.max(), dst.max()) >= N):
+            raise ValueError("GnGraph: edge_index names a node outside [0, %d)" % N)
+        counts = np.bincount(batch, minlength=G) if batch.min() >= 0 else None
+        if counts is None or counts.size != G or counts.min() == 0 or np.any(np.diff(batch) < 0):
+            raise ValueError("GnGraph: batch must be non-decreasing and give every graph of range(%d) a node" % G)
+        eg = batch[src]
+        if np.any(batch[dst] != eg) or np.any(np.diff(eg) < 0):
+            raise ValueError("GnGraph: every edge inside one graph, the edges grouped by graph in the graphs' order")
+        if 2 * E >= 2**31 or N >= 2**31:
+            raise ValueError("GnGraph: too many edges for 32-bit lists")
+        self.n_nodes, self.n_edges, self.n_graphs, self.undirected = N, E, G, bool(undirected)
+        self.device = torch.device(device)
+
+        def csr(ids, n):
+            return np.concatenate([[0], np.cumsum(np.bincount(ids, minlength=n))])
+        h = {"src": src, "dst": dst, "node_graph": batch, "node_ptr": csr(batch, G), "edge_ptr": csr(eg, G)}
+        edges = np.arange(E)
+        if self.undirected:
+            owner, other, edge = np.concatenate([dst, src]), np.concatenate([src, dst]), np.concatenate([edges, edges])
+        else:
+            owner, other, edge = dst, src, edges
+        order = np.argsort(owner, kind="stable")
+        h.update(inc_ptr=csr(owner, N), inc_edge=edge[order], inc_other=other[order])
+        if not self.undirected:
+            order = np.argsort(src, kind="stable")
+            h.update(out_ptr=csr(src, N), out_edge=edges[order], out_other=dst[order])
+        self.n_inc = int(h["inc_edge"].size)
+        self.host = {k: np.ascontiguousarray(v, np.int32) for k, v in h.items()}
+        self._host_ref = self._desc({k: v.ctypes.data for k, v in self.host.items()})
+        _lib.call("gcmi_gn_graph_check", ctypes.byref(self._host_ref))
+        # one upload: the int32 lists as raw words, each block padded to 16 bytes, then the float arrays
+        blocks, where, at = [], {}, 0
+        for k, v in self.host.items():
+            where[k] = (at, v.size)
+            pad = -v.size % 4
+            blocks.append(np.concatenate([v, np.zeros(pad, np.int32)]).view(np.float32))
+            at += v.size + pad
+        fl = [np.ascontiguousarray(a, np.float32) for a in floats]
+        for a in fl:
+            pad = -a.size % 4
+            blocks.append(np.concatenate([a.reshape(-1), np.zeros(pad, np.float32)]))
+        packed = torch.as_tensor(np.concatenate(blocks), device=self.device)
+        words = packed[:at].view(torch.int32)
+        for k, (o, n) in where.items():
+            setattr(self, k, words[o:o + n])
+        self.floats = []
+        for a in fl:
+            self.floats.append(packed[at:at + a.size].view(a.shape))
+            at += a.size + (-a.size % 4)
+        self._packed = packed
+        self.ref = self._desc({k: getattr(self, k).data_ptr() for k in where}) if self.device.type == "cuda" else None
+        self._masks = None
+
+    def _desc(self, ptrs) -> "_lib.GcmiGnGraph":
+        d = _lib.GcmiGnGraph(n_nodes=self.n_nodes, n_edges=self.n_edges, n_graphs=self.n_graphs,
+                             undirected=1 if self.undirected else 0, n_inc=self.n_inc)
+        for k in self._INT_FIELDS:
+            setattr(d, k, ptrs.get(k) or None)
+        return d
+
+    @property
+    def masks(self):
+        """(nodes with an incident edge (N, 1), graphs with an edge (G, 1)) as 0 / 1 floats on the device."""
+        if self._masks is None:
+            self._masks = ((self.inc_ptr[1:] > self.inc_ptr[:-1]).to(torch.float32).unsqueeze(1),
+                           (self.edge_ptr[1:] > self.edge_ptr[:-1]).to(torch.float32).unsqueeze(1))
+        return self._masks
+
+
+def _gn_graph(g, what: str) -> GnGraph:
+    if not isinstance(g, GnGraph) or g.ref is None:
+        raise _lib.GcmiError("%s: the graph must be a GnGraph on the GPU" % what)
+    return g
+
+
+def _gn_rows(t, name: str, rows: int, ld: Optional[int] = None):
+    t = _mat(t, name, rows=rows, cols=GN_WIDTH)
+    if rows and (_ld(t) % 4 or t.data_ptr() % 16):
+        raise ValueError("%s: rows must be 16-byte aligned with a leading dimension of whole 16-byte pieces" % name)
+    if ld is not None and rows > 1 and _ld(t) != ld:
+        raise ValueError("%s: leading dimension %d, expected %d" % (name, _ld(t), ld))
+    return t
+
+
+def _gn_ld(t) -> int:
+    return max(_ld(t), GN_WIDTH)  # (an empty or one-row tensor reports its width)
+
+
+def _gn_inputs(g: GnGraph, ps, pd, q, r, what):
+    g = _gn_graph(g, what)
+    ps = _gn_rows(ps, "Ps", g.n_nodes)
+    pd = _gn_rows(pd, "Pd", g.n_nodes, _ld(ps))
+    q, r = _gn_rows(q, "Q", g.n_edges), _gn_rows(r, "R", g.n_graphs)
+    return (ctypes.byref(g.ref), _ptr(ps), _ptr(pd), _gn_ld(ps), _ptr(q) if g.n_edges else None, _gn_ld(q), _ptr(r), _gn_ld(r))
+
+
+def gn_edge_fwd(g: GnGraph, ps, pd, q, r) -> torch.Tensor:
+    """Hs (n_edges, 32): Q[e] + R[g] + Ps[s] + Pd[d], undirected the mean of both directions (csrc/megnet.hip)."""
+    args = _gn_inputs(g, ps, pd, q, r, "gn_edge_fwd")
+    hs = torch.empty((g.n_edges, GN_WIDTH), dtype=torch.float32, device=ps.device)
+    _lib.call("gcmi_gn_edge_fwd", *args, _ptr(hs) if g.n_edges else None, GN_WIDTH, _stream())
+    return hs
+
+
+def gn_node_fwd(g: GnGraph, ps, pd, q, r) -> torch.Tensor:
+    """Mh (n_nodes, 32): Pd[v] + R[g] + the mean over v's incidence list of Ps[other] + Q[edge]; 0 for an empty list."""
+    args = _gn_inputs(g, ps, pd, q, r, "gn_node_fwd")
+    mh = torch.empty((g.n_nodes, GN_WIDTH), dtype=torch.float32, device=ps.device)
+    _lib.call("gcmi_gn_node_fwd", *args, _ptr(mh), GN_WIDTH, _stream())
+    return mh
+
+
+def _gn_grad_buffers(g: GnGraph, dev):
+    dp = torch.empty((g.n_nodes, 2 * GN_WIDTH), dtype=torch.float32, device=dev)  # [dPs | dPd]
+    return dp, torch.empty((g.n_graphs, GN_WIDTH), dtype=torch.float32, device=dev)
+
+
+def gn_edge_bwd(g: GnGraph, dhs):
+    """(dP = [dPs | dPd] (n_nodes, 64), dR) of the edge pass; dQ is ``dhs`` itself."""
+    g = _gn_graph(g, "gn_edge_bwd")
+    dhs = _gn_rows(dhs, "dHs", g.n_edges)
+    dp, dr = _gn_grad_buffers(g, dhs.device)
+    _lib.call("gcmi_gn_edge_bwd", ctypes.byref(g.ref), _ptr(dhs) if g.n_edges else None, _gn_ld(dhs), _ptr(dp[:, :GN_WIDTH]),
+              _ptr(dp[:, GN_WIDTH:]), 2 * GN_WIDTH, _ptr(dr), GN_WIDTH, _stream())
+    return dp, dr
+
+
+def gn_node_bwd(g: GnGraph, dmh):
+    """(dP = [dPs | dPd], dQ, dR) of the node pass."""
+    g = _gn_graph(g, "gn_node_bwd")
+    dmh = _gn_rows(dmh, "dMh", g.n_nodes)
+    dp, dr = _gn_grad_buffers(g, dmh.device)
+    dq = torch.empty((g.n_edges, GN_WIDTH), dtype=torch.float32, device=dmh.device)
+    _lib.call("gcmi_gn_node_bwd", ctypes.byref(g.ref), _ptr(dmh), _gn_ld(dmh), _ptr(dq) if g.n_edges else None, GN_WIDTH,
+              _ptr(dp[:, :GN_WIDTH]), _ptr(dp[:, GN_WIDTH:]), 2 * GN_WIDTH, _ptr(dr), GN_WIDTH, _stream())
+    return dp, dq, dr
+
+
+def _gn_seg_args(ptr, x, n_rows, what):
+    ptr = _i32vec(ptr, "ptr")
+    if ptr.numel() < 2:
+        raise ValueError("%s: ptr needs at least one range" % what)
+    x = _mat(x, "rows", rows=n_rows)
+    if x.shape[1] == 0:
+        raise ValueError("%s: rows without columns" % what)
+    return ptr, x
+
+
+def gn_seg_reduce(x: torch.Tensor, ptr: torch.Tensor, mean: bool) -> torch.Tensor:
+    """out[s] = the sum (or mean) of rows [ptr[s], ptr[s + 1]) of x (any width); a zero row for an empty range."""
+    ptr, x = _gn_seg_args(ptr, x, None, "gn_seg_reduce")
+    out = torch.empty((ptr.numel() - 1, x.shape[1]), dtype=torch.float32, device=x.device)
+    _lib.call("gcmi_gn_seg_reduce", _ptr(ptr), ptr.numel() - 1, x.shape[0], x.shape[1], 1 if mean else 0,
+              _ptr(x) if x.shape[0] else _ptr(out), max(_ld(x), x.shape[1]), _ptr(out), x.shape[1], _stream())
+    return out
+
+
+def gn_seg_spread(x: torch.Tensor, ptr: torch.Tensor, n_rows: int, mean: bool) -> torch.Tensor:
+    """The transpose of ``gn_seg_reduce``: out[r] = x[s] (mean: / count(s)) for the rows of range s; ptr covers
+    [0, n_rows]."""
+    ptr, x = _gn_seg_args(ptr, x, ptr.numel() - 1, "gn_seg_spread")
+    out = torch.empty((n_rows, x.shape[1]), dtype=torch.float32, device=x.device)
+    if n_rows:
+        _lib.call("gcmi_gn_seg_spread", _ptr(ptr), ptr.numel() - 1, n_rows, x.shape[1], 1 if mean else 0, _ptr(x),
+                  max(_ld(x), x.shape[1]), _ptr(out), x.shape[1], _stream())
+    return out
+
+
+def _gn_halves(p: torch.Tensor):
+    if p.dim() != 2 or p.shape[1] != 2 * GN_WIDTH:
+        raise ValueError("the node projections must be one (n_nodes, %d) matrix [Ps | Pd]" % (2 * GN_WIDTH))
+    p = rowmajor(p)
+    if p.data_ptr() % 16 or _ld(p) % 4:
+        p = p.contiguous()
+    return p[:, :GN_WIDTH], p[:, GN_WIDTH:]
+
+
+def _gn_aligned(t: torch.Tensor) -> torch.Tensor:
+    t = rowmajor(t)
+    return t.contiguous() if t.numel() and (t.data_ptr() % 16 or _ld(t) % 4) else t
+
+
+class GnEdgeFn(torch.autograd.Function):
+    """(P = [Ps | Pd] (n_nodes, 64), Q, R, graph) -> Hs.  Nothing is saved: the pass is linear."""
+
+    @staticmethod
+    def forward(ctx, p, q, r, g: GnGraph):
+        ctx.g = g
+        ps, pd = _gn_halves(p)
+        return gn_edge_fwd(g, ps, pd, _gn_aligned(q), _gn_aligned(r))
+
+    @staticmethod
+    def backward(ctx, dhs):
+        dhs = _gn_aligned(dhs)
+        dp, dr = gn_edge_bwd(ctx.g, dhs)
+        return dp, dhs, dr, None
+
+
+class GnNodeFn(torch.autograd.Function):
+    """(P = [Ps | Pd], Q, R, graph) -> Mh."""
+
+    @staticmethod
+    def forward(ctx, p, q, r, g: GnGraph):
+        ctx.g = g
+        ps, pd = _gn_halves(p)
+        return gn_node_fwd(g, ps, pd, _gn_aligned(q), _gn_aligned(r))
+
+    @staticmethod
+    def backward(ctx, dmh):
+        dp, dq, dr = gn_node_bwd(ctx.g, _gn_aligned(dmh))
+        return dp, dq, dr, None
+
+
+class GnSegMeanFn(torch.autograd.Function):
+    """(rows, ptr) -> the mean of every contiguous range of rows."""
+
+    @staticmethod
+    def forward(ctx, x, ptr):
+        ctx.save_for_backward(ptr)
+        ctx.n_rows = x.shape[0]
+        return gn_seg_reduce(rowmajor(x), ptr, True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (ptr,) = ctx.saved_tensors
+        return gn_seg_spread(rowmajor(dout), ptr, ctx.n_rows, True), None
+
+
+class GnSegSpreadFn(torch.autograd.Function):
+    """(x (n_ranges, w), ptr, n_rows) -> x[s] in every row of range s: ``x[batch]`` for sorted ``batch``, with a
+    backward that sums each range in order (index_select's adds with atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, ptr, n_rows: int):
+        ctx.save_for_backward(ptr)
+        return gn_seg_spread(rowmajor(x), ptr, n_rows, False)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (ptr,) = ctx.saved_tensors
+        return gn_seg_reduce(rowmajor(dout), ptr, False), None, None
+
+
 # ------------------------------------------------------------------ message passing
 # ------------------------------------------------------------------ D-MPNN
 DMPNN_MAX_DEGREE = 32

@@ -999,6 +999,56 @@ int gcmi_mat_attention_bwd(const float* d_q, const float* d_k, const float* d_v,
                            float lambda_attention, const float* d_do, int64_t lddo, float* d_dq, float* d_dk, float* d_dv,
                            int64_t ldg, int32_t shared, void* stream);
 
+/* ---------------------------------------------------------------- graph-network block of MEGNet (megnet.hip)
+ * A batch of n_graphs graphs: their n_nodes nodes concatenated (node_ptr [n_graphs + 1], node_graph [n_nodes]), their
+ * n_edges edges src[e] -> dst[e] concatenated in the same graph order (edge_ptr [n_graphs + 1]; both ends of an edge in
+ * one graph), and per node the incidence list inc(v) = inc_edge / inc_other [inc_ptr[v], inc_ptr[v + 1]): (edge, other
+ * end) of every directed edge ARRIVING at v.  undirected = 1: every edge counts in both directions, so it stands in
+ * the lists of both its ends (a self-loop twice in one list) and n_inc = 2 n_edges; undirected = 0: in the list of its
+ * destination only, n_inc = n_edges, and out_ptr / out_edge / out_other list the edges LEAVING each node the same way
+ * (NULL when undirected).  All int32.  The kernel entries take a description whose arrays are on the DEVICE and check
+ * sizes and pointers only; the kernels compare every index they read with those sizes before using it.
+ * gcmi_gn_graph_check follows a description whose arrays are on the HOST and validates everything above: call it once
+ * per batch on the arrays that are uploaded.
+ * Rows (Ps, Pd: n_nodes; Q: n_edges; R: n_graphs; and what the entries write) are GCMI_GN_WIDTH = 32 floats with a
+ * leading dimension that is a multiple of 4, 16-byte aligned; Ps and Pd share ldp (two column blocks of one product).
+ *   gcmi_gn_edge_fwd   Hs[e] = Q[e] + R[g] + (Ps[s] + Pd[d])  (directed),
+ *                      Hs[e] = Q[e] + R[g] + ((Ps[s] + Pd[d]) + (Ps[d] + Pd[s])) / 2  (undirected)
+ *   gcmi_gn_node_fwd   Mh[v] = Pd[v] + R[g] + (sum over inc(v) of (Ps[other] + Q[edge])) / |inc(v)|, a zero row where
+ *                      inc(v) is empty
+ *   gcmi_gn_edge_bwd   from dHs: dPs, dPd (two distinct buffers, every row written) and dR; dQ is dHs itself
+ *   gcmi_gn_node_bwd   from dMh (rows of nodes with an empty list are ignored): dQ, dPs, dPd, dR, every row written
+ *   gcmi_gn_seg_reduce out[s] = the sum (mean = 0) or mean (mean = 1) of rows [ptr[s], ptr[s + 1]) of x, any width
+ *                      >= 1; a zero row for an empty range
+ *   gcmi_gn_seg_spread its transpose: out[r] = x[s] (mean = 1: / count) for the rows r of range s; ptr must cover
+ *                      [0, n_rows] for every row to be written
+ * No atomics: two calls agree bit for bit.  n_edges = 0 is allowed (edge rows and lists may then be NULL).        */
+#define GCMI_GN_WIDTH 32
+#define GCMI_GN_ROWS_PER_WG 32
+typedef struct gcmi_gn_graph {
+  int32_t n_nodes, n_edges, n_graphs, undirected, n_inc;
+  const int32_t *src, *dst;              /* [n_edges] */
+  const int32_t* node_graph;             /* [n_nodes] */
+  const int32_t *node_ptr, *edge_ptr;    /* [n_graphs + 1] */
+  const int32_t *inc_ptr;                /* [n_nodes + 1] */
+  const int32_t *inc_edge, *inc_other;   /* [n_inc] */
+  const int32_t *out_ptr;                /* [n_nodes + 1], directed only */
+  const int32_t *out_edge, *out_other;   /* [n_edges], directed only */
+} gcmi_gn_graph;
+int gcmi_gn_graph_check(const gcmi_gn_graph* host_graph);
+int gcmi_gn_edge_fwd(const gcmi_gn_graph* g, const float* d_ps, const float* d_pd, int64_t ldp, const float* d_q, int64_t ldq,
+                     const float* d_r, int64_t ldr, float* d_hs, int64_t ldh, void* stream);
+int gcmi_gn_node_fwd(const gcmi_gn_graph* g, const float* d_ps, const float* d_pd, int64_t ldp, const float* d_q, int64_t ldq,
+                     const float* d_r, int64_t ldr, float* d_mh, int64_t ldm, void* stream);
+int gcmi_gn_edge_bwd(const gcmi_gn_graph* g, const float* d_dhs, int64_t ldh, float* d_dps, float* d_dpd, int64_t ldp,
+                     float* d_dr, int64_t ldr, void* stream);
+int gcmi_gn_node_bwd(const gcmi_gn_graph* g, const float* d_dmh, int64_t ldm, float* d_dq, int64_t ldq, float* d_dps,
+                     float* d_dpd, int64_t ldp, float* d_dr, int64_t ldr, void* stream);
+int gcmi_gn_seg_reduce(const int32_t* d_ptr, int32_t n_seg, int32_t n_rows, int32_t width, int32_t mean, const float* d_x,
+                       int64_t ldx, float* d_out, int64_t ldo, void* stream);
+int gcmi_gn_seg_spread(const int32_t* d_ptr, int32_t n_seg, int32_t n_rows, int32_t width, int32_t mean, const float* d_x,
+                       int64_t ldx, float* d_out, int64_t ldo, void* stream);
+
 /* ---------------------------------------------------------------- D-MPNN (dmpnn.hip)
  * The message aggregation of the directed message-passing network (deepchem/models/torch_models/layers.py:1629,
  * `message[mapping].sum(1)`, and :1539, `h_message[atom_to_incoming_bonds].sum(1)`) over a batch whose directed bonds

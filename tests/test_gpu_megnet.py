@@ -1,0 +1,262 @@
+"""MEGNet on the GPU: the kernels of csrc/megnet.hip against the float64 restatement of tests/megnet_refs.py, the
+GraphNetwork layer against the reference's layer fixtures, and ``MEGNetModel`` against the reference's recorded first
+batch, gradients, fit trajectory and predictions (tests/golden/megnet_*.npz).
+
+Bar of the kernels (``bar`` of tests/test_gpu_mat.py): per output tensor, the largest error against float64 is at most
+4 times the largest error of the float32 restatement on the CPU for the same inputs, with a floor of one fp32 ulp of
+the tensor's largest entry.  The ratios are printed.  Bar of layers and models: 1e-4 of each tensor's largest entry;
+the fit trajectory: ``max(1e-4, 4 e_ref[k])`` per step.
+"""
+import numpy as np
+import pytest
+import torch
+
+import deepchem_amd as dc
+from deepchem_amd import ops
+from deepchem_amd.models import MEGNetModel
+from deepchem_amd.models.torch_models import MegnetBatch
+from deepchem_amd.models.torch_models.layers import GraphNetwork
+from tests import megnet_refs as R
+from tests.test_gpu_mat import bar
+from tests.test_megnet_host import (LAYERS, MODES, SIZES, TOL, check_first_batch, check_fit, close, fixture_dataset,
+                                    fixture_model, layer_case)
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+H = ops.GN_WIDTH
+ROWS = ops.GN_ROWS_PER_WG
+
+
+# ------------------------------------------------------------------------------------------------ kernels
+def batch_graphs(name):
+    rng = np.random.RandomState(17)
+    if name == "edge":
+        return R.edge_case_graphs(rng)
+    if name == "g1":
+        return [R.random_graph(rng, 10, 28)]
+    # node and edge counts one below / one above a multiple of the rows a workgroup takes
+    n, extra = {"below": (2 * ROWS - 1, ROWS), "above": (2 * ROWS + 1, ROWS)}[name]
+    g = R.random_graph(rng, n, extra, extras=False)
+    assert g.num_nodes % ROWS == n % ROWS and g.num_edges == 3 * ROWS + (n - 2 * ROWS)
+    return [g]
+
+
+_CASES = {}
+
+
+def kernel_case(name, undirected):
+    """Inputs and the float64 / float32 restatements (outputs and gradients) of both passes, computed once."""
+    key = (name, undirected)
+    if key in _CASES:
+        return _CASES[key]
+    _, ei, _, _, batch = R.pack(batch_graphs(name))
+    G, N, E = int(batch.max()) + 1, batch.size, ei.shape[1]
+    rng = np.random.RandomState(5)
+    c = {"ei": ei, "batch": batch, "G": G, "undirected": undirected}
+    for n, shape in (("P", (N, 2 * H)), ("Q", (E, H)), ("R", (G, H)), ("dHs", (E, H)), ("dMh", (N, H))):
+        c[n] = rng.normal(0, 1, shape).astype(np.float32)
+    L = R.tensor_lists(ei, batch, G, undirected)
+    tei, tb = torch.as_tensor(ei), torch.as_tensor(batch)
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        res = {}
+        for which, cot in (("edge", "dHs"), ("node", "dMh")):
+            P, Q, Rr = (torch.tensor(c[n], dtype=dtype, requires_grad=True) for n in ("P", "Q", "R"))
+            if which == "edge":
+                out = R.edge_pass(P[:, :H], P[:, H:], Q, Rr, tei, tb, undirected)
+            else:
+                out = R.node_pass(P[:, :H], P[:, H:], Q, Rr, L, tb)
+            (out * torch.tensor(c[cot], dtype=dtype)).sum().backward()
+            res.update({which + "_out": out.detach().numpy(), which + "_dP": P.grad.numpy(), which + "_dQ": Q.grad.numpy(),
+                        which + "_dR": Rr.grad.numpy()})
+        c[tag] = res
+    _CASES[key] = c
+    return c
+
+
+def run_native(c):
+    g = ops.GnGraph(c["ei"], c["batch"], c["G"], c["undirected"], DEV)
+    P, Q, Rr, dHs, dMh = (torch.tensor(c[n], device=DEV) for n in ("P", "Q", "R", "dHs", "dMh"))
+    res = {"edge_out": ops.gn_edge_fwd(g, P[:, :H], P[:, H:], Q, Rr), "node_out": ops.gn_node_fwd(g, P[:, :H], P[:, H:], Q, Rr)}
+    res["edge_dP"], res["edge_dR"] = ops.gn_edge_bwd(g, dHs)
+    res["edge_dQ"] = dHs
+    res["node_dP"], res["node_dQ"], res["node_dR"] = ops.gn_node_bwd(g, dMh)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in res.items()}, g
+
+
+@pytest.mark.parametrize("undirected", [True, False])
+@pytest.mark.parametrize("name", ["edge", "g1", "below", "above"])
+def test_edge_and_node_pass_kernels(name, undirected):
+    c = kernel_case(name, undirected)
+    got, g = run_native(c)
+    worst = max(bar(got[k], c["f64"][k], c["f32"][k], "%s %s %s" % (name, "undirected" if undirected else "directed", k))
+                for k in c["f64"])
+    print("worst ratio", worst)
+    if name == "edge":
+        # a node without an arriving edge: a ZERO row forward, and its dMh row reaches nothing
+        empty = np.flatnonzero(np.diff(g.host["inc_ptr"]) == 0)
+        assert empty.size >= 4 and not got["node_out"][empty].any() and not got["node_dP"][empty, H:].any()
+    again, _ = run_native(c)
+    assert all(np.array_equal(got[k], again[k]) for k in got)  # no atomics: bit for bit
+
+
+@pytest.mark.parametrize("width", [1, 5, 32, 33, 100])
+def test_segment_mean_and_spread_kernels(width):
+    _, ei, _, _, batch = R.pack(batch_graphs("edge"))
+    G = int(batch.max()) + 1
+    L = R.tensor_lists(ei, batch, G, True)
+    rng = np.random.RandomState(width)
+    for ptr_name, n_rows in (("node_ptr", batch.size), ("edge_ptr", ei.shape[1])):  # (edge_ptr: empty ranges at both ends)
+        x = rng.normal(0, 1, (n_rows, width)).astype(np.float32)
+        dout = rng.normal(0, 1, (G, width)).astype(np.float32)
+        ptr = L[ptr_name].to(torch.int32).to(DEV)
+        want = {}
+        for dtype in (torch.float64, torch.float32):
+            t = torch.tensor(x, dtype=dtype, requires_grad=True)
+            out = R.seg_mean(t, L[ptr_name])
+            (out * torch.tensor(dout, dtype=dtype)).sum().backward()
+            want[dtype] = (out.detach().numpy(), t.grad.numpy())
+        tx = torch.tensor(x, device=DEV, requires_grad=True)
+        out = ops.GnSegMeanFn.apply(tx, ptr)
+        (out * torch.tensor(dout, device=DEV)).sum().backward()
+        bar(out.detach().cpu().numpy(), want[torch.float64][0], want[torch.float32][0], "%s mean w%d" % (ptr_name, width))
+        bar(tx.grad.cpu().numpy(), want[torch.float64][1], want[torch.float32][1], "%s mean bwd w%d" % (ptr_name, width))
+        if ptr_name == "node_ptr":  # spread: x[batch] exactly, its backward the range sums
+            tu = torch.tensor(dout, device=DEV, requires_grad=True)
+            rows = ops.GnSegSpreadFn.apply(tu, ptr, n_rows)
+            assert np.array_equal(rows.detach().cpu().numpy(), dout[batch])
+            (rows * tx.detach()).sum().backward()
+            sums = [np.zeros((G, width), dt) for dt in (np.float64, np.float32)]
+            for dt, s in zip((np.float64, np.float32), sums):
+                np.add.at(s, batch, x.astype(dt))
+            bar(tu.grad.cpu().numpy(), sums[0], sums[1], "spread bwd w%d" % width)
+
+
+def test_kernel_wrappers_refuse_what_the_kernels_do_not_cover():
+    c = kernel_case("g1", True)
+    g = ops.GnGraph(c["ei"], c["batch"], c["G"], True, DEV)
+    P, Q, Rr = (torch.tensor(c[n], device=DEV) for n in ("P", "Q", "R"))
+    with pytest.raises(ValueError, match="columns"):
+        ops.gn_edge_fwd(g, P[:, :16], P[:, H:], Q, Rr)
+    with pytest.raises(ValueError, match="rows"):
+        ops.gn_node_fwd(g, P[:, :H], P[:, H:], Q[:-1], Rr)
+    with pytest.raises(ValueError, match="16-byte"):
+        ops.gn_edge_fwd(g, P[:, 1:H + 1], P[:, H:], Q, Rr)
+    with pytest.raises(Exception, match="GnGraph on the GPU"):
+        ops.gn_edge_fwd(ops.GnGraph(c["ei"], c["batch"], c["G"], True, "cpu"), P[:, :H], P[:, H:], Q, Rr)
+
+
+# ------------------------------------------------------------------------------------------------ the layer
+@pytest.mark.parametrize("k", range(int(LAYERS["n_cases"])))
+def test_graph_network_against_the_layer_fixtures(k):
+    c = layer_case(k)
+    gn = GraphNetwork(is_undirected=c["undirected"], residual_connection=c["residual"], **SIZES).to(DEV)
+    gn.load_state_dict({n: torch.as_tensor(v) for n, v in c["params"].items()})
+    x, e, u = (torch.tensor(c[n], dtype=torch.float32, device=DEV, requires_grad=True) for n in "xeu")
+    ei = torch.as_tensor(c["ei"], device=DEV)
+    out = gn(x, ei, e, u, torch.as_tensor(c["batch"], device=DEV) if c["with_batch"] else None)
+    assert gn.last_route == "native"
+    sum((t * torch.as_tensor(c["cot_" + n], device=DEV)).sum() for t, n in zip(out, "xeu")).backward()
+    for t, leaf, n in zip(out, (x, e, u), "xeu"):
+        close(t.detach().cpu().numpy(), c["out_" + n], "out_" + n)
+        close(leaf.grad.cpu().numpy(), c["grad_" + n], "grad_" + n)
+    for name, p in gn.named_parameters():
+        close(p.grad.cpu().numpy(), c["gradp"][name], name)
+    # a prebuilt graph gives the same bits; edges out of graph order take the torch route
+    g = ops.GnGraph(c["ei"], c["batch"], c["u"].shape[0], c["undirected"], DEV)
+    with torch.no_grad():
+        again = gn(x, None, e, u, graph=g)
+        assert all(torch.equal(a, b.detach()) for a, b in zip(again, out))
+        if c["with_batch"]:
+            perm = torch.arange(ei.shape[1] - 1, -1, -1, device=DEV)
+            shuffled = gn(x, ei[:, perm], e[perm], u, torch.as_tensor(c["batch"], device=DEV))
+            assert gn.last_route == "torch"
+            close(shuffled[0].cpu().numpy(), c["out_x"], "shuffled x")
+            close(shuffled[1].cpu().numpy(), c["out_e"][perm.cpu().numpy()], "shuffled e")
+
+
+# ------------------------------------------------------------------------------------------------ the models
+@pytest.mark.parametrize("mode", list(MODES))
+def test_model_first_batch_fit_and_predict(mode):
+    ds = fixture_dataset(MODES[mode][0])
+    model = fixture_model(mode, torch.device(DEV))  # (loads the reference-shaped state dict)
+    check_first_batch(model, mode, ds)
+    assert model.last_route == "native" and all(b.last_route == "native" for b in model.model.megnet_blocks)
+    check_fit(model, mode, ds)
+    assert model.last_route == "native"
+
+
+def test_model_save_restore_predicts_identically(tmp_path):
+    ds = fixture_dataset("cls_")
+    m = fixture_model("classification", torch.device(DEV), model_dir=str(tmp_path))
+    m.fit(ds, nb_epoch=1, deterministic=True, checkpoint_interval=0)
+    before = m.predict(ds)
+    m.save_checkpoint()
+    m2 = MEGNetModel(n_blocks=3, mode="classification", n_classes=5, batch_size=8, model_dir=str(tmp_path),
+                     device=torch.device(DEV), **SIZES)
+    m2.restore()
+    assert np.array_equal(m2.predict(ds), before)
+
+
+def test_evaluate_scores_on_the_device():
+    ds = fixture_dataset("")
+    model = fixture_model("regression", torch.device(DEV))
+    metric = dc.metrics.Metric(dc.metrics.mean_squared_error, np.mean)
+    before = model.device_metric_passes
+    got = model.evaluate(ds, [metric])
+    assert model.device_metric_passes == before + 1 and model.last_route == "native"
+    host = metric.compute_metric(ds.y, model.predict(ds), ds.w, n_tasks=2)
+    assert abs(list(got.values())[0] - host) <= TOL * abs(host)
+
+
+def mixed_batch():
+    rng = np.random.RandomState(23)
+    graphs = R.edge_case_graphs(rng)[:6] + R.fixture_graphs()[:3] + [R.make_graph(np.zeros((2, 0)), 1, rng)]
+    return graphs, rng.normal(0, 1, (len(graphs), 2)).astype(np.float32)
+
+
+@pytest.mark.parametrize("undirected", [True, False])
+def test_native_and_torch_routes_agree_on_a_mixed_batch(undirected):
+    graphs, y = mixed_batch()
+    res = {}
+    for route in ("auto", "torch"):
+        torch.manual_seed(4)
+        model = MEGNetModel(n_blocks=2, n_tasks=2, is_undirected=undirected, route=route, device=torch.device(DEV), **SIZES)
+        model.model.train()
+        out = model.model(MegnetBatch(graphs, undirected, DEV))
+        torch.square(out - torch.as_tensor(y, device=DEV)).mean().backward()
+        res[route] = (model.last_route, out.detach().cpu().numpy(),
+                      {k: p.grad.cpu().numpy() for k, p in model.model.named_parameters()})
+    assert res["auto"][0] == "native" and res["torch"][0] == "torch"
+    close(res["auto"][1], res["torch"][1], "outputs")
+    for k, gr in res["torch"][2].items():
+        close(res["auto"][2][k], gr, k)
+
+
+def test_batch_without_any_edge():
+    rng = np.random.RandomState(2)
+    graphs = [R.make_graph(np.zeros((2, 0)), n, rng) for n in (1, 3, 2)]
+    outs = {}
+    for route in ("auto", "torch"):
+        torch.manual_seed(4)
+        model = MEGNetModel(n_blocks=2, n_tasks=2, route=route, device=torch.device(DEV), **SIZES)
+        out = model.model(MegnetBatch(graphs, True, DEV))
+        out.sum().backward()
+        outs[route] = (model.last_route, out.detach().cpu().numpy(), model.model.out.weight.grad.cpu().numpy())
+    assert outs["auto"][0] == "native" and outs["torch"][0] == "torch"
+    close(outs["auto"][1], outs["torch"][1], "outputs")
+    close(outs["auto"][2], outs["torch"][2], "out.weight gradient")
+
+
+def test_two_runs_of_one_training_step_give_bitwise_equal_gradients():
+    graphs, y = mixed_batch()
+    grads = []
+    for _ in range(2):
+        torch.manual_seed(4)
+        model = MEGNetModel(n_blocks=3, n_tasks=2, device=torch.device(DEV), **SIZES)
+        model.model.train()
+        out = model.model(MegnetBatch(graphs, True, DEV))
+        torch.square(out - torch.as_tensor(y, device=DEV)).mean().backward()
+        assert model.last_route == "native"
+        grads.append({k: p.grad.cpu().numpy() for k, p in model.model.named_parameters()})
+    assert all(np.array_equal(grads[0][k], grads[1][k]) for k in grads[0])
