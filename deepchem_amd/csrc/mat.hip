@@ -22,6 +22,7 @@
 // start) for the column-owned half (dK = dS^T Q, dV = W^T dO), which walks T down its columns.  dP is recomputed
 // where it is needed a second time instead of being kept in a second n x n tile: 2 row tiles + T fit the 160 KiB of a
 // CU at 128 atoms and d_k = 64 (136 192 bytes), three would not.  No atomics: every output element has one owner.
+// Sums over atoms run in atom order; the two scalar ones per row (softmax denominator, delta) are compensated (comp_add).
 #include <math.h>
 
 #include "common.h"
@@ -122,6 +123,17 @@ __device__ __forceinline__ void store_row(float* row, const float4 (&x)[NV], int
   }
 }
 
+// sum += x with the rounding error of every addition carried along in comp (Kahan): the sum of n terms is good to an
+// ulp or two for any n.  For the two SCALAR row sums below only (softmax denominator, delta): on a row whose softmax
+// is close to one-hot, dS_ii = p_ii (dP_ii - delta_i) cancels, and what a plain running sum over 100 atoms loses in
+// l (so in p_ii) and in delta comes back multiplied by |dP_ii| in a whole row of dQ and dK.
+__device__ __forceinline__ void comp_add(float& sum, float& comp, float x) {
+  const float y = x - comp;
+  const float t = sum + y;
+  comp = (t - sum) - y;
+  sum = t;
+}
+
 // Row i of T: exp(s_ij - max_j s_ij) with s_ij = q_i . K_j / sqrt(d_k); returns the row sum
 template <int NV>
 __device__ __forceinline__ float softmax_row(const float4 (&q)[NV], const float* Kt, float* Trow, int n, float scale) {
@@ -132,11 +144,11 @@ __device__ __forceinline__ float softmax_row(const float4 (&q)[NV], const float*
     Trow[j] = s;
     m = fmaxf(m, s);
   }
-  float l = 0.f;
+  float l = 0.f, comp = 0.f;
   for (int j = 0; j < n; ++j) {
     const float e = expf(Trow[j] - m);
     Trow[j] = e;
-    l += e;
+    comp_add(l, comp, e);
   }
   return l;
 }
@@ -210,11 +222,11 @@ __global__ __launch_bounds__(kMatMaxAtoms) void mat_attn_bwd_kernel(const MatArg
       float* Trow = T + t * TP;
       const float l = softmax_row<NV>(r, Kt, Trow, b.n, a.inv_sqrt_dk);
       load_row<NV>(r, gO + t * a.lddo, b.nv);  // dO_i
-      float delta = 0.f;
+      float delta = 0.f, comp = 0.f;
       for (int j = 0; j < b.n; ++j) {
         const float p = Trow[j] / l;
         Trow[j] = p;
-        delta = fmaf(p, dot_row<NV>(r, Vt + j * RP), delta);
+        comp_add(delta, comp, p * dot_row<NV>(r, Vt + j * RP));
       }
       Dl[t] = delta;
 #pragma unroll

@@ -230,3 +230,149 @@ def fixture_dataset(dc, model_npz):
     X = np.empty(len(mols), dtype=object)
     X[:] = mols
     return dc.data.NumpyDataset(X, model_npz["y"], model_npz["w"])
+
+
+# ------------------------------------------------------------------------------------------------ edge cases of csrc/mat.hip
+# (shared by tests/test_mat_megnet_edge_cases_host.py and tests/test_gpu_mat_edges.py)
+MAT_CAP = 128
+MAT_NV = (1, 2, 4, 8, 16)  # float4 columns per head the attention kernels are instantiated for
+# the largest n_max whose dynamic LDS stays at or below 64 KiB / the one above it, per NV: (forward, backward)
+LDS_TABLE = {1: ((119, 120), (119, 120)), 2: ((116, 117), (115, 116)), 4: ((109, 110), (109, 110)),
+             8: ((96, 97), (96, 97)), 16: ((76, 77), (76, 77))}
+# n_max -> molecule sizes: at least 48 molecules where the molecules are tiny, else the largest plus a few small ones
+N_MAX_BATCHES = {1: [1] * 48, 2: [2, 2, 1] * 16, 3: [3, 2, 1, 3] * 12, 63: [2, 63, 1, 5], 64: [63, 1, 64], 65: [65, 2],
+                 127: [3, 127, 1]}
+BIAS_EDGE_SIZES = [1] * 5 + [63, 64, 65, 127, 1, 2] + [1] * 6
+
+
+def nv_of(d_k):
+    """The instantiation ``dispatch_mat`` picks for ``d_k``."""
+    return next(nv for nv in MAT_NV if d_k // 4 <= nv)
+
+
+def lds_bytes(nv, n_max, bwd):
+    """Dynamic LDS of one attention workgroup, from the layout at the top of csrc/mat.hip: two row tiles of
+    n_max x (4 NV + 4) floats, the n_max x (n_max | 1) tile and, backward, n_max row sums."""
+    return 4 * (2 * n_max * (4 * nv + 4) + n_max * (n_max | 1) + (n_max if bwd else 0))
+
+
+def lds_boundary(nv, bwd, limit=65536):
+    """(the largest n_max whose LDS is at most ``limit``, the one above it)."""
+    fits = [n for n in range(1, MAT_CAP + 1) if lds_bytes(nv, n, bwd) <= limit]
+    assert fits == list(range(1, fits[-1] + 1)) and fits[-1] < MAT_CAP
+    return fits[-1], fits[-1] + 1
+
+
+_EDGE_CASES = {}
+
+
+def attention_edge_case(n_list, h, d_k, shared=False, kv_same=False, lam=0.33):
+    """Inputs of one attention call on molecules of the sizes ``n_list`` and the float64 / float32 restatements of its
+    outputs and gradients, computed once per case.  ``shared``: q = k = v one leaf; ``kv_same``: k and v equal in value
+    (two leaves for autograd, so dK and dV stay apart)."""
+    key = (tuple(n_list), h, d_k, shared, kv_same, lam)
+    if key in _EDGE_CASES:
+        return _EDGE_CASES[key]
+    rng = np.random.RandomState(1000 * h + 10 * d_k + len(n_list))
+    n_list = [int(n) for n in n_list]
+    _, _, adj, dist = pack([synthetic_molecule(n - 1, rng) for n in n_list])
+    N, W = sum(n_list), h * d_k
+    c = {"n_list": n_list, "h": h, "d_k": d_k, "lam": lam, "shared": shared,
+         "bias": bias_blocks(adj, dist, n_list, "softmax", 0.33, 0.34, 1e-6, torch.float32).numpy(),
+         "q": rng.normal(0, 1, (N, W)).astype(np.float32), "dO": rng.normal(0, 1, (N, W)).astype(np.float32)}
+    c["k"] = c["q"] if shared else rng.normal(0, 1, (N, W)).astype(np.float32)
+    c["v"] = c["q"] if shared else c["k"] if kv_same else rng.normal(0, 1, (N, W)).astype(np.float32)
+    for dtype, name in ((torch.float64, "f64"), (torch.float32, "f32")):
+        q = torch.tensor(c["q"], dtype=dtype, requires_grad=True)
+        k, v = (q, q) if shared else (torch.tensor(c["k"], dtype=dtype, requires_grad=True),
+                                      torch.tensor(c["v"], dtype=dtype, requires_grad=True))
+        o = attention(q, k, v, torch.tensor(c["bias"], dtype=dtype), n_list, h, lam)
+        o.backward(torch.tensor(c["dO"], dtype=dtype))
+        c[name] = {"O": o.detach().numpy(), "dQ": q.grad.numpy()}
+        if not shared:
+            c[name].update({"dK": k.grad.numpy(), "dV": v.grad.numpy()})
+    _EDGE_CASES[key] = c
+    return c
+
+
+def reorder_case(c, order):
+    """The inputs of ``c`` with its molecules in ``order`` (no restatement: compared with ``c`` molecule by molecule)."""
+    aoff, poff = offsets(c["n_list"])
+    rows = np.concatenate([np.arange(aoff[m], aoff[m + 1]) for m in order])
+    pairs = np.concatenate([np.arange(poff[m], poff[m + 1]) for m in order])
+    out = {k: c[k] for k in ("h", "d_k", "lam", "shared")}
+    out["n_list"] = [c["n_list"][m] for m in order]
+    out["bias"] = c["bias"][pairs]
+    out["q"] = c["q"][rows]
+    out["k"], out["v"] = (out["q"], out["q"]) if c["shared"] else (c["k"][rows], c["v"][rows])
+    out["dO"] = c["dO"][rows]
+    return out, rows
+
+
+def _dot4(x, y):
+    """x (..., d) . y (..., d) as the kernels add it: four running sums over the float4 columns, then (a + b) + (c + d);
+    float32, products and sums rounded one by one (no fused multiply-add)."""
+    s = [np.zeros(np.broadcast(x[..., 0], y[..., 0]).shape, np.float32) for _ in range(4)]
+    for c in range(0, x.shape[-1], 4):
+        for i in range(4):
+            s[i] = s[i] + x[..., c + i] * y[..., c + i]
+    return (s[0] + s[1]) + (s[2] + s[3])
+
+
+def _comp_add(total, comp, x):
+    """``comp_add`` of csrc/mat.hip: total += x with the rounding error of the addition carried in ``comp``."""
+    y = x - comp
+    t = total + y
+    return t, (t - total) - y
+
+
+def attention_emulation(c, compensated=True):
+    """float32 numpy in the kernels' own order (the header comment of csrc/mat.hip): per query row the scores, their
+    maximum, the exponentials and their sum, ``lam * e / l + b``, and every sum over atoms accumulated in atom order;
+    the two scalar row sums (the softmax denominator and delta) are compensated as in the kernels, or with
+    ``compensated=False`` plain running sums.  What float32 gives for that order without fused multiply-add and with
+    numpy's ``exp``."""
+    f = np.float32
+    h, d_k, lam, shared = c["h"], c["d_k"], f(c["lam"]), c["shared"]
+    scale = f(1) / np.sqrt(f(d_k))
+    c_ds = lam * scale
+    aoff, poff = offsets(c["n_list"])
+    out = {name: np.zeros_like(c["q"]) for name in (("O", "dQ") if shared else ("O", "dQ", "dK", "dV"))}
+    for m, n in enumerate(c["n_list"]):
+        B = c["bias"][poff[m]:poff[m + 1]].reshape(n, n)
+        for head in range(h):
+            blk = (slice(int(aoff[m]), int(aoff[m + 1])), slice(head * d_k, (head + 1) * d_k))
+            Q, K, V, G = c["q"][blk], c["k"][blk], c["v"][blk], c["dO"][blk]
+            S = np.stack([_dot4(Q, K[j]) * scale for j in range(n)], 1)
+            E = np.exp(S - S.max(1, keepdims=True)).astype(f)
+            l, comp = np.zeros(n, f), np.zeros(n, f)
+            for j in range(n):
+                l, comp = _comp_add(l, comp, E[:, j]) if compensated else (l + E[:, j], comp)
+            o = np.zeros((n, d_k), f)
+            for j in range(n):
+                o = o + (lam * (E[:, j] / l) + B[:, j])[:, None] * V[j]
+            out["O"][blk] = o
+            P = E / l[:, None]
+            dP = np.stack([_dot4(G, V[j]) for j in range(n)], 1)
+            delta, comp = np.zeros(n, f), np.zeros(n, f)
+            for j in range(n):
+                delta, comp = _comp_add(delta, comp, P[:, j] * dP[:, j]) if compensated else (delta + P[:, j] * dP[:, j], comp)
+            dS = c_ds * P * (dP - delta[:, None])
+            dq, dk, dv = np.zeros((n, d_k), f), np.zeros((n, d_k), f), np.zeros((n, d_k), f)
+            for j in range(n):
+                dq = dq + dS[:, j][:, None] * K[j]
+            for i in range(n):
+                dk = dk + dS[i][:, None] * Q[i]
+                dv = dv + (lam * P[i] + B[i])[:, None] * G[i]
+            if shared:
+                out["dQ"][blk] = (dq + dk) + dv
+            else:
+                out["dQ"][blk], out["dK"][blk], out["dV"][blk] = dq, dk, dv
+    return out
+
+
+def bias_edge_case():
+    """(n_list, adjacency blocks, distance blocks) of the bias batch: 333 atoms, one past a multiple of the 4 rows a workgroup takes."""
+    rng = np.random.RandomState(11)
+    n_list, _, adj, dist = pack([synthetic_molecule(n - 1, rng) for n in BIAS_EDGE_SIZES])
+    return n_list, adj, dist

@@ -292,6 +292,49 @@ def edge_case_graphs(rng, Fn=5, Fe=3, Fg=4):
     return gs
 
 
+# ------------------------------------------------------------------------------------------------ grid-stride wrap cases
+# (shared by tests/test_mat_megnet_edge_cases_host.py and tests/test_gpu_megnet_edges.py)
+GN_MAX_BLOCKS = 8192  # the documented cap of a grid-stride launch (kMaxBlocks of csrc/common.h)
+GN_SEG_THREADS = 256  # threads per workgroup of the segment kernels: GN_MAX_BLOCKS x 256 (range, column) pairs per turn
+WRAP_RING_SIZES = [3, 131072, 1, 2, 131099]  # 8192 * 32 + 33 nodes and as many edges: 33 rows past one turn of the grid
+WRAP_SEG_RANGES, WRAP_SEG_WIDTH = 65537, 33
+
+
+def ring_batch(sizes):
+    """(edge_index (2, N), batch (N,)) of directed rings i -> i + 1 of the given sizes, one graph each: edge k leaves
+    node k.  A ring of one node is a self-loop, a ring of two a pair of opposite edges."""
+    sizes = np.asarray(sizes, np.int64)
+    base = np.repeat(np.concatenate([[0], np.cumsum(sizes)[:-1]]), sizes)
+    n = np.repeat(sizes, sizes)
+    node = np.arange(int(sizes.sum()))
+    return np.stack([node, base + (node - base + 1) % n]), np.repeat(np.arange(sizes.size), sizes)
+
+
+def ring_lists(sizes, undirected):
+    """``lists`` of ``ring_batch(sizes)`` in closed form: the edge arriving at node v is edge prev(v) from prev(v), and
+    undirected the doubled list adds (edge v, next(v)) after it; the edge leaving v is (edge v, next(v))."""
+    sizes = np.asarray(sizes, np.int64)
+    ei, batch = ring_batch(sizes)
+    node, nxt = ei[0], ei[1]
+    base = np.repeat(np.concatenate([[0], np.cumsum(sizes)[:-1]]), sizes)
+    prev = base + (node - base - 1) % np.repeat(sizes, sizes)
+    ptr = np.concatenate([[0], np.cumsum(sizes)])
+    out = {"node_ptr": ptr, "edge_ptr": ptr}
+    if undirected:
+        pair = lambda a, b: np.stack([a, b], 1).reshape(-1)  # noqa: E731
+        out.update(inc_ptr=2 * np.arange(node.size + 1), inc_edge=pair(prev, node), inc_other=pair(prev, nxt))
+    else:
+        out.update(inc_ptr=np.arange(node.size + 1), inc_edge=prev, inc_other=prev,
+                   out_ptr=np.arange(node.size + 1), out_edge=node, out_other=nxt)
+    return {k: np.asarray(v, np.int64) for k, v in out.items()}
+
+
+def wrap_segment_ptr():
+    """65 537 ranges of one or two rows: at width 33 more (range, column) pairs than one turn of the grid takes."""
+    counts = np.random.RandomState(7).randint(1, 3, WRAP_SEG_RANGES)
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
 def rel_err(a, b):
     a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
     return float(np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-300))
