@@ -35,6 +35,7 @@ from deepchem_amd.graph import BatchGraph, graph_for_layer_inputs
 from deepchem_amd.metrics import to_one_hot
 from deepchem_amd.models.losses import L2Loss, SoftmaxCrossEntropy, _make_pytorch_shapes_consistent
 from deepchem_amd.models.torch_models import layers as torch_layers
+from deepchem_amd.models.torch_models.functions import DenseFn, linear
 from deepchem_amd.models.torch_models.torch_model import TorchModel
 from deepchem_amd.utils.pytorch_utils import get_activation
 
@@ -220,7 +221,7 @@ class _GraphConvTorchModel(nn.Module):
         bn_t, has_bn, bn_train, eps, mom = self._bn_args(len(self.graph_convs))
         use_dropout = training and not isinstance(self.dropouts[-1], nn.Identity)
         mask_in_bn = has_bn and bn_train and not use_dropout
-        dense = ops.LinearFn.apply(x, self.dense.weight, self.dense.bias, True, mask_in_bn)
+        dense = DenseFn.apply(x, self.dense.weight, self.dense.bias, None, None, "out_in", True, mask_in_bn)
         batch_size = self.graph_gather.batch_size
         assert batch_size > 1, "graph_gather requires batches larger than 1"
         if use_dropout:
@@ -233,19 +234,16 @@ class _GraphConvTorchModel(nn.Module):
             neural_fingerprint = ops.ReadoutFn.apply(dense, *bn_t, graph, batch_size, has_bn, bn_train,
                                                      eps, mom, True, mask_in_bn)
         if self.mode == 'classification':
-            logits = ops.LinearFn.apply(neural_fingerprint, self.reshape_dense.weight,
-                                        self.reshape_dense.bias, False, False)
+            logits = linear(neural_fingerprint, self.reshape_dense)
             logits = torch.reshape(logits, (-1, self.n_tasks, self.n_classes))
             logits = self.trim([logits, n_samples])
             output = ops.SoftmaxFn.apply(logits)
             outputs = [output, logits, neural_fingerprint]
         else:
-            output = ops.LinearFn.apply(neural_fingerprint, self.regression_dense.weight,
-                                        self.regression_dense.bias, False, False)
+            output = linear(neural_fingerprint, self.regression_dense)
             output = self.trim([output, n_samples])
             if self.uncertainty:
-                log_var = ops.LinearFn.apply(neural_fingerprint, self.uncertainty_dense.weight,
-                                             self.uncertainty_dense.bias, False, False)
+                log_var = linear(neural_fingerprint, self.uncertainty_dense)
                 log_var = self.uncertainty_trim([log_var, n_samples])
                 var = torch.exp(log_var)
                 outputs = [output, var, output, log_var, neural_fingerprint]

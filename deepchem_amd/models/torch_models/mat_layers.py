@@ -24,8 +24,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from deepchem_amd import ops
-from deepchem_amd.models.torch_models.dmpnn_layers import PositionwiseFeedForward, linear
-from deepchem_amd.models.torch_models.dtnn_layers import MolSumFn
+from deepchem_amd.models.torch_models.dmpnn_layers import PositionwiseFeedForward
+from deepchem_amd.models.torch_models.functions import MolSumFn, linear
 
 
 class MATEmbedding(nn.Module):

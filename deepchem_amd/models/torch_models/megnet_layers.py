@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from deepchem_amd import ops
-from deepchem_amd.models.torch_models.mpnn import AttendFn, LstmCellFn
+from deepchem_amd.models.torch_models.functions import AttendFn, LstmCellFn
 
 HIDDEN = ops.GN_WIDTH
 

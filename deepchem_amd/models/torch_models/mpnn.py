@@ -26,156 +26,16 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from deepchem_amd import _lib, ops
+from deepchem_amd import ops
+from deepchem_amd._lib import GcmiError
 from deepchem_amd.metrics import to_one_hot
 from deepchem_amd.models.losses import L2Loss, SoftmaxCrossEntropy
+from deepchem_amd.models.torch_models.functions import AttendFn, DenseFn, GruGatesFn, GruOutFn, LstmCellFn, linear
 from deepchem_amd.models.torch_models.torch_model import TorchModel
 from deepchem_amd.models.torch_models.weave_layers import _csr_from_sorted
-from deepchem_amd.ops import _ld, _ptr, _stream
 
 
 # ---------------------------------------------------------------------------------------------- autograd pieces
-class MatmulFn(torch.autograd.Function):
-    """``x @ W (+ x2 @ W2) + b`` with (in, out) weight layout (the layout of the Keras kernels)."""
-
-    @staticmethod
-    def forward(ctx, x, W, b, x2, W2):
-        x, W = ops.rowmajor(x), W.contiguous()
-        n, k = x.shape
-        n_out = W.shape[1]
-        dual = x2 is not None
-        if dual:
-            x2, W2 = ops.rowmajor(x2), W2.contiguous()
-        out = ops.seg_gemm([0], [n], x, W.reshape(-1), [0], x2 if dual else None, W2.reshape(-1) if dual else None,
-                           [0] if dual else None, None if b is None else b.contiguous(), None if b is None else [0],
-                           n_out, False, False, n, k, x2.shape[1] if dual else 0)
-        ctx.dual, ctx.has_bias = dual, b is not None
-        ctx.params = (W, b, W2)
-        ctx.save_for_backward(x, W, x2 if dual else x, W2 if dual else W)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        x, W, x2, W2 = ctx.saved_tensors
-        g = ops.rowmajor(g)
-        n, n_out = g.shape
-        dev = g.device
-
-        def dgrad(Wm):  # g @ Wm^T: Wm (k, n_out) read as an nn.Linear matrix of a layer n_out -> k
-            return ops.seg_gemm([0], [n], g, Wm.reshape(-1), [0], None, None, None, None, None, Wm.shape[0], True, False,
-                                n, n_out, 0)
-
-        def wgrad(a, Wm, want_bias, pW, pb):
-            # (the kernels add into their outputs: with ops.direct_param_grads on, straight into p.grad)
-            tw, tb = ops.grad_target(pW), ops.grad_target(pb) if want_bias else None
-            dw = tw if tw is not None else torch.zeros_like(Wm)
-            db = None
-            if want_bias:
-                db = tb if tb is not None else torch.zeros(n_out, dtype=torch.float32, device=dev)
-            if n > 0:
-                ops.seg_gemm_wgrad([0], [n], a, g, dw, [0], db, [0] if want_bias else None, False)
-            return (None if tw is not None else dw), (None if tb is not None else db)
-
-        pW, pb, pW2 = ctx.params
-        dx = dgrad(W) if ctx.needs_input_grad[0] else None
-        dW = db = None
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            dW, db = wgrad(x, W, ctx.has_bias, pW, pb)
-        dx2 = dW2 = None
-        if ctx.dual:
-            dx2 = dgrad(W2) if ctx.needs_input_grad[3] else None
-            if ctx.needs_input_grad[4]:
-                dW2, _ = wgrad(x2, W2, False, pW2, None)
-        return dx, dW, db, dx2, dW2
-
-
-class GruGatesFn(torch.autograd.Function):
-    """(zp, rp, h) -> (z = sigmoid(zp), r = sigmoid(rp), hr = h r), in place on zp / rp."""
-
-    @staticmethod
-    def forward(ctx, zp, rp, h):
-        h = h.contiguous()
-        hr = ops.gru_gates_(zp, rp, h)
-        ctx.mark_dirty(zp, rp)
-        ctx.save_for_backward(zp, rp, h)
-        return zp, rp, hr
-
-    @staticmethod
-    def backward(ctx, dz, dr_unused, dhr):
-        z, r, h = ctx.saved_tensors
-        dz = torch.zeros_like(z) if dz is None else dz.contiguous()
-        dhr = torch.zeros_like(z) if dhr is None else dhr.contiguous()
-        dzp, drp, dh = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
-        _lib.call("gcmi_gru_gates_bwd", _ptr(z), _ptr(r), _ptr(h), _ptr(dz), _ptr(dhr), _ptr(dzp), _ptr(drp), _ptr(dh),
-                  z.numel(), _stream())
-        return dzp, drp, dh
-
-
-class GruOutFn(torch.autograd.Function):
-    """(z, hpre, x) -> (1 - z) tanh(hpre) + z x."""
-
-    @staticmethod
-    def forward(ctx, z, hpre, x):
-        z, hpre, x = z.contiguous(), hpre.contiguous(), x.contiguous()
-        ctx.save_for_backward(z, hpre, x)
-        return ops.gru_out(z, hpre, x)
-
-    @staticmethod
-    def backward(ctx, dout):
-        z, hpre, x = ctx.saved_tensors
-        dout = dout.contiguous()
-        dz, dhpre, dx = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
-        _lib.call("gcmi_gru_out_bwd", _ptr(z), _ptr(hpre), _ptr(x), _ptr(dout), _ptr(dz), _ptr(dhpre), _ptr(dx),
-                  z.numel(), _stream())
-        return dz, dhpre, dx
-
-
-class AttendFn(torch.autograd.Function):
-    """One set2set attention step: (x, h) -> q_star = [h | sum_a softmax(<x_a, h>) x_a] per molecule."""
-
-    @staticmethod
-    def forward(ctx, x, h, mol_ptr):
-        x, h = ops.rowmajor(x), ops.rowmajor(h)
-        ctx.save_for_backward(x, h, mol_ptr)
-        return ops.set2set_attend(x, mol_ptr, h)
-
-    @staticmethod
-    def backward(ctx, dq):
-        x, h, mol_ptr = ctx.saved_tensors
-        dq = ops.rowmajor(dq)
-        dx = torch.empty_like(x)
-        dh = torch.empty_like(h)
-        n_mols = mol_ptr.numel() - 1
-        # (ops._ld: the row stride of a one-row tensor means nothing, a (d, 1).t() view reports 1)
-        _lib.call("gcmi_set2set_attend_bwd", _ptr(x), _ld(x), x.shape[1], _ptr(mol_ptr), n_mols, _ptr(h), _ld(h),
-                  _ptr(dq), _ld(dq), _ptr(dx), _ld(dx), 0, _ptr(dh), _ld(dh), _stream())
-        return dx, dh, None
-
-
-class LstmCellFn(torch.autograd.Function):
-    """(z (B, 4H) gate pre-activations in order i, f, o, g; c) -> (h', c')."""
-
-    @staticmethod
-    def forward(ctx, z, c):
-        z = ops.rowmajor(z)
-        c_prev = c.contiguous()
-        c_new = c_prev.clone()
-        h_new = ops.lstm_cell_(z, c_new)
-        ctx.save_for_backward(z, c_prev)
-        return h_new, c_new
-
-    @staticmethod
-    def backward(ctx, dh, dc):
-        z, c_prev = ctx.saved_tensors
-        H = c_prev.shape[1]
-        dh = torch.zeros_like(c_prev) if dh is None else dh.contiguous()
-        dz = torch.empty_like(z)
-        dc_prev = torch.empty_like(c_prev)
-        _lib.call("gcmi_lstm_cell_bwd", _ptr(z), _ld(z), H, z.shape[0], _ptr(c_prev), _ptr(dh),
-                  _ptr(dc.contiguous()) if dc is not None else None, _ptr(dz), _ptr(dc_prev), _stream())
-        return dz, dc_prev
-
-
 class PairPlan:
     """The pair list of a batch on the device, in both directions: pairs sorted by their first atom (``dst``; the
     generator's order) with the second atoms ``src``, and the same pairs sorted by their second atom for the
@@ -248,10 +108,8 @@ class EdgeNetworkFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, M, plan: PairPlan, acc: EdgeAccum):
         h = ops.rowmajor(h)
-        d, K = acc.d, acc.K
         T = ops.edge_network_moments(h, plan.pf, plan.dst_ptr, plan.src, plan.mol_ptr, plan.max_mol_atoms)
-        n = T.shape[0]
-        m = ops.seg_gemm([0], [n], T, M.reshape(-1), [0], None, None, None, None, None, d, True, False, n, (K + 1) * d, 0)
+        m = ops.dense(T, M, layout="out_in")
         ctx.plan, ctx.acc = plan, acc
         acc.pending += 1
         ctx.save_for_backward(T, M)
@@ -263,22 +121,19 @@ class EdgeNetworkFn(torch.autograd.Function):
         plan, acc = ctx.plan, ctx.acc
         K, d = acc.K, acc.d
         dm = ops.rowmajor(dm)
-        n = dm.shape[0]
         dh = dM = None
         acc.pending -= 1
         if ctx.needs_input_grad[1]:
             if acc.dM is None:
                 acc.dM = torch.zeros((d, (K + 1) * d), dtype=torch.float32, device=dm.device)
-            if n > 0:  # dM[r, k d + c] += sum_i dm_ir T_i[k d + c]
-                ops.seg_gemm_wgrad([0], [n], T, dm, acc.dM, [0], None, None, True)
+            ops.dense_wgrad(T, dm, acc.dM, layout="out_in")  # dM[r, k d + c] += sum_i dm_ir T_i[k d + c]
             if acc.pending == 0:
                 dM, acc.dM = acc.dM, None
         if ctx.needs_input_grad[0]:
             if acc.M2 is None:
                 acc.M2 = M.reshape(d, K + 1, d).permute(2, 1, 0).reshape(d, (K + 1) * d).contiguous()
             Tt = ops.edge_network_moments(dm, plan.pf_t, plan.src_ptr, plan.dst_of_sorted, plan.mol_ptr, plan.max_mol_atoms)  # [sum_i pf_ijk dm_i | sum_i dm_i]
-            dh = ops.seg_gemm([0], [n], Tt, acc.M2.reshape(-1), [0], None, None, None, None, None, d, True, False, n,
-                              (K + 1) * d, 0)
+            dh = ops.dense(Tt, acc.M2, layout="out_in")
         return dh, dM, None, None
 
 
@@ -327,7 +182,7 @@ class _MPNNTorchModel(nn.Module):
         x = torch.as_tensor(atom_features, dtype=torch.float32, device=dev)
         pf = torch.as_tensor(pair_features, dtype=torch.float32, device=dev).contiguous()
         if not x.is_cuda:
-            raise _lib.GcmiError("MPNNModel: inputs must be on the GPU (no CPU path in deepchem_amd)")
+            raise GcmiError("MPNNModel: inputs must be on the GPU (no CPU path in deepchem_amd)")
         n, d = x.shape[0], self.n_hidden
         if x.shape[1] != self.n_atom_feat or pf.shape[1] != self.n_pair_feat:
             raise ValueError("MPNNModel: feature widths do not match the model")
@@ -341,32 +196,32 @@ class _MPNNTorchModel(nn.Module):
         edge_acc = EdgeAccum(edge_M, self.n_pair_feat, d)
         for _ in range(self.T):
             m = EdgeNetworkFn.apply(h, edge_M, plan, edge_acc)
-            zp = MatmulFn.apply(m, self.gru_Wz, self.gru_bz, h, self.gru_Uz)
-            rp = MatmulFn.apply(m, self.gru_Wr, self.gru_br, h, self.gru_Ur)
+            zp = DenseFn.apply(m, self.gru_Wz, self.gru_bz, h, self.gru_Uz, "in_out", False, False)
+            rp = DenseFn.apply(m, self.gru_Wr, self.gru_br, h, self.gru_Ur, "in_out", False, False)
             z, r, hr = GruGatesFn.apply(zp, rp, h)
-            hpre = MatmulFn.apply(m, self.gru_Wh, self.gru_bh, hr, self.gru_Uh)
+            hpre = DenseFn.apply(m, self.gru_Wh, self.gru_bh, hr, self.gru_Uh, "in_out", False, False)
             # Keras GatedRecurrentUnit.call (models/layers.py:3796-3799): inputs = [out, message] and the carry is
             # z * inputs[0] = z * h (the torch port of the layer, torch_models/layers.py:2912, carries z * message;
             # the stand-alone GatedRecurrentUnit of mpnn_layers.py keeps that, its reference asset pins it)
             h = GruOutFn.apply(z, hpre, h)
-        emb = ops.LinearFn.apply(h, self.atom_embed.weight, self.atom_embed.bias, False, False)
+        emb = linear(h, self.atom_embed)
         B = self.batch_size
         c = torch.zeros((B, d), dtype=torch.float32, device=dev)
         hs = torch.zeros((B, d), dtype=torch.float32, device=dev)
         q_star = None
         for _ in range(self.M):
             q_star = AttendFn.apply(emb, hs, mol_ptr)
-            z4 = MatmulFn.apply(q_star, self.set_U, self.set_b, None, None)
+            z4 = DenseFn.apply(q_star, self.set_U, self.set_b, None, None, "in_out", False, False)
             hs, c = LstmCellFn.apply(z4, c)
-        dense1 = ops.LinearFn.apply(q_star, self.dense1.weight, self.dense1.bias, True, False)
-        out = ops.LinearFn.apply(dense1, self.head.weight, self.head.bias, False, False)
+        dense1 = linear(q_star, self.dense1, relu=True)
+        out = linear(dense1, self.head)
         n_samples = int(n_samples)
         if self.mode == "classification":
             logits = out.reshape(-1, self.n_tasks, self.n_classes)[0:n_samples]
             return [ops.SoftmaxFn.apply(logits), logits]
         output = out[0:n_samples]
         if self.uncertainty:
-            log_var = ops.LinearFn.apply(dense1, self.log_var_head.weight, self.log_var_head.bias, False, False)[0:n_samples]
+            log_var = linear(dense1, self.log_var_head)[0:n_samples]
             return [output, torch.exp(log_var), output, log_var]
         return [output]
 

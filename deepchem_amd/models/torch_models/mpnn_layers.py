@@ -18,13 +18,6 @@ from deepchem_amd import ops
 from deepchem_amd.models.torch_models.weave_layers import _csr_from_sorted, _dev_f32, _host_i64
 
 
-def _linear(x, w, b, x2=None, w2=None):
-    n = x.shape[0]
-    return ops.seg_gemm([0], [n], x, w.reshape(-1), [0], x2, None if w2 is None else w2.reshape(-1),
-                        None if w2 is None else [0], b, None if b is None else [0], w.shape[1], False, False, n,
-                        x.shape[1], 0 if x2 is None else x2.shape[1])
-
-
 class EdgeNetwork(nn.Module):
     """Message function of MPNN: every pair's features select a d x d matrix that multiplies the hidden
     state of the pair's second atom; messages are summed per first atom."""
@@ -78,13 +71,11 @@ class EdgeNetwork(nn.Module):
             # product with M[r, k*d + c] = W_k[r, c] (k < K), M[r, K*d + c] = B[r, c]  (nn.Linear layout)
             T = ops.edge_network_moments(h, pf, dst_ptr, src)
             M = torch.cat([W.reshape(K, d, d), b.reshape(1, d, d)]).permute(1, 0, 2).reshape(d, (K + 1) * d).contiguous()
-            nd = T.shape[0]
-            return ops.seg_gemm([0], [nd], T, M.reshape(-1), [0], None, None, None, None, None, d, True, False, nd,
-                                (K + 1) * d, 0)
+            return ops.dense(T, M, layout="out_in")
         # G = h . [W_0^T | ... | W_{K-1}^T | B^T]: W (K, d*d) read in place as a (K*d, d) nn.Linear-layout matrix
         G = torch.empty((n, (K + 1) * d), dtype=torch.float32, device=self.device)
-        G[:, :K * d] = ops.seg_gemm([0], [n], h, W.reshape(-1), [0], None, None, None, None, None, K * d, True, False, n, d, 0)
-        G[:, K * d:] = ops.seg_gemm([0], [n], h, b, [0], None, None, None, None, None, d, True, False, n, d, 0)
+        G[:, :K * d] = ops.dense(h, W.reshape(K * d, d), layout="out_in")
+        G[:, K * d:] = ops.dense(h, b.reshape(d, d), layout="out_in")
         return ops.edge_network_sum(G, d, pf, dst_ptr, src)
 
 
@@ -110,10 +101,10 @@ class GatedRecurrentUnit(nn.Module):
         """inputs = [h_tm1, x] -> h."""
         h = _dev_f32(inputs[0], self.device).contiguous()
         x = _dev_f32(inputs[1], self.device).contiguous()
-        z = _linear(x, self._p("Wz"), self._p("bz"), h, self._p("Uz"))
-        r = _linear(x, self._p("Wr"), self._p("br"), h, self._p("Ur"))
+        z = ops.dense(x, self._p("Wz"), self._p("bz"), layout="in_out", x2=h, w2=self._p("Uz"))
+        r = ops.dense(x, self._p("Wr"), self._p("br"), layout="in_out", x2=h, w2=self._p("Ur"))
         hr = ops.gru_gates_(z, r, h)
-        hpre = _linear(x, self._p("Wh"), self._p("bh"), hr, self._p("Uh"))
+        hpre = ops.dense(x, self._p("Wh"), self._p("bh"), layout="in_out", x2=hr, w2=self._p("Uh"))
         return ops.gru_out(z, hpre, x)
 
 
@@ -150,6 +141,6 @@ class SetGather(nn.Module):
         q_star = None
         for _ in range(self.M):
             q_star = ops.set2set_attend(x, mol_ptr, h)
-            z = _linear(q_star, U, b)
+            z = ops.dense(q_star, U, b, layout="in_out")
             h = ops.lstm_cell_(z, c)
         return q_star

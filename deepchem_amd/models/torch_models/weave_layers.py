@@ -146,13 +146,6 @@ class WeaveLayer(nn.Module):
         scale, shift = ops.bn_fold_eval(bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps)
         return ops.fold_affine(w, b, scale, shift)
 
-    @staticmethod
-    def _linear(x, w, b, relu: bool, x2=None, w2=None):
-        n = x.shape[0]
-        return ops.seg_gemm([0], [n], x, w.reshape(-1), [0], x2, None if w2 is None else w2.reshape(-1),
-                            None if w2 is None else [0], b, None if b is None else [0], w.shape[1], False, relu, n,
-                            x.shape[1], 0 if x2 is None else x2.shape[1])
-
     def forward(self, inputs: List) -> List[torch.Tensor]:
         """inputs = [atom_features, pair_features, pair_split, atom_to_pair] -> [A, P]."""
         A = _dev_f32(inputs[0], self.device)
@@ -163,11 +156,12 @@ class WeaveLayer(nn.Module):
             raise ValueError("pair_split / atom_to_pair do not match the %d pairs" % n_pairs)
 
         w, b = self._folded(self.W_AA, self.b_AA, self.AA_bn)
-        AA = self._linear(A, w, b, True)
+        AA = ops.dense(A, w, b, layout="in_out", relu=True)
         w, b = self._folded(self.W_PA, self.b_PA, self.PA_bn)
         PA = ops.weave_pair_to_atom(Pf, plan.pair_src, n_atoms, w, b)
         w, b = self._folded(self.W_A, self.b_A, self.A_bn)
-        A_out = self._linear(AA, w[:self.n_hidden_AA].contiguous(), b, True, PA, w[self.n_hidden_AA:].contiguous())
+        A_out = ops.dense(AA, w[:self.n_hidden_AA].contiguous(), b, layout="in_out", x2=PA,
+                          w2=w[self.n_hidden_AA:].contiguous(), relu=True)
         if not self.update_pair:
             return [A_out, Pf]
         Fa = self.n_atom_input_feat
@@ -181,7 +175,7 @@ class WeaveLayer(nn.Module):
         w_uv = torch.zeros((Fa, 2 * Hp), dtype=torch.float32, device=self.device)
         w_uv[:, :H] = w[:Fa]
         w_uv[:, Hp:Hp + H] = w[Fa:]
-        UV = self._linear(A, w_uv, None, False)
+        UV = ops.dense(A, w_uv, layout="in_out")
         b_ap_p = torch.zeros(Hp, dtype=torch.float32, device=self.device)
         b_ap_p[:H] = b_ap
         Z = torch.empty((n_pairs, Hp + H2p), dtype=torch.float32, device=self.device)
@@ -191,8 +185,7 @@ class WeaveLayer(nn.Module):
         w_pp_p[:, :H2] = w_pp
         b_pp_p = torch.zeros(H2p, dtype=torch.float32, device=self.device)
         b_pp_p[:H2] = b_pp
-        ops.seg_gemm([0], [n_pairs], Pf, w_pp_p.reshape(-1), [0], None, None, None, b_pp_p, [0], H2p, False, True,
-                     n_pairs, Pf.shape[1], 0, out=Z[:, Hp:])
+        ops.dense(Pf, w_pp_p, b_pp_p, layout="in_out", relu=True, out=Z[:, Hp:])
         w, b = self._folded(self.W_P, self.b_P, self.P_bn)
         w_p = torch.zeros((Hp + H2p, w.shape[1]), dtype=torch.float32, device=self.device)
         w_p[:H] = w[:H]
@@ -206,7 +199,7 @@ class WeaveLayer(nn.Module):
         w_po[:, :Ho] = w_p
         b_po = torch.zeros(Hop, dtype=torch.float32, device=self.device)
         b_po[:Ho] = b
-        P_out = self._linear(Z, w_po, b_po, True)[:, :Ho]
+        P_out = ops.dense(Z, w_po, b_po, layout="in_out", relu=True)[:, :Ho]
         return [A_out, P_out]
 
 
@@ -252,8 +245,7 @@ class WeaveGather(nn.Module):
         if self.compress_post_gaussian_expansion:
             W = ops.rowmajor(self.W.detach().to(self.device, torch.float32))
             b = self.b.detach().to(self.device, torch.float32).contiguous()
-            out = ops.seg_gemm([0], [n_mols], out, W.reshape(-1), [0], None, None, None, b, [0], W.shape[1], False,
-                               False, n_mols, W.shape[0], 0)
+            out = ops.dense(out, W, b, layout="in_out")
             out = ops.tanh_(out)
         return out
 

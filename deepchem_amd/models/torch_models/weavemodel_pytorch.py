@@ -26,6 +26,7 @@ from deepchem_amd._lib import GcmiError
 from deepchem_amd.metrics import to_one_hot
 from deepchem_amd.models.losses import L2Loss, SoftmaxCrossEntropy
 from deepchem_amd.models.torch_models import weave_layers as torch_layers
+from deepchem_amd.models.torch_models.functions import linear
 from deepchem_amd.models.torch_models.torch_model import TorchModel
 
 
@@ -174,7 +175,7 @@ class Weave(nn.Module):
         # final convolution: the gather re-wraps its input in the reference, so nothing in front of
         # it trains -- plain kernels, no autograd bookkeeping
         with torch.no_grad():
-            dense1 = ops.LinearFn.apply(A, self.dense1.weight, self.dense1.bias, False)
+            dense1 = linear(A, self.dense1)
             if self.dense1_act == "tanh":
                 ops.tanh_(dense1)
             elif self.dense1_act == "relu":
@@ -192,16 +193,16 @@ class Weave(nn.Module):
                 if act not in ("relu", "linear"):
                     raise GcmiError("fully connected activation %r has no kernel" % act)
                 if self.batch_normalize:
-                    out = ops.LinearFn.apply(out, layer.weight, layer.bias, False)
+                    out = linear(out, layer)
                     bn = layer.layer_bn
                     out = EvalNormActFn.apply(out, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, relu)
                 else:
-                    out = ops.LinearFn.apply(out, layer.weight, layer.bias, relu)
+                    out = linear(out, layer, relu)
         if self.mode == 'classification':
-            logits = ops.LinearFn.apply(out, self.layer_2.weight, self.layer_2.bias, False)
+            logits = linear(out, self.layer_2)
             logits = torch.reshape(logits, (-1, self.n_tasks, self.n_classes))
             return [ops.SoftmaxFn.apply(logits), logits]
-        return [ops.LinearFn.apply(out, self.layer_2.weight, self.layer_2.bias, False)]
+        return [linear(out, self.layer_2)]
 
 
 class WeaveModel(TorchModel):

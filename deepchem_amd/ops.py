@@ -388,6 +388,32 @@ def seg_gemm(seg_begin, seg_end, a1, w1, w1_off, a2, w2, w2_off, bias, bias_off,
     return out
 
 
+def _trans_w(layout: str) -> bool:
+    if layout not in ("out_in", "in_out"):
+        raise ValueError("layout must be 'out_in' (nn.Linear) or 'in_out' (Keras), got %r" % (layout,))
+    return layout == "out_in"
+
+
+def dense(x, w, b=None, *, layout: str, x2=None, w2=None, relu: bool = False, out=None, accumulate: bool = False):
+    """act(x . W [+ x2 . W2] + b) over all rows: ``seg_gemm`` with the one segment [0, rows).  ``w`` / ``w2`` are
+    matrices, ``layout`` says which way round: "out_in" is nn.Linear's (n_out, k), "in_out" the Keras (k, n_out)."""
+    trans_w = _trans_w(layout)
+    n, k = x.shape
+    n_out = w.shape[0] if trans_w else w.shape[1]
+    k2 = 0 if x2 is None else x2.shape[1]
+    if (x2 is None) != (w2 is None):
+        raise ValueError("x2 and w2 go together")
+    for wm, kk, nm in ((w, k, "w"), (w2, k2, "w2")):
+        if wm is not None and wm.shape != ((n_out, kk) if trans_w else (kk, n_out)):
+            raise ValueError("%s %s is no %d -> %d matrix in the %s layout" % (nm, tuple(wm.shape), kk, n_out, layout))
+    if b is not None and b.numel() != n_out:
+        raise ValueError("bias has %d elements, expected %d" % (b.numel(), n_out))
+    if n == 0:  # (nothing to launch, and an empty tensor has no address to hand over)
+        return out if out is not None else torch.empty((0, n_out), dtype=torch.float32, device=x.device)
+    return seg_gemm([0], [n], x, w.reshape(-1), [0], x2, None if x2 is None else w2.reshape(-1),
+                    None if x2 is None else [0], b, [0], n_out, trans_w, relu, n, k, k2, out=out, accumulate=accumulate)
+
+
 def task_head_forward(fingerprint: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor],
                       scratch: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """logits = fingerprint . weight^T + bias with nn.Linear's (n_out, k) weight, as the whole-model path runs the task
@@ -615,10 +641,19 @@ def seg_gemm_wgrad(seg_begin, seg_end, a, g, dw, dw_off, dbias, dbias_off, trans
               _i64arr(dbias_off) if dbias is not None else None, 1 if trans_w else 0, _stream())
 
 
+def dense_wgrad(a, g, dw, db=None, *, layout: str):
+    """dw += a^T g (``layout`` "in_out") or g^T a ("out_in"), db += column sums of g, over all rows: ``seg_gemm_wgrad``
+    with the one segment [0, rows).  Nothing is launched for zero rows."""
+    trans_w = _trans_w(layout)
+    if a.shape[0] > 0:
+        seg_gemm_wgrad([0], [a.shape[0]], a, g, dw, [0], db, [0], trans_w)
+
+
 def relu_bwd_(g: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     _mat(g, "g")
     _mat(y, "y", rows=g.shape[0], cols=g.shape[1])
-    _lib.call("gcmi_relu_bwd", _ptr(g), _ld(g), _ptr(y), _ld(y), g.shape[0], g.shape[1], _stream())
+    if g.shape[0] > 0:
+        _lib.call("gcmi_relu_bwd", _ptr(g), _ld(g), _ptr(y), _ld(y), g.shape[0], g.shape[1], _stream())
     return g
 
 
@@ -1498,22 +1533,28 @@ def edge_network_moments(h: torch.Tensor, pair_feat: torch.Tensor, dst_ptr: torc
     return t
 
 
+def _gate_tensors(what: str, *named):
+    shape = named[0][0].shape
+    for t, nm in named:
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == shape):
+            raise ValueError("%s: %s must be a contiguous float32 CUDA tensor of the gate shape" % (what, nm))
+
+
 def gru_gates_(z: torch.Tensor, r: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
-    for t, nm in ((z, "z"), (r, "r"), (h, "h")):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == z.shape):
-            raise ValueError("%s must be a contiguous float32 CUDA tensor of the gate shape" % nm)
+    _gate_tensors("gru_gates_", (z, "z"), (r, "r"), (h, "h"))
     hr = torch.empty_like(h)
     _lib.call("gcmi_gru_gates", _ptr(z), _ptr(r), _ptr(h), _ptr(hr), z.numel(), _stream())
     return hr
 
 
 def gru_out(z: torch.Tensor, hpre: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    for t, nm in ((z, "z"), (hpre, "hpre"), (x, "x")):
-        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == z.shape):
-            raise ValueError("%s must be a contiguous float32 CUDA tensor of the gate shape" % nm)
+    _gate_tensors("gru_out", (z, "z"), (hpre, "hpre"), (x, "x"))
     out = torch.empty_like(x)
     _lib.call("gcmi_gru_out", _ptr(z), _ptr(hpre), _ptr(x), _ptr(out), z.numel(), _stream())
     return out
+
+
+SET2SET_MAX_FEATURES = 512  # (gcmi_set2set_attend and its backward refuse wider rows)
 
 
 def set2set_attend(x: torch.Tensor, mol_ptr: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
@@ -1533,6 +1574,60 @@ def lstm_cell_(z: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     h = torch.empty_like(c)
     _lib.call("gcmi_lstm_cell", _ptr(z), _ld(z), H, z.shape[0], _ptr(c), _ld(c), _ptr(h), _ld(h), _stream())
     return h
+
+
+def gru_gates_bwd(z: torch.Tensor, r: torch.Tensor, h: torch.Tensor, dz: torch.Tensor, dhr: torch.Tensor):
+    """Backward of ``gru_gates_`` from its outputs z, r and its input h: (dzp, drp, dh)."""
+    _gate_tensors("gru_gates_bwd", (z, "z"), (r, "r"), (h, "h"), (dz, "dz"), (dhr, "dhr"))
+    dzp, drp, dh = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
+    _lib.call("gcmi_gru_gates_bwd", _ptr(z), _ptr(r), _ptr(h), _ptr(dz), _ptr(dhr), _ptr(dzp), _ptr(drp), _ptr(dh),
+              z.numel(), _stream())
+    return dzp, drp, dh
+
+
+def gru_out_bwd(z: torch.Tensor, hpre: torch.Tensor, x: torch.Tensor, dout: torch.Tensor):
+    """Backward of ``gru_out``: (dz, dhpre, dx)."""
+    _gate_tensors("gru_out_bwd", (z, "z"), (hpre, "hpre"), (x, "x"), (dout, "dout"))
+    dz, dhpre, dx = torch.empty_like(z), torch.empty_like(z), torch.empty_like(z)
+    _lib.call("gcmi_gru_out_bwd", _ptr(z), _ptr(hpre), _ptr(x), _ptr(dout), _ptr(dz), _ptr(dhpre), _ptr(dx),
+              z.numel(), _stream())
+    return dz, dhpre, dx
+
+
+def set2set_attend_bwd(x: torch.Tensor, mol_ptr: torch.Tensor, h: torch.Tensor, dq: torch.Tensor, *,
+                       dx: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """Backward of ``set2set_attend`` (the softmax is recomputed): (dx, dh).  ``dx``: write into this matrix;
+    ``accumulate``: dx += instead of dx =, needs ``dx``."""
+    if accumulate and dx is None:
+        raise ValueError("accumulate needs the matrix to add to: pass dx")
+    x = _mat(x, "x")
+    n_feat = x.shape[1]
+    if not 0 < n_feat <= SET2SET_MAX_FEATURES:
+        raise _lib.GcmiError("set2set_attend_bwd: %d features, the kernel covers 1..%d" % (n_feat, SET2SET_MAX_FEATURES))
+    n_mols = mol_ptr.numel() - 1
+    h = _mat(h, "h", rows=n_mols, cols=n_feat)
+    dq = _mat(dq, "dq", rows=n_mols, cols=2 * n_feat)
+    dx = torch.empty_like(x) if dx is None else _mat(dx, "dx", rows=x.shape[0], cols=n_feat)
+    dh = torch.empty_like(h)
+    _lib.call("gcmi_set2set_attend_bwd", _ptr(x), _ld(x), n_feat, _ptr(_i32vec(mol_ptr, "mol_ptr")), n_mols, _ptr(h),
+              _ld(h), _ptr(dq), _ld(dq), _ptr(dx), _ld(dx), 1 if accumulate else 0, _ptr(dh), _ld(dh), _stream())
+    return dx, dh
+
+
+def lstm_cell_bwd(z: torch.Tensor, c_prev: torch.Tensor, dh: torch.Tensor, dc: Optional[torch.Tensor] = None):
+    """Backward of ``lstm_cell_`` from the gate pre-activations z and the cell state it started from: (dz, dc_prev).
+    ``dc``: the gradient of the new cell state, None for zero.  The C entry takes a leading dimension for z alone."""
+    z = _mat(z, "z")
+    H = z.shape[1] // 4
+    if H == 0 or z.shape[1] != 4 * H:
+        raise ValueError("z must hold four gates per hidden column, got %d columns" % z.shape[1])
+    _mat(c_prev, "c_prev", rows=z.shape[0], cols=H)
+    _gate_tensors("lstm_cell_bwd", (c_prev, "c_prev"), (dh, "dh"), *([] if dc is None else [(dc, "dc")]))
+    dz = torch.empty(z.shape, dtype=torch.float32, device=z.device)  # (contiguous whatever z's row stride)
+    dc_prev = torch.empty_like(c_prev)
+    _lib.call("gcmi_lstm_cell_bwd", _ptr(z), _ld(z), H, z.shape[0], _ptr(c_prev), _ptr(dh), _ptr(dc), _ptr(dz),
+              _ptr(dc_prev), _stream())
+    return dz, dc_prev
 
 
 def timing_enable(kernel_id: int, on: bool = True):
@@ -1722,49 +1817,14 @@ def grad_target(p):
     return g
 
 
-class LinearFn(torch.autograd.Function):
-    """act(x . W^T + b) with nn.Linear's (out, in) weight layout."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, relu: bool, grad_masked: bool = False):
-        x = rowmajor(x)
-        weight = weight.contiguous()
-        n_out, k = weight.shape
-        _mat(x, "x", cols=k)
-        n = x.shape[0]
-        out = seg_gemm([0], [n], x, weight, [0], None, None, None,
-                       None if bias is None else bias.contiguous(), [0], n_out, True, relu, n, k, 0)
-        ctx.relu = relu and not grad_masked
-        ctx.has_bias = bias is not None
-        ctx.params = (weight, bias)
-        ctx.save_for_backward(x, weight, out)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        x, weight, out = ctx.saved_tensors
-        n_out, k = weight.shape
-        n = x.shape[0]
-        g = rowmajor(dout)
-        if ctx.relu:
-            g = relu_bwd_(g.clone(), out)
-        dw = db = dx = None
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
-            tw, tb = grad_target(ctx.params[0]), grad_target(ctx.params[1])
-            dw = tw if tw is not None else torch.zeros_like(weight)
-            db = None
-            if ctx.has_bias:
-                db = tb if tb is not None else torch.zeros(n_out, dtype=torch.float32, device=g.device)
-            if n > 0:
-                seg_gemm_wgrad([0], [n], x, g, dw, [0], db, [0], True)
-            if tw is not None:
-                dw = None
-            if tb is not None:
-                db = None
-        if ctx.needs_input_grad[0]:
-            dx = seg_gemm([0], [n], g, weight, [0], None, None, None, None, None, k, False, False, n,
-                          n_out, 0)
-        return dx, dw, db, None, None
+def grad_buffer(p, like: torch.Tensor):
+    """Where a kernel that adds into its output accumulates the gradient of ``p``, and what the autograd Function
+    returns for it: ``(p.grad, None)`` if ``grad_target`` allows, else ``(zeros, those same zeros)`` shaped like ``like``."""
+    target = grad_target(p)
+    if target is not None:
+        return target, None
+    buf = torch.zeros_like(like)
+    return buf, buf
 
 
 class StandardLossFn(torch.autograd.Function):

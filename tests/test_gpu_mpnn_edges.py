@@ -34,6 +34,7 @@ The molecule-staged moments kernel is forced with GCMI_EDGE_MOMENTS_MOL=1, read 
 ONE child process, the automatic switch-over (n_dst = 98 304) in a second one with the variable unset.
 """
 import functools
+import itertools
 import os
 import subprocess
 import sys
@@ -321,7 +322,7 @@ class GruCase:
         return self._chain(gates, lambda z, hpre, x: (1 - z) * torch.tanh(hpre) + z * x, leaves, cots)
 
     def gpu(self):
-        from deepchem_amd.models.torch_models.mpnn import GruGatesFn, GruOutFn
+        from deepchem_amd.models.torch_models.functions import GruGatesFn, GruOutFn
         leaves = [_dev(a, grad=True) for a in self.a]
         cots = [_dev(c) for c in self.cots]
         # (the gates work in place on their pre-activations: hand them copies, as the model hands them GEMM outputs)
@@ -353,7 +354,7 @@ class LstmCase:
 
     def gpu(self):
         from deepchem_amd import _lib, ops
-        from deepchem_amd.models.torch_models.mpnn import LstmCellFn
+        from deepchem_amd.models.torch_models.functions import LstmCellFn
         H, rows = self.H, self.rows
         g0, g1 = (_dev(a) for a in self.cots)
         c = _dev(self.c, grad=True)
@@ -458,7 +459,7 @@ class AttendCase:
 
     def gpu(self):
         from deepchem_amd import _lib, ops
-        from deepchem_amd.models.torch_models.mpnn import AttendFn
+        from deepchem_amd.models.torch_models.functions import AttendFn
         F, mol_ptr = self.F, _dev(self.mol_ptr)
         n, B = self.x.shape[0], self.h.shape[0]
         if self.mode == "tview":
@@ -500,6 +501,35 @@ def test_set2set_attend_refuses_513_features():
     with pytest.raises(_lib.GcmiError):
         ops.set2set_attend(_dev(np.ones((2, 513), np.float32)), _dev(np.array([0, 2], np.int32)),
                            _dev(np.ones((1, 513), np.float32)))
+
+
+def test_backward_wrappers_refuse_before_any_launch(monkeypatch):
+    """gru_gates_bwd, gru_out_bwd, set2set_attend_bwd, lstm_cell_bwd: every float argument in turn as a CPU tensor, as
+    float64, with twice the columns and without unit stride (where the C entry takes a leading dimension: without unit
+    COLUMN stride) is refused on the host, and so are 513 attention features."""
+    from deepchem_amd import _lib, ops
+    ok = lambda *s: _dev(np.ones(s, np.float32))
+    good = {"gru_gates_bwd": lambda: [ok(3, 4) for _ in range(5)],
+            "gru_out_bwd": lambda: [ok(3, 4) for _ in range(4)],
+            "set2set_attend_bwd": lambda: [ok(5, 4), _dev(np.array([0, 2, 5], np.int32)), ok(2, 4), ok(2, 8)],
+            "lstm_cell_bwd": lambda: [ok(3, 8), ok(3, 2), ok(3, 2), ok(3, 2)]}
+    spoil = {"cpu": lambda t: t.cpu(), "float64": lambda t: t.double(), "columns": lambda t: torch.cat([t, t], 1),
+             "strided": lambda t: torch.cat([t, t], 1)[:, ::2]}
+    for name, make in good.items():
+        getattr(ops, name)(*make())  # (unspoiled, the arguments are accepted)
+    launched = []
+    monkeypatch.setattr(_lib, "call", lambda entry, *a: launched.append(entry))
+    cases = [("set2set_attend_bwd", "513 features", [ok(5, 513), _dev(np.array([0, 5], np.int32)), ok(1, 513), ok(1, 1026)])]
+    for name, make in good.items():
+        for pos, how in itertools.product(range(len(make())), spoil):
+            args = make()
+            if args[pos].dtype == torch.float32:  # (mol_ptr goes through _i32vec, as in the forward)
+                args[pos] = spoil[how](args[pos])
+                cases.append((name, "%s argument %d" % (how, pos), args))
+    for name, what, args in cases:
+        with pytest.raises((ValueError, TypeError, _lib.GcmiError)):
+            getattr(ops, name)(*args)
+        assert launched == [], (name, what)
 
 
 # ------------------------------------------------------------------------------------------------ EdgeNetworkFn
