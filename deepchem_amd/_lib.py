@@ -147,9 +147,17 @@ class GcmiGnGraph(Structure):
                                  "out_ptr", "out_edge", "out_other")]
 
 
+class GcmiGnSet(Structure):
+    """struct gcmi_gn_set (include/gcmi.h)."""
+    _fields_ = [("n_graphs", c_int64)] + [(k, c_int32) for k in ("undirected", "fn", "fe", "fg")] + \
+        [(k, c_void_p) for k in ("node_ptr", "edge_ptr", "node_features", "edge_features", "global_features", "src", "dst",
+                                 "inc_start", "inc_edge", "inc_other", "out_start", "out_edge", "out_other")]
+
+
 _P = c_void_p
 _G = POINTER(GcmiGraph)
 _GN = POINTER(GcmiGnGraph)
+_GNS = POINTER(GcmiGnSet)
 _MD = POINTER(GcmiModelDesc)
 _MIO = POINTER(GcmiModelIO)
 _I32P = POINTER(c_int32)
@@ -249,6 +257,8 @@ _SIGNATURES = {
     "gcmi_gn_node_bwd": [_GN, _P, c_int64, _P, c_int64, _P, _P, c_int64, _P, c_int64, _P],
     "gcmi_gn_seg_reduce": [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P],
     "gcmi_gn_seg_spread": [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P],
+    "gcmi_gn_collate": [_GNS, _P, c_int32, c_int32, c_int32, _P, c_int64, _P],
+    "gcmi_gn_collate_host": [_GNS, _P, c_int32, c_int32, c_int32, _P, c_int64],
     "gcmi_dmpnn_message": [c_int32, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
     "gcmi_dmpnn_update_fwd": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int64,
                               _P, c_int64, _P],
@@ -290,7 +300,7 @@ _SIGNATURES = {
 EXPORTS = ["gcmi_version", "gcmi_last_error", "gcmi_model_workspace_floats", "gcmi_small_workspace_floats",
            "gcmi_task_head_scratch_floats", "gcmi_fwd_fused_scratch_floats", "gcmi_lamb_scratch_floats", "gcmi_metrics_workspace_bytes",
            "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout",
-           "gcmi_dmpnn_collate_words"] + sorted(_SIGNATURES)
+           "gcmi_dmpnn_collate_words", "gcmi_gn_collate_words"] + sorted(_SIGNATURES)
 
 _lib = None
 
@@ -337,6 +347,7 @@ def load():
         "gcmi_lamb_scratch_floats": (c_int64, [c_int64, c_int64]),
         "gcmi_metrics_workspace_bytes": (c_int64, [c_int64, c_int32]),
         "gcmi_dmpnn_collate_words": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _I64P]),
+        "gcmi_gn_collate_words": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _I64P]),
     }
     for name, (restype, argtypes) in special.items():
         if host_only and not hasattr(lib, name):

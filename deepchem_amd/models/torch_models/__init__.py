@@ -6,4 +6,5 @@ from deepchem_amd.models.torch_models.mpnn import MPNNModel
 from deepchem_amd.models.torch_models.dtnn import DTNN, DTNNModel
 from deepchem_amd.models.torch_models.dmpnn import DMPNN, DMPNNModel
 from deepchem_amd.models.torch_models.mat import MAT, MATModel, MatBatch
-from deepchem_amd.models.torch_models.megnet import MEGNet, MEGNetModel, MegnetBatch
+from deepchem_amd.models.torch_models.megnet import (MEGNet, MEGNetModel, MegnetBatch, MegnetGraphSet,
+                                                      ResidentMegnetSet)

@@ -5,20 +5,55 @@ each with ``global_features`` of shape ``(1, Fg)``) and the reference's state-di
 ``set2set_nodes.lstm.*``, ``set2set_edges.lstm.*``, ``dense.0``, ``dense.1``, ``out``).
 
 ``_prepare_batch`` turns the graphs of a batch into a ``MegnetBatch``: nodes, edges and global rows concatenated, the
-index lists of ``ops.GnGraph`` built once on the host, everything uploaded in one packed transfer.  On the GPU the
+index lists of ``ops.GnGraph`` built once on the host, everything uploaded in one packed transfer.  ``fit`` / ``predict``
+/ ``evaluate`` on a ``NumpyDataset`` of ``GraphData`` keep the flat arrays of the whole dataset (``MegnetGraphSet``,
+built and validated once); a batch is then an index gather over them: in numpy (``MegnetGraphSet.batch``) or, from
+``MEGNET_DEVICE_COLLATE_MIN`` graphs per batch up, by ``gcmi_gn_collate`` over a ``ResidentMegnetSet`` in device memory
+-- the same bytes either way (``MEGNetModel(collate=...)``).  On the GPU the
 blocks run on ``csrc/megnet.hip`` and the two readouts on the set2set kernels (the NATIVE ROUTE); on the CPU, and for
 anything the native route declines, the same batch runs through torch ops in the reference's order (the TORCH ROUTE).
 ``model.last_route`` says which route the last batch took; ``MEGNetModel(..., route="torch")`` forces the second.
 """
+import os
+from typing import Optional
+
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from deepchem_amd import ops
+from deepchem_amd.data.datasets import NumpyDataset
 from deepchem_amd.models.losses import L2Loss, SparseSoftmaxCrossEntropy
+from deepchem_amd.models.torch_models.dmpnn import _ranges
 from deepchem_amd.models.torch_models.megnet_layers import GraphNetwork, Set2Set
 from deepchem_amd.models.torch_models.torch_model import TorchModel
+
+
+def _graph_arrays(graphs):
+    """``(xs, es, us, edge indices)`` of a list of ``GraphData``, float32 / int64 per graph, after the per-graph checks
+    of a MEGNet batch (``ValueError``)."""
+    xs, es, us, idx = [], [], [], []
+    for k, gr in enumerate(graphs):
+        if not all(hasattr(gr, a) for a in ("node_features", "edge_index", "edge_features")):
+            raise ValueError("MEGNetModel takes GraphData objects, got %r" % type(gr))
+        u = getattr(gr, "global_features", None)
+        if u is None:
+            raise ValueError("MEGNetModel: graph %d has no global_features (GraphData(..., global_features=array "
+                             "of shape (1, n_global_features)))" % k)
+        u = np.asarray(u, np.float32)
+        if u.ndim != 2 or u.shape[0] != 1:
+            raise ValueError("MEGNetModel: global_features of graph %d must have shape (1, n_global_features), got %s" %
+                             (k, u.shape))
+        if gr.edge_features is None:
+            raise ValueError("MEGNetModel: graph %d has no edge_features" % k)
+        x, e = np.asarray(gr.node_features, np.float32), np.asarray(gr.edge_features, np.float32)
+        xs.append(x), es.append(e), us.append(u)
+        idx.append(np.asarray(gr.edge_index, np.int64))
+    for name, rows in (("node_features", xs), ("edge_features", es), ("global_features", us)):
+        if any(r.ndim != 2 or r.shape[1] != rows[0].shape[1] for r in rows):
+            raise ValueError("MEGNetModel: the %s of a batch must be 2-D with one width" % name)
+    return xs, es, us, idx
 
 
 class MegnetBatch:
@@ -30,32 +65,24 @@ class MegnetBatch:
         graphs = list(graphs)
         if not graphs:
             raise ValueError("MegnetBatch: no graphs")
-        xs, es, us, idx, at = [], [], [], [], 0
-        for k, gr in enumerate(graphs):
-            if not all(hasattr(gr, a) for a in ("node_features", "edge_index", "edge_features")):
-                raise ValueError("MEGNetModel takes GraphData objects, got %r" % type(gr))
-            u = getattr(gr, "global_features", None)
-            if u is None:
-                raise ValueError("MEGNetModel: graph %d has no global_features (GraphData(..., global_features=array "
-                                 "of shape (1, n_global_features)))" % k)
-            u = np.asarray(u, np.float32)
-            if u.ndim != 2 or u.shape[0] != 1:
-                raise ValueError("MEGNetModel: global_features of graph %d must have shape (1, n_global_features), got %s" %
-                                 (k, u.shape))
-            if gr.edge_features is None:
-                raise ValueError("MEGNetModel: graph %d has no edge_features" % k)
-            x, e = np.asarray(gr.node_features, np.float32), np.asarray(gr.edge_features, np.float32)
-            xs.append(x), es.append(e), us.append(u)
-            idx.append(np.asarray(gr.edge_index, np.int64) + at)
-            at += x.shape[0]
-        for name, rows in (("node_features", xs), ("edge_features", es), ("global_features", us)):
-            if any(r.ndim != 2 or r.shape[1] != rows[0].shape[1] for r in rows):
-                raise ValueError("MEGNetModel: the %s of a batch must be 2-D with one width" % name)
-        batch = np.repeat(np.arange(len(graphs)), [x.shape[0] for x in xs])
-        self.graph = ops.GnGraph(np.concatenate(idx, axis=1), batch, len(graphs), is_undirected, device,
-                                 floats=(np.concatenate(xs), np.concatenate(es), np.concatenate(us)))
-        self.x, self.edge_attr, self.global_features = self.graph.floats
-        self.n_graphs = len(graphs)
+        xs, es, us, idx = _graph_arrays(graphs)
+        node_ptr = np.concatenate([[0], np.cumsum([x.shape[0] for x in xs])])
+        batch = np.repeat(np.arange(len(graphs)), np.diff(node_ptr))
+        self._wrap(ops.GnGraph(np.concatenate([ei + at for ei, at in zip(idx, node_ptr)], axis=1), batch, len(graphs),
+                               is_undirected, device, floats=(np.concatenate(xs), np.concatenate(es), np.concatenate(us))))
+
+    def _wrap(self, graph: "ops.GnGraph"):
+        self.graph = graph
+        self.x, self.edge_attr, self.global_features = graph.floats
+        self.n_graphs = graph.n_graphs
+        return self
+
+    @classmethod
+    def from_device(cls, words: torch.Tensor, n_graphs: int, n_nodes: int, n_edges: int, is_undirected: bool,
+                    widths) -> "MegnetBatch":
+        """Around a packed buffer in the layout of ``ops.gn_batch_layout`` (``gcmi_gn_collate`` wrote it from a
+        ``ResidentMegnetSet``): ``ops.GnGraph.from_device`` and the three feature views.  Not validated per batch."""
+        return cls.__new__(cls)._wrap(ops.GnGraph.from_device(words, n_graphs, n_nodes, n_edges, is_undirected, widths))
 
     def __getitem__(self, key):
         if key == "edge_index":
@@ -65,6 +92,185 @@ class MegnetBatch:
         if key in ("x", "edge_attr", "global_features"):
             return getattr(self, key)
         raise KeyError(key)
+
+
+class MegnetGraphSet(object):
+    """The flat arrays of an array of ``GraphData`` for one mode (undirected or not), built once: nodes, edges and
+    global rows concatenated with per-graph offsets (``node_ptr``, ``edge_ptr``, int64), ``src`` / ``dst`` LOCAL to the
+    graph, and the lists of ``ops.GnGraph`` per graph: ``inc_start`` (per node, the exclusive prefix of the incidence
+    counts inside the graph), ``inc_edge`` / ``inc_other`` (local; ``2E`` entries undirected, ``E`` directed) and,
+    directed, ``out_start`` / ``out_edge`` / ``out_other``.  The per-graph ``ValueError`` s are ``MegnetBatch``'s.
+
+    Every list ``ops.GnGraph`` builds decomposes per graph: its batch-level stable sort of ``concat([dst, src])``
+    (directed: ``dst``, and ``src`` for the out-lists) puts into a node's list only edges of the node's own graph, in
+    ascending edge order.  So the lists of a batch are the local lists of its graphs laid end to end with the graph's
+    offsets added: ``inc_ptr[node_off[m] + i] = k edge_off[m] + inc_start[i]`` (k = 2 undirected, 1 directed),
+    ``out_ptr[node_off[m] + i] = edge_off[m] + out_start[i]``; no scan or sort per batch.
+
+    Validated ONCE, which is why ``batch`` and ``ResidentMegnetSet.batch`` skip the per-batch check: the whole set in
+    dataset order is itself a batch, built here by ``ops.GnGraph`` -- every graph holds a node, every edge stays inside
+    its graph, ``N`` and ``2E`` are below 2^31 - 1 -- and ``gcmi_gn_graph_check`` follows its host lists.  A selection
+    (repeats included) gives each chosen graph a block of its own, ``[node_off[m], node_off[m + 1])`` and ``[edge_off[m],
+    edge_off[m + 1])``, disjoint from every other, and adds the block's offsets to local indices that the check found
+    inside the graph.  Everything the check asserts -- offsets that rise from 0 to the totals, every index inside its
+    graph's block, an entry of a node's list naming an edge with that node at the matching end -- is a statement about
+    one graph's block at a time, so it holds for every selection."""
+
+    def __init__(self, graphs, is_undirected: bool):
+        graphs = list(graphs)
+        if not graphs:
+            raise ValueError("MegnetBatch: no graphs")
+        self.undirected = bool(is_undirected)
+        xs, es, us, idx = _graph_arrays(graphs)
+        M, k = len(graphs), 2 if self.undirected else 1
+        self.n_graphs = M
+        self.n_nodes_of = np.array([x.shape[0] for x in xs], np.int64)
+        for ei in idx:
+            if ei.ndim != 2 or ei.shape[0] != 2:
+                raise ValueError("GnGraph: edge_index must be (2, n_edges), got %s" % (ei.shape,))
+        self.n_edges_of = np.array([ei.shape[1] for ei in idx], np.int64)
+        self.node_ptr = np.concatenate([[0], np.cumsum(self.n_nodes_of)]).astype(np.int64)
+        self.edge_ptr = np.concatenate([[0], np.cumsum(self.n_edges_of)]).astype(np.int64)
+        self.node_features, self.edge_features = np.concatenate(xs), np.concatenate(es)
+        self.global_features = np.concatenate(us)
+        if self.edge_features.shape[0] != self.edge_ptr[-1]:
+            raise ValueError("MEGNetModel: edge_features needs one row per edge of edge_index")
+        local = np.concatenate(idx, axis=1)
+        graph_of_node = np.repeat(np.arange(M), self.n_nodes_of)
+        graph_of_edge = np.repeat(np.arange(M), self.n_edges_of)
+        if local.size and (local.min() < 0 or np.any(local >= self.n_nodes_of[graph_of_edge])):
+            raise ValueError("GnGraph: every edge inside one graph, the edges grouped by graph in the graphs' order")
+        # the whole set as ONE batch: ops.GnGraph makes its checks, builds the global lists and has them followed by
+        # gcmi_gn_graph_check; what is kept are those lists with the graph's offsets taken off
+        whole = ops.GnGraph(local + self.node_ptr[graph_of_edge], graph_of_node, M, self.undirected, "cpu").host
+        graph_of_entry = np.repeat(np.arange(M), k * self.n_edges_of)
+        c = np.ascontiguousarray
+        self.src, self.dst = c(local[0], np.int32), c(local[1], np.int32)
+        self.inc_start = c(whole["inc_ptr"][:-1] - k * self.edge_ptr[graph_of_node], np.int32)
+        self.inc_edge = c(whole["inc_edge"] - self.edge_ptr[graph_of_entry], np.int32)
+        self.inc_other = c(whole["inc_other"] - self.node_ptr[graph_of_entry], np.int32)
+        if not self.undirected:
+            self.out_start = c(whole["out_ptr"][:-1] - self.edge_ptr[graph_of_node], np.int32)
+            self.out_edge = c(whole["out_edge"] - self.edge_ptr[graph_of_edge], np.int32)
+            self.out_other = c(whole["out_other"] - self.node_ptr[graph_of_edge], np.int32)
+
+    @property
+    def widths(self):
+        return (self.node_features.shape[1], self.edge_features.shape[1], self.global_features.shape[1])
+
+    def _select(self, idx) -> np.ndarray:
+        sel = np.asarray(idx, np.int64).reshape(-1)
+        if sel.size == 0:
+            raise ValueError("MegnetBatch: no graphs")
+        if sel.min() < 0 or sel.max() >= self.n_graphs:
+            raise ValueError("MegnetBatch: graph index outside the graph set")
+        return sel
+
+    def batch(self, idx, device="cpu") -> MegnetBatch:
+        """The batch of the graphs ``idx`` (in order, repeats allowed) gathered by numpy over the flat arrays and
+        uploaded in one copy: the bytes of ``MegnetBatch([X[i] for i in idx], is_undirected, device)``."""
+        sel = self._select(idx)
+        n, k = sel.size, 2 if self.undirected else 1
+        nv, ne = self.n_nodes_of[sel], self.n_edges_of[sel]
+        node_off, edge_off = np.concatenate([[0], np.cumsum(nv)]), np.concatenate([[0], np.cumsum(ne)])
+        N, E = int(node_off[-1]), int(edge_off[-1])
+        if max(N, k * E) > 2 ** 31 - 2:
+            raise ValueError("GnGraph: too many edges for 32-bit lists")
+        node_rows, edge_rows = _ranges(self.node_ptr[sel], nv), _ranges(self.edge_ptr[sel], ne)
+        entry_rows = _ranges(k * self.edge_ptr[sel], k * ne)
+        of_node, of_edge, of_entry = (np.repeat(np.arange(n), c) for c in (nv, ne, k * ne))
+        host = {"src": self.src[edge_rows] + node_off[of_edge], "dst": self.dst[edge_rows] + node_off[of_edge],
+                "node_graph": of_node, "node_ptr": node_off, "edge_ptr": edge_off,
+                "inc_ptr": np.append(self.inc_start[node_rows] + k * edge_off[of_node], k * E),
+                "inc_edge": self.inc_edge[entry_rows] + edge_off[of_entry],
+                "inc_other": self.inc_other[entry_rows] + node_off[of_entry]}
+        if not self.undirected:
+            host.update(out_ptr=np.append(self.out_start[node_rows] + edge_off[of_node], E),
+                        out_edge=self.out_edge[edge_rows] + edge_off[of_edge],
+                        out_other=self.out_other[edge_rows] + node_off[of_edge])
+        host = {key: np.ascontiguousarray(v, np.int32) for key, v in host.items()}
+        total, layout = ops.gn_batch_layout(n, N, E, self.undirected, *self.widths)
+        w = np.empty(total, np.int32)  # (malloc aligns to 16 bytes)
+        for key, (o, shape) in layout.items():
+            size = int(np.prod(shape))
+            w[o + size:o + size + (-size % 4)] = 0  # the pad words
+            if key in host:
+                w[o:o + size] = host[key]
+        for key, rows, take in (("x", self.node_features, node_rows), ("edge_attr", self.edge_features, edge_rows),
+                                ("global_features", self.global_features, sel)):
+            o, shape = layout[key]  # gathered straight into the buffer (the indices were checked: no second bounds pass)
+            np.take(rows, take, axis=0, out=w[o:o + int(np.prod(shape))].view(np.float32).reshape(shape), mode="clip")
+        made = MegnetBatch.from_device(torch.from_numpy(w).to(device), n, N, E, self.undirected, self.widths)
+        made.graph._host = host
+        return made
+
+
+class ResidentMegnetSet(object):
+    """A ``MegnetGraphSet`` in device memory, uploaded once per dataset; ``batch(idx)`` is then O(n_graphs) work on the
+    host -- the counts of the selected graphs, their two prefix sums, one pinned staging buffer ``[graph_idx ; node_off ;
+    edge_off]`` in one copy -- and ``gcmi_gn_collate`` writes the packed batch buffer on the device, the same bytes
+    ``MegnetGraphSet.batch(idx, device)`` uploads.  The arrays are ``ops.GN_SET_ARRAYS`` (undirected: without the
+    ``out_*`` lists); the per-graph counts stay on the host.  No check per batch: see ``MegnetGraphSet``.
+
+    ``device`` may be the CPU: the arrays then stay there, for ``plan`` and ``ops.gn_collate_host``."""
+
+    def __init__(self, graphs: MegnetGraphSet, device):
+        self.graphs, self.device = graphs, torch.device(device)
+        self.host_arrays = self.arrays_of(graphs)
+        self.arrays = {k: torch.from_numpy(a).to(self.device) for k, a in self.host_arrays.items()}
+        self.nbytes = self.bytes_needed(graphs)
+
+    @staticmethod
+    def bytes_needed(graphs: MegnetGraphSet) -> int:
+        N, E, M = int(graphs.node_ptr[-1]), int(graphs.edge_ptr[-1]), graphs.n_graphs
+        fn, fe, fg = graphs.widths
+        lists = (N + 6 * E) if graphs.undirected else (2 * N + 6 * E)
+        return 16 * (M + 1) + 4 * (N * fn + E * fe + M * fg + lists)
+
+    @staticmethod
+    def arrays_of(graphs: MegnetGraphSet):
+        names = [k for k in ops.GN_SET_ARRAYS if hasattr(graphs, k)]
+        return {k: np.ascontiguousarray(getattr(graphs, k)) for k in names}
+
+    def plan(self, idx, pinned: bool = False):
+        """``(plan, n_nodes, n_edges)``: the int32 words ``[graph_idx ; node_off ; edge_off]`` of a batch (a torch
+        tensor, in pinned memory if asked) and its totals.  O(n_graphs); a graph index outside the set, or no graph at
+        all, is a ``ValueError``."""
+        sel = self.graphs._select(idx)
+        n = sel.size
+        nv, ne = self.graphs.n_nodes_of[sel], self.graphs.n_edges_of[sel]
+        n_nodes, n_edges = int(nv.sum()), int(ne.sum())
+        if max(n, n_nodes, (2 if self.graphs.undirected else 1) * n_edges) > 2 ** 31 - 2:
+            raise ValueError("GnGraph: too many edges for 32-bit lists")
+        staging = torch.empty(3 * n + 2, dtype=torch.int32, pin_memory=pinned)
+        words = staging.numpy()
+        words[:n] = sel
+        words[n], words[2 * n + 1] = 0, 0
+        np.cumsum(nv, out=words[n + 1:2 * n + 1])
+        np.cumsum(ne, out=words[2 * n + 2:])
+        return staging, n_nodes, n_edges
+
+    def batch(self, idx) -> MegnetBatch:
+        """The batch of the graphs ``idx`` (in order, repeats allowed), collated on the current stream."""
+        if self.device.type != "cuda":
+            raise ValueError("ResidentMegnetSet.batch: the set is not on a GPU (there is no CPU path)")
+        staging, n_nodes, n_edges = self.plan(idx, pinned=True)
+        n = (staging.numel() - 2) // 3
+        und = self.graphs.undirected
+        words = ops.gn_collate(self.arrays, und, staging.to(self.device, non_blocking=True), n, n_nodes, n_edges)
+        return MegnetBatch.from_device(words, n, n_nodes, n_edges, und, self.graphs.widths)
+
+
+# Batches of at least this many graphs are collated on the device by collate="auto".  The rule: the smallest measured
+# batch size, not below 32, at which the device-collated training step (median) is below the step that builds its
+# MegnetBatch from the graphs, as fit did before the graph set.  Measured (DESIGN section 52.2; ms, median of three runs
+# with the spread behind it, host-built on the parent commit | device-collated):
+#     32: 9.70 (0.46) | 7.89 (1.69)      64: 7.85 (1.08) | 7.89 (2.01)     128: 8.21 (0.06) | 7.63 (0.29)
+#    256: 8.79 (0.12) | 7.62 (0.30)     512: 9.96 (0.03) | 7.67 (0.89)    1024: 13.67 (0.76) | 8.65 (0.99)
+#   4096: 43.23 (0.37) | 11.96 (0.64)
+# It holds at 32, so the value is 32 (at 64 the medians are level inside their spreads; inside every run the
+# device-collated step was the faster one at every size).  Smaller batches were not measured and stay on the host route
+MEGNET_DEVICE_COLLATE_MIN = 32
 
 
 class MEGNet(nn.Module):
@@ -134,9 +340,12 @@ class MEGNetModel(TorchModel):
 
     def __init__(self, n_node_features: int = 32, n_edge_features: int = 32, n_global_features: int = 32,
                  n_blocks: int = 1, is_undirected: bool = True, residual_connection: bool = True,
-                 mode: str = 'regression', n_classes: int = 2, n_tasks: int = 1, route: str = "auto", **kwargs):
+                 mode: str = 'regression', n_classes: int = 2, n_tasks: int = 1, route: str = "auto",
+                 collate: str = "auto", **kwargs):
         if route not in ("auto", "torch"):
             raise ValueError("route must be 'auto' or 'torch'")
+        if collate not in ("auto", "host", "device"):
+            raise ValueError("collate must be 'auto', 'host' or 'device' (got %r)" % (collate,))
         model = MEGNet(n_node_features=n_node_features, n_edge_features=n_edge_features,
                        n_global_features=n_global_features, n_blocks=n_blocks, is_undirected=is_undirected,
                        residual_connection=residual_connection, mode=mode, n_classes=n_classes, n_tasks=n_tasks)
@@ -146,19 +355,104 @@ class MEGNetModel(TorchModel):
         else:
             loss, output_types = SparseSoftmaxCrossEntropy(), ['prediction', 'loss']
         super(MEGNetModel, self).__init__(model, loss=loss, output_types=output_types, **kwargs)
+        self.collate = collate
+        self._graph_set = None  # (the X array it was built from, the mode, MegnetGraphSet)
+        self._resident = None   # (that X array, the mode, ResidentMegnetSet or the reason why there is none)
 
     @property
     def last_route(self):
         return self.model.last_route
+
+    def _check_widths(self, got):
+        m = self.model
+        if tuple(got) != (m.n_node_features, m.n_edge_features, m.n_global_features):
+            raise ValueError("MEGNetModel: node, edge and global widths %s, the model was built for %s" %
+                             (tuple(got), (m.n_node_features, m.n_edge_features, m.n_global_features)))
+
+    def graph_set(self, X) -> MegnetGraphSet:
+        """The flat arrays of ``X`` (an array of ``GraphData``) in the model's mode, kept until another array is asked
+        for.  Widths other than the model's: today's ``ValueError``, once per set."""
+        held, mode = self._graph_set, bool(self.model.is_undirected)
+        if held is None or held[0] is not X or held[1] != mode:
+            made = MegnetGraphSet(X, mode)
+            self._check_widths(made.widths)
+            self._graph_set = (X, mode, made)
+        return self._graph_set[2]
+
+    def _device_collate_refusal(self) -> Optional[str]:
+        """What, apart from the dataset, keeps the batches from being collated on the device; None: nothing."""
+        if self.device.type != "cuda":
+            return "the model is on %s, not on a GPU" % self.device
+        if self.model.route == "torch":
+            return "route='torch' runs plain torch, the device collation belongs to the native route"
+        if os.environ.get("GCMI_RESIDENT_SET", "1") == "0":
+            return "GCMI_RESIDENT_SET=0 switches resident sets off"
+        return None
+
+    def _resident_for(self, X):
+        """The ``ResidentMegnetSet`` of ``X``, uploaded once and kept until another array is asked for -- or, as a
+        string, why there is none: the set must fit into a quarter of the device memory that is free when it is built."""
+        held, mode = self._resident, bool(self.model.is_undirected)
+        if held is None or held[0] is not X or held[1] != mode:
+            graphs = self.graph_set(X)
+            need = ResidentMegnetSet.bytes_needed(graphs)
+            free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
+            if need > free // 4:
+                made = "the set needs %d bytes, more than a quarter of the %d free on the device" % (need, free)
+            else:
+                made = ResidentMegnetSet(graphs, self.device)
+            self._resident = (X, mode, made)
+        return self._resident[2]
+
+    def resident_set(self, X) -> ResidentMegnetSet:
+        """The graphs of ``X`` in device memory (cached); a ``ValueError`` where the set does not fit there."""
+        made = self._resident_for(X)
+        if isinstance(made, str):
+            raise ValueError("MEGNetModel: no resident graph set: " + made)
+        return made
+
+    def _route(self, X) -> Optional[ResidentMegnetSet]:
+        """The resident set that collates the batches of ``X`` on the device, or None: the host collates them."""
+        if self.collate == "host":
+            return None
+        why = self._device_collate_refusal()
+        if why is None:
+            if self.collate == "auto" and self.batch_size < MEGNET_DEVICE_COLLATE_MIN:
+                return None  # (a preference, not an obstacle: collate="device" goes below it)
+            made = self._resident_for(X)
+            if not isinstance(made, str):
+                return made
+            why = made
+        if self.collate == "device":
+            raise ValueError("MEGNetModel(collate='device'): " + why)
+        return None
+
+    def _batch_generator(self, dataset, epochs: int = 1, mode: str = 'fit', deterministic: bool = True,
+                         pad_batches: bool = True):
+        """For a ``NumpyDataset`` of graphs: the graph INDICES follow the dataset's own batch walk (same order, same
+        shuffles from ``np.random``), a batch is an index gather over the cached flat arrays: by numpy
+        (``MegnetGraphSet.batch``) or, where ``_route`` says so, by the device over the resident set.  Anything else:
+        ``default_generator``."""
+        X = getattr(dataset, "X", None) if isinstance(dataset, NumpyDataset) else None
+        if not (isinstance(X, np.ndarray) and X.dtype == object and X.ndim == 1):
+            if self.collate == "device":
+                raise ValueError("MEGNetModel(collate='device'): the dataset is not a NumpyDataset of GraphData")
+            yield from self.default_generator(dataset, epochs=epochs, mode=mode, deterministic=deterministic,
+                                              pad_batches=pad_batches)
+            return
+        graphs = self.graph_set(X)
+        resident = self._route(X)
+        index_set = NumpyDataset(np.arange(X.shape[0]), dataset.y, dataset.w, dataset.ids)
+        for _ in range(epochs):
+            for (idx, y_b, w_b, _ids) in index_set.iterbatches(batch_size=self.batch_size, deterministic=deterministic,
+                                                               pad_batches=pad_batches):
+                made = graphs.batch(idx, self.device) if resident is None else resident.batch(idx)
+                yield (made, [y_b], [w_b])
 
     def _prepare_batch(self, batch):
         """The graphs of ``default_generator`` (an object array nested in a list) become one ``MegnetBatch``."""
         graphs, labels, weights = batch
         if not isinstance(graphs, MegnetBatch):
             graphs = MegnetBatch(graphs[0], self.model.is_undirected, self.device)
-            m = self.model
-            got = (graphs.x.shape[1], graphs.edge_attr.shape[1], graphs.global_features.shape[1])
-            if got != (m.n_node_features, m.n_edge_features, m.n_global_features):
-                raise ValueError("MEGNetModel: node, edge and global widths %s, the model was built for %s" %
-                                 (got, (m.n_node_features, m.n_edge_features, m.n_global_features)))
+            self._check_widths((graphs.x.shape[1], graphs.edge_attr.shape[1], graphs.global_features.shape[1]))
         return (graphs, [self._to_device(x) for x in labels or ()], [self._to_device(x) for x in weights or ()])

@@ -1054,18 +1054,45 @@ class MatAttentionFn(torch.autograd.Function):
 GN_WIDTH, GN_ROWS_PER_WG = 32, 32
 
 
+GN_INT_BLOCKS = ("src", "dst", "node_graph", "node_ptr", "edge_ptr", "inc_ptr", "inc_edge", "inc_other", "out_ptr",
+                 "out_edge", "out_other")
+GN_FLOAT_BLOCKS = ("x", "edge_attr", "global_features")
+GN_BATCH_BLOCKS = GN_INT_BLOCKS + GN_FLOAT_BLOCKS
+# gn_collate_kernel: one workgroup of GN_COLLATE_THREADS threads per graph; a pass of the workgroup covers that many words
+GN_COLLATE_THREADS = 256
+
+
+def gn_batch_layout(n_graphs: int, n_nodes: int, n_edges: int, undirected: bool, n_node_features: int = 0,
+                    n_edge_features: int = 0, n_global_features: int = 0):
+    """The packed MEGNet batch buffer (``gcmi_gn_collate_words``): ``(words, {block: (offset, shape)})`` for the blocks
+    of ``GN_BATCH_BLOCKS`` the mode has (undirected: no ``out_*``), 4-byte words, every block at a 16-byte boundary.  The
+    one routine that places the blocks: for ``GnGraph``'s upload, for ``gcmi_gn_collate`` and for ``GnGraph.from_device``."""
+    sizes = (n_graphs, n_nodes, n_edges, n_node_features, n_edge_features, n_global_features)
+    if min(sizes) < 0 or max(n_graphs, n_nodes, 2 * n_edges) > 2 ** 31 - 2 or max(sizes[3:]) > 2 ** 31 - 1:
+        raise ValueError("gn_batch_layout: sizes must be within [0, 2^31): %r" % (sizes,))
+    G, N, E, k = int(n_graphs), int(n_nodes), int(n_edges), 2 if undirected else 1
+    off = (ctypes.c_int64 * len(GN_BATCH_BLOCKS))()
+    words = int(_lib.load().gcmi_gn_collate_words(G, N, E, 1 if undirected else 0, int(n_node_features),
+                                                  int(n_edge_features), int(n_global_features), off))
+    if words < 0:
+        raise _lib.GcmiError("gcmi_gn_collate_words: %s" % _lib.load().gcmi_last_error().decode())
+    shapes = ((E,), (E,), (N,), (G + 1,), (G + 1,), (N + 1,), (k * E,), (k * E,), (N + 1,), (E,), (E,),
+              (N, int(n_node_features)), (E, int(n_edge_features)), (G, int(n_global_features)))
+    return words, {b: (int(off[i]), shapes[i]) for i, b in enumerate(GN_BATCH_BLOCKS) if off[i] >= 0}
+
+
 class GnGraph:
     """The graphs of one batch for csrc/megnet.hip: ``src``, ``dst``, ``node_graph``, ``node_ptr``, ``edge_ptr``, the
     incidence list of every node (``inc_ptr``, ``inc_edge``, ``inc_other``: the edges ARRIVING there; undirected: every
     edge at both its ends, in the order of the reference's doubled edge list) and, directed, the list of the edges
     LEAVING every node.  Built on the host in numpy, validated there by ``gcmi_gn_graph_check``, uploaded in ONE
-    packed transfer together with ``floats`` (arrays that travel along, e.g. the features: ``self.floats``).
+    packed transfer together with ``floats`` (arrays that travel along, e.g. the features: ``self.floats``) in the
+    layout of ``gn_batch_layout``.  ``from_device`` wraps a buffer the device collated in that layout instead.
 
     ``batch``: the graph of every node, non-decreasing; every graph of ``range(n_graphs)`` holds a node; the edges are
     grouped by graph in the same order (what concatenating graphs gives).  Anything else: ``ValueError``."""
 
-    _INT_FIELDS = ("src", "dst", "node_graph", "node_ptr", "edge_ptr", "inc_ptr", "inc_edge", "inc_other", "out_ptr",
-                   "out_edge", "out_other")
+    _INT_FIELDS = GN_INT_BLOCKS
 
     def __init__(self, edge_index, batch, n_graphs: int, undirected: bool, device, floats=()):
         ei = np.asarray(edge_index)
@@ -1103,31 +1130,69 @@ class GnGraph:
             order = np.argsort(src, kind="stable")
             h.update(out_ptr=csr(src, N), out_edge=edges[order], out_other=dst[order])
         self.n_inc = int(h["inc_edge"].size)
-        self.host = {k: np.ascontiguousarray(v, np.int32) for k, v in h.items()}
-        self._host_ref = self._desc({k: v.ctypes.data for k, v in self.host.items()})
-        _lib.call("gcmi_gn_graph_check", ctypes.byref(self._host_ref))
-        # one upload: the int32 lists as raw words, each block padded to 16 bytes, then the float arrays
-        blocks, where, at = [], {}, 0
-        for k, v in self.host.items():
-            where[k] = (at, v.size)
-            pad = -v.size % 4
-            blocks.append(np.concatenate([v, np.zeros(pad, np.int32)]).view(np.float32))
-            at += v.size + pad
+        self._host = {k: np.ascontiguousarray(v, np.int32) for k, v in h.items()}
+        self._host_ref_ = self._desc({k: v.ctypes.data for k, v in self._host.items()})
+        _lib.call("gcmi_gn_graph_check", ctypes.byref(self._host_ref_))
+        # one upload: the int32 lists as raw words, each block padded to 16 bytes, then the float arrays.  The three
+        # feature arrays of a MEGNet batch are blocks of gn_batch_layout; other arrays follow the lists the same way
         fl = [np.ascontiguousarray(a, np.float32) for a in floats]
-        for a in fl:
-            pad = -a.size % 4
-            blocks.append(np.concatenate([a.reshape(-1), np.zeros(pad, np.float32)]))
-        packed = torch.as_tensor(np.concatenate(blocks), device=self.device)
-        words = packed[:at].view(torch.int32)
-        for k, (o, n) in where.items():
-            setattr(self, k, words[o:o + n])
-        self.floats = []
-        for a in fl:
-            self.floats.append(packed[at:at + a.size].view(a.shape))
-            at += a.size + (-a.size % 4)
+        features = len(fl) == 3 and all(a.ndim == 2 for a in fl) and [a.shape[0] for a in fl] == [N, E, G]
+        total, layout = gn_batch_layout(G, N, E, self.undirected, *([a.shape[1] for a in fl] if features else (0, 0, 0)))
+        where = [layout[k][0] for k in GN_FLOAT_BLOCKS] if features else []
+        for a in ([] if features else fl):
+            where.append(total)
+            total += a.size + (-a.size % 4)
+        words = np.zeros(total, np.int32)
+        for k, v in self._host.items():
+            words[layout[k][0]:layout[k][0] + v.size] = v
+        for o, a in zip(where, fl):
+            words[o:o + a.size] = a.reshape(-1).view(np.int32)
+        self._adopt(torch.as_tensor(words.view(np.float32), device=self.device), layout, list(zip(where, (a.shape for a in fl))))
+
+    def _adopt(self, packed: torch.Tensor, layout, floats):
+        """The lists, ``floats`` ((offset, shape) each) and ``ref`` as views of the packed float32 buffer on its device."""
+        words = packed.view(torch.int32)
+        for k in self._INT_FIELDS:
+            if k in layout:
+                setattr(self, k, words[layout[k][0]:layout[k][0] + layout[k][1][0]])
+        self.floats = [packed[o:o + int(np.prod(shape))].view(shape) for o, shape in floats]
         self._packed = packed
-        self.ref = self._desc({k: getattr(self, k).data_ptr() for k in where}) if self.device.type == "cuda" else None
+        self.ref = self._desc({k: getattr(self, k).data_ptr() for k in self._INT_FIELDS if k in layout}) \
+            if self.device.type == "cuda" else None
         self._masks = None
+
+    @classmethod
+    def from_device(cls, words: torch.Tensor, n_graphs: int, n_nodes: int, n_edges: int, undirected: bool, widths) -> "GnGraph":
+        """Around a buffer ``gcmi_gn_collate`` wrote (``gn_batch_layout`` with the three feature ``widths``): the
+        attributes of the constructor as views of it, ``floats`` = x, edge_attr, global_features; nothing on the host
+        until ``host`` is asked for.  Not validated per batch: see ``ResidentMegnetSet``."""
+        self = cls.__new__(cls)
+        self.n_nodes, self.n_edges, self.n_graphs, self.undirected = int(n_nodes), int(n_edges), int(n_graphs), bool(undirected)
+        self.n_inc = (2 if self.undirected else 1) * self.n_edges
+        self.device = words.device
+        total, layout = gn_batch_layout(self.n_graphs, self.n_nodes, self.n_edges, self.undirected, *widths)
+        if words.dtype != torch.int32 or words.dim() != 1 or words.numel() != total or words.data_ptr() % 16:
+            raise ValueError("GnGraph.from_device: the buffer must hold the %d int32 words of the layout, 16-byte aligned" % total)
+        self._host, self._host_ref_ = None, None
+        self._layout = layout
+        self._adopt(words.view(torch.float32), layout, [layout[k] for k in GN_FLOAT_BLOCKS])
+        return self
+
+    @property
+    def host(self):
+        """The int32 lists on the host.  A graph collated by the device (``from_device``) downloads its buffer and
+        splits it on first use."""
+        if self._host is None:
+            words = self._packed.view(torch.int32).cpu().numpy()
+            self._host = {k: words[self._layout[k][0]:self._layout[k][0] + self._layout[k][1][0]].copy()
+                          for k in self._INT_FIELDS if k in self._layout}
+        return self._host
+
+    @property
+    def _host_ref(self):
+        if self._host_ref_ is None:
+            self._host_ref_ = self._desc({k: v.ctypes.data for k, v in self.host.items()})
+        return self._host_ref_
 
     def _desc(self, ptrs) -> "_lib.GcmiGnGraph":
         d = _lib.GcmiGnGraph(n_nodes=self.n_nodes, n_edges=self.n_edges, n_graphs=self.n_graphs,
@@ -1143,6 +1208,83 @@ class GnGraph:
             self._masks = ((self.inc_ptr[1:] > self.inc_ptr[:-1]).to(torch.float32).unsqueeze(1),
                            (self.edge_ptr[1:] > self.edge_ptr[:-1]).to(torch.float32).unsqueeze(1))
         return self._masks
+
+
+GN_SET_ARRAYS = ("node_ptr", "edge_ptr", "node_features", "edge_features", "global_features", "src", "dst", "inc_start",
+                 "inc_edge", "inc_other", "out_start", "out_edge", "out_other")
+_GN_SET_DIRECTED_ONLY = ("out_start", "out_edge", "out_other")
+
+
+def _gn_set_desc(arrays, undirected: bool, n_graphs: int, n_nodes: int, n_edges: int, ptr_of, what: str):
+    """``(gcmi_gn_set, widths)`` of the set ``arrays`` (``GN_SET_ARRAYS``; undirected: without the ``out_*`` lists) after
+    the size checks the C entry cannot make: it sees pointers only."""
+    names = [k for k in GN_SET_ARRAYS if not (undirected and k in _GN_SET_DIRECTED_ONLY)]
+    if set(arrays) != set(names):
+        raise ValueError("%s: the set of a%s batch holds %s" % (what, "n undirected" if undirected else " directed", ", ".join(names)))
+    M = arrays["node_ptr"].shape[0] - 1
+    if M < 0 or arrays["edge_ptr"].shape[0] != M + 1 or arrays["global_features"].shape[0] != M or \
+            any(arrays[k].ndim != 2 for k in ("node_features", "edge_features", "global_features")):
+        raise ValueError("%s: node_ptr, edge_ptr and global_features (2-D) must cover the same graphs" % what)
+    N, E, k = arrays["node_features"].shape[0], arrays["edge_features"].shape[0], 2 if undirected else 1
+    entries = {"src": E, "dst": E, "inc_start": N, "inc_edge": k * E, "inc_other": k * E, "out_start": N, "out_edge": E,
+               "out_other": E}
+    for name in names:
+        if name in entries and tuple(arrays[name].shape) != (entries[name],):
+            raise ValueError("%s: %s needs %d entries" % (what, name, entries[name]))
+    if min(n_graphs, n_nodes, n_edges) < 0 or max(n_graphs, n_nodes, k * n_edges) > 2 ** 31 - 2:
+        raise ValueError("%s: a batch holds at most 2^31 - 2 graphs, nodes and incidence entries" % what)
+    widths = tuple(int(arrays[k].shape[1]) for k in ("node_features", "edge_features", "global_features"))
+    d = _lib.GcmiGnSet(n_graphs=M, undirected=1 if undirected else 0, fn=widths[0], fe=widths[1], fg=widths[2])
+    for name in names:
+        setattr(d, name, ptr_of(arrays[name]) or None)
+    return d, widths
+
+
+def _gn_set_dtype(k, i32, i64, f32):
+    return i64 if k in ("node_ptr", "edge_ptr") else f32 if k.endswith("features") else i32
+
+
+def gn_collate(arrays, undirected: bool, plan: torch.Tensor, n_graphs: int, n_nodes: int, n_edges: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``gcmi_gn_collate``: the packed batch buffer (int32 words, ``gn_batch_layout``) of the graphs named by ``plan`` =
+    ``[graph_idx ; node_off ; edge_off]`` (int32, on the device), gathered from the resident set ``arrays``
+    (``GN_SET_ARRAYS``: contiguous CUDA tensors, the two offset arrays int64, indices int32, features float32 2-D).
+    The graph indices must have been validated by the caller: the kernel skips a bad one, it does not report it.
+    ``out``: an int32 CUDA vector of exactly the layout's words to write into."""
+    for k, t in arrays.items():
+        want = _gn_set_dtype(k, torch.int32, torch.int64, torch.float32)
+        if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == want):
+            raise _lib.GcmiError("gn_collate: %s must be a contiguous %s CUDA tensor" % (k, want))
+    d, widths = _gn_set_desc(arrays, undirected, n_graphs, n_nodes, n_edges, lambda t: t.data_ptr(), "gn_collate")
+    _i32vec(plan, "plan", 3 * n_graphs + 2)
+    words, _ = gn_batch_layout(n_graphs, n_nodes, n_edges, undirected, *widths)
+    if out is None:
+        out = torch.empty(words, dtype=torch.int32, device=plan.device)
+    _i32vec(out, "out", words)
+    _lib.call("gcmi_gn_collate", ctypes.byref(d), _ptr(plan), n_graphs, n_nodes, n_edges, _ptr(out), words, _stream())
+    return out
+
+
+def gn_collate_host(arrays, undirected: bool, plan: np.ndarray, n_graphs: int, n_nodes: int, n_edges: int,
+                    out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``gcmi_gn_collate_host``: the same routine over numpy arrays, for tests without a GPU.  ``out``: a 16-byte
+    aligned int32 vector of exactly the layout's words to write into."""
+    for k, a in arrays.items():
+        want = _gn_set_dtype(k, np.int32, np.int64, np.float32)
+        if not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == want):
+            raise ValueError("gn_collate_host: %s must be a C-contiguous %s array" % (k, np.dtype(want)))
+    d, widths = _gn_set_desc(arrays, undirected, n_graphs, n_nodes, n_edges, lambda a: a.ctypes.data, "gn_collate_host")
+    if not (isinstance(plan, np.ndarray) and plan.dtype == np.int32 and plan.flags.c_contiguous and
+            plan.size == 3 * n_graphs + 2):
+        raise ValueError("gn_collate_host: plan must hold 3 * n_graphs + 2 int32 words")
+    words, _ = gn_batch_layout(n_graphs, n_nodes, n_edges, undirected, *widths)
+    if out is None:
+        out = torch.empty(words, dtype=torch.int32).numpy()  # (torch allocates 64-byte aligned)
+    if not (out.dtype == np.int32 and out.flags.c_contiguous and out.ndim == 1):
+        raise ValueError("gn_collate_host: out must be a contiguous int32 vector")
+    _lib.call("gcmi_gn_collate_host", ctypes.byref(d), _vp(plan.ctypes.data), n_graphs, n_nodes, n_edges,
+              _vp(out.ctypes.data), out.size)
+    return out
 
 
 def _gn_graph(g, what: str) -> GnGraph:

@@ -1114,6 +1114,42 @@ int gcmi_dmpnn_collate_host(const int64_t* atom_ptr, const int64_t* bond_ptr, co
                             int32_t bond_fdim, int32_t global_fdim, const int32_t* plan, int32_t n_mols, int32_t n_atoms,
                             int32_t n_bonds, int32_t* out, int64_t out_words);
 
+/* ---------------------------------------------------------------- MEGNet batch collation (megnet_collate.hip)
+ * A batch of the graph-network kernels above (the int32 lists of gcmi_gn_graph plus the three feature arrays), gathered
+ * on the device from a graph set that stays in device memory.  The set, n_graphs = M graphs with N nodes and E edges in
+ * all, k = 2 (undirected) or 1: node_ptr, edge_ptr [M + 1]; node_features [N x fn]; edge_features [E x fe];
+ * global_features [M x fg]; src, dst [E] LOCAL to the graph; inc_start [N]: where the node's incidence list begins,
+ * relative to the graph's first entry; inc_edge, inc_other [k E] local, the entries of graph g at [k edge_ptr[g],
+ * k edge_ptr[g + 1]); directed only: out_start [N], out_edge, out_other [E], the same for the edges LEAVING a node.
+ * d_plan: int32 words [graph_idx (n_graphs) ; node_off (n_graphs + 1) ; edge_off (n_graphs + 1)], the offsets being the
+ * exclusive prefix sums of the selected graphs' node and edge counts, totals last (= n_nodes, n_edges).
+ * d_out receives blocks of 4-byte words, each starting at a 16-byte boundary, pad words zero: the int32 blocks src, dst
+ * (n_edges), node_graph (n_nodes), node_ptr, edge_ptr (n_graphs + 1), inc_ptr (n_nodes + 1), inc_edge, inc_other
+ * (k n_edges), directed only out_ptr (n_nodes + 1), out_edge, out_other (n_edges), then the float blocks x (n_nodes x
+ * fn), edge_attr (n_edges x fe), global_features (n_graphs x fg).
+ * gcmi_gn_collate_words returns the words of that buffer and, with offsets != NULL, the GCMI_GN_COLLATE_BLOCKS block
+ * offsets in that order, -1 for a block the mode lacks (-1 returned: a negative size).  Every word is written exactly
+ * once, pad words included; no atomics.  A graph index outside [0, M), or a graph that would not fit the totals, is
+ * skipped and not read through (its words stay unwritten: the caller validates the indices).  NULL pointers, negative
+ * sizes, n_graphs < 1, misaligned buffers, an output that is not 16-byte aligned and out_words other than the layout's:
+ * GCMI_ERR_ARG before any launch.
+ * gcmi_gn_collate_host: the same routine run by host loops over host buffers, for tests without a GPU.             */
+#define GCMI_GN_COLLATE_BLOCKS 14
+typedef struct gcmi_gn_set {
+  int64_t n_graphs;
+  int32_t undirected, fn, fe, fg;
+  const int64_t *node_ptr, *edge_ptr;
+  const float *node_features, *edge_features, *global_features;
+  const int32_t *src, *dst, *inc_start, *inc_edge, *inc_other;
+  const int32_t *out_start, *out_edge, *out_other; /* directed only */
+} gcmi_gn_set;
+int64_t gcmi_gn_collate_words(int32_t n_graphs, int32_t n_nodes, int32_t n_edges, int32_t undirected, int32_t fn,
+                              int32_t fe, int32_t fg, int64_t* offsets);
+int gcmi_gn_collate(const gcmi_gn_set* set, const int32_t* d_plan, int32_t n_graphs, int32_t n_nodes, int32_t n_edges,
+                    int32_t* d_out, int64_t out_words, void* stream);
+int gcmi_gn_collate_host(const gcmi_gn_set* set, const int32_t* plan, int32_t n_graphs, int32_t n_nodes, int32_t n_edges,
+                         int32_t* out, int64_t out_words);
+
 /* ---------------------------------------------------------------- measurement
  * Optional per-kernel timing with hipEvents recorded on `stream` around the
  * launches of one kernel family (bench.py roofline).  id: see GCMI_K_*.       */

@@ -2,14 +2,17 @@
 kernels) against the torch route (the reference's order: doubled edges, concatenated rows, scatter-means) of the SAME
 ``MEGNetModel`` on the same GPU and batch.
 
-    python tools/megnet_step_time.py [--batches 4096] [--warmup 5] [--steps 30]
+    python tools/megnet_step_time.py [--batches 32 64 128 256 512 1024 4096] [--warmup 5] [--steps 30]
 
 The default-width model (Fn = Fe = Fg = 32, n_blocks = 3, undirected) on molecule-like graphs: a random tree of about
 18 nodes (at least 3, at most 29) plus up to two ring closures, every bond listed in both directions.  Per route:
 warm-up steps, then the MEDIAN of repeated steps, each ended by a device synchronise; peak memory =
 ``torch.cuda.max_memory_allocated`` over the timed steps.  ``*_ms`` builds and uploads the ``MegnetBatch`` in every step,
-as ``fit`` does; ``*_uploaded_ms`` reuses an uploaded batch.  ``build_ms``: the host-side build and upload alone.  One
-JSON line per batch size.
+as ``fit`` did before the graph set; ``*_uploaded_ms`` reuses an uploaded batch.  ``build_ms``: the host-side build and
+upload alone.  The two routes ``fit`` takes over a ``NumpyDataset`` now, both over the cached ``MegnetGraphSet`` of the same
+graphs and a fixed permutation of them: ``native_setcollate_ms`` gathers the batch in numpy and uploads it,
+``native_devcollate_ms`` is plan, index upload, ``gcmi_gn_collate`` over the ``ResidentMegnetSet`` and the step together.
+One JSON line per batch size.
 """
 import argparse
 import gc
@@ -56,7 +59,7 @@ def timed(step, warmup, steps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", type=int, nargs="+", default=[4096])
+    ap.add_argument("--batches", type=int, nargs="+", default=[32, 64, 128, 256, 512, 1024, 4096])
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--steps", type=int, default=30)
     args = ap.parse_args()
@@ -92,6 +95,19 @@ def main():
             row[tag + "_uploaded_ms"], row[tag + "_uploaded_peak_mib"] = (round(v, 3) for v in
                                                                           timed(uploaded_step, args.warmup, args.steps))
             if tag == "native":
+                X = np.empty(B, dtype=object)
+                X[:] = graphs
+                order = np.random.RandomState(3).permutation(B)
+                held, resident = model.graph_set(X), model.resident_set(X)
+                for name, make in (("native_setcollate", lambda: held.batch(order, model.device)),
+                                   ("native_devcollate", lambda: resident.batch(order))):
+                    def collated_step():
+                        model._train_step(make(), labels, weights, model._loss_fn, model._pytorch_optimizer)
+                    row[name + "_ms"], row[name + "_peak_mib"] = (round(v, 3) for v in
+                                                                  timed(collated_step, args.warmup, args.steps))
+                    assert model.last_route == "native"
+                row["set_mib"] = round(resident.nbytes / 2**20, 3)
+                del X, held, resident, make, collated_step
                 row["build_ms"] = round(timed(build, 2, 10)[0], 3)
                 row["nodes"], row["edges"] = uploaded.graph.n_nodes, uploaded.graph.n_edges
             del model, uploaded, build, step, uploaded_step, labels, weights  # (the closures hold the model)
