@@ -98,6 +98,7 @@ int max_sum_launches();  // launches of that pass so far (tests)
 int win_gather_max_bwd_if_ill(const gcmi_graph* g, const float* d_dout, int64_t lddo, int n_feat, const uint8_t* d_arg,
                               float* d_dx, int64_t lddx, const float* d_gamma, const float* d_beta, hipStream_t st);
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
 inline int64_t up4(int64_t n) { return (n + 3) / 4 * 4; }  // floats of a 16-byte aligned block
 inline int64_t up8(int64_t n) { return (n + 7) / 8 * 8; }  // bf16 elements of one

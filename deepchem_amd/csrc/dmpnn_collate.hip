@@ -1,151 +1,90 @@
 // D-MPNN batch collation from a resident graph set (gcmi_dmpnn_collate): the packed batch buffer that
 // DmpnnBatch.to() builds on the host, written by the device from the flat arrays of the whole dataset.  No arithmetic
-// beyond index offsets: the result is the same bytes.
+// beyond index offsets: the result is the same bytes.  The plan, the workgroup per molecule, the tail and the host
+// twin are collate_set.h's; this file states the set, the blocks, what a molecule owns and the closing entries.
 //
 // The set (deepchem_amd/models/torch_models/dmpnn.py, ResidentDmpnnSet), M molecules, A atoms, B directed bonds:
 //   atom_ptr, bond_ptr [M + 1] int64;  atom_features [A x Fa];  bond_features [B x Fb] in the KERNELS' order (inside
 //   every molecule stably sorted by source atom);  sorted_src [B] the source atom and sorted_rev [B] the position of the
 //   reverse bond, both LOCAL to the molecule;  out_start [A] where an atom's run of outgoing bonds begins, relative to
 //   the molecule's first bond;  global_features [M x G].
-// The plan of a batch of n molecules, int32 words made by the host in O(n): [mol_idx (n) ; atom_off (n + 1) ;
-// bond_off (n + 1)], the offsets being the exclusive prefix sums of the selected molecules' counts with the totals last.
 //
 // The buffer (dmpnn_collate_layout): nine blocks of 4-byte words in the order mol_ptr (n + 1), out_ptr (n_atoms + 1),
 // bond_src, rev (n_bonds each), atom_membership (n_atoms), atoms_per_mol (n, float), atom_features (n_atoms x Fa),
-// f_ini_atoms_bonds (n_bonds x (Fa + Fb): [features of the source atom ; bond features]), global_features (n x G);
-// every block starts at a 16-byte boundary and the pad words behind a block are zero.
+// f_ini_atoms_bonds (n_bonds x (Fa + Fb): [features of the source atom ; bond features]), global_features (n x G).
 //
-// One workgroup per selected molecule (collate_molecule).  Molecule m of the batch owns mol_ptr[m], atoms_per_mol[m],
-// global row m, the entries of its atoms [atom_off[m], atom_off[m + 1]) and of its bonds [bond_off[m], bond_off[m + 1]);
-// the LAST workgroup also writes what no molecule owns (collate_tail): mol_ptr[n], out_ptr[n_atoms] and the pad words.
-// So every word of the buffer is written exactly once, without atomics and without a dependence between workgroups.
-//   * the atom rows of a molecule are contiguous in the set AND in the batch: one flat copy of n_a * Fa words, thread t
-//     taking word t, t + 256, ...: consecutive lanes, consecutive dwords on both sides;
+// Molecule m of the batch owns mol_ptr[m], atoms_per_mol[m], global row m, the entries of its atoms [atom_off[m],
+// atom_off[m + 1]) and of its bonds [bond_off[m], bond_off[m + 1]); the tail writes mol_ptr[n] and out_ptr[n_atoms].
+//   * the atom rows of a molecule are contiguous in the set AND in the batch: one flat copy of n_a * Fa words;
 //   * an f_ini row is owned by one wave, lane = column (64 columns per pass): rows of 133 + 14 = 147 floats are only
 //     4-byte aligned, so dwords, not 16-byte pieces; never one lane per row.
-// A plan entry outside [0, M), or one whose rows would not fit the totals, is skipped without reading through it (the
-// Python side refuses such a batch before any launch); a source atom outside its molecule gives a zero atom part.
-//
-// The same routine runs on the host (gcmi_dmpnn_collate_host: one "thread", one "wave" of one "lane") so that the
-// layout is testable without a GPU.
-#include "common.h"
+// A source atom outside its molecule gives a zero atom part.
+#include "collate_set.h"
 
 namespace gcmi {
 namespace {
 
-constexpr int kCollateThreads = 256;
 constexpr int kCollateBlocks = 9;
+// the blocks in buffer order
+enum { B_MOL_PTR, B_OUT_PTR, B_BOND_SRC, B_REV, B_MEMBERSHIP, B_PER_MOL, B_ATOM_ROWS, B_F_INI, B_GLOBAL };
 
-struct DmpnnCollateArgs {
-  const int64_t* atom_ptr;
-  const int64_t* bond_ptr;
-  const float* atom_features;
-  const float* bond_features;
-  const int32_t* sorted_src;
-  const int32_t* sorted_rev;
-  const int32_t* out_start;
-  const float* global_features;
+struct DmpnnCollateArgs : CollateBatch<kCollateBlocks> {  // n_a atoms, n_b bonds
+  const int64_t *atom_ptr, *bond_ptr;
+  const float *atom_features, *bond_features, *global_features;
+  const int32_t *sorted_src, *sorted_rev, *out_start;
   int64_t n_mols_all;
   int32_t fa, fb, fg;
-  const int32_t* plan;
-  int32_t n_mols, n_atoms, n_bonds;
-  int32_t* out;
-  // word offsets of the blocks (dmpnn_collate_layout) and the end of the buffer
-  int64_t mol_ptr, out_ptr, bond_src, rev, membership, per_mol, atom_rows, f_ini, global, end;
 };
 
-__host__ __device__ inline int64_t up4w(int64_t n) { return (n + 3) / 4 * 4; }
-
-// offsets[0..8]: where each block starts; returns the words of the whole buffer
-__host__ __device__ inline int64_t dmpnn_collate_layout(int64_t n_mols, int64_t n_atoms, int64_t n_bonds, int64_t fa,
-                                                        int64_t fb, int64_t fg, int64_t* offsets) {
+// at[0..8]: where each block starts, sizes likewise (either may be NULL); returns the words of the whole buffer
+inline int64_t dmpnn_collate_layout(int64_t n_mols, int64_t n_atoms, int64_t n_bonds, int64_t fa, int64_t fb, int64_t fg,
+                                    int64_t* at, int64_t* sizes) {
   const int64_t size[kCollateBlocks] = {n_mols + 1, n_atoms + 1,  n_bonds,           n_bonds,    n_atoms,
                                         n_mols,     n_atoms * fa, n_bonds * (fa + fb), n_mols * fg};
-  int64_t at = 0;
-  for (int k = 0; k < kCollateBlocks; ++k) {
-    if (offsets) offsets[k] = at;
-    at += up4w(size[k]);
-  }
-  return at;
+  return place_blocks(kCollateBlocks, size, nullptr, at, sizes);
 }
 
 // Everything molecule m of the batch owns.  tid of n_threads walks the per-atom and per-bond words and the flat atom
-// rows; wave of n_waves owns whole f_ini rows, lane of n_lanes their columns.
-__host__ __device__ inline void collate_molecule(const DmpnnCollateArgs& p, int m, int tid, int n_threads, int wave,
-                                                 int n_waves, int lane, int n_lanes) {
-  const int32_t* mol_idx = p.plan;
-  const int32_t* atom_off = p.plan + p.n_mols;
-  const int32_t* bond_off = atom_off + p.n_mols + 1;
-  const int64_t mi = mol_idx[m];
-  const int a0 = atom_off[m], b0 = bond_off[m];
+// rows; a wave (64 lanes of the workgroup, the one "thread" of the host) owns whole f_ini rows, a lane their columns.
+__host__ __device__ inline void collate_item(const DmpnnCollateArgs& p, int m, int tid, int n_threads) {
+  const PlanEntry e = plan_entry(p.plan, p.n, m, p.atom_ptr, p.bond_ptr, p.n_mols_all, p.n_a, p.n_b);
+  const int a0 = e.a0, b0 = e.b0;
   int32_t* o = p.out;
   float* of = reinterpret_cast<float*>(p.out);
-  if (tid == 0) o[p.mol_ptr + m] = a0;
-  const bool known = mi >= 0 && mi < p.n_mols_all;
-  const int64_t ap = known ? p.atom_ptr[mi] : 0, bp = known ? p.bond_ptr[mi] : 0;
-  const int64_t na64 = known ? p.atom_ptr[mi + 1] - ap : 0, nb64 = known ? p.bond_ptr[mi + 1] - bp : 0;
-  const bool fits = known && na64 >= 0 && nb64 >= 0 && a0 >= 0 && b0 >= 0 && a0 + na64 <= p.n_atoms &&
-                    b0 + nb64 <= p.n_bonds;
-  if (tid == 0) of[p.per_mol + m] = fits ? (float)na64 : 0.f;
+  if (tid == 0) {
+    o[p.at[B_MOL_PTR] + m] = a0;
+    of[p.at[B_PER_MOL] + m] = e.fits ? (float)e.na : 0.f;
+  }
   for (int c = tid; c < p.fg; c += n_threads)
-    of[p.global + (int64_t)m * p.fg + c] = fits ? p.global_features[mi * p.fg + c] : 0.f;
-  if (!fits) return;
-  const int na = (int)na64, nb = (int)nb64;
-  for (int i = tid; i < na; i += n_threads) {
-    o[p.out_ptr + a0 + i] = b0 + p.out_start[ap + i];
-    o[p.membership + a0 + i] = m;
-  }
-  for (int j = tid; j < nb; j += n_threads) {
-    o[p.bond_src + b0 + j] = a0 + p.sorted_src[bp + j];
-    o[p.rev + b0 + j] = b0 + p.sorted_rev[bp + j];
-  }
-  {
-    const float* src = p.atom_features + ap * p.fa;
-    float* dst = of + p.atom_rows + (int64_t)a0 * p.fa;
-    const int64_t words = (int64_t)na * p.fa;
-    for (int64_t w = tid; w < words; w += n_threads) dst[w] = src[w];
-  }
+    of[p.at[B_GLOBAL] + (int64_t)m * p.fg + c] = e.fits ? p.global_features[e.idx * p.fg + c] : 0.f;
+  if (!e.fits) return;
+  const int na = (int)e.na, nb = (int)e.nb;
+  const int64_t ap = e.ap, bp = e.bp;
+  copy_add(o + p.at[B_OUT_PTR] + a0, p.out_start + ap, na, b0, tid, n_threads);
+  fill_words(o + p.at[B_MEMBERSHIP] + a0, na, m, tid, n_threads);
+  copy_add(o + p.at[B_BOND_SRC] + b0, p.sorted_src + bp, nb, a0, tid, n_threads);
+  copy_add(o + p.at[B_REV] + b0, p.sorted_rev + bp, nb, b0, tid, n_threads);
+  copy_rows(of + p.at[B_ATOM_ROWS] + (int64_t)a0 * p.fa, p.atom_features + ap * p.fa, (int64_t)na * p.fa, tid, n_threads);
+  const int n_lanes = n_threads < 64 ? n_threads : 64, n_waves = n_threads / n_lanes;
+  const int wave = tid / n_lanes, lane = tid % n_lanes;
   const int f = p.fa + p.fb;
   for (int j = wave; j < nb; j += n_waves) {
     const int s = p.sorted_src[bp + j];
     const bool inside = s >= 0 && s < na;
     const float* xa = p.atom_features + (ap + (inside ? s : 0)) * p.fa;
     const float* xb = p.bond_features + (bp + j) * p.fb;
-    float* dst = of + p.f_ini + (int64_t)(b0 + j) * f;
+    float* dst = of + p.at[B_F_INI] + (int64_t)(b0 + j) * f;
     for (int c = lane; c < f; c += n_lanes) dst[c] = c < p.fa ? (inside ? xa[c] : 0.f) : xb[c - p.fa];
   }
 }
 
-// What no molecule owns: the closing entries of mol_ptr and out_ptr and the (at most three) zero words behind a block
+// What no molecule owns: the closing entries of mol_ptr and out_ptr and the pad words
 __host__ __device__ inline void collate_tail(const DmpnnCollateArgs& p, int tid, int n_threads) {
-  const int64_t begin[kCollateBlocks + 1] = {p.mol_ptr,    p.out_ptr,   p.bond_src, p.rev,    p.membership,
-                                             p.per_mol,    p.atom_rows, p.f_ini,    p.global, p.end};
-  const int64_t size[kCollateBlocks] = {(int64_t)p.n_mols + 1,
-                                        (int64_t)p.n_atoms + 1,
-                                        p.n_bonds,
-                                        p.n_bonds,
-                                        p.n_atoms,
-                                        p.n_mols,
-                                        (int64_t)p.n_atoms * p.fa,
-                                        (int64_t)p.n_bonds * (p.fa + p.fb),
-                                        (int64_t)p.n_mols * p.fg};
   if (tid == 0) {
-    p.out[p.mol_ptr + p.n_mols] = p.n_atoms;
-    p.out[p.out_ptr + p.n_atoms] = p.n_bonds;
+    p.out[p.at[B_MOL_PTR] + p.n] = p.n_a;
+    p.out[p.at[B_OUT_PTR] + p.n_a] = p.n_b;
   }
-  // 4 slots per block: slot q of block k is the q-th word behind the block's data, if the block has that many pad words
-  for (int t = tid; t < 4 * kCollateBlocks; t += n_threads) {
-    const int k = t / 4;
-    const int64_t w = begin[k] + size[k] + t % 4;
-    if (w < begin[k + 1]) p.out[w] = 0;
-  }
-}
-
-__global__ __launch_bounds__(kCollateThreads) void dmpnn_collate_kernel(const DmpnnCollateArgs p) {
-  const int m = blockIdx.x;
-  const int tid = threadIdx.x;
-  if (m == (int)gridDim.x - 1) collate_tail(p, tid, kCollateThreads);
-  if (m < p.n_mols) collate_molecule(p, m, tid, kCollateThreads, tid / 64, kCollateThreads / 64, tid % 64, 64);
+  write_pads(p, tid, n_threads);
 }
 
 int fill_args(DmpnnCollateArgs& p, const char* what, const int64_t* atom_ptr, const int64_t* bond_ptr,
@@ -162,15 +101,16 @@ int fill_args(DmpnnCollateArgs& p, const char* what, const int64_t* atom_ptr, co
   GCMI_CHECK_ARG(n_mols == 0 || fg == 0 || global_features, "%s: NULL global features", what);
   GCMI_CHECK_ARG(aligned4(atom_features) && aligned4(bond_features) && aligned4(global_features) && aligned4(plan) &&
                      aligned4(out) && aligned4(sorted_src) && aligned4(sorted_rev) && aligned4(out_start) &&
-                     (reinterpret_cast<uintptr_t>(atom_ptr) & 7u) == 0 && (reinterpret_cast<uintptr_t>(bond_ptr) & 7u) == 0,
+                     aligned8(atom_ptr) && aligned8(bond_ptr),
                  "%s: a buffer is not aligned to its element size", what);
-  int64_t off[kCollateBlocks];
-  const int64_t words = dmpnn_collate_layout(n_mols, n_atoms, n_bonds, fa, fb, fg, off);
-  GCMI_CHECK_ARG(out_words >= words, "%s: the output buffer holds %lld words, the layout needs %lld", what,
-                 (long long)out_words, (long long)words);
-  p = DmpnnCollateArgs{atom_ptr, bond_ptr, atom_features, bond_features, sorted_src, sorted_rev, out_start,
-                       global_features, n_mols_all, fa, fb, fg, plan, n_mols, n_atoms, n_bonds, out,
-                       off[0], off[1], off[2], off[3], off[4], off[5], off[6], off[7], off[8], words};
+  p = DmpnnCollateArgs{};
+  p.plan = plan, p.n = n_mols, p.n_a = n_atoms, p.n_b = n_bonds, p.out = out;
+  p.atom_ptr = atom_ptr, p.bond_ptr = bond_ptr, p.atom_features = atom_features, p.bond_features = bond_features;
+  p.sorted_src = sorted_src, p.sorted_rev = sorted_rev, p.out_start = out_start, p.global_features = global_features;
+  p.n_mols_all = n_mols_all, p.fa = fa, p.fb = fb, p.fg = fg;
+  p.end = dmpnn_collate_layout(n_mols, n_atoms, n_bonds, fa, fb, fg, p.at, p.size);
+  GCMI_CHECK_ARG(out_words >= p.end, "%s: the output buffer holds %lld words, the layout needs %lld", what,
+                 (long long)out_words, (long long)p.end);
   return GCMI_OK;
 }
 
@@ -187,7 +127,7 @@ int64_t gcmi_dmpnn_collate_words(int32_t n_mols, int32_t n_atoms, int32_t n_bond
     set_error("dmpnn_collate_words: negative size");
     return -1;
   }
-  return dmpnn_collate_layout(n_mols, n_atoms, n_bonds, atom_fdim, bond_fdim, global_fdim, offsets);
+  return dmpnn_collate_layout(n_mols, n_atoms, n_bonds, atom_fdim, bond_fdim, global_fdim, offsets, nullptr);
 }
 
 int gcmi_dmpnn_collate(const int64_t* d_atom_ptr, const int64_t* d_bond_ptr, const float* d_atom_features,
@@ -201,10 +141,7 @@ int gcmi_dmpnn_collate(const int64_t* d_atom_ptr, const int64_t* d_bond_ptr, con
                            d_plan, n_mols, n_atoms, n_bonds, d_out, out_words);
   if (rc != GCMI_OK) return rc;
   // (an empty batch still has its closing entries and pad words: one workgroup, the tail alone)
-  hipLaunchKernelGGL(dmpnn_collate_kernel, dim3(n_mols > 0 ? n_mols : 1), dim3(kCollateThreads), 0,
-                     static_cast<hipStream_t>(stream), p);
-  GCMI_CHECK_LAUNCH("dmpnn_collate");
-  return GCMI_OK;
+  return collate_set_launch(p, n_mols > 0 ? n_mols : 1, stream, "dmpnn_collate");
 }
 
 int gcmi_dmpnn_collate_host(const int64_t* atom_ptr, const int64_t* bond_ptr, const float* atom_features,
@@ -216,10 +153,7 @@ int gcmi_dmpnn_collate_host(const int64_t* atom_ptr, const int64_t* bond_ptr, co
   const int rc = fill_args(p, "dmpnn_collate_host", atom_ptr, bond_ptr, atom_features, bond_features, sorted_src,
                            sorted_rev, out_start, global_features, n_mols_all, atom_fdim, bond_fdim, global_fdim, plan,
                            n_mols, n_atoms, n_bonds, out, out_words);
-  if (rc != GCMI_OK) return rc;
-  collate_tail(p, 0, 1);
-  for (int m = 0; m < n_mols; ++m) collate_molecule(p, m, 0, 1, 0, 1, 0, 1);
-  return GCMI_OK;
+  return rc != GCMI_OK ? rc : collate_set_host(p);
 }
 
 }  // extern "C"

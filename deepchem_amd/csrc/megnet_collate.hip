@@ -1,6 +1,7 @@
 // MEGNet batch collation from a resident graph set (gcmi_gn_collate): the packed batch buffer that ops.GnGraph builds on
 // the host and uploads, written by the device from the flat arrays of the whole dataset.  No arithmetic beyond index
-// offsets: the result is the same bytes.
+// offsets: the result is the same bytes.  The plan, the workgroup per graph, the tail and the host twin are
+// collate_set.h's; this file states the set, the blocks, what a graph owns and the closing entries.
 //
 // The set (deepchem_amd/models/torch_models/megnet.py, ResidentMegnetSet; gcmi_gn_set), M graphs, N nodes, E edges and
 // k E incidence entries (k = 2 undirected, 1 directed):
@@ -11,96 +12,58 @@
 // Every list ops.GnGraph builds decomposes per graph: the batch-level stable sort puts into a node's list only edges of
 // its own graph in ascending edge order, so the batch lists are the per-graph local lists laid end to end with the
 // graph's node and edge offsets added.
-// The plan of a batch of n graphs, int32 words made by the host in O(n): [graph_idx (n) ; node_off (n + 1) ;
-// edge_off (n + 1)], the offsets being the exclusive prefix sums of the selected graphs' counts with the totals last.
 //
 // The buffer (gn_collate_layout): the int32 blocks src, dst (n_edges), node_graph (n_nodes), node_ptr, edge_ptr (n + 1),
 // inc_ptr (n_nodes + 1), inc_edge, inc_other (k n_edges), directed only out_ptr (n_nodes + 1), out_edge, out_other
-// (n_edges), then the float blocks x (n_nodes x Fn), edge_attr (n_edges x Fe), global_features (n x Fg); every block
-// starts at a 16-byte boundary and the pad words behind a block are zero.
+// (n_edges), then the float blocks x (n_nodes x Fn), edge_attr (n_edges x Fe), global_features (n x Fg).
 //
-// One workgroup per selected graph (collate_graph).  Graph m of the batch owns node_ptr[m], edge_ptr[m], global row m
-// and the entries and rows of its nodes [node_off[m], node_off[m + 1]), edges and incidence entries; the LAST workgroup
-// also writes what no graph owns (collate_tail): node_ptr[n], edge_ptr[n], inc_ptr[n_nodes], out_ptr[n_nodes] and the
-// pad words.  So every word of the buffer is written exactly once, without atomics, without a dependence between
-// workgroups and without LDS.  A graph's node rows, edge rows and index entries are contiguous in the set AND in the
-// batch: each is one flat copy, thread t taking word t, t + 256, ...: consecutive lanes, consecutive dwords on both
-// sides (rows of 5 or 33 floats are only 4-byte aligned, so dwords, not 16-byte pieces; never one lane per row).
-// A plan entry outside [0, M), or one whose rows would not fit the totals, is skipped without reading through it (the
-// Python side refuses such a batch before any launch).
-//
-// The same routine runs on the host (gcmi_gn_collate_host: one "thread") so that the layout is testable without a GPU.
-#include "common.h"
+// Graph m of the batch owns node_ptr[m], edge_ptr[m], global row m and the entries and rows of its nodes [node_off[m],
+// node_off[m + 1]), edges and incidence entries; the tail writes node_ptr[n], edge_ptr[n], inc_ptr[n_nodes] and
+// out_ptr[n_nodes].  A graph's node rows, edge rows and index entries are contiguous in the set AND in the batch: each
+// is one flat copy.
+#include "collate_set.h"
 
 namespace gcmi {
 namespace {
 
-constexpr int kGnCollateThreads = 256;
 constexpr int kGnBlocks = 14;
 // the blocks in buffer order
 enum { B_SRC, B_DST, B_NODE_GRAPH, B_NODE_PTR, B_EDGE_PTR, B_INC_PTR, B_INC_EDGE, B_INC_OTHER, B_OUT_PTR, B_OUT_EDGE,
        B_OUT_OTHER, B_X, B_EDGE_ATTR, B_GLOBAL };
 
-struct GnCollateArgs {
+struct GnCollateArgs : CollateBatch<kGnBlocks> {  // n_a nodes, n_b edges
   gcmi_gn_set set;
-  const int32_t* plan;
-  int32_t n_graphs, n_nodes, n_edges;
-  int32_t* out;
-  int64_t at[kGnBlocks];    // word offset of every block, -1: the mode lacks it
-  int64_t size[kGnBlocks];  // its words before padding
-  int64_t end;
 };
 
-// offsets[0..13]: where each block starts (-1: a block the mode lacks); sizes likewise; returns the words of the buffer
-__host__ __device__ inline int64_t gn_collate_layout(int64_t n_graphs, int64_t n_nodes, int64_t n_edges, bool undirected,
-                                                     int64_t fn, int64_t fe, int64_t fg, int64_t* offsets, int64_t* sizes) {
+// at[0..13]: where each block starts (-1: a block the mode lacks), sizes likewise (either may be NULL); returns the words
+// of the buffer
+inline int64_t gn_collate_layout(int64_t n_graphs, int64_t n_nodes, int64_t n_edges, bool undirected, int64_t fn,
+                                 int64_t fe, int64_t fg, int64_t* at, int64_t* sizes) {
   const int64_t n_inc = undirected ? 2 * n_edges : n_edges;
   const int64_t size[kGnBlocks] = {n_edges,     n_edges, n_nodes, n_graphs + 1, n_graphs + 1, n_nodes + 1,  n_inc,
                                    n_inc,       n_nodes + 1, n_edges, n_edges,  n_nodes * fn, n_edges * fe, n_graphs * fg};
-  int64_t at = 0;
-  for (int k = 0; k < kGnBlocks; ++k) {
-    const bool lacks = undirected && k >= B_OUT_PTR && k <= B_OUT_OTHER;
-    if (offsets) offsets[k] = lacks ? -1 : at;
-    if (sizes) sizes[k] = lacks ? 0 : size[k];
-    if (!lacks) at += (size[k] + 3) / 4 * 4;
-  }
-  return at;
-}
-
-// dst[w] = src[w] + add over `words` words, thread tid of n_threads taking every n_threads-th
-__host__ __device__ inline void copy_add(int32_t* dst, const int32_t* src, int64_t words, int32_t add, int tid,
-                                         int n_threads) {
-  for (int64_t w = tid; w < words; w += n_threads) dst[w] = src[w] + add;
-}
-
-__host__ __device__ inline void copy_rows(float* dst, const float* src, int64_t words, int tid, int n_threads) {
-  for (int64_t w = tid; w < words; w += n_threads) dst[w] = src[w];
+  bool lacks[kGnBlocks];
+  for (int k = 0; k < kGnBlocks; ++k) lacks[k] = undirected && k >= B_OUT_PTR && k <= B_OUT_OTHER;
+  return place_blocks(kGnBlocks, size, lacks, at, sizes);
 }
 
 // Everything graph m of the batch owns
-__host__ __device__ inline void collate_graph(const GnCollateArgs& p, int m, int tid, int n_threads) {
+__host__ __device__ inline void collate_item(const GnCollateArgs& p, int m, int tid, int n_threads) {
   const gcmi_gn_set& s = p.set;
-  const int32_t* graph_idx = p.plan;
-  const int32_t* node_off = p.plan + p.n_graphs;
-  const int32_t* edge_off = node_off + p.n_graphs + 1;
-  const int64_t gi = graph_idx[m];
-  const int v0 = node_off[m], e0 = edge_off[m];
+  const PlanEntry en = plan_entry(p.plan, p.n, m, s.node_ptr, s.edge_ptr, s.n_graphs, p.n_a, p.n_b);
+  const int v0 = en.a0, e0 = en.b0;
   int32_t* o = p.out;
   float* of = reinterpret_cast<float*>(p.out);
   if (tid == 0) {
     o[p.at[B_NODE_PTR] + m] = v0;
     o[p.at[B_EDGE_PTR] + m] = e0;
   }
-  const bool known = gi >= 0 && gi < s.n_graphs;
-  const int64_t vp = known ? s.node_ptr[gi] : 0, ep = known ? s.edge_ptr[gi] : 0;
-  const int64_t nv = known ? s.node_ptr[gi + 1] - vp : 0, ne = known ? s.edge_ptr[gi + 1] - ep : 0;
-  const bool fits = known && vp >= 0 && ep >= 0 && nv >= 0 && ne >= 0 && v0 >= 0 && e0 >= 0 && v0 + nv <= p.n_nodes &&
-                    e0 + ne <= p.n_edges;
   for (int c = tid; c < s.fg; c += n_threads)
-    of[p.at[B_GLOBAL] + (int64_t)m * s.fg + c] = fits ? s.global_features[gi * s.fg + c] : 0.f;
-  if (!fits) return;
+    of[p.at[B_GLOBAL] + (int64_t)m * s.fg + c] = en.fits ? s.global_features[en.idx * s.fg + c] : 0.f;
+  if (!en.fits) return;
+  const int64_t vp = en.ap, ep = en.bp, nv = en.na, ne = en.nb;
   const int k = s.undirected ? 2 : 1;
-  for (int64_t i = tid; i < nv; i += n_threads) o[p.at[B_NODE_GRAPH] + v0 + i] = m;
+  fill_words(o + p.at[B_NODE_GRAPH] + v0, nv, m, tid, n_threads);
   copy_add(o + p.at[B_INC_PTR] + v0, s.inc_start + vp, nv, k * e0, tid, n_threads);
   copy_add(o + p.at[B_SRC] + e0, s.src + ep, ne, v0, tid, n_threads);
   copy_add(o + p.at[B_DST] + e0, s.dst + ep, ne, v0, tid, n_threads);
@@ -115,29 +78,16 @@ __host__ __device__ inline void collate_graph(const GnCollateArgs& p, int m, int
   copy_rows(of + p.at[B_EDGE_ATTR] + (int64_t)e0 * s.fe, s.edge_features + ep * s.fe, ne * s.fe, tid, n_threads);
 }
 
-// What no graph owns: the closing entries of the four offset lists and the (at most three) zero words behind a block
+// What no graph owns: the closing entries of the four offset lists and the pad words
 __host__ __device__ inline void collate_tail(const GnCollateArgs& p, int tid, int n_threads) {
   if (tid == 0) {
-    p.out[p.at[B_NODE_PTR] + p.n_graphs] = p.n_nodes;
-    p.out[p.at[B_EDGE_PTR] + p.n_graphs] = p.n_edges;
-    p.out[p.at[B_INC_PTR] + p.n_nodes] = (p.set.undirected ? 2 : 1) * p.n_edges;
-    if (!p.set.undirected) p.out[p.at[B_OUT_PTR] + p.n_nodes] = p.n_edges;
+    p.out[p.at[B_NODE_PTR] + p.n] = p.n_a;
+    p.out[p.at[B_EDGE_PTR] + p.n] = p.n_b;
+    p.out[p.at[B_INC_PTR] + p.n_a] = (p.set.undirected ? 2 : 1) * p.n_b;
+    if (!p.set.undirected) p.out[p.at[B_OUT_PTR] + p.n_a] = p.n_b;
   }
-  // 4 slots per block: slot q of block b is the q-th word behind the block's data, if the block has that many pad words
-  for (int t = tid; t < 4 * kGnBlocks; t += n_threads) {
-    const int b = t / 4, q = t % 4;
-    if (p.at[b] >= 0 && q < (4 - p.size[b] % 4) % 4) p.out[p.at[b] + p.size[b] + q] = 0;
-  }
+  write_pads(p, tid, n_threads);
 }
-
-__global__ __launch_bounds__(kGnCollateThreads) void gn_collate_kernel(const GnCollateArgs p) {
-  const int m = blockIdx.x;
-  const int tid = threadIdx.x;
-  if (m == (int)gridDim.x - 1) collate_tail(p, tid, kGnCollateThreads);
-  if (m < p.n_graphs) collate_graph(p, m, tid, kGnCollateThreads);
-}
-
-inline bool aligned8(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 7u) == 0; }
 
 int fill_args(GnCollateArgs& p, const char* what, const gcmi_gn_set* set, const int32_t* plan, int32_t n_graphs,
               int32_t n_nodes, int32_t n_edges, int32_t* out, int64_t out_words) {
@@ -165,9 +115,7 @@ int fill_args(GnCollateArgs& p, const char* what, const gcmi_gn_set* set, const 
   p = GnCollateArgs{};
   p.set = s;
   p.set.undirected = s.undirected ? 1 : 0;
-  p.plan = plan;
-  p.n_graphs = n_graphs, p.n_nodes = n_nodes, p.n_edges = n_edges;
-  p.out = out;
+  p.plan = plan, p.n = n_graphs, p.n_a = n_nodes, p.n_b = n_edges, p.out = out;
   p.end = gn_collate_layout(n_graphs, n_nodes, n_edges, s.undirected != 0, s.fn, s.fe, s.fg, p.at, p.size);
   GCMI_CHECK_ARG(out_words == p.end, "%s: the output buffer holds %lld words, the layout has %lld", what,
                  (long long)out_words, (long long)p.end);
@@ -194,20 +142,14 @@ int gcmi_gn_collate(const gcmi_gn_set* set, const int32_t* d_plan, int32_t n_gra
                     int32_t* d_out, int64_t out_words, void* stream) {
   GnCollateArgs p;
   const int rc = fill_args(p, "gn_collate", set, d_plan, n_graphs, n_nodes, n_edges, d_out, out_words);
-  if (rc != GCMI_OK) return rc;
-  hipLaunchKernelGGL(gn_collate_kernel, dim3(n_graphs), dim3(kGnCollateThreads), 0, static_cast<hipStream_t>(stream), p);
-  GCMI_CHECK_LAUNCH("gn_collate");
-  return GCMI_OK;
+  return rc != GCMI_OK ? rc : collate_set_launch(p, n_graphs, stream, "gn_collate");
 }
 
 int gcmi_gn_collate_host(const gcmi_gn_set* set, const int32_t* plan, int32_t n_graphs, int32_t n_nodes, int32_t n_edges,
                          int32_t* out, int64_t out_words) {
   GnCollateArgs p;
   const int rc = fill_args(p, "gn_collate_host", set, plan, n_graphs, n_nodes, n_edges, out, out_words);
-  if (rc != GCMI_OK) return rc;
-  collate_tail(p, 0, 1);
-  for (int m = 0; m < n_graphs; ++m) collate_graph(p, m, 0, 1);
-  return GCMI_OK;
+  return rc != GCMI_OK ? rc : collate_set_host(p);
 }
 
 }  // extern "C"

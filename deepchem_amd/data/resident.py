@@ -182,3 +182,46 @@ class ResidentMolSet:
             n_feat = 75
         return DeviceBatch(feats, graph, n_sel if n_samples is None else n_samples, n_feat,
                            small_int_features=self.small_int)
+
+
+class ResidentGraphSet(object):
+    """A graph set in device memory, uploaded once per dataset, with the batches collated there: ``batch(idx)`` is
+    O(len(idx)) work on the host -- the two counts of every selected item (atoms and bonds, nodes and edges), their prefix
+    sums, one pinned staging buffer ``[idx ; off_a ; off_b]`` in one copy -- and a kernel of csrc/collate_set.h writes the
+    packed batch buffer from ``arrays``.  A subclass states ``arrays_of(graphs)`` and ``bytes_needed(graphs)`` (static),
+    ``_select(idx)`` (the validated int64 indices), ``_counts()`` (the two per-item count arrays and the factor on the
+    second total in the 2^31 check), ``_too_large`` (that check's message) and ``_collate(idx, plan, n, total_a,
+    total_b)`` (the launch and the batch around its buffer).  ``device`` may be the CPU: the arrays then stay there, for
+    ``plan`` and the host twin of the kernel."""
+
+    def __init__(self, graphs, device):
+        self.graphs, self.device = graphs, torch.device(device)
+        self.host_arrays = self.arrays_of(graphs)
+        self.arrays = {k: torch.from_numpy(a).to(self.device) for k, a in self.host_arrays.items()}
+        self.nbytes = self.bytes_needed(graphs)
+
+    def plan(self, idx, pinned: bool = False):
+        """``(plan, total_a, total_b)``: the int32 words ``[idx ; off_a ; off_b]`` of a batch (a torch tensor, in pinned
+        memory if asked) and its totals.  O(len(idx)); an index outside the set is a ``ValueError``."""
+        sel = self._select(idx)
+        n = sel.size
+        count_a, count_b, factor = self._counts()
+        ca, cb = count_a[sel], count_b[sel]
+        total_a, total_b = int(ca.sum()), int(cb.sum())
+        if max(n, total_a, factor * total_b) > 2 ** 31 - 2:
+            raise ValueError(self._too_large)
+        staging = torch.empty(3 * n + 2, dtype=torch.int32, pin_memory=pinned)
+        words = staging.numpy()
+        words[:n] = sel
+        words[n], words[2 * n + 1] = 0, 0
+        np.cumsum(ca, out=words[n + 1:2 * n + 1])
+        np.cumsum(cb, out=words[2 * n + 2:])
+        return staging, total_a, total_b
+
+    def batch(self, idx):
+        """The batch of the items ``idx`` (in order, repeats allowed), collated on the current stream."""
+        if self.device.type != "cuda":
+            raise ValueError("%s.batch: the set is not on a GPU (there is no CPU path)" % type(self).__name__)
+        staging, total_a, total_b = self.plan(idx, pinned=True)
+        n = (staging.numel() - 2) // 3
+        return self._collate(idx, staging.to(self.device, non_blocking=True), n, total_a, total_b)

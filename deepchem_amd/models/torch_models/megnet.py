@@ -14,7 +14,6 @@ blocks run on ``csrc/megnet.hip`` and the two readouts on the set2set kernels (t
 anything the native route declines, the same batch runs through torch ops in the reference's order (the TORCH ROUTE).
 ``model.last_route`` says which route the last batch took; ``MEGNetModel(..., route="torch")`` forces the second.
 """
-import os
 from typing import Optional
 
 import numpy as np
@@ -23,10 +22,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from deepchem_amd import ops
-from deepchem_amd.data.datasets import NumpyDataset
+from deepchem_amd.data.resident import ResidentGraphSet
 from deepchem_amd.models.losses import L2Loss, SparseSoftmaxCrossEntropy
 from deepchem_amd.models.torch_models.dmpnn import _ranges
 from deepchem_amd.models.torch_models.megnet_layers import GraphNetwork, Set2Set
+from deepchem_amd.models.torch_models.resident_collate import ResidentCollateMixin, check_collate
 from deepchem_amd.models.torch_models.torch_model import TorchModel
 
 
@@ -205,20 +205,13 @@ class MegnetGraphSet(object):
         return made
 
 
-class ResidentMegnetSet(object):
-    """A ``MegnetGraphSet`` in device memory, uploaded once per dataset; ``batch(idx)`` is then O(n_graphs) work on the
-    host -- the counts of the selected graphs, their two prefix sums, one pinned staging buffer ``[graph_idx ; node_off ;
-    edge_off]`` in one copy -- and ``gcmi_gn_collate`` writes the packed batch buffer on the device, the same bytes
-    ``MegnetGraphSet.batch(idx, device)`` uploads.  The arrays are ``ops.GN_SET_ARRAYS`` (undirected: without the
-    ``out_*`` lists); the per-graph counts stay on the host.  No check per batch: see ``MegnetGraphSet``.
+class ResidentMegnetSet(ResidentGraphSet):
+    """A ``MegnetGraphSet`` in device memory (``ResidentGraphSet``): the plan is ``[graph_idx ; node_off ; edge_off]`` and
+    ``gcmi_gn_collate`` writes the packed batch buffer, the same bytes ``MegnetGraphSet.batch(idx, device)`` uploads.  The
+    arrays are ``ops.GN_SET_ARRAYS`` (undirected: without the ``out_*`` lists).  No check per batch: see
+    ``MegnetGraphSet``.  On the CPU device: for ``plan`` and ``ops.gn_collate_host``."""
 
-    ``device`` may be the CPU: the arrays then stay there, for ``plan`` and ``ops.gn_collate_host``."""
-
-    def __init__(self, graphs: MegnetGraphSet, device):
-        self.graphs, self.device = graphs, torch.device(device)
-        self.host_arrays = self.arrays_of(graphs)
-        self.arrays = {k: torch.from_numpy(a).to(self.device) for k, a in self.host_arrays.items()}
-        self.nbytes = self.bytes_needed(graphs)
+    _too_large = "GnGraph: too many edges for 32-bit lists"
 
     @staticmethod
     def bytes_needed(graphs: MegnetGraphSet) -> int:
@@ -232,32 +225,15 @@ class ResidentMegnetSet(object):
         names = [k for k in ops.GN_SET_ARRAYS if hasattr(graphs, k)]
         return {k: np.ascontiguousarray(getattr(graphs, k)) for k in names}
 
-    def plan(self, idx, pinned: bool = False):
-        """``(plan, n_nodes, n_edges)``: the int32 words ``[graph_idx ; node_off ; edge_off]`` of a batch (a torch
-        tensor, in pinned memory if asked) and its totals.  O(n_graphs); a graph index outside the set, or no graph at
-        all, is a ``ValueError``."""
-        sel = self.graphs._select(idx)
-        n = sel.size
-        nv, ne = self.graphs.n_nodes_of[sel], self.graphs.n_edges_of[sel]
-        n_nodes, n_edges = int(nv.sum()), int(ne.sum())
-        if max(n, n_nodes, (2 if self.graphs.undirected else 1) * n_edges) > 2 ** 31 - 2:
-            raise ValueError("GnGraph: too many edges for 32-bit lists")
-        staging = torch.empty(3 * n + 2, dtype=torch.int32, pin_memory=pinned)
-        words = staging.numpy()
-        words[:n] = sel
-        words[n], words[2 * n + 1] = 0, 0
-        np.cumsum(nv, out=words[n + 1:2 * n + 1])
-        np.cumsum(ne, out=words[2 * n + 2:])
-        return staging, n_nodes, n_edges
+    def _select(self, idx) -> np.ndarray:
+        return self.graphs._select(idx)  # (no graph at all is a ``ValueError`` too)
 
-    def batch(self, idx) -> MegnetBatch:
-        """The batch of the graphs ``idx`` (in order, repeats allowed), collated on the current stream."""
-        if self.device.type != "cuda":
-            raise ValueError("ResidentMegnetSet.batch: the set is not on a GPU (there is no CPU path)")
-        staging, n_nodes, n_edges = self.plan(idx, pinned=True)
-        n = (staging.numel() - 2) // 3
+    def _counts(self):
+        return self.graphs.n_nodes_of, self.graphs.n_edges_of, 2 if self.graphs.undirected else 1
+
+    def _collate(self, idx, plan, n, n_nodes, n_edges) -> MegnetBatch:
         und = self.graphs.undirected
-        words = ops.gn_collate(self.arrays, und, staging.to(self.device, non_blocking=True), n, n_nodes, n_edges)
+        words = ops.gn_collate(self.arrays, und, plan, n, n_nodes, n_edges)
         return MegnetBatch.from_device(words, n, n_nodes, n_edges, und, self.graphs.widths)
 
 
@@ -335,7 +311,7 @@ class MEGNet(nn.Module):
         return out
 
 
-class MEGNetModel(TorchModel):
+class MEGNetModel(ResidentCollateMixin, TorchModel):
     """MatErials Graph Network for molecules and crystals, on datasets of ``GraphData`` with ``global_features``."""
 
     def __init__(self, n_node_features: int = 32, n_edge_features: int = 32, n_global_features: int = 32,
@@ -344,8 +320,7 @@ class MEGNetModel(TorchModel):
                  collate: str = "auto", **kwargs):
         if route not in ("auto", "torch"):
             raise ValueError("route must be 'auto' or 'torch'")
-        if collate not in ("auto", "host", "device"):
-            raise ValueError("collate must be 'auto', 'host' or 'device' (got %r)" % (collate,))
+        self.collate = check_collate(collate)
         model = MEGNet(n_node_features=n_node_features, n_edge_features=n_edge_features,
                        n_global_features=n_global_features, n_blocks=n_blocks, is_undirected=is_undirected,
                        residual_connection=residual_connection, mode=mode, n_classes=n_classes, n_tasks=n_tasks)
@@ -355,9 +330,6 @@ class MEGNetModel(TorchModel):
         else:
             loss, output_types = SparseSoftmaxCrossEntropy(), ['prediction', 'loss']
         super(MEGNetModel, self).__init__(model, loss=loss, output_types=output_types, **kwargs)
-        self.collate = collate
-        self._graph_set = None  # (the X array it was built from, the mode, MegnetGraphSet)
-        self._resident = None   # (that X array, the mode, ResidentMegnetSet or the reason why there is none)
 
     @property
     def last_route(self):
@@ -369,85 +341,33 @@ class MEGNetModel(TorchModel):
             raise ValueError("MEGNetModel: node, edge and global widths %s, the model was built for %s" %
                              (tuple(got), (m.n_node_features, m.n_edge_features, m.n_global_features)))
 
-    def graph_set(self, X) -> MegnetGraphSet:
-        """The flat arrays of ``X`` (an array of ``GraphData``) in the model's mode, kept until another array is asked
-        for.  Widths other than the model's: today's ``ValueError``, once per set."""
-        held, mode = self._graph_set, bool(self.model.is_undirected)
-        if held is None or held[0] is not X or held[1] != mode:
-            made = MegnetGraphSet(X, mode)
-            self._check_widths(made.widths)
-            self._graph_set = (X, mode, made)
-        return self._graph_set[2]
+    # what ResidentCollateMixin asks of a model
+    resident_set_class, _name = ResidentMegnetSet, "MEGNetModel"
 
-    def _device_collate_refusal(self) -> Optional[str]:
-        """What, apart from the dataset, keeps the batches from being collated on the device; None: nothing."""
-        if self.device.type != "cuda":
-            return "the model is on %s, not on a GPU" % self.device
-        if self.model.route == "torch":
-            return "route='torch' runs plain torch, the device collation belongs to the native route"
-        if os.environ.get("GCMI_RESIDENT_SET", "1") == "0":
-            return "GCMI_RESIDENT_SET=0 switches resident sets off"
-        return None
+    def _device_collate_min(self) -> int:
+        return MEGNET_DEVICE_COLLATE_MIN
 
-    def _resident_for(self, X):
-        """The ``ResidentMegnetSet`` of ``X``, uploaded once and kept until another array is asked for -- or, as a
-        string, why there is none: the set must fit into a quarter of the device memory that is free when it is built."""
-        held, mode = self._resident, bool(self.model.is_undirected)
-        if held is None or held[0] is not X or held[1] != mode:
-            graphs = self.graph_set(X)
-            need = ResidentMegnetSet.bytes_needed(graphs)
-            free = torch.cuda.mem_get_info(self.device)[0] if self.device.type == "cuda" else need * 4
-            if need > free // 4:
-                made = "the set needs %d bytes, more than a quarter of the %d free on the device" % (need, free)
-            else:
-                made = ResidentMegnetSet(graphs, self.device)
-            self._resident = (X, mode, made)
-        return self._resident[2]
+    def _set_key(self) -> tuple:
+        return (bool(self.model.is_undirected),)
 
-    def resident_set(self, X) -> ResidentMegnetSet:
-        """The graphs of ``X`` in device memory (cached); a ``ValueError`` where the set does not fit there."""
-        made = self._resident_for(X)
-        if isinstance(made, str):
-            raise ValueError("MEGNetModel: no resident graph set: " + made)
+    def _new_graph_set(self, X) -> MegnetGraphSet:
+        """In the model's mode.  Widths other than the model's: ``_prepare_batch``'s ``ValueError``, once per set."""
+        made = MegnetGraphSet(X, bool(self.model.is_undirected))
+        self._check_widths(made.widths)
         return made
 
-    def _route(self, X) -> Optional[ResidentMegnetSet]:
-        """The resident set that collates the batches of ``X`` on the device, or None: the host collates them."""
-        if self.collate == "host":
-            return None
-        why = self._device_collate_refusal()
-        if why is None:
-            if self.collate == "auto" and self.batch_size < MEGNET_DEVICE_COLLATE_MIN:
-                return None  # (a preference, not an obstacle: collate="device" goes below it)
-            made = self._resident_for(X)
-            if not isinstance(made, str):
-                return made
-            why = made
-        if self.collate == "device":
-            raise ValueError("MEGNetModel(collate='device'): " + why)
+    def _own_refusal(self) -> Optional[str]:
+        if self.model.route == "torch":
+            return "route='torch' runs plain torch, the device collation belongs to the native route"
         return None
+
+    def _host_batch(self, graphs: MegnetGraphSet, idx) -> MegnetBatch:
+        return graphs.batch(idx, self.device)
 
     def _batch_generator(self, dataset, epochs: int = 1, mode: str = 'fit', deterministic: bool = True,
                          pad_batches: bool = True):
-        """For a ``NumpyDataset`` of graphs: the graph INDICES follow the dataset's own batch walk (same order, same
-        shuffles from ``np.random``), a batch is an index gather over the cached flat arrays: by numpy
-        (``MegnetGraphSet.batch``) or, where ``_route`` says so, by the device over the resident set.  Anything else:
-        ``default_generator``."""
-        X = getattr(dataset, "X", None) if isinstance(dataset, NumpyDataset) else None
-        if not (isinstance(X, np.ndarray) and X.dtype == object and X.ndim == 1):
-            if self.collate == "device":
-                raise ValueError("MEGNetModel(collate='device'): the dataset is not a NumpyDataset of GraphData")
-            yield from self.default_generator(dataset, epochs=epochs, mode=mode, deterministic=deterministic,
-                                              pad_batches=pad_batches)
-            return
-        graphs = self.graph_set(X)
-        resident = self._route(X)
-        index_set = NumpyDataset(np.arange(X.shape[0]), dataset.y, dataset.w, dataset.ids)
-        for _ in range(epochs):
-            for (idx, y_b, w_b, _ids) in index_set.iterbatches(batch_size=self.batch_size, deterministic=deterministic,
-                                                               pad_batches=pad_batches):
-                made = graphs.batch(idx, self.device) if resident is None else resident.batch(idx)
-                yield (made, [y_b], [w_b])
+        """``ResidentCollateMixin._collated_batches``."""
+        return self._collated_batches(dataset, epochs, mode, deterministic, pad_batches)
 
     def _prepare_batch(self, batch):
         """The graphs of ``default_generator`` (an object array nested in a list) become one ``MegnetBatch``."""

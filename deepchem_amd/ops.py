@@ -1050,6 +1050,40 @@ class MatAttentionFn(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None
 
 
+# ------------------------------------------------------------------ collation from a resident graph set
+def _batch_layout(entry: str, sizes, blocks, shapes):
+    """``(words, {block: (offset, shape)})`` of a packed batch buffer as the C routine ``entry`` places its ``blocks``
+    (``-1``: a block the mode lacks, left out)."""
+    off = (ctypes.c_int64 * len(blocks))()
+    words = int(getattr(_lib.load(), entry)(*[int(v) for v in sizes], off))
+    if words < 0:
+        raise _lib.GcmiError("%s: %s" % (entry, _lib.load().gcmi_last_error().decode()))
+    return words, {b: (int(off[i]), shapes[i]) for i, b in enumerate(blocks) if off[i] >= 0}
+
+
+def _check_set(arrays, offsets, on_device: bool, what: str):
+    """Every array of a resident set -- the ``offsets`` arrays int64, ``*features`` float32, the rest int32 -- is a
+    contiguous CUDA tensor (``_lib.GcmiError``) or, for the host routine, a C-contiguous numpy array (``ValueError``)."""
+    lib = torch if on_device else np
+    for k, a in arrays.items():
+        want = lib.int64 if k in offsets else lib.float32 if k.endswith("features") else lib.int32
+        if on_device:
+            if not (torch.is_tensor(a) and a.is_cuda and a.is_contiguous() and a.dtype == want):
+                raise _lib.GcmiError("%s: %s must be a contiguous %s CUDA tensor" % (what, k, want))
+        elif not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == want):
+            raise ValueError("%s: %s must be a C-contiguous %s array" % (what, k, np.dtype(want)))
+
+
+def _check_host_plan(plan, n: int, noun: str, what: str):
+    if not (isinstance(plan, np.ndarray) and plan.dtype == np.int32 and plan.flags.c_contiguous and plan.size == 3 * n + 2):
+        raise ValueError("%s: plan must hold 3 * %s + 2 int32 words" % (what, noun))
+
+
+def _check_host_out(out, what: str):
+    if not (out.dtype == np.int32 and out.flags.c_contiguous and out.ndim == 1):
+        raise ValueError("%s: out must be a contiguous int32 vector" % what)
+
+
 # ------------------------------------------------------------------ graph-network block (MEGNet)
 GN_WIDTH, GN_ROWS_PER_WG = 32, 32
 
@@ -1058,7 +1092,7 @@ GN_INT_BLOCKS = ("src", "dst", "node_graph", "node_ptr", "edge_ptr", "inc_ptr", 
                  "out_edge", "out_other")
 GN_FLOAT_BLOCKS = ("x", "edge_attr", "global_features")
 GN_BATCH_BLOCKS = GN_INT_BLOCKS + GN_FLOAT_BLOCKS
-# gn_collate_kernel: one workgroup of GN_COLLATE_THREADS threads per graph; a pass of the workgroup covers that many words
+# collate_set_kernel over the MEGNet args: one workgroup of GN_COLLATE_THREADS threads per graph; a pass of the workgroup covers that many words
 GN_COLLATE_THREADS = 256
 
 
@@ -1071,14 +1105,9 @@ def gn_batch_layout(n_graphs: int, n_nodes: int, n_edges: int, undirected: bool,
     if min(sizes) < 0 or max(n_graphs, n_nodes, 2 * n_edges) > 2 ** 31 - 2 or max(sizes[3:]) > 2 ** 31 - 1:
         raise ValueError("gn_batch_layout: sizes must be within [0, 2^31): %r" % (sizes,))
     G, N, E, k = int(n_graphs), int(n_nodes), int(n_edges), 2 if undirected else 1
-    off = (ctypes.c_int64 * len(GN_BATCH_BLOCKS))()
-    words = int(_lib.load().gcmi_gn_collate_words(G, N, E, 1 if undirected else 0, int(n_node_features),
-                                                  int(n_edge_features), int(n_global_features), off))
-    if words < 0:
-        raise _lib.GcmiError("gcmi_gn_collate_words: %s" % _lib.load().gcmi_last_error().decode())
     shapes = ((E,), (E,), (N,), (G + 1,), (G + 1,), (N + 1,), (k * E,), (k * E,), (N + 1,), (E,), (E,),
               (N, int(n_node_features)), (E, int(n_edge_features)), (G, int(n_global_features)))
-    return words, {b: (int(off[i]), shapes[i]) for i, b in enumerate(GN_BATCH_BLOCKS) if off[i] >= 0}
+    return _batch_layout("gcmi_gn_collate_words", (G, N, E, 1 if undirected else 0) + sizes[3:], GN_BATCH_BLOCKS, shapes)
 
 
 class GnGraph:
@@ -1240,10 +1269,6 @@ def _gn_set_desc(arrays, undirected: bool, n_graphs: int, n_nodes: int, n_edges:
     return d, widths
 
 
-def _gn_set_dtype(k, i32, i64, f32):
-    return i64 if k in ("node_ptr", "edge_ptr") else f32 if k.endswith("features") else i32
-
-
 def gn_collate(arrays, undirected: bool, plan: torch.Tensor, n_graphs: int, n_nodes: int, n_edges: int,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``gcmi_gn_collate``: the packed batch buffer (int32 words, ``gn_batch_layout``) of the graphs named by ``plan`` =
@@ -1251,10 +1276,7 @@ def gn_collate(arrays, undirected: bool, plan: torch.Tensor, n_graphs: int, n_no
     (``GN_SET_ARRAYS``: contiguous CUDA tensors, the two offset arrays int64, indices int32, features float32 2-D).
     The graph indices must have been validated by the caller: the kernel skips a bad one, it does not report it.
     ``out``: an int32 CUDA vector of exactly the layout's words to write into."""
-    for k, t in arrays.items():
-        want = _gn_set_dtype(k, torch.int32, torch.int64, torch.float32)
-        if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == want):
-            raise _lib.GcmiError("gn_collate: %s must be a contiguous %s CUDA tensor" % (k, want))
+    _check_set(arrays, ("node_ptr", "edge_ptr"), True, "gn_collate")
     d, widths = _gn_set_desc(arrays, undirected, n_graphs, n_nodes, n_edges, lambda t: t.data_ptr(), "gn_collate")
     _i32vec(plan, "plan", 3 * n_graphs + 2)
     words, _ = gn_batch_layout(n_graphs, n_nodes, n_edges, undirected, *widths)
@@ -1269,19 +1291,13 @@ def gn_collate_host(arrays, undirected: bool, plan: np.ndarray, n_graphs: int, n
                     out: Optional[np.ndarray] = None) -> np.ndarray:
     """``gcmi_gn_collate_host``: the same routine over numpy arrays, for tests without a GPU.  ``out``: a 16-byte
     aligned int32 vector of exactly the layout's words to write into."""
-    for k, a in arrays.items():
-        want = _gn_set_dtype(k, np.int32, np.int64, np.float32)
-        if not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == want):
-            raise ValueError("gn_collate_host: %s must be a C-contiguous %s array" % (k, np.dtype(want)))
+    _check_set(arrays, ("node_ptr", "edge_ptr"), False, "gn_collate_host")
     d, widths = _gn_set_desc(arrays, undirected, n_graphs, n_nodes, n_edges, lambda a: a.ctypes.data, "gn_collate_host")
-    if not (isinstance(plan, np.ndarray) and plan.dtype == np.int32 and plan.flags.c_contiguous and
-            plan.size == 3 * n_graphs + 2):
-        raise ValueError("gn_collate_host: plan must hold 3 * n_graphs + 2 int32 words")
+    _check_host_plan(plan, n_graphs, "n_graphs", "gn_collate_host")
     words, _ = gn_batch_layout(n_graphs, n_nodes, n_edges, undirected, *widths)
     if out is None:
         out = torch.empty(words, dtype=torch.int32).numpy()  # (torch allocates 64-byte aligned)
-    if not (out.dtype == np.int32 and out.flags.c_contiguous and out.ndim == 1):
-        raise ValueError("gn_collate_host: out must be a contiguous int32 vector")
+    _check_host_out(out, "gn_collate_host")
     _lib.call("gcmi_gn_collate_host", ctypes.byref(d), _vp(plan.ctypes.data), n_graphs, n_nodes, n_edges,
               _vp(out.ctypes.data), out.size)
     return out
@@ -1534,7 +1550,7 @@ def dmpnn_update_fwd(x: torch.Tensor, inp: torch.Tensor, weight: torch.Tensor, o
 
 DMPNN_BATCH_BLOCKS = ("mol_ptr", "out_ptr", "bond_src", "rev", "atom_membership", "atoms_per_mol", "atom_features",
                       "f_ini_atoms_bonds", "global_features")
-# dmpnn_collate_kernel: one workgroup of DMPNN_COLLATE_THREADS threads per molecule; a pass of the workgroup covers that
+# collate_set_kernel over the D-MPNN args: one workgroup of DMPNN_COLLATE_THREADS threads per molecule; a pass of the workgroup covers that
 # many per-atom / per-bond words and flat atom-row words, and DMPNN_COLLATE_ROWS_PER_PASS f_ini rows (one per wave)
 DMPNN_COLLATE_MOLS_PER_WORKGROUP = 1
 DMPNN_COLLATE_THREADS = 256
@@ -1547,13 +1563,9 @@ def dmpnn_batch_layout(n_mols: int, n_atoms: int, n_bonds: int, atom_fdim: int, 
     sizes = (n_mols, n_atoms, n_bonds, atom_fdim, bond_fdim, global_fdim)
     if min(sizes) < 0 or max(sizes) > 2 ** 31 - 1:
         raise ValueError("dmpnn_batch_layout: sizes must be within [0, 2^31): %r" % (sizes,))
-    off = (ctypes.c_int64 * len(DMPNN_BATCH_BLOCKS))()
-    words = int(_lib.load().gcmi_dmpnn_collate_words(*[int(s) for s in sizes], off))
-    if words < 0:
-        raise _lib.GcmiError("gcmi_dmpnn_collate_words: %s" % _lib.load().gcmi_last_error().decode())
     shapes = ((n_mols + 1,), (n_atoms + 1,), (n_bonds,), (n_bonds,), (n_atoms,), (n_mols, 1), (n_atoms, atom_fdim),
               (n_bonds, atom_fdim + bond_fdim), (n_mols, global_fdim))
-    return words, {k: (int(off[i]), shapes[i]) for i, k in enumerate(DMPNN_BATCH_BLOCKS)}
+    return _batch_layout("gcmi_dmpnn_collate_words", sizes, DMPNN_BATCH_BLOCKS, shapes)
 
 
 DMPNN_SET_ARRAYS = ("atom_ptr", "bond_ptr", "atom_features", "bond_features", "sorted_src", "sorted_rev", "out_start",
@@ -1579,12 +1591,7 @@ def dmpnn_collate(arrays, plan: torch.Tensor, n_mols: int, n_atoms: int, n_bonds
     (``DMPNN_SET_ARRAYS``: contiguous CUDA tensors, the two offset arrays int64, indices int32, features float32 2-D).
     The molecule indices must have been validated by the caller: the kernel skips a bad one, it does not report it."""
     M, fa, fb, fg = _dmpnn_collate_sizes(arrays, n_mols, n_atoms, n_bonds)
-    want = {"atom_ptr": torch.int64, "bond_ptr": torch.int64, "sorted_src": torch.int32, "sorted_rev": torch.int32,
-            "out_start": torch.int32}
-    for k in DMPNN_SET_ARRAYS:
-        t = arrays[k]
-        if not (torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == want.get(k, torch.float32)):
-            raise _lib.GcmiError("dmpnn_collate: %s must be a contiguous %s CUDA tensor" % (k, want.get(k, torch.float32)))
+    _check_set({k: arrays[k] for k in DMPNN_SET_ARRAYS}, ("atom_ptr", "bond_ptr"), True, "dmpnn_collate")
     _i32vec(plan, "plan", 3 * n_mols + 2)
     words, _ = dmpnn_batch_layout(n_mols, n_atoms, n_bonds, fa, fb, fg)
     out = torch.empty(words, dtype=torch.int32, device=plan.device)
@@ -1598,20 +1605,12 @@ def dmpnn_collate_host(arrays, plan: np.ndarray, n_mols: int, n_atoms: int, n_bo
     """``gcmi_dmpnn_collate_host``: the same routine over numpy arrays, for tests without a GPU.  ``out``: an int32
     vector to write into (at least the layout's words)."""
     M, fa, fb, fg = _dmpnn_collate_sizes(arrays, n_mols, n_atoms, n_bonds)
-    want = {"atom_ptr": np.int64, "bond_ptr": np.int64, "sorted_src": np.int32, "sorted_rev": np.int32,
-            "out_start": np.int32}
-    for k in DMPNN_SET_ARRAYS:
-        a = arrays[k]
-        if not (isinstance(a, np.ndarray) and a.flags.c_contiguous and a.dtype == want.get(k, np.float32)):
-            raise ValueError("dmpnn_collate_host: %s must be a C-contiguous %s array" % (k, np.dtype(want.get(k, np.float32))))
-    if not (isinstance(plan, np.ndarray) and plan.dtype == np.int32 and plan.flags.c_contiguous and
-            plan.size == 3 * n_mols + 2):
-        raise ValueError("dmpnn_collate_host: plan must hold 3 * n_mols + 2 int32 words")
+    _check_set({k: arrays[k] for k in DMPNN_SET_ARRAYS}, ("atom_ptr", "bond_ptr"), False, "dmpnn_collate_host")
+    _check_host_plan(plan, n_mols, "n_mols", "dmpnn_collate_host")
     words, _ = dmpnn_batch_layout(n_mols, n_atoms, n_bonds, fa, fb, fg)
     if out is None:
         out = np.empty(words, np.int32)
-    if not (out.dtype == np.int32 and out.flags.c_contiguous and out.ndim == 1):
-        raise ValueError("dmpnn_collate_host: out must be a contiguous int32 vector")
+    _check_host_out(out, "dmpnn_collate_host")
     _lib.call("gcmi_dmpnn_collate_host", *[_vp(arrays[k].ctypes.data) for k in DMPNN_SET_ARRAYS], M, fa, fb, fg,
               _vp(plan.ctypes.data), n_mols, n_atoms, n_bonds, _vp(out.ctypes.data), out.size)
     return out

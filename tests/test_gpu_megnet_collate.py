@@ -159,7 +159,7 @@ def test_auto_switches_to_the_device_at_the_threshold(dataset96, monkeypatch):
     m = MEGNetModel(batch_size=at, device=DEV)
     got = routes(m, dataset96)
     assert got == ["device"] * len(got) and len(got) == -(-96 // at)
-    assert isinstance(m._resident[2], ResidentMegnetSet) and m.resident_set(dataset96.X) is m._resident[2]
+    assert isinstance(m._resident[1], ResidentMegnetSet) and m.resident_set(dataset96.X) is m._resident[1]
     assert set(routes(MEGNetModel(batch_size=at, device=DEV, collate="host"), dataset96)) == {"host"}
     assert set(routes(MEGNetModel(batch_size=at, device=DEV, route="torch"), dataset96)) == {"host"}
     assert set(routes(MEGNetModel(batch_size=8, device=DEV, collate="device"), dataset96)) == {"device"}  # below, on request
@@ -174,7 +174,7 @@ def test_auto_switches_to_the_device_at_the_threshold(dataset96, monkeypatch):
     with pytest.raises(ValueError, match="more than a quarter"):
         routes(MEGNetModel(batch_size=at, device=DEV, collate="device"), dataset96)
     auto = MEGNetModel(batch_size=at, device=DEV)
-    assert set(routes(auto, dataset96)) == {"host"} and isinstance(auto._resident[2], str)
+    assert set(routes(auto, dataset96)) == {"host"} and isinstance(auto._resident[1], str)
 
 
 def test_the_set_is_built_once(dataset96, monkeypatch):
