@@ -259,6 +259,13 @@ _SIGNATURES = {
     "gcmi_gn_seg_spread": [_P, c_int32, c_int32, c_int32, c_int32, _P, c_int64, _P, c_int64, _P],
     "gcmi_gn_collate": [_GNS, _P, c_int32, c_int32, c_int32, _P, c_int64, _P],
     "gcmi_gn_collate_host": [_GNS, _P, c_int32, c_int32, c_int32, _P, c_int64],
+    "gcmi_cg_stats": [_GN, _P, _P, c_int64, _P, c_int64, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P, c_int64, _P],
+    "gcmi_cg_conv_fwd": [_GN, _P, _P, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P],
+    "gcmi_cg_bwd_stats": [_GN, _P, _P, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P,
+                          c_int64, _P],
+    "gcmi_cg_bwd_edges": [_GN, _P, _P, c_int64, _P, c_int64, c_int32, _P, _P, _P, _P, _P, c_int64, _P, c_int64, _P, _P,
+                          c_int64, _P, c_int64, _P, c_int64, _P],
+    "gcmi_cg_bwd_src": [_GN, _P, c_int64, c_int32, _P, c_int64, _P],
     "gcmi_dmpnn_message": [c_int32, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
     "gcmi_dmpnn_update_fwd": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int64,
                               _P, c_int64, _P],
@@ -300,7 +307,7 @@ _SIGNATURES = {
 EXPORTS = ["gcmi_version", "gcmi_last_error", "gcmi_model_workspace_floats", "gcmi_small_workspace_floats",
            "gcmi_task_head_scratch_floats", "gcmi_fwd_fused_scratch_floats", "gcmi_lamb_scratch_floats", "gcmi_metrics_workspace_bytes",
            "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout",
-           "gcmi_dmpnn_collate_words", "gcmi_gn_collate_words"] + sorted(_SIGNATURES)
+           "gcmi_dmpnn_collate_words", "gcmi_gn_collate_words", "gcmi_cg_workspace_floats"] + sorted(_SIGNATURES)
 
 _lib = None
 
@@ -348,6 +355,7 @@ def load():
         "gcmi_metrics_workspace_bytes": (c_int64, [c_int64, c_int32]),
         "gcmi_dmpnn_collate_words": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _I64P]),
         "gcmi_gn_collate_words": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _I64P]),
+        "gcmi_cg_workspace_floats": (c_int64, [c_int32, c_int32, c_int32]),
     }
     for name, (restype, argtypes) in special.items():
         if host_only and not hasattr(lib, name):

@@ -1477,6 +1477,156 @@ class GnSegSpreadFn(torch.autograd.Function):
         return gn_seg_reduce(rowmajor(dout), ptr, False), None, None
 
 
+# ------------------------------------------------------------------ crystal-graph convolution (CGCNN)
+CG_MIN_WIDTH, CG_MAX_WIDTH = 4, 128
+
+
+def cg_width_ok(hidden: int) -> bool:
+    """Whether csrc/cgcnn.hip covers the hidden width."""
+    return CG_MIN_WIDTH <= hidden <= CG_MAX_WIDTH and hidden % 4 == 0
+
+
+def _cg_graph(g, what: str) -> GnGraph:
+    g = _gn_graph(g, what)
+    if g.undirected:
+        raise _lib.GcmiError("%s: the graph must be a DIRECTED GnGraph (arriving and leaving lists)" % what)
+    return g
+
+
+def _cg_rows(t, name: str, rows: int, cols: int, ld: Optional[int] = None):
+    t = _mat(t, name, rows=rows, cols=cols)
+    if rows and (_ld(t) % 4 or t.data_ptr() % 16):
+        raise ValueError("%s: rows must be 16-byte aligned with a leading dimension of whole 16-byte pieces" % name)
+    if ld is not None and rows > 1 and _ld(t) != ld:
+        raise ValueError("%s: leading dimension %d, expected %d" % (name, _ld(t), ld))
+    return t
+
+
+def _cg_ld(t, cols: int) -> int:
+    return max(_ld(t), cols)  # (an empty or one-row tensor reports its width)
+
+
+def _cg_inputs(g, p, q, what: str):
+    """The leading arguments of every entry: graph, Ps, Pd, ldp, Q, ldq, H.  ``p`` = [Ps | Pd] (n_nodes, 4H)."""
+    g = _cg_graph(g, what)
+    if p.dim() != 2 or p.shape[1] % 4 or not cg_width_ok(p.shape[1] // 4):
+        raise ValueError("%s: the node projections must be one (n_nodes, 4H) matrix [Ps | Pd], H a multiple of 4 in "
+                         "[%d, %d]; got %s" % (what, CG_MIN_WIDTH, CG_MAX_WIDTH, tuple(p.shape)))
+    H = p.shape[1] // 4
+    p = _cg_rows(p, "P", g.n_nodes, 4 * H)
+    q = _cg_rows(q, "Q", g.n_edges, 2 * H)
+    return H, (ctypes.byref(g.ref), _ptr(p[:, :2 * H]), _ptr(p[:, 2 * H:]), _cg_ld(p, 4 * H), _ptr(q) if g.n_edges else None,
+               _cg_ld(q, 2 * H), H)
+
+
+def _cg_norm(H: int, mean, invstd, gamma, beta):
+    return tuple(_ptr(_vec(t, name, 2 * H)) for t, name in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma"), (beta, "beta")))
+
+
+def _cg_workspace(g: GnGraph, H: int, dev) -> torch.Tensor:
+    n = int(_lib.load().gcmi_cg_workspace_floats(g.n_nodes, g.n_edges, H))
+    return torch.empty(n, dtype=torch.float32, device=dev)
+
+
+def cg_stats(g: GnGraph, p, q, eps: float = 1e-5, momentum: float = 0.1, running_mean=None, running_var=None,
+             num_batches_tracked=None):
+    """(mean, invstd) of the columns of z[k] = Ps[src k] + Pd[dst k] + Q[k] over the edges (biased variance), z never
+    written; the running statistics (unbiased variance) and ``num_batches_tracked`` are updated in place when given."""
+    H, args = _cg_inputs(g, p, q, "cg_stats")
+    if g.n_edges < 2:
+        raise ValueError("cg_stats: the statistics need at least 2 edges, got %d" % g.n_edges)
+    _vec(running_mean, "running_mean", 2 * H)
+    _vec(running_var, "running_var", 2 * H)
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1 or
+                                            not num_batches_tracked.is_cuda):
+        raise ValueError("num_batches_tracked must be one int64 on the GPU")
+    stats = torch.empty((2, 2 * H), dtype=torch.float32, device=p.device)
+    ws = _cg_workspace(g, H, p.device)
+    _lib.call("gcmi_cg_stats", *args, float(eps), float(momentum), _ptr(stats[0]), _ptr(stats[1]), _ptr(running_mean),
+              _ptr(running_var), _ptr(num_batches_tracked), _ptr(ws), ws.numel(), _stream())
+    return stats[0], stats[1]
+
+
+def cg_conv_fwd(g: GnGraph, p, q, h, mean=None, invstd=None, gamma=None, beta=None) -> torch.Tensor:
+    """h' (n_nodes, H) = softplus(h + the gated messages summed over each arriving list); a zero row for an empty list."""
+    H, args = _cg_inputs(g, p, q, "cg_conv_fwd")
+    h = _cg_rows(h, "h", g.n_nodes, H)
+    out = torch.empty((g.n_nodes, H), dtype=torch.float32, device=p.device)
+    _lib.call("gcmi_cg_conv_fwd", *args, *_cg_norm(H, mean, invstd, gamma, beta), _ptr(h), _cg_ld(h, H), _ptr(out), H, _stream())
+    return out
+
+
+def cg_bwd_stats(g: GnGraph, p, q, hnew, dhnew, mean=None, invstd=None, gamma=None, beta=None) -> torch.Tensor:
+    """[sum of dzh | sum of dzh * xhat] over the edges, (4H,): dbeta and dgamma."""
+    H, args = _cg_inputs(g, p, q, "cg_bwd_stats")
+    hnew, dhnew = _cg_rows(hnew, "h'", g.n_nodes, H), _cg_rows(dhnew, "dh'", g.n_nodes, H)
+    sums = torch.empty(4 * H, dtype=torch.float32, device=p.device)
+    ws = _cg_workspace(g, H, p.device)
+    _lib.call("gcmi_cg_bwd_stats", *args, *_cg_norm(H, mean, invstd, gamma, beta), _ptr(hnew), _cg_ld(hnew, H), _ptr(dhnew),
+              _cg_ld(dhnew, H), _ptr(sums), _ptr(ws), ws.numel(), _stream())
+    return sums
+
+
+def cg_bwd_edges(g: GnGraph, p, q, hnew, dhnew, sums=None, mean=None, invstd=None, gamma=None, beta=None):
+    """(dP = [dPs | dPd] (n_nodes, 4H) with the dPd half written, dQ (n_edges, 2H), dpre (n_nodes, H)).  ``sums`` (from
+    ``cg_bwd_stats``): the BatchNorm backward of training mode; without, the statistics are constants."""
+    H, args = _cg_inputs(g, p, q, "cg_bwd_edges")
+    hnew, dhnew = _cg_rows(hnew, "h'", g.n_nodes, H), _cg_rows(dhnew, "dh'", g.n_nodes, H)
+    _vec(sums, "sums", 4 * H)
+    dev = p.device
+    dp = torch.empty((g.n_nodes, 4 * H), dtype=torch.float32, device=dev)
+    dq = torch.empty((g.n_edges, 2 * H), dtype=torch.float32, device=dev)
+    dpre = torch.empty((g.n_nodes, H), dtype=torch.float32, device=dev)
+    _lib.call("gcmi_cg_bwd_edges", *args, *_cg_norm(H, mean, invstd, gamma, beta), _ptr(hnew), _cg_ld(hnew, H), _ptr(dhnew),
+              _cg_ld(dhnew, H), _ptr(sums), _ptr(dq) if g.n_edges else None, 2 * H, _ptr(dp[:, 2 * H:]), 4 * H, _ptr(dpre), H,
+              _stream())
+    return dp, dq, dpre
+
+
+def cg_bwd_src(g: GnGraph, dq, dp) -> torch.Tensor:
+    """Writes dPs[v] = the sum of dQ over the leaving list of v into the first half of ``dp`` (n_nodes, 4H)."""
+    g = _cg_graph(g, "cg_bwd_src")
+    if dp.dim() != 2 or dp.shape[1] % 4 or not cg_width_ok(dp.shape[1] // 4):
+        raise ValueError("cg_bwd_src: dP must be (n_nodes, 4H)")
+    H = dp.shape[1] // 4
+    dp, dq = _cg_rows(dp, "dP", g.n_nodes, 4 * H), _cg_rows(dq, "dQ", g.n_edges, 2 * H)
+    _lib.call("gcmi_cg_bwd_src", ctypes.byref(g.ref), _ptr(dq) if g.n_edges else None, _cg_ld(dq, 2 * H), H, _ptr(dp[:, :2 * H]),
+              _cg_ld(dp, 4 * H), _stream())
+    return dp
+
+
+class CgConvFn(torch.autograd.Function):
+    """(P = [Ps | Pd] (n_nodes, 4H), Q (n_edges, 2H), h, mean, invstd, gamma, beta, graph, train) -> h'.  ``train``: mean
+    and invstd are this batch's statistics of z (``cg_stats``) and the backward differentiates through them; otherwise
+    they are constants (eval mode, or None without a BatchNorm).  Saved: P, Q and h' -- no tensor with E rows but Q."""
+
+    @staticmethod
+    def forward(ctx, p, q, h, mean, invstd, gamma, beta, g: GnGraph, train: bool):
+        p, q, h = _gn_aligned(p), _gn_aligned(q), _gn_aligned(h)
+        gamma = None if gamma is None else gamma.contiguous()
+        beta = None if beta is None else beta.contiguous()
+        out = cg_conv_fwd(g, p, q, h, mean, invstd, gamma, beta)
+        ctx.g, ctx.train = g, bool(train) and mean is not None
+        ctx.save_for_backward(p, q, out, mean, invstd, gamma, beta)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        p, q, out, mean, invstd, gamma, beta = ctx.saved_tensors
+        g, dout = ctx.g, _gn_aligned(dout)
+        norm = dict(mean=mean, invstd=invstd, gamma=gamma, beta=beta)
+        sums = dgamma = dbeta = None
+        H = out.shape[1]
+        if gamma is not None and g.n_edges:
+            sums = cg_bwd_stats(g, p, q, out, dout, **norm)
+            dbeta, dgamma = sums[:2 * H], sums[2 * H:]
+        elif gamma is not None:
+            dbeta, dgamma = torch.zeros_like(beta), torch.zeros_like(gamma)
+        dp, dq, dpre = cg_bwd_edges(g, p, q, out, dout, sums if ctx.train else None, **norm)
+        cg_bwd_src(g, dq, dp)
+        return dp, dq, dpre, None, None, dgamma, dbeta, None, None
+
+
 # ------------------------------------------------------------------ message passing
 # ------------------------------------------------------------------ D-MPNN
 DMPNN_MAX_DEGREE = 32

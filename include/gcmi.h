@@ -1150,6 +1150,55 @@ int gcmi_gn_collate(const gcmi_gn_set* set, const int32_t* d_plan, int32_t n_gra
 int gcmi_gn_collate_host(const gcmi_gn_set* set, const int32_t* plan, int32_t n_graphs, int32_t n_nodes, int32_t n_edges,
                          int32_t* out, int64_t out_words);
 
+/* ---------------------------------------------------------------- crystal-graph convolution of CGCNN (cgcnn.hip)
+ * One CGCNNLayer between its two products, over a DIRECTED gcmi_gn_graph on the device (undirected = 0; the arriving
+ * list inc_* and the leaving list out_*).  H = the hidden width, a multiple of 4 in [GCMI_CG_MIN_WIDTH,
+ * GCMI_CG_MAX_WIDTH].  With linear.weight split by columns into A_s | A_d | C:
+ *     Ps = h A_s^T, Pd = h A_d^T (n_nodes rows of 2H floats, two column blocks of one product: they share ldp),
+ *     Q = e C^T + b (n_edges rows of 2H floats),      z[k] = (Ps[src k] + Pd[dst k]) + Q[k]   -- never stored.
+ * Columns [0, H) of such a row are the gate half, [H, 2H) the message half.  The normalisation is
+ *     xhat = (z - mean) * invstd,  zh = xhat * gamma + beta      (vectors of 2H floats; NULL: 0, 1, 1, 0),
+ * the message m[k] = sigmoid(zh[k, :H]) * softplus(zh[k, H:]) and the new row
+ *     h'[v] = softplus(h[v] + sum over inc(v) of m[edge]),  a ZERO row where inc(v) is empty,
+ * softplus with beta 1 and threshold 20.  Every row pointer is 16-byte aligned with a leading dimension that is a
+ * multiple of 4 and at least the row's width; vectors are 16-byte aligned.
+ *   gcmi_cg_stats      mean and invstd = 1 / sqrt(biased variance + eps) of the columns of z over the n_edges >= 2
+ *                      rows: per-workgroup moments about a pivot row in double, combined in double in a fixed order.  With
+ *                      running_mean / running_var (optional, both or neither): r = (1 - momentum) r + momentum * (mean |
+ *                      unbiased variance); batches_tracked (optional, int64) is incremented.
+ *   gcmi_cg_conv_fwd   h' from h with the given normalisation (training: what gcmi_cg_stats wrote; eval: the running
+ *                      statistics).  n_edges = 0 is allowed.
+ *   gcmi_cg_bwd_stats  with dpre[v] = dh'[v] * sigmoid(h[v] + S[v]) recovered from h' itself (1 - exp(-h'); 0 for an
+ *                      empty list): sums = [sum of dzh (2H) | sum of dzh * xhat (2H)] over the edges, which are dbeta
+ *                      and dgamma.  n_edges >= 1.
+ *   gcmi_cg_bwd_edges  dQ[k] = dz[k], dPd[v] = sum over inc(v) of dz, dpre[v] (n_nodes rows of H floats: the gradient
+ *                      of h through the residual).  sums != NULL (training): dz = gamma invstd (dzh - sums_0 / E - xhat
+ *                      sums_1 / E); sums == NULL (eval, or no normalisation): dz = gamma invstd dzh.
+ *   gcmi_cg_bwd_src    dPs[v] = sum over out(v) of dQ[edge].
+ * The two statistics entries take a workspace of gcmi_cg_workspace_floats(n_nodes, n_edges, H) floats.  No atomics;
+ * every sum runs in list order or in an order the sizes alone fix: two calls agree bit for bit.                                     */
+#define GCMI_CG_MIN_WIDTH 4
+#define GCMI_CG_MAX_WIDTH 128
+int64_t gcmi_cg_workspace_floats(int32_t n_nodes, int32_t n_edges, int32_t H);
+int gcmi_cg_stats(const gcmi_gn_graph* g, const float* d_ps, const float* d_pd, int64_t ldp, const float* d_q, int64_t ldq,
+                  int32_t H, float eps, float momentum, float* d_mean, float* d_invstd, float* d_running_mean,
+                  float* d_running_var, int64_t* d_batches_tracked, float* d_workspace, int64_t workspace_floats,
+                  void* stream);
+int gcmi_cg_conv_fwd(const gcmi_gn_graph* g, const float* d_ps, const float* d_pd, int64_t ldp, const float* d_q,
+                     int64_t ldq, int32_t H, const float* d_mean, const float* d_invstd, const float* d_gamma,
+                     const float* d_beta, const float* d_h, int64_t ldh, float* d_out, int64_t ldo, void* stream);
+int gcmi_cg_bwd_stats(const gcmi_gn_graph* g, const float* d_ps, const float* d_pd, int64_t ldp, const float* d_q,
+                      int64_t ldq, int32_t H, const float* d_mean, const float* d_invstd, const float* d_gamma,
+                      const float* d_beta, const float* d_hnew, int64_t ldhn, const float* d_dhnew, int64_t lddh,
+                      float* d_sums, float* d_workspace, int64_t workspace_floats, void* stream);
+int gcmi_cg_bwd_edges(const gcmi_gn_graph* g, const float* d_ps, const float* d_pd, int64_t ldp, const float* d_q,
+                      int64_t ldq, int32_t H, const float* d_mean, const float* d_invstd, const float* d_gamma,
+                      const float* d_beta, const float* d_hnew, int64_t ldhn, const float* d_dhnew, int64_t lddh,
+                      const float* d_sums, float* d_dq, int64_t lddq, float* d_dpd, int64_t lddp, float* d_dpre,
+                      int64_t lddpre, void* stream);
+int gcmi_cg_bwd_src(const gcmi_gn_graph* g, const float* d_dq, int64_t lddq, int32_t H, float* d_dps, int64_t lddp,
+                    void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Optional per-kernel timing with hipEvents recorded on `stream` around the
  * launches of one kernel family (bench.py roofline).  id: see GCMI_K_*.       */

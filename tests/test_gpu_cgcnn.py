@@ -1,0 +1,334 @@
+"""CGCNN on the GPU: the kernels of csrc/cgcnn.hip and the native route of ``CGCNNLayer`` against the float64 restatement
+of tests/cgcnn_refs.py, the layer against the reference's layer fixtures, and ``CGCNNModel`` against the reference's
+recorded first batch, gradients and fit trajectory (tests/golden/cgcnn_*.npz).
+
+Bar of the kernels and of the layer (``bar`` of tests/test_gpu_mat.py): per output tensor, the largest error against
+float64 is at most 4 times the largest error of the float32 restatement on the CPU for the same inputs, with a floor of
+one fp32 ulp of the tensor's largest entry.  The ratios are printed.  One gradient has no scale of its own: behind a
+BatchNorm on batch statistics the gradient of ``linear.bias`` is zero, the column sum of E rows of dz that cancel; its
+floor is the worst-case rounding of such a sum, E * 2^-24 * max|dz|.  Bar of layers and models against the fixtures:
+1e-4 of each tensor's largest entry; the fit trajectory: ``check_fit`` of tests/test_cgcnn_host.py with the float64 bar.
+
+The cancellation case: a per-column offset of +-OFFSET_SIGMAS standard deviations of z in Q, so the column means of z
+stand 300 standard deviations from zero.  Checked on the CPU first: at 300 the float32 restatement is finite and its
+errors against float64 are 1e-7 (mean, invstd) to 5e-5 (dgamma) of each output's largest entry, about 300 * 2^-24
+(test_cancellation_case_is_meaningful_in_float32 keeps that check), so the offset was not lowered.
+"""
+import numpy as np
+import pytest
+import torch
+
+from deepchem_amd import ops
+from deepchem_amd.models import CGCNNModel
+from deepchem_amd.models.torch_models import CgcnnBatch, CGCNNLayer
+from tests import cgcnn_refs as R
+from tests.test_cgcnn_host import (FE, FN, H as FIX_H, LAYERS, MODES, SIZES, case_batch, check_first_batch, check_fit,
+                                   check_layer, close, fixture_dataset, fixture_model, graph_data, layer_case, load_layer)
+from tests.test_gpu_mat import bar
+
+DEV = "cuda:0"
+WIDTHS = [4, 60, 64, 68, 128]
+OFFSET_SIGMAS = 300.0
+gpu = pytest.mark.gpu
+
+
+# ------------------------------------------------------------------------------------------------ kernels
+_CASES = {}
+
+
+def kernel_case(name, hidden, training, offset=0.0):
+    """Inputs and the float64 / float32 restatements (outputs, statistics, gradients) of one pass, computed once."""
+    key = (name, hidden, training, offset)
+    if key in _CASES:
+        return _CASES[key]
+    _, ei, _, batch = R.pack(R.case_graphs(name))
+    G, N, E = int(batch.max()) + 1, batch.size, ei.shape[1]
+    rng = np.random.RandomState(5 + hidden)
+    c = {"ei": ei, "batch": batch, "G": G, "training": training, "H": hidden}
+    for n, shape in (("P", (N, 4 * hidden)), ("Q", (E, 2 * hidden)), ("h", (N, hidden)), ("cot", (N, hidden))):
+        c[n] = rng.normal(0, 1, shape).astype(np.float32)
+    if offset:  # per column, +-offset standard deviations of z as it stands
+        z = (c["P"][:, :2 * hidden][ei[0]].astype(np.float64) + c["P"][:, 2 * hidden:][ei[1]]) + c["Q"]
+        c["Q"] = (c["Q"] + offset * z.std(0) * rng.choice([-1.0, 1.0], 2 * hidden)).astype(np.float32)
+    c["gamma"] = rng.uniform(0.5, 1.5, 2 * hidden).astype(np.float32)
+    c["beta"] = rng.normal(0, 0.3, 2 * hidden).astype(np.float32)
+    c["rm0"] = rng.normal(0, 0.3, 2 * hidden).astype(np.float32)
+    c["rv0"] = rng.uniform(0.5, 2, 2 * hidden).astype(np.float32)
+    tei = torch.as_tensor(ei)
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        P, Q, h, gamma, beta = (torch.tensor(c[n], dtype=dtype, requires_grad=True) for n in ("P", "Q", "h", "gamma", "beta"))
+        state = R.BNState(2 * hidden, dtype, c["rm0"], c["rv0"])
+        out = R.conv_pass(P, Q, h, gamma, beta, tei, state, training)
+        (out * torch.tensor(c["cot"], dtype=dtype)).sum().backward()
+        res = {"out": out.detach().numpy(), "dP": P.grad.numpy(), "dQ": Q.grad.numpy(), "dh": h.grad.numpy(),
+               "dgamma": gamma.grad.numpy(), "dbeta": beta.grad.numpy()}
+        if training:
+            with torch.no_grad():
+                z = (P[:, :2 * hidden][tei[0]] + P[:, 2 * hidden:][tei[1]]) + Q
+                res.update(mean=z.mean(0).numpy(), invstd=torch.rsqrt(z.var(0, unbiased=False) + R.EPS).numpy(),
+                           rm=state.mean.numpy(), rv=state.var.numpy())
+        c[tag] = res
+    _CASES[key] = c
+    return c
+
+
+def run_native(c):
+    g = ops.GnGraph(c["ei"], c["batch"], c["G"], False, DEV)
+    P, Q, h = (torch.tensor(c[n], device=DEV, requires_grad=True) for n in ("P", "Q", "h"))
+    gamma, beta = (torch.tensor(c[n], device=DEV, requires_grad=True) for n in ("gamma", "beta"))
+    rm, rv = torch.tensor(c["rm0"], device=DEV), torch.tensor(c["rv0"], device=DEV)
+    tracked = torch.zeros((), dtype=torch.int64, device=DEV)
+    res = {}
+    if c["training"]:
+        mean, invstd = ops.cg_stats(g, P.detach(), Q.detach(), R.EPS, R.MOMENTUM, rm, rv, tracked)
+        res.update(mean=mean, invstd=invstd, rm=rm, rv=rv)
+    else:
+        mean, invstd = rm, torch.rsqrt(rv + R.EPS)
+    out = ops.CgConvFn.apply(P, Q, h, mean, invstd, gamma, beta, g, c["training"])
+    (out * torch.tensor(c["cot"], device=DEV)).sum().backward()
+    res.update(out=out.detach(), dP=P.grad, dQ=Q.grad, dh=h.grad, dgamma=gamma.grad, dbeta=beta.grad)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in res.items()}, int(tracked), g
+
+
+def check_kernels(c, label):
+    got, tracked, g = run_native(c)
+    assert set(got) == set(c["f64"]) and tracked == (1 if c["training"] else 0)
+    worst = max(bar(got[k], c["f64"][k], c["f32"][k], "%s %s" % (label, k)) for k in c["f64"])
+    print("worst ratio", worst)
+    return got, g
+
+
+@gpu
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("hidden", WIDTHS)
+def test_kernels_on_the_edge_case_batch(hidden, training):
+    c = kernel_case("edge", hidden, training)
+    got, g = check_kernels(c, "edge H%d %s" % (hidden, "train" if training else "eval"))
+    # a node without an arriving edge: a ZERO row forward, no gradient through it to h or to Pd
+    empty = np.flatnonzero(np.diff(g.host["inc_ptr"]) == 0)
+    assert empty.size >= 300 and not got["out"][empty].any() and not got["dh"][empty].any()
+    assert not got["dP"][empty, 2 * hidden:].any()
+    again, _, _ = run_native(c)
+    assert all(np.array_equal(got[k], again[k]) for k in got)  # no atomics: bit for bit
+
+
+@gpu
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("name", ["g1", "below", "above"])
+def test_kernels_on_one_graph_and_at_the_row_group_edges(name, training):
+    for hidden in (64, 60):  # 16 lanes per row, 16 rows per workgroup; 15 lanes, 17 rows and an idle thread
+        check_kernels(kernel_case(name, hidden, training), "%s H%d %s" % (name, hidden, "train" if training else "eval"))
+
+
+def test_cancellation_case_is_meaningful_in_float32():
+    """No GPU: at the offset the GPU test uses, the float32 restatement is finite and close to float64."""
+    c = kernel_case("edge", 64, True, OFFSET_SIGMAS)
+    sigmas = np.abs(c["f64"]["mean"]) * c["f64"]["invstd"]
+    assert 0.95 * OFFSET_SIGMAS < sigmas.min() and sigmas.max() < 1.05 * OFFSET_SIGMAS
+    for k, want in c["f64"].items():
+        got = c["f32"][k]
+        assert np.all(np.isfinite(got)), k
+        err = R.rel_err(got, want)
+        print("%s: float32 restatement %.3g of the largest entry" % (k, err))
+        # 300 sigma costs log2(300) = 8 of float32's 24 bits in every z - mean; sums over ~1000 edges on top
+        assert err <= 1000 * OFFSET_SIGMAS * 2.0 ** -24, (k, err)
+
+
+@gpu
+def test_batchnorm_statistics_under_cancellation():
+    c = kernel_case("edge", 64, True, OFFSET_SIGMAS)
+    check_kernels(c, "offset %g sigma" % OFFSET_SIGMAS)
+
+
+@gpu
+def test_kernel_wrappers_refuse_what_the_kernels_do_not_cover():
+    c = kernel_case("g1", 64, True)
+    g = ops.GnGraph(c["ei"], c["batch"], c["G"], False, DEV)
+    P, Q, h = (torch.tensor(c[n], device=DEV) for n in ("P", "Q", "h"))
+    with pytest.raises(ValueError, match="4H"):
+        ops.cg_conv_fwd(g, P[:, :24], Q, h)
+    with pytest.raises(ValueError, match="rows"):
+        ops.cg_conv_fwd(g, P, Q[:-1], h)
+    with pytest.raises(ValueError, match="columns"):
+        ops.cg_conv_fwd(g, P, Q, h[:, :32])
+    with pytest.raises(ValueError, match="16-byte"):
+        ops.cg_conv_fwd(g, P, torch.zeros((Q.shape[0], 132), device=DEV)[:, 1:129], h)  # rows that start 4 bytes off
+    with pytest.raises(Exception, match="DIRECTED"):
+        ops.cg_conv_fwd(ops.GnGraph(c["ei"], c["batch"], c["G"], True, DEV), P, Q, h)
+    with pytest.raises(Exception, match="GnGraph on the GPU"):
+        ops.cg_conv_fwd(ops.GnGraph(c["ei"], c["batch"], c["G"], False, "cpu"), P, Q, h)
+    with pytest.raises(ValueError, match="at least 2 edges"):
+        ops.cg_stats(ops.GnGraph(np.zeros((2, 1), np.int64), np.zeros(3, np.int64), 1, False, DEV), P[:3], Q[:1])
+
+
+# ------------------------------------------------------------------------------------------------ the layer
+def layer_restatement(c, dtype, steps=1):
+    """The split form on a layer case: outputs, gradients, dz (the gradient of Q) and the BatchNorm state after ``steps``
+    forwards (the gradients are those of the last one)."""
+    p = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in c["params"].items()}
+    state = R.BNState(p["linear.bias"].numel(), dtype, c.get("rm0"), c.get("rv0"))
+    ei = torch.as_tensor(c["ei"])
+    for _ in range(steps):
+        h, e = (torch.tensor(c[n], dtype=dtype, requires_grad=True) for n in "he")
+        P, Q = R.projections(p["linear.weight"], p["linear.bias"], h, e)
+        Q.retain_grad()
+        out = R.conv_pass(P, Q, h, p.get("batch_norm.weight"), p.get("batch_norm.bias"), ei, state, c["training"])
+    (out * torch.tensor(c["cot"], dtype=dtype)).sum().backward()
+    res = {"out": out.detach().numpy(), "grad_h": h.grad.numpy(), "grad_e": e.grad.numpy(), "rm": state.mean.numpy(),
+           "rv": state.var.numpy()}
+    res.update({"gradp_" + k: v.grad.numpy() for k, v in p.items()})
+    return res, state.tracked, Q.grad.numpy()
+
+
+def native_layer(c, steps=1):
+    hidden, fe = c["h"].shape[1], c["e"].shape[1]
+    layer = CGCNNLayer(hidden, fe, batch_norm=c["with_bn"]).to(DEV)
+    layer.load_state_dict({n: torch.as_tensor(np.asarray(v, np.float32)) for n, v in c["params"].items()}, strict=False)
+    if c["with_bn"]:
+        layer.batch_norm.running_mean.copy_(torch.as_tensor(c["rm0"]))
+        layer.batch_norm.running_var.copy_(torch.as_tensor(c["rv0"]))
+    layer.train(c["training"])
+    g = ops.GnGraph(c["ei"], np.zeros(c["h"].shape[0], np.int64), 1, False, DEV)
+    for _ in range(steps):
+        h, e = (torch.tensor(c[n], dtype=torch.float32, device=DEV, requires_grad=True) for n in "he")
+        out = layer(g, h, e)
+        assert layer.last_route == "native"
+    (out * torch.tensor(c["cot"], dtype=torch.float32, device=DEV)).sum().backward()
+    res = {"out": out.detach(), "grad_h": h.grad, "grad_e": e.grad}
+    res.update({"gradp_" + k: p.grad for k, p in layer.named_parameters()})
+    if c["with_bn"]:
+        res.update(rm=layer.batch_norm.running_mean, rv=layer.batch_norm.running_var)
+    return {k: v.cpu().numpy() for k, v in res.items()}, int(layer.batch_norm.num_batches_tracked) if c["with_bn"] else 0
+
+
+def check_native_layer(c, label, steps=1):
+    want64, tracked, dz64 = layer_restatement(c, torch.float64, steps)
+    want32, _, _ = layer_restatement(c, torch.float32, steps)
+    got, got_tracked = native_layer(c, steps)
+    assert got_tracked == tracked == (steps if c["with_bn"] and c["training"] else 0)
+    worst = 0.0
+    for k in got:
+        if k == "gradp_linear.bias" and c["with_bn"] and c["training"]:
+            floor = dz64.shape[0] * 2.0 ** -24 * float(np.max(np.abs(dz64)))  # see the module docstring
+            e, e32 = float(np.max(np.abs(got[k]))), float(np.max(np.abs(want32[k])))
+            print("%s %s: %.3g, fp32 restatement %.3g, floor %.3g (the true gradient is zero)" % (label, k, e, e32, floor))
+            assert e <= max(4 * e32, floor), (k, e, e32, floor)
+            continue
+        worst = max(worst, bar(got[k], want64[k], want32[k], "%s %s" % (label, k)))
+    print("worst ratio", worst)
+
+
+@gpu
+@pytest.mark.parametrize("training", [True, False])
+@pytest.mark.parametrize("fe", [1, 41])
+@pytest.mark.parametrize("hidden", WIDTHS)
+def test_native_layer_on_the_edge_case_batch(hidden, fe, training):
+    c = case_batch("edge", True, training, hidden, fe)
+    c.update({k: np.asarray(c[k], np.float32) for k in ("h", "e", "cot", "rm0", "rv0")})  # the inputs both sides see
+    c["params"] = {k: np.asarray(v, np.float32) for k, v in c["params"].items()}
+    check_native_layer(c, "H%d Fe%d %s" % (hidden, fe, "train" if training else "eval"))
+
+
+@gpu
+def test_native_layer_without_batch_norm():
+    c = case_batch("edge", False, True, 64, 41)
+    c.update({k: np.asarray(c[k], np.float32) for k in ("h", "e", "cot")})
+    c["params"] = {k: np.asarray(v, np.float32) for k, v in c["params"].items()}
+    check_native_layer(c, "no BatchNorm")
+
+
+@gpu
+def test_running_statistics_after_three_steps():
+    c = case_batch("edge", True, True, 64, 41)
+    c.update({k: np.asarray(c[k], np.float32) for k in ("h", "e", "cot", "rm0", "rv0")})
+    c["params"] = {k: np.asarray(v, np.float32) for k, v in c["params"].items()}
+    check_native_layer(c, "three steps", steps=3)
+
+
+@gpu
+@pytest.mark.parametrize("k", range(int(LAYERS["n_cases"])))
+def test_layer_against_the_layer_fixtures(k):
+    c = layer_case(k)
+    out = check_layer(load_layer(c, DEV), c, DEV, "native")
+    # a prebuilt graph gives the same bits
+    g = ops.GnGraph(c["ei"], np.zeros(c["h"].shape[0], np.int64), 1, False, DEV)
+    layer = load_layer(c, DEV)
+    again = check_layer(layer, c, DEV, "native", graph=g)
+    assert torch.equal(out, again)
+
+
+@gpu
+def test_a_batch_without_any_edge_in_eval_mode():
+    rng = np.random.RandomState(2)
+    graphs = [graph_data(R.make_graph(np.zeros((2, 0)), n, rng, FN, FE)) for n in (1, 3, 2)]
+    outs = {}
+    for route in ("auto", "torch"):
+        torch.manual_seed(4)
+        model = CGCNNModel(n_tasks=2, route=route, device=torch.device(DEV), **SIZES)
+        model.model.eval()
+        out = model.model(CgcnnBatch(graphs, DEV))
+        out.sum().backward()
+        outs[route] = (model.last_route, out.detach().cpu().numpy(), model.model.out.weight.grad.cpu().numpy())
+        with pytest.raises(ValueError, match="more than 1 value per channel"):
+            model.model.train()(CgcnnBatch(graphs, DEV))
+    assert outs["auto"][0] == "native" and outs["torch"][0] == "torch"
+    close(outs["auto"][1], outs["torch"][1], "outputs")
+    close(outs["auto"][2], outs["torch"][2], "out.weight gradient")
+
+
+# ------------------------------------------------------------------------------------------------ the models
+@gpu
+@pytest.mark.parametrize("mode", list(MODES))
+def test_model_first_batch_and_fit(mode):
+    ds = fixture_dataset(MODES[mode][0])
+    model = fixture_model(mode, torch.device(DEV))  # (loads the reference-shaped state dict)
+    check_first_batch(model, mode, ds)
+    assert model.last_route == "native" and all(c.last_route == "native" for c in model.model.conv_layers)
+    worst, worst64 = check_fit(model, mode, ds, bar64=True)
+    print("fit: largest relative distance to the reference's losses %.3g, to the float64 restatement's %.3g" % (worst, worst64))
+    assert model.last_route == "native"
+
+
+def mixed_batch():
+    rng = np.random.RandomState(23)
+    graphs = R.edge_case_graphs(rng, FN, FE)[:8] + R.fixture_graphs(FN, FE)[:3] + [R.make_graph(np.zeros((2, 0)), 1, rng, FN, FE)]
+    return [graph_data(g) for g in graphs], rng.normal(0, 1, (len(graphs), 2)).astype(np.float32)
+
+
+@gpu
+def test_last_route_and_agreement_of_the_routes():
+    graphs, y = mixed_batch()
+    res = {}
+    for tag, hidden, route in (("native", FIX_H, "auto"), ("forced", FIX_H, "torch"), ("h6", 6, "auto")):
+        torch.manual_seed(4)
+        model = CGCNNModel(n_tasks=2, route=route, device=torch.device(DEV), **dict(SIZES, hidden_node_dim=hidden))
+        model.model.train()
+        out = model.model(CgcnnBatch(graphs, DEV))
+        torch.square(out - torch.as_tensor(y, device=DEV)).mean().backward()
+        res[tag] = (model.last_route, out.detach().cpu().numpy(),
+                    {k: p.grad.cpu().numpy() for k, p in model.model.named_parameters()})
+    assert res["native"][0] == "native" and res["forced"][0] == "torch" and res["h6"][0] == "torch"
+    close(res["native"][1], res["forced"][1], "outputs")
+    for k, gr in res["forced"][2].items():
+        if not k.endswith("linear.bias") or not k.startswith("conv_layers"):  # (zero gradients: see test_cgcnn_host)
+            close(res["native"][2][k], gr, k)
+    cpu = CGCNNModel(n_tasks=2, device=torch.device("cpu"), **SIZES)
+    cpu.model.eval()(CgcnnBatch(graphs, "cpu"))
+    assert cpu.last_route == "torch"
+
+
+@gpu
+def test_two_runs_of_one_training_step_give_bitwise_equal_gradients():
+    graphs, y = mixed_batch()
+    grads = []
+    for _ in range(2):
+        torch.manual_seed(4)
+        model = CGCNNModel(n_tasks=2, device=torch.device(DEV), **SIZES)
+        model.model.train()
+        out = model.model(CgcnnBatch(graphs, DEV))
+        torch.square(out - torch.as_tensor(y, device=DEV)).mean().backward()
+        assert model.last_route == "native"
+        grads.append({k: p.grad.cpu().numpy() for k, p in model.model.named_parameters()})
+        grads[-1].update({k: v.cpu().numpy() for k, v in model.model.state_dict().items() if "running" in k})
+    assert all(np.array_equal(grads[0][k], grads[1][k]) for k in grads[0])
