@@ -10,3 +10,5 @@ from deepchem_amd.models.torch_models.megnet import (MEGNet, MEGNetModel, Megnet
                                                       ResidentMegnetSet)
 from deepchem_amd.models.torch_models.cgcnn_layers import CGCNNLayer
 from deepchem_amd.models.torch_models.cgcnn import CGCNN, CGCNNModel, CgcnnBatch
+from deepchem_amd.models.torch_models.layers import AtomicConvolution
+from deepchem_amd.models.torch_models.acnn import AcnnBatch, AtomConvModel, AtomicConv

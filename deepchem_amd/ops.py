@@ -1627,6 +1627,139 @@ class CgConvFn(torch.autograd.Function):
         return dp, dq, dpre, None, None, dgamma, dbeta, None, None
 
 
+# ------------------------------------------------------------------ atomic convolution (ACNN)
+AC_MAX_NEIGHBORS, AC_MAX_TYPES, AC_MAX_CHANNELS = 64, 32, 2048
+
+
+def ac_types(atom_types) -> tuple:
+    """The type table as the kernels take it: a tuple of float32 values, () for ``None`` or an empty list."""
+    if atom_types is None:
+        return ()
+    return tuple(float(np.float32(t)) for t in atom_types)
+
+
+def ac_width_ok(n_filters: int, types=()) -> bool:
+    """Whether csrc/atomconv.hip covers the row: at most AC_MAX_TYPES types without duplicates (a neighbour stands in
+    one channel block) and 1 .. AC_MAX_CHANNELS channels (a row is held in LDS)."""
+    types = ac_types(types)
+    return (len(types) <= AC_MAX_TYPES and len(set(types)) == len(types) and not any(t != t for t in types) and
+            1 <= n_filters and max(len(types), 1) * n_filters <= AC_MAX_CHANNELS)
+
+
+def ac_shape_ok(x, nbrs, z) -> bool:
+    """Whether the kernels take these inputs: float32 (B, N, 3) on the GPU with 1 .. AC_MAX_NEIGHBORS neighbours."""
+    return (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == 3 and
+            nbrs.dim() == 3 and 1 <= nbrs.shape[2] <= AC_MAX_NEIGHBORS and x.shape[0] > 0 and x.shape[1] > 0 and
+            x.shape[0] * x.shape[1] * AC_MAX_NEIGHBORS < 2 ** 31 and z.dtype == torch.float32)
+
+
+class AcInput:
+    """One layer input on the device as ``gcmi_ac_input`` describes it: ``x`` (B, N, 3) float32, ``nbrs`` (B, N, M) int32,
+    ``z`` (B, N, M) float32, the filters ``rc``, ``rs``, ``re`` (L values each), the type table and the box.  An index of
+    ``nbrs`` outside [0, N) is compared with N on the device before it is used and contributes nothing."""
+
+    def __init__(self, x, nbrs, z, rc, rs, re, types=(), box=None):
+        if not (torch.is_tensor(x) and x.is_cuda):
+            raise _lib.GcmiError("x must be a CUDA tensor: the hot path has no CPU implementation")
+        if x.dtype != torch.float32 or x.dim() != 3:
+            raise ValueError("x must be float32 (B, N, 3), got %s %s" % (x.dtype, tuple(x.shape)))
+        B, N, d = x.shape
+        dev = x.device
+        if not (torch.is_tensor(nbrs) and nbrs.device == dev and nbrs.dtype == torch.int32 and nbrs.dim() == 3 and
+                tuple(nbrs.shape[:2]) == (B, N)):
+            raise ValueError("nbrs must be int32 (B, N, M) on the device of x")
+        M = nbrs.shape[2]
+        if not (torch.is_tensor(z) and z.device == dev and z.dtype == torch.float32 and tuple(z.shape) == (B, N, M)):
+            raise ValueError("z must be float32 (B, N, M) on the device of x")
+        rc, rs, re = (t.detach().reshape(-1) for t in (rc, rs, re))
+        L = rc.numel()
+        for t, name in ((rc, "rc"), (rs, "rs"), (re, "re")):
+            if t.device != dev or t.dtype != torch.float32 or t.numel() != L:
+                raise ValueError("%s must hold %d float32 values on the device of x" % (name, L))
+        self.types = ac_types(types)
+        if len(self.types) > AC_MAX_TYPES:
+            raise ValueError("%d atom types, at most %d" % (len(self.types), AC_MAX_TYPES))
+        if box is not None:
+            box = [float(v) for v in (box.tolist() if torch.is_tensor(box) else box)]
+            if len(box) != d:
+                raise ValueError("Length of `box_size` must be equal to `d`")
+        # (the tensors are kept: the description holds their addresses)
+        self.x, self.nbrs, self.z = x.contiguous(), nbrs.contiguous(), z.contiguous()
+        self.rc, self.rs, self.re = rc.contiguous(), rs.contiguous(), re.contiguous()
+        self.B, self.N, self.M, self.d, self.L = B, N, M, d, L
+        self.C = max(len(self.types), 1) * L
+        self.ref = _lib.GcmiAcInput()
+        for k in ("x", "nbrs", "z", "rc", "rs", "re"):
+            setattr(self.ref, k, getattr(self, k).data_ptr())
+        self.ref.B, self.ref.N, self.ref.M, self.ref.d, self.ref.L = B, N, M, d, L
+        self.ref.n_types = len(self.types)
+        for i, t in enumerate(self.types):
+            self.ref.types[i] = t
+        self.ref.has_box = int(box is not None)
+        for i, v in enumerate(box or ()):
+            if i < 3:
+                self.ref.box[i] = v
+
+    def workspace(self) -> torch.Tensor:
+        n = int(_lib.load().gcmi_ac_workspace_floats(self.B, self.N, self.L))
+        if n < 0:
+            raise ValueError("atomic convolution: B %d, N %d, L %d are outside the kernels' range" % (self.B, self.N, self.L))
+        return torch.empty(n, dtype=torch.float32, device=self.x.device)
+
+
+def _ac_stats_arg(a: AcInput, stats):
+    if not (torch.is_tensor(stats) and stats.is_cuda and stats.dtype == torch.float32 and tuple(stats.shape) == (a.N, 2) and
+            stats.is_contiguous()):
+        raise ValueError("stats must be a contiguous float32 CUDA tensor of shape (%d, 2)" % a.N)
+    return _ptr(stats)
+
+
+def ac_stats(a: AcInput, eps: float = 1e-5) -> torch.Tensor:
+    """stats (N, 2) = (mean, invstd) of the atom slots: over the B * C values of a slot, unbiased variance, the rows
+    never written."""
+    stats = torch.empty((a.N, 2), dtype=torch.float32, device=a.x.device)
+    ws = a.workspace()
+    _lib.call("gcmi_ac_stats", ctypes.byref(a.ref), float(eps), _ptr(stats), _ptr(ws), ws.numel(), _stream())
+    return stats
+
+
+def ac_fwd(a: AcInput, stats) -> torch.Tensor:
+    """y (B, N, C) = (row - mean[n]) * invstd[n]."""
+    out = torch.empty((a.B, a.N, a.C), dtype=torch.float32, device=a.x.device)
+    _lib.call("gcmi_ac_fwd", ctypes.byref(a.ref), _ac_stats_arg(a, stats), _ptr(out), _stream())
+    return out
+
+
+def ac_bwd(a: AcInput, stats, dy) -> torch.Tensor:
+    """(3, L): the gradients of rc, rs and re for the output gradient ``dy`` (B, N, C), the statistics being constants."""
+    if not (dy.is_cuda and dy.dtype == torch.float32 and tuple(dy.shape) == (a.B, a.N, a.C)):
+        raise ValueError("dy must be float32 %s on the GPU" % ((a.B, a.N, a.C),))
+    dy = dy.contiguous()
+    grad = torch.empty((3, a.L), dtype=torch.float32, device=a.x.device)
+    ws = a.workspace()
+    _lib.call("gcmi_ac_bwd", ctypes.byref(a.ref), _ac_stats_arg(a, stats), _ptr(dy), _ptr(grad), _ptr(ws), ws.numel(), _stream())
+    return grad
+
+
+class AtomConvFn(torch.autograd.Function):
+    """(rc, rs, re, AcInput built from their values) -> y (B, N, C).  The statistics are taken in the forward and are
+    constants of the backward, as in the reference; ``x`` takes no gradient.  Saved: the statistics (2 N values) -- the
+    pairs are recomputed."""
+
+    @staticmethod
+    def forward(ctx, rc, rs, re, a: AcInput, eps: float):
+        stats = ac_stats(a, eps)
+        ctx.a, ctx.shapes = a, (rc.shape, rs.shape, re.shape)
+        ctx.save_for_backward(stats)
+        return ac_fwd(a, stats)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (stats,) = ctx.saved_tensors
+        g = ac_bwd(ctx.a, stats, dy)
+        return g[0].reshape(ctx.shapes[0]), g[1].reshape(ctx.shapes[1]), g[2].reshape(ctx.shapes[2]), None, None
+
+
 # ------------------------------------------------------------------ message passing
 # ------------------------------------------------------------------ D-MPNN
 DMPNN_MAX_DEGREE = 32

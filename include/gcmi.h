@@ -1199,6 +1199,47 @@ int gcmi_cg_bwd_edges(const gcmi_gn_graph* g, const float* d_ps, const float* d_
 int gcmi_cg_bwd_src(const gcmi_gn_graph* g, const float* d_dq, int64_t lddq, int32_t H, float* d_dps, int64_t lddp,
                     void* stream);
 
+/* ---------------------------------------------------------------- atomic convolution of ACNN (atomconv.hip)
+ * The whole AtomicConvolution layer over B samples of N atom slots with M neighbours each, d = 3 coordinates, fp32.
+ *     D[m] = x[b, nbrs[b, n, m]] - x[b, n],  with has_box: D -= rint(D / box) * box (half to even),  R[m] = |D[m]|,
+ *     rsf(R, l) = exp(-re[l] (R - rs[l])^2) * (R <= rc[l] ? 0.5 (cos(pi R / rc[l]) + 1) : 0),
+ *     row[b, n, a L + l] = sum over the m with z[b, n, m] == types[a] of rsf(R[m], l)        (n_types > 0),
+ *     row[b, n, l]       = sum over the m with z[b, n, m] != 0 of rsf(R[m], l)               (n_types == 0),
+ *     y[b, n, c] = (row[b, n, c] - mean[n]) * invstd[n],   C = max(n_types, 1) * L channels,
+ * mean[n] and the UNBIASED variance of slot n over its B * C values, invstd = 1 / sqrt(variance + eps); stats[n] =
+ * (mean[n], invstd[n]), N pairs of floats, 8-byte aligned.  The statistics are constants of the backward, and x takes
+ * no gradient.  A neighbour whose distance is NaN makes its whole row NaN.  Limits: M <= GCMI_AC_MAX_NEIGHBORS (one lane per neighbour),
+ * n_types <= GCMI_AC_MAX_TYPES without duplicates (the table travels by value), C <= GCMI_AC_MAX_CHANNELS (a row is
+ * held in LDS, four rows per workgroup).  An index nbrs[b, n, m] outside [0, N) is compared with N before it is used
+ * and contributes nothing.  All arrays are contiguous and 4-byte aligned.
+ *   gcmi_ac_stats  stats; B * C >= 2.  Per row a mean and a centred second moment in double about the
+ *                  row's first value, combined over b in index order in double.  The rows are not written.
+ *   gcmi_ac_fwd    y (B, N, C).
+ *   gcmi_ac_bwd    grad[3 L] = [d rc | d rs | d re], the sums over b, n, m, a of dy[b, n, a L + l] * invstd[n] *
+ *                  d rsf / d{rc, rs, re}, per workgroup in double in row order, the workgroups by a fixed tree.
+ * gcmi_ac_stats and gcmi_ac_bwd take a 16-byte aligned workspace of gcmi_ac_workspace_floats(B, N, L) floats (-1: bad
+ * sizes).  No atomics: two calls agree bit for bit.                                                                    */
+#define GCMI_AC_MAX_NEIGHBORS 64
+#define GCMI_AC_MAX_TYPES 32
+#define GCMI_AC_MAX_CHANNELS 2048
+typedef struct {
+  const float* x;       /* (B, N, 3) */
+  const int32_t* nbrs;  /* (B, N, M) */
+  const float* z;       /* (B, N, M): the type of each neighbour */
+  const float *rc, *rs, *re; /* L each */
+  int32_t B, N, M, d, L;
+  int32_t n_types;
+  float types[GCMI_AC_MAX_TYPES];
+  int32_t has_box;
+  float box[3];
+} gcmi_ac_input;
+int64_t gcmi_ac_workspace_floats(int32_t B, int32_t N, int32_t L);
+int gcmi_ac_stats(const gcmi_ac_input* in, float eps, float* d_stats, float* d_workspace, int64_t workspace_floats,
+                  void* stream);
+int gcmi_ac_fwd(const gcmi_ac_input* in, const float* d_stats, float* d_out, void* stream);
+int gcmi_ac_bwd(const gcmi_ac_input* in, const float* d_stats, const float* d_dy, float* d_grad, float* d_workspace,
+                int64_t workspace_floats, void* stream);
+
 /* ---------------------------------------------------------------- measurement
  * Optional per-kernel timing with hipEvents recorded on `stream` around the
  * launches of one kernel family (bench.py roofline).  id: see GCMI_K_*.       */

@@ -1,0 +1,259 @@
+"""csrc/atomconv.hip on the GPU against the float64 restatement of tests/acnn_refs.py.
+
+The bar is ``bar`` of tests/test_gpu_mat.py: the error against float64 is at most 4 times the float32 restatement's own,
+with a floor of one float32 ulp of the tensor's largest entry.  It is applied to the statistics (mean, invstd), the
+output and the three filter gradients of the kernels, and to the same tensors through ``AtomicConvolution`` and
+``AtomicConv``.  Shapes are the smallest at which the kernel can go wrong: B in {1, 2, 3}, N in {1, 5, 63, 64, 65} (a
+workgroup takes 4 rows), M in {1, 12, 13}, L in {1, 3, 66} (64 lanes along l), no types / one type / the 15 defaults
+(C = 990), and C = 2048 | 2049 either side of the native bound.
+
+The rule for a neighbour index outside [0, N) (documented in include/gcmi.h): the kernel compares it with N before it
+is used and the neighbour contributes nothing; the test hands such indices straight to ``ops`` and compares with the
+same lists masked by type 0.
+
+Inputs with a component of D / box within 1e-3 of a half-integer are excluded by construction (``settle_box``); the box
+test asserts ``rounds_alike`` on the inputs it uses, so the exclusion cannot hide a case."""
+import numpy as np
+import pytest
+import torch
+
+from deepchem_amd import ops
+from deepchem_amd.models.torch_models import AtomicConv, AtomicConvolution
+from tests import acnn_refs as R
+from tests.test_acnn_host import (BATCH, LAYER, MAX_NBRS, MODEL, MODEL_RADIAL, MODEL_TYPES, SIZES, check_first_batch, check_fit,
+                                  check_layer, fixture_dataset, fixture_model)
+from tests.test_gpu_mat import bar
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+TYPES = {"none": None, "one": [6.0], "defaults": R.DEFAULT_TYPES}
+
+
+def params_for(rng, L):
+    return R.radial_params()[:66] if L == 66 else R.random_params(rng, L)
+
+
+def run_ops(X, nbrs, Z, params, types, box, cot):
+    """stats, y and the gradients through the checked wrappers, as float64 arrays."""
+    f = [torch.as_tensor(np.asarray(params, np.float32)[:, i].copy(), device=DEV) for i in range(3)]
+    a = ops.AcInput(torch.as_tensor(X, device=DEV), torch.as_tensor(nbrs, device=DEV), torch.as_tensor(Z, device=DEV), *f,
+                    types or (), box)
+    stats = ops.ac_stats(a)
+    y = ops.ac_fwd(a, stats)
+    g = ops.ac_bwd(a, stats, torch.as_tensor(np.asarray(cot, np.float32), device=DEV))
+    torch.cuda.synchronize()
+    return dict(mean=stats[:, 0], invstd=stats[:, 1], y=y, rc=g[0], rs=g[1], re=g[2])
+
+
+def check_bars(got, X, nbrs, Z, params, types, box, cot, name):
+    want = R.layer_with_grads(X, nbrs, Z, params, types, box, cot, torch.float64)
+    r32 = R.layer_with_grads(X, nbrs, Z, params, types, box, cot, torch.float32)
+    worst = 0.0
+    for k in ("mean", "invstd", "y", "rc", "rs", "re"):
+        if k in got:
+            worst = max(worst, bar(got[k].detach().cpu().numpy(), want[k], r32[k], "%s %s" % (name, k)))
+    print("%s: worst ratio %.2f" % (name, worst))
+    return want
+
+
+SHAPES = [(1, 1, 1, 3, "none"), (2, 1, 1, 1, "none"), (1, 5, 12, 66, "defaults"), (2, 63, 13, 3, "one"),
+          (3, 64, 12, 66, "none"), (2, 65, 13, 66, "defaults"), (3, 65, 1, 1, "one"), (3, 5, 13, 1, "defaults"),
+          (1, 64, 12, 3, "defaults"), (2, 64, 1, 66, "one"), (3, 63, 12, 1, "none")]
+
+
+@pytest.mark.parametrize("B,N,M,L,kind", SHAPES)
+def test_kernels_hold_the_bar(B, N, M, L, kind):
+    rng = np.random.RandomState(B * 1000 + N * 10 + M + L)
+    X, nbrs, Z = R.random_case(rng, B, N, M, scale=3.0 if L == 66 else 1.5)
+    params, types = params_for(rng, L), TYPES[kind]
+    cot = rng.normal(0, 1, (B, N, max(len(types or ()), 1) * L)).astype(np.float32)
+    got = run_ops(X, nbrs, Z, params, types, None, cot)
+    check_bars(got, X, nbrs, Z, params, types, None, cot, "B%d N%d M%d L%d %s" % (B, N, M, L, kind))
+    again = run_ops(X, nbrs, Z, params, types, None, cot)
+    for k in got:
+        assert torch.equal(got[k], again[k]), k  # bit for bit
+
+
+def test_edge_cases():
+    rng = np.random.RandomState(11)
+    X, nbrs, Z = R.edge_case(rng)
+    cot = rng.normal(0, 1, (3, 8, 9)).astype(np.float32)
+    got = run_ops(X, nbrs, Z, R.EDGE_PARAMS, R.EDGE_TYPES, None, cot)
+    want = check_bars(got, X, nbrs, Z, R.EDGE_PARAMS, R.EDGE_TYPES, None, cot, "edge")
+    # the padding slot and the slot beyond every rc: variance 0, output exactly 0
+    for slot in (R.EDGE_PAD_SLOT, R.EDGE_FAR_SLOT):
+        assert float(got["y"][:, slot].abs().max()) == 0.0 and float(got["mean"][slot]) == 0.0
+        assert abs(float(got["invstd"][slot]) - 1e-5 ** -0.5) <= 1e-4 * 1e-5 ** -0.5
+    # the pair at exactly R == rc is inside the cut-off (<=) and contributes (cos(pi) + 1) / 2 = 0 in exact arithmetic
+    assert np.all(np.isfinite(want["y"]))
+
+
+def test_mean_far_from_zero():
+    rng = np.random.RandomState(0)
+    X, nbrs, Z, N = R.far_mean_case(rng)
+    cot = rng.normal(0, 1, (X.shape[0], X.shape[1], 1)).astype(np.float32)
+    got = run_ops(X, nbrs, Z, R.FAR_PARAMS, None, None, cot)
+    want = check_bars(got, X, nbrs, Z, R.FAR_PARAMS, None, None, cot, "far mean")
+    assert np.min(np.abs(want["mean"][:N]) * want["invstd"][:N]) > 100  # (the case is what it says)
+
+
+def test_periodic_box():
+    rng = np.random.RandomState(5)
+    box = [2.0, 2.5, 1.75]
+    X, nbrs, Z = R.random_case(rng, 3, 65, 13, scale=6.0)
+    X = R.settle_box(rng, X, nbrs, box, 6.0)
+    assert R.rounds_alike(X, nbrs, box)  # float64 and float32 round every entry alike, none within 1e-3 of a half
+    D, q = R.displacement(X, nbrs, box, torch.float64)
+    assert float(torch.round(q).abs().max()) >= 2  # (the box does wrap)
+    params = R.random_params(rng, 3)
+    cot = rng.normal(0, 1, (3, 65, 9)).astype(np.float32)
+    got = run_ops(X, nbrs, Z, params, R.EDGE_TYPES, box, cot)
+    check_bars(got, X, nbrs, Z, params, R.EDGE_TYPES, box, cot, "box")
+
+
+def test_an_index_outside_the_atoms_reads_nothing():
+    rng = np.random.RandomState(8)
+    X, nbrs, Z = R.random_case(rng, 2, 5, 12)
+    Z[Z == 0] = 6
+    params = R.random_params(rng, 3)
+    cot = rng.normal(0, 1, (2, 5, 9)).astype(np.float32)
+    bad, masked_z = nbrs.copy(), Z.copy()
+    for (b, n, m), v in zip([(0, 0, 0), (0, 1, 3), (1, 2, 11), (1, 4, 5), (1, 4, 6)], [-1, 5, 2 ** 31 - 1, -2 ** 31, 6]):
+        bad[b, n, m], masked_z[b, n, m] = v, 0
+    got = run_ops(X, bad, Z, params, R.EDGE_TYPES, None, cot)
+    want = run_ops(X, nbrs, masked_z, params, R.EDGE_TYPES, None, cot)
+    for k in got:
+        assert torch.equal(got[k], want[k]), k
+
+
+def test_ops_refuse_what_the_kernels_do_not_take():
+    rng = np.random.RandomState(1)
+    X, nbrs, Z = R.random_case(rng, 2, 5, 3)
+    f = [torch.ones(3, device=DEV) for _ in range(3)]
+    x, nb, z = torch.as_tensor(X, device=DEV), torch.as_tensor(nbrs, device=DEV), torch.as_tensor(Z, device=DEV)
+    with pytest.raises(Exception, match="stands twice"):
+        ops.ac_stats(ops.AcInput(x, nb, z, *f, [6, 7, 6]))
+    with pytest.raises(Exception, match="3 coordinates"):
+        ops.ac_stats(ops.AcInput(x[:, :, :2].contiguous(), nb, z, *f))
+    with pytest.raises(ValueError, match="int32"):
+        ops.AcInput(x, nb.long(), z, *f)
+    with pytest.raises(Exception, match="at least 2 values"):
+        ops.ac_stats(ops.AcInput(x[:1], nb[:1], z[:1], *[t[:1] for t in f]))
+    assert ops.ac_shape_ok(x, nb, z) and not ops.ac_shape_ok(x.cpu(), nb.cpu(), z.cpu()) and not ops.ac_shape_ok(x.double(), nb, z)
+
+
+# ---------------------------------------------------------------------------------------------- the layer
+def layer_on(types, params, box=None):
+    layer = AtomicConvolution(atom_types=types, radial_params=params, box_size=box).to(DEV)
+    return layer
+
+
+@pytest.mark.parametrize("kind", ["none", "defaults"])
+def test_layer_holds_the_bar_and_takes_the_native_route(kind):
+    rng = np.random.RandomState(21)
+    X, nbrs, Z = R.random_case(rng, 2, 65, 12, scale=3.0)
+    params, types = R.radial_params(), TYPES[kind]
+    layer = layer_on(types, params)
+    out = layer([X, nbrs.astype(np.int64), Z])
+    assert layer.last_route == "native" and out.dtype == torch.float32
+    cot = rng.normal(0, 1, tuple(out.shape)).astype(np.float32)
+    (out * torch.as_tensor(cot, device=DEV)).sum().backward()
+    got = dict(y=out, rc=layer.rc.grad.reshape(-1), rs=layer.rs.grad.reshape(-1), re=layer.re.grad.reshape(-1))
+    check_bars(got, X, nbrs, Z, params, types, None, cot, "layer " + kind)
+    forced = layer_on(types, params)
+    forced.route = "torch"
+    out_t = forced([X, nbrs, Z])
+    assert forced.last_route == "torch"
+    bar(out_t.detach().cpu().numpy(), R.layer_with_grads(X, nbrs, Z, params, types, None, cot, torch.float64)["y"],
+        R.layer_with_grads(X, nbrs, Z, params, types, None, cot, torch.float32)["y"], "torch route " + kind)
+
+
+def test_layer_routes():
+    rng = np.random.RandomState(22)
+    X, nbrs, Z = R.random_case(rng, 2, 5, 3)
+    params = R.random_params(rng, 3)
+    for types, x, want in ((None, X, "native"), (None, X[:, :, :2], "torch"), ([6, 7, 6], X, "torch"), ([6, 7], X, "native"),
+                           (None, X.astype(np.float64), "torch")):
+        layer = layer_on(types, params)
+        out = layer([x, nbrs, Z.astype(np.int64)])  # (integer types: compared as float32 on both routes)
+        assert layer.last_route == want, (types, x.shape, x.dtype)
+        assert out.shape == (2, 5, 3 * max(len(types or ()), 1))
+    cpu = AtomicConvolution(radial_params=params)
+    cpu([X, nbrs, Z])
+    assert cpu.last_route == "torch"
+    # one value per slot: NaN on the torch route, as the reference
+    one = layer_on(None, params[:1])
+    out = one([X[:1], nbrs[:1], Z[:1]])
+    assert one.last_route == "torch" and bool(torch.isnan(out).all())
+
+
+def test_the_native_bound_on_the_channels():
+    """C = 2048 is the last row the kernels hold in LDS; C = 2049 lands on the torch route."""
+    rng = np.random.RandomState(23)
+    X, nbrs, Z = R.random_case(rng, 2, 3, 2)
+    for L, want in ((2048, "native"), (2049, "torch")):
+        params = R.random_params(rng, L)
+        layer = layer_on(None, params)
+        out = layer([X, nbrs, Z])
+        assert layer.last_route == want and out.shape == (2, 3, L)
+        cot = rng.normal(0, 1, (2, 3, L)).astype(np.float32)
+        (out * torch.as_tensor(cot, device=DEV)).sum().backward()
+        got = dict(y=out, rc=layer.rc.grad.reshape(-1), rs=layer.rs.grad.reshape(-1), re=layer.re.grad.reshape(-1))
+        check_bars(got, X, nbrs, Z, params, None, None, cot, "C = %d" % L)
+
+
+@pytest.mark.parametrize("k", range(int(LAYER["n_cases"])))
+def test_layer_holds_the_fixture(k):
+    layer = check_layer(k, DEV, "auto")
+    assert layer.last_route == ("torch" if k == 4 else "native")  # (case 4: float64 coordinates)
+
+
+# ---------------------------------------------------------------------------------------------- the model
+def test_atomic_conv_holds_the_bar():
+    model = fixture_model(DEV)
+    ds = fixture_dataset()
+    inputs, labels, weights = model._prepare_batch(next(iter(model._batch_generator(ds))))
+    model.model.zero_grad()
+    out = model.model(inputs)[0]
+    assert model.last_route == "native"
+    cot = torch.as_tensor(np.random.RandomState(3).normal(0, 1, tuple(out.shape)).astype(np.float32), device=DEV)
+    (out * cot).sum().backward()
+    got = {"out": out}
+    got.update({k: p.grad for k, p in model.model.named_parameters()})
+    state0 = {k: MODEL["param0_" + k] for k in MODEL["keys"]}
+    host = [MODEL["gen0_%d" % j] for j in range(12)]
+    refs = {}
+    for dtype in (torch.float64, torch.float32):
+        ref = R.ACNNRef(state0, dtype, MODEL_TYPES, MODEL_RADIAL)
+        o = ref(host)
+        (o * cot.cpu().to(dtype)).sum().backward()
+        refs[dtype] = {"out": o.detach().double().numpy()}
+        refs[dtype].update({k: ref.p[k.replace(".", "_")].grad.double().numpy() for k in state0})
+    worst = max(bar(got[k].detach().cpu().numpy(), refs[torch.float64][k], refs[torch.float32][k], "AtomicConv " + k) for k in got)
+    print("AtomicConv: worst ratio %.2f" % worst)
+
+
+def test_model_holds_the_fixtures_and_the_fit_bar():
+    ds = fixture_dataset()
+    model = fixture_model(DEV)
+    check_first_batch(model, ds)
+    assert model.last_route == "native"
+    model = fixture_model(DEV)
+    worst, worst64 = check_fit(model, ds, bar64=True)
+    print("fit: largest relative distance to the reference's losses %.3g, to the float64 restatement's %.3g" % (worst, worst64))
+    assert model.last_route == "native"
+    forced = fixture_model(DEV, route="torch")
+    check_first_batch(forced, ds)
+    assert forced.last_route == "torch"
+
+
+def test_defaults_take_the_native_route():
+    module = AtomicConv(n_tasks=1, frag1_num_atoms=2, frag2_num_atoms=3, complex_num_atoms=4, batch_size=2).to(DEV)
+    rng = np.random.RandomState(2)
+    inputs = []
+    for n in (2, 3, 4):
+        X, nbrs, Z = R.random_case(rng, 2, n, 12)
+        inputs += [torch.as_tensor(a, device=DEV) for a in (X, nbrs, Z)] + [None]
+    out = module(inputs)[0]
+    assert module.last_route == "native" and out.shape == (2, 1) and module.layers[0].weight.shape == (100, 9 * 990)
+    assert (BATCH, MAX_NBRS, SIZES) == (3, 4, (3, 5, 7))
