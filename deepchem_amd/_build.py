@@ -11,7 +11,7 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libgcmi.so")
-SOURCES = ["core.cpp", "collate.cpp", "featurize.cpp", "gather.hip", "gather_lds.hip", "readout.hip", "bn.hip", "gemm.hip", "gemm_split.hip", "bwd_fused.hip", "fwd_fused.hip", "fwd_bf16.hip", "head_bwd.hip", "loss.hip", "metrics.hip", "optim.hip", "weave.hip", "mpnn.hip", "dtnn.hip", "dmpnn.hip", "dmpnn_collate.hip", "mat.hip", "megnet.hip", "megnet_collate.hip", "cgcnn.hip", "atomconv.hip", "model.hip", "smallstep.hip"]
+SOURCES = ["core.cpp", "collate.cpp", "featurize.cpp", "gather.hip", "gather_lds.hip", "readout.hip", "bn.hip", "gemm.hip", "gemm_split.hip", "bwd_fused.hip", "fwd_fused.hip", "fwd_bf16.hip", "head_bwd.hip", "loss.hip", "metrics.hip", "optim.hip", "weave.hip", "mpnn.hip", "dtnn.hip", "dmpnn.hip", "dmpnn_collate.hip", "mat.hip", "megnet.hip", "megnet_collate.hip", "cgcnn.hip", "atomconv.hip", "lcnn.hip", "model.hip", "smallstep.hip"]
 ARCH = "gfx950"
 
 

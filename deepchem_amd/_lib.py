@@ -161,8 +161,14 @@ class GcmiAcInput(Structure):
         [("types", c_float * 32), ("has_box", c_int32), ("box", c_float * 3)]
 
 
+class GcmiLcBatch(Structure):
+    """struct gcmi_lc_batch (include/gcmi.h)."""
+    _fields_ = [(k, c_int32) for k in ("n_sites", "P", "K", "O")] + [(k, c_void_p) for k in ("nbr", "rev_ptr", "rev_row")]
+
+
 _P = c_void_p
 _G = POINTER(GcmiGraph)
+_LC = POINTER(GcmiLcBatch)
 _GN = POINTER(GcmiGnGraph)
 _AC = POINTER(GcmiAcInput)
 _GNS = POINTER(GcmiGnSet)
@@ -277,6 +283,10 @@ _SIGNATURES = {
     "gcmi_ac_stats": [_AC, c_float, _P, _P, c_int64, _P],
     "gcmi_ac_fwd": [_AC, _P, _P, _P],
     "gcmi_ac_bwd": [_AC, _P, _P, _P, _P, c_int64, _P],
+    "gcmi_lc_site_fwd": [_LC, _P, c_int64, _P, _P, _P, _P, _P, c_float, _P, _P, c_int64, _P, _P],
+    "gcmi_lc_site_bwd": [_LC, _P, _P, c_int64, _P, _P, _P, _P, c_float, _P, _P, _P, c_int64, _P],
+    "gcmi_lc_rev_sum": [_LC, _P, _P, c_int64, _P],
+    "gcmi_lc_running": [_LC, _P, c_float, _P, _P, _P, _P],
     "gcmi_dmpnn_message": [c_int32, _P, c_int64, c_int32, _P, _P, c_int32, c_int32, _P, c_int64, _P, c_int64, _P, c_int64, _P],
     "gcmi_dmpnn_update_fwd": [_P, c_int64, _P, c_int64, _P, c_int64, c_int32, c_int32, _P, _P, _P, c_int32, c_int32, _P, c_int64,
                               _P, c_int64, _P],
@@ -318,7 +328,7 @@ _SIGNATURES = {
 EXPORTS = ["gcmi_version", "gcmi_last_error", "gcmi_model_workspace_floats", "gcmi_small_workspace_floats",
            "gcmi_task_head_scratch_floats", "gcmi_fwd_fused_scratch_floats", "gcmi_lamb_scratch_floats", "gcmi_metrics_workspace_bytes",
            "gcmi_smiles_check", "gcmi_collate_plan_words", "gcmi_collate_batches_layout",
-           "gcmi_dmpnn_collate_words", "gcmi_gn_collate_words", "gcmi_cg_workspace_floats", "gcmi_ac_workspace_floats"] + sorted(_SIGNATURES)
+           "gcmi_dmpnn_collate_words", "gcmi_gn_collate_words", "gcmi_cg_workspace_floats", "gcmi_ac_workspace_floats", "gcmi_lc_workspace_floats"] + sorted(_SIGNATURES)
 
 _lib = None
 
@@ -368,6 +378,7 @@ def load():
         "gcmi_gn_collate_words": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _I64P]),
         "gcmi_cg_workspace_floats": (c_int64, [c_int32, c_int32, c_int32]),
         "gcmi_ac_workspace_floats": (c_int64, [c_int32, c_int32, c_int32]),
+        "gcmi_lc_workspace_floats": (c_int64, [c_int32, c_int32]),
     }
     for name, (restype, argtypes) in special.items():
         if host_only and not hasattr(lib, name):

@@ -1627,6 +1627,200 @@ class CgConvFn(torch.autograd.Function):
         return dp, dq, dpre, None, None, dgamma, dbeta, None, None
 
 
+# ------------------------------------------------------------------ lattice convolution (LCNN)
+LC_MAX_WIDTH, LC_MIN_PERM, LC_MAX_PERM, LC_MAX_SLOTS = 64, 2, 8, 32
+
+
+def lc_shape_ok(n_sites: int, P: int, K: int, O: int) -> bool:
+    """Whether csrc/lcnn.hip covers the shape."""
+    return 1 <= O <= LC_MAX_WIDTH and LC_MIN_PERM <= P <= LC_MAX_PERM and 1 <= K <= LC_MAX_SLOTS and \
+        0 < n_sites and n_sites * P * K * LC_MAX_WIDTH < 2 ** 31 - 1
+
+
+def lc_graph_tables(edge_index, n_sites: int, P: int, K: int, graph: int = 0):
+    """The tables of ONE graph in local indices: ``(nbr (n, P * K) int32, rev_count (n * K,) int32, rev_row (n * P * K,)
+    int32)``.  ``nbr[v, p * K + j]`` is the source of the ``(p * K + j)``-th edge arriving at ``v`` (a stable sort by
+    destination: a no-op where the edges already arrive grouped); the list of ``(u, j)`` holds the rows ``v * P + p``
+    with ``nbr[v, p, j] = u`` in ascending order.  ``ValueError`` naming graph and node where an in-degree is not
+    ``P * K``."""
+    ei = np.asarray(edge_index)
+    if ei.ndim != 2 or ei.shape[0] != 2:
+        raise ValueError("lc_graph_tables: edge_index of graph %d must be (2, n_edges), got %s" % (graph, ei.shape))
+    src, dst = ei[0].astype(np.int64), ei[1].astype(np.int64)
+    n, D = int(n_sites), P * K
+    if src.size and (min(src.min(), dst.min()) < 0 or max(src.max(), dst.max()) >= n):
+        raise ValueError("lc_graph_tables: edge_index of graph %d names a node outside [0, %d)" % (graph, n))
+    degree = np.bincount(dst, minlength=n)
+    bad = np.nonzero(degree != D)[0]
+    if bad.size:
+        raise ValueError("LCNN: graph %d, node %d has in-degree %d, every site needs n_permutation * n_neighbor_sites = "
+                         "%d * %d = %d arriving edges" % (graph, bad[0], degree[bad[0]], P, K, D))
+    if dst.size and np.any(np.diff(dst) < 0):
+        src = src[np.argsort(dst, kind="stable")]
+    nbr = src.reshape(n, D)
+    key = (nbr.reshape(n, P, K) * K + np.arange(K)).reshape(-1)  # (u, j) of entry (v, p, j)
+    order = np.argsort(key, kind="stable")
+    rev_row = (order // K).astype(np.int32)  # entry (v, p, j) -> row v * P + p
+    return nbr.astype(np.int32), np.bincount(key, minlength=n * K).astype(np.int32), rev_row
+
+
+class LcBatch:
+    """The sites of one batch for csrc/lcnn.hip: the dense neighbour table ``nbr`` (N, P * K), the reverse lists keyed
+    by (node, slot) (``rev_ptr`` (N * K + 1,), ``rev_row``) and ``node_ptr`` (graphs + 1,), put together from per-graph
+    tables in local indices (``lc_graph_tables``) by concatenation plus offsets, validated on the host and uploaded in
+    ONE packed transfer together with ``floats`` (``self.floats``)."""
+
+    def __init__(self, tables, P: int, K: int, device, floats=()):
+        tables = list(tables)
+        if not tables:
+            raise ValueError("LcBatch: no graphs")
+        self.P, self.K = int(P), int(K)
+        sizes = np.asarray([t[0].shape[0] for t in tables], np.int64)
+        if sizes.min() <= 0 or any(t[0].shape[1] != P * K or t[1].size != t[0].shape[0] * K or t[2].size != t[0].size
+                                   for t in tables):
+            raise ValueError("LcBatch: every graph needs a site and tables of (n, %d), (n * %d,), (n * %d,)" % (P * K, K, P * K))
+        if any(a.dtype != np.int32 for t in tables for a in t):
+            raise ValueError("LcBatch: the tables must be int32 (ops.lc_graph_tables)")
+        node_ptr = np.concatenate([[0], np.cumsum(sizes)])
+        N = int(node_ptr[-1])
+        if N * P * K * LC_MAX_WIDTH >= 2 ** 31 - 1:
+            raise ValueError("LcBatch: %d sites are too many for 32-bit lists" % N)
+        # the packed buffer first, the tables concatenated straight into it in int32 and offset in place: no second copy
+        fl = [np.ascontiguousarray(a, np.float32) for a in floats]
+        shapes = {"nbr": (N, P * K), "rev_ptr": (N * K + 1,), "rev_row": (N * P * K,), "node_ptr": (len(tables) + 1,)}
+        where, total = {}, 0
+        for k, shape in list(shapes.items()) + [(i, a.shape) for i, a in enumerate(fl)]:
+            where[k] = total
+            total += int(np.prod(shape)) + (-int(np.prod(shape)) % 4)
+        words = np.zeros(total, np.int32)
+        host = {k: words[where[k]:where[k] + int(np.prod(shape))].reshape(shape) for k, shape in shapes.items()}
+        nbr, rev_ptr, rev_row = host["nbr"].reshape(-1), host["rev_ptr"], host["rev_row"]
+        at = np.repeat(node_ptr[:-1].astype(np.int32), sizes * (P * K))
+        np.concatenate([t[0].reshape(-1) for t in tables], out=nbr)
+        nbr += at
+        np.concatenate([t[2] for t in tables], out=rev_row)
+        at *= P
+        rev_row += at
+        np.cumsum(np.concatenate([t[1] for t in tables]), out=rev_ptr[1:])
+        host["node_ptr"][:] = node_ptr
+        # validated before it leaves: the kernels compare every index again, a table that fails here is a bug upstream
+        if nbr.min() < 0 or nbr.max() >= N or rev_row.min() < 0 or rev_row.max() >= N * P or rev_ptr[-1] != N * P * K or \
+                np.any(rev_ptr[1:] < rev_ptr[:-1]):
+            raise ValueError("LcBatch: a neighbour or reverse-list entry is out of range")
+        self.n_sites, self.n_graphs = N, len(tables)
+        self.device = torch.device(device)
+        for i, a in enumerate(fl):
+            words[where[i]:where[i] + a.size] = a.reshape(-1).view(np.int32)
+        packed = torch.as_tensor(words.view(np.float32), device=self.device)
+        ints = packed.view(torch.int32)
+        for k, a in host.items():  # (the packed host buffer is not kept: the tables live on the device)
+            setattr(self, k, ints[where[k]:where[k] + a.size].view(a.shape))
+        self.floats = [packed[where[i]:where[i] + a.size].view(a.shape) for i, a in enumerate(fl)]
+        self._packed = packed
+
+    def ref(self, O: int) -> "_lib.GcmiLcBatch":
+        return _lib.GcmiLcBatch(n_sites=self.n_sites, P=self.P, K=self.K, O=int(O), nbr=self.nbr.data_ptr(),
+                                rev_ptr=self.rev_ptr.data_ptr(), rev_row=self.rev_row.data_ptr())
+
+
+def _lc_batch(b, O: int, what: str):
+    if not isinstance(b, LcBatch) or b.device.type != "cuda":
+        raise _lib.GcmiError("%s: the batch must be an ops.LcBatch on the GPU" % what)
+    if not lc_shape_ok(b.n_sites, b.P, b.K, O):
+        raise ValueError("%s: n_sites %d, P %d, K %d, O %d are outside what csrc/lcnn.hip covers" % (what, b.n_sites, b.P, b.K, O))
+    return b.ref(O)
+
+
+def _lc_x(t, name: str, b: LcBatch, O: int):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or tuple(t.shape) != (b.n_sites, b.P, O) or \
+            not t.is_contiguous():
+        raise ValueError("%s must be a contiguous float32 CUDA tensor of (%d, %d, %d)" % (name, b.n_sites, b.P, O))
+    return t
+
+
+def _lc_mask(mask, b: LcBatch):
+    if mask is not None and (not mask.is_cuda or mask.dtype != torch.float32 or tuple(mask.shape) != (b.n_sites, b.P) or
+                             not mask.is_contiguous()):
+        raise ValueError("mask must be a contiguous float32 CUDA tensor of (%d, %d)" % (b.n_sites, b.P))
+    return mask
+
+
+def lc_site_fwd(b: LcBatch, y, bias, gamma, beta, mean=None, var=None, eps: float = 1e-5, mask=None, want_x: bool = True):
+    """(out (N, O), X (N, P, O) or None).  ``mean`` / ``var`` None: each site's own statistics over its P rows."""
+    O = int(gamma.numel())
+    ref = _lc_batch(b, O, "lc_site_fwd")
+    y = _mat(y, "Y", rows=b.n_sites, cols=b.K * O)
+    vecs = [_vec(t, name, O) for t, name in ((bias, "bias"), (gamma, "gamma"), (beta, "beta"), (mean, "mean"), (var, "var"))]
+    out = torch.empty((b.n_sites, O), dtype=torch.float32, device=y.device)
+    x = torch.empty((b.n_sites, b.P, O), dtype=torch.float32, device=y.device) if want_x else None
+    _lib.call("gcmi_lc_site_fwd", ctypes.byref(ref), _ptr(y), _ld(y), *(_ptr(t) for t in vecs), float(eps),
+              _ptr(_lc_mask(mask, b)), _ptr(out), O, _ptr(x), _stream())
+    return out, x
+
+
+def lc_site_bwd(b: LcBatch, x, dout, gamma, mean=None, var=None, eps: float = 1e-5, mask=None):
+    """(dX (N, P, O), sums (3 O,) = [dgamma | dbeta | dbias])."""
+    O = int(gamma.numel())
+    ref = _lc_batch(b, O, "lc_site_bwd")
+    x, dout = _lc_x(x, "X", b, O), _mat(dout, "dOut", rows=b.n_sites, cols=O)
+    vecs = [_vec(t, name, O) for t, name in ((gamma, "gamma"), (mean, "mean"), (var, "var"))]
+    dx, sums = torch.empty_like(x), torch.empty(3 * O, dtype=torch.float32, device=x.device)
+    ws = torch.empty(int(_lib.load().gcmi_lc_workspace_floats(b.n_sites, O)), dtype=torch.float32, device=x.device)
+    _lib.call("gcmi_lc_site_bwd", ctypes.byref(ref), _ptr(x), _ptr(dout), _ld(dout), _ptr(_lc_mask(mask, b)),
+              *(_ptr(t) for t in vecs), float(eps), _ptr(dx), _ptr(sums), _ptr(ws), ws.numel(), _stream())
+    return dx, sums
+
+
+def lc_rev_sum(b: LcBatch, dx) -> torch.Tensor:
+    """dY (N, K * O): dY[u, j, :] = the sum of dX over the reverse list of (u, j), in list order."""
+    O = int(dx.shape[-1])
+    ref = _lc_batch(b, O, "lc_rev_sum")
+    dx = _lc_x(dx, "dX", b, O)
+    dy = torch.empty((b.n_sites, b.K * O), dtype=torch.float32, device=dx.device)
+    _lib.call("gcmi_lc_rev_sum", ctypes.byref(ref), _ptr(dx), _ptr(dy), b.K * O, _stream())
+    return dy
+
+
+def lc_running(b: LcBatch, x, running_mean, running_var, num_batches_tracked=None, momentum: float = 0.1):
+    """The running statistics after one BatchNorm update per site, in site order, in closed form; in place."""
+    O = int(x.shape[-1])
+    ref = _lc_batch(b, O, "lc_running")
+    x = _lc_x(x, "X", b, O)
+    if running_mean is None or running_var is None:
+        raise ValueError("lc_running: running_mean and running_var are needed")
+    _vec(running_mean, "running_mean", O), _vec(running_var, "running_var", O)
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or num_batches_tracked.numel() != 1 or
+                                            not num_batches_tracked.is_cuda):
+        raise ValueError("num_batches_tracked must be one int64 on the GPU")
+    _lib.call("gcmi_lc_running", ctypes.byref(ref), _ptr(x), float(momentum), _ptr(running_mean), _ptr(running_var),
+              _ptr(num_batches_tracked), _stream())
+
+
+class LcSiteFn(torch.autograd.Function):
+    """(Y (N, K * O), bias, gamma, beta, mean, var, mask, batch, eps, want_x) -> (out (N, O), X (N, P, O) or None).
+    ``mean`` and ``var`` None: training, each site normalised by its own statistics over P and the backward
+    differentiates through them; otherwise they are constants (eval).  X is written where ``want_x`` asks for it
+    (training: ``lc_running`` reads it) or an input takes a gradient (the backward reads it); it is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, y, bias, gamma, beta, mean, var, mask, b: LcBatch, eps: float, want_x: bool):
+        y = rowmajor(y)
+        bias, gamma, beta = bias.contiguous(), gamma.contiguous(), beta.contiguous()
+        out, x = lc_site_fwd(b, y, bias, gamma, beta, mean, var, eps, mask, bool(want_x) or any(ctx.needs_input_grad[:4]))
+        ctx.b, ctx.eps = b, eps
+        ctx.save_for_backward(x, gamma, mean, var, mask)
+        if x is not None:
+            ctx.mark_non_differentiable(x)
+        return out, x
+
+    @staticmethod
+    def backward(ctx, dout, _dx_unused):
+        x, gamma, mean, var, mask = ctx.saved_tensors
+        O = gamma.numel()
+        dx, sums = lc_site_bwd(ctx.b, x, rowmajor(dout), gamma, mean, var, ctx.eps, mask)
+        return lc_rev_sum(ctx.b, dx), sums[2 * O:], sums[:O], sums[O:2 * O], None, None, None, None, None, None
+
+
 # ------------------------------------------------------------------ atomic convolution (ACNN)
 AC_MAX_NEIGHBORS, AC_MAX_TYPES, AC_MAX_CHANNELS = 64, 32, 2048
 

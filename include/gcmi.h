@@ -1199,6 +1199,52 @@ int gcmi_cg_bwd_edges(const gcmi_gn_graph* g, const float* d_ps, const float* d_
 int gcmi_cg_bwd_src(const gcmi_gn_graph* g, const float* d_dq, int64_t lddq, int32_t H, float* d_dps, int64_t lddp,
                     void* stream);
 
+/* ---------------------------------------------------------------- lattice convolution of LCNN (lcnn.hip)
+ * One LCNNBlock behind its one product, fp32.  n_sites sites with P permutations of K neighbour slots each; O = the
+ * output width.  With conv_weights.weight (O, K * F) split by slot into K blocks W_j (O, F):
+ *     Y = x [W_0; ...; W_{K-1}]^T   (n_sites rows of K * O floats, leading dimension ldy),
+ *     X[v, p, :] = bias + sum over j in order of Y[nbr[v, p, j], j, :]           (n_sites, P, O), contiguous,
+ *     xhat = (X - mean) / sqrt(var + eps);  mean == var == NULL (training): per site and channel, the mean and the
+ *            biased variance over the P rows;  otherwise (eval) the given vectors of O floats, the root in double,
+ *     out[v, :] = sum over p of mask[v, p] * (xhat[v, p, :] * gamma + beta)     mask (n_sites, P), NULL: ones.
+ * Limits: O in [1, GCMI_LC_MAX_WIDTH], P in [GCMI_LC_MIN_PERM, GCMI_LC_MAX_PERM], K in [1, GCMI_LC_MAX_SLOTS],
+ * n_sites * P * K * GCMI_LC_MAX_WIDTH < 2^31.  Every pointer is 4-byte aligned (one channel per lane: no wider access), the
+ * workspace 16-byte.  An index of nbr outside [0, n_sites) or of rev_row outside [0, n_sites * P) is compared with
+ * the size before it is used and contributes nothing.
+ *   gcmi_lc_site_fwd  out, and X when d_x != NULL (the backward and gcmi_lc_running read it).
+ *   gcmi_lc_site_bwd  dX (n_sites, P, O) from X, dOut, mask, gamma: training, the BatchNorm backward over the P rows of
+ *                     each site; eval, dX = mask dOut gamma / sqrt(var + eps).  sums[3 O] = [dgamma | dbeta | dbias], summed per
+ *                     workgroup in double in row order, the workgroups in double by a fixed tree.  Workspace:
+ *                     gcmi_lc_workspace_floats(n_sites, O) floats (-1: bad sizes).
+ *   gcmi_lc_rev_sum   dY[u, j, :] = the sum of dX[rev_row[k], :] for k in [rev_ptr[u K + j], rev_ptr[u K + j + 1]) in
+ *                     that order: the (v, p) with nbr[v, p, j] = u as rows v P + p.  A zero row for an empty list.
+ *   gcmi_lc_running   the running statistics after one update per site in site order, r <- (1 - m) r + m s_v with s_v
+ *                     the mean / the UNBIASED variance of site v, in closed form: r = (1 - m)^N r + m sum_v
+ *                     (1 - m)^(N - 1 - v) s_v with weights and sums in double in a fixed order, over the last 2048
+ *                     sites (the rest cannot reach a float32 result for m >= 0.1, which the entry requires);
+ *                     batches_tracked (optional, int64) += n_sites.
+ * No atomics: two calls agree bit for bit.                                                                             */
+#define GCMI_LC_MAX_WIDTH 64
+#define GCMI_LC_MIN_PERM 2
+#define GCMI_LC_MAX_PERM 8
+#define GCMI_LC_MAX_SLOTS 32
+typedef struct {
+  int32_t n_sites, P, K, O;
+  const int32_t* nbr;     /* (n_sites, P * K) */
+  const int32_t* rev_ptr; /* n_sites * K + 1 */
+  const int32_t* rev_row; /* n_sites * P * K */
+} gcmi_lc_batch;
+int64_t gcmi_lc_workspace_floats(int32_t n_sites, int32_t O);
+int gcmi_lc_site_fwd(const gcmi_lc_batch* b, const float* d_y, int64_t ldy, const float* d_bias, const float* d_gamma,
+                     const float* d_beta, const float* d_mean, const float* d_var, float eps, const float* d_mask,
+                     float* d_out, int64_t ldo, float* d_x, void* stream);
+int gcmi_lc_site_bwd(const gcmi_lc_batch* b, const float* d_x, const float* d_dout, int64_t lddo, const float* d_mask,
+                     const float* d_gamma, const float* d_mean, const float* d_var, float eps, float* d_dx, float* d_sums,
+                     float* d_workspace, int64_t workspace_floats, void* stream);
+int gcmi_lc_rev_sum(const gcmi_lc_batch* b, const float* d_dx, float* d_dy, int64_t lddy, void* stream);
+int gcmi_lc_running(const gcmi_lc_batch* b, const float* d_x, float momentum, float* d_running_mean, float* d_running_var,
+                    int64_t* d_batches_tracked, void* stream);
+
 /* ---------------------------------------------------------------- atomic convolution of ACNN (atomconv.hip)
  * The whole AtomicConvolution layer over B samples of N atom slots with M neighbours each, d = 3 coordinates, fp32.
  *     D[m] = x[b, nbrs[b, n, m]] - x[b, n],  with has_box: D -= rint(D / box) * box (half to even),  R[m] = |D[m]|,
