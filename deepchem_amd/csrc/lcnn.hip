@@ -175,10 +175,13 @@ __global__ __launch_bounds__(kLcThreads) void lc_site_bwd_kernel(gcmi_lc_batch b
         if (p < P) {
           const float dx = a * ((dy[p] - c1) - x[p] * c2);
           dxs[(v * P + p) * O + w.c] = dx;
-          sums[2] += (double)dx;  // db
+          if (train) sums[2] += (double)dx;  // db
         }
       }
     }
+    // eval: dX = (gamma * invstd) dy exactly, so db is that factor times dbeta, in double; the sum of the float32 dX
+    // would carry one rounding per term and the rounding of the factor, the same in every term, on top
+    if (!train) sums[2] = (double)gamma * invstd_d * sums[1];
   }
   // over the rows of the workgroup, rows in order; valid in the threads of row 0
   __shared__ double red[kLcSums][kLcThreads];

@@ -1214,7 +1214,8 @@ int gcmi_cg_bwd_src(const gcmi_gn_graph* g, const float* d_dq, int64_t lddq, int
  *   gcmi_lc_site_fwd  out, and X when d_x != NULL (the backward and gcmi_lc_running read it).
  *   gcmi_lc_site_bwd  dX (n_sites, P, O) from X, dOut, mask, gamma: training, the BatchNorm backward over the P rows of
  *                     each site; eval, dX = mask dOut gamma / sqrt(var + eps).  sums[3 O] = [dgamma | dbeta | dbias], summed per
- *                     workgroup in double in row order, the workgroups in double by a fixed tree.  Workspace:
+ *                     workgroup in double in row order, the workgroups in double by a fixed tree (eval: dbias is
+ *                     gamma / sqrt(var + eps) times dbeta in double, not the sum of the rounded dX).  Workspace:
  *                     gcmi_lc_workspace_floats(n_sites, O) floats (-1: bad sizes).
  *   gcmi_lc_rev_sum   dY[u, j, :] = the sum of dX[rev_row[k], :] for k in [rev_ptr[u K + j], rev_ptr[u K + j + 1]) in
  *                     that order: the (v, p) with nbr[v, p, j] = u as rows v P + p.  A zero row for an empty list.

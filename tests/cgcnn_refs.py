@@ -203,11 +203,16 @@ def sized_graph(rng, n_nodes, n_edges, Fn=5, Fe=3):
 
 def case_graphs(name, Fn=5, Fe=3):
     """The graph batches of the kernel and layer tests by name: 'edge' (``edge_case_graphs``), 'g1' (one small graph),
-    'below' / 'above' (one graph with node and edge counts one below / one above a multiple of 64)."""
+    'below' / 'above' (one graph with node and edge counts one below / one above a multiple of 64), 'cap' (8200 nodes
+    and 8300 edges: at H = 128, 8 rows per workgroup, 1025 node groups and 1038 edge groups, past the 1024 partial rows
+    of csrc/cgcnn.hip), 'tile' (2731 nodes, 4099 edges: the graph the tiling test repeats) and 'pair' (two nodes, the
+    edges 0 -> 1 and 1 -> 0: the smallest batch the statistics accept)."""
     rng = np.random.RandomState(17)
     if name == "edge":
         return edge_case_graphs(rng, Fn, Fe)
     if name == "g1":
         return [random_graph(rng, 10, 28, Fn, Fe)]
-    n, e = {"below": (127, 191), "above": (129, 193)}[name]
+    if name == "pair":
+        return [make_graph([[0, 1], [1, 0]], 2, rng, Fn, Fe)]
+    n, e = {"below": (127, 191), "above": (129, 193), "cap": (8200, 8300), "tile": (2731, 4099)}[name]
     return [sized_graph(rng, n, e, Fn, Fe)]

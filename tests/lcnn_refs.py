@@ -9,6 +9,9 @@ so float64 gradients come from autograd; nothing here touches the package under 
 * ``block_loop``    the literal per-site loop: one ``F.batch_norm`` call per site on its (P, O) rows, which also runs the
                     running-statistics recurrence ``r <- 0.9 r + 0.1 s_v`` in site order; pins the closed form.
 * ``running_loop`` / ``running_closed``  the recurrence and its closed form on per-site statistics.
+* ``site_fwd_ref``, ``site_bwd_ref``, ``rev_sum_ref``, ``running_ref``  the four ops of csrc/lcnn.hip one by one, from Y
+                    (no product ahead of them), in a chosen precision and slot order; ``op_case`` / ``op_references``:
+                    the inputs of an op-level case and the float64 values with the float32 restatements' errors.
 * ``LCNNRef``       the whole model on a state dict; ``fit`` is that of tests/megnet_refs.py with the masks injected.
 * ``torus``, ``random_sites``, ``hub_sites``: the graphs.  ``torus(a, b)`` is an a x b periodic triangular lattice in
   axial coordinates: the 19 sites within two shells as neighbour slots and the six 60-degree rotations (q, r) -> (-r, q
@@ -90,6 +93,125 @@ def block_loop(x, nbr, W, b, gamma, beta, mask, state, training):
         state.tracked += int(training)
         rows.append(xh.sum(0) if mask is None else (_t(mask[v], x.dtype).unsqueeze(1) * xh).sum(0))
     return torch.stack(rows)
+
+
+# ------------------------------------------------------------------------------------------------ the ops one by one
+SLOT_ORDERS = ("asc", "desc")
+OP_NAMES = ("out", "X", "dX", "dgamma", "dbeta", "db", "dY", "rm", "rv")
+
+
+def _g(a, dtype):
+    """``a`` in ``dtype``; a tensor that already has it passes through (so a leaf keeps its place in the graph)."""
+    return a if torch.is_tensor(a) and a.dtype == dtype else _t(a, dtype)
+
+
+def site_fwd_ref(Y, nbr, bias, gamma, beta, mask, mean, var, eps, dtype, slot_order="asc"):
+    """lc_site_fwd: (out (N, O), X (N, P, O)) from Y (N, K * O).  X[v, p] = bias + sum_j Y[nbr[v, p, j], j] with j
+    ascending (``"asc"``, what the kernel does) or descending; ``mean`` None: training, each site's own mean and biased
+    variance over its P rows; ``mask`` (N, P) or None (ones); ``bias`` None: zero."""
+    nbr = torch.as_tensor(np.asarray(nbr), dtype=torch.int64)
+    N, P, K = nbr.shape
+    gamma, beta = _g(gamma, dtype), _g(beta, dtype)
+    O = gamma.numel()
+    Y = _g(Y, dtype).reshape(N, K, O)
+    X = (torch.zeros(O, dtype=dtype) if bias is None else _g(bias, dtype)).expand(N, P, O)
+    for j in (range(K) if slot_order == "asc" else range(K - 1, -1, -1)):
+        X = X + Y[nbr[:, :, j], j]
+    if mean is None:
+        mu, v = X.mean(1, keepdim=True), X.var(1, unbiased=False, keepdim=True)
+    else:
+        mu, v = _g(mean, dtype), _g(var, dtype)
+    Xhat = (X - mu) / torch.sqrt(v + eps) * gamma + beta
+    return (Xhat.sum(1) if mask is None else (_g(mask, dtype).unsqueeze(2) * Xhat).sum(1)), X
+
+
+def site_bwd_ref(Y, nbr, bias, gamma, beta, mask, mean, var, eps, dout, dtype, slot_order="asc"):
+    """lc_site_bwd by autograd on ``site_fwd_ref`` with respect to X: (dX (N, P, O), dgamma, dbeta, db) for the output
+    gradient ``dout`` (N, O)."""
+    gamma, beta = (_t(a, dtype).clone().requires_grad_(True) for a in (gamma, beta))
+    b = (torch.zeros(gamma.numel(), dtype=dtype) if bias is None else _t(bias, dtype).clone()).requires_grad_(True)
+    out, X = site_fwd_ref(Y, nbr, b, gamma, beta, mask, mean, var, eps, dtype, slot_order)
+    dX, dgamma, dbeta, db = torch.autograd.grad((out * _t(dout, dtype)).sum(), [X, gamma, beta, b])
+    return dX, dgamma, dbeta, db
+
+
+def rev_sum_ref(dX, nbr, dtype, slot_order="asc"):
+    """lc_rev_sum: dY (N, K * O), dY[u, j] = the sum of dX[v, p] over the (v, p) with nbr[v, p, j] = u, one term after the
+    other in ascending order of v * P + p (``"asc"``, the kernel's list order) or descending."""
+    nbr = np.asarray(nbr, np.int64)
+    N, P, K = nbr.shape
+    rows = _t(dX, dtype).numpy().reshape(N * P, -1)
+    out = np.zeros((N, K, rows.shape[1]), rows.dtype)
+    step = 1 if slot_order == "asc" else -1
+    for j in range(K):
+        np.add.at(out[:, j], nbr[:, :, j].reshape(-1)[::step], rows[::step])  # (unbuffered: in index order)
+    return torch.as_tensor(out.reshape(N, -1))
+
+
+def running_ref(X, rm0, rv0, momentum, dtype):
+    """lc_running: the literal loop of the N per-site BatchNorm updates in site order, in ``dtype`` throughout: the mean
+    and the unbiased variance over the P rows of site v, then r = (1 - m) r + m s for both."""
+    X = _t(X, dtype)
+    rm, rv = _t(rm0, dtype).clone(), _t(rv0, dtype).clone()
+    P = X.shape[1]
+    for v in range(X.shape[0]):
+        mean = X[v].sum(0) / P
+        var = ((X[v] - mean) ** 2).sum(0) / (P - 1)
+        rm = (1 - momentum) * rm + momentum * mean
+        rv = (1 - momentum) * rv + momentum * var
+    return rm, rv
+
+
+_OP_CASES = {}
+# cases whose two float32 slot orders lay more than 4 times apart at the first seed (on the CPU, before any GPU run):
+# the seed of their values moved on, the sites stay
+OP_RESEED = {}
+
+
+def op_case(O, P, K, n_sites, training):
+    """The inputs of one op-level case (cached): random sites, Y drawn N(0, 1) directly, gamma in [0.5, 1.5], the mask
+    of the block tests (kept rows / 0.8 in training, ones in eval)."""
+    key = (O, P, K, n_sites, bool(training))
+    if key not in _OP_CASES:
+        seed = 7 + O + 64 * (P + 8 * (K + 32 * (n_sites % 9973)))
+        graph = random_sites(np.random.RandomState(seed), n_sites, P, K, 1)
+        rng = np.random.RandomState(seed + 1 + OP_RESEED.get((O, P, K, n_sites), 0))
+        f = lambda a: a.astype(np.float32)  # noqa: E731
+        c = dict(O=O, P=P, K=K, N=n_sites, training=bool(training), graph=graph, nbr=table_of(graph, P, K),
+                 Y=f(rng.normal(0, 1, (n_sites, K * O))), b=f(rng.normal(0, 0.3, O)), gamma=f(rng.uniform(0.5, 1.5, O)),
+                 beta=f(rng.normal(0, 0.3, O)), rm=f(rng.normal(0, 0.3, O)), rv=f(rng.uniform(0.5, 2, O)),
+                 cot=f(rng.normal(0, 1, (n_sites, O))))
+        c["mask"] = f((rng.rand(n_sites, P) >= 0.2) / 0.8) if training else np.ones((n_sites, P), np.float32)
+        _OP_CASES[key] = c
+    return _OP_CASES[key]
+
+
+def op_chain(c, dtype, slot_order):
+    """The four ops one after the other on a case, as the GPU test calls them: forward, backward of ``cot``, reverse
+    sum of dX, and in training the running statistics from X.  Float64 arrays by ``OP_NAMES``."""
+    stats = (None, None) if c["training"] else (c["rm"], c["rv"])
+    args = (c["Y"], c["nbr"], c["b"], c["gamma"], c["beta"], c["mask"]) + stats + (EPS,)
+    out, X = site_fwd_ref(*args, dtype, slot_order)
+    dX, dgamma, dbeta, db = site_bwd_ref(*args, c["cot"], dtype, slot_order)
+    dY = rev_sum_ref(dX, c["nbr"], dtype, slot_order)
+    rm, rv = running_ref(X, c["rm"], c["rv"], MOMENTUM, dtype) if c["training"] else (_t(c["rm"], dtype), _t(c["rv"], dtype))
+    vals = (out, X, dX, dgamma, dbeta, db, dY, rm, rv)
+    return {n: v.detach().double().numpy() for n, v in zip(OP_NAMES, vals)}
+
+
+def op_references(c):
+    """(float64 values by name, e32 by name: the larger error of the float32 chains in the two slot orders, and the
+    largest ratio between the two orders' errors over the tensors), cached on the case."""
+    if "refs" not in c:
+        want = op_chain(c, torch.float64, "asc")
+        errs = {n: [] for n in OP_NAMES}
+        for order in SLOT_ORDERS:
+            got = op_chain(c, torch.float32, order)
+            for n in OP_NAMES:
+                errs[n].append(float(np.max(np.abs(got[n] - want[n]))))
+        spread = max([max(e) / max(min(e), 1e-300) for e in errs.values() if max(e) > 0] or [1.0])
+        c["refs"] = (want, {n: max(e) for n, e in errs.items()}, spread)
+    return c["refs"]
 
 
 # ------------------------------------------------------------------------------------------------ the model
