@@ -18,6 +18,12 @@
 // the end of the segment.  Arithmetic = the exact three-way bf16 split of gemm_split.hip (six products per term on
 // v_mfma_f32_32x32x16_bf16, fp32 accumulation).  A block that needs no input gradient (the first GraphConv) runs
 // the four weight-gradient waves only.
+//
+// The dense fp32 form (RD && !HB) splits its In rows -- the pooled rows, the same eight fragments for all four
+// weight-gradient waves -- once per tile: all 512 threads transpose what they prefetched across the lanes of their
+// wave in phase (a) and store the three bf16 pieces as an image [piece][column][row] in LDS (in_img_col), published by
+// the barrier that was there; a weight-gradient wave reads an In fragment as three ds_read_b128, splits only its own
+// columns of G, and requests the next tile's rows behind its products instead of in front of them.
 #include <atomic>
 #include <type_traits>
 
@@ -61,6 +67,27 @@ struct FusedArgs {
   unsigned long long* diag;
 };
 
+// The In image of the dense fp32 form: the place of column c of In among the 64 columns of a piece.  A column is 144
+// bytes (36 banks) apart from the next, so places that differ mod 16 lie in different 16-byte slots of the 256-byte
+// bank row.  A ds_read_b128 of a weight-gradient wave is served in groups of 16 lanes that hold every value of
+// c mod 16 once, with c bit 4 a function of c bits 2..3 within a group: the low four bits of the place must be a
+// bijection of c bits 0..3 there.  The phase (a) stores (8 bytes, 16 consecutive lanes = columns 4q + j, q = 0..15, at
+// one row offset; banks mod 32) need the low THREE bits of the place to take all eight values over q, which the
+// identity does not (c mod 8 has two): so place bits 0..3 = c bits 2, 3, 0 ^ 4, 1.  Bits 4..5 stay.
+__host__ __device__ constexpr int in_img_col(int c) {
+  return (c & 0x30) | ((c >> 2) & 3) | (((c ^ (c >> 4)) & 1) << 2) | ((c & 2) << 2);
+}
+constexpr bool in_img_col_is_a_permutation() {
+  unsigned long long seen = 0;
+  for (int c = 0; c < 64; ++c) {
+    const int p = in_img_col(c);
+    if (p < 0 || p > 63 || (p & 0x20) != (c & 0x20) || (seen >> p & 1ull)) return false;
+    seen |= 1ull << p;
+  }
+  return seen == ~0ull;
+}
+static_assert(in_img_col_is_a_permutation(), "in_img_col must be a permutation that keeps the 32-column group");
+
 // HB: the block's forward activations (x = its ReLU output, In = its inputs) are stored as bf16
 // (gcmi_model_desc.storage == 1): they arrive as 8-byte pieces of four elements -- half the prefetch registers -- and
 // are widened on their way to LDS; a weight-gradient fragment of In then IS its own first bf16 piece (one v_perm_b32
@@ -97,13 +124,22 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
   constexpr int IPASS = kFRows * IQ / NT;     // passes of the In loads, per operand
   constexpr int STEPS = kFRows / 16;          // k-steps of the weight-gradient contraction
   // the weight-gradient waves interleave the split of the next fragment with the MFMAs of the current one; the
-  // dense-layer form has no registers left for that (80 hold its prefetched rows) and only reads a fragment ahead
+  // bf16 dense-layer forms have no registers left for that (80 hold their prefetched rows) and only read a fragment
+  // ahead (the fp32 dense-layer form has its own branch: INIMG)
   constexpr bool INTERLEAVE = !RD;
   constexpr int OT = NOPS * KT;               // 32-column tiles of the input gradients
   constexpr int TPW = OT / 2;                 // ... per dgrad wave (two waves per 32-row block)
   constexpr int OP = OT * 32 + 8;             // pitch of a row of the input-gradient tile in LDS (floats)
   constexpr int OQ = OT * 8;                  // its 16-byte pieces
   constexpr int OPASS = DGRAD ? kFRows * OQ / NT : 1;
+  // The dense fp32 form splits In ONCE per tile, in phase (a), by all threads: the four weight-gradient waves read the
+  // same eight In fragments (they differ in their column group of G only), so what `read_frag` + `split_frag` would
+  // build per wave stands in LDS as a prepared image [piece][column of In][row] of bf16 (in_img_col, kImgPitch).
+  constexpr bool INIMG = RD && !HB;
+  constexpr int kImgPitch = 2 * kFRows + 16;  // bytes of one column: 64 rows of bf16 and one 16-byte entry of padding
+  constexpr int kImgPiece = KP * kImgPitch;   // bytes of one piece
+  static_assert(!INIMG || (DGRAD && NOPS == 1 && NT == 512 && IQ == 16 && KP == 64),
+                "the In image: four rows of a pass in the four 16-lane rows of a wave, 64 columns");
   static_assert(NOPS * NJ == 4, "four weight-gradient waves: one (operand, column group) each");
   static_assert(!DGRAD || (OT % 2 == 0), "input-gradient tiles split over two waves per row block");
   static_assert(kFRows * IQ % NT == 0, "In tile loads divide evenly");
@@ -112,6 +148,7 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
   float* Ins = Gs + kFRows * GP;                                   // [NOPS][64][IP]
   unsigned short* Wimg = reinterpret_cast<unsigned short*>(Ins + NOPS * kFRows * IP);
   float* Outs = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(Wimg) + kWBytes);  // [64][OP] (DGRAD)
+  unsigned char* InImg = reinterpret_cast<unsigned char*>(Outs + kFRows * OP);               // [3][KP][kImgPitch] (INIMG)
   __shared__ SegTableLds tl;  // (tl.b: the bias-gradient rows)
   __shared__ __attribute__((aligned(16))) float coef_s[3 * NG];  // [A | B | C] of the BatchNorm backward
   __shared__ double stat_s[2][DGRAD ? KP : 1];                   // sum dP | sum dP * P per input column (psums)
@@ -404,6 +441,28 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
         v.z = (ok && tail > 2) ? v.z : 0.f;
         v.w = (ok && tail > 3) ? v.w : 0.f;
         *reinterpret_cast<float4*>(Ins + (o * kFRows + r) * IP + 4 * q) = v;
+        if constexpr (INIMG) {
+          // The four rows r0 .. r0 + 3 of this pass (r0 = 4 * wave + 32 * p) lie in the four 16-lane rows of the
+          // wave: a 4 x 4 transposition across lanes 16 apart (register bit 1 <-> lane bit 5, register bit 0 <-> lane
+          // bit 4) leaves the thread in lane row j with column 4q + j of rows r0 .. r0 + 3: two row pairs, split
+          // exactly as split_frag splits (raw[2i], raw[2i + 1]), 8 bytes per piece of the 16-byte entry of rows
+          // 8 * (r0 / 8) .. + 7.  (all 512 threads are here: the swaps need every lane)
+          unsigned t0 = __float_as_uint(v.x), t1 = __float_as_uint(v.y), t2 = __float_as_uint(v.z), t3 = __float_as_uint(v.w);
+          auto s02 = __builtin_amdgcn_permlane32_swap(t0, t2, false, false);
+          t0 = s02[0]; t2 = s02[1];
+          auto s13 = __builtin_amdgcn_permlane32_swap(t1, t3, false, false);
+          t1 = s13[0]; t3 = s13[1];
+          auto s01 = __builtin_amdgcn_permlane16_swap(t0, t1, false, false);
+          t0 = s01[0]; t1 = s01[1];
+          auto s23 = __builtin_amdgcn_permlane16_swap(t2, t3, false, false);
+          t2 = s23[0]; t3 = s23[1];
+          uint2 pc[3];
+          split3_pair(__uint_as_float(t0), __uint_as_float(t1), pc[0].x, pc[1].x, pc[2].x);
+          split3_pair(__uint_as_float(t2), __uint_as_float(t3), pc[0].y, pc[1].y, pc[2].y);
+          unsigned char* dst = InImg + in_img_col(4 * (lane & 15) + (lane >> 4)) * kImgPitch + 8 * wave + 64 * p;
+#pragma unroll
+          for (int s = 0; s < 3; ++s) *reinterpret_cast<uint2*>(dst + s * kImgPiece) = pc[s];
+        }
       }
     }
     if (stamp) { t1 = wall_clock64(); d_a += t1 - t0; }
@@ -413,8 +472,11 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
     // ---- phase (b): next tile's sources in flight, products from LDS
     int n2seg = nseg, n2row0 = nrow0, n2valid = nvalid;
     if (i + 2 < my_tiles) tile_info(tiles.at(i + 2), n2seg, n2row0, n2valid);
-    load_src(nrow0, nvalid);             // uses mem1 = molecule indices of the next tile (read when the loads issue)
-    load_mem(n2row0, n2valid, mem1);     // ... which the indices of the tile after it then replace
+    // (the In-image form: its weight-gradient waves request the next tile BEHIND their products, see there)
+    if (!(INIMG && !is_dgrad)) {
+      load_src(nrow0, nvalid);           // uses mem1 = molecule indices of the next tile (read when the loads issue)
+      load_mem(n2row0, n2valid, mem1);   // ... which the indices of the tile after it then replace
+    }
     if (is_dgrad) {
       if constexpr (DGRAD) {
         // input gradients of this tile: `accs` starts from zero (the weight-gradient waves keep theirs across tiles)
@@ -478,7 +540,91 @@ fused_bwd_kernel(SegTable st, int n_tiles, FusedArgs a, int rev) {
       // fragment f + 1 are issued before fragment f is split and multiplied: with two waves per SIMD nobody else
       // hides their latency.
       constexpr int FPS = 1 + KT, NF = STEPS * FPS;
-      if constexpr (INTERLEAVE) {
+      if constexpr (INIMG) {
+      // The In fragments come ready-made from the image of phase (a): three ds_read_b128 each, no `raw` and no split.
+      // Only the G fragment of a 16-row step is read as rows and split here.  Per (fragment, accumulator) the six
+      // MFMAs of mfma_split6 in its order, the fragments of an accumulator in the order of the steps.  A wave issues
+      // in order and the six MFMAs of a chain depend on each other, so what else the wave has to do goes between
+      // them: the split of the NEXT step's G in four quarters between the MFMAs of the step's first In fragment, and
+      // the three reads of the next In fragment, each behind the last product that reads the piece it replaces (In as
+      // operand B is read in the order 1 3 2 1 2 1; piece 1 goes to registers of its own, three products ahead).
+      // (`on` is not looked at: with no weight block the products go into accumulators that flush_w drops)
+      const unsigned char* ibase = InImg + in_img_col(l31) * kImgPitch + 16 * half;
+      auto in_piece = [&](int f, int pc) -> u32x4 {  // f = 16-row step * KT + 32-column group (in_img_col keeps it)
+        return *reinterpret_cast<const u32x4*>(ibase + (f % KT) * 32 * kImgPitch + 32 * (f / KT) + pc * kImgPiece);
+      };
+      float raw[8];
+      auto read_g = [&](int st_) {
+        const float* src = Gs + (16 * st_ + 8 * half) * GP + wj * 32 + l31;  // zero beyond `valid`
+#pragma unroll
+        for (int u = 0; u < 8; ++u) raw[u] = src[u * GP];
+      };
+      auto add_bsum = [&]() {
+        if (wo == 0) {
+#pragma unroll
+          for (int u = 0; u < 8; ++u) bsum += raw[u];
+        }
+      };
+      constexpr int NIF = STEPS * KT;
+      read_g(0);
+      Frag3 fa = {{in_piece(0, 0), in_piece(0, 1), in_piece(0, 2)}}, fg, fgn;
+      add_bsum();
+      fgn = split_frag(raw);
+      if (STEPS > 1) read_g(1);
+      unsigned q[3][4];
+#pragma unroll
+      for (int f = 0; f < NIF; ++f) {
+        const int st_ = f / KT, t = f - st_ * KT;
+        if (t == 0) fg = fgn;
+        const bool more = f + 1 < NIF;
+        const bool split_next = t == 0 && st_ + 1 < STEPS;  // this chain carries the split of the next step's G
+        if (split_next) add_bsum();
+        auto pair_split = [&](int i) {
+          if (split_next) split3_pair(raw[2 * i], raw[2 * i + 1], q[0][i], q[1][i], q[2][i]);
+          __builtin_amdgcn_sched_barrier(0);
+        };
+        const Frag3& L = TRANS ? fg : fa;
+        const Frag3& R = TRANS ? fa : fg;
+        Frag3 nf = fa;
+        // mfma_split6(accs[t], L, R) spelled out, in its order
+        accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[2]), as_bf16x8(R.p[0]), accs[t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        pair_split(0);
+        accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[2]), accs[t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more && TRANS) nf.p[2] = in_piece(f + 1, 2);
+        pair_split(1);
+        accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[1]), as_bf16x8(R.p[1]), accs[t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more && TRANS) nf.p[0] = in_piece(f + 1, 0);
+        pair_split(2);
+        accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[1]), as_bf16x8(R.p[0]), accs[t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        pair_split(3);
+        accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[1]), accs[t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more && TRANS) nf.p[1] = in_piece(f + 1, 1);
+        if (split_next && st_ + 2 < STEPS) read_g(st_ + 2);  // `raw` is free: the G rows of the step after next
+        __builtin_amdgcn_sched_barrier(0);
+        accs[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf16x8(L.p[0]), as_bf16x8(R.p[0]), accs[t], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more && !TRANS) nf = {{in_piece(f + 1, 0), in_piece(f + 1, 1), in_piece(f + 1, 2)}};
+        fa = nf;
+        if (split_next) {
+#pragma unroll
+          for (int pc = 0; pc < 3; ++pc) {
+            fgn.p[pc].x = q[pc][0]; fgn.p[pc].y = q[pc][1]; fgn.p[pc].z = q[pc][2]; fgn.p[pc].w = q[pc][3];
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // The next tile's sources, requested here and not in front of the products: with all eight waves asking at
+      // once the memory pipeline takes 2.4 us to accept the last wave's 22 loads (phase clocks), and
+      // these waves' products, 1.6 us that need nothing from memory, would only start then.  The input-gradient waves
+      // ask first and have the queue to themselves; these waves' requests follow while those still multiply.
+      load_src(nrow0, nvalid);
+      load_mem(n2row0, n2valid, mem1);
+      } else if constexpr (INTERLEAVE) {
       float raw[8];
       auto read_frag = [&](int f) {
         const int st_ = f / FPS, w_ = f - st_ * FPS;
@@ -674,6 +820,7 @@ static int launch_fused(const SegTable& st, int n_tiles, const FusedArgs& a, hip
   size_t shmem = sizeof(float) * kFRows * (NG + 4) + sizeof(float) * (size_t)NOPS * kFRows * (KP + 4);
   if (DGRAD)
     shmem += sizeof(unsigned short) * (size_t)NOPS * 3 * KP * (NG + 8) + sizeof(float) * kFRows * (NOPS * KT * 32 + 8);
+  if (RD && !HB) shmem += (size_t)3 * KP * (2 * kFRows + 16);  // the In image of the dense fp32 form
   auto kern = fused_bwd_kernel<NG, KT, NOPS, TRANS, RD, DGRAD, HB, GB, IB>;
   // exactly what is asked for: the kernel also has a few hundred bytes of static LDS (the segment table)
   static LdsLimit lim;  // per instantiation
