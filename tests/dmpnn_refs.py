@@ -10,6 +10,8 @@ rows are zero, so the two agree.  State-dict keys are the reference's.
 import numpy as np
 import torch
 
+from tests.yardstick import f32_threads
+
 U = 2.0 ** -24  # unit roundoff of float32
 
 
@@ -322,8 +324,10 @@ def update_ref(dtype, x, inp, W, out_ptr, rev, relu):
 
 
 def update_f32(x, inp, W, out_ptr, rev, relu):
-    """The D-MPNN bond update in float32 on the CPU: the yardstick of the edge tests' bar."""
-    return update_ref(torch.float32, x, inp, W, out_ptr, rev, relu)
+    """The D-MPNN bond update in float32 on the CPU: the yardstick of the edge tests' bar, at one thread like
+    ``dtnn_refs.pair_f32`` (its largest case gives the same bits at 1, 2, 8 and 16 threads; the pin keeps it so)."""
+    with f32_threads(1):
+        return update_ref(torch.float32, x, inp, W, out_ptr, rev, relu)
 
 
 def update_f64(x, inp, W, out_ptr, rev, relu):

@@ -7,6 +7,8 @@ State-dict keys are the reference's, so its parameters load directly into ``DTNN
 import numpy as np
 import torch
 
+from tests.yardstick import any_order_e32, f32_threads
+
 
 def gaussians(distance, distance_min, distance_max, n_distance, dtype=torch.float64):
     """exp(-(d - s_k)^2 / (2 step^2)), s_k = distance_min + k step, computed in ``dtype`` from ``distance``."""
@@ -196,8 +198,81 @@ def pair_f64(gauss, c, chunk=32768):
 
 def pair_f32(gauss, c, chunk=32768):
     """The same restatement in float32 on the CPU, forward and autograd backward: the yardstick of the edge tests' bar
-    (what plain float32 arithmetic makes of the case)."""
-    return pair_grads(torch.float32, gauss, c, chunk)
+    (what plain float32 arithmetic makes of the case).  One thread: the float32 ``index_add_`` of ``pair_sum`` and of
+    its backward follow the thread count and are not repeatable above one, so only the sequential run is a number."""
+    with f32_threads(1):
+        return pair_grads(torch.float32, gauss, c, chunk)
+
+
+def pair_addends(gauss, c, grids=None):
+    """What csrc/dtnn.hip adds with float atomics, formed in float64: per tensor of ``PAIR_TENSORS``
+    ``(addends (A, C), row of each addend, rows)``.
+
+    * Y: one partial per (run of equal first atoms, 32-pair tile), added to row ``mem_i`` (forward, after the tanh).
+    * d_ah: one addend per pair, added to row ``mem_j``.
+    * d_W_df, d_b_df, d_W_fc: one partial per persistent wave of the backward launch, the tensor flattened to one row;
+      wave ``w`` of ``nw = 4 * grid`` owns the tiles ``w, w + nw, ...`` (``grids``: ``(dtnn_grid(P, False),
+      dtnn_grid(P, True))``, by default of this case's P).
+
+    With t = tanh(hid W_fc), hid = (g W_df + b_df) * ah[j], dpre = dY[i] (1 - t^2) and dhid = dpre W_fc^T the per-pair
+    terms are: d_ah dhid * (g W_df + b_df); d_b_df dhid * ah[j]; d_W_df g^T (dhid * ah[j]); d_W_fc hid^T dpre.  Every
+    partial is an exact (float64) sum, so what ``any_order_e32`` makes of them is the order-dependent error alone."""
+    g = np.asarray(gauss.numpy() if torch.is_tensor(gauss) else gauss, np.float64)
+    ah, W_df, b_df, W_fc, dY = (np.asarray(c[k], np.float64) for k in ("ah", "W_df", "b_df", "W_fc", "dY"))
+    mem_i, mem_j = np.asarray(c["mem_i"], np.int64), np.asarray(c["mem_j"], np.int64)
+    N, P = c["N"], mem_i.shape[0]
+    K, H = W_df.shape
+    E = W_fc.shape[1]
+    fwd, bwd = grids if grids is not None else (dtnn_grid(P, False), dtnn_grid(P, True))
+    if fwd[2] != (P + 31) // 32 or bwd[2] != fwd[2]:
+        raise ValueError("pair_addends: the grids are not those of %d pairs" % P)
+    dh = g @ W_df + b_df
+    hid = dh * ah[mem_j]
+    t = np.tanh(hid @ W_fc)
+    dpre = dY[mem_i] * (1.0 - t * t)
+    dhid = dpre @ W_fc.T
+    ddh = dhid * ah[mem_j]
+    tile = np.arange(P) // 32
+    if P:
+        first = np.nonzero(np.r_[True, (mem_i[1:] != mem_i[:-1]) | (tile[1:] != tile[:-1])])[0]
+        y_part, y_row = np.add.reduceat(t, first, axis=0), mem_i[first]
+    else:
+        y_part, y_row = np.zeros((0, E)), np.zeros(0, np.int64)
+    nw = bwd[0] * DTNN_WAVES
+    wave = tile % nw
+    order = np.argsort(wave, kind="stable")
+    start = np.searchsorted(wave[order], np.arange(nw + 1))
+    dwdf, dbdf, dwfc = np.zeros((nw, K * H)), np.zeros((nw, H)), np.zeros((nw, H * E))
+    for w in range(nw):
+        sel = order[start[w]:start[w + 1]]
+        if sel.size:
+            dwdf[w] = (g[sel].T @ ddh[sel]).reshape(-1)
+            dbdf[w] = ddh[sel].sum(0)
+            dwfc[w] = (hid[sel].T @ dpre[sel]).reshape(-1)
+    one_row = np.zeros(nw, np.int64)
+    return {"Y": (y_part, y_row, N), "d_ah": (dhid * dh, mem_j, N), "d_W_df": (dwdf, one_row, 1),
+            "d_b_df": (dbdf, one_row, 1), "d_W_fc": (dwfc, one_row, 1)}
+
+
+def composed(addends):
+    """The float64 sums of ``pair_addends``, (rows, C) each: ``pair_f64``'s tensors, the three parameter gradients as
+    one flattened row."""
+    out = {}
+    for k, (a, row, rows) in addends.items():
+        total = np.zeros((rows, a.shape[1]))
+        np.add.at(total, row, a)
+        out[k] = total
+    return out
+
+
+def pair_e_order(gauss, c, want, orders=8, seed=0):
+    """Per tensor: ``any_order_e32`` of the kernel's addends relative to the largest entry of ``want[k]`` (the scale of
+    ``rel_err``): the error float32 accumulation in arrival order may make of a correct kernel's own addends."""
+    out = {}
+    for k, (a, row, rows) in pair_addends(gauss, c).items():
+        scale = max(float(np.max(np.abs(want[k]))), 1e-30) if np.asarray(want[k]).size else 1.0
+        out[k] = any_order_e32(a, row, rows, scale, orders, seed)
+    return out
 
 
 def collate_ref(z_all, dist_all, n_all, mol_idx):

@@ -21,6 +21,7 @@ from deepchem_amd.utils.synthetic import (PackedMols, concat_packed, single_atom
                                           synthetic_molecules)
 from oracle import graphconv_oracle as O
 from oracle import mol_graphs_oracle as MO
+from tests.yardstick import f32_threads
 
 BOUND = 1e-4          # the project's per-tensor gradient bound (tests/test_gpu_fused_bwd.py holds the large step to it)
 Q1_MAX = 2.5e-5       # float32 oracle against float64 oracle: a quarter of the bound
@@ -286,14 +287,6 @@ Reference = collections.namedtuple("Reference", "loss outs grads state")
 F32_THREADS = 8
 
 
-@contextlib.contextmanager
-def _torch_threads(n):
-    prev = torch.get_num_threads()
-    torch.set_num_threads(n)
-    try:
-        yield
-    finally:
-        torch.set_num_threads(prev)
 
 
 def _reference(step):
@@ -306,7 +299,7 @@ def references(model_id, kind, seed, grad_mode):
     """(float64, float32) oracle steps of one case; computed once per process, shared, never modified."""
     packed, y, w, cfg, state, n_real = case_inputs(model_id, kind, seed)
     r64 = _reference(oracle_step(packed, y, w, cfg, state, grad_mode, n_real, double=True))
-    with _torch_threads(F32_THREADS):
+    with f32_threads(F32_THREADS):
         r32 = _reference(oracle_step(packed, y, w, cfg, state, grad_mode, n_real, double=False))
     return r64, r32
 
@@ -331,7 +324,7 @@ def qualify_inputs(packed, y, w, cfg, state, n_real, grad_mode, draw_seed=0, ref
     unperturbed one.  ``refs``: the (float64, float32) oracle steps where the caller already has them."""
     if refs is None:
         r64 = _reference(oracle_step(packed, y, w, cfg, state, grad_mode, n_real, double=True))
-        with _torch_threads(F32_THREADS):
+        with f32_threads(F32_THREADS):
             r32 = _reference(oracle_step(packed, y, w, cfg, state, grad_mode, n_real, double=False))
     else:
         r64, r32 = refs

@@ -25,6 +25,7 @@ from tests import cgcnn_refs as R
 from tests.test_cgcnn_host import (FE, FN, H as FIX_H, LAYERS, MODES, SIZES, case_batch, check_first_batch, check_fit,
                                    check_layer, close, fixture_dataset, fixture_model, graph_data, layer_case, load_layer)
 from tests.test_gpu_mat import bar
+from tests.yardstick import f32_threads, restatement_threads
 
 DEV = "cuda:0"
 WIDTHS = [4, 60, 64, 68, 128]
@@ -56,18 +57,19 @@ def kernel_case(name, hidden, training, offset=0.0):
     c["rv0"] = rng.uniform(0.5, 2, 2 * hidden).astype(np.float32)
     tei = torch.as_tensor(ei)
     for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
-        P, Q, h, gamma, beta = (torch.tensor(c[n], dtype=dtype, requires_grad=True) for n in ("P", "Q", "h", "gamma", "beta"))
-        state = R.BNState(2 * hidden, dtype, c["rm0"], c["rv0"])
-        out = R.conv_pass(P, Q, h, gamma, beta, tei, state, training)
-        (out * torch.tensor(c["cot"], dtype=dtype)).sum().backward()
-        res = {"out": out.detach().numpy(), "dP": P.grad.numpy(), "dQ": Q.grad.numpy(), "dh": h.grad.numpy(),
-               "dgamma": gamma.grad.numpy(), "dbeta": beta.grad.numpy()}
-        if training:
-            with torch.no_grad():
-                z = (P[:, :2 * hidden][tei[0]] + P[:, 2 * hidden:][tei[1]]) + Q
-                res.update(mean=z.mean(0).numpy(), invstd=torch.rsqrt(z.var(0, unbiased=False) + R.EPS).numpy(),
-                           rm=state.mean.numpy(), rv=state.var.numpy())
-        c[tag] = res
+        with restatement_threads(dtype, 1):  # (its scatter-adds are repeatable at one thread only)
+            P, Q, h, gamma, beta = (torch.tensor(c[n], dtype=dtype, requires_grad=True) for n in ("P", "Q", "h", "gamma", "beta"))
+            state = R.BNState(2 * hidden, dtype, c["rm0"], c["rv0"])
+            out = R.conv_pass(P, Q, h, gamma, beta, tei, state, training)
+            (out * torch.tensor(c["cot"], dtype=dtype)).sum().backward()
+            res = {"out": out.detach().numpy(), "dP": P.grad.numpy(), "dQ": Q.grad.numpy(), "dh": h.grad.numpy(),
+                   "dgamma": gamma.grad.numpy(), "dbeta": beta.grad.numpy()}
+            if training:
+                with torch.no_grad():
+                    z = (P[:, :2 * hidden][tei[0]] + P[:, 2 * hidden:][tei[1]]) + Q
+                    res.update(mean=z.mean(0).numpy(), invstd=torch.rsqrt(z.var(0, unbiased=False) + R.EPS).numpy(),
+                               rm=state.mean.numpy(), rv=state.var.numpy())
+            c[tag] = res
     _CASES[key] = c
     return c
 
@@ -181,6 +183,12 @@ def layer_restatement(c, dtype, steps=1):
     return res, state.tracked, Q.grad.numpy()
 
 
+def layer_f32(c, steps=1):
+    """The float32 yardstick of ``check_native_layer``, at one thread (repeatable at no other count)."""
+    with f32_threads(1):
+        return layer_restatement(c, torch.float32, steps)
+
+
 def native_layer(c, steps=1):
     hidden, fe = c["h"].shape[1], c["e"].shape[1]
     layer = CGCNNLayer(hidden, fe, batch_norm=c["with_bn"]).to(DEV)
@@ -204,7 +212,7 @@ def native_layer(c, steps=1):
 
 def check_native_layer(c, label, steps=1):
     want64, tracked, dz64 = layer_restatement(c, torch.float64, steps)
-    want32, _, _ = layer_restatement(c, torch.float32, steps)
+    want32, _, _ = layer_f32(c, steps)
     got, got_tracked = native_layer(c, steps)
     assert got_tracked == tracked == (steps if c["with_bn"] and c["training"] else 0)
     worst = 0.0

@@ -5,7 +5,7 @@ Exact cases: x, input in [-4, 4] and W in [-2, 2], all integers.  Every bf16 pie
 product and partial sum an integer below 2^24, so the fused result must equal the float64 one bit for bit -- whatever
 the order of the six piece products or of the staging sums.
 Accuracy cases: ``rel_err <= max(4 * e32, 1e-6)`` relative to the largest entry of the float64 restatement, ``e32`` the
-error of the same restatement in float32 on the CPU (dmpnn_refs.update_f32) on the same case; the floor is the 1e-6 the
+error of the same restatement in float32 on the CPU (dmpnn_refs.update_f32, at one thread) on the same case; the floor is the 1e-6 the
 project recorded for this kernel on the MI355X (there is no transcendental function in it: the floor only covers the
 six-term split standing in for a float32 product).  Every check prints ``rel_err / bar``; the last test prints the worst per NB.
 """

@@ -2,10 +2,15 @@
 both input forms, pair lists that are not whole molecules, the grid caps, leading dimensions / alignment / accumulation
 through the C ABI, and the device collation at every ``chunk`` of its offsets kernel.
 
-Bar, per tensor (Y, d_ah, dW_df, db_df, dW_fc): ``rel_err <= max(4 * e32, 1e-6)``, errors relative to the tensor's
-largest entry in the float64 restatement (dtnn_refs.pair_f64).  ``e32`` is the error of the SAME restatement run in
-float32 on the CPU (dtnn_refs.pair_f32) on the same case, computed here; the factor 4 over a float32 yardstick is the one
-test_model_fit_follows_the_reference uses.  The floor is 2.5 x the 4e-7 recorded for these kernels on the MI355X when
+Bar, per tensor (Y, d_ah, dW_df, db_df, dW_fc): ``rel_err <= max(4 * max(e32, e_order), 1e-6)``, errors relative to the
+tensor's largest entry in the float64 restatement (dtnn_refs.pair_f64).  ``e32`` is the error of the SAME restatement run
+in float32 on the CPU (dtnn_refs.pair_f32, at one thread: its scatter-adds are repeatable at no other count) on the same
+case, computed here; the factor 4 over a float32 yardstick is the one test_model_fit_follows_the_reference uses.
+``e_order`` (dtnn_refs.pair_e_order) is what float32 accumulation, one addend after another in 8 seeded random orders,
+makes of the float64 addends the kernel adds with float atomics: Y per (run, tile), d_ah per pair, dW_df / db_df / dW_fc
+per persistent wave.  torch's float32 sums are blocked, so ``e32`` alone says nothing about a chain of 2 000 atomics in
+arrival order; ``e_order`` is that part of the yardstick, from the reference alone, and on short pair lists it lies below
+``e32``.  The floor is 2.5 x the 4e-7 recorded for these kernels on the MI355X when
 they were added, and stands for the ASSUMPTION that the device's ``tanhf`` / ``exp2f`` are accurate to a few ulp: where the
 CPU's float32 run happens to be nearly exact the kernel is still allowed float32 rounding of its transcendental
 functions.  Every check prints ``rel_err / bar``; the worst per tensor and instantiation is printed by the last test.
@@ -52,20 +57,21 @@ def lists():
 LISTS = lists()
 
 
-def bar_of(e32):
-    return max(FACTOR * e32, FLOOR)
+def bar_of(e32, e_order):
+    return max(FACTOR * max(e32, e_order), FLOOR)
 
 
 def references(c, K):
-    """Per input form: (float64 restatement, e32 per tensor).  Form (b) is handed the float32-rounded Gaussian matrix,
-    so both of its references start from that matrix; form (a)'s float32 yardstick generates its Gaussians in float32."""
+    """Per input form: (float64 restatement, e32 per tensor, e_order per tensor).  Form (b) is handed the
+    float32-rounded Gaussian matrix, so its references start from that matrix; form (a)'s float32 yardstick generates
+    its Gaussians in float32."""
     g64 = R.gaussians(c["d"].astype(np.float64), DMIN, DMAX, K, torch.float64)
     g32 = g64.to(torch.float32)
     want_a, want_b = R.pair_f64(g64, c), R.pair_f64(g32, c)
     f32_a = R.pair_f32(R.gaussians(c["d"], DMIN, DMAX, K, torch.float32), c)
     f32_b = R.pair_f32(g32, c)
-    return {True: (want_a, {k: R.rel_err(f32_a[k], want_a[k]) for k in want_a}),
-            False: (want_b, {k: R.rel_err(f32_b[k], want_b[k]) for k in want_b})}, g32
+    return {True: (want_a, {k: R.rel_err(f32_a[k], want_a[k]) for k in want_a}, R.pair_e_order(g64, c, want_a)),
+            False: (want_b, {k: R.rel_err(f32_b[k], want_b[k]) for k in want_b}, R.pair_e_order(g32, c, want_b))}, g32
 
 
 def native(c, src, from_distance, step):
@@ -79,16 +85,17 @@ def native(c, src, from_distance, step):
     return out
 
 
-def judge(label, E, H, K, from_distance, got, want, e32):
+def judge(label, E, H, K, from_distance, got, want, e32, e_order):
     """Every tensor within the bar; prints rel_err / bar and keeps the worst per (instantiation, tensor)."""
     nth, nte, _, _ = R.dtnn_branch(E, H, K, from_distance)
     fails = []
     for k in R.PAIR_TENSORS:
         assert got[k].shape == want[k].shape, (label, k)
-        e, bar = R.rel_err(got[k], want[k]), bar_of(e32[k])
+        e, bar = R.rel_err(got[k], want[k]), bar_of(e32[k], e_order[k])
         key = ("d" if from_distance else "g", nth, nte, k)
         WORST[key] = max(WORST.get(key, 0.0), e / bar)
-        print("%s %s<%d,%d> %s rel_err %.3g e32 %.3g ratio %.3f" % (label, key[0], nth, nte, k, e, e32[k], e / bar))
+        print("%s %s<%d,%d> %s rel_err %.3g e32 %.3g e_order %.3g ratio %.3f" % (label, key[0], nth, nte, k, e, e32[k],
+                                                                                 e_order[k], e / bar))
         if not e <= bar:
             fails.append((k, e, bar))
     assert not fails, (label, fails)
@@ -244,7 +251,7 @@ def test_leading_dimensions_alignment_and_accumulation(widths):
     prefill = [rng.choice(np.array([-1.0, -0.5, 0.25, 0.5, 1.0], np.float32), s) for s in ((K, H), (H,), (H, E))]
     ldy, lddah = E + 3, H + 5
     for form in FORMS:
-        want, e32 = refs[form]
+        want, e32, e_order = refs[form]
         results = {}
         for layout in ("off", "aligned"):
             if layout == "off":
@@ -262,7 +269,7 @@ def test_leading_dimensions_alignment_and_accumulation(widths):
             assert np.isnan(dah[:N, H:]).all() and np.isnan(dah[N]).all() and not np.isnan(dah[:N, :H]).any()
             got = {"Y": Y[:N, :E], "d_ah": dah[:N, :H]}
             got.update({k: bufs[n].astype(np.float64) - prefill[n] for n, k in enumerate(("d_W_df", "d_b_df", "d_W_fc"))})
-            judge("ld %s %s" % (layout, wid(widths)), E, H, K, form, got, want, e32)
+            judge("ld %s %s" % (layout, wid(widths)), E, H, K, form, got, want, e32, e_order)
             results[layout] = got
         assert np.array_equal(results["off"]["Y"], results["aligned"]["Y"])
     if widths == (64, 64, 128):

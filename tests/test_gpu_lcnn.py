@@ -25,6 +25,7 @@ import torch
 from deepchem_amd import ops
 from deepchem_amd.models.torch_models import LCNNBlock, LcnnBatch
 from tests import lcnn_refs as R
+from tests.yardstick import f32_threads
 
 DEV = "cuda"
 ORDERS = ("concat", "split", "split_rev")
@@ -99,7 +100,8 @@ def references(c, steps=1):
     want, tracked = restate(c, torch.float64, "concat", steps)
     errs = {n: [] for n in NAMES}
     for order in ORDERS:
-        got, _ = restate(c, torch.float32, order, steps)
+        with f32_threads(1):  # (the O = 64 case is repeatable at one thread only)
+            got, _ = restate(c, torch.float32, order, steps)
         for n in NAMES:
             errs[n].append(float(np.max(np.abs(got[n] - want[n]))))
     spread = max(max(e) / max(min(e), 1e-300) for n, e in errs.items() if max(e) > 0)

@@ -16,6 +16,7 @@ from deepchem_amd import _lib, ops
 from tests import megnet_refs as R
 from tests.test_gpu_mat import bar
 from tests.test_gpu_megnet import batch_graphs, kernel_case, run_native
+from tests.yardstick import restatement_threads
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -188,17 +189,18 @@ def ring_case(undirected):
     L = {k: torch.as_tensor(v) for k, v in c["lists"].items()}
     tei, tb = torch.as_tensor(ei), torch.as_tensor(batch)
     for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
-        res = {}
-        for which, cot in (("edge", "dHs"), ("node", "dMh")):
-            P, Q, Rr = (torch.tensor(c[n], dtype=dtype, requires_grad=True) for n in ("P", "Q", "R"))
-            if which == "edge":
-                out = R.edge_pass(P[:, :H], P[:, H:], Q, Rr, tei, tb, undirected)
-            else:
-                out = R.node_pass(P[:, :H], P[:, H:], Q, Rr, L, tb)
-            (out * torch.tensor(c[cot], dtype=dtype)).sum().backward()
-            res.update({which + "_out": out.detach().numpy(), which + "_dP": P.grad.numpy(), which + "_dQ": Q.grad.numpy(),
-                        which + "_dR": Rr.grad.numpy()})
-        c[tag] = res
+        with restatement_threads(dtype, 1):
+            res = {}
+            for which, cot in (("edge", "dHs"), ("node", "dMh")):
+                P, Q, Rr = (torch.tensor(c[n], dtype=dtype, requires_grad=True) for n in ("P", "Q", "R"))
+                if which == "edge":
+                    out = R.edge_pass(P[:, :H], P[:, H:], Q, Rr, tei, tb, undirected)
+                else:
+                    out = R.node_pass(P[:, :H], P[:, H:], Q, Rr, L, tb)
+                (out * torch.tensor(c[cot], dtype=dtype)).sum().backward()
+                res.update({which + "_out": out.detach().numpy(), which + "_dP": P.grad.numpy(), which + "_dQ": Q.grad.numpy(),
+                            which + "_dR": Rr.grad.numpy()})
+            c[tag] = res
     return c
 
 
